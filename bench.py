@@ -13,6 +13,9 @@ Launched by the driver as
     python bench.py --gpus 1 --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 Rank 0 prints one JSON line.
+A plain run sets up, warms up, times the K steps and prints the line (`--dump-outputs DIR`: the last timed step's results as .npy
+files as well). `--full` adds what takes runs or checks of its own: the parity gate and labels digest, the one-group probe, the
+column-download leg, the file-to-file leg and the CPU baseline.
 """
 import argparse
 import json
@@ -78,6 +81,36 @@ def throttle_stats():
         except Exception:
             pass
     return None
+
+
+DUMP_SAMPLE = 1 << 19      # rows kept of a longer table by --dump-outputs (a fixed seeded sample): C4's SNP and label tables stay under 40 MB
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, snap, cv):
+    """--dump-outputs: what the last timed step returned (ref_outputs.pipeline_snapshot of it), one DIR/<name>.npy per array, floats as
+    float32 and integers as float64 (exact: every value is below 2^53). The SNP table (snp_*) and the window entries (entry_ids /
+    entry_labels) are sampled by rows when longer than DUMP_SAMPLE; the rows kept are in snp_rows / entry_rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    f64 = lambda a: np.asarray(a, np.float64)
+    arrays = {"error_rate": np.array([cv["error_rate"]], np.float64), "mean_distance": np.asarray(snap["mean_distance"], np.float32),
+              "depth": np.asarray(snap["depth"], np.float32), "snp_off": f64(snap["snp_off"]), "win_off": f64(snap["win_off"]),
+              "win_start": f64(snap["win_start"]), "win_end": f64(snap["win_end"]), "entry_off": f64(snap["row_off"])}
+
+    def table(prefix, cols):
+        n = len(next(iter(cols.values())))
+        rows = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(12345).choice(n, DUMP_SAMPLE, replace=False))
+        arrays[prefix + "_rows"] = f64(rows)
+        for k, v in cols.items():
+            arrays[k] = f64(np.asarray(v)[rows])
+
+    table("snp", {k: snap[k] for k in ("snp_pos", "snp_ref", "snp_alt", "snp_n_ref", "snp_n_alt")})
+    table("entry", {"entry_ids": snap["ids"], "entry_labels": snap["lab"]})
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def run_stage_pair(cv, sr, files, td, tag, threads, env=None):
@@ -206,6 +239,10 @@ def main():
     ap.add_argument("--as-rank-of", type=int, default=0, help="readiness check without a node: run rank 0's LPT shard of an N-rank job on this one GPU with the "
                     "host threads / groups a rank of N gets (the line says so in config.emulated_rank_of; `value` is this ONE rank's rate)")
     ap.add_argument("--cores", type=int, default=0, help="pin the process to this many CPUs before anything starts (with --as-rank-of: the share of the host one rank has)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the parity gate and labels digest, the one-group probe, the "
+                    "column-download leg, the file-to-file leg with the CPU baseline (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                    "a fixed seeded sample of the long arrays; at most 64 MB in all)")
     args = ap.parse_args()
 
     rank_env, world_env = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -224,7 +261,7 @@ def main():
     # job's three input files for the file-to-file leg ----
     shards = hdist.lpt_shards([float(s[0] * s[2]) for s in shapes], world_env)
     my_ids = shards[rank_env]
-    want_f2f = world_env == 1 and args.cpu_contigs != 0      # (never for an emulated rank)
+    want_f2f = args.full and world_env == 1 and args.cpu_contigs != 0      # (never for an emulated rank)
     job_dir = tempfile.mkdtemp(prefix="hs_bench_job_") if (want_f2f and not args.no_f2f_job) else None
     t_gen = time.perf_counter()
     # HS_BENCH_SERIAL_SETUP=1: no forked workers (under `rocprofv3 --pmc` the profiler has initialised the GPU before this program
@@ -432,13 +469,16 @@ def main():
     # next call). Compared with the reference's files in the file-to-file leg below; one rank = the whole job only ----
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     snap_timed = snap_col = None
-    if rank == 0 and world == 1 and not emulated and last_results is not None:
+    if rank == 0 and last_results is not None and args.dump_outputs:
+        import ref_outputs
+        dump_outputs(args.dump_outputs, ref_outputs.pipeline_snapshot(batch, last_results[0], last_results[1], contig_names), last_results[0])
+    if args.full and rank == 0 and world == 1 and not emulated and last_results is not None:
         import ref_outputs
         snap_timed = ref_outputs.pipeline_snapshot(batch, last_results[0], last_results[1], contig_names)
     # what rank 0 holds of the WHOLE job after the last timed step, as an order-independent digest: one process and N ranks must agree on it
     labels_digest = None
     try:
-        if rank == 0 and last_results is not None:
+        if args.full and rank == 0 and last_results is not None:
             if use_dist and last_gathered is not None:
                 labels_digest = dict(hdist.sparse_digest([hdist.decode_sparse(np.asarray(o)) for o in last_gathered]), ranks=len(last_gathered))
             elif not use_dist and "sparse" in last_results[1]:
@@ -448,7 +488,7 @@ def main():
     # ... and what stage 3 leaves beside the labels: the job's SNP count, the contigs' mean distances (error_rate.txt is their mean) -- summed
     # / put together over the ranks after the clock has stopped (two tiny host-side exchanges every rank takes part in)
     try:
-        if last_results is not None and not emulated:
+        if args.full and last_results is not None and not emulated:
             import zlib
             md_full = np.zeros(n_job, np.float32); md_full[my_ids_np] = np.asarray(last_results[0]["mean_distance"], np.float32)[:len(my_ids)]
             snps = np.array([int(last_results[0].get("n_snps", 0))], np.int64)
@@ -484,7 +524,7 @@ def main():
             cv1, sr1 = pl.run(0.33, n_threads, error_rate_fn, rarest_strain_abundance=0.01, window_size=window_size)
         return cv1, sr1
 
-    if G > 1 and not use_dist and not profiled and not os.environ.get("HS_BENCH_NO_PROBE"):
+    if args.full and G > 1 and not use_dist and not profiled and not os.environ.get("HS_BENCH_NO_PROBE"):
         probe = None
         try:
             probe = batch.sibling(1)
@@ -503,7 +543,7 @@ def main():
     # After the timed region too: the same steps with .col's payload (the entries of every SNP column) brought to the host inside
     # the call -- the timed steps hand stage 3 -> 4 over on the device and return the SNPs' positions, alleles and counts only
     ms_with_col = None
-    if (not use_dist or world == 1) and not profiled and not os.environ.get("HS_BENCH_NO_PROBE"):
+    if args.full and (not use_dist or world == 1) and not profiled and not os.environ.get("HS_BENCH_NO_PROBE"):
         try:
             batch.keep_columns(True)
             for _ in range(4):      # (the pinned blocks of the entries are sized in these)
@@ -694,7 +734,8 @@ def main():
                                  "not_compared": "the SNPS lines of the .col (positions, alleles, entries): the reference gate of a --gpus 1 run with the file-to-file leg compares them",
                                  "diffs": None if same else {"got": {k: labels_digest.get(k) for k in keys}, "expected": {k: known[k] for k in keys}}}
         if "parity" not in out:
-            out["parity"] = {"checked": False, "why": "several ranks (each holds a shard; the full-job comparison runs at --gpus 1)" if (use_dist or emulated) else
+            out["parity"] = {"checked": False, "why": "a plain run: the checks run with --full" if not args.full else
+                             "several ranks (each holds a shard; the full-job comparison runs at --gpus 1)" if (use_dist or emulated) else
                              ("no file-to-file leg in this run (--cpu-contigs 0) or no reference / oracle binaries on this box" if "error" not in (out.get("cpu_baseline") or {}) else "the file-to-file leg failed")}
         print(json.dumps(out), flush=True)
         if out["parity"].get("checked") and not out["parity"].get("identical"):

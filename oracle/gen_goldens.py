@@ -584,6 +584,21 @@ def gen_edlib_long_dist_vectors():
     print("edlib long distance vectors:", {k: len(v) for k, v in out.items()})
 
 
+def gen_ref_runs():
+    """tests/golden/ref_runs: the reference's outputs on inputs that tests make themselves (randomised .gro files of test_cpu_gaf.py,
+    degenerate stage-3 inputs of test_cpu_oracle.py), so that those tests need no compiled reference"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_cpu_gaf
+    import test_cpu_oracle
+    runs = test_cpu_gaf.random_partition_ref_runs(os.path.join(REF, "HS_create_new_contigs"))
+    runs.update(test_cpu_oracle.degenerate_ref_runs(os.path.join(REF, "HS_call_variants")))
+    out = os.path.join(GOLD, "ref_runs")
+    os.makedirs(out, exist_ok=True)
+    for name, data in sorted(runs.items()):
+        with open(os.path.join(out, name + ".gz"), "wb") as f, gzip.GzipFile(fileobj=f, mode="wb", mtime=0, filename="") as g:
+            g.write(data)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check-oracle", action="store_true", help="also run oracle/_build/hs_oracle and report parity")
@@ -595,7 +610,10 @@ def main():
     ap.add_argument("--edlib-edge", action="store_true", help="only tests/golden/edlib_edge_vectors.json")
     ap.add_argument("--stage5-alphabet", action="store_true", help="only tests/golden/stage5_alphabet_cases.json")
     ap.add_argument("--c5u", action="store_true", help="only the uncut 10 Mb variant of C5: outputs into tests/golden_big/c5u (12 minutes of the reference)")
+    ap.add_argument("--ref-runs", action="store_true", help="only tests/golden/ref_runs (the reference on inputs the CPU tests make themselves)")
     args = ap.parse_args()
+    if args.ref_runs:
+        return gen_ref_runs()
     if args.c5u:
         return gen_c5u()
     if args.edlib_path:

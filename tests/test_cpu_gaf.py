@@ -1,7 +1,7 @@
 """The .gro consumer of the next stage (parse_split_file + merge_intervals + output_GAF of
 create_new_contigs.cpp) against the reference: the golden .gaf files (written by the reference's own
-HS_create_new_contigs, oracle/gen_goldens.py) and, where oracle/_ref holds that binary, the reference run live on
-randomised .gro files. Host code only: runs without a GPU."""
+HS_create_new_contigs, oracle/gen_goldens.py) and its .gaf files from randomised .gro files (stored; run live as well where
+oracle/_ref holds that binary). Host code only: runs without a GPU."""
 import os
 import random
 import subprocess
@@ -128,33 +128,63 @@ def _random_gro(td, rng, style):
     return p
 
 
-@pytest.mark.parametrize("case,style,seed", [("linked", "smooth", 1), ("linked", "rough", 2), ("multi", "rough", 3), ("penta30k", "rough", 4),
-                                             ("linked", "rough", 5), ("short_reads_w500", "smooth", 6), ("clips", "rough", 7),
-                                             ("penta30k", "sparse", 8), ("linked", "sparse", 9), ("lowdepth", "sparse", 10)])
+RANDOM_PARTITIONS = [("linked", "smooth", 1), ("linked", "rough", 2), ("multi", "rough", 3), ("penta30k", "rough", 4), ("linked", "rough", 5),
+                     ("short_reads_w500", "smooth", 6), ("clips", "rough", 7), ("penta30k", "sparse", 8), ("linked", "sparse", 9), ("lowdepth", "sparse", 10)]
+
+
+def _ref_gaf(ref_cnc, td, gro, ref):
+    """the reference's HS_create_new_contigs on `gro`: it writes the .gaf `ref`, then stops at its first external tool"""
+    tmp = os.path.join(td, "cnc_tmp")
+    os.makedirs(tmp, exist_ok=True)
+    if os.path.exists(ref):
+        os.remove(ref)
+    subprocess.run([ref_cnc, os.path.join(td, "assembly.gfa"), os.path.join(td, "reads.fasta"), "0.05", gro,
+                    os.path.join(td, "aln.sam"), tmp + "/", "1", "ont", os.path.join(tmp, "o.gfa"), ref, "racon", "0", "0",
+                    "/nonexistent/minimap2", "/nonexistent/racon", "/nonexistent/medaka", "/nonexistent/samtools",
+                    "/nonexistent/python", "0"], cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    assert os.path.exists(ref), "the reference did not write a .gaf"
+
+
+def _random_partition_run(case, style, seed, rep):
+    return "gaf_%s_%s_%d_%d.gaf" % (case, style, seed, rep)
+
+
+def random_partition_ref_runs(ref_cnc):
+    """{stored run: the .gaf the reference writes} for every randomised .gro of the test below (oracle/gen_goldens.py --ref-runs)"""
+    out = {}
+    for case, style, seed in RANDOM_PARTITIONS:
+        rng = random.Random(seed)
+        with tempfile.TemporaryDirectory() as td:
+            gu.unpack(case, td)
+            for rep in range(3):
+                ref = os.path.join(td, "ref.gaf")
+                _ref_gaf(ref_cnc, td, _random_gro(td, rng, style), ref)
+                out[_random_partition_run(case, style, seed, rep)] = _read(ref)
+    return out
+
+
+@pytest.mark.parametrize("case,style,seed", RANDOM_PARTITIONS)
 def test_gaf_against_live_reference_on_random_partitions(built, case, style, seed):
-    """Randomised windows/labels through the reference binary and through hs_gro_to_gaf: identical files. (The reference
-    stops later, at its first external tool; the .gaf is complete by then.) Skipped where oracle/_ref was not built."""
-    if not os.path.exists(built["ref_cnc"]):
-        pytest.skip("oracle/_ref/HS_create_new_contigs not built here")
+    """Randomised windows/labels through hs_gro_to_gaf: the .gaf the reference writes from the same .gro, byte for byte (stored in
+    tests/golden/ref_runs; where oracle/_ref holds HS_create_new_contigs the reference runs live as well and must still write it)."""
+    live = os.path.exists(built["ref_cnc"])
     rng = random.Random(seed)
     with tempfile.TemporaryDirectory() as td:
         gu.unpack(case, td)
         for rep in range(3):
             gro = _random_gro(td, rng, style)
-            ref, mine, tmp = os.path.join(td, "ref.gaf"), os.path.join(td, "mine.gaf"), os.path.join(td, "cnc_tmp")
-            os.makedirs(tmp, exist_ok=True)
-            for p in (ref, mine):
-                if os.path.exists(p):
-                    os.remove(p)
-            subprocess.run([built["ref_cnc"], os.path.join(td, "assembly.gfa"), os.path.join(td, "reads.fasta"), "0.05", gro,
-                            os.path.join(td, "aln.sam"), tmp + "/", "1", "ont", os.path.join(tmp, "o.gfa"), ref, "racon", "0", "0",
-                            "/nonexistent/minimap2", "/nonexistent/racon", "/nonexistent/medaka", "/nonexistent/samtools",
-                            "/nonexistent/python", "0"], cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-            assert os.path.exists(ref), "the reference did not write a .gaf"
+            expected = gu.ref_run_output(_random_partition_run(case, style, seed, rep))
+            mine = os.path.join(td, "mine.gaf")
+            if os.path.exists(mine):
+                os.remove(mine)
             r = subprocess.run([built["gaf"], os.path.join(td, "assembly.gfa"), os.path.join(td, "reads.fasta"), os.path.join(td, "aln.sam"),
                                 gro, "0", mine], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
             assert r.returncode == 0, r.stdout.decode()[-2000:]
-            assert _read(mine) == _read(ref), "rep %d" % rep
+            assert _read(mine) == expected, "rep %d" % rep
+            if live:
+                ref = os.path.join(td, "ref.gaf")
+                _ref_gaf(built["ref_cnc"], td, gro, ref)
+                assert _read(ref) == expected, "rep %d: the reference no longer writes the stored .gaf" % rep
 
 
 def test_gaf_tool_usage_and_errors(built):

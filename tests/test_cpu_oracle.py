@@ -193,25 +193,43 @@ def test_probe_calls_of_the_orchestrator(built):
     assert subprocess.run([built["sr"], "a", "b"], stdout=subprocess.DEVNULL).returncode == 1
 
 
-@pytest.mark.parametrize("which", ["empty_sam", "empty_gfa"])
-def test_degenerate_files_match_reference_binary(built, which):
-    """inputs without alignments / without contigs: the product's host glue writes what the compiled reference writes"""
-    if not os.path.exists(built["ref_cv"]):
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
+DEGENERATE = ["empty_sam", "empty_gfa"]
+
+
+def _degenerate_call_variants(cmd, td, which):
+    """stage 3 on inputs without alignments / without contigs: (.col, .vcf, error rate) as bytes"""
     from hairsplitter_amd import synth
+    f = synth.write_files([synth.make_contig(9, 0, 8000, 2, 0.01, 30, "ont")], td)
+    if which == "empty_sam":
+        open(f["sam"], "w").write("@HD\tVN:1.6\n")
+    else:
+        open(f["gfa"], "w").write("H\tVN:Z:1.0\n")
+    col, vcf, err = (os.path.join(td, "out" + x) for x in (".col", ".vcf", ".err"))
+    r = subprocess.run(cmd + [f["gfa"], f["reads"], f["sam"], "1", td, err, "0", "0", col, vcf, "0.33"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert r.returncode == 0
+    return tuple(open(p, "rb").read() for p in (col, vcf, err))
+
+
+def degenerate_ref_runs(ref_cv):
+    """{stored run: file the reference writes} for the test below (oracle/gen_goldens.py --ref-runs)"""
+    out = {}
+    for which in DEGENERATE:
+        with tempfile.TemporaryDirectory() as td:
+            for x, data in zip((".col", ".vcf", ".err"), _degenerate_call_variants([ref_cv], td, which)):
+                out["degenerate_" + which + x] = data
+    return out
+
+
+@pytest.mark.parametrize("which", DEGENERATE)
+def test_degenerate_files_match_reference_binary(built, which):
+    """inputs without alignments / without contigs: the product's host glue writes what the compiled reference writes (stored in
+    tests/golden/ref_runs; where oracle/_ref holds the reference it runs live as well and must still write the same)"""
+    expected = tuple(gu.ref_run_output("degenerate_" + which + x) for x in (".col", ".vcf", ".err"))
     with tempfile.TemporaryDirectory() as td:
-        f = synth.write_files([synth.make_contig(9, 0, 8000, 2, 0.01, 30, "ont")], td)
-        if which == "empty_sam":
-            open(f["sam"], "w").write("@HD\tVN:1.6\n")
-        else:
-            open(f["gfa"], "w").write("H\tVN:Z:1.0\n")
-        outs = {}
-        for tag, cmd in (("ref", [built["ref_cv"]]), ("hs", [built["harness"], "call_variants"])):
-            col, vcf, err = (os.path.join(td, tag + x) for x in (".col", ".vcf", ".err"))
-            r = subprocess.run(cmd + [f["gfa"], f["reads"], f["sam"], "1", td, err, "0", "0", col, vcf, "0.33"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-            assert r.returncode == 0
-            outs[tag] = tuple(open(p, "rb").read() for p in (col, vcf, err))
-        assert outs["ref"] == outs["hs"]
+        assert _degenerate_call_variants([built["harness"], "call_variants"], td, which) == expected
+    if os.path.exists(built["ref_cv"]):
+        with tempfile.TemporaryDirectory() as td:
+            assert _degenerate_call_variants([built["ref_cv"]], td, which) == expected
 
 
 def test_host_glue_deep_coverage_equals_oracle(built):

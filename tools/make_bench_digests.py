@@ -8,7 +8,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-JOBS = [("C4", 0, ["--steps", "2", "--warmup", "1", "--f2f-runs", "1"]), ("C2", 6, ["--steps", "2", "--warmup", "1", "--f2f-runs", "1"])]
+JOBS = [("C4", 0, ["--full", "--steps", "2", "--warmup", "1", "--f2f-runs", "1"]), ("C2", 6, ["--full", "--steps", "2", "--warmup", "1", "--f2f-runs", "1"])]
 out = {}
 for cfg, contigs, extra in JOBS:
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", cfg] + (["--contigs", str(contigs)] if contigs else []) + extra

@@ -6,17 +6,18 @@
 # launch time `roofline.achieved` is quoted on.
 # usage (on the GPU box, through gpurun): bash tools/pmc_traffic.sh <tag>
 tag=${1:-r02}
+repo=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 export HS_BENCH_SERIAL_SETUP=1
-cd "$GRAFT_REPO_ROOT"
+cd "$repo"
 i=0
 for g in "FETCH_SIZE" "WRITE_SIZE"; do
-  out=gpurun_out/pmc_${tag}/g$i
+  out=${OUT:-evidence_out}/pmc_${tag}/g$i
   mkdir -p $out
   timeout 900 rocprofv3 --kernel-trace --pmc $g --output-format csv -d $out -- python3 bench.py --steps 2 --warmup 0 --cpu-contigs 0 --groups ${HS_PMC_GROUPS:-1} > $out/bench.json 2> $out/err.log
   i=$((i+1))
 done
-python3 tools/pmc_summary.py gpurun_out/pmc_${tag} > gpurun_out/pmc_${tag}/summary.csv
-python3 tools/pmc_traffic_json.py gpurun_out/pmc_${tag} > gpurun_out/pmc_${tag}/traffic.json
-grep -E "k_pileup_runs|k_pileup_packed|k_column_stats_tiled|k_simdiff|k_cw_seeded_lanes|k_cw_seed_sets|k_window_tail|k_column_partition_lanes" gpurun_out/pmc_${tag}/traffic.json
-find gpurun_out/pmc_${tag} -name "*.csv" -size +5M -delete
+python3 tools/pmc_summary.py ${OUT:-evidence_out}/pmc_${tag} > ${OUT:-evidence_out}/pmc_${tag}/summary.csv
+python3 tools/pmc_traffic_json.py ${OUT:-evidence_out}/pmc_${tag} > ${OUT:-evidence_out}/pmc_${tag}/traffic.json
+grep -E "k_pileup_runs|k_pileup_packed|k_column_stats_tiled|k_simdiff|k_cw_seeded_lanes|k_cw_seed_sets|k_window_tail|k_column_partition_lanes" ${OUT:-evidence_out}/pmc_${tag}/traffic.json
+find ${OUT:-evidence_out}/pmc_${tag} -name "*.csv" -size +5M -delete
