@@ -12,8 +12,89 @@ import oracle_lib as ol
 pytestmark = pytest.mark.gpu
 
 
+def _m_only_contig(name, seq, starts, reads):
+    """a contig whose records are forward, M-only: read k starts at starts[k] and carries the bases reads[k] (which sets the
+    pileup codes, the mismatch and length counters exactly)"""
+    from hairsplitter_amd import synth
+    alns = [synth.Alignment(k, int(s), True, np.array([(len(r) << 4) | synth.OP_M], np.uint32), 0) for k, (s, r) in enumerate(zip(starts, reads))]
+    return synth.ContigData(name, np.ascontiguousarray(seq, np.uint8), [np.ascontiguousarray(r, np.uint8) for r in reads],
+                            [f"{name}_r{k}" for k in range(len(reads))], alns, np.zeros(len(reads), np.int32))
+
+
+def _md_edge_contigs():
+    """three contigs of 20 M-only reads over 19 999 aligned bases (total length 20 000 with the reference's start at 1) and 299 / 300 / 301
+    mismatches: 300 / 20000 is 0.015 in double and 0.0149999997 as the float the reference keeps (call_variants.cpp:434), so its read minimum
+    is 3 (:463-466); 301 gives 5. Every contig holds columns whose second count is 4 or 5 with no third allele: candidates only at 3."""
+    rng = np.random.default_rng(71)
+    out = []
+    for n_single in (3, 4, 5):
+        seq = rng.integers(0, 4, 1000).astype(np.uint8)
+        M = np.tile(seq, (20, 1))
+        for i in range(69):                              # 20 events of 5 reads + 49 of 4: 296 mismatches
+            p = 20 + 12 * i
+            rs = rng.choice(19, 5 if i < 20 else 4, replace=False)
+            M[rs, p] = (seq[p] + 1) & 3
+        for j in range(n_single):                        # + single-read mismatches
+            M[j, 900 + 20 * j] = (seq[900 + 20 * j] + 2) & 3
+        reads = [M[k] for k in range(19)] + [M[19, 1:]]
+        out.append(_m_only_contig(f"md{296 + n_single}", seq, [0] * 19 + [1], reads))
+    return out
+
+
+def _depth_contigs(n_reads):
+    """one contig whose deepest positions (100-399) are covered by exactly n_reads M-only reads, with allele splits such as 128 : 127
+    (and, with the 256th read, 129 : 127), three-way ties and a 254 : 1"""
+    rng = np.random.default_rng(72)
+    seq = rng.integers(0, 4, 600).astype(np.uint8)
+    M = np.tile(seq, (255, 1))
+    splits = [(128, 127), (200, 55), (254, 1), (85, 85, 85), (130, 125), (127, 64, 64), (240, 15), (128, 127), (100, 100, 55), (250, 5)]
+    for i in range(28):
+        p = 110 + 10 * i
+        cnt = splits[i % len(splits)]
+        perm = rng.permutation(255)
+        at = cnt[0]
+        for a, k in enumerate(cnt[1:]):
+            M[perm[at:at + k], p] = (seq[p] + 1 + a) & 3
+            at += k
+    starts = rng.integers(0, 101, 255)
+    ends = rng.integers(400, 601, 255)
+    reads = [M[k, starts[k]:ends[k]] for k in range(255)]
+    starts = list(starts)
+    if n_reads == 256:
+        reads.append(seq[50:450].copy()); starts.append(50)
+    return [_m_only_contig(f"depth{n_reads}", seq, starts, reads)]
+
+
+def _ties8192_contigs():
+    """columns deeper than 8191 reads with tied counts (k_column_top3_exact's packed key `count << 18` overflows there): position 4 of
+    contig t0 holds A x 8200, C x 40, G x 40, T x 20 (second count == third), position 4 of contig t1 A x 8192, C x 8192, G x 5 (first ==
+    second); the next positions carry the same split in the previous base of their codes"""
+    rng = np.random.default_rng(73)
+    out = []
+    for name, split in (("t0", (8200, 40, 40, 20)), ("t1", (8192, 8192, 5))):
+        seq = np.array([0, 1, 2, 3, 0, 1, 2, 3, 0], np.uint8)
+        n = sum(split)
+        M = np.tile(seq, (n, 1))
+        alle = np.repeat(np.arange(len(split)), split)
+        rng.shuffle(alle)
+        M[:, 4] = (seq[4] + alle) & 3
+        starts = rng.integers(0, 3, n)
+        ends = rng.integers(7, 10, n)
+        out.append(_m_only_contig(name, seq, starts, [M[k, starts[k]:ends[k]] for k in range(n)]))
+    return out
+
+
 def _contigs(kind):
     from hairsplitter_amd import synth
+    if kind == "md_edge":
+        return _md_edge_contigs()
+    if kind in ("depth255", "depth256"):
+        return _depth_contigs(int(kind[5:]))
+    if kind == "deep":
+        return [synth.make_contig(15, 0, 2_500, 2, 0.01, 600, "ont", read_len_override=(300, 2000)),
+                synth.make_contig(15, 1, 1_200, 2, 0.01, 1500, "ont", read_len_override=(200, 1000))]
+    if kind == "ties8192":
+        return _ties8192_contigs()
     if kind == "dip":
         return [synth.make_contig(11, 0, 30_000, 2, 0.01, 40, "ont")]
     if kind == "multi":
@@ -28,11 +109,42 @@ def _contigs(kind):
     raise ValueError(kind)
 
 
-@pytest.fixture(scope="module", params=["dip", "multi", "hifi", "edge"])
+def _assert_regime(kind, flat):
+    """the hand-made kinds reach the branch they are there for (from the oracle's pileup and counts)"""
+    if kind not in ("md_edge", "depth255", "depth256", "deep", "ties8192"):
+        return
+    pile, _, md = ol.pileup(flat)
+    top = [ol.column_top3(flat, pile, c) for c in range(flat.n_contigs)]
+    max_depth = max(int(t[5].max()) for t in top)
+    if kind == "md_edge":
+        assert md.tolist() == [np.float32(299 / 20000), np.float32(0.015), np.float32(301 / 20000)]
+        assert float(md[1]) < 0.015 and not md[1] < np.float32(0.015) and float(md[2]) > 0.015
+        for c, want in ((0, True), (1, True), (2, False)):
+            _, _, c0, c1, c2, _ = top[c]
+            fl = ol.call_variants_flags(flat, pile, c, float(md[c]))
+            low = (fl & 1).astype(bool) & (c1 <= 5)          # candidates that only the read minimum of 3 admits
+            assert bool(low.any()) == want and set(c1[low].tolist()) <= {4, 5}, c
+            assert want or int(((c1 == 4) | (c1 == 5)).sum()) > 40
+    elif kind in ("depth255", "depth256"):
+        assert max_depth == int(kind[5:])
+        _, _, c0, c1, _, d = top[0]
+        assert np.any((c0 == 128 + (kind == "depth256")) & (c1 == 127) & (d == max_depth))
+    elif kind == "deep":
+        assert max_depth > 1400
+        fl = ol.call_variants_flags(flat, pile, 0, float(md[0]))
+        assert int((top[0][5][(fl & 1) != 0] > 64).sum()) > 10      # candidate columns of more than 64 entries
+    elif kind == "ties8192":
+        assert max_depth >= 16_384
+        n_tied = sum(int(((t[2] >= 8192) & ((t[2] == t[3]) | ((t[3] == t[4]) & (t[3] > 0)))).sum()) for t in top)
+        assert n_tied >= 2 and any(bool(np.any((t[2] >= 8192) & (t[2] == t[3]))) for t in top)
+
+
+@pytest.fixture(scope="module", params=["dip", "multi", "hifi", "edge", "md_edge", "depth255", "depth256", "deep", "ties8192"])
 def batch(request, built):
     from hairsplitter_amd import api
     api.require_gpu()
     flat = api.FlatBatch(_contigs(request.param))
+    _assert_regime(request.param, flat)
     t = api.device_tensors(flat)
     return flat, t
 
@@ -127,10 +239,10 @@ def test_column_stats_counts(batch):
     flat, t = batch
     pile, _ = api.pileup(t, flat)
     st, sel_g, sel_d = api.column_stats(t, flat, pile, min_second=4)
-    # 8-bit counter variant (valid: no position of these batches is deeper than 255) must give the same bytes
-    st8, sel_g8, sel_d8 = api.column_stats(t, flat, pile, min_second=4, max_depth=255)
-    assert int(st["depth"].max()) <= 255
-    assert np.array_equal(st8.view(np.uint8), st.view(np.uint8)) and np.array_equal(sel_g8, sel_g) and np.array_equal(sel_d8, sel_d)
+    # 8-bit counter variant (valid where no position of the batch is deeper than 255) must give the same bytes
+    if int(st["depth"].max()) <= 255:
+        st8, sel_g8, sel_d8 = api.column_stats(t, flat, pile, min_second=4, max_depth=255)
+        assert np.array_equal(st8.view(np.uint8), st.view(np.uint8)) and np.array_equal(sel_g8, sel_g) and np.array_equal(sel_d8, sel_d)
     hp = pile.cpu().numpy()
     exp_sel = np.flatnonzero((st["cnt"][:, 1] > 4) | ((st["cnt"][:, 1] == 4) & (st["cnt"][:, 2] == 0)))
     assert np.array_equal(sel_g, exp_sel) and np.array_equal(sel_d, st["depth"][exp_sel].astype(np.int32))
@@ -172,56 +284,59 @@ def test_tile_plan_lists_every_overlap_once_in_record_order(batch):
 def taps(batch):
     """the column pass of stage 3 AS THE PIPELINE QUEUES IT over the whole batch (hs_cv_column_pass_taps: K0, K1, k_column_stats_tiled_dw,
     k_columns_compact, k_gather_tiles_direct / k_gather_tiles, k_column_top3_exact, k_candidates_scan, k_flag_block_*, k_pack_flagged, k_cand_bits),
-    with what those kernels left on the device, + the oracle's pileup of the same batch"""
+    with what those kernels left on the device, + the oracle's pileup and per-contig mean distances of the same batch"""
     from hairsplitter_amd import api
     flat, t = batch
     b = api.CvBatch(flat)
     tp = api.cv_column_pass_taps(b, 0, flat.n_contigs, 0.33)
     b.close()
-    o_pile, _, _ = ol.pileup(flat)
-    return flat, tp, o_pile
+    o_pile, _, o_md = ol.pileup(flat)
+    return flat, tp, o_pile, o_md
 
 
-def test_column_pass_selection_and_gather(taps):
-    """K2's selection (k_column_stats_tiled_dw + k_columns_compact) and K3 (k_gather_tiles_direct / k_gather_tiles): the extracted columns
-    ascend by position, hold every position that can still become a SNP (second count >= 5, or a candidate of call_variants.cpp:525-529) and
-    nothing whose second count is below 4, and every column is the reference's Column (Partition.h:8-14) of its position: the reads covering
-    it in ascending index with their pileup codes."""
-    flat, tp, hp = taps
+def _central_base_test(k0, k1):
+    """call_variants.cpp:527-528 (and loop D, :751-752) on arrays of leading codes"""
+    k0, k1 = k0.astype(np.int64), k1.astype(np.int64)
+    return (k0 % 5 != k1 % 5) & (((k1 - 33) % 5 != 4) | ((k1 // 5 % 5 != k0 % 5) & (k1 // 25 % 5 != k0 % 5)))
+
+
+def _check_selection_and_gather(flat, tp, hp, md, c_lo, c_hi):
     g = tp["col_gpos"]
     assert np.all(np.diff(g) > 0)
+    assert len(g) == 0 or (g[0] >= flat.contig_off[c_lo] and g[-1] < flat.contig_off[c_hi])
     ctg = np.searchsorted(flat.contig_off, g, side="right") - 1
     pos = g - flat.contig_off[ctg]
     assert np.array_equal(tp["col_rec"]["contig"], ctg.astype(np.int32)) and np.array_equal(tp["col_rec"]["pos"], pos.astype(np.int32))
     off, idx, code = tp["col_off"], tp["col_idx"], tp["col_code"]
     assert off[0] == 0 and off[-1] == len(idx) == len(code)
-    have = set(int(x) for x in g)
-    for c in range(flat.n_contigs):
+    for c in range(c_lo, c_hi):
         r0, r1 = int(flat.contig_rec_off[c]), int(flat.contig_rec_off[c + 1])
         g0 = int(flat.contig_off[c])
         k0, k1, c0, c1, c2, depth = ol.column_top3(flat, hp, c)
-        md = float(tp["contig_mean_distance"][c])
-        fl = ol.call_variants_flags(flat, hp, c, md)
+        fl = ol.call_variants_flags(flat, hp, c, float(md[c]))
         # (what K2 drops: positions nobody reads -- neither a candidate nor a column loop D could rescue, call_variants.cpp:751-756)
-        rescue = np.array([p for p in np.flatnonzero(c1 >= 5) if (int(k0[p]) % 5 != int(k1[p]) % 5 and ((int(k1[p]) - 33) % 5 != 4 or (int(k1[p]) // 5 % 5 != int(k0[p]) % 5 and int(k1[p]) // 25 % 5 != int(k0[p]) % 5)))], dtype=np.int64)
-        for p in list(np.flatnonzero((fl & 1).astype(bool))) + list(rescue):
-            assert g0 + int(p) in have, (c, int(p))
-        for i in np.flatnonzero(ctg == c):
-            p = int(pos[i])
-            assert c1[p] >= 4
-            rs = np.arange(r0, r1)
-            cover = rs[(flat.rec_pos[r0:r1] <= p) & (p < flat.rec_qend[r0:r1])]
-            assert idx[off[i]:off[i + 1]].tolist() == (cover - r0).tolist()
-            assert code[off[i]:off[i + 1]].tolist() == [int(hp[flat.pile_off[r] + p - flat.rec_pos[r]]) for r in cover]
+        need = np.flatnonzero(((fl & 1) != 0) | ((c1 >= 5) & _central_base_test(k0, k1)))
+        assert np.all(np.isin(g0 + need, g)), c
+        sel = np.flatnonzero(ctg == c)
+        if len(sel) == 0:
+            continue
+        assert np.all(np.diff(sel) == 1)
+        P = pos[sel]
+        assert np.all(c1[P] >= 4)
+        rp, rq = flat.rec_pos[r0:r1].astype(np.int64), flat.rec_qend[r0:r1].astype(np.int64)
+        for s in range(0, len(sel), 1024):      # every column is the reads covering it in ascending index, with their pileup codes
+            Pb, kb = P[s:s + 1024], sel[s:s + 1024]
+            ci, ri = np.nonzero((rp[None, :] <= Pb[:, None]) & (Pb[:, None] < rq[None, :]))
+            assert np.array_equal(np.diff(off[kb[0]:kb[-1] + 2]), np.bincount(ci, minlength=len(kb)))
+            e0, e1 = int(off[kb[0]]), int(off[kb[-1] + 1])
+            assert np.array_equal(idx[e0:e1], ri.astype(np.int32))
+            assert np.array_equal(code[e0:e1], hp[flat.pile_off[r0 + ri] + Pb[ci] - rp[ri]])
 
 
-def test_column_pass_leading_codes(taps):
-    """K2's second pass + k_column_top3_exact: the two leading codes and their counts of EVERY extracted column are the reference's
-    (call_variants.cpp:477-507), equal counts in the order of its hash map and its std::sort included"""
-    flat, tp, hp = taps
+def _check_leading_codes(flat, tp, hp, c_lo, c_hi):
     rec = tp["col_rec"]
     n = 0
-    for c in range(flat.n_contigs):
+    for c in range(c_lo, c_hi):
         k0, k1, c0, c1, c2, _ = ol.column_top3(flat, hp, c)
         sel = np.flatnonzero(rec["contig"] == c)
         p = rec["pos"][sel]
@@ -232,62 +347,89 @@ def test_column_pass_leading_codes(taps):
     assert n == len(rec)
 
 
-def test_column_pass_candidates(taps):
-    """k_candidates_scan: the candidate SNPs (predicate + greedy spacing of call_variants.cpp:525-529, column-parallel on the device) and the
-    automatic ones (:531) of every contig, with the contig's own mean distance deciding the read minimum (:463-466); k_flag_block_* +
-    k_pack_flagged: the packed candidates are those columns, in order, records intact"""
-    from hairsplitter_amd import api  # noqa: F401
-    flat, tp, hp = taps
+def _check_candidates(flat, tp, hp, md, c_lo, c_hi, thr=0.33):
     rec = tp["col_rec"]
     HS_COL_CAND, HS_COL_AUTO = 1, 2
+    assert np.array_equal(tp["contig_mean_distance"].view(np.uint32), md[c_lo:c_hi].view(np.uint32))      # generate_msa's value, bit for bit
     n_cand = 0
-    for c in range(flat.n_contigs):
-        fl = ol.call_variants_flags(flat, hp, c, float(tp["contig_mean_distance"][c]))
+    for c in range(c_lo, c_hi):
+        fl = ol.call_variants_flags(flat, hp, c, float(md[c]), automatic_snp_threshold=thr)
         sel = np.flatnonzero(rec["contig"] == c)
         p = rec["pos"][sel]
         got_c = (rec["flags"][sel] & HS_COL_CAND) != 0
         got_a = (rec["flags"][sel] & HS_COL_AUTO) != 0
-        assert np.array_equal(got_c, (fl[p] & 1) != 0)
-        assert np.array_equal(got_a, (fl[p] & 2) != 0)
-        assert int(tp["contig_n_cand"][c]) == int((fl & 1).sum()) == int(got_c.sum())      # (no candidate outside the extracted columns)
+        assert np.array_equal(got_c, (fl[p] & 1) != 0), c
+        assert np.array_equal(got_a, (fl[p] & 2) != 0), c
+        assert int(tp["contig_n_cand"][c - c_lo]) == int((fl & 1).sum()) == int(got_c.sum())      # (no candidate outside the extracted columns)
         n_cand += int(got_c.sum())
     cand_cols = np.flatnonzero((rec["flags"] & HS_COL_CAND) != 0)
     assert len(tp["cand_rec"]) == n_cand and np.array_equal(tp["cand_col"], cand_cols.astype(np.int32))
     assert np.array_equal(tp["cand_rec"].view(np.uint8), rec[cand_cols].view(np.uint8))
 
 
-def test_column_pass_candidate_bit_sets(taps):
-    """k_cand_bits: every candidate column as loop A reads it (hs::CandBits) -- one bit set per distinct code in the order the column's
-    entries bring them, bit k = the read of rank k by (start position, index) on its contig -- holds exactly the column's (read, code) pairs"""
-    flat, tp, hp = taps
+def _check_candidate_bit_sets(flat, tp):
     off, idx, code = tp["col_off"], tp["col_idx"], tp["col_code"]
     bits, words = tp["cand_bits"], tp["cand_words"]
     rank_of = {}
-    for c in range(flat.n_contigs):
-        r0, r1 = int(flat.contig_rec_off[c]), int(flat.contig_rec_off[c + 1])
-        order = np.lexsort((np.arange(r1 - r0), flat.rec_pos[r0:r1]))
-        rk = np.zeros(r1 - r0, np.int64); rk[order] = np.arange(r1 - r0)
-        rank_of[c] = rk
     ref_span_end = flat.rec_pos + np.asarray(flat.rec_refspan)
     for k, col in enumerate(tp["cand_col"]):
         h = bits[k]
         c = int(tp["cand_rec"]["contig"][k])
-        r0 = int(flat.contig_rec_off[c])
+        r0, r1 = int(flat.contig_rec_off[c]), int(flat.contig_rec_off[c + 1])
+        if c not in rank_of:
+            order = np.lexsort((np.arange(r1 - r0), flat.rec_pos[r0:r1]))
+            rk = np.zeros(r1 - r0, np.int64); rk[order] = np.arange(r1 - r0)
+            rank_of[c] = rk
         ci, cc = idx[off[col]:off[col + 1]], code[off[col]:off[col + 1]]
         assert int(h["n_entries"]) == len(ci) and int(h["idx_min"]) == int(ci[0]) and int(h["idx_max"]) == int(ci[-1])
         rk = rank_of[c][ci]
         assert int(h["wlo"]) == int(rk.min() >> 6) and int(h["n_words"]) == int(rk.max() >> 6) - int(rk.min() >> 6) + 1
         assert int(h["reach"]) == int(ref_span_end[r0 + ci].max())
-        slots = list(dict.fromkeys(int(x) for x in cc))
+        u, first = np.unique(cc, return_index=True)
+        slots = u[np.argsort(first)]                     # the distinct codes in the order the entries bring them
         assert int(h["n_slots"]) == len(slots)
+        slot_of = np.zeros(256, np.int64); slot_of[slots] = np.arange(len(slots))
         W, o = int(h["n_words"]), int(h["word_off"])
         blk = words[o:o + W * (len(slots) + 1) + (len(slots) + 7) // 8]
         exp = np.zeros((len(slots) + 1, W), np.uint64)
-        for r, x in zip(rk, cc):
-            w, b = int(r >> 6) - int(h["wlo"]), np.uint64(1) << np.uint64(int(r) & 63)
-            exp[0, w] |= b; exp[1 + slots.index(int(x)), w] |= b
+        w, b = rk >> 6, np.left_shift(np.uint64(1), (rk & 63).astype(np.uint64))
+        w = w - int(h["wlo"])
+        np.bitwise_or.at(exp[0], w, b)
+        np.bitwise_or.at(exp, (1 + slot_of[cc], w), b)
         assert np.array_equal(blk[:W * (len(slots) + 1)].reshape(len(slots) + 1, W), exp)
-        assert blk[W * (len(slots) + 1):].view(np.uint8)[:len(slots)].tolist() == slots
+        assert blk[W * (len(slots) + 1):].view(np.uint8)[:len(slots)].tolist() == slots.tolist()
+
+
+def test_column_pass_selection_and_gather(taps):
+    """K2's selection (k_column_stats_tiled_dw + k_columns_compact) and K3 (k_gather_tiles_direct / k_gather_tiles): the extracted columns
+    ascend by position, hold every position that can still become a SNP (second count >= 5, or a candidate of call_variants.cpp:525-529) and
+    nothing whose second count is below 4, and every column is the reference's Column (Partition.h:8-14) of its position: the reads covering
+    it in ascending index with their pileup codes."""
+    flat, tp, hp, md = taps
+    _check_selection_and_gather(flat, tp, hp, md, 0, flat.n_contigs)
+
+
+def test_column_pass_leading_codes(taps):
+    """K2's second pass + k_column_top3_exact: the two leading codes and their counts of EVERY extracted column are the reference's
+    (call_variants.cpp:477-507), equal counts in the order of its hash map and its std::sort included"""
+    flat, tp, hp, _ = taps
+    _check_leading_codes(flat, tp, hp, 0, flat.n_contigs)
+
+
+def test_column_pass_candidates(taps):
+    """k_contig_error: every contig's mean distance is generate_msa's return value (call_variants.cpp:434), bit for bit; k_candidates_scan: the
+    candidate SNPs (predicate + greedy spacing of call_variants.cpp:525-529, column-parallel on the device) and the automatic ones (:531) of
+    every contig, with that mean distance deciding the read minimum (:463-466); k_flag_block_* + k_pack_flagged: the packed candidates are
+    those columns, in order, records intact"""
+    flat, tp, hp, md = taps
+    _check_candidates(flat, tp, hp, md, 0, flat.n_contigs)
+
+
+def test_column_pass_candidate_bit_sets(taps):
+    """k_cand_bits: every candidate column as loop A reads it (hs::CandBits) -- one bit set per distinct code in the order the column's
+    entries bring them, bit k = the read of rank k by (start position, index) on its contig -- holds exactly the column's (read, code) pairs"""
+    flat, tp, _, _ = taps
+    _check_candidate_bit_sets(flat, tp)
 
 
 @pytest.mark.parametrize("n", [0, 1, 63, 4095, 4096, 4097, 70_001, 1_000_000, 4_300_000])
@@ -399,16 +541,26 @@ def _partition_test_case(rng, n_contigs, cols_per_contig, mode):
                 part_state_off=np.array(pso, np.int64), part_state=cat(states, np.int8)), nreads
 
 
-@pytest.mark.parametrize("mode", ["snp", "ties", "high", "many", "snp_third_count", "ties_third_count"])
+@pytest.mark.parametrize("mode", ["snp", "ties", "high", "many", "snp_third_count", "ties_third_count", "tables", "tables_third_count"])
 def test_column_partition_test_matches_oracle(built, mode):
     """K4 (k_column_partition_lanes -> _grouped -> _test) == loops C and D of keep_only_robust_variants. The `_third_count` modes hand the
     kernels what the pipeline does: the column's third count in bits 16-21 of the second count's word (63 - min(c2, 63); 0 = not known),
-    which lets the first kernel settle a pair whose second allele is provably the column's own second code."""
+    which lets the first kernel settle a pair whose second allele is provably the column's own second code. The `tables` modes: prescribed
+    2x2 tables at and around chi-square 15 and 20 (chi_tables.table_case), where the kernels hand the fast form over to the reference's
+    float / double sequence and the rounding alone decides the verdict, laid out for each of the three kernels."""
     from hairsplitter_amd import api
+    import chi_tables as ct
     base = mode.replace("_third_count", "")
-    rng = np.random.default_rng({"snp": 11, "ties": 12, "high": 13, "many": 14}[base])
-    case, nreads = _partition_test_case(rng, 24 if base != "many" else 10, 60 if base != "many" else 40, base)
-    want, _, _ = ol.column_partition_test(n_reads_of_contig=nreads, **case)
+    if base == "tables":
+        case, nreads, _, _ = ct.table_case()
+    else:
+        rng = np.random.default_rng({"snp": 11, "ties": 12, "high": 13, "many": 14}[base])
+        case, nreads = _partition_test_case(rng, 24 if base != "many" else 10, 60 if base != "many" else 40, base)
+    want, chi, _ = ol.column_partition_test(n_reads_of_contig=nreads, **case)
+    if base == "tables":      # the regime: many tables in each window, both verdicts in each
+        for thr in (15, 20):
+            w = np.abs(chi - thr) < 0.06
+            assert int(w.sum()) >= 50 and 0 < int(want[w].sum()) < int(w.sum()), thr
     if mode.endswith("_third_count"):
         c1w = case["col_c1"].copy()
         for k in range(len(c1w)):
@@ -427,7 +579,7 @@ def test_column_partition_test_matches_oracle(built, mode):
     assert 0 < cnt["to_grouped"] < len(want)
     if base == "ties":
         assert cnt["pairs_to_exact"] > 0
-    if base in ("high", "many"):
+    if base in ("high", "many", "tables"):
         assert cnt["whole_columns_to_exact"] > 0
     if mode == "snp_third_count":
         assert cnt["to_grouped"] < 0.5 * len(want)      # (with the third count known the first kernel settles most columns on its own)
