@@ -24,7 +24,7 @@ SYMBOLS = [
     "hs_event_elapsed_ms", "hs_pileup", "hs_pileup_plan", "hs_free_host", "hs_tile_plan", "hs_column_stats_tiled", "hs_cv_column_pass_taps", "hs_cv_taps_destroy", "hs_sr_run_taps", "hs_sr_taps_destroy", "hs_exclusive_scan_i32", "hs_gaf_from_files", "hs_gaf_from_labels", "hs_gro_to_gaf_main", "hs_column_partition_test", "hs_column_partition_last_counts", "hs_partition_pair_distance", "hs_snp_planes", "hs_simdiff", "hs_read_graphs",
     "hs_edit_distance", "hs_cv_batch_create", "hs_cv_batch_destroy", "hs_cv_batch_aligned_bp", "hs_cv_run",
     "hs_cv_result_destroy", "hs_cv_select", "hs_cv_run_range", "hs_cv_selection_destroy", "hs_sr_run", "hs_sr_run_cv", "hs_sr_run_cv_range", "hs_pipeline_create", "hs_pipeline_select", "hs_pipeline_run", "hs_pipeline_destroy", "hs_pipeline_thread_devices", "hs_cv_batch_device", "hs_sr_result_destroy", "hs_sr_window_size", "hs_call_variants_main", "hs_call_variants_epilogue",
-    "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_reattach_ends", "hs_trim_polished", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
+    "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_edlib_align", "hs_alignment_to_cigar", "hs_reattach_ends", "hs_trim_polished", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
 ]
 
 HS_NKERNELS = 28
@@ -996,6 +996,83 @@ def edlib_hw_align(pairs, path=True):
     for i in range(n):
         out.append({"distance": int(dd[i]), "start": int(ds[i]), "end": int(de[i]),
                     "ops": ops[oo[i]:oo[i] + dl[i]].copy() if path and dl[i] >= 0 else None})
+    return out
+
+
+EDLIB_MODES = {"NW": 0, "SHW": 1, "HW": 2}
+EDLIB_TASKS = {"distance": 0, "loc": 1, "path": 2}
+
+
+def _edlib_codes(pairs):
+    """(query, target) -> code arrays 0..3. Strings / bytes: one bijection per pair from its bytes to the codes, in order of first
+    appearance (hs_stage5.cpp encode_pair): edlib compares bytes, so this keeps its results exactly. Arrays are codes already."""
+    qs, ts = [], []
+    for i, (q, t) in enumerate(pairs):
+        if isinstance(q, (str, bytes)) and isinstance(t, (str, bytes)):
+            qb = np.frombuffer(q.encode() if isinstance(q, str) else q, dtype=np.uint8)
+            tb = np.frombuffer(t.encode() if isinstance(t, str) else t, dtype=np.uint8)
+            seen = np.unique(np.concatenate((qb, tb)), return_index=True)
+            if len(seen[0]) > 4:
+                raise HsError(f"edlib_align: pair {i} has {len(seen[0])} distinct bytes; the kernel has four codes")
+            code = np.zeros(256, np.uint8)
+            code[seen[0][np.argsort(seen[1])]] = np.arange(len(seen[0]), dtype=np.uint8)
+            qs.append(code[qb]); ts.append(code[tb])
+        elif isinstance(q, (str, bytes)) or isinstance(t, (str, bytes)):
+            raise HsError(f"edlib_align: pair {i} mixes a string with a code array")
+        else:
+            qa, ta = np.asarray(q), np.asarray(t)
+            if (qa.size and (qa.min() < 0 or qa.max() > 3)) or (ta.size and (ta.min() < 0 or ta.max() > 3)):
+                raise HsError(f"edlib_align: pair {i}: code arrays hold codes 0..3")
+            qs.append(qa.astype(np.uint8).reshape(-1)); ts.append(ta.astype(np.uint8).reshape(-1))
+    return qs, ts
+
+
+def alignment_to_cigar(ops, fmt="extended"):
+    """edlibAlignmentToCigar on host (hs_alignment_to_cigar): fmt "standard" (M I D) or "extended" (= X I D)."""
+    lib = load()
+    f = {"standard": 0, "extended": 1}[fmt]
+    a = _np(ops if ops is not None else [], np.uint8)
+    out = C.c_char_p()
+    lib.hs_alignment_to_cigar.argtypes = [C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.POINTER(C.c_char_p)]
+    _check(lib.hs_alignment_to_cigar(_hp(a, C.c_uint8), C.c_int32(len(a)), C.c_int32(f), C.byref(out)))
+    s = C.cast(out, C.c_char_p).value.decode()
+    lib.hs_free_host(C.cast(out, C.c_void_p))
+    return s
+
+
+def edlib_align(pairs, mode="NW", task="path", k=-1, cigar=None):
+    """edlibAlign(query, target, edlibNewAlignConfig(k, mode, task, NULL, 0)) for every (query, target) pair, on the device
+    (hs_edlib_align). mode NW | SHW | HW; task "distance" | "loc" | "path"; k = -1: no bound. Pairs: strings / bytes (at most four
+    distinct bytes per pair) or arrays of codes 0..3. -> one dict per pair: {distance (-1 beyond k), start, end (-1 when none),
+    n_locations, ops (numpy uint8 of edlib move codes; None unless task "path"), cigar (None unless cigar = "standard" |
+    "extended")}."""
+    import torch
+    require_gpu()
+    dev = "cuda:0"
+    m, tk = EDLIB_MODES[mode], EDLIB_TASKS[task]
+    if cigar is not None and tk != 2:
+        raise HsError("edlib_align: a CIGAR needs task 'path'")
+    qs, ts = _edlib_codes(pairs)
+    n = len(pairs)
+    qo = np.zeros(n + 1, np.int64); to = np.zeros(n + 1, np.int64); oo = np.zeros(n + 1, np.int64)
+    np.cumsum([len(x) for x in qs], out=qo[1:]); np.cumsum([len(x) for x in ts], out=to[1:])
+    np.cumsum([len(a) + len(b) for a, b in zip(qs, ts)], out=oo[1:])
+    cat = lambda xs: np.concatenate(xs) if xs and sum(len(x) for x in xs) else np.zeros(1, np.uint8)
+    dq = torch.from_numpy(cat(qs)).to(dev); dt = torch.from_numpy(cat(ts)).to(dev)
+    dd = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    ds, de, dn, dl = (torch.zeros_like(dd) for _ in range(4))
+    dops = torch.zeros(max(int(oo[-1]), 1), dtype=torch.uint8, device=dev) if tk == 2 else None
+    _check(load().hs_edlib_align(_p(dq), _hp(qo, C.c_int64), _p(dt), _hp(to, C.c_int64), C.c_int32(n), C.c_int32(m), C.c_int32(tk),
+                                 C.c_int32(int(k)), _p(dd), _p(ds), _p(de), _p(dn), _p(dops), _hp(oo, C.c_int64) if tk == 2 else None,
+                                 _p(dl) if tk == 2 else C.c_void_p(0), C.c_void_p(0)))
+    torch.cuda.synchronize()
+    dd, ds, de, dn, dl = (x.cpu().numpy() for x in (dd, ds, de, dn, dl))
+    ops = dops.cpu().numpy() if tk == 2 else None
+    out = []
+    for i in range(n):
+        o = ops[oo[i]:oo[i] + dl[i]].copy() if tk == 2 and dl[i] >= 0 else None
+        out.append({"distance": int(dd[i]), "start": int(ds[i]), "end": int(de[i]), "n_locations": int(dn[i]), "ops": o,
+                    "cigar": alignment_to_cigar(o, cigar) if cigar is not None and o is not None else None})
     return out
 
 

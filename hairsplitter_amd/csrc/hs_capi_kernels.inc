@@ -593,14 +593,40 @@ int hs_edit_distance(const uint8_t* d_query, const int64_t* d_query_off, const u
     return HS_OK;
 }
 
-// A1 as the stage-5 call sites use edlib: HW mode, k = -1, TASK_PATH (see hs_kernels_myers.hip). Host offsets; the device
-// buffers of the sequences and results are the caller's. d_ops may be NULL (locations only: edlib's TASK_LOC).
-int hs_edlib_hw_align(const uint8_t* d_query, const int64_t* h_query_off, const uint8_t* d_target, const int64_t* h_target_off, int32_t n_pairs,
-                      int32_t* d_dist, int32_t* d_start, int32_t* d_end, uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream) {
+// One class of pairs (0: 8 lanes, 1: 16, 2: 32, 3: a wavefront) through the path kernel of one edlib mode.
+extern "C++" {
+struct MyersPathArgs {
+    const uint8_t* query; const int64_t* qo; const uint8_t* target; const int64_t* to; int8_t* hs; const int64_t* ho;
+    unsigned long long* st; const int64_t* so; int32_t* cols; int k, task;
+    int32_t *dist, *start, *end, *nloc; uint8_t* ops; const int64_t* oo; int32_t* ops_len;
+};
+template <int MODE>
+static void myers_path_launch(const MyersPathArgs& a, int cls, const int32_t* ids, int n, hipStream_t s) {
+#define HS_MYERS_GROUPED(G)                                                                                                                               \
+    hipLaunchKernelGGL((hsdev::k_myers_hw_path_grouped<G, MODE>), dim3((unsigned)((n + 64 / G - 1) / (64 / G))), dim3(64), 0, s, a.query, a.qo, a.target, \
+                       a.to, ids, n, a.st, a.so, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len)
+    if (cls == 0) HS_MYERS_GROUPED(8);
+    else if (cls == 1) HS_MYERS_GROUPED(16);
+    else if (cls == 2) HS_MYERS_GROUPED(32);
+    else
+        hipLaunchKernelGGL(hsdev::k_myers_hw_path<MODE>, dim3((unsigned)n), dim3(64), 0, s, a.query, a.qo, a.target, a.to, ids, n, a.hs, a.ho, a.st, a.so,
+                           a.cols, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len);
+#undef HS_MYERS_GROUPED
+}
+}  // extern "C++"
+
+// A1 as edlibAlign(query, target, edlibNewAlignConfig(k, mode, task, NULL, 0)) (see hs_kernels_myers.hip): mode 0 NW, 1 SHW, 2 HW;
+// task 0 distance, 1 locations, 2 path (d_ops required). Host offsets; the device buffers of the sequences and results are the
+// caller's. d_nloc may be NULL.
+static int edlib_align_launch(const char* who, const uint8_t* d_query, const int64_t* h_query_off, const uint8_t* d_target, const int64_t* h_target_off,
+                              int32_t n_pairs, int32_t mode, int32_t task, int32_t k, int32_t* d_dist, int32_t* d_start, int32_t* d_end, int32_t* d_nloc,
+                              uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream) {
     if (int rc = require_device()) return rc;
     if (n_pairs <= 0) return HS_OK;
-    if (!h_query_off || !h_target_off || !d_dist || !d_start || !d_end || (d_ops && (!h_ops_off || !d_ops_len))) { set_error("hs_edlib_hw_align: bad arguments"); return HS_EINVAL; }
-    const bool path = d_ops != nullptr;
+    if (mode < 0 || mode > 2 || task < 0 || task > 2) { set_error(std::string(who) + ": mode must be 0 (NW), 1 (SHW) or 2 (HW), task 0 (distance), 1 (locations) or 2 (path)"); return HS_EINVAL; }
+    if (!h_query_off || !h_target_off || !d_dist || !d_start || !d_end || (task == 2 && (!d_ops || !h_ops_off || !d_ops_len))) { set_error(std::string(who) + ": bad arguments"); return HS_EINVAL; }
+    const bool path = task == 2;
+    if (k < 0) k = -1;
     std::vector<int64_t> hs_off((size_t)n_pairs + 1, 0), st_off((size_t)n_pairs + 1, 0), qo(h_query_off, h_query_off + n_pairs + 1), to(h_target_off, h_target_off + n_pairs + 1),
         oo;
     // short queries whose matrix edlib keeps whole share a wavefront: 8 / 16 / 32 lanes per pair (k_myers_hw_path_grouped); the
@@ -616,7 +642,7 @@ int hs_edlib_hw_align(const uint8_t* d_query, const int64_t* h_query_off, const 
         cls[c].push_back(i);
         need_hs[(size_t)i] = c == 3 ? ((tn + 64 + 3) & ~(int64_t)3) + 4 * (tn + 64) : 0;      // deltas (bytes) and bottoms (ints) between two passes
         need_st[(size_t)i] = path ? std::min<int64_t>(tn * nb, MY_LEAF_CELLS) * 3 : 0;      // one leaf matrix (edlib's 1-MB rule), in 8-byte words
-        if (path && h_ops_off[i + 1] - h_ops_off[i] < qn + tn) { set_error("hs_edlib_hw_align: an alignment needs room for query + target operations"); return HS_EINVAL; }
+        if (path && h_ops_off[i + 1] - h_ops_off[i] < qn + tn) { set_error(std::string(who) + ": an alignment needs room for query + target operations"); return HS_EINVAL; }
     }
     if (path) oo.assign(h_ops_off, h_ops_off + n_pairs + 1);
     // The pairs go out class by class, in chunks whose scratch (a leaf matrix per pair: up to 1.26 MB) stays within a budget: the
@@ -651,23 +677,50 @@ int hs_edlib_hw_align(const uint8_t* d_query, const int64_t* h_query_off, const 
     if (int rc = d_st.alloc(std::max<size_t>((size_t)max_st, 1) * 8)) return rc;
     if (int rc = d_cols.alloc(std::max<size_t>(path && !cls[3].empty() ? (size_t)(qo.back() - qo.front()) * 2 : 0, 1) * sizeof(int32_t))) return rc;      // Hirschberg's two columns
     const int32_t* idp = d_ids.as<int32_t>();
-    const int64_t* oop = path ? d_oo.as<int64_t>() : nullptr;
+    const MyersPathArgs args{d_query, d_qo.as<int64_t>(), d_target, d_to.as<int64_t>(), d_hs.as<int8_t>(), d_ho.as<int64_t>(), d_st.as<unsigned long long>(),
+                             d_so.as<int64_t>(), d_cols.as<int32_t>(), k, task, d_dist, d_start, d_end, d_nloc, path ? d_ops : nullptr,
+                             path ? d_oo.as<int64_t>() : nullptr, d_ops_len};
     for (const Slice& sl : slices) {
         const int n = (int)(sl.end - sl.begin);
-#define HS_MYERS_GROUPED(G)                                                                                                                               \
-        hipLaunchKernelGGL(hsdev::k_myers_hw_path_grouped<G>, dim3((unsigned)((n + 64 / G - 1) / (64 / G))), dim3(64), 0, (hipStream_t)stream, d_query,        \
-                           d_qo.as<int64_t>(), d_target, d_to.as<int64_t>(), idp + sl.begin, n, d_st.as<unsigned long long>(), d_so.as<int64_t>(),        \
-                           path ? 1 : 0, d_dist, d_start, d_end, d_ops, oop, d_ops_len)
-        if (sl.cls == 0) HS_MYERS_GROUPED(8);
-        else if (sl.cls == 1) HS_MYERS_GROUPED(16);
-        else if (sl.cls == 2) HS_MYERS_GROUPED(32);
-        else
-            hipLaunchKernelGGL(hsdev::k_myers_hw_path, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, d_query, d_qo.as<int64_t>(), d_target, d_to.as<int64_t>(),
-                               idp + sl.begin, n, d_hs.as<int8_t>(), d_ho.as<int64_t>(), d_st.as<unsigned long long>(), d_so.as<int64_t>(), d_cols.as<int32_t>(),
-                               path ? 1 : 0, d_dist, d_start, d_end, d_ops, oop, d_ops_len);
-#undef HS_MYERS_GROUPED
+        if (mode == 0) myers_path_launch<0>(args, sl.cls, idp + sl.begin, n, (hipStream_t)stream);
+        else if (mode == 1) myers_path_launch<1>(args, sl.cls, idp + sl.begin, n, (hipStream_t)stream);
+        else myers_path_launch<2>(args, sl.cls, idp + sl.begin, n, (hipStream_t)stream);
     }
     HS_HIP(hipGetLastError());
     return stream_wait((hipStream_t)stream);   // the scratch goes back to the pool with this scope
+}
+
+// A1 as the stage-5 call sites use edlib: HW mode, k = -1, TASK_PATH. d_ops may be NULL (locations only: edlib's TASK_LOC).
+int hs_edlib_hw_align(const uint8_t* d_query, const int64_t* h_query_off, const uint8_t* d_target, const int64_t* h_target_off, int32_t n_pairs,
+                      int32_t* d_dist, int32_t* d_start, int32_t* d_end, uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream) {
+    return edlib_align_launch("hs_edlib_hw_align", d_query, h_query_off, d_target, h_target_off, n_pairs, 2, d_ops ? 2 : 1, -1, d_dist, d_start, d_end, nullptr,
+                              d_ops, h_ops_off, d_ops_len, stream);
+}
+
+int hs_edlib_align(const uint8_t* d_query, const int64_t* h_query_off, const uint8_t* d_target, const int64_t* h_target_off, int32_t n_pairs, int32_t mode,
+                   int32_t task, int32_t k, int32_t* d_dist, int32_t* d_start, int32_t* d_end, int32_t* d_nloc, uint8_t* d_ops, const int64_t* h_ops_off,
+                   int32_t* d_ops_len, void* stream) {
+    return edlib_align_launch("hs_edlib_align", d_query, h_query_off, d_target, h_target_off, n_pairs, mode, task, k, d_dist, d_start, d_end, d_nloc, d_ops,
+                              h_ops_off, d_ops_len, stream);
+}
+
+// edlibAlignmentToCigar (edlib.cpp:299-349): runs of equal move characters, count then character; STANDARD writes '=' and 'X' as 'M'.
+int hs_alignment_to_cigar(const uint8_t* ops, int32_t n_ops, int32_t format, char** out) {
+    if (!out || n_ops < 0 || (n_ops > 0 && !ops) || format < 0 || format > 1) { set_error("hs_alignment_to_cigar: bad arguments"); return HS_EINVAL; }
+    const char* sym = format == 0 ? "MIDM" : "=IDX";
+    std::string s;
+    for (int32_t i = 0; i < n_ops;) {
+        if (ops[i] > 3) { set_error("hs_alignment_to_cigar: move code above 3 at " + std::to_string(i)); return HS_EINVAL; }
+        int32_t j = i + 1;
+        while (j < n_ops && ops[j] <= 3 && sym[ops[j]] == sym[ops[i]]) ++j;
+        s += std::to_string(j - i);
+        s += sym[ops[i]];
+        i = j;
+    }
+    char* p = static_cast<char*>(std::malloc(s.size() + 1));
+    if (!p) { set_error("hs_alignment_to_cigar: out of host memory"); return HS_EINVAL; }
+    std::memcpy(p, s.c_str(), s.size() + 1);
+    *out = p;
+    return HS_OK;
 }
 

@@ -21,8 +21,12 @@
 //      computation that is exact on the cells of alignments within the bound gives the same decisions: whole columns
 //      (oracle/edlib_path_oracle.py, numpy, pinned against the reference's edlib up to 60 kb) or the static band of the sweeps
 //      here (MyersBand below).
-// Kernels: k_myers_hw_path (a wavefront per pair, any length), k_myers_hw_path_grouped<8|16|32> (short queries, 64 / G pairs per
-// wavefront), k_myers_distance / k_myers_distance_grouped<G> (hs_edit_distance: NW / SHW / HW distance + first end location).
+// Kernels: k_myers_hw_path<MODE> (a wavefront per pair, any length), k_myers_hw_path_grouped<8|16|32, MODE> (short queries, 64 / G
+// pairs per wavefront), k_myers_distance / k_myers_distance_grouped<G> (hs_edit_distance: NW / SHW / HW distance + first end location).
+// The path kernels take edlib's three modes (hs_edlib_align; HW is what stage 5 calls): NW and SHW skip step 2 (start location 0)
+// and run step 3 on target[0 .. end] -- the whole target for NW. With a bound k >= 0, step 1 is one sweep in the band of k and an
+// optimum above k is reported as edlib reports it (distance -1, no location, no path); steps 2 and 3 are bounded by the distance
+// found, as edlib bounds them, so a pair within k gets the same locations and path as with k = -1.
 // Alignment ops as edlib's: 0 match, 1 insertion (query base without target base), 2 deletion, 3 mismatch.
 // Sequences are 2-bit base codes (A C G T), as everywhere on this path. Included by hs_capi.hip after hs_kernels.hip.
 #pragma once
@@ -96,10 +100,11 @@ struct MyersBand {
 // that enters the band starts from them).
 // store != nullptr: P, M, bottom score of every (column, block) of the band at store[(col * nblocks + blk) * 3 ...] as three
 // 64-bit words {P, M, score}. col_scores != nullptr: the scores of the LAST column, one int per query row (what Hirschberg's
-// split reads), MY_INF outside the band.
+// split reads), MY_INF outside the band. out_count != nullptr: how many columns attain the best score, the position before the
+// target included where it takes part (edlib's numLocations, :660-695).
 static __device__ void myers_sweep(const MyersSeq& q, const MyersSeq& t, int mode, MyersBand band, int8_t* __restrict__ hb, int32_t* __restrict__ hbot,
                                    uint8_t* tbuf /* LDS [MY_TCHUNK + 64] */, unsigned long long* __restrict__ store, int32_t* __restrict__ col_scores,
-                                   int& out_score, int& out_best, int& out_first, int& out_last) {
+                                   int& out_score, int& out_best, int& out_first, int& out_last, int* out_count = nullptr) {
     const int lane = lane_id();
     const int qn = q.n, tn = t.n;
     const int nblocks = (qn + 63) >> 6;
@@ -108,7 +113,7 @@ static __device__ void myers_sweep(const MyersSeq& q, const MyersSeq& t, int mod
     // rows, edlib.cpp:664-690): with W > 0 the columns "before the target" (score = query length) take part and win ties, which is
     // what best = qn, first = -1 reproduces; with W == 0 there are none, and the first real column that reaches the best score --
     // query length included -- is the answer (64 x 'A' in 'CCC...': end location 0, path 1X63I).
-    int score = qn, best = (qn & 63) == 0 ? qn + 1 : qn, best_first = -1, best_last = -1;
+    int score = qn, best = (qn & 63) == 0 ? qn + 1 : qn, best_first = -1, best_last = -1, n_best = (qn & 63) == 0 ? 0 : 1;
     bool reached_end = false;
     for (int pb = 0; pb < nblocks; pb += 64) {
         const int blk = pb + lane;
@@ -172,8 +177,8 @@ static __device__ void myers_sweep(const MyersSeq& q, const MyersSeq& t, int mod
                     if (is_last_blk) {
                         score += (int)((Ph >> last_row) & 1ull) - (int)((Mh >> last_row) & 1ull);
                         if (mode != 0) {
-                            if (score < best) { best = score; best_first = j; best_last = j; }
-                            else if (score == best) best_last = j;
+                            if (score < best) { best = score; best_first = j; best_last = j; n_best = 1; }
+                            else if (score == best) { best_last = j; ++n_best; }
                         }
                         if (j == tn - 1) reached_end = true;
                     }
@@ -205,6 +210,7 @@ static __device__ void myers_sweep(const MyersSeq& q, const MyersSeq& t, int mod
     const int owner = (nblocks - 1) & 63;
     out_score = __shfl(reached_end ? score : MY_INF, owner, 64); out_best = __shfl(best, owner, 64);
     out_first = __shfl(best_first, owner, 64); out_last = __shfl(best_last, owner, 64);
+    if (out_count) *out_count = __shfl(n_best, owner, 64);
 }
 
 // exact score of cell (row, col) of the NW matrix from the stored words; boundaries as edlib's (:980-984)
@@ -254,15 +260,52 @@ static __device__ __forceinline__ bool myers_leaf(int qn, int tn) {
 #define MY_LEAF_CELLS 52428      /* blocks x columns of the largest matrix that passes myers_leaf */
 #define MY_MAX_QUERY (1 << 20)   /* (a matrix that does not pass has >= 4 columns up to this query length) */
 
+// The band of a sweep of mode 0 / 1 / 2 whose optimum is at most k (all: every cell), and the first bound tried when none is given:
+// 1/16 of the query length (+ the length difference for NW).
+static __device__ __forceinline__ MyersBand myers_mode_band(int mode, int qn, int tn, int k, bool all) {
+    if (all) return MyersBand::whole();
+    return mode == 0 ? MyersBand::global(qn, tn, k) : mode == 1 ? MyersBand::prefix(k) : MyersBand::infix(qn, tn, k);
+}
+static __device__ __forceinline__ int myers_first_bound(int mode, int qn, int tn) {
+    const int D = tn > qn ? tn - qn : qn - tn;
+    return max(64, qn >> 4) + (mode == 0 ? D : 0);
+}
+
+// Step 1 of the path kernels (edlibAlign :194-221): distance d, first end location e and the number of end locations n (NW: the
+// last column, one location). kb < 0: the bound is found on the way -- when the score found lies above the bound it is the
+// score of an alignment that exists (every score in the band is one), so the optimum is at most that and the next sweep, with
+// that bound, holds it (edlibAlign doubles its bound from 64 instead, :194-214; the answer does not depend on the bounds tried:
+// the first one that holds the optimum returns it exactly). kb >= 0: one sweep in the band of kb (HW: of at most the query
+// length, :566-569); an optimum above kb is d = -1, as is an NW pair whose lengths differ by more than kb (:746-749).
+template <int MODE>
+static __device__ void myers_locate(const MyersSeq& q, const MyersSeq& t, int kb, int8_t* __restrict__ hb, int32_t* __restrict__ hbot, uint8_t* tbuf,
+                                    int& d, int& e, int& n) {
+    const int qn = q.n, tn = t.n;
+    const int kmax = MODE == 0 ? max(qn, tn) : qn;
+    d = -1; e = -1; n = 0;
+    if (kb >= 0 && MODE == 0 && kb < abs(tn - qn)) return;
+    int sc, best, first, last, cnt;
+    for (int k = kb >= 0 ? min(kb, kmax) : myers_first_bound(MODE, qn, tn);;) {
+        const bool all = k >= kmax;
+        myers_sweep(q, t, MODE, myers_mode_band(MODE, qn, tn, k, all), hb, hbot, tbuf, nullptr, nullptr, sc, best, first, last, &cnt);
+        const int got = MODE == 0 ? sc : best;
+        if (all || got <= k) { d = got; e = MODE == 0 ? tn - 1 : first; n = MODE == 0 ? 1 : cnt; return; }
+        if (kb >= 0) return;
+        k = got >= MY_INF ? 2 * k : got;
+    }
+}
+
 #ifndef MY_WAVES_PER_EU
 #define MY_WAVES_PER_EU 1
 #endif
+// task: 0 distance (no start location), 1 locations, 2 locations and path. kbound < 0: no bound. n_loc may be null.
+template <int MODE>
 __global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
     const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,
     const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list, int8_t* __restrict__ hscratch,
     const int64_t* __restrict__ hscratch_off, unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off,
-    int32_t* __restrict__ col_scratch, int want_path,
-    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc,
+    int32_t* __restrict__ col_scratch, int kbound, int task,
+    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc, int32_t* __restrict__ n_loc,
     uint8_t* __restrict__ ops, const int64_t* __restrict__ ops_off, int32_t* __restrict__ ops_len) {
     __shared__ uint8_t tbuf[MY_TCHUNK + 64];
     __shared__ int s_stack[40][5];
@@ -276,34 +319,40 @@ __global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
     int8_t* hb = hscratch + hscratch_off[pr];                                   // [tn + 64] bytes, then [tn + 64] ints
     int32_t* hbot = reinterpret_cast<int32_t*>(hb + ((tn + 64 + 3) & ~3));
     uint8_t* op = ops ? ops + ops_off[pr] : nullptr;
-    if (qn == 0 || tn == 0) {      // edlib.cpp:174-191: distance = query length, end location -1, no start location / path
-        if (lane == 0) { dist[pr] = qn; end_loc[pr] = -1; start_loc[pr] = -1; if (ops_len) ops_len[pr] = 0; }
+    if (qn == 0 || tn == 0) {      // edlib.cpp:161-180, whatever the bound: NW max(qn, tn) at the last column, SHW / HW the query length at -1; no start location / path
+        if (lane == 0) {
+            dist[pr] = MODE == 0 ? max(qn, tn) : qn; end_loc[pr] = MODE == 0 ? tn - 1 : -1; start_loc[pr] = -1;
+            if (n_loc) n_loc[pr] = 1;
+            if (ops_len) ops_len[pr] = 0;
+        }
         return;
     }
     int sc, best, first, last;
-    // 1. HW: distance and first end location. The band needs a bound on the distance: 1/16 of the query length first; when the
-    //    best score found lies above the bound it is the score of an alignment that exists (every score in the band is one), so
-    //    the optimum is at most that and the second sweep, with that bound, holds it (edlibAlign doubles its bound from 64
-    //    instead, :194-214; the answer does not depend on the bounds tried: the first one that holds the optimum returns it
-    //    exactly).
-    for (int k = max(64, qn >> 4);;) {
-        const bool all = k >= qn;
-        myers_sweep(MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, 2, all ? MyersBand::whole() : MyersBand::infix(qn, tn, k), hb, hbot, tbuf, nullptr, nullptr,
-                    sc, best, first, last);
-        if (all || best <= k) break;
-        k = best;
-    }
-    const int d = best, e = first;
-    if (e < 0) {   // the whole query before the target (:233-246): start location 0, the alignment over an empty target is all insertions (:1171-1178)
-        if (lane == 0) { dist[pr] = d; end_loc[pr] = -1; start_loc[pr] = 0; }
-        if (want_path && op) { for (int i = lane; i < qn; i += 64) op[i] = 1; if (lane == 0) ops_len[pr] = qn; }
+    // 1. distance, first end location, number of end locations
+    int d, e, nl;
+    myers_locate<MODE>(MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, kbound, hb, hbot, tbuf, d, e, nl);
+    if (d < 0) {   // above the bound (:212-215): no location, no path
+        if (lane == 0) { dist[pr] = -1; end_loc[pr] = -1; start_loc[pr] = -1; if (n_loc) n_loc[pr] = 0; if (ops_len) ops_len[pr] = 0; }
         return;
     }
-    // 2. start location: reversed query against the reversed target prefix [0, e], last best column
-    myers_sweep(MyersSeq{qp, qn, true}, MyersSeq{tp, e + 1, true}, 1, MyersBand::prefix(d), hb, hbot, tbuf, nullptr, nullptr, sc, best, first, last);
-    const int st = e - last;
+    if (lane == 0 && n_loc) n_loc[pr] = nl;
+    if (task == 0) {      // TASK_DISTANCE: edlib finds no start location (:223-224)
+        if (lane == 0) { dist[pr] = d; end_loc[pr] = e; start_loc[pr] = -1; }
+        return;
+    }
+    if (e < 0) {   // the whole query before the target (HW :233-246, SHW: start 0): the alignment over an empty target is all insertions (:1171-1178)
+        if (lane == 0) { dist[pr] = d; end_loc[pr] = -1; start_loc[pr] = 0; }
+        if (task == 2 && op) { for (int i = lane; i < qn; i += 64) op[i] = 1; if (lane == 0) ops_len[pr] = qn; }
+        return;
+    }
+    // 2. start location -- HW: reversed query against the reversed target prefix [0, e], last best column; NW / SHW: 0 (:263-267)
+    int st = 0;
+    if (MODE == 2) {
+        myers_sweep(MyersSeq{qp, qn, true}, MyersSeq{tp, e + 1, true}, 1, MyersBand::prefix(d), hb, hbot, tbuf, nullptr, nullptr, sc, best, first, last);
+        st = e - last;
+    }
     if (lane == 0) { dist[pr] = d; end_loc[pr] = e; start_loc[pr] = st; }
-    if (!want_path || !ops) return;
+    if (task != 2 || !ops) return;
     // 3. the alignment of the query with target[st .. e] (obtainAlignment, :1166-1219), depth first with the upper-left part before
     //    the lower-right one, so that the moves come out in order. A frame: {query begin, query length, target begin, target length, score}.
     if (qn > MY_MAX_QUERY) { if (lane == 0) ops_len[pr] = -1; return; }
@@ -382,12 +431,13 @@ __global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
 #define MY_GCHUNK 1024
 template <int G>
 static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const MyersSeq& t, int mode, MyersBand band, uint8_t* __restrict__ tb /* this group's LDS [MY_GCHUNK + 64] */,
-                                           unsigned long long* __restrict__ store, int& out_score, int& out_best, int& out_first, int& out_last) {
+                                           unsigned long long* __restrict__ store, int& out_score, int& out_best, int& out_first, int& out_last,
+                                           int* out_count = nullptr) {
     const int lane = lane_id(), gl = lane & (G - 1);
     const int qn = q.n, tn = t.n;
     const int nblocks = (qn + 63) >> 6;
     const int last_row = (qn - 1) & 63;
-    int score = qn, best = (qn & 63) == 0 ? qn + 1 : qn, best_first = -1, best_last = -1;
+    int score = qn, best = (qn & 63) == 0 ? qn + 1 : qn, best_first = -1, best_last = -1, n_best = (qn & 63) == 0 ? 0 : 1;
     bool reached_end = false;
     const int blk = gl;
     const bool is_last_blk = blk == nblocks - 1;
@@ -460,8 +510,8 @@ static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const
                 if (is_last_blk) {
                     score += (int)((Ph >> last_row) & 1ull) - (int)((Mh >> last_row) & 1ull);
                     if (mode != 0) {
-                        if (score < best) { best = score; best_first = j; best_last = j; }
-                        else if (score == best) best_last = j;
+                        if (score < best) { best = score; best_first = j; best_last = j; n_best = 1; }
+                        else if (score == best) { best_last = j; ++n_best; }
                     }
                     if (j == tn - 1) reached_end = true;
                 }
@@ -480,14 +530,15 @@ static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const
     const int owner = (lane & ~(G - 1)) + ((nblocks - 1) & (G - 1));
     out_score = __shfl(reached_end ? score : MY_INF, owner, 64); out_best = __shfl(best, owner, 64);
     out_first = __shfl(best_first, owner, 64); out_last = __shfl(best_last, owner, 64);
+    if (out_count) *out_count = __shfl(n_best, owner, 64);
 }
 
-template <int G>
+template <int G, int MODE>
 __global__ __launch_bounds__(64) void k_myers_hw_path_grouped(
     const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,
     const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list,
-    unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off, int want_path,
-    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc,
+    unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off, int kbound, int task,
+    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc, int32_t* __restrict__ n_loc,
     uint8_t* __restrict__ ops, const int64_t* __restrict__ ops_off, int32_t* __restrict__ ops_len) {
     constexpr int NG = 64 / G;
     __shared__ __attribute__((aligned(16))) uint8_t tbuf[NG][MY_GCHUNK + 64];
@@ -501,26 +552,48 @@ __global__ __launch_bounds__(64) void k_myers_hw_path_grouped(
     uint8_t* op = (ops && live) ? ops + ops_off[pr] : nullptr;
     uint8_t* tb = tbuf[grp];
     bool act = live && qn > 0 && tn > 0;
-    if (live && !act && gl == 0) { dist[pr] = qn; end_loc[pr] = -1; start_loc[pr] = -1; if (ops_len) ops_len[pr] = 0; }      // edlib.cpp:174-191
-    int sc, best, first, last;
-    // 1. HW with a doubled bound (every group at its own)
-    int k = max(64, qn >> 4), d = 0, e = -1;
-    bool pending = act;
+    if (live && !act && gl == 0) {      // edlib.cpp:161-180 (see k_myers_hw_path)
+        dist[pr] = MODE == 0 ? max(qn, tn) : qn; end_loc[pr] = MODE == 0 ? tn - 1 : -1; start_loc[pr] = -1;
+        if (n_loc) n_loc[pr] = 1;
+        if (ops_len) ops_len[pr] = 0;
+    }
+    int sc, best, first, last, cnt;
+    // 1. as myers_locate, every group at its own bound
+    const int kmax = MODE == 0 ? max(qn, tn) : qn;
+    int k = kbound >= 0 ? min(kbound, kmax) : myers_first_bound(MODE, qn, tn), d = -1, e = -1, nl = 0;
+    bool pending = act && !(kbound >= 0 && MODE == 0 && kbound < abs(tn - qn));
     while (__ballot(pending) != 0ull) {
-        const bool all = k >= qn;
-        myers_sweep_grouped<G>(pending, MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, 2, all ? MyersBand::whole() : MyersBand::infix(qn, tn, k), tb, nullptr, sc, best, first, last);
-        if (pending) { if (all || best <= k) { pending = false; d = best; e = first; } else k = best; }      // (see k_myers_hw_path)
+        const bool all = k >= kmax;
+        myers_sweep_grouped<G>(pending, MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, MODE, myers_mode_band(MODE, qn, tn, k, all), tb, nullptr, sc, best, first, last, &cnt);
+        if (pending) {
+            const int got = MODE == 0 ? sc : best;
+            if (all || got <= k) { pending = false; d = got; e = MODE == 0 ? tn - 1 : first; nl = MODE == 0 ? 1 : cnt; }
+            else if (kbound >= 0) pending = false;
+            else k = got >= MY_INF ? 2 * k : got;
+        }
+    }
+    if (act && d < 0) {      // above the bound: no location, no path
+        if (gl == 0) { dist[pr] = -1; end_loc[pr] = -1; start_loc[pr] = -1; if (n_loc) n_loc[pr] = 0; if (ops_len) ops_len[pr] = 0; }
+        act = false;
+    }
+    if (act && gl == 0 && n_loc) n_loc[pr] = nl;
+    if (task == 0) {
+        if (act && gl == 0) { dist[pr] = d; end_loc[pr] = e; start_loc[pr] = -1; }
+        return;
     }
     if (act && e < 0) {      // the whole query before the target (:233-246)
         if (gl == 0) { dist[pr] = d; end_loc[pr] = -1; start_loc[pr] = 0; }
-        if (want_path && op) { for (int i = gl; i < qn; i += G) op[i] = 1; if (gl == 0) ops_len[pr] = qn; }
+        if (task == 2 && op) { for (int i = gl; i < qn; i += G) op[i] = 1; if (gl == 0) ops_len[pr] = qn; }
         act = false;
     }
-    // 2. start location
-    myers_sweep_grouped<G>(act, MyersSeq{qp, qn, true}, MyersSeq{tp, e + 1, true}, 1, MyersBand::prefix(d), tb, nullptr, sc, best, first, last);
-    const int st = e - last;
+    // 2. start location (HW; NW / SHW: 0)
+    int st = 0;
+    if (MODE == 2) {
+        myers_sweep_grouped<G>(act, MyersSeq{qp, qn, true}, MyersSeq{tp, e + 1, true}, 1, MyersBand::prefix(d), tb, nullptr, sc, best, first, last);
+        st = e - last;
+    }
     if (act && gl == 0) { dist[pr] = d; end_loc[pr] = e; start_loc[pr] = st; }
-    if (!want_path || !ops) return;
+    if (task != 2 || !ops) return;
     // 3. one leaf: the matrix whole, the traceback by the group's first lane
     const int an = e - st + 1;
     const MyersBand band = MyersBand::global(qn, an, d);
@@ -534,15 +607,8 @@ __global__ __launch_bounds__(64) void k_myers_hw_path_grouped(
 
 // ---- distance and end location only (hs_edit_distance: edlib's TASK_DISTANCE / TASK_LOC end, modes NW / SHW / HW) ------------
 // The same banded sweeps. The bound: 1/16 of the query length (+ the length difference for NW) first; a score above the bound
-// is the score of an alignment that exists, so the sweep with that score as its bound holds the optimum.
-static __device__ __forceinline__ MyersBand myers_mode_band(int mode, int qn, int tn, int k, bool all) {
-    if (all) return MyersBand::whole();
-    return mode == 0 ? MyersBand::global(qn, tn, k) : mode == 1 ? MyersBand::prefix(k) : MyersBand::infix(qn, tn, k);
-}
-static __device__ __forceinline__ int myers_first_bound(int mode, int qn, int tn) {
-    const int D = tn > qn ? tn - qn : qn - tn;
-    return max(64, qn >> 4) + (mode == 0 ? D : 0);
-}
+// is the score of an alignment that exists, so the sweep with that score as its bound holds the optimum (myers_mode_band,
+// myers_first_bound above).
 
 __global__ __launch_bounds__(64) void k_myers_distance(
     const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,

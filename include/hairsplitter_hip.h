@@ -249,6 +249,21 @@ int hs_edlib_hw_align(const uint8_t* d_query, const int64_t* h_query_off, const 
                       int32_t n_pairs, int32_t* d_dist, int32_t* d_start, int32_t* d_end, uint8_t* d_ops, const int64_t* h_ops_off,
                       int32_t* d_ops_len, void* stream);
 
+/* edlibAlign(query, target, edlibNewAlignConfig(k, mode, task, NULL, 0)) for n pairs, batched, on the kernels of hs_edlib_hw_align.
+ * mode: 0 NW, 1 SHW, 2 HW; task: 0 DISTANCE, 1 LOC, 2 PATH; k = -1 (any k < 0): no bound.
+ * d_dist = editDistance (-1 beyond k), d_start / d_end = startLocations[0] / endLocations[0] (-1 when none; no start location
+ * for DISTANCE, nor for an empty query or target, as edlib), d_nloc = numLocations (0 beyond k; may be NULL),
+ * d_ops / h_ops_off / d_ops_len as hs_edlib_hw_align (task PATH only; may be NULL otherwise; d_ops_len = 0 where edlib has no
+ * alignment). With k >= 0 the band of the first sweep is sized from k; a pair within k gets the locations and path of k = -1.
+ * Offsets are HOST arrays [n+1]; sequences are codes 0..3. Synchronous with respect to `stream`. */
+int hs_edlib_align(const uint8_t* d_query, const int64_t* h_query_off, const uint8_t* d_target, const int64_t* h_target_off,
+                   int32_t n_pairs, int32_t mode, int32_t task, int32_t k,
+                   int32_t* d_dist, int32_t* d_start, int32_t* d_end, int32_t* d_nloc,
+                   uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream);
+/* edlibAlignmentToCigar on host: format 0 STANDARD (M I D), 1 EXTENDED (= X I D); returns a malloc'd string (hs_free_host).
+ * An empty alignment gives "". */
+int hs_alignment_to_cigar(const uint8_t* ops, int32_t n_ops, int32_t format, char** out);
+
 /* A1 on the path: a CIGAR-less input. The reference reads the base-level alignments from the CIGARs of a SAM file and
  * refuses a .paf (call_variants.cpp:1256-1267; CIGAR required at input_output.cpp:357-368). hs_realign_paf turns a PAF file (read
  * interval, strand, contig interval per line) into that SAM: every read segment is aligned against its contig window (the PAF

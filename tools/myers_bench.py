@@ -3,7 +3,10 @@ piece inside its polished version of a few kb; tools.cpp:515-534: 200 bases insi
 hs_edlib_hw_align (HW + start location + path), next to the reference's edlib on one host core on a sample of the same pairs.
 With a query length above 300 the pairs are READS against a contig window (the read with ~8 % substitutions, insertions and
 deletions inside target_len bases): the banded sweeps and Hirschberg's cuts, one wavefront per read.
-Usage: python tools/myers_bench.py [n_pairs=20000] [target_len=2000] [query_len=300]     (prints one JSON line)"""
+Usage: python tools/myers_bench.py [n_pairs=20000] [target_len=2000] [query_len=300]     (prints one JSON line)
+       python tools/myers_bench.py nw [n_pairs=2048] [read_len=10000]: hs_edlib_align NW TASK_PATH of reads against a copy with
+       ~6 % edits (edlib's default mode; these pairs go through Hirschberg's cuts), with k = -1 and with k = the largest distance
+       of the batch (every pair within the bound: the same results, the first sweep's band sized from k)."""
 import ctypes as C
 import json
 import os
@@ -17,7 +20,59 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def nw_paths(n, rl):
+    import torch
+    from hairsplitter_amd import api
+    api.require_gpu()
+    lib = api.load()
+    rng = np.random.default_rng(10)
+    qs, ts = [], []
+    for _ in range(n):
+        q = rng.integers(0, 4, size=rl, dtype=np.uint8)
+        u = rng.random(rl)
+        t = q.copy()
+        sub = u < 0.02
+        t[sub] = (t[sub] + 1) & 3
+        ins = np.flatnonzero((u >= 0.02) & (u < 0.04))
+        keep = np.insert(~((u >= 0.04) & (u < 0.06)), ins, True)
+        t = np.insert(t, ins, rng.integers(0, 4, size=len(ins), dtype=np.uint8))[keep]
+        qs.append(q); ts.append(t)
+    qo = np.zeros(n + 1, np.int64); to = np.zeros(n + 1, np.int64)
+    np.cumsum([len(x) for x in qs], out=qo[1:]); np.cumsum([len(x) for x in ts], out=to[1:])
+    oo = qo + to
+    dev = "cuda:0"
+    dq = torch.from_numpy(np.concatenate(qs)).to(dev); dt = torch.from_numpy(np.concatenate(ts)).to(dev)
+    dd = torch.zeros(n, dtype=torch.int32, device=dev); ds, de, dn, dl = (torch.zeros_like(dd) for _ in range(4))
+    dops = torch.zeros(int(oo[-1]), dtype=torch.uint8, device=dev)
+    hp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    out = {"mode": "NW", "task": "path", "pairs": n, "read_len": rl, "target_len_mean": float(np.mean([len(x) for x in ts]))}
+    ref = None
+    for label, k in (("k_-1", -1), ("k_max_distance", None)):
+        if k is None:
+            k = int(dd.max().item())
+            out["k"] = k
+        times = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            api._check(lib.hs_edlib_align(api._p(dq), hp(qo), api._p(dt), hp(to), C.c_int32(n), C.c_int32(0), C.c_int32(2), C.c_int32(k),
+                                          api._p(dd), api._p(ds), api._p(de), api._p(dn), api._p(dops), hp(oo), api._p(dl), C.c_void_p(0)))
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        best = min(times[1:])
+        res = (dd.cpu().numpy().copy(), dl.cpu().numpy().copy(), dops.cpu().numpy())
+        if ref is None:
+            ref = res
+            out["distance_mean"] = float(res[0].mean())
+        else:
+            assert np.array_equal(ref[0], res[0]) and np.array_equal(ref[1], res[1]) and np.array_equal(ref[2], res[2])
+        out[label] = {"seconds": best, "pairs_per_s": n / best}
+    print(json.dumps(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "nw":
+        return nw_paths(int(sys.argv[2]) if len(sys.argv) > 2 else 2048, int(sys.argv[3]) if len(sys.argv) > 3 else 10000)
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
     tl = int(sys.argv[2]) if len(sys.argv) > 2 else 2000
     import torch
