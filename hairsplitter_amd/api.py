@@ -24,7 +24,7 @@ SYMBOLS = [
     "hs_event_elapsed_ms", "hs_pileup", "hs_pileup_plan", "hs_free_host", "hs_tile_plan", "hs_column_stats_tiled", "hs_cv_column_pass_taps", "hs_cv_taps_destroy", "hs_sr_run_taps", "hs_sr_taps_destroy", "hs_exclusive_scan_i32", "hs_gaf_from_files", "hs_gaf_from_labels", "hs_gro_to_gaf_main", "hs_column_partition_test", "hs_column_partition_last_counts", "hs_partition_pair_distance", "hs_snp_planes", "hs_simdiff", "hs_read_graphs",
     "hs_edit_distance", "hs_cv_batch_create", "hs_cv_batch_destroy", "hs_cv_batch_aligned_bp", "hs_cv_run",
     "hs_cv_result_destroy", "hs_cv_select", "hs_cv_run_range", "hs_cv_selection_destroy", "hs_sr_run", "hs_sr_run_cv", "hs_sr_run_cv_range", "hs_pipeline_create", "hs_pipeline_select", "hs_pipeline_run", "hs_pipeline_destroy", "hs_pipeline_thread_devices", "hs_cv_batch_device", "hs_sr_result_destroy", "hs_sr_window_size", "hs_call_variants_main", "hs_call_variants_epilogue",
-    "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_edlib_align", "hs_alignment_to_cigar", "hs_reattach_ends", "hs_trim_polished", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
+    "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_edlib_align", "hs_edlib_align_bytes", "hs_alignment_to_cigar", "hs_reattach_ends", "hs_trim_polished", "hs_reattach_ends_bytes", "hs_trim_polished_bytes", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
 ]
 
 HS_NKERNELS = 28
@@ -1040,19 +1040,54 @@ def alignment_to_cigar(ops, fmt="extended"):
     return s
 
 
-def edlib_align(pairs, mode="NW", task="path", k=-1, cigar=None):
-    """edlibAlign(query, target, edlibNewAlignConfig(k, mode, task, NULL, 0)) for every (query, target) pair, on the device
-    (hs_edlib_align). mode NW | SHW | HW; task "distance" | "loc" | "path"; k = -1: no bound. Pairs: strings / bytes (at most four
-    distinct bytes per pair) or arrays of codes 0..3. -> one dict per pair: {distance (-1 beyond k), start, end (-1 when none),
-    n_locations, ops (numpy uint8 of edlib move codes; None unless task "path"), cigar (None unless cigar = "standard" |
-    "extended")}."""
+def _edlib_bytes(pairs):
+    """(query, target) -> uint8 arrays of the bytes as they are (str: its encoding; bytes; arrays of values 0..255)"""
+    def one(x, i):
+        if isinstance(x, str):
+            x = x.encode()
+        if isinstance(x, (bytes, bytearray)):
+            return np.frombuffer(bytes(x), dtype=np.uint8)
+        a = np.asarray(x)
+        if a.size and (a.min() < 0 or a.max() > 255):
+            raise HsError(f"edlib_align: pair {i}: byte arrays hold values 0..255")
+        return a.astype(np.uint8).reshape(-1)
+    return [one(q, i) for i, (q, _) in enumerate(pairs)], [one(t, i) for i, (_, t) in enumerate(pairs)]
+
+
+def _equality_pairs(equalities):
+    """[(a, b), ...] of one-character strings, bytes or ints -> uint8 array [n, 2] (hs_equality_pair, == EdlibEqualityPair)"""
+    def byte(x):
+        if isinstance(x, str):
+            x = x.encode()
+        if isinstance(x, (bytes, bytearray)):
+            if len(x) != 1:
+                raise HsError("edlib_align: an equality names single bytes")
+            return x[0]
+        if not 0 <= int(x) <= 255:
+            raise HsError("edlib_align: an equality names bytes 0..255")
+        return int(x)
+    return np.array([[byte(a), byte(b)] for a, b in equalities], dtype=np.uint8).reshape(-1, 2)
+
+
+def edlib_align(pairs, mode="NW", task="path", k=-1, cigar=None, alphabet=None, equalities=None):
+    """edlibAlign(query, target, edlibNewAlignConfig(k, mode, task, equalities, len(equalities))) for every (query, target) pair, on
+    the device. mode NW | SHW | HW; task "distance" | "loc" | "path"; k = -1: no bound.
+    alphabet None (hs_edlib_align): strings / bytes with at most four distinct bytes per pair, or arrays of codes 0..3.
+    alphabet "bytes" (hs_edlib_align_bytes): str, bytes and uint8 arrays as they are, any alphabet up to 256 distinct bytes.
+    equalities: edlib's additionalEqualities, a list of 2-tuples of one-character strings, bytes or ints, e.g. [("N", "A"), ("N", "C"),
+    ("N", "G"), ("N", "T")]; implies alphabet "bytes".
+    -> one dict per pair: {distance (-1 beyond k), start, end (-1 when none), n_locations, ops (numpy uint8 of edlib move codes;
+    None unless task "path"), cigar (None unless cigar = "standard" | "extended")}."""
     import torch
     require_gpu()
     dev = "cuda:0"
     m, tk = EDLIB_MODES[mode], EDLIB_TASKS[task]
     if cigar is not None and tk != 2:
         raise HsError("edlib_align: a CIGAR needs task 'path'")
-    qs, ts = _edlib_codes(pairs)
+    if alphabet not in (None, "bytes"):
+        raise HsError("edlib_align: alphabet is None or 'bytes'")
+    as_bytes = alphabet == "bytes" or equalities is not None
+    qs, ts = _edlib_bytes(pairs) if as_bytes else _edlib_codes(pairs)
     n = len(pairs)
     qo = np.zeros(n + 1, np.int64); to = np.zeros(n + 1, np.int64); oo = np.zeros(n + 1, np.int64)
     np.cumsum([len(x) for x in qs], out=qo[1:]); np.cumsum([len(x) for x in ts], out=to[1:])
@@ -1062,9 +1097,14 @@ def edlib_align(pairs, mode="NW", task="path", k=-1, cigar=None):
     dd = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
     ds, de, dn, dl = (torch.zeros_like(dd) for _ in range(4))
     dops = torch.zeros(max(int(oo[-1]), 1), dtype=torch.uint8, device=dev) if tk == 2 else None
-    _check(load().hs_edlib_align(_p(dq), _hp(qo, C.c_int64), _p(dt), _hp(to, C.c_int64), C.c_int32(n), C.c_int32(m), C.c_int32(tk),
-                                 C.c_int32(int(k)), _p(dd), _p(ds), _p(de), _p(dn), _p(dops), _hp(oo, C.c_int64) if tk == 2 else None,
-                                 _p(dl) if tk == 2 else C.c_void_p(0), C.c_void_p(0)))
+    outs = (_p(dd), _p(ds), _p(de), _p(dn), _p(dops), _hp(oo, C.c_int64) if tk == 2 else None, _p(dl) if tk == 2 else C.c_void_p(0), C.c_void_p(0))
+    if as_bytes:
+        eq = _equality_pairs(equalities if equalities is not None else [])
+        _check(load().hs_edlib_align_bytes(_p(dq), _hp(qo, C.c_int64), _p(dt), _hp(to, C.c_int64), C.c_int32(n), C.c_int32(m), C.c_int32(tk),
+                                           C.c_int32(int(k)), _hp(eq, C.c_uint8) if len(eq) else None, C.c_int32(len(eq)), *outs))
+    else:
+        _check(load().hs_edlib_align(_p(dq), _hp(qo, C.c_int64), _p(dt), _hp(to, C.c_int64), C.c_int32(n), C.c_int32(m), C.c_int32(tk),
+                                     C.c_int32(int(k)), *outs))
     torch.cuda.synchronize()
     dd, ds, de, dn, dl = (x.cpu().numpy() for x in (dd, ds, de, dn, dl))
     ops = dops.cpu().numpy() if tk == 2 else None
@@ -1092,11 +1132,18 @@ def _string_batch(fn, lists, ints=()):
     return res
 
 
-def reattach_ends(backbones, consensuses):
-    """tools.cpp:505-536, batched"""
-    return _string_batch(load().hs_reattach_ends, [backbones, consensuses])
+def _stage5_fn(name, alphabet):
+    if alphabet not in (None, "bytes"):
+        raise HsError(name + ": alphabet is None or 'bytes'")
+    return getattr(load(), name + ("_bytes" if alphabet == "bytes" else ""))
 
 
-def trim_polished(to_polish, newcontigs, overhang_left, overhang_right):
-    """create_new_contigs.cpp:556-629, batched"""
-    return _string_batch(load().hs_trim_polished, [to_polish, newcontigs], [overhang_left, overhang_right])
+def reattach_ends(backbones, consensuses, alphabet=None):
+    """tools.cpp:505-536, batched. alphabet None: at most four distinct bytes per aligned pair (hs_reattach_ends); "bytes": any
+    bytes, compared as edlib compares them (hs_reattach_ends_bytes)"""
+    return _string_batch(_stage5_fn("hs_reattach_ends", alphabet), [backbones, consensuses])
+
+
+def trim_polished(to_polish, newcontigs, overhang_left, overhang_right, alphabet=None):
+    """create_new_contigs.cpp:556-629, batched. alphabet as in reattach_ends (hs_trim_polished / hs_trim_polished_bytes)"""
+    return _string_batch(_stage5_fn("hs_trim_polished", alphabet), [to_polish, newcontigs], [overhang_left, overhang_right])

@@ -599,9 +599,25 @@ struct MyersPathArgs {
     const uint8_t* query; const int64_t* qo; const uint8_t* target; const int64_t* to; int8_t* hs; const int64_t* ho;
     unsigned long long* st; const int64_t* so; int32_t* cols; int k, task;
     int32_t *dist, *start, *end, *nloc; uint8_t* ops; const int64_t* oo; int32_t* ops_len;
+    int tier; hsdev::MyersEq eq;      // 0: codes 0..3; 1 / 2: symbols and an equality table in LDS / in scratch (hs_kernels_myers.hip)
 };
+template <int MODE, int TIER>
+static void myers_path_launch_eq(const MyersPathArgs& a, int cls, const int32_t* ids, int n, hipStream_t s) {
+#define HS_MYERS_GROUPED_EQ(G)                                                                                                                            \
+    hipLaunchKernelGGL((hsdev::k_myers_hw_path_grouped_eq<G, MODE, TIER>), dim3((unsigned)((n + 64 / G - 1) / (64 / G))), dim3(64), 0, s, a.query, a.qo,  \
+                       a.target, a.to, ids, n, a.st, a.so, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len, a.eq)
+    if (cls == 0) HS_MYERS_GROUPED_EQ(8);
+    else if (cls == 1) HS_MYERS_GROUPED_EQ(16);
+    else if (cls == 2) HS_MYERS_GROUPED_EQ(32);
+    else
+        hipLaunchKernelGGL((hsdev::k_myers_hw_path_eq<MODE, TIER>), dim3((unsigned)n), dim3(64), 0, s, a.query, a.qo, a.target, a.to, ids, n, a.hs, a.ho, a.st,
+                           a.so, a.cols, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len, a.eq);
+#undef HS_MYERS_GROUPED_EQ
+}
 template <int MODE>
 static void myers_path_launch(const MyersPathArgs& a, int cls, const int32_t* ids, int n, hipStream_t s) {
+    if (a.tier == 1) return myers_path_launch_eq<MODE, 1>(a, cls, ids, n, s);
+    if (a.tier == 2) return myers_path_launch_eq<MODE, 2>(a, cls, ids, n, s);
 #define HS_MYERS_GROUPED(G)                                                                                                                               \
     hipLaunchKernelGGL((hsdev::k_myers_hw_path_grouped<G, MODE>), dim3((unsigned)((n + 64 / G - 1) / (64 / G))), dim3(64), 0, s, a.query, a.qo, a.target, \
                        a.to, ids, n, a.st, a.so, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len)
@@ -617,10 +633,12 @@ static void myers_path_launch(const MyersPathArgs& a, int cls, const int32_t* id
 
 // A1 as edlibAlign(query, target, edlibNewAlignConfig(k, mode, task, NULL, 0)) (see hs_kernels_myers.hip): mode 0 NW, 1 SHW, 2 HW;
 // task 0 distance, 1 locations, 2 path (d_ops required). Host offsets; the device buffers of the sequences and results are the
-// caller's. d_nloc may be NULL.
+// caller's. d_nloc may be NULL. eqs != nullptr: the sequences are symbols 0 .. n_sym - 1 and eqs->mask (device) their equality
+// rows (hs_edlib_align_bytes below); the scratch table of tier 2 (n_sym x 64 words per wavefront) counts against the budget.
+struct MyersEqCall { int tier, n_sym, words; const uint32_t* d_mask; };
 static int edlib_align_launch(const char* who, const uint8_t* d_query, const int64_t* h_query_off, const uint8_t* d_target, const int64_t* h_target_off,
                               int32_t n_pairs, int32_t mode, int32_t task, int32_t k, int32_t* d_dist, int32_t* d_start, int32_t* d_end, int32_t* d_nloc,
-                              uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream) {
+                              uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream, const MyersEqCall* eqs = nullptr) {
     if (int rc = require_device()) return rc;
     if (n_pairs <= 0) return HS_OK;
     if (mode < 0 || mode > 2 || task < 0 || task > 2) { set_error(std::string(who) + ": mode must be 0 (NW), 1 (SHW) or 2 (HW), task 0 (distance), 1 (locations) or 2 (path)"); return HS_EINVAL; }
@@ -634,6 +652,7 @@ static int edlib_align_launch(const char* who, const uint8_t* d_query, const int
     std::vector<int32_t> cls[4];      // 0: 8 lanes, 1: 16, 2: 32, 3: a wavefront
     const bool no_groups = std::getenv("HS_MYERS_NO_GROUPS") != nullptr;      // (diagnostic, read at every call: every pair on a wavefront of its own)
     std::vector<int64_t> need_st((size_t)n_pairs, 0), need_hs((size_t)n_pairs, 0);
+    const int64_t tab_words = (eqs && eqs->tier == 2) ? (int64_t)eqs->n_sym * 64 : 0;      // per wavefront; counted per pair (grouped pairs share one)
     for (int i = 0; i < n_pairs; ++i) {
         const int64_t qn = qo[(size_t)i + 1] - qo[(size_t)i], tn = to[(size_t)i + 1] - to[(size_t)i];
         const int64_t nb = (qn + 63) / 64;
@@ -653,22 +672,23 @@ static int edlib_align_launch(const char* who, const uint8_t* d_query, const int
     struct Slice { int cls; size_t begin, end; };
     std::vector<Slice> slices;
     std::vector<int32_t> ids;
-    int64_t cur_st = 0, cur_hs = 0, max_st = 0, max_hs = 0;
+    int64_t cur_st = 0, cur_hs = 0, cur_tab = 0, max_st = 0, max_hs = 0, max_tab = 0;
     for (int c = 0; c < 4; ++c) {
         size_t begin = ids.size();
+        cur_tab = 0;      // (blocks are numbered from 0 in every launch)
         for (int32_t i : cls[c]) {
-            if ((cur_st > 0 || cur_hs > 0) && (cur_st + need_st[(size_t)i]) * 8 + cur_hs + need_hs[(size_t)i] > budget) {      // the chunk is full: what came before goes out, the scratch starts over
+            if ((cur_st > 0 || cur_hs > 0 || cur_tab > 0) && (cur_st + need_st[(size_t)i] + cur_tab + tab_words) * 8 + cur_hs + need_hs[(size_t)i] > budget) {      // the chunk is full: what came before goes out, the scratch starts over
                 if (ids.size() > begin) slices.push_back(Slice{c, begin, ids.size()});
-                begin = ids.size(); cur_st = 0; cur_hs = 0;
+                begin = ids.size(); cur_st = 0; cur_hs = 0; cur_tab = 0;
             }
             st_off[(size_t)i] = cur_st; hs_off[(size_t)i] = cur_hs;
-            cur_st += need_st[(size_t)i]; cur_hs += need_hs[(size_t)i];
-            max_st = std::max(max_st, cur_st); max_hs = std::max(max_hs, cur_hs);
+            cur_st += need_st[(size_t)i]; cur_hs += need_hs[(size_t)i]; cur_tab += tab_words;
+            max_st = std::max(max_st, cur_st); max_hs = std::max(max_hs, cur_hs); max_tab = std::max(max_tab, cur_tab);
             ids.push_back(i);
         }
         if (ids.size() > begin) slices.push_back(Slice{c, begin, ids.size()});
     }
-    DBuf d_qo, d_to, d_ho, d_so, d_oo, d_hs, d_st, d_cols, d_ids;
+    DBuf d_qo, d_to, d_ho, d_so, d_oo, d_hs, d_st, d_cols, d_ids, d_tab;
     UploadPack pk;
     pk.add(qo, d_qo); pk.add(to, d_to); pk.add(hs_off, d_ho); pk.add(st_off, d_so); pk.add(ids, d_ids);
     if (path) pk.add(oo, d_oo);
@@ -676,10 +696,12 @@ static int edlib_align_launch(const char* who, const uint8_t* d_query, const int
     if (int rc = d_hs.alloc(std::max<size_t>((size_t)max_hs, 1))) return rc;
     if (int rc = d_st.alloc(std::max<size_t>((size_t)max_st, 1) * 8)) return rc;
     if (int rc = d_cols.alloc(std::max<size_t>(path && !cls[3].empty() ? (size_t)(qo.back() - qo.front()) * 2 : 0, 1) * sizeof(int32_t))) return rc;      // Hirschberg's two columns
+    if (int rc = d_tab.alloc(std::max<size_t>((size_t)max_tab, 1) * 8)) return rc;
     const int32_t* idp = d_ids.as<int32_t>();
     const MyersPathArgs args{d_query, d_qo.as<int64_t>(), d_target, d_to.as<int64_t>(), d_hs.as<int8_t>(), d_ho.as<int64_t>(), d_st.as<unsigned long long>(),
                              d_so.as<int64_t>(), d_cols.as<int32_t>(), k, task, d_dist, d_start, d_end, d_nloc, path ? d_ops : nullptr,
-                             path ? d_oo.as<int64_t>() : nullptr, d_ops_len};
+                             path ? d_oo.as<int64_t>() : nullptr, d_ops_len, eqs ? eqs->tier : 0,
+                             eqs ? hsdev::MyersEq{eqs->d_mask, eqs->n_sym, eqs->words, d_tab.as<unsigned long long>()} : hsdev::MyersEq{nullptr, 0, 0, nullptr}};
     for (const Slice& sl : slices) {
         const int n = (int)(sl.end - sl.begin);
         if (mode == 0) myers_path_launch<0>(args, sl.cls, idp + sl.begin, n, (hipStream_t)stream);
@@ -702,6 +724,63 @@ int hs_edlib_align(const uint8_t* d_query, const int64_t* h_query_off, const uin
                    int32_t* d_ops_len, void* stream) {
     return edlib_align_launch("hs_edlib_align", d_query, h_query_off, d_target, h_target_off, n_pairs, mode, task, k, d_dist, d_start, d_end, d_nloc, d_ops,
                               h_ops_off, d_ops_len, stream);
+}
+
+// edlibAlign with additionalEqualities on raw bytes (edlib.cpp:61-92 EqualityDefinition, :357-380 buildPeq, :1422-1460
+// transformSequences). Two pre-passes: which byte values the call's sequences hold (one alphabet for the whole call: a symbol a
+// pair does not hold never takes part in its comparisons, so this gives what edlib's per-pair alphabet gives), then the
+// sequences as symbols 0 .. A - 1 in scratch. The tier follows from A: four codes in registers (A <= 4, no equality among
+// them), the LDS table (A <= 16), the scratch table (A <= 256).
+int hs_edlib_align_bytes(const uint8_t* d_query, const int64_t* h_query_off, const uint8_t* d_target, const int64_t* h_target_off, int32_t n_pairs, int32_t mode,
+                         int32_t task, int32_t k, const hs_equality_pair* h_equalities, int32_t n_equalities, int32_t* d_dist, int32_t* d_start, int32_t* d_end,
+                         int32_t* d_nloc, uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream) {
+    if (int rc = require_device()) return rc;
+    if (n_equalities < 0 || (n_equalities > 0 && !h_equalities)) { set_error("hs_edlib_align_bytes: n_equalities must be >= 0 and h_equalities given with it"); return HS_EINVAL; }
+    if (n_pairs <= 0) return HS_OK;
+    if (!h_query_off || !h_target_off) { set_error("hs_edlib_align_bytes: bad arguments"); return HS_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t q0 = h_query_off[0], t0 = h_target_off[0], nq = h_query_off[n_pairs] - q0, nt = h_target_off[n_pairs] - t0;
+    if (nq < 0 || nt < 0 || (nq > 0 && !d_query) || (nt > 0 && !d_target)) { set_error("hs_edlib_align_bytes: bad arguments"); return HS_EINVAL; }
+    DBuf d_pres, d_map, d_mask, d_sq, d_st;
+    if (int rc = d_pres.alloc(32)) return rc;
+    HS_HIP(hipMemsetAsync(d_pres.p, 0, 32, st));
+    if (nq + nt > 0) {
+        const unsigned nblk = (unsigned)std::min<int64_t>(1024, (nq + nt + 4095) / 4096);
+        hipLaunchKernelGGL(hsdev::k_myers_byte_presence, dim3(nblk), dim3(256), 0, st, d_query + q0, nq, d_target + t0, nt, d_pres.as<uint32_t>());
+        HS_HIP(hipGetLastError());
+    }
+    uint32_t pres[8];
+    if (int rc = d2h_pinned(pres, d_pres.p, sizeof pres, st)) return rc;
+    std::vector<uint8_t> map(256, 0);
+    int sym_of[256], A = 0;
+    for (int b = 0; b < 256; ++b) { sym_of[b] = ((pres[b >> 5] >> (b & 31)) & 1u) ? A++ : -1; if (sym_of[b] >= 0) map[(size_t)b] = (uint8_t)sym_of[b]; }
+    if (A == 0) A = 1;      // (every sequence empty: nothing is compared)
+    const int words = A <= 32 ? 1 : (A + 31) / 32;
+    std::vector<uint32_t> mask((size_t)A * words, 0u);
+    for (int a = 0; a < A; ++a) mask[(size_t)a * words + (a >> 5)] |= 1u << (a & 31);
+    bool extra = false;
+    for (int i = 0; i < n_equalities; ++i) {
+        const int a = sym_of[h_equalities[i].first], b = sym_of[h_equalities[i].second];
+        if (a < 0 || b < 0 || a == b) continue;      // edlib.cpp:75-85: a pair naming a byte outside the alphabet is ignored
+        mask[(size_t)a * words + (b >> 5)] |= 1u << (b & 31); mask[(size_t)b * words + (a >> 5)] |= 1u << (a & 31);
+        extra = true;
+    }
+    MyersEqCall eqs{(A <= 4 && !extra) ? 0 : A <= 16 ? 1 : 2, A, words, nullptr};
+    UploadPack pk;
+    pk.add(map, d_map); pk.add(mask, d_mask);
+    if (int rc = pk.commit(st)) return rc;
+    eqs.d_mask = d_mask.as<uint32_t>();
+    if (int rc = d_sq.alloc((size_t)std::max<int64_t>(nq, 1))) return rc;
+    if (int rc = d_st.alloc((size_t)std::max<int64_t>(nt, 1))) return rc;
+    if (nq > 0) hipLaunchKernelGGL(hsdev::k_myers_compact, dim3((unsigned)std::min<int64_t>(4096, (nq + 1023) / 1024)), dim3(256), 0, st, d_query + q0, nq, d_map.as<uint8_t>(), d_sq.as<uint8_t>());
+    if (nt > 0) hipLaunchKernelGGL(hsdev::k_myers_compact, dim3((unsigned)std::min<int64_t>(4096, (nt + 1023) / 1024)), dim3(256), 0, st, d_target + t0, nt, d_map.as<uint8_t>(), d_st.as<uint8_t>());
+    HS_HIP(hipGetLastError());
+    std::vector<int64_t> qo((size_t)n_pairs + 1), to((size_t)n_pairs + 1);
+    for (int i = 0; i <= n_pairs; ++i) { qo[(size_t)i] = h_query_off[i] - q0; to[(size_t)i] = h_target_off[i] - t0; }
+    const int rc = edlib_align_launch("hs_edlib_align_bytes", d_sq.as<uint8_t>(), qo.data(), d_st.as<uint8_t>(), to.data(), n_pairs, mode, task, k, d_dist, d_start,
+                                      d_end, d_nloc, d_ops, h_ops_off, d_ops_len, stream, &eqs);      // (waits for the stream: the scratch of this scope is free after it)
+    if (rc != HS_OK) stream_wait_quiet(st);      // refused arguments: the pre-passes still run on this scope's scratch
+    return rc;
 }
 
 // edlibAlignmentToCigar (edlib.cpp:299-349): runs of equal move characters, count then character; STANDARD writes '=' and 'X' as 'M'.

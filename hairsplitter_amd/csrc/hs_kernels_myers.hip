@@ -28,7 +28,10 @@
 // optimum above k is reported as edlib reports it (distance -1, no location, no path); steps 2 and 3 are bounded by the distance
 // found, as edlib bounds them, so a pair within k gets the same locations and path as with k = -1.
 // Alignment ops as edlib's: 0 match, 1 insertion (query base without target base), 2 deletion, 3 mismatch.
-// Sequences are 2-bit base codes (A C G T), as everywhere on this path. Included by hs_capi.hip after hs_kernels.hip.
+// Sequences are 2-bit base codes (A C G T), as everywhere on this path -- or, in the table forms of the path kernels
+// (k_myers_hw_path_eq<MODE, TIER>, k_myers_hw_path_grouped_eq<G, MODE, TIER>; hs_edlib_align_bytes), symbols of any byte alphabet
+// with edlib's additionalEqualities: the equality vectors of a block then come from a table in LDS (up to 16 symbols) or in
+// device scratch (up to 256) instead of four registers (MyersEq below). Included by hs_capi.hip after hs_kernels.hip.
 #pragma once
 #define MY_TCHUNK 2048      /* target columns staged in LDS at a time */
 
@@ -37,6 +40,7 @@ namespace hsdev {
 struct MyersSeq {              // a sequence seen forwards or backwards
     const uint8_t* p; int n; bool rev;
     __device__ __forceinline__ int at(int i) const { return (int)(p[rev ? n - 1 - i : i] & 3); }
+    __device__ __forceinline__ int raw(int i) const { return (int)p[rev ? n - 1 - i : i]; }      // a symbol 0 .. A - 1 of the table forms below
     // rows r0 .. r0 + 63 (those below n) as two bit planes: bit k of m0 / m1 = bit 0 / 1 of the code of row r0 + k. Sixteen
     // (unaligned) dword loads in flight; bit b of the four bytes of a dword lands in one nibble through a multiplication whose
     // partial products do not meet (byte i, bit b -> bit 28 + i forwards, 31 - i backwards).
@@ -65,6 +69,33 @@ struct MyersSeq {              // a sequence seen forwards or backwards
         m0 = ((uint64_t)hi0 << 32) | lo0; m1 = ((uint64_t)hi1 << 32) | lo1;
     }
 };
+// Where the equality vectors of a query block live (TIER of the sweeps and of the path kernels):
+//   0  four 2-bit codes, four registers per lane built from two bit planes (planes() above)
+//   1  an alphabet of up to 16 symbols: a table peq[symbol][lane] of 64-bit words in LDS (8 KB per wavefront; the lanes of one
+//      ds_read_b64 are 8 bytes apart within a row of 512 bytes: distinct banks whatever their symbols are)
+//   2  up to 256 symbols: the same table in the call's device scratch, one of n_sym x 64 words per wavefront, read through L2
+// Tiers 1 and 2 take sequences of symbols 0 .. n_sym - 1 (the call's bytes compacted, hs_edlib_align_bytes) and edlib's equality
+// relation (EqualityDefinition, edlib.cpp:61-92: identity + the listed pairs, symmetric, not transitive) as one bit row per
+// symbol: bit b of mask[a * words + (b >> 5)] = symbols a and b are equal. Bit r of peq[s] = areEqual(query[r], s) (buildPeq,
+// :357-380): a lane walks its 64 query symbols and sets bit r in the rows its symbol's mask names.
+struct MyersEq { const uint32_t* mask; int n_sym, words; unsigned long long* gtab; };
+template <int TIER> struct MyersPeqTab { static __device__ __forceinline__ unsigned long long* get(const MyersEq&) { return nullptr; } };
+template <> struct MyersPeqTab<1> {
+    static __device__ __forceinline__ unsigned long long* get(const MyersEq&) { __shared__ unsigned long long s_peq[16 * 64]; return s_peq; }
+};
+template <> struct MyersPeqTab<2> {
+    static __device__ __forceinline__ unsigned long long* get(const MyersEq& eq) { return eq.gtab + (size_t)blockIdx.x * (size_t)eq.n_sym * 64; }
+};
+// this lane's column of the table for the query rows r0 .. r0 + 63 (those below q.n); every lane touches its own column only
+static __device__ __forceinline__ void myers_peq_build(const MyersSeq& q, int r0, const MyersEq& eq, unsigned long long* __restrict__ tab, int lane) {
+    for (int s = 0; s < eq.n_sym; ++s) tab[s * 64 + lane] = 0ull;
+    const int nrow = (q.n - r0) < 64 ? (q.n - r0) : 64;
+    for (int r = 0; r < nrow; ++r) {
+        const uint32_t* m = eq.mask + q.raw(r0 + r) * eq.words;
+        for (int w = 0; w < eq.words; ++w)
+            for (uint32_t x = m[w]; x; x &= x - 1u) tab[((w << 5) + __builtin_ctz(x)) * 64 + lane] |= 1ull << r;
+    }
+}
 // lane i takes the value of lane i - 1 (lane 0: zero): one DPP move across the whole wavefront
 static __device__ __forceinline__ int wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
 
@@ -102,10 +133,12 @@ struct MyersBand {
 // 64-bit words {P, M, score}. col_scores != nullptr: the scores of the LAST column, one int per query row (what Hirschberg's
 // split reads), MY_INF outside the band. out_count != nullptr: how many columns attain the best score, the position before the
 // target included where it takes part (edlib's numLocations, :660-695).
+template <int TIER = 0>
 static __device__ void myers_sweep(const MyersSeq& q, const MyersSeq& t, int mode, MyersBand band, int8_t* __restrict__ hb, int32_t* __restrict__ hbot,
                                    uint8_t* tbuf /* LDS [MY_TCHUNK + 64] */, unsigned long long* __restrict__ store, int32_t* __restrict__ col_scores,
-                                   int& out_score, int& out_best, int& out_first, int& out_last, int* out_count = nullptr) {
+                                   int& out_score, int& out_best, int& out_first, int& out_last, int* out_count = nullptr, const MyersEq& eq = MyersEq()) {
     const int lane = lane_id();
+    unsigned long long* const tab = MyersPeqTab<TIER>::get(eq);
     const int qn = q.n, tn = t.n;
     const int nblocks = (qn + 63) >> 6;
     const int last_row = (qn - 1) & 63;
@@ -129,9 +162,11 @@ static __device__ void myers_sweep(const MyersSeq& q, const MyersSeq& t, int mod
         for (int o = 32; o > 0; o >>= 1) { s_begin = min(s_begin, __shfl_xor(s_begin, o, 64)); s_last = max(s_last, __shfl_xor(s_last, o, 64)); }
         uint64_t peq[4] = {0, 0, 0, 0};
         if (some) {
-            uint64_t m0, m1, valid;
-            q.planes(blk << 6, m0, m1, valid);
-            peq[0] = ~m1 & ~m0 & valid; peq[1] = ~m1 & m0 & valid; peq[2] = m1 & ~m0 & valid; peq[3] = m1 & m0 & valid;
+            if (TIER == 0) {
+                uint64_t m0, m1, valid;
+                q.planes(blk << 6, m0, m1, valid);
+                peq[0] = ~m1 & ~m0 & valid; peq[1] = ~m1 & m0 & valid; peq[2] = m1 & ~m0 & valid; peq[3] = m1 & m0 & valid;
+            } else myers_peq_build(q, blk << 6, eq, tab, lane);
         }
         uint64_t Pv = ~0ull, Mv = 0ull;
         int h_prev = 0;                       // horizontal delta out of the last column done: bit 0 = +1, bit 1 = -1
@@ -143,7 +178,7 @@ static __device__ void myers_sweep(const MyersSeq& q, const MyersSeq& t, int mod
             __builtin_amdgcn_wave_barrier();
             for (int x = lane; x < MY_TCHUNK + 64; x += 64) {
                 const int col = s0 - 63 + x;
-                tbuf[x] = (col >= 0 && col < tn) ? (uint8_t)t.at(col) : (uint8_t)0;
+                tbuf[x] = (col >= 0 && col < tn) ? (uint8_t)(TIER == 0 ? t.at(col) : t.raw(col)) : (uint8_t)0;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
             __builtin_amdgcn_wave_barrier();
@@ -165,8 +200,8 @@ static __device__ void myers_sweep(const MyersSeq& q, const MyersSeq& t, int mod
                         bottom = bot_up - (h_up & 1) + (h_up >> 1) + 64;
                         if (is_last_blk) score = bottom - (63 - last_row);
                     }
-                    const int sym = trow[s] & 3;
-                    uint64_t Eq = peq[sym];
+                    uint64_t Eq;
+                    if (TIER == 0) Eq = peq[trow[s] & 3]; else Eq = tab[(int)trow[s] * 64 + lane];
                     const uint64_t Xv = Eq | Mv;
                     Eq |= (uint64_t)(uint32_t)(h >> 1);
                     const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
@@ -277,9 +312,9 @@ static __device__ __forceinline__ int myers_first_bound(int mode, int qn, int tn
 // that bound, holds it (edlibAlign doubles its bound from 64 instead, :194-214; the answer does not depend on the bounds tried:
 // the first one that holds the optimum returns it exactly). kb >= 0: one sweep in the band of kb (HW: of at most the query
 // length, :566-569); an optimum above kb is d = -1, as is an NW pair whose lengths differ by more than kb (:746-749).
-template <int MODE>
+template <int MODE, int TIER>
 static __device__ void myers_locate(const MyersSeq& q, const MyersSeq& t, int kb, int8_t* __restrict__ hb, int32_t* __restrict__ hbot, uint8_t* tbuf,
-                                    int& d, int& e, int& n) {
+                                    int& d, int& e, int& n, const MyersEq& eq) {
     const int qn = q.n, tn = t.n;
     const int kmax = MODE == 0 ? max(qn, tn) : qn;
     d = -1; e = -1; n = 0;
@@ -287,7 +322,7 @@ static __device__ void myers_locate(const MyersSeq& q, const MyersSeq& t, int kb
     int sc, best, first, last, cnt;
     for (int k = kb >= 0 ? min(kb, kmax) : myers_first_bound(MODE, qn, tn);;) {
         const bool all = k >= kmax;
-        myers_sweep(q, t, MODE, myers_mode_band(MODE, qn, tn, k, all), hb, hbot, tbuf, nullptr, nullptr, sc, best, first, last, &cnt);
+        myers_sweep<TIER>(q, t, MODE, myers_mode_band(MODE, qn, tn, k, all), hb, hbot, tbuf, nullptr, nullptr, sc, best, first, last, &cnt, eq);
         const int got = MODE == 0 ? sc : best;
         if (all || got <= k) { d = got; e = MODE == 0 ? tn - 1 : first; n = MODE == 0 ? 1 : cnt; return; }
         if (kb >= 0) return;
@@ -299,14 +334,16 @@ static __device__ void myers_locate(const MyersSeq& q, const MyersSeq& t, int kb
 #define MY_WAVES_PER_EU 1
 #endif
 // task: 0 distance (no start location), 1 locations, 2 locations and path. kbound < 0: no bound. n_loc may be null.
-template <int MODE>
-__global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
-    const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,
-    const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list, int8_t* __restrict__ hscratch,
-    const int64_t* __restrict__ hscratch_off, unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off,
-    int32_t* __restrict__ col_scratch, int kbound, int task,
-    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc, int32_t* __restrict__ n_loc,
-    uint8_t* __restrict__ ops, const int64_t* __restrict__ ops_off, int32_t* __restrict__ ops_len) {
+#define MY_PATH_PARAMS                                                                                                             \
+    const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,                  \
+    const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list, int8_t* __restrict__ hscratch,       \
+    const int64_t* __restrict__ hscratch_off, unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off,       \
+    int32_t* __restrict__ col_scratch, int kbound, int task,                                                                       \
+    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc, int32_t* __restrict__ n_loc,       \
+    uint8_t* __restrict__ ops, const int64_t* __restrict__ ops_off, int32_t* __restrict__ ops_len
+#define MY_PATH_ARGS query, query_off, target, target_off, pair_ids, n_list, hscratch, hscratch_off, store, store_off, col_scratch, kbound, task, dist, start_loc, end_loc, n_loc, ops, ops_off, ops_len
+template <int MODE, int TIER>
+static __device__ __forceinline__ void myers_path_pair(MY_PATH_PARAMS, const MyersEq& eq) {
     __shared__ uint8_t tbuf[MY_TCHUNK + 64];
     __shared__ int s_stack[40][5];
     const int lane = lane_id();
@@ -330,7 +367,7 @@ __global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
     int sc, best, first, last;
     // 1. distance, first end location, number of end locations
     int d, e, nl;
-    myers_locate<MODE>(MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, kbound, hb, hbot, tbuf, d, e, nl);
+    myers_locate<MODE, TIER>(MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, kbound, hb, hbot, tbuf, d, e, nl, eq);
     if (d < 0) {   // above the bound (:212-215): no location, no path
         if (lane == 0) { dist[pr] = -1; end_loc[pr] = -1; start_loc[pr] = -1; if (n_loc) n_loc[pr] = 0; if (ops_len) ops_len[pr] = 0; }
         return;
@@ -348,7 +385,7 @@ __global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
     // 2. start location -- HW: reversed query against the reversed target prefix [0, e], last best column; NW / SHW: 0 (:263-267)
     int st = 0;
     if (MODE == 2) {
-        myers_sweep(MyersSeq{qp, qn, true}, MyersSeq{tp, e + 1, true}, 1, MyersBand::prefix(d), hb, hbot, tbuf, nullptr, nullptr, sc, best, first, last);
+        myers_sweep<TIER>(MyersSeq{qp, qn, true}, MyersSeq{tp, e + 1, true}, 1, MyersBand::prefix(d), hb, hbot, tbuf, nullptr, nullptr, sc, best, first, last, nullptr, eq);
         st = e - last;
     }
     if (lane == 0) { dist[pr] = d; end_loc[pr] = e; start_loc[pr] = st; }
@@ -377,7 +414,7 @@ __global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
         if (myers_leaf(fqn, ftn)) {                            // :1196-1209: the whole matrix and the traceback
             const int nblocks = (fqn + 63) >> 6;
             const MyersBand band = MyersBand::global(fqn, ftn, fbest);
-            myers_sweep(MyersSeq{qp + fqa, fqn, false}, MyersSeq{tp + fta, ftn, false}, 0, band, hb, hbot, tbuf, sto, nullptr, sc, best, first, last);
+            myers_sweep<TIER>(MyersSeq{qp + fqa, fqn, false}, MyersSeq{tp + fta, ftn, false}, 0, band, hb, hbot, tbuf, sto, nullptr, sc, best, first, last, nullptr, eq);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
             __builtin_amdgcn_wave_barrier();
             int n = 0;
@@ -389,8 +426,8 @@ __global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
         // FIRST query row whose two scores add up to the optimum (:1322-1333), the two boundary rows after it (:1335-1353)
         const int lw = ftn / 2, rw = ftn - lw;
         const MyersBand band = MyersBand::global(fqn, ftn, fbest);      // (of the whole frame: both halves see the same diagonals, the right one mirrored)
-        myers_sweep(MyersSeq{qp + fqa, fqn, false}, MyersSeq{tp + fta, lw, false}, 0, band, hb, hbot, tbuf, nullptr, left, sc, best, first, last);
-        myers_sweep(MyersSeq{qp + fqa, fqn, true}, MyersSeq{tp + fta + lw, rw, true}, 0, band, hb, hbot, tbuf, nullptr, right_rev, sc, best, first, last);
+        myers_sweep<TIER>(MyersSeq{qp + fqa, fqn, false}, MyersSeq{tp + fta, lw, false}, 0, band, hb, hbot, tbuf, nullptr, left, sc, best, first, last, nullptr, eq);
+        myers_sweep<TIER>(MyersSeq{qp + fqa, fqn, true}, MyersSeq{tp + fta + lw, rw, true}, 0, band, hb, hbot, tbuf, nullptr, right_rev, sc, best, first, last, nullptr, eq);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
         __builtin_amdgcn_wave_barrier();
         // left[i]: query[0..i] against the left half; right[i] = right_rev[fqn - 1 - i]: query[i..] against the right half
@@ -422,6 +459,12 @@ __global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
     }
     if (lane == 0) ops_len[pr] = n_out;
 }
+template <int MODE>
+__global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(MY_PATH_PARAMS) { myers_path_pair<MODE, 0>(MY_PATH_ARGS, MyersEq()); }
+template <int MODE, int TIER>      // the table forms: sequences of symbols, equality vectors from eq (MyersEq above)
+__global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path_eq(MY_PATH_PARAMS, MyersEq eq) { myers_path_pair<MODE, TIER>(MY_PATH_ARGS, eq); }
+#undef MY_PATH_PARAMS
+#undef MY_PATH_ARGS
 
 // ---- short queries: G lanes per pair, 64 / G pairs per wavefront ----------------------------------------------------------
 // The stage-5 call sites align 200-300 bases (five 64-row blocks): with a wavefront per pair five lanes of 64 work. Here a pair
@@ -429,11 +472,12 @@ __global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
 // per-pair quantity lives in the lanes of its group, the loops run to the longest pair of the wavefront and a group that is
 // done idles under the exec mask. Same sweeps, same band, same traceback as above.
 #define MY_GCHUNK 1024
-template <int G>
+template <int G, int TIER = 0>
 static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const MyersSeq& t, int mode, MyersBand band, uint8_t* __restrict__ tb /* this group's LDS [MY_GCHUNK + 64] */,
                                            unsigned long long* __restrict__ store, int& out_score, int& out_best, int& out_first, int& out_last,
-                                           int* out_count = nullptr) {
+                                           int* out_count = nullptr, const MyersEq& eq = MyersEq()) {
     const int lane = lane_id(), gl = lane & (G - 1);
+    unsigned long long* const tab = MyersPeqTab<TIER>::get(eq);
     const int qn = q.n, tn = t.n;
     const int nblocks = (qn + 63) >> 6;
     const int last_row = (qn - 1) & 63;
@@ -456,9 +500,11 @@ static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const
     for (int o = 32; o >= G; o >>= 1) n_max = max(n_max, __shfl_xor(n_max, o, 64));
     uint64_t peq[4] = {0, 0, 0, 0};
     if (some) {
-        uint64_t m0, m1, valid;
-        q.planes(blk << 6, m0, m1, valid);
-        peq[0] = ~m1 & ~m0 & valid; peq[1] = ~m1 & m0 & valid; peq[2] = m1 & ~m0 & valid; peq[3] = m1 & m0 & valid;
+        if (TIER == 0) {
+            uint64_t m0, m1, valid;
+            q.planes(blk << 6, m0, m1, valid);
+            peq[0] = ~m1 & ~m0 & valid; peq[1] = ~m1 & m0 & valid; peq[2] = m1 & ~m0 & valid; peq[3] = m1 & m0 & valid;
+        } else myers_peq_build(q, blk << 6, eq, tab, lane);
     }
     uint64_t Pv = ~0ull, Mv = 0ull;
     int h_prev = 0, bottom = (blk + 1) << 6;
@@ -475,7 +521,7 @@ static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const
                     w = t.rev ? __builtin_bswap32(*reinterpret_cast<const u32_unaligned*>(t.p + (tn - 4 - c))) : *reinterpret_cast<const u32_unaligned*>(t.p + c);
                 } else {
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) if (c + b >= 0 && c + b < tn) w |= (uint32_t)t.at(c + b) << (8 * b);
+                    for (int b = 0; b < 4; ++b) if (c + b >= 0 && c + b < tn) w |= (uint32_t)(TIER == 0 ? t.at(c + b) : t.raw(c + b)) << (8 * b);
                 }
                 *reinterpret_cast<uint32_t*>(tb + x) = w;
             }
@@ -498,8 +544,8 @@ static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const
                     bottom = bot_up - (h_up & 1) + (h_up >> 1) + 64;
                     if (is_last_blk) score = bottom - (63 - last_row);
                 }
-                const int sym = trow[i] & 3;
-                uint64_t Eq = peq[sym];
+                uint64_t Eq;
+                if (TIER == 0) Eq = peq[trow[i] & 3]; else Eq = tab[(int)trow[i] * 64 + lane];
                 const uint64_t Xv = Eq | Mv;
                 Eq |= (uint64_t)(uint32_t)(h >> 1);
                 const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
@@ -533,13 +579,15 @@ static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const
     if (out_count) *out_count = __shfl(n_best, owner, 64);
 }
 
-template <int G, int MODE>
-__global__ __launch_bounds__(64) void k_myers_hw_path_grouped(
-    const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,
-    const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list,
-    unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off, int kbound, int task,
-    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc, int32_t* __restrict__ n_loc,
-    uint8_t* __restrict__ ops, const int64_t* __restrict__ ops_off, int32_t* __restrict__ ops_len) {
+#define MY_GROUP_PARAMS                                                                                                            \
+    const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,                  \
+    const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list,                                      \
+    unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off, int kbound, int task,                           \
+    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc, int32_t* __restrict__ n_loc,       \
+    uint8_t* __restrict__ ops, const int64_t* __restrict__ ops_off, int32_t* __restrict__ ops_len
+#define MY_GROUP_ARGS query, query_off, target, target_off, pair_ids, n_list, store, store_off, kbound, task, dist, start_loc, end_loc, n_loc, ops, ops_off, ops_len
+template <int G, int MODE, int TIER>
+static __device__ __forceinline__ void myers_path_groups(MY_GROUP_PARAMS, const MyersEq& eq) {
     constexpr int NG = 64 / G;
     __shared__ __attribute__((aligned(16))) uint8_t tbuf[NG][MY_GCHUNK + 64];
     const int lane = lane_id(), gl = lane & (G - 1), grp = lane / G;
@@ -564,7 +612,7 @@ __global__ __launch_bounds__(64) void k_myers_hw_path_grouped(
     bool pending = act && !(kbound >= 0 && MODE == 0 && kbound < abs(tn - qn));
     while (__ballot(pending) != 0ull) {
         const bool all = k >= kmax;
-        myers_sweep_grouped<G>(pending, MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, MODE, myers_mode_band(MODE, qn, tn, k, all), tb, nullptr, sc, best, first, last, &cnt);
+        myers_sweep_grouped<G, TIER>(pending, MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, MODE, myers_mode_band(MODE, qn, tn, k, all), tb, nullptr, sc, best, first, last, &cnt, eq);
         if (pending) {
             const int got = MODE == 0 ? sc : best;
             if (all || got <= k) { pending = false; d = got; e = MODE == 0 ? tn - 1 : first; nl = MODE == 0 ? 1 : cnt; }
@@ -589,7 +637,7 @@ __global__ __launch_bounds__(64) void k_myers_hw_path_grouped(
     // 2. start location (HW; NW / SHW: 0)
     int st = 0;
     if (MODE == 2) {
-        myers_sweep_grouped<G>(act, MyersSeq{qp, qn, true}, MyersSeq{tp, e + 1, true}, 1, MyersBand::prefix(d), tb, nullptr, sc, best, first, last);
+        myers_sweep_grouped<G, TIER>(act, MyersSeq{qp, qn, true}, MyersSeq{tp, e + 1, true}, 1, MyersBand::prefix(d), tb, nullptr, sc, best, first, last, nullptr, eq);
         st = e - last;
     }
     if (act && gl == 0) { dist[pr] = d; end_loc[pr] = e; start_loc[pr] = st; }
@@ -598,10 +646,36 @@ __global__ __launch_bounds__(64) void k_myers_hw_path_grouped(
     const int an = e - st + 1;
     const MyersBand band = MyersBand::global(qn, an, d);
     unsigned long long* sto = store + (live ? store_off[pr] : 0);
-    myers_sweep_grouped<G>(act, MyersSeq{qp, qn, false}, MyersSeq{tp + st, an, false}, 0, band, tb, sto, sc, best, first, last);
+    myers_sweep_grouped<G, TIER>(act, MyersSeq{qp, qn, false}, MyersSeq{tp + st, an, false}, 0, band, tb, sto, sc, best, first, last, nullptr, eq);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
     __builtin_amdgcn_wave_barrier();
     if (act && gl == 0) ops_len[pr] = myers_traceback(sto, (qn + 63) >> 6, band, qn, an, sc, op);
+}
+template <int G, int MODE>
+__global__ __launch_bounds__(64) void k_myers_hw_path_grouped(MY_GROUP_PARAMS) { myers_path_groups<G, MODE, 0>(MY_GROUP_ARGS, MyersEq()); }
+template <int G, int MODE, int TIER>
+__global__ __launch_bounds__(64) void k_myers_hw_path_grouped_eq(MY_GROUP_PARAMS, MyersEq eq) { myers_path_groups<G, MODE, TIER>(MY_GROUP_ARGS, eq); }
+#undef MY_GROUP_PARAMS
+#undef MY_GROUP_ARGS
+
+// ---- the pre-passes of the table forms (hs_edlib_align_bytes; transformSequences, edlib.cpp:1422-1460, once per call) ----------
+// which of the 256 byte values the call's sequences hold: bit b of present[b >> 5]
+__global__ __launch_bounds__(256) void k_myers_byte_presence(const uint8_t* __restrict__ a, int64_t na, const uint8_t* __restrict__ b, int64_t nb, uint32_t* __restrict__ present) {
+    __shared__ uint32_t s_pres[8];
+    if (threadIdx.x < 8) s_pres[threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < na + nb; i += stride) {
+        const uint32_t v = i < na ? a[i] : b[i - na];
+        if (!((s_pres[v >> 5] >> (v & 31)) & 1u)) atomicOr(&s_pres[v >> 5], 1u << (v & 31));
+    }
+    __syncthreads();
+    if (threadIdx.x < 8 && s_pres[threadIdx.x]) atomicOr(&present[threadIdx.x], s_pres[threadIdx.x]);
+}
+// bytes -> symbols 0 .. A - 1 through the call's map
+__global__ __launch_bounds__(256) void k_myers_compact(const uint8_t* __restrict__ src, int64_t n, const uint8_t* __restrict__ map, uint8_t* __restrict__ dst) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = map[src[i]];
 }
 
 

@@ -9,7 +9,8 @@
 // equality: 'N' only matches 'N', 'a' is not 'A'), the kernel compares codes 0..3; distance and path only depend on which
 // positions are equal, so every pair gets its own bijection from the bytes it contains to the codes -- exact for any pair with at
 // most four distinct bytes (ACGT in either case, ACG + N, ...). A pair with more than four (ACGT + N) is an error (HS_EFORMAT),
-// not an approximation.
+// not an approximation. hs_reattach_ends_bytes / hs_trim_polished_bytes are the same host code around hs_edlib_align_bytes, which
+// compares the bytes themselves (any alphabet: N runs, soft-masked lower case, IUPAC codes) and refuses nothing.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -45,7 +46,7 @@ bool encode_pair(const std::string& q, const std::string& t, uint8_t* cq, uint8_
 }
 
 // edlibAlign(query, target, HW, k = -1, TASK_PATH) for every pair
-int align_all(const std::vector<std::string>& q, const std::vector<std::string>& t, bool path, std::vector<Aln>& out) {
+int align_all(const std::vector<std::string>& q, const std::vector<std::string>& t, bool path, bool bytes, std::vector<Aln>& out) {
     const int n = (int)q.size();
     out.assign((size_t)n, Aln());
     if (n == 0) return HS_OK;
@@ -53,7 +54,10 @@ int align_all(const std::vector<std::string>& q, const std::vector<std::string>&
     for (int i = 0; i < n; ++i) { qo[(size_t)i + 1] = qo[(size_t)i] + (int64_t)q[(size_t)i].size(); to[(size_t)i + 1] = to[(size_t)i] + (int64_t)t[(size_t)i].size(); oo[(size_t)i + 1] = oo[(size_t)i] + (int64_t)(q[(size_t)i].size() + t[(size_t)i].size()); }
     std::vector<uint8_t> hq((size_t)qo.back() + 1), ht((size_t)to.back() + 1);
     for (int i = 0; i < n; ++i)
-        if (!encode_pair(q[(size_t)i], t[(size_t)i], hq.data() + qo[(size_t)i], ht.data() + to[(size_t)i])) {
+        if (bytes) {
+            std::memcpy(hq.data() + qo[(size_t)i], q[(size_t)i].data(), q[(size_t)i].size());
+            std::memcpy(ht.data() + to[(size_t)i], t[(size_t)i].data(), t[(size_t)i].size());
+        } else if (!encode_pair(q[(size_t)i], t[(size_t)i], hq.data() + qo[(size_t)i], ht.data() + to[(size_t)i])) {
             hs::set_error("stage 5 alignment " + std::to_string(i) + ": more than four distinct bytes in one query / target pair (edlib compares bytes; this path has four codes)");
             return HS_EFORMAT;
         }
@@ -68,8 +72,11 @@ int align_all(const std::vector<std::string>& q, const std::vector<std::string>&
     if (path) { if (int rc = dev.alloc(&dops, (size_t)oo.back() + 1)) return rc; }
     if (int rc = hs_memcpy_h2d(dq, hq.data(), hq.size())) return rc;
     if (int rc = hs_memcpy_h2d(dt, ht.data(), ht.size())) return rc;
-    if (int rc = hs_edlib_hw_align((const uint8_t*)dq, qo.data(), (const uint8_t*)dt, to.data(), n, (int32_t*)dd, (int32_t*)ds, (int32_t*)de, (uint8_t*)dops,
-                                   oo.data(), (int32_t*)dl, nullptr)) return rc;
+    if (bytes) {
+        if (int rc = hs_edlib_align_bytes((const uint8_t*)dq, qo.data(), (const uint8_t*)dt, to.data(), n, 2, path ? 2 : 1, -1, nullptr, 0, (int32_t*)dd, (int32_t*)ds,
+                                          (int32_t*)de, nullptr, (uint8_t*)dops, oo.data(), (int32_t*)dl, nullptr)) return rc;
+    } else if (int rc = hs_edlib_hw_align((const uint8_t*)dq, qo.data(), (const uint8_t*)dt, to.data(), n, (int32_t*)dd, (int32_t*)ds, (int32_t*)de, (uint8_t*)dops,
+                                          oo.data(), (int32_t*)dl, nullptr)) return rc;
     std::vector<int32_t> hd((size_t)n), hs_((size_t)n), he((size_t)n), hl((size_t)n, 0);
     if (int rc = hs_memcpy_d2h(hd.data(), dd, (size_t)n * 4)) return rc;
     if (int rc = hs_memcpy_d2h(hs_.data(), ds, (size_t)n * 4)) return rc;
@@ -100,20 +107,18 @@ std::string substr_like_std(const std::string& s, long pos, long len) {   // std
     return s.substr((size_t)pos, (size_t)len);
 }
 
-}  // namespace
-
-extern "C" int hs_reattach_ends(const char* const* backbone, const char* const* consensus, int32_t n, char*** out) {
-    if (n < 0 || !out || (n && (!backbone || !consensus))) { hs::set_error("hs_reattach_ends: bad arguments"); return HS_EINVAL; }
+int reattach_ends(const char* who, bool bytes, const char* const* backbone, const char* const* consensus, int32_t n, char*** out) {
+    if (n < 0 || !out || (n && (!backbone || !consensus))) { hs::set_error(std::string(who) + ": bad arguments"); return HS_EINVAL; }
     std::vector<std::string> q, t;
     for (int i = 0; i < n; ++i) {
         const std::string b = backbone[i], c = consensus[i];
-        if (b.empty() || c.empty()) { hs::set_error("hs_reattach_ends: empty sequence (the reference returns the backbone before it gets here)"); return HS_EINVAL; }
+        if (b.empty() || c.empty()) { hs::set_error(std::string(who) + ": empty sequence (the reference returns the backbone before it gets here)"); return HS_EINVAL; }
         const size_t before = std::min<size_t>(300, b.size()), after = std::min<size_t>(200, c.size());      // tools.cpp:508-509
         q.push_back(c.substr(0, after)); t.push_back(b.substr(0, before));                                   // :512-516
         q.push_back(c.substr(c.size() - after, after)); t.push_back(b.substr(b.size() - before, before));    // :525-529
     }
     std::vector<Aln> al;
-    if (int rc = align_all(q, t, false, al)) return rc;
+    if (int rc = align_all(q, t, false, bytes, al)) return rc;
     std::vector<std::string> res((size_t)n);
     for (int i = 0; i < n; ++i) {
         const std::string& bs = t[(size_t)2 * i]; const std::string& be = t[(size_t)2 * i + 1];
@@ -125,21 +130,21 @@ extern "C" int hs_reattach_ends(const char* const* backbone, const char* const* 
     return HS_OK;
 }
 
-extern "C" int hs_trim_polished(const char* const* to_polish, const char* const* newcontig, const int32_t* overhang_left, const int32_t* overhang_right,
-                                int32_t n, char*** out) {
-    if (n < 0 || !out || (n && (!to_polish || !newcontig || !overhang_left || !overhang_right))) { hs::set_error("hs_trim_polished: bad arguments"); return HS_EINVAL; }
+int trim_polished(const char* who, bool bytes, const char* const* to_polish, const char* const* newcontig, const int32_t* overhang_left, const int32_t* overhang_right,
+                  int32_t n, char*** out) {
+    if (n < 0 || !out || (n && (!to_polish || !newcontig || !overhang_left || !overhang_right))) { hs::set_error(std::string(who) + ": bad arguments"); return HS_EINVAL; }
     std::vector<std::string> q, t;
     std::vector<int> begin_of_end((size_t)n);
     for (int i = 0; i < n; ++i) {
         const std::string tp = to_polish[i], nc = newcontig[i];
-        if (tp.empty() || nc.empty()) { hs::set_error("hs_trim_polished: empty sequence"); return HS_EINVAL; }
+        if (tp.empty() || nc.empty()) { hs::set_error(std::string(who) + ": empty sequence"); return HS_EINVAL; }
         q.push_back(tp.substr(0, (size_t)std::max(300, overhang_left[i] * 2))); t.push_back(nc);             // create_new_contigs.cpp:559
         const int boe = std::max(0, std::min((int)tp.size() - overhang_right[i] * 2, (int)tp.size() - 300)); // :594
         begin_of_end[(size_t)i] = boe;
         q.push_back(tp.substr((size_t)boe, tp.size() - (size_t)boe)); t.push_back(nc);                      // :595
     }
     std::vector<Aln> al;
-    if (int rc = align_all(q, t, true, al)) return rc;
+    if (int rc = align_all(q, t, true, bytes, al)) return rc;
     std::vector<std::string> res((size_t)n);
     for (int i = 0; i < n; ++i) {
         const std::string tp = to_polish[i], nc = newcontig[i];
@@ -162,6 +167,23 @@ extern "C" int hs_trim_polished(const char* const* to_polish, const char* const*
     }
     *out = to_c_strings(res);
     return HS_OK;
+}
+
+}  // namespace
+
+extern "C" int hs_reattach_ends(const char* const* backbone, const char* const* consensus, int32_t n, char*** out) {
+    return reattach_ends("hs_reattach_ends", false, backbone, consensus, n, out);
+}
+extern "C" int hs_reattach_ends_bytes(const char* const* backbone, const char* const* consensus, int32_t n, char*** out) {      // tools.cpp:505-536
+    return reattach_ends("hs_reattach_ends_bytes", true, backbone, consensus, n, out);
+}
+extern "C" int hs_trim_polished(const char* const* to_polish, const char* const* newcontig, const int32_t* overhang_left, const int32_t* overhang_right,
+                                int32_t n, char*** out) {
+    return trim_polished("hs_trim_polished", false, to_polish, newcontig, overhang_left, overhang_right, n, out);
+}
+extern "C" int hs_trim_polished_bytes(const char* const* to_polish, const char* const* newcontig, const int32_t* overhang_left,      // create_new_contigs.cpp:556-629
+                                      const int32_t* overhang_right, int32_t n, char*** out) {
+    return trim_polished("hs_trim_polished_bytes", true, to_polish, newcontig, overhang_left, overhang_right, n, out);
 }
 
 extern "C" void hs_free_strings(char** s, int32_t n) {

@@ -260,6 +260,20 @@ int hs_edlib_align(const uint8_t* d_query, const int64_t* h_query_off, const uin
                    int32_t n_pairs, int32_t mode, int32_t task, int32_t k,
                    int32_t* d_dist, int32_t* d_start, int32_t* d_end, int32_t* d_nloc,
                    uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream);
+/* edlibAlign(query, target, edlibNewAlignConfig(k, mode, task, equalities, n_equalities)) on raw bytes 0..255: any alphabet edlib
+ * accepts (up to 256 distinct bytes) with its additionalEqualities (edlib.h:92-95, EqualityDefinition edlib.cpp:61-92: every byte
+ * equals itself and the listed pairs are equal both ways; the relation need not be transitive; a pair naming a byte that occurs
+ * in neither sequence changes nothing). The bytes the call's sequences hold are compacted to symbols once per call
+ * (transformSequences, edlib.cpp:1422-1460) and the equality vectors of a query block (buildPeq, :357-380) come from a table: in
+ * LDS up to 16 symbols, in device scratch up to 256; a call with at most four symbols and no equality among them runs on the
+ * four-code kernels. h_equalities is a HOST array (NULL / 0: bytes equal themselves only). Outputs, empty-sequence behaviour,
+ * error codes and synchronisation as hs_edlib_align; n_equalities < 0, or h_equalities == NULL with n_equalities > 0: HS_EINVAL. */
+typedef struct hs_equality_pair { uint8_t first, second; } hs_equality_pair;   /* == EdlibEqualityPair (edlib.h:92-95) */
+int hs_edlib_align_bytes(const uint8_t* d_query, const int64_t* h_query_off, const uint8_t* d_target, const int64_t* h_target_off,
+                         int32_t n_pairs, int32_t mode, int32_t task, int32_t k,
+                         const hs_equality_pair* h_equalities, int32_t n_equalities,
+                         int32_t* d_dist, int32_t* d_start, int32_t* d_end, int32_t* d_nloc,
+                         uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream);
 /* edlibAlignmentToCigar on host: format 0 STANDARD (M I D), 1 EXTENDED (= X I D); returns a malloc'd string (hs_free_host).
  * An empty alignment gives "". */
 int hs_alignment_to_cigar(const uint8_t* ops, int32_t n_ops, int32_t format, char** out);
@@ -277,11 +291,18 @@ int hs_realign_paf(const char* gfa, const char* reads, const char* paf, const ch
 /* The two stage-5 computations that sit on those edlib calls, batched (two alignments per item in ONE hs_edlib_hw_align call):
  * hs_reattach_ends == tools.cpp:505-536 (the ends of the backbone that racon dropped are attached to the consensus again),
  * hs_trim_polished == create_new_contigs.cpp:556-629 (the overhangs the piece was polished with are cut off the polished
- * sequence through the alignment path of the piece's ends). Strings are NUL-terminated ACGT; *out = n malloc'ed strings,
+ * sequence through the alignment path of the piece's ends). Strings are NUL-terminated, at most four distinct bytes per aligned
+ * pair (HS_EFORMAT otherwise; the _bytes forms below take any); *out = n malloc'ed strings,
  * released with hs_free_strings. */
 int hs_reattach_ends(const char* const* backbone, const char* const* consensus, int32_t n, char*** out);
 int hs_trim_polished(const char* const* to_polish, const char* const* newcontig, const int32_t* overhang_left, const int32_t* overhang_right,
                      int32_t n, char*** out);
+/* The same two computations (tools.cpp:505-536, create_new_contigs.cpp:556-629) through hs_edlib_align_bytes (HW, k = -1, no
+ * equalities, as the reference calls edlib): any bytes -- N runs, soft-masked lower case, IUPAC codes -- compared as edlib
+ * compares them. They never refuse an alphabet; everything else as the two calls above. */
+int hs_reattach_ends_bytes(const char* const* backbone, const char* const* consensus, int32_t n, char*** out);
+int hs_trim_polished_bytes(const char* const* to_polish, const char* const* newcontig, const int32_t* overhang_left,
+                           const int32_t* overhang_right, int32_t n, char*** out);
 void hs_free_strings(char** s, int32_t n);
 
 /* ------------------------------------------------------------------------------------------------

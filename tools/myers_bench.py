@@ -6,7 +6,12 @@ deletions inside target_len bases): the banded sweeps and Hirschberg's cuts, one
 Usage: python tools/myers_bench.py [n_pairs=20000] [target_len=2000] [query_len=300]     (prints one JSON line)
        python tools/myers_bench.py nw [n_pairs=2048] [read_len=10000]: hs_edlib_align NW TASK_PATH of reads against a copy with
        ~6 % edits (edlib's default mode; these pairs go through Hirschberg's cuts), with k = -1 and with k = the largest distance
-       of the batch (every pair within the bound: the same results, the first sweep's band sized from k)."""
+       of the batch (every pair within the bound: the same results, the first sweep's band sized from k).
+       python tools/myers_bench.py bytes [n_pairs=2048] [read_len=10000] [n_symbols=5]: the pairs of the nw leg through
+       hs_edlib_align (four codes), the same pairs as bytes with 1 % of the bases replaced by N through hs_edlib_align_bytes
+       without equalities, and the same with N = A, C, G, T: pairs/s of each and the two ratios to the four-code run. With
+       n_symbols above 5 the replaced bases become bytes outside ACGT drawn from n_symbols - 4 values (17 and more: the scratch
+       table instead of the LDS table; the equalities then make the first of them equal to every base)."""
 import ctypes as C
 import json
 import os
@@ -20,11 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def nw_paths(n, rl):
-    import torch
-    from hairsplitter_amd import api
-    api.require_gpu()
-    lib = api.load()
+def nw_pairs(n, rl):
     rng = np.random.default_rng(10)
     qs, ts = [], []
     for _ in range(n):
@@ -37,6 +38,62 @@ def nw_paths(n, rl):
         keep = np.insert(~((u >= 0.04) & (u < 0.06)), ins, True)
         t = np.insert(t, ins, rng.integers(0, 4, size=len(ins), dtype=np.uint8))[keep]
         qs.append(q); ts.append(t)
+    return qs, ts
+
+
+def bytes_paths(n, rl, n_symbols):
+    import torch
+    from hairsplitter_amd import api
+    api.require_gpu()
+    lib = api.load()
+    qs, ts = nw_pairs(n, rl)
+    qo = np.zeros(n + 1, np.int64); to = np.zeros(n + 1, np.int64)
+    np.cumsum([len(x) for x in qs], out=qo[1:]); np.cumsum([len(x) for x in ts], out=to[1:])
+    oo = qo + to
+    codes_q, codes_t = np.concatenate(qs), np.concatenate(ts)
+    rng = np.random.default_rng(11)
+    others = np.array(([ord("N")] + [b for b in range(256) if b not in b"ACGTN"])[:max(1, n_symbols - 4)], dtype=np.uint8)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+    def with_others(codes):      # identical lengths and edit positions: 1 % of the bases become bytes outside ACGT
+        s = acgt[codes].copy()
+        hit = rng.random(len(s)) < 0.01
+        s[hit] = rng.choice(others, size=int(hit.sum()))
+        return s
+    bq, bt = with_others(codes_q), with_others(codes_t)
+    eq = np.array([[ord("N"), b] for b in b"ACGT"], dtype=np.uint8)
+    dev = "cuda:0"
+    dd = torch.zeros(n, dtype=torch.int32, device=dev); ds, de, dn, dl = (torch.zeros_like(dd) for _ in range(4))
+    dops = torch.zeros(int(oo[-1]), dtype=torch.uint8, device=dev)
+    hp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    out = {"mode": "NW", "task": "path", "pairs": n, "read_len": rl, "n_symbols": int(len(set(bq.tolist()) | set(bt.tolist())))}
+    for label, q, t, e in (("four_codes", codes_q, codes_t, None), ("bytes", bq, bt, 0), ("bytes_N_equals_ACGT", bq, bt, len(eq))):
+        dq = torch.from_numpy(q).to(dev); dt = torch.from_numpy(t).to(dev)
+        tail = (api._p(dd), api._p(ds), api._p(de), api._p(dn), api._p(dops), hp(oo), api._p(dl), C.c_void_p(0))
+        times = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if e is None:
+                api._check(lib.hs_edlib_align(api._p(dq), hp(qo), api._p(dt), hp(to), C.c_int32(n), C.c_int32(0), C.c_int32(2), C.c_int32(-1), *tail))
+            else:
+                api._check(lib.hs_edlib_align_bytes(api._p(dq), hp(qo), api._p(dt), hp(to), C.c_int32(n), C.c_int32(0), C.c_int32(2), C.c_int32(-1),
+                                                    eq.ctypes.data_as(C.POINTER(C.c_uint8)) if e else None, C.c_int32(e), *tail))
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        best = min(times[1:])
+        out[label] = {"seconds": best, "pairs_per_s": n / best, "distance_mean": float(dd.float().mean().item())}
+    for label in ("bytes", "bytes_N_equals_ACGT"):
+        out[label]["ratio_to_four_codes"] = out[label]["pairs_per_s"] / out["four_codes"]["pairs_per_s"]
+    print(json.dumps(out))
+
+
+def nw_paths(n, rl):
+    import torch
+    from hairsplitter_amd import api
+    api.require_gpu()
+    lib = api.load()
+    qs, ts = nw_pairs(n, rl)
     qo = np.zeros(n + 1, np.int64); to = np.zeros(n + 1, np.int64)
     np.cumsum([len(x) for x in qs], out=qo[1:]); np.cumsum([len(x) for x in ts], out=to[1:])
     oo = qo + to
@@ -73,6 +130,9 @@ def nw_paths(n, rl):
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "nw":
         return nw_paths(int(sys.argv[2]) if len(sys.argv) > 2 else 2048, int(sys.argv[3]) if len(sys.argv) > 3 else 10000)
+    if len(sys.argv) > 1 and sys.argv[1] == "bytes":
+        return bytes_paths(int(sys.argv[2]) if len(sys.argv) > 2 else 2048, int(sys.argv[3]) if len(sys.argv) > 3 else 10000,
+                           int(sys.argv[4]) if len(sys.argv) > 4 else 5)
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
     tl = int(sys.argv[2]) if len(sys.argv) > 2 else 2000
     import torch
