@@ -19,6 +19,7 @@
 // second count is >= 5 can ever be rescued -- exactly the columns the device already extracted.
 #include "hs_host.h"
 #include "hs_rh8.h"
+#include "hs_rules.h"
 
 #include <algorithm>
 #include <atomic>
@@ -138,45 +139,15 @@ float mean_distance_from_counts(int64_t n_err, int64_t n_len) {
 }
 
 
-// most frequent non-reference code among `codes` restricted to the entries flagged in `take`
-// (first in robin_hood iteration order on ties: call_variants.cpp:837-844, Partition.cpp:59-66).
-// `signed_ref_quirk`: in distance() the reference compares a *signed* char with unsigned keys (:838), so a
-// reference code >= 128 never equals any key and stays eligible.
-// decision half of second_most_frequent(): `seen` = distinct codes in first-appearance order with their counts
+// hs::second_from_seen (hs_rules.h) with the hash-map emulator and its order buffer on the stack
 static uint8_t second_from_seen(const uint8_t* seen, const int* cnt, int nseen, uint8_t ref, bool signed_ref_quirk, bool insert_ref_last,
                                 uint8_t dflt) {
-    if (nseen == 0) return dflt;
-    const bool ref_eligible = signed_ref_quirk && ref >= 128;
-    int best = -1, nbest = 0;
-    uint8_t bestk = dflt;
-    bool ref_seen = false;
-    for (int i = 0; i < nseen; ++i) {
-        const uint8_t k = seen[i];
-        if (k == ref) { ref_seen = true; if (!ref_eligible) continue; }
-        if (cnt[i] > best) { best = cnt[i]; nbest = 1; bestk = k; }
-        else if (cnt[i] == best) nbest++;
-    }
-    if (ref_eligible && !ref_seen && insert_ref_last) {   // content2[ref_base] inserts a zero-count key
-        if (0 > best) { best = 0; nbest = 1; bestk = ref; } else if (best == 0) nbest++;
-    }
-    if (best < 0) return dflt;
-    if (nbest == 1) return bestk;
-    // tie: the winner is the first of the tied keys in the hash map's iteration order
     Rh8 rh; rh.clear();
-    for (int i = 0; i < nseen; ++i) rh.insert(seen[i]);
-    if (insert_ref_last) rh.insert(ref);
     uint8_t ord[260];
-    const int m = rh.order(ord);
-    for (int i = 0; i < m; ++i) {
-        const uint8_t k = ord[i];
-        if (k == ref && !ref_eligible) continue;
-        int c = 0;
-        for (int j = 0; j < nseen; ++j) if (seen[j] == k) { c = cnt[j]; break; }
-        if (c == best) return k;
-    }
-    return bestk;
+    return (uint8_t)second_from_seen(rh, ord, seen, cnt, nseen, ref, signed_ref_quirk, insert_ref_last, dflt);
 }
 
+// most frequent non-reference code among `codes` restricted to the entries flagged in `take`
 static uint8_t second_most_frequent(const uint8_t* code, int n, const uint8_t* take, uint8_t ref, bool signed_ref_quirk,
                                     bool insert_ref_last, uint8_t dflt) {
     // distinct codes in first-appearance order with their counts (a column carries a dozen codes at most: linear search)
@@ -398,23 +369,7 @@ static Contingency column_vs_partition_bits(const RankPartition& p, const ColVie
     return r;
 }
 
-// computeChiSquare: call_variants.cpp:1135-1163 (float marginals, double squares, float result)
-static float chi_square(const Contingency& d) {
-    const int n = d.n00 + d.n01 + d.n10 + d.n11;
-    if (n == 0) return 0;
-    const float pmax1 = float(d.n10 + d.n11) / n;
-    const float pmax2 = float(d.n01 + d.n11) / n;
-    if (pmax1 * (1 - pmax1) == 0 && pmax2 * (1 - pmax2) == 0) return -1;
-    if (pmax1 * pmax2 * (1 - pmax1) * (1 - pmax2) == 0) return 0;
-    const float e00 = (1 - pmax1) * (1 - pmax2) * n, e01 = (1 - pmax1) * pmax2 * n;
-    const float e10 = pmax1 * (1 - pmax2) * n, e11 = pmax1 * pmax2 * n;
-    const double d00 = (double)(float)(d.n00 - e00), d01 = (double)(float)(d.n01 - e01);
-    const double d10 = (double)(float)(d.n10 - e10), d11 = (double)(float)(d.n11 - e11);
-    return (float)(d00 * d00 / (double)e00 + d01 * d01 / (double)e01 + d10 * d10 / (double)e10 + d11 * d11 / (double)e11);
-}
-
-
-// chi_square(d) > 15 for a table whose margins are known to be neither empty nor full: N (ad - bc)^2 / (r1 r2 c1 c2) in double decides unless
+// hs::chi_square (hs_rules.h) > 15 for a table whose margins are known to be neither empty nor full: N (ad - bc)^2 / (r1 r2 c1 c2) in double decides unless
 // it comes within 0.05 of the threshold, then the reference's own sequence of float and double operations does
 static inline bool chi_square_above_15(const Contingency& d) {
     const double n = (double)(d.n00 + d.n01 + d.n10 + d.n11);
@@ -426,7 +381,7 @@ static inline bool chi_square_above_15(const Contingency& d) {
         if (chi > 15.05) return true;
         if (chi < 14.95) return false;
     }
-    return chi_square(d) > 15;
+    return chi_square(d.n00, d.n01, d.n10, d.n11) > 15;
 }
 
 // Partition::Partition(Column&, pos, ref_base): Partition.cpp:32-83
@@ -734,7 +689,7 @@ void cv_phase_a_host(CvContigState& st, const CandidateSet& cs, const int32_t* r
                     // the bit-set form leaves the counts at zero where they cannot matter (few shared reads): the entry walk must
                     // then say "no correlation, no fit" as well
                     const int ec = e.n00 + e.n11 + e.n01 + e.n10;
-                    const bool e_corr = e.n00 + e.n01 > 0.1 * ec && e.n00 + e.n01 < 0.9 * ec && e.n01 + e.n11 > 0.1 * ec && e.n01 + e.n11 < 0.9 * ec && chi_square(e) > 15;
+                    const bool e_corr = e.n00 + e.n01 > 0.1 * ec && e.n00 + e.n01 < 0.9 * ec && e.n01 + e.n11 > 0.1 * ec && e.n01 + e.n11 < 0.9 * ec && chi_square(e.n00, e.n01, e.n10, e.n11) > 15;
                     const bool e_enough = (size_t)ec >= (size_t)n / 2;
                     const bool e_fit = (e.n01 <= std::max(0.1 * (e.n00 + e.n01), 1.0) && e.n10 < std::max(0.1 * (e.n11 + e.n10), 1.0) && e_enough)
                                        || (e.n00 <= std::max(0.1 * (e.n00 + e.n01), 1.0) && e.n11 < std::max(0.1 * (e.n11 + e.n10), 1.0) && e_enough);

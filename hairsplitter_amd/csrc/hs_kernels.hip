@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include "hs_device.h"
 #include "hs_rh8.h"
+#include "hs_rules.h"
 
 namespace hsdev {
 
@@ -45,14 +46,35 @@ static __device__ __forceinline__ int wave_max_i32(int v) {
     return __builtin_amdgcn_readlane(v, 63);
 }
 static __device__ __forceinline__ int wave_sum_i32(int v) { return __builtin_amdgcn_readlane(wave_scan_incl(v), 63); }
-// value of the lane to the left (lane 0 receives `fill`)
-static __device__ __forceinline__ int wave_shr1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }
+static __device__ __forceinline__ int wave_or_i32(int v) {
+    v |= __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
+    v |= __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
+    v |= __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
+    v |= __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
+    v |= __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
+    v |= __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
+    return __builtin_amdgcn_readlane(v, 63);
+}
+static __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) {
+    unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+#define HS_OR_STEP(ctrl, rm) lo |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, ctrl, rm, 0xf, false); hi |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, ctrl, rm, 0xf, false);
+    HS_OR_STEP(0x111, 0xf) HS_OR_STEP(0x112, 0xf) HS_OR_STEP(0x114, 0xf) HS_OR_STEP(0x118, 0xf) HS_OR_STEP(0x142, 0xa) HS_OR_STEP(0x143, 0xc)
+#undef HS_OR_STEP
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)hi, 63) << 32) | (unsigned)__builtin_amdgcn_readlane((int)lo, 63);
+}
+// v_readlane of a 64-bit value (l wave-uniform)
+static __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(v & 0xffffffffull), l);
+}
+// lane i takes the value of lane i - 1 (lane 0 receives `fill`): one DPP move across the whole wavefront
+static __device__ __forceinline__ int wave_shr1(int v, int fill = 0) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }
 // x clamped into [0, hi] (hi >= 0, wave-uniform): one v_med3_i32
 static __device__ __forceinline__ int clamp_i32(int x, int hi) {
     int r;
     asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "s"(hi));
     return r;
 }
+// LDS writes of the wavefront made visible to its own lanes: fence + wave barrier (no s_barrier: one wavefront owns the data)
 static __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -729,8 +751,7 @@ static __device__ __forceinline__ void column_stats_tiled_dw_body(
             const int k0 = 33 + (int)(K0 & 255u), k1 = 33 + (int)(K1 & 255u);
             const bool tie = n0 == n1 || n1 == n2 || n1 == 0;
             const bool gt5 = n1 > 5 * n2;
-            // call_variants.cpp:527-528 / :751-752 on the raw code bytes
-            const bool central = k0 % 5 != k1 % 5 && ((k1 - 33) % 5 != 4 || (k1 / 5 % 5 != k0 % 5 && k1 / 25 % 5 != k0 % 5));
+            const bool central = hs::central_base_test(k0, k1);
             // the selection itself (second count above the floor, or exactly at it with no third allele: column_stats_tail), then what the path reads
             const bool chosen = n1 > min_second || (n1 == min_second && n2 == 0);
             const bool keep = item < n_sel && chosen && (tie || (central && (n1 >= 5 || gt5)));
@@ -1087,42 +1108,12 @@ __global__ __launch_bounds__(256) void k_simdiff_windows(
 //  * second allele = most frequent non-reference code; ties go to the first key in the reference's hash-map iteration
 //    order (hs_rh8.h emulator, run by one lane, rare). A reference code >= 128 never equals a key in the reference's
 //    signed/unsigned comparison (:838) and then competes as well.
-//  * chi-square with the reference's operation types (float marginals, double squares, float result); hipcc is run
-//    with -ffp-contract=off and IEEE division so the bits match the host.
+//  * chi-square is hs::chi_square (hs_rules.h); hipcc is run with -ffp-contract=off and IEEE division so the bits match the host.
 // keep[col] = 1 if the column is kept by loop C (candidates) or rescued by loop D (second count >= 5 + byte predicate).
 // ------------------------------------------------------------------------------------------------
 struct Table2x2 { int n00, n01, n10, n11; };
 
-static __device__ __forceinline__ float chi_square_dev(const Table2x2& d) {
-    const int n = d.n00 + d.n01 + d.n10 + d.n11;
-    if (n == 0) return 0;
-    const float pmax1 = float(d.n10 + d.n11) / n;
-    const float pmax2 = float(d.n01 + d.n11) / n;
-    if (pmax1 * (1 - pmax1) == 0 && pmax2 * (1 - pmax2) == 0) return -1;
-    if (pmax1 * pmax2 * (1 - pmax1) * (1 - pmax2) == 0) return 0;
-    const float e00 = (1 - pmax1) * (1 - pmax2) * n, e01 = (1 - pmax1) * pmax2 * n;
-    const float e10 = pmax1 * (1 - pmax2) * n, e11 = pmax1 * pmax2 * n;
-    const double d00 = (double)(float)(d.n00 - e00), d01 = (double)(float)(d.n01 - e01);
-    const double d10 = (double)(float)(d.n10 - e10), d11 = (double)(float)(d.n11 - e11);
-    return (float)(d00 * d00 / (double)e00 + d01 * d01 / (double)e01 + d10 * d10 / (double)e10 + d11 * d11 / (double)e11);
-}
-
-static __device__ __forceinline__ bool central_base_test_dev(int k0, int k1) {
-    // call_variants.cpp:527-528 and :751-752 (same predicate on raw code bytes)
-    return k0 % 5 != k1 % 5 && ((k1 - '!') % 5 != 4 || (k1 / 5 % 5 != k0 % 5 && k1 / 25 % 5 != k0 % 5));
-}
-
 // the 2x2 table of one column against one partition; wave-uniform result
-// place of a byte key in the iteration order of the reference's hash map while it has at most 12 keys (tests/harness/rh8_static_order.cpp): up to 6
-// keys 8 buckets and the first multiplier, 7 to 12 keys (`wide`) 16 buckets and the second one; rank = home bucket << 5 | 31 - low five hash bits
-static __device__ __forceinline__ int rh8_rank_dev(int key, bool wide) {
-    unsigned long long x = (unsigned long long)(key & 255);
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33;
-    x *= wide ? (0xc4ceb9fe1a85ec53ull + 0xc4ceb9fe1a85ec54ull) : 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return (int)((((x >> 5) & (wide ? 15ull : 7ull)) << 5) | (31ull - (x & 31ull)));
-}
-
 static __device__ Table2x2 column_vs_partition_dev(const int32_t* __restrict__ idx, const uint8_t* __restrict__ code, int n,
                                                    const int8_t* __restrict__ state, int ref, uint8_t* s_seen /* [128] */,
                                                    uint8_t* s_ord /* [260] */, int* s_ord_n /* [1] */, uint8_t* s_map /* [3 * 512]: the hash map's tables */) {
@@ -1180,13 +1171,13 @@ static __device__ Table2x2 column_vs_partition_dev(const int32_t* __restrict__ i
             second = b0 ? __builtin_amdgcn_readlane(sc[0], __builtin_ctzll(b0)) : __builtin_amdgcn_readlane(sc[1], __builtin_ctzll(b1));
         } else {
             // tie: first of the tied keys in the hash map's iteration order (keys inserted in first-appearance order, then ref). While the map has
-            // at most 12 keys that order is the keys' static rank (unless two tied keys share a rank, or a key sits six slots from its bucket) ...
+            // at most 12 keys that order is the keys' hs::rh8_static_rank (unless two tied keys share a rank, or a key sits six slots from its bucket) ...
             bool resolved = false;
             const int nkeys = nseen + (ref_seen ? 0 : 1);
             if (nkeys <= 12) {
                 const bool wide = nkeys > 6;
-                const int rk = lane < nseen ? rh8_rank_dev(sc[0], wide) : 0x7fffffff;      // (at most 12 codes: slot 0 of the lanes only)
-                const int rref = rh8_rank_dev(ref, wide);
+                const int rk = lane < nseen ? hs::rh8_static_rank(sc[0], wide) : 0x7fffffff;      // (at most 12 codes: slot 0 of the lanes only)
+                const int rref = hs::rh8_static_rank(ref, wide);
                 bool far = false;
                 if (wide) {
                     int carry = 0;
@@ -1273,14 +1264,12 @@ __global__ __launch_bounds__(1024) void k_column_partition_test(
         const uint8_t* __restrict__ code = col_code + e0;
         const int k0 = col_k0[col], k1 = col_k1[col];
         const bool loop_c = col_is_cand[col] != 0;                                   // loop C (:721-738)
-        const bool loop_d = (col_c1[col] & 0xffff) >= 5 && central_base_test_dev(k0, k1);     // loop D (:745-764) on the columns that can be rescued
+        const bool loop_d = (col_c1[col] & 0xffff) >= 5 && hs::central_base_test(k0, k1);     // loop D (:745-764) on the columns that can be rescued
         bool kept = false;
         if (loop_c || loop_d) {
             for (int p = p0 + wv; p < p1 && !kept; p += 16) {
                 const Table2x2 d = column_vs_partition_dev(idx, code, n, part_state + part_state_off[p], k0, s_seen[wv], s_ord[wv], &s_ord_n[wv], s_map[wv]);
-                const float chi = chi_square_dev(d);
-                if (loop_c && (double)(d.n00 + d.n01 + d.n10 + d.n11) > 0.5 * (double)n && chi > 15) kept = true;
-                if (loop_d && (double)chi > 20.0 && d.n10 + d.n00 > 4 && d.n01 + d.n11 > 4) kept = true;
+                kept = hs::loop_cd_keeps(d.n00, d.n01, d.n10, d.n11, hs::chi_square(d.n00, d.n01, d.n10, d.n11), n, loop_c, loop_d);
             }
         }
         if (kept && lane == 0) atomicOr(&s_kept, 1);
@@ -1315,12 +1304,9 @@ __global__ __launch_bounds__(256) void k_column_partition_pairs(
         const int n = (int)(col_off[col + 1] - e0);
         const int k0 = col_k0[col], k1 = col_k1[col];
         const bool loop_c = col_is_cand[col] != 0;
-        const bool loop_d = (col_c1[col] & 0xffff) >= 5 && central_base_test_dev(k0, k1);
+        const bool loop_d = (col_c1[col] & 0xffff) >= 5 && hs::central_base_test(k0, k1);
         const Table2x2 d = column_vs_partition_dev(col_idx + e0, col_code + e0, n, part_state + part_state_off[p], k0, s_seen[wv], s_ord[wv], &s_ord_n[wv], s_map[wv]);
-        const float chi = chi_square_dev(d);
-        bool kept = false;
-        if (loop_c && (double)(d.n00 + d.n01 + d.n10 + d.n11) > 0.5 * (double)n && chi > 15) kept = true;
-        if (loop_d && (double)chi > 20.0 && d.n10 + d.n00 > 4 && d.n01 + d.n11 > 4) kept = true;
+        const bool kept = hs::loop_cd_keeps(d.n00, d.n01, d.n10, d.n11, hs::chi_square(d.n00, d.n01, d.n10, d.n11), n, loop_c, loop_d);
         if (kept && lane_id() == 0) keep[col] = 1;
     }
 }
@@ -1446,6 +1432,25 @@ __global__ __launch_bounds__(256) void k_partition_pair_distance(
 #define HS_K4L_K1 0x140F0A1Eu
 #define HS_K4L_OTHER 0x1919191Eu
 #define HS_K4L_NONE 0x1E1E1E1Eu
+// K4's fast verdict of loops C (:721-738) and D (:745-764) on one table (`n` the column's depth): chi-square as N (ad - bc)^2 / (r1 r2 c1 c2)
+// in float unless that comes within 0.05 of a threshold, then the reference's own sequence of float and double operations (hs::chi_square).
+// The margins are a speed decision of K4; what they fall back to is the rule. Inlined into k_column_partition_lanes, called by
+// k_column_partition_grouped (k4_verdict).
+static __device__ __forceinline__ bool k4_verdict_inline(int n11, int n01, int n10, int n00, int n, bool is_cand, bool loop_d) {
+    const int total = n00 + n01 + n10 + n11;
+    const bool pre_c = is_cand && 2 * total > n;                       // (double)total > 0.5 * (double)n
+    const bool pre_d = loop_d && n10 + n00 > 4 && n01 + n11 > 4;
+    const int r1 = n10 + n11, c1 = n01 + n11;
+    if (!((pre_c || pre_d) && r1 > 0 && r1 < total && c1 > 0 && c1 < total)) return false;      // (a margin of 0 or all: chi-square is -1 or 0)
+    const float det = (float)(n11 * n00 - n10 * n01);
+    float chi = (float)total * det * det * __builtin_amdgcn_rcpf((float)((r1 * (total - r1)) * (c1 * (total - c1))));
+    const bool near = (pre_c && fabsf(chi - 15.0f) < 0.05f) || (pre_d && fabsf(chi - 20.0f) < 0.05f);
+    if (near) chi = hs::chi_square(n00, n01, n10, n11);
+    return (pre_c && chi > 15) || (pre_d && (double)chi > 20.0);
+}
+static __device__ __noinline__ bool k4_verdict(int n11, int n01, int n10, int n00, int n, bool is_cand, bool loop_d) {
+    return k4_verdict_inline(n11, n01, n10, n00, n, is_cand, loop_d);
+}
 __global__ __launch_bounds__(256) void k_column_partition_lanes(
     const int64_t* __restrict__ col_off, const int32_t* __restrict__ col_idx, const uint8_t* __restrict__ col_code,
     const int32_t* __restrict__ col_contig, const uint8_t* __restrict__ col_k0, const uint8_t* __restrict__ col_k1,
@@ -1471,7 +1476,7 @@ __global__ __launch_bounds__(256) void k_column_partition_lanes(
         k0 = col_k0[col]; k1 = col_k1[col];
         is_cand = col_is_cand[col] != 0;
         const int c1w = col_c1[col];
-        loop_d = (c1w & 0xffff) >= 5 && central_base_test_dev(k0, k1);
+        loop_d = (c1w & 0xffff) >= 5 && hs::central_base_test(k0, k1);
         c2 = 63 - ((c1w >> 16) & 63);      // the column's third count (63: that or more, or not known)
         if (c2 >= 63) c2 = 1 << 20;
         ppad = (uint32_t)((P + 15) & ~15);
@@ -1558,17 +1563,7 @@ __global__ __launch_bounds__(256) void k_column_partition_lanes(
             const int take_k = (int)(w_k & 1023u) + n10 + n00, rest = (int)w_o;
             const int other_ub = rest < c2 ? rest : c2;      // what one other code can have here at most: all of them together, or the column's third count
             if (take_k > other_ub) {      // k1 is the partition's most frequent other code, strictly
-                const int total = n00 + n01 + n10 + n11;
-                const bool pre_c = is_cand && 2 * total > n;                       // loop C (:721-738): (double)total > 0.5 * (double)n
-                const bool pre_d = loop_d && n10 + n00 > 4 && n01 + n11 > 4;       // loop D (:745-764)
-                const int r1 = n10 + n11, c1 = n01 + n11;
-                if ((pre_c || pre_d) && r1 > 0 && r1 < total && c1 > 0 && c1 < total) {      // (a margin of 0 or all: chi-square is -1 or 0)
-                    const float det = (float)(n11 * n00 - n10 * n01);
-                    float chi = (float)total * det * det * __builtin_amdgcn_rcpf((float)((r1 * (total - r1)) * (c1 * (total - c1))));
-                    const bool near = (pre_c && fabsf(chi - 15.0f) < 0.05f) || (pre_d && fabsf(chi - 20.0f) < 0.05f);
-                    if (near) { Table2x2 d; d.n00 = n00; d.n01 = n01; d.n10 = n10; d.n11 = n11; chi = chi_square_dev(d); }
-                    ok = (pre_c && chi > 15) || (pre_d && (double)chi > 20.0);
-                }
+                ok = k4_verdict_inline(n11, n01, n10, n00, n, is_cand, loop_d);
             } else {
                 const int ub = other_ub > take_k ? other_ub : take_k;      // what the second allele can have at most
                 open = ub > 0 && ((is_cand && 2 * (n11 + n01 + ub) > n) || (loop_d && ub >= 5 && n01 + n11 > 4));
@@ -1603,32 +1598,9 @@ __global__ __launch_bounds__(256) void k_column_partition_lanes(
 // Not decided here (keep = 2, re-done by the exact kernel above): a column with a partition whose tied candidates give different
 // verdicts, reference codes >= 128 (signed-char quirk), columns
 // deeper than 255, codes outside 33..160, contigs with more than 65535 reads or partitions or a table beyond 4 GB.
-// the verdict of loops C (:721-738) and D (:745-764) on one table: chi-square as N (ad - bc)^2 / (r1 r2 c1 c2) in float unless that comes
-// within 0.05 of a threshold, then the reference's own sequence of float and double operations (chi_square_dev)
-static __device__ __noinline__ bool k4_verdict(int n11, int n01, int n10, int n00, int n, bool is_cand, bool loop_d) {
-    const int total = n00 + n01 + n10 + n11;
-    const bool pre_c = is_cand && 2 * total > n;                       // (double)total > 0.5 * (double)n
-    const bool pre_d = loop_d && n10 + n00 > 4 && n01 + n11 > 4;
-    const int r1 = n10 + n11, c1 = n01 + n11;
-    if (!((pre_c || pre_d) && r1 > 0 && r1 < total && c1 > 0 && c1 < total)) return false;      // (a margin of 0 or all: chi-square is -1 or 0)
-    const float det = (float)(n11 * n00 - n10 * n01);
-    float chi = (float)total * det * det * __builtin_amdgcn_rcpf((float)((r1 * (total - r1)) * (c1 * (total - c1))));
-    const bool near = (pre_c && fabsf(chi - 15.0f) < 0.05f) || (pre_d && fabsf(chi - 20.0f) < 0.05f);
-    if (near) { Table2x2 d; d.n00 = n00; d.n01 = n01; d.n10 = n10; d.n11 = n11; chi = chi_square_dev(d); }
-    return (pre_c && chi > 15) || (pre_d && (double)chi > 20.0);
-}
 #define HS_K4_COLS 4              // columns a wavefront takes at a time: their pairs fill about one round of 64
 #define HS_K4_ROW 264             // u16 entries of a column's row in LDS: 255 entries + the gap behind the reference code's + the tail
 #define HS_K4_PAIRS 80
-static __device__ __forceinline__ int wave_or_i32(int v) {
-    v |= __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
-    v |= __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
-    v |= __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
-    v |= __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
-    v |= __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-    v |= __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-    return __builtin_amdgcn_readlane(v, 63);
-}
 __global__ __launch_bounds__(64) void k_column_partition_grouped(
     const int64_t* __restrict__ col_off, const int32_t* __restrict__ col_idx, const uint8_t* __restrict__ col_code,
     const int32_t* __restrict__ col_contig, const uint8_t* __restrict__ col_k0, const uint8_t* __restrict__ col_k1,
@@ -1661,7 +1633,7 @@ __global__ __launch_bounds__(64) void k_column_partition_grouped(
         h_k0 = col_k0[hc];
         const int k1 = col_k1[hc];
         const bool is_cand = col_is_cand[hc] != 0;
-        const bool loop_d = (col_c1[hc] & 0xffff) >= 5 && central_base_test_dev(h_k0, k1);
+        const bool loop_d = (col_c1[hc] & 0xffff) >= 5 && hs::central_base_test(h_k0, k1);
         h_flags = (is_cand ? 1 : 0) | (loop_d ? 2 : 0);
         h_ppad = (P + 15) & ~15;
         const int64_t tb = tab_off[c];

@@ -258,9 +258,7 @@ __global__ __launch_bounds__(256) void k_column_top3_exact(const int64_t* __rest
     __shared__ int s_stack[4][120];
     __shared__ uint8_t s_first[4][128];
     __shared__ int s_fpos[4][128];
-    // place of every byte key in the iteration order of the reference's hash map while it has not grown past 16 buckets (tests/harness/
-    // rh8_static_order.cpp): up to 6 keys 8 buckets and the first multiplier, 7 to 12 keys 16 buckets and the second one; rank = home bucket << 5 |
-    // 31 - low five hash bits. Keys of different rank iterate in rank order whatever order they were inserted in.
+    // hs::rh8_static_rank of every byte key, for up to 6 keys and for 7 to 12
     __shared__ uint16_t s_rank8[256], s_rank16[256];
     __shared__ int s_bucket[4][16];
     const int lane = lane_id();
@@ -269,14 +267,8 @@ __global__ __launch_bounds__(256) void k_column_top3_exact(const int64_t* __rest
     int* __restrict__ h = s_hist[wv];
     __shared__ int s_ties[2];
     if (threadIdx.x < 2) s_ties[threadIdx.x] = 0;
-    {
-        unsigned long long x = (unsigned long long)threadIdx.x;
-        x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33;
-        unsigned long long a = x * 0xc4ceb9fe1a85ec53ull; a ^= a >> 33;
-        unsigned long long b = x * (0xc4ceb9fe1a85ec53ull + 0xc4ceb9fe1a85ec54ull); b ^= b >> 33;
-        s_rank8[threadIdx.x] = (uint16_t)((((a >> 5) & 7ull) << 5) | (31ull - (a & 31ull)));
-        s_rank16[threadIdx.x] = (uint16_t)((((b >> 5) & 15ull) << 5) | (31ull - (b & 31ull)));
-    }
+    s_rank8[threadIdx.x] = (uint16_t)hs::rh8_static_rank((int)threadIdx.x, false);
+    s_rank16[threadIdx.x] = (uint16_t)hs::rh8_static_rank((int)threadIdx.x, true);
     __syncthreads();
     int my_ties = 0, my_big = 0;
     // a wavefront looks at 64 column records at a time and does the ones k_columns_compact left open (since K2 forms the leading codes itself:
@@ -709,11 +701,6 @@ __global__ __launch_bounds__(64 * HS_CB_WAVES) void k_cand_bits(
     }
 }
 
-static __device__ __forceinline__ bool central_base_test_cols(int k0, int k1) {
-    // call_variants.cpp:527-528 and :751-752 (same predicate on raw code bytes)
-    return k0 % 5 != k1 % 5 && ((k1 - '!') % 5 != 4 || (k1 / 5 % 5 != k0 % 5 && k1 / 25 % 5 != k0 % 5));
-}
-
 // ------------------------------------------------------------------------------------------------
 // V1: the candidate and the "automatic" columns of every contig of the range (call_variants.cpp:525-536). One thread per
 // column. The reference walks a contig's positions and takes a column that passes the predicate when it lies more than five
@@ -749,7 +736,7 @@ __global__ __launch_bounds__(256) void k_candidates_scan(
         ci = r.contig - c_first;
         const int mr = min_reads[ci];
         auto passes = [&](const hs_colrec_dev& q) {
-            return q.pos > 0 && (int)q.c1 > mr && (q.flags & HS_COL_C1GT5C2) && central_base_test_cols(q.k0, q.k1);
+            return q.pos > 0 && (int)q.c1 > mr && (q.flags & HS_COL_C1GT5C2) && hs::central_base_test(q.k0, q.k1);
         };
         if (passes(r)) {
             // back to the head of the chain
@@ -777,7 +764,7 @@ __global__ __launch_bounds__(256) void k_candidates_scan(
         }
         uint8_t f = r.flags & (HS_COL_TIE | HS_COL_C1GT5C2);
         if (cand) { f |= HS_COL_CAND; if ((float)r.c1 > thr * (float)r.c0) f |= HS_COL_AUTO; }
-        if ((int)r.c1 >= 5 && central_base_test_cols(r.k0, r.k1)) f |= HS_COL_LOOPD;
+        if ((int)r.c1 >= 5 && hs::central_base_test(r.k0, r.k1)) f |= HS_COL_LOOPD;
         r.flags = f;
         int4 w; __builtin_memcpy(&w, &r, 16);
         reinterpret_cast<int4*>(col_rec)[k] = w;

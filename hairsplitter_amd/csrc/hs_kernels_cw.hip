@@ -33,11 +33,6 @@ namespace hsdev {
 #define HS_CW_REG_LABELS 8
 #endif
 
-static __device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // position of read id r in the ascending list ids[0..m), or -1
 static __device__ __forceinline__ int local_index(const int32_t* __restrict__ ids, int m, int r) {
     int lo = 0, hi = m;
@@ -182,16 +177,16 @@ static __device__ int cw_local_wave(const int64_t* __restrict__ off_w /* at the 
                     best_lab = best_cnt ? 65535 - (int)(best_key & 0xffffu) : -1;
                     if (rem) {
                         if (lb >= 0) atomicAdd(&cnt[lb], 1);
-                        wave_sync_lds();
+                        wave_lds_sync();
                         const int c = lb >= 0 ? cnt[lb] : 0;
                         best_cnt = wave_max_i32(c);
                         best_lab = 0x7fffffff - wave_max_i32((lb >= 0 && c == best_cnt) ? 0x7fffffff - lb : 0);
-                        wave_sync_lds();
+                        wave_lds_sync();
                         if (lb >= 0) cnt[lb] = 0;
                     }
                 } else {
                     for (int o = o0 + lane; o < o1; o += 64) { const int lb = lab[anb[o]]; if (lb >= 0) atomicAdd(&cnt[lb], 1); }
-                    wave_sync_lds();
+                    wave_lds_sync();
                     unsigned long long best = 0ull;
                     for (int o = o0 + lane; o < o1; o += 64) {
                         const int lb = lab[anb[o]];
@@ -201,17 +196,17 @@ static __device__ int cw_local_wave(const int64_t* __restrict__ off_w /* at the 
                         }
                     }
                     best = wave_max_u64(best);
-                    wave_sync_lds();
+                    wave_lds_sync();
                     for (int o = o0 + lane; o < o1; o += 64) { const int lb = lab[anb[o]]; if (lb >= 0) cnt[lb] = 0; }
                     best_cnt = (int)(best >> 32);
                     best_lab = 0x7fffffff - (int)(best & 0xffffffffull);
                 }
                 if (best_cnt > 0) {
                     if (lab[i] != best_lab) changes++;
-                    wave_sync_lds();
+                    wave_lds_sync();
                     if (lane == 0) lab[i] = best_lab;
                 }
-                wave_sync_lds();
+                wave_lds_sync();
             }
         }
         iters++;
@@ -310,13 +305,13 @@ __global__ __launch_bounds__(128) void k_cw_seeded_rows(
 #pragma unroll
     for (int k = 0; k < 4; ++k) { e_j[k] = (live && e_r[k] >= 0) ? local_index(s_ids, m, e_r[k]) : -1; if (e_j[k] >= 0) atomicMin(&cnt[e_c[k]], e_j[k]); }
     if (live) for (int64_t e = c0 + 64 + l; e < c1; e += 16) { const int j = local_index(s_ids, m, col_idx[e]); if (j >= 0) atomicMin(&cnt[col_code[e]], j); }
-    wave_sync_lds();
+    wave_lds_sync();
 #pragma unroll
     for (int k = 0; k < 4; ++k) if (e_j[k] >= 0) lab[e_j[k]] = (uint8_t)cnt[e_c[k]];
     if (live) for (int64_t e = c0 + 64 + l; e < c1; e += 16) { const int j = local_index(s_ids, m, col_idx[e]); if (j >= 0) lab[j] = (uint8_t)cnt[col_code[e]]; }
-    wave_sync_lds();
+    wave_lds_sync();
     for (int j = l; j < cnt_cap; j += 16) cnt[j] = 0;
-    wave_sync_lds();
+    wave_lds_sync();
 #ifdef HS_CW_DIAG
     if (live && l == 0) { int alive = 0; for (int j = 0; j < m; ++j) alive += lab[j] == j ? 1 : 0; atomicAdd(&stat[20 + (alive > 15 ? 15 : alive)], 1ull); atomicAdd(&stat[36 + (m >> 4 > 15 ? 15 : m >> 4)], 1ull); }
 #endif
@@ -377,13 +372,13 @@ __global__ __launch_bounds__(128) void k_cw_seeded_rows(
                         if (m1 >= 0) atomicAdd(&cnt[m1], 1);
                         if (m2 >= 0) atomicAdd(&cnt[m2], 1);
                         if (m3 >= 0) atomicAdd(&cnt[m3], 1);
-                        wave_sync_lds();
+                        wave_lds_sync();
                         if (m0 >= 0) { const unsigned k = ((unsigned)cnt[m0] << 16) | (unsigned)(65535 - m0); best = k > best ? k : best; }
                         if (m1 >= 0) { const unsigned k = ((unsigned)cnt[m1] << 16) | (unsigned)(65535 - m1); best = k > best ? k : best; }
                         if (m2 >= 0) { const unsigned k = ((unsigned)cnt[m2] << 16) | (unsigned)(65535 - m2); best = k > best ? k : best; }
                         if (m3 >= 0) { const unsigned k = ((unsigned)cnt[m3] << 16) | (unsigned)(65535 - m3); best = k > best ? k : best; }
                         best = row_max_u32(best);
-                        wave_sync_lds();
+                        wave_lds_sync();
                         if (m0 >= 0) cnt[m0] = 0;
                         if (m1 >= 0) cnt[m1] = 0;
                         if (m2 >= 0) cnt[m2] = 0;
@@ -391,17 +386,17 @@ __global__ __launch_bounds__(128) void k_cw_seeded_rows(
                     }
                 } else {
                     for (int c = 0; c < nc; ++c) { const int nb = pg[c * 16]; if (nb != 255) atomicAdd(&cnt[lab[nb]], 1); }
-                    wave_sync_lds();
+                    wave_lds_sync();
                     for (int c = 0; c < nc; ++c) { const int nb = pg[c * 16]; if (nb != 255) { const int lb = lab[nb]; const unsigned k = ((unsigned)cnt[lb] << 16) | (unsigned)(65535 - lb); best = k > best ? k : best; } }
                     best = row_max_u32(best);
-                    wave_sync_lds();
+                    wave_lds_sync();
                     for (int c = 0; c < nc; ++c) { const int nb = pg[c * 16]; if (nb != 255) cnt[lab[nb]] = 0; }
                 }
                 const int best_lab = 65535 - (int)(best & 0xffffu);      // a visited node has neighbours: the count is > 0
                 changes += old != best_lab ? 1 : 0;
-                wave_sync_lds();
+                wave_lds_sync();
                 if (l == 0 && active) lab[i] = (uint8_t)best_lab;
-                wave_sync_lds();
+                wave_lds_sync();
                 inf = inf_next;
             }
             if (active) { iters++; active = changes > 2 && iters < 15; }
@@ -415,16 +410,16 @@ __global__ __launch_bounds__(128) void k_cw_seeded_rows(
                 const int o0 = (int)(off_w[i] - base), o1 = (int)(off_w[i + 1] - base);
                 unsigned best = 0u;
                 for (int o = o0 + l; o < o1; o += 16) atomicAdd(&cnt[lab[anb[o]]], 1);
-                wave_sync_lds();
+                wave_lds_sync();
                 for (int o = o0 + l; o < o1; o += 16) { const int lb = lab[anb[o]]; const unsigned key = ((unsigned)cnt[lb] << 16) | (unsigned)(65535 - lb); best = key > best ? key : best; }
                 best = row_max_u32(best);
-                wave_sync_lds();
+                wave_lds_sync();
                 for (int o = o0 + l; o < o1; o += 16) cnt[lab[anb[o]]] = 0;
                 const int best_lab = 65535 - (int)(best & 0xffffu);
                 if ((int)lab[i] != best_lab) changes++;
-                wave_sync_lds();
+                wave_lds_sync();
                 if (l == 0) lab[i] = (uint8_t)best_lab;
-                wave_sync_lds();
+                wave_lds_sync();
             }
             iters++;
         }
@@ -455,7 +450,7 @@ __global__ __launch_bounds__(64) void k_cw_seeded_wave(
     const int lane = lane_id();
     const int n_runs = n_list_dev ? *n_list_dev : n_list;
     for (int k = (int)blockIdx.x; k < n_runs; k += (int)gridDim.x) {
-    wave_sync_lds();
+    wave_lds_sync();
     const int inst = inst_list[k];
     const int w = inst_win[inst];
     const int64_t r0 = win_row0[w];
@@ -465,15 +460,15 @@ __global__ __launch_bounds__(64) void k_cw_seeded_wave(
     int32_t* cnt = lab + (m <= lds_cap ? lds_cap : m);
     for (int j = lane; j < m; j += 64) { lab[j] = j; cnt[j] = 0; }
     for (int j = lane; j < 256; j += 64) s_first[j] = 0x7fffffff;
-    wave_sync_lds();
+    wave_lds_sync();
     const int64_t s = inst_seed_col[inst];
     cw_seed_labels<64>(ids, m, col_off[s], col_off[s + 1], col_idx, col_code, s_first, lane);
-    wave_sync_lds();
+    wave_lds_sync();
     for (int64_t e = col_off[s] + lane; e < col_off[s + 1]; e += 64) {
         const int j = local_index(ids, m, col_idx[e]);
         if (j >= 0) lab[j] = s_first[col_code[e]];
     }
-    wave_sync_lds();
+    wave_lds_sync();
     const int iters = cw_local_wave(off + r0, nbr, visit + r0, visit_n[w], m, lab, cnt, lane);
     int32_t* __restrict__ out = slab + inst_slab_off[inst];
     for (int j = lane; j < m; j += 64) out[j] = lab[j];
@@ -525,14 +520,14 @@ __global__ __launch_bounds__(256) void k_cw_seed_sets(
     ids[lane] = lane < m ? mask_ids[r0 + lane] : 0x7fffffff;
     lab[lane] = lane;
     for (int c = lane; c < 256; c += 64) first[c] = 0x7fffffff;
-    wave_sync_lds();
+    wave_lds_sync();
     const int j0 = R0 >= 0 ? local_index(ids, m, R0) : -1;
     if (j0 >= 0) atomicMin(&first[code0], j0);
     for (int64_t e = e0 + 64; e < c1; e += 64) { const int j = local_index(ids, m, col_idx[e]); if (j >= 0) atomicMin(&first[col_code[e]], j); }
-    wave_sync_lds();
+    wave_lds_sync();
     if (j0 >= 0) lab[j0] = first[code0];
     for (int64_t e = e0 + 64; e < c1; e += 64) { const int j = local_index(ids, m, col_idx[e]); if (j >= 0) lab[j] = first[col_code[e]]; }
-    wave_sync_lds();
+    wave_lds_sync();
     const int L = lab[lane];                                            // < 64
     const bool node = lane < m;
     const unsigned long long leaders = __ballot(node && L == lane);
@@ -548,7 +543,7 @@ __global__ __launch_bounds__(256) void k_cw_seed_sets(
     for (int k = 0; k < HS_CWL_SLOTS; ++k) { const unsigned long long S = __ballot(node && slot == k); if (lane == k) mine = S; }
     if (lane < HS_CWL_SLOTS) seed_sets[(int64_t)q * HS_CWL_SLOTS + lane] = mine;
     if (node && L == lane) ids[slot] = lane;                            // (the read ids are not needed any more)
-    wave_sync_lds();
+    wave_lds_sync();
     if (lane < HS_CWL_SLOTS) seed_names[(int64_t)q * HS_CWL_SLOTS + lane] = (uint8_t)(lane < alive ? ids[lane] : 0);
     if (lane == 0) seed_n[q] = (uint8_t)alive;
 }
@@ -633,7 +628,7 @@ __global__ __launch_bounds__(64) void k_cw_seeded_lanes(
         for (int k = 0; k < 16; ++k) { const int x = lane + 64 * k; s_slot[(x >> 4) * 17 + (x & 15)] = src[x]; }
         if (lane < 16) s_hist[lane] = 0u;
     }
-    wave_sync_lds();
+    wave_lds_sync();
     int nmax = 0;                                  // slots in use by any run of this wavefront
 #pragma unroll
     for (int k = 1; k <= HS_CWL_SLOTS; ++k) if (__ballot(ok && na >= k) != 0ull) nmax = k;
@@ -645,7 +640,7 @@ __global__ __launch_bounds__(64) void k_cw_seeded_lanes(
     else if (nmax <= 10) iters = cwl_sweeps<10>(set_lo, set_hi, my_slot, prog_adj + r0, prog_info + r0, nv, ok);
     else if (nmax <= 12) iters = cwl_sweeps<12>(set_lo, set_hi, my_slot, prog_adj + r0, prog_info + r0, nv, ok);
     else iters = cwl_sweeps<HS_CWL_SLOTS>(set_lo, set_hi, my_slot, prog_adj + r0, prog_info + r0, nv, ok);
-    wave_sync_lds();
+    wave_lds_sync();
     // labels out, run by run: lane j writes node j (coalesced)
     const unsigned long long okm = __ballot(ok);
     const uint8_t* names = reinterpret_cast<const uint8_t*>(s_name);
@@ -663,7 +658,7 @@ __global__ __launch_bounds__(64) void k_cw_seeded_lanes(
         if (ok) atomicAdd(&s_hist[iters > 15 ? 15 : iters], 1u);
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) { sw += __shfl_xor(sw, d, 64); by += __shfl_xor(by, d, 64); }
-        wave_sync_lds();
+        wave_lds_sync();
         if (lane == 0) { atomicAdd(&stat[0], sw); atomicAdd(&stat[1], by); }
         if (lane < 16 && s_hist[lane]) atomicAdd(&stat[4 + lane], (unsigned long long)s_hist[lane]);
     }
@@ -686,7 +681,7 @@ __global__ __launch_bounds__(64) void k_cw_local(
     int32_t* cnt = lab + (m <= lds_cap ? lds_cap : m);
     int32_t* __restrict__ io = labels_io + inst_label_off[k];
     for (int j = lane; j < m; j += 64) { lab[j] = io[j]; cnt[j] = 0; }
-    wave_sync_lds();
+    wave_lds_sync();
     cw_local_wave(off + r0, nbr, visit + r0, win_final_empty[w] ? 0 : visit_n[w], m, lab, cnt, lane);
     for (int j = lane; j < m; j += 64) io[j] = lab[j];
 }
@@ -697,24 +692,14 @@ __global__ __launch_bounds__(64) void k_cw_local(
 // neighbours (one bit mask `adj`, k_cw_visit_lists) is then popcount(adj & S) in every lane at once and one wave maximum, instead of a
 // leader loop over the distinct labels among the neighbours.
 // ------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v) {
-    unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
-#define HS_OR_STEP(ctrl, rm) lo |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, ctrl, rm, 0xf, false); hi |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, ctrl, rm, 0xf, false);
-    HS_OR_STEP(0x111, 0xf) HS_OR_STEP(0x112, 0xf) HS_OR_STEP(0x114, 0xf) HS_OR_STEP(0x118, 0xf) HS_OR_STEP(0x142, 0xa) HS_OR_STEP(0x143, 0xc)
-#undef HS_OR_STEP
-    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)hi, 63) << 32) | (unsigned)__builtin_amdgcn_readlane((int)lo, 63);
-}
-static __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
-    return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(v & 0xffffffffull), l);
-}
 // S from L: one 64-bit LDS atomic per node (s_sets: 64 words)
 static __device__ __forceinline__ unsigned long long sets_from_labels(int L, unsigned long long* s_sets, int lane) {
     s_sets[lane] = 0ull;
-    wave_sync_lds();
+    wave_lds_sync();
     if (L >= 0) atomicOr(&s_sets[L], 1ull << lane);
-    wave_sync_lds();
+    wave_lds_sync();
     const unsigned long long S = s_sets[lane];
-    wave_sync_lds();
+    wave_lds_sync();
     return S;
 }
 // labels renumbered by first appearance (the label whose first node comes first becomes 0, ...): returns the number of labels
@@ -723,12 +708,12 @@ static __device__ __forceinline__ int sets_renumber(unsigned long long& S, int& 
     const unsigned long long F = wave_or_u64(S ? 1ull << f : 0ull);      // the first nodes of all labels
     const int nl = S ? __popcll(F & ((1ull << f) - 1ull)) : -1;
     s_sets[lane] = 0ull; s_relabel[lane] = nl;
-    wave_sync_lds();
+    wave_lds_sync();
     if (nl >= 0) s_sets[nl] = S;
     const int Ln = L >= 0 ? s_relabel[L] : -1;
-    wave_sync_lds();
+    wave_lds_sync();
     S = s_sets[lane]; L = Ln;
-    wave_sync_lds();
+    wave_lds_sync();
     return __popcll(F);
 }
 // one Chinese-Whispers run (cluster_graph.cpp:240-310; what cw_local_wave does on lists): lane v holds the v-th visit's node and
@@ -805,9 +790,9 @@ static __device__ void first_seen_ids_wave(const int32_t* first, int m, int32_t*
         if (j < m) pre[j] = carry + __popcll(b & ((1ull << lane) - 1ull));
         carry += __popcll(b);
     }
-    wave_sync_lds();
+    wave_lds_sync();
     for (int j = lane; j < m; j += 64) { const int f = first[j]; out_id[j] = f >= 0 ? pre[f] : -1; }
-    wave_sync_lds();
+    wave_lds_sync();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -876,7 +861,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
 #endif
     // ---- merge_clusterings ids (:840-874): the reference's double key sum_i label_i * 2^i, labels = read ids ----
     for (int j = lane; j < m; j += 64) t1[j] = ids[j];      // (the read ids out of LDS: the labels of the runs index them)
-    wave_sync_lds();
+    wave_lds_sync();
     for (int j = lane; j < m; j += 64) {
         double a = 0.0, f = 1.0;
         int i = 0;
@@ -894,7 +879,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
         for (; i < K; ++i) { a += (double)t1[sl[(int64_t)i * m + j]] * f; f *= 2.0; }
         agg[j] = a; cnt[j] = 0;
     }
-    wave_sync_lds();
+    wave_lds_sync();
     {
         // t0[j] = the first node with node j's key: an open-addressing table over nc|cnt (2 * stride ints) holds, per distinct key, the
         // smallest index seen so far -- any index in a slot carries the slot's key, so a probe compares against whichever is there
@@ -902,7 +887,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
         while (T <= m) T <<= 1;      // m < T <= 2 m: an empty slot always exists
         int32_t* tab = nc;
         for (int x = lane; x < T; x += 64) tab[x] = -1;
-        wave_sync_lds();
+        wave_lds_sync();
         for (int j = lane; j < m; j += 64) {
             const double a = agg[j];
             const unsigned long long bits = (unsigned long long)__double_as_longlong(a);
@@ -916,16 +901,16 @@ __global__ __launch_bounds__(64) void k_window_tail(
             }
             t0[j] = (int)h;
         }
-        wave_sync_lds();
+        wave_lds_sync();
         for (int j = lane; j < m; j += 64) t0[j] = tab[t0[j]];
-        wave_sync_lds();
+        wave_lds_sync();
         for (int j = lane; j < m; j += 64) cnt[j] = 0;
-        wave_sync_lds();
+        wave_lds_sync();
     }
     first_seen_ids_wave(t0, m, t1, lab, lane);
     HS_TQ(0)
     const bool masks = m <= 64 && prog_adj != nullptr;      // the window's neighbour masks exist (k_cw_visit_lists)
-    wave_sync_lds();
+    wave_lds_sync();
     int Kc = 0;
     unsigned long long fin_S = 0ull, fin_adjn = 0ull;      // (narrow windows: the finished label sets and every node's neighbours, for the steps below)
     int fin_L = -1;
@@ -935,11 +920,11 @@ __global__ __launch_bounds__(64) void k_window_tail(
         const int nodev = lane < n_visit ? (int)(prog_info[r0 + lane] & 255u) : 0;
         int L = lane < m ? lab[lane] : -1;
         s_sets[lane] = 0ull;
-        wave_sync_lds();
+        wave_lds_sync();
         if (lane < n_visit) s_sets[nodev] = adjv;
-        wave_sync_lds();
+        wave_lds_sync();
         const unsigned long long adjn = s_sets[lane];      // node j's neighbours (none: not in the visiting list)
-        wave_sync_lds();
+        wave_lds_sync();
         unsigned long long S = sets_from_labels(L, s_sets, lane);
         // run on the finalize graph (:881)
         sweeps += (unsigned long long)cw_run_sets(adjv, nodev, adjn, n_visit, S, L, lane);
@@ -1018,28 +1003,28 @@ __global__ __launch_bounds__(64) void k_window_tail(
         }
         if (lane < m) { lab[lane] = L; nc[lane] = L; }
         fin_S = S; fin_L = L; fin_adjn = adjn;
-        wave_sync_lds();
+        wave_lds_sync();
     } else {
     // ---- wider windows: labels in LDS (or global scratch), neighbour lists ----
     // ---- run on the finalize graph (:881) ----
     sweeps += (unsigned long long)cw_local_wave(off_w, nbr, vis, n_visit, m, lab, cnt, lane);
     // ---- clusters with fewer than 5 reads become -1, the others are renumbered by first appearance (:924-955) ----
     for (int j = lane; j < m; j += 64) { nc[j] = 0; t1[j] = 0x7fffffff; }
-    wave_sync_lds();
+    wave_lds_sync();
     for (int j = lane; j < m; j += 64) { const int l = lab[j]; if (l >= 0 && l < m) atomicAdd(&nc[l], 1); }
-    wave_sync_lds();
+    wave_lds_sync();
     for (int j = lane; j < m; j += 64) {
         int l = lab[j];
         if (l < 0 || l >= m || nc[l] < 5) l = -1;
         t0[j] = l;
         if (l >= 0) atomicMin(&t1[l], j);
     }
-    wave_sync_lds();
+    wave_lds_sync();
     for (int j = lane; j < m; j += 64) nc[j] = t0[j] >= 0 ? t1[t0[j]] : -1;     // first position of the node's label
-    wave_sync_lds();
+    wave_lds_sync();
     first_seen_ids_wave(nc, m, t1, lab, lane);
     // ---- run (:970) ----
-    wave_sync_lds();
+    wave_lds_sync();
     sweeps += (unsigned long long)cw_local_wave(off_w, nbr, vis, n_visit, m, lab, cnt, lane);
     for (int j = lane; j < m; j += 64) l3[j] = lab[j];
     if (lane == 0 && stat) {
@@ -1051,10 +1036,10 @@ __global__ __launch_bounds__(64) void k_window_tail(
     HS_TQ(1)
     // ---- first-seen renumbering (:973-984): a label's new number = how many labels appear for the first time before it does ----
     for (int j = lane; j < m; j += 64) t1[j] = 0x7fffffff;
-    wave_sync_lds();
+    wave_lds_sync();
     bool bad_l = false;
     for (int j = lane; j < m; j += 64) { const int l = lab[j]; if (l >= 0) { if (l >= m) bad_l = true; else atomicMin(&t1[l], j); } }
-    wave_sync_lds();
+    wave_lds_sync();
     if (__ballot(bad_l) != 0ull) { bail(); return; }
     for (int b0 = 0; b0 < m; b0 += 64) {
         const int j = b0 + lane;
@@ -1062,21 +1047,21 @@ __global__ __launch_bounds__(64) void k_window_tail(
         if (j < m) { const int l = lab[j]; f = l >= 0 ? t1[l] : -1; nc[j] = f; }
         Kc += __popcll(__ballot(j < m && f == j));
     }
-    wave_sync_lds();
+    wave_lds_sync();
     first_seen_ids_wave(nc, m, t1, lab, lane);
     if (Kc > HS_FIN_KCAP) { bail(); return; }
 
     HS_TQ(2)
     // ---- merge_close_clusters (cluster_graph.cpp:402-501) ----
     if (lane < HS_FIN_KCAP) { s_initial[lane] = 0; s_tested[lane] = 0; }
-    wave_sync_lds();
+    wave_lds_sync();
     for (int j = lane; j < m; j += 64) { const int l = lab[j]; if (l >= 0) atomicAdd(&s_initial[l], 1); nc[j] = l; }
-    wave_sync_lds();
+    wave_lds_sync();
     for (int j = 0; j < m; ++j) {
         const int target = lab[j];                      // uniform
         if (target < 0 || s_tested[target]) continue;
         if (lane < Kc) s_count[lane] = s_initial[lane];
-        wave_sync_lds();
+        wave_lds_sync();
         int changes = 3, iters = 0;
         while (changes > 0 && iters < 10) {
             changes = 0;
@@ -1130,13 +1115,13 @@ __global__ __launch_bounds__(64) void k_window_tail(
                         if (lane == 0) { s_count[target]--; s_count[second_index]++; nc[i] = second_index; }
                         changes++;
                     }
-                    wave_sync_lds();
+                    wave_lds_sync();
                 }
             }
             iters++;
         }
         const bool dissolved = s_count[target] == 0;
-        wave_sync_lds();
+        wave_lds_sync();
         if (lane == 0) s_tested[target] = 1;
         if (dissolved) {
             for (int q = lane; q < m; q += 64) lab[q] = nc[q];
@@ -1144,7 +1129,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
         } else {
             for (int q = lane; q < m; q += 64) nc[q] = lab[q];
         }
-        wave_sync_lds();
+        wave_lds_sync();
     }
 
     }
@@ -1152,7 +1137,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
     HS_TQ(3)
     // ---- merge_wrongly_split_haplotypes (separate_reads.cpp:1007-1327) ----
     if (lane < HS_FIN_KCAP) { s_index_of[lane] = -1; s_slot_of[lane] = -1; }
-    wave_sync_lds();
+    wave_lds_sync();
     if (masks) {      // lane = label: its place in the order of first appearance, its slot among the labels that are left
         const bool present = fin_S != 0ull;
         const int f = present ? __builtin_ctzll(fin_S) : 0;
@@ -1171,7 +1156,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
         for (int l = 0; l < Kc; ++l) if (s_index_of[l] >= 0) { if (G < HS_FIN_GCAP) { s_slot_of[l] = G; s_glist[G] = l; s_gidx[G] = s_index_of[l]; } G++; }
         s_scalar[2] = G;
     }
-    wave_sync_lds();
+    wave_lds_sync();
     const int G = s_scalar[2];
     if (G <= 1) {
         for (int j = lane; j < m; j += 64) lout[j] = 0;
@@ -1180,10 +1165,10 @@ __global__ __launch_bounds__(64) void k_window_tail(
     }
     if (G > HS_FIN_GCAP) { bail(); return; }
     for (int x = lane; x < G * G; x += 64) s_incompat[x] = 0;
-    wave_sync_lds();
+    wave_lds_sync();
     const int pos_lo = win_pos_lo[c], pos_hi = win_pos_hi[c];
     for (int j = lane; j < m; j += 64) t0[j] = ids[j];          // the read ids next to the labels: the look-ups below stay off global memory
-    wave_sync_lds();
+    wave_lds_sync();
     const int32_t* ids_l = t0;
     // read id -> cluster slot as a byte map over the window's id range (the `agg` doubles are free by now), when the range fits:
     // one LDS byte per column entry instead of a bisection of the id list
@@ -1195,9 +1180,9 @@ __global__ __launch_bounds__(64) void k_window_tail(
     uint8_t* smap = 8ll * stride > HS_TAIL_MAP_EXTRA ? reinterpret_cast<uint8_t*>(agg) : reinterpret_cast<uint8_t*>(tail_dyn + 7 * lds_cap);
     if (use_map) {
         for (int x = lane; x < (int)id_range; x += 64) smap[x] = 0xff;
-        wave_sync_lds();
+        wave_lds_sync();
         for (int j = lane; j < m; j += 64) { const int cl = lab[j]; if (cl > -1) smap[ids_l[j] - id_lo] = (uint8_t)s_slot_of[cl]; }
-        wave_sync_lds();
+        wave_lds_sync();
     }
     HS_TQ(5)
     // lane a * G + b keeps the pair of clusters (a, b) with label(a) > label(b): its count of incompatible SNPs and the position of
@@ -1258,7 +1243,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
         for (int i = 0; i < G; ++i) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) s_cnts[lane + 64 * q] = 0;
-            wave_sync_lds();
+            wave_lds_sync();
             int nb_i = 0;
             for (int64_t eb = e0; eb < e0 + n; eb += 64) {
                 const int64_t e = eb + lane;
@@ -1271,7 +1256,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
                 }
                 nb_i += __popcll(__ballot(mine));
             }
-            wave_sync_lds();
+            wave_lds_sync();
             int t1v = 0, c1 = -1, t2v = 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -1279,7 +1264,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
                 const int v = s_cnts[cd];
                 if (v > t1v) { t2v = t1v; t1v = v; c1 = cd; } else if (v > t2v) t2v = v;
             }
-            wave_sync_lds();
+            wave_lds_sync();
             // one reduction gives the maximum and, among the lanes that hold it, the largest of their codes (counts < 2^23)
             const int top = wave_max_i32((t1v << 8) | (c1 & 255));
             const int mx = top >> 8;
@@ -1343,13 +1328,13 @@ __global__ __launch_bounds__(64) void k_window_tail(
     if (lane == 0 && stat) { atomicAdd(&stat[18 + 8], dq_fast); atomicAdd(&stat[18 + 9], dq_slow); atomicAdd(&stat[18 + 10], dq_keys); atomicAdd(&stat[18 + 11], use_map ? 1ull : 0ull); atomicAdd(&stat[18 + 12], (unsigned long long)G); }
 #endif
     if (pair_owner) { const int i1 = s_gidx[pa], i2 = s_gidx[pb]; s_incompat[i1 * G + i2] = pair_inc; s_incompat[i2 * G + i1] = pair_inc; }
-    wave_sync_lds();
+    wave_lds_sync();
     HS_TQ(6)
     // link ratios (:1189-1250): a dense (label + 2) x (label + 2) count matrix walked in ascending key order
     const int M = Kc + 2;
     for (int x = lane; x < M * M; x += 64) s_link_cnt[x] = 0;
     if (lane < M) s_links_in[lane] = 0;
-    wave_sync_lds();
+    wave_lds_sync();
     if (masks) {
         // lane = node q with its neighbour mask: per label c1 (and for the neighbours without a label) how many of q's neighbours carry it
         const int c2 = fin_L + 2;
@@ -1374,7 +1359,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
             }
         }
     }
-    wave_sync_lds();
+    wave_lds_sync();
     HS_TQ(7)
     // the links in ascending (c1, c2) order: the non-zero cells of the count matrix, ranked by a ballot prefix
     {
@@ -1389,7 +1374,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
         }
         if (lane == 0) s_scalar[4] = nl_all;
     }
-    wave_sync_lds();
+    wave_lds_sync();
     if (lane == 0) {
         int* lc1 = s_lc1; int* lc2 = s_lc2; double* lr = s_lr;      // (indexed at run time: LDS, not registers)
         const int nl = s_scalar[4] > HS_FIN_LCAP ? HS_FIN_LCAP : s_scalar[4];
@@ -1425,7 +1410,7 @@ __global__ __launch_bounds__(64) void k_window_tail(
             for (int i = 0; i < G; ++i) s_o2n[s_glist[i] + 2] = s_new_index[s_o2n[s_glist[i] + 2] + 2];
         }
     }
-    wave_sync_lds();
+    wave_lds_sync();
     if (s_scalar[3]) { bail(); return; }
     for (int j = lane; j < m; j += 64) lout[j] = s_o2n[lab[j] + 2];
     if (lane == 0) ok_out[c] = 1;

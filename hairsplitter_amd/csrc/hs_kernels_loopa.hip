@@ -24,9 +24,9 @@
 //     themselves (more | less << 16 per read, what loop B reads) only ever receive additions: no-return atomics on a zeroed row
 //     in global memory, nothing waits for them.
 //   * Equal counts among the second alleles are broken by the reference in the iteration order of its hash map. With up to six
-//     keys (8 buckets, no growth) that order is (home bucket, low five hash bits descending, insertion) -- tests/harness/
-//     rh8_static_order.cpp --, a byte per code made by k_loop_a_prepare; two tied keys with the same byte, more than six keys,
-//     and reference codes >= 128 (the reference's signed / unsigned comparison, :838) go through the emulator, one lane at a time.
+//     keys that order is hs::rh8_static_rank(code, false) (hs_rules.h), a byte per code made by k_loop_a_prepare; two tied keys with
+//     the same byte, more than six keys, and reference codes >= 128 (the reference's signed / unsigned comparison, :838) go through
+//     hs::second_from_seen on the emulator, one lane at a time.
 // A contig that does not fit (more than 2048 reads, 64 live partitions, a column with more than 15 codes / 128 reads / 4 words,
 // the partition pool, a counter beyond its width) is reported and done by the host (cv_phase_a_host).
 // Included by hs_capi.hip after hs_kernels_cols.hip.
@@ -66,7 +66,7 @@ struct LoopAShared {           // scratch of the emulator path (one wavefront pe
     int x_seen[16], x_cnt[16], x_first[16];
 };
 
-// computeChiSquare(...) > 15 (call_variants.cpp:1135-1163). The reference's own sequence of float / double operations (chi_square_dev)
+// computeChiSquare(...) > 15 (call_variants.cpp:1135-1163). The reference's own sequence of float / double operations (hs::chi_square)
 // decides only where a single-precision form of the same statistic, n (ad - bc)^2 / (row and column sums), comes within 2 of
 // the threshold; its relative error is a few 1e-7 on tables of at most a few hundred reads, the margin is 13 %
 static __device__ __forceinline__ bool chi_square_gt15(int n00, int n01, int n10, int n11) {
@@ -76,46 +76,15 @@ static __device__ __forceinline__ bool chi_square_gt15(int n00, int n01, int n10
     const float est = (float)(r0 + r1) * det * det / ((float)r0 * (float)r1 * (float)c0 * (float)c1);
     if (est < 13.0f) return false;
     if (est > 17.0f) return true;
-    Table2x2 t; t.n00 = n00; t.n01 = n01; t.n10 = n10; t.n11 = n11;
-    return chi_square_dev(t) > 15;
+    return hs::chi_square(n00, n01, n10, n11) > 15;
 }
 
-// place of a key in the iteration order of an 8-bucket robin_hood map (up to six keys): home bucket << 5 | 31 - low five hash bits
-static __device__ __forceinline__ int rh8_order_byte(int k) {
-    unsigned long long h = (unsigned long long)(k & 255);
-    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33;
-    h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
-    return (int)((((h >> 5) & 7ull) << 5) | (31ull - (h & 31ull)));
-}
-
-// second_from_seen() of the host (hs_host_cv.cpp): the most frequent eligible code among `seen` (first-appearance order) with
-// the reference's tie order; run by ONE lane (the tables in LDS belong to the wavefront)
+// hs::second_from_seen (hs_rules.h) on the wavefront's tables in LDS; run by ONE lane, and out of line: it is rare, and inlined
+// the emulator would cost the kernels twice their code
 template <class Sh>
-static __device__ int second_from_seen_dev(Sh& S, int nseen, int ref, bool quirk, bool insert_ref_last, int dflt) {
-    if (nseen == 0) return dflt;
-    const bool ref_eligible = quirk && ref >= 128;
-    int best = -1, nbest = 0, bestk = dflt;
-    bool ref_seen = false;
-    for (int i = 0; i < nseen; ++i) {
-        const int k = S.x_seen[i];
-        if (k == ref) { ref_seen = true; if (!ref_eligible) continue; }
-        if (S.x_cnt[i] > best) { best = S.x_cnt[i]; nbest = 1; bestk = k; } else if (S.x_cnt[i] == best) nbest++;
-    }
-    if (ref_eligible && !ref_seen && insert_ref_last) { if (0 > best) { best = 0; nbest = 1; bestk = ref; } else if (best == 0) nbest++; }
-    if (best < 0) return dflt;
-    if (nbest == 1) return bestk;
+static __device__ __noinline__ int second_from_seen_lds(Sh& S, int nseen, int ref, bool quirk, bool insert_ref_last, int dflt) {
     hs::Rh8View rh; rh.init(S.rh_info, S.rh_key, S.rh_tmp, 128);
-    for (int i = 0; i < nseen; ++i) rh.insert((uint8_t)S.x_seen[i]);
-    if (insert_ref_last) rh.insert((uint8_t)ref);
-    const int m = rh.order(S.rh_tmp);
-    for (int i = 0; i < m; ++i) {
-        const int k = S.rh_tmp[i];
-        if (k == ref && !ref_eligible) continue;
-        int c = 0;
-        for (int j = 0; j < nseen; ++j) if (S.x_seen[j] == k) { c = S.x_cnt[j]; break; }
-        if (c == best) return k;
-    }
-    return bestk;
+    return hs::second_from_seen(rh, S.rh_tmp, S.x_seen, S.x_cnt, nseen, ref, quirk, insert_ref_last, dflt);
 }
 
 // One wavefront per candidate column of the contigs the device walks (on_dev[contig - c_first] != 0), the others are left alone.
@@ -202,7 +171,7 @@ __global__ __launch_bounds__(256) void k_loop_a_prepare(
                 if (lane < nslots) { S.x_seen[lane] = slot_code; S.x_cnt[lane] = slot_cnt; }
                 wave_lds_sync();
                 if (lane == 0) {
-                    const int sc = second_from_seen_dev(S, nslots, ref, false, false, 0);
+                    const int sc = second_from_seen_lds(S, nslots, ref, false, false, 0);
                     int q = -1;
                     for (int i = 0; i < nslots; ++i) if (S.x_seen[i] == sc) q = i;
                     S.x_first[0] = q;
@@ -232,7 +201,7 @@ __global__ __launch_bounds__(256) void k_loop_a_prepare(
     if (lane >= 9 && lane < 16) hw[lane] = 0;
     if (lane < 16) S.x_cnt[lane] = 0;
     wave_lds_sync();
-    if (lane < nslots) S.x_cnt[perm] = (int)((unsigned)slot_code | ((unsigned)rh8_order_byte(slot_code) << 8) | ((unsigned)slot_cnt << 16));
+    if (lane < nslots) S.x_cnt[perm] = (int)((unsigned)slot_code | ((unsigned)hs::rh8_static_rank(slot_code, false) << 8) | ((unsigned)slot_cnt << 16));
     wave_lds_sync();
     if (lane < 16) h->slot[lane] = (unsigned)S.x_cnt[lane];
     unsigned long long word = 0ull;
@@ -262,12 +231,6 @@ __global__ __launch_bounds__(64) void k_loop_a_offsets(const int32_t* __restrict
         base += __builtin_amdgcn_readlane(incl, 63);
     }
     if (lane == 0) cand_off[c_count] = base;
-}
-
-static __device__ __forceinline__ unsigned long long la_rl64(unsigned long long v, int l) {      // v_readlane of a 64-bit value (l wave-uniform)
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v & 0xffffffffull), l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-    return ((unsigned long long)hi << 32) | lo;
 }
 
 #ifdef HS_LA_DIAG      // cycles of the sections of k_loop_a, summed over the wavefronts (diag[0..7]) + candidates (diag[8]) + emulator lanes (diag[9])
@@ -373,7 +336,7 @@ __global__ __launch_bounds__(64) void k_loop_a(
 #pragma unroll
         for (int w = 0; w < WW; ++w) {
             pr[w] = tb[w * HS_LA_SLOTS]; pl[w] = tb[(HS_LA_MAXW + w) * HS_LA_SLOTS]; mi[w] = tb[(2 * HS_LA_MAXW + w) * HS_LA_SLOTS];
-            an[w] = la_rl64(dw, w);
+            an[w] = readlane_u64(dw, w);
         }
         int shared = 0, decided = 0;
 #pragma unroll
@@ -393,7 +356,7 @@ __global__ __launch_bounds__(64) void k_loop_a(
                 const int info = __builtin_amdgcn_readlane(cur.hw, 16 + q);
                 int c = 0;
 #pragma unroll
-                for (int w = 0; w < WW; ++w) c += __popcll(la_rl64(dw, 4 * (q + 1) + w) & pr[w]);
+                for (int w = 0; w < WW; ++w) c += __popcll(readlane_u64(dw, 4 * (q + 1) + w) & pr[w]);
                 const int key = c ? ((c << 8) | (255 - ((info >> 8) & 255))) : 0;
                 nkeys += c ? 1 : 0;
                 const int lo_k = key < best_key ? key : best_key;
@@ -413,7 +376,7 @@ __global__ __launch_bounds__(64) void k_loop_a(
             const bool want = !skip & !need_exact;
             if (ref_slot == 0) {
 #pragma unroll
-                for (int w = 0; w < WW; ++w) { const unsigned long long x = la_rl64(dw, 4 + w); n11 += __popcll(x & pl[w]); n01 += __popcll(x & mi[w]); }
+                for (int w = 0; w < WW; ++w) { const unsigned long long x = readlane_u64(dw, 4 + w); n11 += __popcll(x & pl[w]); n01 += __popcll(x & mi[w]); }
             }
             n11 = want ? n11 : 0; n01 = want ? n01 : 0;
             // the words of the lane's own second allele: a gather across the lanes of `dw`
@@ -464,7 +427,7 @@ __global__ __launch_bounds__(64) void k_loop_a(
                             t = S.x_seen[j]; S.x_seen[j] = S.x_seen[j - 1]; S.x_seen[j - 1] = t;
                             t = S.x_cnt[j]; S.x_cnt[j] = S.x_cnt[j - 1]; S.x_cnt[j - 1] = t;
                         }
-                    const int second = second_from_seen_dev(S, nseen, ref, true, true, ' ');
+                    const int second = second_from_seen_lds(S, nseen, ref, true, true, ' ');
                     int sm = -1, ss = -1;
                     for (int q = 0; q < nslots; ++q) { if (S.code_of[q] == ref) sm = q; if (S.code_of[q] == second) ss = q; }
                     n11 = 0; n01 = 0; n10 = 0; n00 = 0;
@@ -534,9 +497,9 @@ __global__ __launch_bounds__(64) void k_loop_a(
 #pragma unroll
                 for (int w = 0; w < WW; ++w) {
                     const unsigned long long any = an[w];      // (uniform: made by v_readlane)
-                    const unsigned long long A = ref_slot == 0 ? la_rl64(dw, 4 + w) : 0ull;
-                    const unsigned long long a = sa >= 0 ? la_rl64(dw, 4 * (sa + 1) + w) : 0ull;
-                    const unsigned long long PR = la_rl64(pr[w], f), PL = la_rl64(pl[w], f), MI = la_rl64(mi[w], f);
+                    const unsigned long long A = ref_slot == 0 ? readlane_u64(dw, 4 + w) : 0ull;
+                    const unsigned long long a = sa >= 0 ? readlane_u64(dw, 4 * (sa + 1) + w) : 0ull;
+                    const unsigned long long PR = readlane_u64(pr[w], f), PL = readlane_u64(pl[w], f), MI = readlane_u64(mi[w], f);
                     const unsigned long long s_plus = (vA == 1 ? A : 0ull) | (va == 1 ? a : 0ull), s_minus = (vA == -1 ? A : 0ull) | (va == -1 ? a : 0ull);
                     const unsigned long long voting = s_plus | s_minus;
                     const unsigned long long fresh = any & ~PR;                              // not in the partition yet: takes the vote as it is
@@ -589,8 +552,8 @@ __global__ __launch_bounds__(64) void k_loop_a(
 #pragma unroll
             for (int w = 0; w < WW; ++w) {
                 const unsigned long long any = an[w];
-                const unsigned long long A = ref_slot == 0 ? la_rl64(dw, 4 + w) : 0ull;
-                const unsigned long long a = new_second >= 0 ? la_rl64(dw, 4 * (new_second + 1) + w) : 0ull;
+                const unsigned long long A = ref_slot == 0 ? readlane_u64(dw, 4 + w) : 0ull;
+                const unsigned long long a = new_second >= 0 ? readlane_u64(dw, 4 * (new_second + 1) + w) : 0ull;
                 if (lane == 0) { la_tab[0][wlo + w][s] = any; la_tab[1][wlo + w][s] = A; la_tab[2][wlo + w][s] = a; }
                 if (__builtin_amdgcn_inverse_ballot_w64(any)) { s_d[s][((wlo + w) & (HS_LA_RING - 1)) * 64 + lane] = 1; row[(wlo + w) * 64 + lane] = 1; }      // more = 1, less = 0
             }

@@ -96,8 +96,6 @@ static __device__ __forceinline__ void myers_peq_build(const MyersSeq& q, int r0
             for (uint32_t x = m[w]; x; x &= x - 1u) tab[((w << 5) + __builtin_ctz(x)) * 64 + lane] |= 1ull << r;
     }
 }
-// lane i takes the value of lane i - 1 (lane 0: zero): one DPP move across the whole wavefront
-static __device__ __forceinline__ int wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
 
 // The band of a sweep: block b (query rows 64 b .. 64 b + 63) is computed for the columns 64 b + lo .. 64 b + 63 + hi only
 // (Ukkonen: a cell on an alignment of at most k errors lies within k diagonals of where the alignment starts and of where it

@@ -7,12 +7,7 @@
 // tests/golden/robin_hood_order.json.
 #pragma once
 #include <stdint.h>
-
-#if defined(__HIPCC__)
-#define HS_HD __host__ __device__
-#else
-#define HS_HD
-#endif
+#include "hs_rules.h"      // HS_HD, rh8_mix and the multipliers
 
 namespace hs {
 
@@ -26,15 +21,13 @@ struct Rh8 {
     uint8_t info[kCap];
     uint8_t key[kCap];
 
-    HS_HD void clear() { mult = 0xc4ceb9fe1a85ec53ull; mask = 0; nslots = 0; count = 0; limit = 0; inc = 32; shift = 0; }
+    HS_HD void clear() { mult = kRh8Mult; mask = 0; nslots = 0; count = 0; limit = 0; inc = 32; shift = 0; }
 
     HS_HD static int load_limit(int buckets) { return buckets * 80 / 100; }
     HS_HD static int slots_for(int buckets) { int m = load_limit(buckets); return buckets + (m < 255 ? m : 255); }
 
     HS_HD void home(uint8_t k, int& idx, uint32_t& inf) const {
-        uint64_t h = (uint64_t)k;
-        h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33;
-        h *= mult; h ^= h >> 33;
+        const uint64_t h = rh8_mix(k, mult);
         inf = inc + (uint32_t)((h & 31u) >> shift);
         idx = (int)((h >> 5) & (uint64_t)mask);
     }
@@ -80,7 +73,7 @@ struct Rh8 {
     HS_HD void grow() {
         if (mask == 0) { alloc(8); return; }
         if (count < load_limit(mask + 1) && widen_distance_bits()) return;
-        mult += 0xc4ceb9fe1a85ec54ull;
+        mult += kRh8MultStep;
         if (count * 2 < load_limit(mask + 1)) rebuild(mask + 1);
         else rebuild((mask + 1) * 2);
     }
@@ -123,12 +116,10 @@ struct Rh8View {
 
     HS_HD void init(uint8_t* info_, uint8_t* key_, uint8_t* tmp_, int cap_) {
         info = info_; key = key_; tmp = tmp_; cap = cap_;
-        mult = 0xc4ceb9fe1a85ec53ull; mask = 0; nslots = 0; count = 0; limit = 0; inc = 32; shift = 0; overflow = false;
+        mult = kRh8Mult; mask = 0; nslots = 0; count = 0; limit = 0; inc = 32; shift = 0; overflow = false;
     }
     HS_HD void home(uint8_t k, int& idx, uint32_t& inf) const {
-        uint64_t h = (uint64_t)k;
-        h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33;
-        h *= mult; h ^= h >> 33;
+        const uint64_t h = rh8_mix(k, mult);
         inf = inc + (uint32_t)((h & 31u) >> shift);
         idx = (int)((h >> 5) & (uint64_t)mask);
     }
@@ -174,7 +165,7 @@ struct Rh8View {
     HS_HD void grow() {
         if (mask == 0) { alloc(8); return; }
         if (count < Rh8::load_limit(mask + 1) && widen_distance_bits()) return;
-        mult += 0xc4ceb9fe1a85ec54ull;
+        mult += kRh8MultStep;
         if (count * 2 < Rh8::load_limit(mask + 1)) rebuild(mask + 1);
         else rebuild((mask + 1) * 2);
     }

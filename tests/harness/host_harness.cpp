@@ -14,6 +14,7 @@
 #include <unordered_map>
 
 #include "../../hairsplitter_amd/csrc/hs_driver.h"
+#include "../../hairsplitter_amd/csrc/hs_rules.h"
 #include "../../oracle/hs_oracle.h"
 
 namespace hs {
@@ -103,8 +104,7 @@ struct OracleCvOps : hs::CvDeviceOps {
                 if (c1v > 5 * c2v) r.flags |= HS_COL_C1GT5C2;
                 if (is_cand[p]) r.flags |= HS_COL_CAND;
                 if (is_auto[p]) r.flags |= HS_COL_AUTO;
-                const int rb = r.k0, sb = r.k1;
-                if (c1v >= 5 && rb % 5 != sb % 5 && ((sb - '!') % 5 != 4 || (sb / 5 % 5 != rb % 5 && sb / 25 % 5 != rb % 5))) r.flags |= HS_COL_LOOPD;
+                if (c1v >= 5 && hs::central_base_test(r.k0, r.k1)) r.flags |= HS_COL_LOOPD;
                 out.n_entries += (int64_t)m.cols[p].content.size();
                 if (is_cand[p]) out.contig_n_cand[(size_t)(c - c0)]++;
                 xcols.push_back(x);

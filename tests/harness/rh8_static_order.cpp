@@ -1,5 +1,6 @@
-// TEST INFRASTRUCTURE: the rule k_robust_partitions uses to break ties between second alleles without replaying the
-// insertions on the hash-map emulator -- "a robin_hood map of up to 12 char keys iterates them by (home bucket ascending, low
+// TEST INFRASTRUCTURE: the rule the kernels use (hs::rh8_static_rank of hs_rules.h: K4's column_vs_partition_dev, K3b's
+// k_column_top3_exact, loop A's k_loop_a_prepare) to break ties between second alleles without replaying the insertions on the
+// hash-map emulator -- "a robin_hood map of up to 12 char keys iterates them by (home bucket ascending, low
 // five hash bits descending, insertion order), 8 buckets up to 6 keys, 16 buckets and the next multiplier from 7 to 12, unless
 // some key sits 6 or more slots from its home bucket" -- against hs_rh8.h (itself pinned to the reference's header by
 // tests/golden/robin_hood_order.json) on random key sets, half of them from small alphabets so that buckets collide.
@@ -9,15 +10,11 @@
 #include <cstdlib>
 #include <vector>
 #include "../../hairsplitter_amd/csrc/hs_rh8.h"
-static void home_low(uint8_t k, uint64_t mult, int buckets, int& home, int& low) {
-    uint64_t h = k; h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= mult; h ^= h >> 33;
-    home = (int)((h >> 5) & (uint64_t)(buckets - 1)); low = (int)(h & 31);
-}
+#include "../../hairsplitter_amd/csrc/hs_rules.h"
 int main(int argc, char** argv) {
     const long trials = argc > 1 ? std::atol(argv[1]) : 2000000;
     long bad = 0, checked = 0, collisions = 0, displaced = 0;
     srand(3);
-    const uint64_t m0 = 0xc4ceb9fe1a85ec53ull, m1 = m0 + 0xc4ceb9fe1a85ec54ull;
     for (long it = 0; it < trials; ++it) {
         int n = 1 + rand() % 12;
         const int alpha = (it & 1) ? 125 : 24;
@@ -31,7 +28,7 @@ int main(int argc, char** argv) {
         const bool big = n > 6;
         std::vector<int> rank((size_t)n);
         int cnt[16] = {0};
-        for (int i = 0; i < n; ++i) { int home, low; home_low(keys[(size_t)i], big ? m1 : m0, big ? 16 : 8, home, low); rank[(size_t)i] = home * 32 + (31 - low); cnt[home]++; }
+        for (int i = 0; i < n; ++i) { rank[(size_t)i] = hs::rh8_static_rank(keys[(size_t)i], big); cnt[rank[(size_t)i] >> 5]++; }
         bool far = false;
         if (big) { int carry = 0; for (int b = 0; b < 16; ++b) { if (cnt[b] > 0 && carry + cnt[b] - 1 >= 6) far = true; carry = std::max(0, carry + cnt[b] - 1); } }
         if (far) { displaced++; continue; }      // the kernel hands these to the emulator

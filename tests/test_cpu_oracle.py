@@ -89,8 +89,8 @@ def test_hash_map_view_holds_every_key_set_of_the_path(built):
 
 
 def test_rh8_static_order(built):
-    """The closed form k_robust_partitions uses for the iteration order of small hash maps (hs_kernels_parts.hip) against the
-    emulator, on two million random key sets"""
+    """The closed form the kernels use for the iteration order of small hash maps (hs::rh8_static_rank of hs_rules.h, called by
+    column_vs_partition_dev of K4, k_column_top3_exact and k_loop_a_prepare) against the emulator, on two million random key sets"""
     exe = os.path.join(ROOT, "tests", "harness", "_build", "rh8_static_order")
     r = subprocess.run([exe, "2000000"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout
