@@ -25,6 +25,7 @@ SYMBOLS = [
     "hs_edit_distance", "hs_cv_batch_create", "hs_cv_batch_destroy", "hs_cv_batch_aligned_bp", "hs_cv_run",
     "hs_cv_result_destroy", "hs_cv_select", "hs_cv_run_range", "hs_cv_selection_destroy", "hs_sr_run", "hs_sr_run_cv", "hs_sr_run_cv_range", "hs_pipeline_create", "hs_pipeline_select", "hs_pipeline_run", "hs_pipeline_destroy", "hs_pipeline_thread_devices", "hs_cv_batch_device", "hs_sr_result_destroy", "hs_sr_window_size", "hs_call_variants_main", "hs_call_variants_epilogue",
     "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_edlib_align", "hs_edlib_align_bytes", "hs_alignment_to_cigar", "hs_reattach_ends", "hs_trim_polished", "hs_reattach_ends_bytes", "hs_trim_polished_bytes", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
+    "hs_polish_inputs", "hs_polish_inputs_from_files", "hs_polish_result_destroy", "hs_polish_inputs_main",
 ]
 
 HS_NKERNELS = 28
@@ -968,6 +969,122 @@ def gaf_from_labels(gfa: str, reads: str, sam: str, sr: Dict, out_gaf: str, cont
     _check(load().hs_gaf_from_labels(gfa.encode(), reads.encode(), sam.encode(), C.c_int32(1 if amplicon else 0), C.c_int32(len(win_off) - 1),
                                      ptr(win_off), ptr(win_start), ptr(win_end), ptr(label_off), ptr(labels), None if has is None else ptr(has),
                                      out_gaf.encode(), C.c_int32(n_threads)))
+
+
+# ---- next stage: the polisher's inputs (device work on the resident batch) ---------------------------------
+POLISH_START_BEYOND_SEQ = 2      # piece_flags bit: posOnReadStart lies beyond the read (the reference's substr throws there); the piece is empty
+_POLISH_I32_BUNDLE = ("bundle_contig", "bundle_interval", "bundle_start", "bundle_end", "bundle_group", "bundle_left_to_polish",
+                      "bundle_right_to_polish", "bundle_overhang_left", "bundle_overhang_right")
+_POLISH_I32_PIECE = ("piece_rec", "piece_read_start", "piece_read_end", "piece_sam_pos", "piece_flags")
+
+
+class PolishResult(C.Structure):
+    _fields_ = ([("n_bundles", C.c_int64), ("n_pieces", C.c_int64), ("n_dropped", C.c_int64)] +
+                [(k, C.POINTER(C.c_int32)) for k in _POLISH_I32_BUNDLE] +
+                [("backbone_off", C.POINTER(C.c_int64)), ("backbone", C.POINTER(C.c_uint8)), ("piece_off", C.POINTER(C.c_int64))] +
+                [(k, C.POINTER(C.c_int32)) for k in _POLISH_I32_PIECE] +
+                [("base_off", C.POINTER(C.c_int64)), ("bases", C.POINTER(C.c_uint8)), ("cig_off", C.POINTER(C.c_int64)),
+                 ("cigar", C.POINTER(C.c_uint32)), ("dropped", C.POINTER(C.c_int32)),
+                 ("t_scan_ms", C.c_double), ("t_cut_ms", C.c_double), ("t_gather_ms", C.c_double), ("t_cigar_ms", C.c_double),
+                 ("n_tasks", C.c_int64), ("n_rounds", C.c_int64), ("cut_ops_read", C.c_int64)])
+
+
+def polish_inputs(batch_or_pipeline, sr: Dict, polish_everything: bool = False, c0: int = 0, c1: Optional[int] = None,
+                  contig_has_snps=None) -> Dict:
+    """The polisher's inputs of the reference's stage 5 (create_new_contigs.cpp:358-521) for the contigs [c0, c1) of a resident
+    batch (a CvBatch or a PipelineGroups) from a stage-4 result `sr` (win_off, win_start, win_end, label_off, labels, as
+    gaf_from_labels takes them). Returns numpy arrays: per bundle (one group of one merged interval) bundle_* and backbone_off /
+    backbone (toPolish, text), piece_off; per piece piece_* , base_off / bases (text), cig_off / cigar (len << 4 | op); dropped
+    [n][3] = (contig, interval, record) of the reads the walk drops; "stats" = kernel times and counts of the call."""
+    batch = getattr(batch_or_pipeline, "batch", batch_or_pipeline)
+    lib = load()
+    win_off = _np(sr["win_off"], np.int64); win_start = _np(sr["win_start"], np.int32); win_end = _np(sr["win_end"], np.int32)
+    label_off = _np(sr["label_off"], np.int64); labels = _np(sr["labels"], np.int32)
+    has = None if contig_has_snps is None else _np(np.asarray(contig_has_snps).astype(np.uint8), np.uint8)
+    if len(win_off) - 1 != batch.flat.n_contigs:
+        raise HsError("polish_inputs: the result does not cover the contigs of the batch")
+    if c1 is None:
+        c1 = batch.flat.n_contigs
+
+    def ptr(a):
+        return a.ctypes.data_as(C.c_void_p)
+    res = C.POINTER(PolishResult)()
+    lib.hs_polish_inputs.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.POINTER(C.POINTER(PolishResult))]
+    lib.hs_polish_result_destroy.argtypes = [C.c_void_p]
+    lib.hs_polish_result_destroy.restype = None
+    _check(lib.hs_polish_inputs(batch.handle, C.c_int32(c0), C.c_int32(c1), ptr(win_off), ptr(win_start), ptr(win_end), ptr(label_off), ptr(labels),
+                                None if has is None else ptr(has), C.c_int32(1 if polish_everything else 0), C.byref(res)))
+    try:
+        r = res.contents
+        B, P, D = int(r.n_bundles), int(r.n_pieces), int(r.n_dropped)
+
+        def arr(p, n, dtype):
+            return np.ctypeslib.as_array(p, (n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
+        out = {"n_bundles": B, "n_pieces": P}
+        for k in _POLISH_I32_BUNDLE:
+            out[k] = arr(getattr(r, k), B, np.int32)
+        for k in _POLISH_I32_PIECE:
+            out[k] = arr(getattr(r, k), P, np.int32)
+        out["backbone_off"] = arr(r.backbone_off, B + 1, np.int64)
+        out["piece_off"] = arr(r.piece_off, B + 1, np.int64)
+        out["base_off"] = arr(r.base_off, P + 1, np.int64)
+        out["cig_off"] = arr(r.cig_off, P + 1, np.int64)
+        out["backbone"] = arr(r.backbone, int(out["backbone_off"][-1]), np.uint8)
+        out["bases"] = arr(r.bases, int(out["base_off"][-1]), np.uint8)
+        out["cigar"] = arr(r.cigar, int(out["cig_off"][-1]), np.uint32)
+        out["dropped"] = arr(r.dropped, 3 * D, np.int32).reshape(D, 3)
+        out["stats"] = {"scan_ms": r.t_scan_ms, "cut_ms": r.t_cut_ms, "gather_ms": r.t_gather_ms, "cigar_ms": r.t_cigar_ms,
+                        "n_tasks": int(r.n_tasks), "n_rounds": int(r.n_rounds), "cut_ops_read": int(r.cut_ops_read)}
+    finally:
+        lib.hs_polish_result_destroy(res)
+    return out
+
+
+def polish_inputs_from_files(gfa: str, reads: str, sam: str, gro: str, out_path: str, polish_everything: bool = False, n_threads: int = 1) -> None:
+    """The same from the four files HS_create_new_contigs reads, written as the text of bin/hs_polish_inputs."""
+    _check(load().hs_polish_inputs_from_files(gfa.encode(), reads.encode(), sam.encode(), gro.encode(), C.c_int32(1 if polish_everything else 0),
+                                              out_path.encode(), C.c_int32(n_threads)))
+
+
+def polish_cigar_string(words) -> str:
+    return "".join("%d%s" % (int(w) >> 4, "MIDNSHP=X"[int(w) & 15]) for w in words)
+
+
+def polish_bundle_text(res: Dict, i: int, contig_name: Optional[str] = None) -> str:
+    """Bundle i as bin/hs_polish_inputs writes it"""
+    p0, p1 = int(res["piece_off"][i]), int(res["piece_off"][i + 1])
+    head = [contig_name if contig_name is not None else str(int(res["bundle_contig"][i]))] + [
+        str(int(res[k][i])) for k in ("bundle_start", "bundle_end", "bundle_group", "bundle_left_to_polish", "bundle_right_to_polish",
+                                      "bundle_overhang_left", "bundle_overhang_right")] + [str(p1 - p0)]
+    out = ["BUNDLE\t" + "\t".join(head), ">seq", res["backbone"][int(res["backbone_off"][i]):int(res["backbone_off"][i + 1])].tobytes().decode()]
+    for p in range(p0, p1):
+        b0, b1 = int(res["base_off"][p]), int(res["base_off"][p + 1])
+        if b1 > b0:      # tools.cpp:357: empty pieces are left out
+            out.append(">read%d %d %s" % (p - p0, int(res["piece_sam_pos"][p]), polish_cigar_string(res["cigar"][int(res["cig_off"][p]):int(res["cig_off"][p + 1])])))
+            out.append(res["bases"][b0:b1].tobytes().decode())
+    return "\n".join(out) + "\n"
+
+
+def polish_bundle_files(res: Dict, i: int, dir: str, id: str = "0") -> Dict:
+    """Bundle i as the files the reference's consensus_reads hands to its polisher (tools.cpp:351-361): unpolished_<id>.fasta and
+    reads_<id>.fasta, plus mapped_<id>.sam built from the clipped CIGARs -- the SAM of the commented-out block at tools.cpp:383-392,
+    which makes the minimap2 run of :374-380 unnecessary: `racon reads_<id>.fasta mapped_<id>.sam unpolished_<id>.fasta`."""
+    p0, p1 = int(res["piece_off"][i]), int(res["piece_off"][i + 1])
+    backbone = res["backbone"][int(res["backbone_off"][i]):int(res["backbone_off"][i + 1])].tobytes().decode()
+    paths = {k: os.path.join(dir, "%s_%s.%s" % (k, id, ext)) for k, ext in (("unpolished", "fasta"), ("reads", "fasta"), ("mapped", "sam"))}
+    with open(paths["unpolished"], "w") as f:
+        f.write(">seq\n" + backbone + "\n")
+    with open(paths["reads"], "w") as fr, open(paths["mapped"], "w") as fs:
+        fs.write("@HD\tVN:1.6\tSO:coordinate\n@SQ\tSN:seq\tLN:%d\n" % len(backbone))
+        for p in range(p0, p1):
+            b0, b1 = int(res["base_off"][p]), int(res["base_off"][p + 1])
+            if b1 == b0:
+                continue
+            seq = res["bases"][b0:b1].tobytes().decode()
+            fr.write(">read%d\n%s\n" % (p - p0, seq))
+            fs.write("read%d\t0\tseq\t%d\t60\t%s\t*\t0\t0\t%s\t*\tAS:i:0\tXS:i:0\n" % (
+                p - p0, int(res["piece_sam_pos"][p]), polish_cigar_string(res["cigar"][int(res["cig_off"][p]):int(res["cig_off"][p + 1])]), seq))
+    return paths
 
 
 def edlib_hw_align(pairs, path=True):

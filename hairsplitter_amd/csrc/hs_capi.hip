@@ -5,7 +5,9 @@
 //   hs_cv_backend.inc    stage 3 on the device (hs_cv_batch, HipCvOps)
 //   hs_sr_backend.inc    stage 4 on the device (GraphRows, HipSrOps)
 //   hs_capi_stage.inc    stage-level C ABI on one device, contig groups (hs_pipeline_*)
-//   hs_capi_multi.inc    several GPUs in one process There is no CPU fallback anywhere in this file: without a usable HIP device every entry
+//   hs_capi_multi.inc    several GPUs in one process
+//   hs_capi_polish.inc   the polisher's inputs of the next stage (hs_polish_inputs)
+// There is no CPU fallback anywhere in this file: without a usable HIP device every entry
 // point fails with HS_ENODEVICE.
 #include <hip/hip_runtime.h>
 #include <malloc.h>
@@ -37,6 +39,7 @@
 #include "hs_kernels_myers.hip"
 #include "hs_kernels_cols.hip"
 #include "hs_kernels_loopa.hip"
+#include "hs_kernels_polish.hip"
 
 namespace hs {
 static thread_local std::string g_err;
@@ -60,3 +63,4 @@ using hs::set_error;
 #include "hs_sr_backend.inc"
 #include "hs_capi_stage.inc"
 #include "hs_capi_multi.inc"
+#include "hs_capi_polish.inc"

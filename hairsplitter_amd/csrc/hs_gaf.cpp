@@ -37,7 +37,7 @@ namespace hs {
 namespace {
 
 struct GafLink { long n1; int e1; long n2; int e2; };
-typedef std::pair<std::pair<int, int>, std::vector<int>> GafInterval;             // (start, end), label of every record of the contig
+typedef LabelledInterval GafInterval;                                            // (start, end), label of every record of the contig
 typedef std::vector<std::pair<std::string, bool>> GafSteps;                      // (new contig name, same orientation as the read)
 struct GafPath { std::pair<int, int> on_read; GafSteps steps; long backbone; };
 
@@ -359,6 +359,24 @@ int write_gaf(const GafModel& m, const std::string& out_path, GafStats& st) {
     return HS_OK;
 }
 
+// the windows of one contig of an hs_sr_result as the reference's partitions: one label per record, carried by the record that
+// represents its read on this contig -- the last one (see the header). key_of(k): what identifies the read of record k
+template <class Key, class KeyOf>
+int windows_to_intervals(int n, KeyOf key_of, int64_t w0, int64_t w1, const int32_t* win_start, const int32_t* win_end, const int64_t* label_off,
+                         const int32_t* labels, std::vector<GafInterval>& ivs, const char* who) {
+    std::unordered_map<Key, int> last_of;
+    for (int k = 0; k < n; ++k) last_of[key_of(k)] = k;
+    for (int64_t w = w0; w < w1; ++w) {
+        if (label_off[w + 1] - label_off[w] != n) { set_error(std::string(who) + ": a window does not hold one label per record"); return HS_EINVAL; }
+        const int32_t* lab = labels + label_off[w];
+        std::vector<int> full((size_t)n, -2);
+        for (int k = 0; k < n; ++k)
+            if (lab[k] != -2) full[(size_t)last_of[key_of(k)]] = lab[k];
+        ivs.push_back(std::make_pair(std::make_pair((int)win_start[w], (int)win_end[w]), full));
+    }
+    return HS_OK;
+}
+
 int build_model(const std::string& gfa, const CvFileInput& in, GafModel& m) {
     m.in = &in;
     m.n_reads = (long)in.read_names.size(); m.n_contigs = (long)in.contig_names.size();
@@ -391,22 +409,47 @@ int gaf_from_labels(const std::string& gfa, const CvFileInput& in, int n_contigs
     for (long c = 0; c < m.n_contigs; ++c) {
         if (contig_has_snps ? !contig_has_snps[c] : win_off[c + 1] == win_off[c]) continue;   // a contig with SNPs has at least one window
         const int r0 = in.contig_rec_off[(size_t)c], n = in.contig_rec_off[(size_t)c + 1] - r0;
-        // the record that represents a read name on this contig: the last one (see the header)
-        std::unordered_map<std::string, int> last_of;
-        for (int k = 0; k < n; ++k) last_of[in.read_names[(size_t)in.rec_read[(size_t)(r0 + k)]]] = k;
-        std::vector<GafInterval>& ivs = m.partitions[m.n_reads + c];
-        for (int64_t w = win_off[c]; w < win_off[c + 1]; ++w) {
-            if (label_off[w + 1] - label_off[w] != n) { set_error("gaf_from_labels: a window does not hold one label per record"); return HS_EINVAL; }
-            const int32_t* lab = labels + label_off[w];
-            std::vector<int> full((size_t)n, -2);
-            for (int k = 0; k < n; ++k)
-                if (lab[k] != -2) full[(size_t)last_of[in.read_names[(size_t)in.rec_read[(size_t)(r0 + k)]]]] = lab[k];
-            ivs.push_back(std::make_pair(std::make_pair((int)win_start[w], (int)win_end[w]), full));
-        }
+        if (int rc = windows_to_intervals<std::string>(n, [&](int k) -> const std::string& { return in.read_names[(size_t)in.rec_read[(size_t)(r0 + k)]]; },
+                                                       win_off[c], win_off[c + 1], win_start, win_end, label_off, labels, m.partitions[m.n_reads + c], "gaf_from_labels"))
+            return rc;
     }
     GafStats st;
     for (auto& kv : m.partitions) merge_intervals(kv.second, st);
     return write_gaf(m, out_gaf, st);
+}
+
+// ---- internal entries of the polishing inputs (hs_capi_polish.inc): the merged intervals of every contig, labels by record index on
+// the contig, without the GAF model around them. has[c] = the contig has an entry in `partitions` (possibly without intervals).
+int polish_intervals_from_gro(const CvFileInput& in, const std::string& gro, std::vector<std::vector<LabelledInterval>>& ivs, std::vector<uint8_t>& has) {
+    GafModel m;
+    m.in = &in;
+    m.n_reads = (long)in.read_names.size(); m.n_contigs = (long)in.contig_names.size();
+    if (int rc = parse_gro(gro, m)) return rc;
+    GafStats st;
+    ivs.assign((size_t)m.n_contigs, {}); has.assign((size_t)m.n_contigs, 0);
+    for (auto& kv : m.partitions) {
+        merge_intervals(kv.second, st);
+        has[(size_t)(kv.first - m.n_reads)] = 1;
+        ivs[(size_t)(kv.first - m.n_reads)].swap(kv.second);
+    }
+    return HS_OK;
+}
+
+int polish_intervals_from_labels(int n_contigs, const int32_t* contig_rec_off, const int32_t* rec_read, const int64_t* win_off, const int32_t* win_start,
+                                 const int32_t* win_end, const int64_t* label_off, const int32_t* labels, const uint8_t* contig_has_snps,
+                                 std::vector<std::vector<LabelledInterval>>& ivs, std::vector<uint8_t>& has) {
+    GafStats st;
+    ivs.assign((size_t)n_contigs, {}); has.assign((size_t)n_contigs, 0);
+    for (int c = 0; c < n_contigs; ++c) {
+        if (contig_has_snps ? !contig_has_snps[c] : win_off[c + 1] == win_off[c]) continue;
+        const int r0 = contig_rec_off[c], n = contig_rec_off[c + 1] - r0;
+        if (int rc = windows_to_intervals<int32_t>(n, [&](int k) { return rec_read[r0 + k]; }, win_off[c], win_off[c + 1], win_start, win_end, label_off, labels,
+                                                   ivs[(size_t)c], "hs_polish_inputs"))
+            return rc;
+        has[(size_t)c] = 1;
+        merge_intervals(ivs[(size_t)c], st);
+    }
+    return HS_OK;
 }
 
 }  // namespace hs

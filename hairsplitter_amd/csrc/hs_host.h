@@ -148,6 +148,13 @@ int gaf_from_files(const std::string& gfa, const std::string& reads, const std::
 int gaf_from_labels(const std::string& gfa, const CvFileInput& in, int n_contigs, const int64_t* win_off, const int32_t* win_start,
                     const int32_t* win_end, const int64_t* label_off, const int32_t* labels, const uint8_t* contig_has_snps,
                     const std::string& out_gaf);
+// the merged intervals of every contig ((start, end), label of every record of the contig) for the polishing inputs (hs_capi_polish.inc):
+// parse_split_file / the windows of an hs_sr_result, then merge_intervals, as hs_gaf.cpp implements them for the GAF
+typedef std::pair<std::pair<int, int>, std::vector<int>> LabelledInterval;
+int polish_intervals_from_gro(const CvFileInput& in, const std::string& gro, std::vector<std::vector<LabelledInterval>>& ivs, std::vector<uint8_t>& has);
+int polish_intervals_from_labels(int n_contigs, const int32_t* contig_rec_off, const int32_t* rec_read, const int64_t* win_off, const int32_t* win_start,
+                                 const int32_t* win_end, const int64_t* label_off, const int32_t* labels, const uint8_t* contig_has_snps,
+                                 std::vector<std::vector<LabelledInterval>>& ivs, std::vector<uint8_t>& has);
 
 // the calling thread's persistent worker pool (hs_driver.cpp)
 void hs_parallel_for(int n, int n_threads, const std::function<void(int)>& f);

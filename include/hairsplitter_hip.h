@@ -588,6 +588,56 @@ int hs_gaf_from_labels(const char* gfa, const char* reads, const char* sam, int3
 int hs_gro_to_gaf_main(int argc, char** argv);
 
 /* ------------------------------------------------------------------------------------------------
+ * Next stage, the polisher's inputs (device work on the resident batch): for every merged interval of every contig and every
+ * group of reads, the backbone piece and the pieces of the reads that the reference hands to its polisher.  Replaces the loop
+ * of modify_GFA, create_new_contigs.cpp:358-521: the bounds of :371-375, the base-by-base CIGAR walk of :392-447 (on the
+ * run-length ops, one wavefront per (interval, read)), the cut of the read or of its reverse complement (:453-459), the
+ * clipped CIGAR (:460-462, convert_cigar2 of tools.cpp:61-80), the groups of :478-506 and toPolish of :517-519.  What
+ * consensus_reads writes from them (tools.cpp:351-361) is what the tool below writes.  No consensus, no GFA.
+ *
+ * A bundle = one group of one interval; bundles come contig by contig, interval by interval, group label ascending (the
+ * reference iterates an unordered_map).  A bundle exists only where the reference polishes: more than one cluster in the
+ * interval, or polish_everything (:523).  Pieces of a bundle are in record order; piece k of a bundle is read<k> of
+ * reads_<id>.fasta.  All arrays are host memory, released by hs_polish_result_destroy.
+ * ---------------------------------------------------------------------------------------------- */
+#define HS_POLISH_START_BEYOND_SEQ 2   /* piece_flags: posOnReadStart lies beyond the read (the reference's substr throws, :459): empty piece */
+typedef struct hs_polish_result {
+    int64_t n_bundles, n_pieces, n_dropped;
+    /* per bundle */
+    int32_t *bundle_contig, *bundle_interval /* index among the contig's merged intervals */, *bundle_start, *bundle_end, *bundle_group,
+        *bundle_left_to_polish, *bundle_right_to_polish, *bundle_overhang_left, *bundle_overhang_right;   /* :371-375 */
+    int64_t* backbone_off;      /* [n_bundles + 1] into backbone: toPolish (:517-519), text */
+    uint8_t* backbone;
+    int64_t* piece_off;         /* [n_bundles + 1]: the bundle's pieces */
+    /* per piece */
+    int32_t *piece_rec /* index of the record on its contig */, *piece_read_start, *piece_read_end /* posOnReadStart / posOnReadEnd */,
+        *piece_sam_pos /* startPosition, :394-395 */, *piece_flags;
+    int64_t* base_off;          /* [n_pieces + 1] into bases: clippedRead (:459), text */
+    uint8_t* bases;
+    int64_t* cig_off;           /* [n_pieces + 1] into cigar: clippedCIGAR (:460-462) as len << 4 | op words (none for an empty range) */
+    uint32_t* cigar;
+    int32_t* dropped;           /* [n_dropped][3]: contig, interval, record on the contig of the reads whose label became -2 (:444-447) */
+    /* accounting (HIP events around the launches): the cursor table, k_polish_cut, k_polish_gather (reads + backbones), k_polish_cigar */
+    double t_scan_ms, t_cut_ms, t_gather_ms, t_cigar_ms;
+    int64_t n_tasks, n_rounds, cut_ops_read;   /* (interval, read) tasks; rounds of HS_POLISH_CHUNK_MB; CIGAR ops k_polish_cut loaded, in whole 64-op chunks */
+} hs_polish_result;
+/* windows + labels exactly as hs_gaf_from_labels takes them (all contigs of the batch); bundles of the contigs [c0, c1).
+ * polish_everything: the contigs without partitions get the default interval of :249-251.  The output goes through device
+ * scratch of HS_POLISH_CHUNK_MB (default 1024) megabytes: a larger call runs in several rounds over contig sub-ranges. */
+int hs_polish_inputs(hs_cv_batch* b, int32_t c0, int32_t c1, const int64_t* win_off, const int32_t* win_start, const int32_t* win_end,
+                     const int64_t* label_off, const int32_t* labels, const uint8_t* contig_has_snps, int32_t polish_everything,
+                     hs_polish_result** out);
+/* the same from the four files HS_create_new_contigs reads (main, :1586-1595), written as text: per bundle a line
+ * "BUNDLE <contig> <interval start> <interval end> <group> <leftToPolish> <rightToPolish> <overhangLeft> <overhangRight> <reads>"
+ * (tab-separated), then ">seq" and toPolish, then per non-empty piece ">read<k> <startPosition> <CIGAR>" and the piece
+ * (tools.cpp:351-361). */
+int hs_polish_inputs_from_files(const char* gfa, const char* reads, const char* sam, const char* gro, int32_t polish_everything,
+                                const char* out_path, int32_t n_threads);
+void hs_polish_result_destroy(hs_polish_result* r);
+/* argv = <gfa> <reads> <sam> <gro> <polish_everything:0|1> <out> [threads] */
+int hs_polish_inputs_main(int argc, char** argv);
+
+/* ------------------------------------------------------------------------------------------------
  * Upstream feeders of stage 3 that are plain text transforms (host code): the 300 kb cutter the orchestrator runs before the
  * reads are aligned (src/cut_gfa.py:33-66, hairsplitter.py:583) and the GFA -> FASTA converter (src/gfa2fa.cpp).
  * hs_cut_gfa_main: argv of cut_gfa.py (--assembly/-a, --length/-l, --output/-o); hs_gfa2fa_main: argv[1] = gfa, FASTA on

@@ -1,0 +1,85 @@
+"""The polisher's inputs (hs_polish_inputs: k_polish_cut, k_polish_gather) on a job of a bench configuration, with the labels of one
+pipeline step: own time of the two kernels (HIP events around their launches), algorithmic bytes and the fraction of the HBM peak,
+median of `runs` calls after a warm-up. Next to it, where oracle/_ref holds HS_create_new_contigs, the wall time of the reference's
+stage 5 on the files of the same job with the stand-in executables of tools/record_polish_goldens.py (no polisher runs), on one
+thread and on 16: its parsing and the .gaf are inside that time, the external tools are not.
+Usage: python tools/polish_bench.py [config=C4] [contigs=0: the configuration's own] [runs=5]      (prints one JSON line)"""
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+HBM_PEAK_GBS = 8000.0      # MI355X HBM3E
+OWN = {"C2": 256, "C3": 50, "C4": 500, "C5": 34}
+
+
+def reference_wall(paths, files, gro, td, threads):
+    import record_polish_goldens as rec
+    tools, tmp = os.path.join(td, "standins"), os.path.join(td, "cnc_tmp_%d" % threads)
+    os.makedirs(tools, exist_ok=True); os.makedirs(tmp)
+    cap = os.path.join(td, "capture_%d" % threads)
+    os.makedirs(cap)
+    rec._script(os.path.join(tools, "minimap2"), rec.MINIMAP2)
+    rec._script(os.path.join(tools, "samtools"), "#!/bin/sh\nexit 0\n")
+    rec._script(os.path.join(tools, "racon"), "#!/bin/sh\nexit 1\n")
+    env = dict(os.environ, HS_POLISH_CAPTURE=cap, PATH=tools + os.pathsep + os.environ.get("PATH", ""))
+    t0 = time.perf_counter()
+    r = subprocess.run([paths["ref_cnc"], files["gfa"], files["reads"], "0.05", gro, files["sam"], tmp + "/", str(threads), "ont", os.path.join(tmp, "o.gfa"),
+                        os.path.join(tmp, "o.gaf"), "racon", "0", "0", os.path.join(tools, "minimap2"), os.path.join(tools, "racon"), "/nonexistent/medaka",
+                        os.path.join(tools, "samtools"), "/nonexistent/python", "0"], cwd=tmp, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return {"threads": threads, "seconds": time.perf_counter() - t0, "exit_status": r.returncode, "bundles_handed_to_the_polisher": len(os.listdir(cap))}
+
+
+def main():
+    cfg = sys.argv[1] if len(sys.argv) > 1 else "C4"
+    n = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    runs = max(5, int(sys.argv[3])) if len(sys.argv) > 3 else 5
+    n = n or OWN.get(cfg, 50)
+    import __graft_entry__ as ge
+    from hairsplitter_amd import synth
+    paths = ge.paths()
+    with tempfile.TemporaryDirectory() as td:
+        contigs, files = synth.generate_job(cfg, list(range(n)), workers=min(16, os.cpu_count() or 1), outdir=td)      # before the GPU is touched (forks)
+        from hairsplitter_amd import api
+        api.require_gpu()
+        pl = api.PipelineGroups(contigs, 4)
+        cv, sr = pl.run_fused(0.33, 0, rarest_strain_abundance=0.01)
+        samples = []
+        for i in range(runs + 1):
+            t0 = time.perf_counter()
+            res = api.polish_inputs(pl, sr)
+            wall = time.perf_counter() - t0
+            if i:      # the first call is the warm-up
+                samples.append((res["stats"], wall))
+        st = res["stats"]
+        piece_bytes = int(res["base_off"][-1]) + int(res["backbone_off"][-1])
+        bytes_of = {"cut": 4 * st["cut_ops_read"] + 64 * st["n_tasks"], "gather": 2 * piece_bytes}      # ops read + task in / out; piece bytes in plus out
+        out = {"config": cfg, "contigs": n, "aligned_bp": int(pl.aligned_bp), "runs": runs, "bundles": res["n_bundles"], "pieces": res["n_pieces"],
+               "tasks": st["n_tasks"], "rounds": st["n_rounds"], "piece_bytes": piece_bytes, "cigar_words": int(res["cig_off"][-1]),
+               "call_wall_ms_median": statistics.median(w for _, w in samples) * 1e3}
+        for k in ("scan", "cut", "gather", "cigar"):
+            ms = statistics.median(s[k + "_ms"] for s, _ in samples)
+            out["k_polish_" + k] = {"ms_median": ms}
+            if k in bytes_of and ms > 0:
+                gbs = bytes_of[k] / (ms * 1e-3) / 1e9
+                out["k_polish_" + k].update({"algorithmic_bytes": bytes_of[k], "GBs": gbs, "frac_of_hbm_peak": gbs / HBM_PEAK_GBS})
+        pl.close()
+        if os.path.exists(paths["ref_cnc"]):
+            col, vcf, err, gro = (os.path.join(td, x) for x in ("v.col", "v.vcf", "err.txt", "reads_haplo.gro"))
+            subprocess.run([paths["cv"], files["gfa"], files["reads"], files["sam"], "16", td, err, "0", "0", col, vcf, "0.33"], check=True, stdout=subprocess.DEVNULL)
+            e = min(float(open(err).read().strip()), 0.15)
+            subprocess.run([paths["sr"], col, "16", str(e), os.path.join(td, "no_ploidy"), "0", "0.01", "0", gro, "0"], check=True, stdout=subprocess.DEVNULL)
+            out["reference_create_new_contigs"] = [reference_wall(paths, files, gro, td, t) for t in (1, 16)]
+        print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
