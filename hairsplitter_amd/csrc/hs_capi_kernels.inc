@@ -547,98 +547,44 @@ int hs_simdiff(const uint64_t* d_alt, const uint64_t* d_ref, const int64_t* d_pl
 }
 
 
-int hs_edit_distance(const uint8_t* d_query, const int64_t* d_query_off, const uint8_t* d_target,
-                     const int64_t* d_target_off, int32_t n_pairs, int32_t mode, int32_t* d_dist, int32_t* d_end,
-                     void* stream) {
-    if (int rc = require_device()) return rc;
-    if (n_pairs <= 0) return HS_OK;
-    if (mode < 0 || mode > 2) { set_error("hs_edit_distance: mode must be 0 (NW), 1 (SHW) or 2 (HW)"); return HS_EINVAL; }
-    // the offsets come back once: short queries share a wavefront (8 / 16 / 32 lanes per pair), the others take one each with the
-    // hand-over row between two passes of 64 blocks as scratch (see hs_kernels_myers.hip)
-    std::vector<int64_t> toff((size_t)n_pairs + 1), qoff((size_t)n_pairs + 1);
-    HS_HIP(hipMemcpy(toff.data(), d_target_off, sizeof(int64_t) * toff.size(), hipMemcpyDeviceToHost));
-    HS_HIP(hipMemcpy(qoff.data(), d_query_off, sizeof(int64_t) * qoff.size(), hipMemcpyDeviceToHost));
-    std::vector<int32_t> cls[4];
-    std::vector<int64_t> hs_off((size_t)n_pairs + 1, 0);
-    const bool no_groups = std::getenv("HS_MYERS_NO_GROUPS") != nullptr;
-    for (int i = 0; i < n_pairs; ++i) {
-        const int64_t qn = qoff[(size_t)i + 1] - qoff[(size_t)i], tn = toff[(size_t)i + 1] - toff[(size_t)i];
-        const int64_t nb = (qn + 63) / 64;
-        const int c = (no_groups || nb > 32) ? 3 : nb <= 8 ? 0 : nb <= 16 ? 1 : 2;
-        cls[c].push_back(i);
-        hs_off[(size_t)i + 1] = hs_off[(size_t)i] + (c == 3 ? ((tn + 64 + 3) & ~(int64_t)3) + 4 * (tn + 64) : 0);
-    }
-    std::vector<int32_t> ids;
-    size_t cls_off[5] = {0, 0, 0, 0, 0};
-    for (int c = 0; c < 4; ++c) { ids.insert(ids.end(), cls[c].begin(), cls[c].end()); cls_off[c + 1] = ids.size(); }
-    DBuf scratch, d_ho, d_ids;
-    UploadPack pk;
-    pk.add(hs_off, d_ho); pk.add(ids, d_ids);
-    if (int rc = pk.commit((hipStream_t)stream)) return rc;
-    if (int rc = scratch.alloc(std::max<size_t>((size_t)hs_off.back(), 1))) return rc;
-    const int32_t* idp = d_ids.as<int32_t>();
-#define HS_MYERS_DIST_GROUPED(G, c)                                                                                                                       \
-    if (!cls[c].empty())                                                                                                                                  \
-        hipLaunchKernelGGL(hsdev::k_myers_distance_grouped<G>, dim3((unsigned)((cls[c].size() + 64 / G - 1) / (64 / G))), dim3(64), 0, (hipStream_t)stream, d_query, \
-                           d_query_off, d_target, d_target_off, idp + cls_off[c], (int)cls[c].size(), mode, d_dist, d_end);
-    HS_MYERS_DIST_GROUPED(8, 0)
-    HS_MYERS_DIST_GROUPED(16, 1)
-    HS_MYERS_DIST_GROUPED(32, 2)
-#undef HS_MYERS_DIST_GROUPED
-    if (!cls[3].empty())
-        hipLaunchKernelGGL(hsdev::k_myers_distance, dim3((unsigned)cls[3].size()), dim3(64), 0, (hipStream_t)stream, d_query, d_query_off, d_target, d_target_off,
-                           idp + cls_off[3], (int)cls[3].size(), mode, scratch.as<int8_t>(), d_ho.as<int64_t>(), d_dist, d_end);
-    HS_HIP(hipGetLastError());
-    if (int rc_w = stream_wait((hipStream_t)stream)) return rc_w;
-    return HS_OK;
-}
-
-// One class of pairs (0: 8 lanes, 1: 16, 2: 32, 3: a wavefront) through the path kernel of one edlib mode.
+// One class of pairs (0: 8 lanes, 1: 16, 2: 32, 3: a wavefront) through the path kernel of one edlib mode and one tier of equality
+// vectors (0: codes 0..3; 1 / 2: symbols and an equality table in LDS / in scratch, hs_kernels_myers.hip).
 extern "C++" {
 struct MyersPathArgs {
     const uint8_t* query; const int64_t* qo; const uint8_t* target; const int64_t* to; int8_t* hs; const int64_t* ho;
     unsigned long long* st; const int64_t* so; int32_t* cols; int k, task;
     int32_t *dist, *start, *end, *nloc; uint8_t* ops; const int64_t* oo; int32_t* ops_len;
-    int tier; hsdev::MyersEq eq;      // 0: codes 0..3; 1 / 2: symbols and an equality table in LDS / in scratch (hs_kernels_myers.hip)
+    hsdev::MyersEq eq;
 };
 template <int MODE, int TIER>
-static void myers_path_launch_eq(const MyersPathArgs& a, int cls, const int32_t* ids, int n, hipStream_t s) {
-#define HS_MYERS_GROUPED_EQ(G)                                                                                                                            \
-    hipLaunchKernelGGL((hsdev::k_myers_hw_path_grouped_eq<G, MODE, TIER>), dim3((unsigned)((n + 64 / G - 1) / (64 / G))), dim3(64), 0, s, a.query, a.qo,  \
-                       a.target, a.to, ids, n, a.st, a.so, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len, a.eq)
-    if (cls == 0) HS_MYERS_GROUPED_EQ(8);
-    else if (cls == 1) HS_MYERS_GROUPED_EQ(16);
-    else if (cls == 2) HS_MYERS_GROUPED_EQ(32);
-    else
-        hipLaunchKernelGGL((hsdev::k_myers_hw_path_eq<MODE, TIER>), dim3((unsigned)n), dim3(64), 0, s, a.query, a.qo, a.target, a.to, ids, n, a.hs, a.ho, a.st,
-                           a.so, a.cols, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len, a.eq);
-#undef HS_MYERS_GROUPED_EQ
-}
-template <int MODE>
 static void myers_path_launch(const MyersPathArgs& a, int cls, const int32_t* ids, int n, hipStream_t s) {
-    if (a.tier == 1) return myers_path_launch_eq<MODE, 1>(a, cls, ids, n, s);
-    if (a.tier == 2) return myers_path_launch_eq<MODE, 2>(a, cls, ids, n, s);
 #define HS_MYERS_GROUPED(G)                                                                                                                               \
-    hipLaunchKernelGGL((hsdev::k_myers_hw_path_grouped<G, MODE>), dim3((unsigned)((n + 64 / G - 1) / (64 / G))), dim3(64), 0, s, a.query, a.qo, a.target, \
-                       a.to, ids, n, a.st, a.so, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len)
+    hipLaunchKernelGGL((hsdev::k_myers_hw_path_grouped<G, MODE, TIER>), dim3((unsigned)((n + 64 / G - 1) / (64 / G))), dim3(64), 0, s, a.query, a.qo,     \
+                       a.target, a.to, ids, n, a.st, a.so, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len, a.eq)
+#define HS_MYERS_WAVE(LOCATE_ONLY)                                                                                                                        \
+    hipLaunchKernelGGL((hsdev::k_myers_hw_path<MODE, TIER, LOCATE_ONLY>), dim3((unsigned)n), dim3(64), 0, s, a.query, a.qo, a.target, a.to, ids, n, a.hs, \
+                       a.ho, a.st, a.so, a.cols, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len, a.eq)
     if (cls == 0) HS_MYERS_GROUPED(8);
     else if (cls == 1) HS_MYERS_GROUPED(16);
     else if (cls == 2) HS_MYERS_GROUPED(32);
-    else
-        hipLaunchKernelGGL(hsdev::k_myers_hw_path<MODE>, dim3((unsigned)n), dim3(64), 0, s, a.query, a.qo, a.target, a.to, ids, n, a.hs, a.ho, a.st, a.so,
-                           a.cols, a.k, a.task, a.dist, a.start, a.end, a.nloc, a.ops, a.oo, a.ops_len);
+    else {
+        if constexpr (TIER == 0)      // task 0 on four codes: the instantiation without steps 2 and 3 (72-79 VGPRs instead of 110)
+            if (a.task == 0) { HS_MYERS_WAVE(true); return; }
+        HS_MYERS_WAVE(false);
+    }
 #undef HS_MYERS_GROUPED
+#undef HS_MYERS_WAVE
 }
 }  // extern "C++"
 
 // A1 as edlibAlign(query, target, edlibNewAlignConfig(k, mode, task, NULL, 0)) (see hs_kernels_myers.hip): mode 0 NW, 1 SHW, 2 HW;
 // task 0 distance, 1 locations, 2 path (d_ops required). Host offsets; the device buffers of the sequences and results are the
-// caller's. d_nloc may be NULL. eqs != nullptr: the sequences are symbols 0 .. n_sym - 1 and eqs->mask (device) their equality
-// rows (hs_edlib_align_bytes below); the scratch table of tier 2 (n_sym x 64 words per wavefront) counts against the budget.
-struct MyersEqCall { int tier, n_sym, words; const uint32_t* d_mask; };
+// caller's. d_nloc may be NULL. tier 1 / 2: the sequences are symbols 0 .. eq.n_sym - 1 and eq.mask (device) their equality
+// rows (hs_edlib_align_bytes below); the scratch table of tier 2 (n_sym x 64 words per wavefront, eq.gtab: set here) counts
+// against the budget.
 static int edlib_align_launch(const char* who, const uint8_t* d_query, const int64_t* h_query_off, const uint8_t* d_target, const int64_t* h_target_off,
                               int32_t n_pairs, int32_t mode, int32_t task, int32_t k, int32_t* d_dist, int32_t* d_start, int32_t* d_end, int32_t* d_nloc,
-                              uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream, const MyersEqCall* eqs = nullptr) {
+                              uint8_t* d_ops, const int64_t* h_ops_off, int32_t* d_ops_len, void* stream, int tier = 0, hsdev::MyersEq eq = {nullptr, 0, 0, nullptr}) {
     if (int rc = require_device()) return rc;
     if (n_pairs <= 0) return HS_OK;
     if (mode < 0 || mode > 2 || task < 0 || task > 2) { set_error(std::string(who) + ": mode must be 0 (NW), 1 (SHW) or 2 (HW), task 0 (distance), 1 (locations) or 2 (path)"); return HS_EINVAL; }
@@ -652,7 +598,7 @@ static int edlib_align_launch(const char* who, const uint8_t* d_query, const int
     std::vector<int32_t> cls[4];      // 0: 8 lanes, 1: 16, 2: 32, 3: a wavefront
     const bool no_groups = std::getenv("HS_MYERS_NO_GROUPS") != nullptr;      // (diagnostic, read at every call: every pair on a wavefront of its own)
     std::vector<int64_t> need_st((size_t)n_pairs, 0), need_hs((size_t)n_pairs, 0);
-    const int64_t tab_words = (eqs && eqs->tier == 2) ? (int64_t)eqs->n_sym * 64 : 0;      // per wavefront; counted per pair (grouped pairs share one)
+    const int64_t tab_words = tier == 2 ? (int64_t)eq.n_sym * 64 : 0;      // per wavefront; counted per pair (grouped pairs share one)
     for (int i = 0; i < n_pairs; ++i) {
         const int64_t qn = qo[(size_t)i + 1] - qo[(size_t)i], tn = to[(size_t)i + 1] - to[(size_t)i];
         const int64_t nb = (qn + 63) / 64;
@@ -698,16 +644,15 @@ static int edlib_align_launch(const char* who, const uint8_t* d_query, const int
     if (int rc = d_cols.alloc(std::max<size_t>(path && !cls[3].empty() ? (size_t)(qo.back() - qo.front()) * 2 : 0, 1) * sizeof(int32_t))) return rc;      // Hirschberg's two columns
     if (int rc = d_tab.alloc(std::max<size_t>((size_t)max_tab, 1) * 8)) return rc;
     const int32_t* idp = d_ids.as<int32_t>();
+    eq.gtab = d_tab.as<unsigned long long>();
     const MyersPathArgs args{d_query, d_qo.as<int64_t>(), d_target, d_to.as<int64_t>(), d_hs.as<int8_t>(), d_ho.as<int64_t>(), d_st.as<unsigned long long>(),
                              d_so.as<int64_t>(), d_cols.as<int32_t>(), k, task, d_dist, d_start, d_end, d_nloc, path ? d_ops : nullptr,
-                             path ? d_oo.as<int64_t>() : nullptr, d_ops_len, eqs ? eqs->tier : 0,
-                             eqs ? hsdev::MyersEq{eqs->d_mask, eqs->n_sym, eqs->words, d_tab.as<unsigned long long>()} : hsdev::MyersEq{nullptr, 0, 0, nullptr}};
-    for (const Slice& sl : slices) {
-        const int n = (int)(sl.end - sl.begin);
-        if (mode == 0) myers_path_launch<0>(args, sl.cls, idp + sl.begin, n, (hipStream_t)stream);
-        else if (mode == 1) myers_path_launch<1>(args, sl.cls, idp + sl.begin, n, (hipStream_t)stream);
-        else myers_path_launch<2>(args, sl.cls, idp + sl.begin, n, (hipStream_t)stream);
-    }
+                             path ? d_oo.as<int64_t>() : nullptr, d_ops_len, eq};
+    static constexpr decltype(&myers_path_launch<0, 0>) launch[3][3] = {      // [mode][tier]
+        {myers_path_launch<0, 0>, myers_path_launch<0, 1>, myers_path_launch<0, 2>},
+        {myers_path_launch<1, 0>, myers_path_launch<1, 1>, myers_path_launch<1, 2>},
+        {myers_path_launch<2, 0>, myers_path_launch<2, 1>, myers_path_launch<2, 2>}};
+    for (const Slice& sl : slices) launch[mode][tier](args, sl.cls, idp + sl.begin, (int)(sl.end - sl.begin), (hipStream_t)stream);
     HS_HIP(hipGetLastError());
     return stream_wait((hipStream_t)stream);   // the scratch goes back to the pool with this scope
 }
@@ -724,6 +669,25 @@ int hs_edlib_align(const uint8_t* d_query, const int64_t* h_query_off, const uin
                    int32_t* d_ops_len, void* stream) {
     return edlib_align_launch("hs_edlib_align", d_query, h_query_off, d_target, h_target_off, n_pairs, mode, task, k, d_dist, d_start, d_end, d_nloc, d_ops,
                               h_ops_off, d_ops_len, stream);
+}
+
+// hs_edlib_align with TASK_DISTANCE and k = -1 for a caller whose offsets are on the device: they come back once, and the start
+// locations the kernels write (-1 for this task) go to scratch.
+int hs_edit_distance(const uint8_t* d_query, const int64_t* d_query_off, const uint8_t* d_target,
+                     const int64_t* d_target_off, int32_t n_pairs, int32_t mode, int32_t* d_dist, int32_t* d_end,
+                     void* stream) {
+    if (int rc = require_device()) return rc;
+    if (n_pairs <= 0) return HS_OK;
+    if (mode < 0 || mode > 2) { set_error("hs_edit_distance: mode must be 0 (NW), 1 (SHW) or 2 (HW)"); return HS_EINVAL; }
+    std::vector<int64_t> toff((size_t)n_pairs + 1), qoff((size_t)n_pairs + 1);
+    HS_HIP(hipMemcpy(toff.data(), d_target_off, sizeof(int64_t) * toff.size(), hipMemcpyDeviceToHost));
+    HS_HIP(hipMemcpy(qoff.data(), d_query_off, sizeof(int64_t) * qoff.size(), hipMemcpyDeviceToHost));
+    DBuf d_start;
+    if (int rc = d_start.alloc(sizeof(int32_t) * (size_t)n_pairs)) return rc;
+    const int rc = edlib_align_launch("hs_edit_distance", d_query, qoff.data(), d_target, toff.data(), n_pairs, mode, 0, -1, d_dist, d_start.as<int32_t>(), d_end,
+                                      nullptr, nullptr, nullptr, nullptr, stream);      // (waits for the stream: the scratch of this scope is free after it)
+    if (rc != HS_OK) stream_wait_quiet((hipStream_t)stream);      // an error after the launches: the kernels may still write d_start
+    return rc;
 }
 
 // edlibAlign with additionalEqualities on raw bytes (edlib.cpp:61-92 EqualityDefinition, :357-380 buildPeq, :1422-1460
@@ -765,11 +729,10 @@ int hs_edlib_align_bytes(const uint8_t* d_query, const int64_t* h_query_off, con
         mask[(size_t)a * words + (b >> 5)] |= 1u << (b & 31); mask[(size_t)b * words + (a >> 5)] |= 1u << (a & 31);
         extra = true;
     }
-    MyersEqCall eqs{(A <= 4 && !extra) ? 0 : A <= 16 ? 1 : 2, A, words, nullptr};
+    const int tier = (A <= 4 && !extra) ? 0 : A <= 16 ? 1 : 2;
     UploadPack pk;
     pk.add(map, d_map); pk.add(mask, d_mask);
     if (int rc = pk.commit(st)) return rc;
-    eqs.d_mask = d_mask.as<uint32_t>();
     if (int rc = d_sq.alloc((size_t)std::max<int64_t>(nq, 1))) return rc;
     if (int rc = d_st.alloc((size_t)std::max<int64_t>(nt, 1))) return rc;
     if (nq > 0) hipLaunchKernelGGL(hsdev::k_myers_compact, dim3((unsigned)std::min<int64_t>(4096, (nq + 1023) / 1024)), dim3(256), 0, st, d_query + q0, nq, d_map.as<uint8_t>(), d_sq.as<uint8_t>());
@@ -778,7 +741,7 @@ int hs_edlib_align_bytes(const uint8_t* d_query, const int64_t* h_query_off, con
     std::vector<int64_t> qo((size_t)n_pairs + 1), to((size_t)n_pairs + 1);
     for (int i = 0; i <= n_pairs; ++i) { qo[(size_t)i] = h_query_off[i] - q0; to[(size_t)i] = h_target_off[i] - t0; }
     const int rc = edlib_align_launch("hs_edlib_align_bytes", d_sq.as<uint8_t>(), qo.data(), d_st.as<uint8_t>(), to.data(), n_pairs, mode, task, k, d_dist, d_start,
-                                      d_end, d_nloc, d_ops, h_ops_off, d_ops_len, stream, &eqs);      // (waits for the stream: the scratch of this scope is free after it)
+                                      d_end, d_nloc, d_ops, h_ops_off, d_ops_len, stream, tier, hsdev::MyersEq{d_mask.as<uint32_t>(), A, words, nullptr});      // (waits for the stream: the scratch of this scope is free after it)
     if (rc != HS_OK) stream_wait_quiet(st);      // refused arguments: the pre-passes still run on this scope's scratch
     return rc;
 }

@@ -21,17 +21,19 @@
 //      computation that is exact on the cells of alignments within the bound gives the same decisions: whole columns
 //      (oracle/edlib_path_oracle.py, numpy, pinned against the reference's edlib up to 60 kb) or the static band of the sweeps
 //      here (MyersBand below).
-// Kernels: k_myers_hw_path<MODE> (a wavefront per pair, any length), k_myers_hw_path_grouped<8|16|32, MODE> (short queries, 64 / G
-// pairs per wavefront), k_myers_distance / k_myers_distance_grouped<G> (hs_edit_distance: NW / SHW / HW distance + first end location).
-// The path kernels take edlib's three modes (hs_edlib_align; HW is what stage 5 calls): NW and SHW skip step 2 (start location 0)
+// Kernels: k_myers_hw_path<MODE, TIER> (a wavefront per pair, any length) and k_myers_hw_path_grouped<8|16|32, MODE, TIER> (short
+// queries, 64 / G pairs per wavefront) behind every entry: hs_edlib_hw_align, hs_edlib_align, hs_edlib_align_bytes and
+// hs_edit_distance (task 0, k = -1: step 1 alone, whose bound search is myers_locate / myers_locate_grouped). Task 0 of four-code
+// pairs on a wavefront each runs k_myers_hw_path<MODE, 0, LOCATE_ONLY = true>: steps 2 and 3 compiled out, 72-79 VGPRs instead of 110.
+// They take edlib's three modes (hs_edlib_align; HW is what stage 5 calls): NW and SHW skip step 2 (start location 0)
 // and run step 3 on target[0 .. end] -- the whole target for NW. With a bound k >= 0, step 1 is one sweep in the band of k and an
 // optimum above k is reported as edlib reports it (distance -1, no location, no path); steps 2 and 3 are bounded by the distance
 // found, as edlib bounds them, so a pair within k gets the same locations and path as with k = -1.
 // Alignment ops as edlib's: 0 match, 1 insertion (query base without target base), 2 deletion, 3 mismatch.
-// Sequences are 2-bit base codes (A C G T), as everywhere on this path -- or, in the table forms of the path kernels
-// (k_myers_hw_path_eq<MODE, TIER>, k_myers_hw_path_grouped_eq<G, MODE, TIER>; hs_edlib_align_bytes), symbols of any byte alphabet
-// with edlib's additionalEqualities: the equality vectors of a block then come from a table in LDS (up to 16 symbols) or in
-// device scratch (up to 256) instead of four registers (MyersEq below). Included by hs_capi.hip after hs_kernels.hip.
+// Sequences are 2-bit base codes (A C G T), as everywhere on this path (TIER 0) -- or, in the table forms (TIER 1 / 2;
+// hs_edlib_align_bytes), symbols of any byte alphabet with edlib's additionalEqualities: the equality vectors of a block then
+// come from a table in LDS (up to 16 symbols) or in device scratch (up to 256) instead of four registers (MyersEq below, which
+// TIER 0 does not read). Included by hs_capi.hip after hs_kernels.hip.
 #pragma once
 #define MY_TCHUNK 2048      /* target columns staged in LDS at a time */
 
@@ -310,38 +312,61 @@ static __device__ __forceinline__ int myers_first_bound(int mode, int qn, int tn
 // that bound, holds it (edlibAlign doubles its bound from 64 instead, :194-214; the answer does not depend on the bounds tried:
 // the first one that holds the optimum returns it exactly). kb >= 0: one sweep in the band of kb (HW: of at most the query
 // length, :566-569); an optimum above kb is d = -1, as is an NW pair whose lengths differ by more than kb (:746-749).
+struct MyersLoc { int d, e, n; };
 template <int MODE, int TIER>
-static __device__ void myers_locate(const MyersSeq& q, const MyersSeq& t, int kb, int8_t* __restrict__ hb, int32_t* __restrict__ hbot, uint8_t* tbuf,
-                                    int& d, int& e, int& n, const MyersEq& eq) {
+static __device__ __forceinline__ MyersLoc myers_locate(const MyersSeq q, const MyersSeq t, int kb, int8_t* __restrict__ hb, int32_t* __restrict__ hbot, uint8_t* tbuf, const MyersEq& eq) {
     const int qn = q.n, tn = t.n;
     const int kmax = MODE == 0 ? max(qn, tn) : qn;
-    d = -1; e = -1; n = 0;
-    if (kb >= 0 && MODE == 0 && kb < abs(tn - qn)) return;
+    if (kb >= 0 && MODE == 0 && kb < abs(tn - qn)) return MyersLoc{-1, -1, 0};
     int sc, best, first, last, cnt;
     for (int k = kb >= 0 ? min(kb, kmax) : myers_first_bound(MODE, qn, tn);;) {
         const bool all = k >= kmax;
         myers_sweep<TIER>(q, t, MODE, myers_mode_band(MODE, qn, tn, k, all), hb, hbot, tbuf, nullptr, nullptr, sc, best, first, last, &cnt, eq);
         const int got = MODE == 0 ? sc : best;
-        if (all || got <= k) { d = got; e = MODE == 0 ? tn - 1 : first; n = MODE == 0 ? 1 : cnt; return; }
-        if (kb >= 0) return;
+        if (all || got <= k) return MyersLoc{got, MODE == 0 ? tn - 1 : first, MODE == 0 ? 1 : cnt};
+        if (kb >= 0) return MyersLoc{-1, -1, 0};
         k = got >= MY_INF ? 2 * k : got;
     }
+}
+template <int G, int TIER = 0>      // (defined with the grouped kernel below)
+static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const MyersSeq& t, int mode, MyersBand band, uint8_t* __restrict__ tb, unsigned long long* __restrict__ store,
+                                           int& out_score, int& out_best, int& out_first, int& out_last, int* out_count = nullptr, const MyersEq& eq = MyersEq());
+// The same rule with G lanes per pair: every group of the wavefront at its own bound, the sweeps repeated until no group is
+// pending (a group that has its answer idles in them). act: this group holds a pair with a non-empty query and target.
+template <int G, int MODE, int TIER>
+static __device__ MyersLoc myers_locate_grouped(bool act, const MyersSeq q, const MyersSeq t, int kb, uint8_t* tb, const MyersEq& eq) {
+    const int qn = q.n, tn = t.n;
+    const int kmax = MODE == 0 ? max(qn, tn) : qn;
+    MyersLoc r{-1, -1, 0};
+    int sc, best, first, last, cnt;
+    int k = kb >= 0 ? min(kb, kmax) : myers_first_bound(MODE, qn, tn);
+    bool pending = act && !(kb >= 0 && MODE == 0 && kb < abs(tn - qn));
+    while (__ballot(pending) != 0ull) {
+        const bool all = k >= kmax;
+        myers_sweep_grouped<G, TIER>(pending, q, t, MODE, myers_mode_band(MODE, qn, tn, k, all), tb, nullptr, sc, best, first, last, &cnt, eq);
+        if (pending) {
+            const int got = MODE == 0 ? sc : best;
+            if (all || got <= k) { pending = false; r.d = got; r.e = MODE == 0 ? tn - 1 : first; r.n = MODE == 0 ? 1 : cnt; }
+            else if (kb >= 0) pending = false;
+            else k = got >= MY_INF ? 2 * k : got;
+        }
+    }
+    return r;
 }
 
 #ifndef MY_WAVES_PER_EU
 #define MY_WAVES_PER_EU 1
 #endif
 // task: 0 distance (no start location), 1 locations, 2 locations and path. kbound < 0: no bound. n_loc may be null.
-#define MY_PATH_PARAMS                                                                                                             \
-    const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,                  \
-    const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list, int8_t* __restrict__ hscratch,       \
-    const int64_t* __restrict__ hscratch_off, unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off,       \
-    int32_t* __restrict__ col_scratch, int kbound, int task,                                                                       \
-    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc, int32_t* __restrict__ n_loc,       \
-    uint8_t* __restrict__ ops, const int64_t* __restrict__ ops_off, int32_t* __restrict__ ops_len
-#define MY_PATH_ARGS query, query_off, target, target_off, pair_ids, n_list, hscratch, hscratch_off, store, store_off, col_scratch, kbound, task, dist, start_loc, end_loc, n_loc, ops, ops_off, ops_len
-template <int MODE, int TIER>
-static __device__ __forceinline__ void myers_path_pair(MY_PATH_PARAMS, const MyersEq& eq) {
+// LOCATE_ONLY: steps 2 and 3 compiled out, for task 0 only (four codes: long pairs of hs_edit_distance at more wavefronts per SIMD).
+template <int MODE, int TIER, bool LOCATE_ONLY = false>
+__global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(
+    const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,
+    const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list, int8_t* __restrict__ hscratch,
+    const int64_t* __restrict__ hscratch_off, unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off,
+    int32_t* __restrict__ col_scratch, int kbound, int task,
+    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc, int32_t* __restrict__ n_loc,
+    uint8_t* __restrict__ ops, const int64_t* __restrict__ ops_off, int32_t* __restrict__ ops_len, MyersEq eq) {
     __shared__ uint8_t tbuf[MY_TCHUNK + 64];
     __shared__ int s_stack[40][5];
     const int lane = lane_id();
@@ -364,14 +389,14 @@ static __device__ __forceinline__ void myers_path_pair(MY_PATH_PARAMS, const Mye
     }
     int sc, best, first, last;
     // 1. distance, first end location, number of end locations
-    int d, e, nl;
-    myers_locate<MODE, TIER>(MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, kbound, hb, hbot, tbuf, d, e, nl, eq);
+    const MyersLoc loc = myers_locate<MODE, TIER>(MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, kbound, hb, hbot, tbuf, eq);
+    const int d = loc.d, e = loc.e, nl = loc.n;
     if (d < 0) {   // above the bound (:212-215): no location, no path
         if (lane == 0) { dist[pr] = -1; end_loc[pr] = -1; start_loc[pr] = -1; if (n_loc) n_loc[pr] = 0; if (ops_len) ops_len[pr] = 0; }
         return;
     }
     if (lane == 0 && n_loc) n_loc[pr] = nl;
-    if (task == 0) {      // TASK_DISTANCE: edlib finds no start location (:223-224)
+    if (LOCATE_ONLY || task == 0) {      // TASK_DISTANCE: edlib finds no start location (:223-224)
         if (lane == 0) { dist[pr] = d; end_loc[pr] = e; start_loc[pr] = -1; }
         return;
     }
@@ -457,12 +482,6 @@ static __device__ __forceinline__ void myers_path_pair(MY_PATH_PARAMS, const Mye
     }
     if (lane == 0) ops_len[pr] = n_out;
 }
-template <int MODE>
-__global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path(MY_PATH_PARAMS) { myers_path_pair<MODE, 0>(MY_PATH_ARGS, MyersEq()); }
-template <int MODE, int TIER>      // the table forms: sequences of symbols, equality vectors from eq (MyersEq above)
-__global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path_eq(MY_PATH_PARAMS, MyersEq eq) { myers_path_pair<MODE, TIER>(MY_PATH_ARGS, eq); }
-#undef MY_PATH_PARAMS
-#undef MY_PATH_ARGS
 
 // ---- short queries: G lanes per pair, 64 / G pairs per wavefront ----------------------------------------------------------
 // The stage-5 call sites align 200-300 bases (five 64-row blocks): with a wavefront per pair five lanes of 64 work. Here a pair
@@ -470,10 +489,10 @@ __global__ __launch_bounds__(64, MY_WAVES_PER_EU) void k_myers_hw_path_eq(MY_PAT
 // per-pair quantity lives in the lanes of its group, the loops run to the longest pair of the wavefront and a group that is
 // done idles under the exec mask. Same sweeps, same band, same traceback as above.
 #define MY_GCHUNK 1024
-template <int G, int TIER = 0>
+template <int G, int TIER>
 static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const MyersSeq& t, int mode, MyersBand band, uint8_t* __restrict__ tb /* this group's LDS [MY_GCHUNK + 64] */,
                                            unsigned long long* __restrict__ store, int& out_score, int& out_best, int& out_first, int& out_last,
-                                           int* out_count = nullptr, const MyersEq& eq = MyersEq()) {
+                                           int* out_count, const MyersEq& eq) {
     const int lane = lane_id(), gl = lane & (G - 1);
     unsigned long long* const tab = MyersPeqTab<TIER>::get(eq);
     const int qn = q.n, tn = t.n;
@@ -577,15 +596,13 @@ static __device__ void myers_sweep_grouped(bool active, const MyersSeq& q, const
     if (out_count) *out_count = __shfl(n_best, owner, 64);
 }
 
-#define MY_GROUP_PARAMS                                                                                                            \
-    const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,                  \
-    const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list,                                      \
-    unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off, int kbound, int task,                           \
-    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc, int32_t* __restrict__ n_loc,       \
-    uint8_t* __restrict__ ops, const int64_t* __restrict__ ops_off, int32_t* __restrict__ ops_len
-#define MY_GROUP_ARGS query, query_off, target, target_off, pair_ids, n_list, store, store_off, kbound, task, dist, start_loc, end_loc, n_loc, ops, ops_off, ops_len
 template <int G, int MODE, int TIER>
-static __device__ __forceinline__ void myers_path_groups(MY_GROUP_PARAMS, const MyersEq& eq) {
+__global__ __launch_bounds__(64) void k_myers_hw_path_grouped(
+    const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,
+    const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list,
+    unsigned long long* __restrict__ store, const int64_t* __restrict__ store_off, int kbound, int task,
+    int32_t* __restrict__ dist, int32_t* __restrict__ start_loc, int32_t* __restrict__ end_loc, int32_t* __restrict__ n_loc,
+    uint8_t* __restrict__ ops, const int64_t* __restrict__ ops_off, int32_t* __restrict__ ops_len, MyersEq eq) {
     constexpr int NG = 64 / G;
     __shared__ __attribute__((aligned(16))) uint8_t tbuf[NG][MY_GCHUNK + 64];
     const int lane = lane_id(), gl = lane & (G - 1), grp = lane / G;
@@ -603,21 +620,10 @@ static __device__ __forceinline__ void myers_path_groups(MY_GROUP_PARAMS, const 
         if (n_loc) n_loc[pr] = 1;
         if (ops_len) ops_len[pr] = 0;
     }
-    int sc, best, first, last, cnt;
-    // 1. as myers_locate, every group at its own bound
-    const int kmax = MODE == 0 ? max(qn, tn) : qn;
-    int k = kbound >= 0 ? min(kbound, kmax) : myers_first_bound(MODE, qn, tn), d = -1, e = -1, nl = 0;
-    bool pending = act && !(kbound >= 0 && MODE == 0 && kbound < abs(tn - qn));
-    while (__ballot(pending) != 0ull) {
-        const bool all = k >= kmax;
-        myers_sweep_grouped<G, TIER>(pending, MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, MODE, myers_mode_band(MODE, qn, tn, k, all), tb, nullptr, sc, best, first, last, &cnt, eq);
-        if (pending) {
-            const int got = MODE == 0 ? sc : best;
-            if (all || got <= k) { pending = false; d = got; e = MODE == 0 ? tn - 1 : first; nl = MODE == 0 ? 1 : cnt; }
-            else if (kbound >= 0) pending = false;
-            else k = got >= MY_INF ? 2 * k : got;
-        }
-    }
+    int sc, best, first, last;
+    // 1. distance, first end location, number of end locations
+    const MyersLoc loc = myers_locate_grouped<G, MODE, TIER>(act, MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, kbound, tb, eq);
+    const int d = loc.d, e = loc.e, nl = loc.n;
     if (act && d < 0) {      // above the bound: no location, no path
         if (gl == 0) { dist[pr] = -1; end_loc[pr] = -1; start_loc[pr] = -1; if (n_loc) n_loc[pr] = 0; if (ops_len) ops_len[pr] = 0; }
         act = false;
@@ -649,12 +655,6 @@ static __device__ __forceinline__ void myers_path_groups(MY_GROUP_PARAMS, const 
     __builtin_amdgcn_wave_barrier();
     if (act && gl == 0) ops_len[pr] = myers_traceback(sto, (qn + 63) >> 6, band, qn, an, sc, op);
 }
-template <int G, int MODE>
-__global__ __launch_bounds__(64) void k_myers_hw_path_grouped(MY_GROUP_PARAMS) { myers_path_groups<G, MODE, 0>(MY_GROUP_ARGS, MyersEq()); }
-template <int G, int MODE, int TIER>
-__global__ __launch_bounds__(64) void k_myers_hw_path_grouped_eq(MY_GROUP_PARAMS, MyersEq eq) { myers_path_groups<G, MODE, TIER>(MY_GROUP_ARGS, eq); }
-#undef MY_GROUP_PARAMS
-#undef MY_GROUP_ARGS
 
 // ---- the pre-passes of the table forms (hs_edlib_align_bytes; transformSequences, edlib.cpp:1422-1460, once per call) ----------
 // which of the 256 byte values the call's sequences hold: bit b of present[b >> 5]
@@ -675,80 +675,5 @@ __global__ __launch_bounds__(256) void k_myers_compact(const uint8_t* __restrict
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = map[src[i]];
 }
-
-
-// ---- distance and end location only (hs_edit_distance: edlib's TASK_DISTANCE / TASK_LOC end, modes NW / SHW / HW) ------------
-// The same banded sweeps. The bound: 1/16 of the query length (+ the length difference for NW) first; a score above the bound
-// is the score of an alignment that exists, so the sweep with that score as its bound holds the optimum (myers_mode_band,
-// myers_first_bound above).
-
-__global__ __launch_bounds__(64) void k_myers_distance(
-    const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,
-    const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list, int mode, int8_t* __restrict__ hscratch,
-    const int64_t* __restrict__ hscratch_off, int32_t* __restrict__ dist, int32_t* __restrict__ end_loc) {
-    __shared__ uint8_t tbuf[MY_TCHUNK + 64];
-    const int lane = lane_id();
-    if ((int)blockIdx.x >= n_list) return;
-    const int pr = pair_ids[blockIdx.x];
-    const uint8_t* qp = query + query_off[pr];
-    const int qn = (int)(query_off[pr + 1] - query_off[pr]);
-    const uint8_t* tp = target + target_off[pr];
-    const int tn = (int)(target_off[pr + 1] - target_off[pr]);
-    if (qn == 0 || tn == 0) {      // nothing to sweep: all deletions / all insertions (NW), an empty placement otherwise
-        if (lane == 0) { dist[pr] = mode == 0 ? (qn ? qn : tn) : qn; end_loc[pr] = (mode == 0 && qn == 0) ? tn - 1 : -1; }
-        return;
-    }
-    int8_t* hb = hscratch + hscratch_off[pr];
-    int32_t* hbot = reinterpret_cast<int32_t*>(hb + ((tn + 64 + 3) & ~3));
-    const int kmax = mode == 0 ? max(qn, tn) : qn;
-    int sc, best, first, last;
-    for (int k = myers_first_bound(mode, qn, tn);;) {
-        const bool all = k >= kmax;
-        myers_sweep(MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, mode, myers_mode_band(mode, qn, tn, k, all), hb, hbot, tbuf, nullptr, nullptr, sc, best, first, last);
-        const int got = mode == 0 ? sc : best;
-        if (all || got <= k) break;
-        k = got >= MY_INF ? 2 * k : got;
-    }
-    if (lane == 0) {
-        if (mode == 0) { dist[pr] = sc; end_loc[pr] = tn - 1; }
-        else { dist[pr] = best; end_loc[pr] = first; }
-    }
-}
-
-template <int G>
-__global__ __launch_bounds__(64) void k_myers_distance_grouped(
-    const uint8_t* __restrict__ query, const int64_t* __restrict__ query_off, const uint8_t* __restrict__ target,
-    const int64_t* __restrict__ target_off, const int32_t* __restrict__ pair_ids, int n_list, int mode,
-    int32_t* __restrict__ dist, int32_t* __restrict__ end_loc) {
-    constexpr int NG = 64 / G;
-    __shared__ __attribute__((aligned(16))) uint8_t tbuf[NG][MY_GCHUNK + 64];
-    const int lane = lane_id(), gl = lane & (G - 1), grp = lane / G;
-    const int slot = (int)blockIdx.x * NG + grp;
-    const bool live = slot < n_list;
-    const int pr = live ? pair_ids[slot] : 0;
-    const uint8_t* qp = query; const uint8_t* tp = target;
-    int qn = 0, tn = 0;
-    if (live) { qp += query_off[pr]; qn = (int)(query_off[pr + 1] - query_off[pr]); tp += target_off[pr]; tn = (int)(target_off[pr + 1] - target_off[pr]); }
-    const bool act = live && qn > 0 && tn > 0;
-    if (live && !act && gl == 0) { dist[pr] = mode == 0 ? (qn ? qn : tn) : qn; end_loc[pr] = (mode == 0 && qn == 0) ? tn - 1 : -1; }
-    const int kmax = mode == 0 ? max(qn, tn) : qn;
-    int sc = 0, best = 0, first = -1, last = -1, r_sc = 0, r_best = 0, r_first = -1;
-    int k = myers_first_bound(mode, qn, tn);
-    bool pending = act;
-    while (__ballot(pending) != 0ull) {
-        const bool all = k >= kmax;
-        myers_sweep_grouped<G>(pending, MyersSeq{qp, qn, false}, MyersSeq{tp, tn, false}, mode, myers_mode_band(mode, qn, tn, k, all), tbuf[grp], nullptr, sc, best, first, last);
-        if (pending) {
-            const int got = mode == 0 ? sc : best;
-            if (all || got <= k) { pending = false; r_sc = sc; r_best = best; r_first = first; }
-            else k = got >= MY_INF ? 2 * k : got;
-        }
-    }
-    if (act && gl == 0) {
-        if (mode == 0) { dist[pr] = r_sc; end_loc[pr] = tn - 1; }
-        else { dist[pr] = r_best; end_loc[pr] = r_first; }
-    }
-}
-
 
 }  // namespace hsdev

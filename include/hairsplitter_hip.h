@@ -230,8 +230,10 @@ int hs_read_graphs(const int32_t* d_sim, const int32_t* d_diff, const int64_t* c
  * a wavefront per pair, queries up to 2048 bases 8 / 16 / 32 lanes per pair; the band's bound is found on the way, as
  * edlib's k = -1 does). The reference's hot path takes base-level alignments from the SAM CIGAR;
  * its bundled edlib (edlib.h:242-246, modes edlib.h:36-62) is the behavioural oracle for this kernel.
+ * hs_edit_distance is hs_edlib_align (below) with task DISTANCE and k = -1 for offsets that live on the DEVICE: the same
+ * kernels, the same grouping of the pairs, the same scratch budget.
  * mode: 0 = NW (global), 1 = SHW (prefix), 2 = HW (infix). Outputs: edit distance and the first end location
- * on the target (0-based, inclusive), like edlibAlign's editDistance / endLocations[0].
+ * on the target (0-based, inclusive), like edlibAlign's editDistance / endLocations[0]. Synchronous with respect to `stream`.
  * ---------------------------------------------------------------------------------------------- */
 int hs_edit_distance(const uint8_t* d_query, const int64_t* d_query_off, const uint8_t* d_target,
                      const int64_t* d_target_off, int32_t n_pairs, int32_t mode, int32_t* d_dist,

@@ -883,6 +883,45 @@ def test_edit_distance_long_and_mixed_pairs_match_reference_edlib(built):
         assert len(bad) == 0, (mode, [(int(i), len(pairs[i][0]), len(pairs[i][1]), int(d[i]), int(e[i]), w[i].tolist()) for i in bad[:5]])
 
 
+def test_edit_distance_at_the_edges_of_the_lane_classes(built, monkeypatch):
+    """hs_edit_distance is hs_edlib_align with TASK_DISTANCE and k = -1: it shares the 8 / 16 / 32-lane / wavefront classing of the
+    path calls. Query lengths at a multiple of 64 (no column before the target takes part) and at the last length of each class
+    and the first of the next; per length a copy with ~5 % edits, an unrelated target of equal length (from 512 bases on its
+    optimum lies above the first bound max(64, n / 16), so the bound is raised), the query planted in a target three times as
+    long, and an empty target for 1 and 65. All pairs of a mode in one call, against the DP oracle; once more with a wavefront
+    per pair (HS_MYERS_NO_GROUPS is read at every call)."""
+    from hairsplitter_amd import api
+    rng = np.random.default_rng(20261019)
+    qs, ts, unrelated = [], [], []
+    for qn in (1, 63, 64, 65, 512, 513, 1024, 1025, 2048, 2049):
+        q = rng.integers(0, 4, size=qn, dtype=np.uint8)
+        u = rng.random(qn)
+        t = q.copy()
+        sub = u < 0.02
+        t[sub] = (t[sub] + 1) & 3
+        ins = np.flatnonzero((u >= 0.02) & (u < 0.035))
+        keep = np.insert(~((u >= 0.035) & (u < 0.05)), ins, True)
+        t = np.insert(t, ins, rng.integers(0, 4, size=len(ins), dtype=np.uint8))[keep]
+        planted = rng.integers(0, 4, size=3 * qn, dtype=np.uint8)
+        planted[qn:2 * qn] = q
+        unrelated.append(len(qs) + 1)
+        targets = [t, rng.integers(0, 4, size=qn, dtype=np.uint8), planted] + ([np.zeros(0, np.uint8)] if qn in (1, 65) else [])
+        qs += [q] * len(targets); ts += targets
+    want = {mi: [ol.edit_distance(q, t, mi) for q, t in zip(qs, ts)] for mi in (0, 1, 2)}
+    for mi in (0, 1, 2):
+        for i in unrelated:
+            if len(qs[i]) >= 512:
+                assert want[mi][i][0] > max(64, len(qs[i]) >> 4), (mi, len(qs[i]))
+    for no_groups in (False, True):
+        if no_groups:
+            monkeypatch.setenv("HS_MYERS_NO_GROUPS", "1")
+        for mode, mi in (("NW", 0), ("SHW", 1), ("HW", 2)):
+            d, e = api.edit_distance(qs, ts, mode)
+            got = list(zip(d.tolist(), e.tolist()))
+            bad = [(len(qs[i]), len(ts[i]), got[i], want[mi][i]) for i in range(len(qs)) if got[i] != tuple(want[mi][i])]
+            assert not bad, (mode, no_groups, bad[:5])
+
+
 def test_edlib_hw_path_random_pairs_against_the_numpy_restatement(built):
     """Seeded random pairs of 1-2600 bases (substitutions, insertions, deletions at 0-35 %, unrelated pairs, repeats) through
     hs_edlib_hw_align, against oracle/edlib_path_oracle.py -- the numpy restatement that the CPU suite pins on the reference's

@@ -11,7 +11,10 @@ Usage: python tools/myers_bench.py [n_pairs=20000] [target_len=2000] [query_len=
        hs_edlib_align (four codes), the same pairs as bytes with 1 % of the bases replaced by N through hs_edlib_align_bytes
        without equalities, and the same with N = A, C, G, T: pairs/s of each and the two ratios to the four-code run. With
        n_symbols above 5 the replaced bases become bytes outside ACGT drawn from n_symbols - 4 values (17 and more: the scratch
-       table instead of the LDS table; the equalities then make the first of them equal to every base)."""
+       table instead of the LDS table; the equalities then make the first of them equal to every base).
+       python tools/myers_bench.py dist: hs_edit_distance (distance and first end location, offsets on the device) in NW and in HW
+       on the 20 000 pairs of 300 x 2 000 of the first form (8 lanes per pair) and on the 2 048 reads of 10 kb of the nw leg (a
+       wavefront per pair): pairs/s of each."""
 import ctypes as C
 import json
 import os
@@ -127,34 +130,72 @@ def nw_paths(n, rl):
     print(json.dumps(out))
 
 
+def planted_pairs(n, tl, qn):
+    """the query, with ~4 % substitutions, somewhere inside the target; above 300 bases 2 % deletions and 2 % insertions on top"""
+    rng = np.random.default_rng(9)
+    reads = qn > 300
+    q = rng.integers(0, 4, size=(n, qn), dtype=np.uint8)
+    t = rng.integers(0, 4, size=(n, tl), dtype=np.uint8)
+    pos = rng.integers(0, tl - qn - (qn >> 4), size=n)
+    for i in range(n):
+        m = q[i].copy()
+        e = rng.random(qn) < 0.04
+        m[e] = (m[e] + 1) & 3
+        if reads:
+            keep = rng.random(qn) >= 0.02
+            m = m[keep]
+            ins = np.flatnonzero(rng.random(len(m)) < 0.02)
+            m = np.insert(m, ins, rng.integers(0, 4, size=len(ins), dtype=np.uint8))
+        t[i, pos[i]:pos[i] + len(m)] = m
+    return q, t, pos
+
+
+def distances():
+    import torch
+    from hairsplitter_amd import api
+    api.require_gpu()
+    lib = api.load()
+    dev = "cuda:0"
+    q, t, _ = planted_pairs(20000, 2000, 300)
+    rq, rt = nw_pairs(2048, 10000)
+    out = {"leg": "dist"}
+    for label, qs, ts in (("pairs_300_in_2000", list(q), list(t)), ("reads_10kb", rq, rt)):
+        n = len(qs)
+        qo = np.zeros(n + 1, np.int64); to = np.zeros(n + 1, np.int64)
+        np.cumsum([len(x) for x in qs], out=qo[1:]); np.cumsum([len(x) for x in ts], out=to[1:])
+        dq, dqo, dt, dto = (torch.from_numpy(a).to(dev) for a in (np.concatenate(qs), qo, np.concatenate(ts), to))
+        dd = torch.zeros(n, dtype=torch.int32, device=dev); de = torch.zeros_like(dd)
+        out[label] = {"pairs": n}
+        for mode, mi in (("NW", 0), ("HW", 2)):
+            times = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                api._check(lib.hs_edit_distance(api._p(dq), api._p(dqo), api._p(dt), api._p(dto), C.c_int32(n), C.c_int32(mi), api._p(dd), api._p(de), C.c_void_p(0)))
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+            best = min(times[1:])
+            out[label][mode] = {"seconds": best, "pairs_per_s": n / best, "distance_mean": float(dd.float().mean().item()), "end_mean": float(de.float().mean().item())}
+    print(json.dumps(out))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "nw":
         return nw_paths(int(sys.argv[2]) if len(sys.argv) > 2 else 2048, int(sys.argv[3]) if len(sys.argv) > 3 else 10000)
     if len(sys.argv) > 1 and sys.argv[1] == "bytes":
         return bytes_paths(int(sys.argv[2]) if len(sys.argv) > 2 else 2048, int(sys.argv[3]) if len(sys.argv) > 3 else 10000,
                            int(sys.argv[4]) if len(sys.argv) > 4 else 5)
+    if len(sys.argv) > 1 and sys.argv[1] == "dist":
+        return distances()
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
     tl = int(sys.argv[2]) if len(sys.argv) > 2 else 2000
     import torch
     from hairsplitter_amd import api
     api.require_gpu()
     lib = api.load()
-    rng = np.random.default_rng(9)
     qn = int(sys.argv[3]) if len(sys.argv) > 3 else 300
     reads = qn > 300
-    q = rng.integers(0, 4, size=(n, qn), dtype=np.uint8)
-    t = rng.integers(0, 4, size=(n, tl), dtype=np.uint8)
-    pos = rng.integers(0, tl - qn - (qn >> 4), size=n)
-    for i in range(n):                       # the query, with ~4 % substitutions, somewhere inside the target
-        m = q[i].copy()
-        e = rng.random(qn) < 0.04
-        m[e] = (m[e] + 1) & 3
-        if reads:                            # reads: 2 % deletions and 2 % insertions on top
-            keep = rng.random(qn) >= 0.02
-            m = m[keep]
-            ins = np.flatnonzero(rng.random(len(m)) < 0.02)
-            m = np.insert(m, ins, rng.integers(0, 4, size=len(ins), dtype=np.uint8))
-        t[i, pos[i]:pos[i] + len(m)] = m
+    q, t, pos = planted_pairs(n, tl, qn)
     qo = np.arange(n + 1, dtype=np.int64) * qn
     to = np.arange(n + 1, dtype=np.int64) * tl
     oo = np.arange(n + 1, dtype=np.int64) * (qn + tl)
