@@ -541,7 +541,70 @@ class _SrResultOwner:
 class _SrTaps(C.Structure):
     _fields_ = [("n_windows", C.c_int32), ("win_contig", C.POINTER(C.c_int32)), ("win_start", C.POINTER(C.c_int32)), ("win_row0", C.POINTER(C.c_int64)),
                 ("mask_ids", C.POINTER(C.c_int32)), ("run_begin", C.POINTER(C.c_int64)), ("run_snp", C.POINTER(C.c_int32)), ("run_off", C.POINTER(C.c_int64)),
-                ("run_labels", C.POINTER(C.c_int32)), ("third", C.POINTER(C.c_int32))]
+                ("run_labels", C.POINTER(C.c_int32)), ("third", C.POINTER(C.c_int32)),
+                ("g_n_windows", C.c_int32), ("g_win_contig", C.POINTER(C.c_int32)), ("g_win_kind", C.POINTER(C.c_int32)), ("g_win_row0", C.POINTER(C.c_int64)),
+                ("g_mask_ids", C.POINTER(C.c_int32)), ("g_nbr_off", C.POINTER(C.c_int64)), ("g_nbr", C.POINTER(C.c_int32)), ("g_n_contigs", C.c_int32),
+                ("g_plane_n", C.POINTER(C.c_int32)), ("g_words", C.POINTER(C.c_int32)), ("g_plane_off", C.POINTER(C.c_int64)), ("g_alt", C.POINTER(C.c_uint64)),
+                ("g_ref", C.POINTER(C.c_uint64)), ("g_n_reads", C.POINTER(C.c_int32)), ("g_out_off", C.POINTER(C.c_int64)), ("g_read_base", C.POINTER(C.c_int64)),
+                ("g_pos_orig", C.POINTER(C.c_int32)), ("g_n_pos_orig", C.c_int64), ("g_n_plane_words", C.c_int64), ("g_n_pairs", C.c_int64),
+                ("g_matrix", C.POINTER(C.c_int32)), ("g_rows_on_host", C.c_int64), ("g_rows_late", C.c_int64), ("g_row_waves", C.c_int32)]
+
+
+SR_TAP_SENTINEL = -2 ** 31      # HS_SR_TAP_SENTINEL
+
+
+def _sr_run_taps_fn(lib):
+    lib.hs_sr_run_taps.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.POINTER(SrResult)),
+                                   C.POINTER(C.POINTER(_SrTaps))]
+    lib.hs_sr_taps_destroy.argtypes = [C.POINTER(_SrTaps)]; lib.hs_sr_taps_destroy.restype = None
+    return lib.hs_sr_run_taps
+
+
+def _graph_taps_to_dict(t):
+    a = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, (max(n, 1),))[:n].astype(dt).copy()
+    W, Cn = int(t.g_n_windows), int(t.g_n_contigs)
+    row0 = a(t.g_win_row0, W + 1, np.int64)
+    rows = int(row0[-1])
+    noff = a(t.g_nbr_off, rows + 1, np.int64)
+    return {"win_contig": a(t.g_win_contig, W, np.int32), "win_kind": a(t.g_win_kind, W, np.int32), "win_row0": row0, "mask_ids": a(t.g_mask_ids, rows, np.int32),
+            "nbr_off": noff, "nbr": a(t.g_nbr, int(noff[-1]), np.int32),
+            "plane_n": a(t.g_plane_n, Cn, np.int32), "words": a(t.g_words, Cn, np.int32), "plane_off": a(t.g_plane_off, Cn, np.int64),
+            "alt": a(t.g_alt, int(t.g_n_plane_words), np.uint64), "ref": a(t.g_ref, int(t.g_n_plane_words), np.uint64),
+            "n_reads": a(t.g_n_reads, Cn, np.int32), "out_off": a(t.g_out_off, Cn, np.int64), "read_base": a(t.g_read_base, Cn, np.int64),
+            "pos_orig": a(t.g_pos_orig, int(t.g_n_pos_orig), np.int32), "matrix": a(t.g_matrix, 2 * int(t.g_n_pairs), np.int32).reshape(-1, 2),
+            "rows_on_host": int(t.g_rows_on_host), "rows_late": int(t.g_rows_late), "row_waves": int(t.g_row_waves)}
+
+
+def separate_reads_graph_taps(contigs: Sequence[Dict], window_size: int, error_rate: float, low_memory: bool = False, seed: int = 12345,
+                              n_threads: int = 0) -> Dict:
+    """hs_sr_run_taps in its graphs mode on stage-4 inputs given directly: one dict per contig with length, read_start, read_end, snp_pos, snp_ref,
+    snp_alt, col_off, col_idx, col_code (what separate_reads(taps=...) leaves in out["contigs"]). The call runs hs_sr_run's own code up to the read
+    graphs and returns what its kernels left (include/hairsplitter_hip.h: the g_ fields of hs_sr_taps); there is no clustering and no result."""
+    require_gpu()
+    lib = load()
+    Cn = len(contigs)
+    arr = (SrContig * max(Cn, 1))()
+    keep = []
+    for c, ctg in enumerate(contigs):
+        rs, re = _np(ctg["read_start"], np.int32), _np(ctg["read_end"], np.int32)
+        sp, sr, sa = _np(ctg["snp_pos"], np.int32), _np(ctg["snp_ref"], np.uint8), _np(ctg["snp_alt"], np.uint8)
+        co, ci, cc = _np(ctg["col_off"], np.int64), _np(ctg["col_idx"], np.int32), _np(ctg["col_code"], np.uint8)
+        if len(ci) == 0:
+            ci, cc = np.zeros(1, np.int32), np.zeros(1, np.uint8)
+        keep += [rs, re, sp, sr, sa, co, ci, cc]
+        a = arr[c]
+        a.length = int(ctg["length"]); a.n_reads = len(rs); a.n_snps = len(sp)
+        a.read_start = _hp(rs, C.c_int32); a.read_end = _hp(re, C.c_int32)
+        a.snp_pos = _hp(sp, C.c_int32); a.snp_ref = _hp(sr, C.c_uint8); a.snp_alt = _hp(sa, C.c_uint8)
+        a.col_off = _hp(co, C.c_int64); a.col_idx = _hp(ci, C.c_int32); a.col_code = _hp(cc, C.c_uint8)
+        a.ploidy = 0
+    res = C.POINTER(SrResult)()
+    tp = C.POINTER(_SrTaps)()
+    _check(_sr_run_taps_fn(lib)(C.cast(arr, C.c_void_p), C.c_int32(Cn), C.c_int32(int(window_size)), C.c_float(error_rate), C.c_int32(1 if low_memory else 0),
+                                C.c_uint32(seed), C.c_int32(n_threads), C.c_int32(1), C.byref(res), C.byref(tp)))
+    out = _graph_taps_to_dict(tp.contents)
+    lib.hs_sr_taps_destroy(tp)
+    return out
 
 
 def _sr_result_to_dict(res, Cn, take_ownership=False):
@@ -577,7 +640,8 @@ def separate_reads(cv_out: Dict, flat: FlatBatch, error_rate: float, low_memory:
                    seed: int = 12345, n_threads: int = 0, ploidy: Optional[Sequence[int]] = None,
                    rarest_strain_abundance: float = 0.0, window_size: Optional[int] = None, taps: bool = False) -> Dict:
     """(taps=True: through hs_sr_run_taps -- out["taps"] holds what the kernels of the clustering chain left, out["contigs"] the per-contig
-    inputs as numpy arrays, for the tests.)
+    inputs as numpy arrays, for the tests. taps="graphs": the call stops behind the read graphs -- separate_reads_graph_taps on the same
+    per-contig inputs; out = {"window_size", "contigs", "taps"}.)
     Stage 4 on the in-memory result of stage 3 == HS_separate_reads without the .col round trip
     (separate_reads.cpp:1440-1739). READ limits are (position_2_1, position_2_2) of the records
     (call_variants.cpp:1186-1189 -> separate_reads.cpp:176-179)."""
@@ -631,13 +695,13 @@ def separate_reads(cv_out: Dict, flat: FlatBatch, error_rate: float, low_memory:
         a.col_off = _hp(col_off, C.c_int64); a.col_idx = _hp(col_idx, C.c_int32); a.col_code = _hp(col_code, C.c_uint8)
         a.ploidy = int(ploidy[c]) if ploidy is not None else 0
     w = lib.hs_sr_window_size(arr, C.c_int32(Cn), C.c_int32(1 if amplicon else 0)) if window_size is None else int(window_size)
+    if taps == "graphs":
+        return {"window_size": int(w), "contigs": per_contig, "taps": separate_reads_graph_taps(per_contig, int(w), error_rate, low_memory, seed, n_threads)}
     res = C.POINTER(SrResult)()
     tp = C.POINTER(_SrTaps)()
     if taps:
-        lib.hs_sr_run_taps.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(C.POINTER(SrResult)), C.POINTER(C.POINTER(_SrTaps))]
-        lib.hs_sr_taps_destroy.argtypes = [C.POINTER(_SrTaps)]; lib.hs_sr_taps_destroy.restype = None
-        _check(lib.hs_sr_run_taps(C.cast(arr, C.c_void_p), C.c_int32(Cn), C.c_int32(w), C.c_float(error_rate), C.c_int32(1 if low_memory else 0),
-                                  C.c_uint32(seed), C.c_int32(n_threads), C.byref(res), C.byref(tp)))
+        _check(_sr_run_taps_fn(lib)(C.cast(arr, C.c_void_p), C.c_int32(Cn), C.c_int32(w), C.c_float(error_rate), C.c_int32(1 if low_memory else 0),
+                                    C.c_uint32(seed), C.c_int32(n_threads), C.c_int32(0), C.byref(res), C.byref(tp)))
     else:
         _check(lib.hs_sr_run(arr, C.c_int32(Cn), C.c_int32(w), C.c_float(error_rate), C.c_int32(1 if low_memory else 0),
                              C.c_uint32(seed), C.c_int32(n_threads), C.byref(res)))

@@ -61,13 +61,17 @@ void hs_sr_taps_destroy(hs_sr_taps* t) {
     if (!t) return;
     std::free(t->win_contig); std::free(t->win_start); std::free(t->win_row0); std::free(t->mask_ids); std::free(t->run_begin); std::free(t->run_snp); std::free(t->run_off);
     std::free(t->run_labels); std::free(t->third);
+    std::free(t->g_win_contig); std::free(t->g_win_kind); std::free(t->g_win_row0); std::free(t->g_mask_ids); std::free(t->g_nbr_off); std::free(t->g_nbr);
+    std::free(t->g_plane_n); std::free(t->g_words); std::free(t->g_plane_off); std::free(t->g_alt); std::free(t->g_ref); std::free(t->g_n_reads); std::free(t->g_out_off);
+    std::free(t->g_read_base); std::free(t->g_pos_orig); std::free(t->g_matrix);
     std::free(t);
 }
 int hs_sr_run_taps(const hs_sr_contig* contigs, int32_t n_contigs, int32_t window_size, float error_rate, int32_t low_memory, uint32_t seed,
-                   int32_t n_threads, hs_sr_result** out, hs_sr_taps** taps) {
+                   int32_t n_threads, int32_t mode, hs_sr_result** out, hs_sr_taps** taps) {
     if (int rc = require_device()) return rc;
-    if (!out || !taps || n_contigs < 0) { set_error("hs_sr_run_taps: bad arguments"); return HS_EINVAL; }
+    if (!out || !taps || n_contigs < 0 || (mode != HS_SR_TAPS_CHAIN && mode != HS_SR_TAPS_GRAPHS)) { set_error("hs_sr_run_taps: bad arguments"); return HS_EINVAL; }
     hs::SrTaps tp;
+    tp.graphs = mode == HS_SR_TAPS_GRAPHS;
     {
         HipSrOps ops;
         if (int rc = hs::sr_run(ops, contigs, n_contigs, window_size, error_rate, low_memory, seed, n_threads, out, nullptr, nullptr, &tp)) return rc;
@@ -84,6 +88,18 @@ int hs_sr_run_taps(const hs_sr_contig* contigs, int32_t n_contigs, int32_t windo
     t->n_windows = (int32_t)Wc;
     t->win_contig = dup_vec(tp.win_contig); t->win_start = dup_vec(tp.win_start); t->win_row0 = dup_vec(tp.win_row0); t->mask_ids = dup_vec(tp.mask_ids);
     t->run_begin = dup_vec(tp.run_begin); t->run_snp = dup_vec(tp.run_snp); t->run_off = dup_vec(tp.run_off); t->run_labels = dup_vec(tp.run_labels); t->third = dup_vec(tp.third);
+    if (tp.graphs) {
+        const hs::SrGraphTaps& f = tp.front;
+        t->g_n_windows = (int32_t)f.win_contig.size();
+        t->g_win_contig = dup_vec(f.win_contig); t->g_win_kind = dup_vec(f.win_kind); t->g_win_row0 = dup_vec(f.win_row0); t->g_mask_ids = dup_vec(f.mask_ids);
+        t->g_nbr_off = dup_vec(f.nbr_off); t->g_nbr = dup_vec(f.nbr);
+        t->g_n_contigs = (int32_t)f.plane_n.size();
+        t->g_plane_n = dup_vec(f.plane_n); t->g_words = dup_vec(f.words); t->g_plane_off = dup_vec(f.plane_off); t->g_alt = dup_vec(f.alt); t->g_ref = dup_vec(f.ref);
+        t->g_n_reads = dup_vec(f.n_reads); t->g_out_off = dup_vec(f.out_off); t->g_read_base = dup_vec(f.read_base); t->g_pos_orig = dup_vec(f.pos_orig);
+        t->g_n_pos_orig = (int64_t)f.pos_orig.size(); t->g_n_plane_words = (int64_t)f.alt.size(); t->g_n_pairs = (int64_t)f.matrix.size() / 2;
+        t->g_matrix = dup_vec(f.matrix);
+        t->g_rows_on_host = f.rows_on_host; t->g_rows_late = f.rows_late; t->g_row_waves = f.row_waves;
+    }
     *taps = t;
     return HS_OK;
 }

@@ -690,8 +690,17 @@ int sr_run(SrDeviceOps& dev, const hs_sr_contig* contigs, int32_t n_contigs, int
         laps.lap("columns");
         matrices_by_position = !job.pos_orig.empty();
         const double t0 = now_ms();
-        if (int rc = dev.simdiff_columns(job, &k_ms[0])) return rc;
+        const bool tap_front = taps && taps->graphs;
+        if (tap_front) dev.tap_front(&taps->front);
+        const int rc_sd = dev.simdiff_columns(job, &k_ms[0]);
+        if (tap_front) dev.tap_front(nullptr);
+        if (rc_sd) return rc_sd;
         dev_ms += now_ms() - t0;
+        if (tap_front) {
+            SrGraphTaps& f = taps->front;
+            f.plane_n = job.plane_n; f.words = job.words; f.n_reads = job.n_reads;
+            f.plane_off = job.plane_off; f.out_off = job.out_off; f.read_base = job.read_base; f.pos_orig = job.pos_orig;
+        }
     }
 
     const double t_simdiff_done = now_ms();
@@ -884,6 +893,36 @@ int sr_run(SrDeviceOps& dev, const hs_sr_contig* contigs, int32_t n_contigs, int
         });
     }
     laps.lap("chain_build");
+    if (taps && taps->graphs) {      // (test taps, graphs mode: the graphs as the calls above left them, and nothing behind them)
+        SrGraphTaps& f = taps->front;
+        if (!wrefs.empty()) {
+            if (two_phase) dev.tap_front(&f);
+            const int rc_e = two_phase ? dev.build_graphs_end(ws, &rows_on_host) : HS_OK;
+            if (two_phase) dev.tap_front(nullptr);
+            if (rc_e) return rc_e;
+        }
+        f.rows_on_host = rows_on_host;
+        std::vector<int64_t> off; std::vector<int32_t> nbr;
+        if (!wrefs.empty()) { if (int rc = dev.fetch_graphs(off, nbr)) return rc; }
+        else off.assign(1, 0);
+        if ((int64_t)off.size() != ws.rows() + 1) { set_error("sr_run: the fetched graphs do not have the rows of the window set"); return HS_EINVAL; }
+        f.win_contig = ws.win_contig; f.win_row0 = ws.win_row0; f.mask_ids = ws.mask_ids;
+        if (f.win_row0.empty()) f.win_row0.assign(1, 0);
+        f.win_kind.resize(wrefs.size());
+        f.nbr_off.assign(off.begin(), off.end());
+        f.nbr.resize(nbr.size());
+        for (size_t i = 0; i < wrefs.size(); ++i) {
+            f.win_kind[i] = (int32_t)i < ws.n_matrix_windows ? 0 : ((int32_t)i < ws.n_dev_windows ? 1 : 2);
+            const int64_t r0 = ws.win_row0[i], r1 = ws.win_row0[i + 1];
+            for (int64_t e = off[(size_t)r0]; e < off[(size_t)r1]; ++e) {
+                const int32_t j = nbr[(size_t)e];
+                if (j < 0 || j >= r1 - r0) { set_error("sr_run: a neighbour outside its window"); return HS_EINVAL; }
+                f.nbr[(size_t)e] = ws.mask_ids[(size_t)(r0 + j)];
+            }
+        }
+        if (out) *out = nullptr;
+        return HS_OK;
+    }
     if (two_phase) {
         const double t0 = now_ms();
         if (int rc = dev.build_graphs_end(ws, &rows_on_host)) return rc;

@@ -214,6 +214,7 @@ struct SrChainStats {                 // what the clustering chain did (bench.py
     int64_t graph_nnz = 0;            // neighbour entries of all window graphs
 };
 
+struct SrGraphTaps;
 struct SrDeviceOps {
     virtual ~SrDeviceOps() {}
     // K5a + K5: bit-planes from the SNP columns, then sim / diff for every contig with n_reads[c] > 0. The columns (the same
@@ -238,6 +239,9 @@ struct SrDeviceOps {
     virtual int cw(CwWave& wave, float* k_ms) = 0;
     // (test taps: the next cw_chain() also leaves the labels of its per-SNP runs -- run_off / run_labels -- and always fills `labels`)
     virtual void tap_chain(std::vector<int64_t>* run_off, std::vector<int32_t>* run_labels) { (void)run_off; (void)run_labels; }
+    // (test taps: the next simdiff_columns() fills the matrices with SrGraphTaps::kSentinel before K5 and leaves bit rows and matrices in `t`,
+    // the next build_graphs_end() the late-row counter and the wave count; nullptr: off)
+    virtual void tap_front(SrGraphTaps* t) { (void)t; }
     // The SNP columns of the call may be with the implementation already (stage 3 left them on the device, in the order and with
     // the offsets of CwChain::col_off): then CwChain's col_idx / col_code stay empty and ...
     // create_read_graph_low_memory on the device (window-local sim / diff from the bit rows); false: the caller builds those rows
@@ -269,6 +273,26 @@ struct SrSparseLabels {
 // state of a stage-4 call that is worth keeping for the next one on the same contigs (a pipeline group runs the same contigs step
 // after step): the per-contig plans with their storage, the shuffled visiting orders
 struct SrWorkspace { std::vector<SrContigState> st; };
+// Test taps of the front of a stage-4 call (hs_sr_run_taps, graphs mode): what K5a, K5 and the graph kernels left, reached through the calls
+// sr_run makes anyway. An implementation that has bit rows / matrices to show fills planes_* / matrix (tap_front) inside simdiff_columns().
+struct SrGraphTaps {
+    static constexpr int32_t kSentinel = INT32_MIN;   // the matrices are filled with it before K5: an entry K5 did not write (a skipped tile) keeps it
+    // every window of the window set, in set order
+    std::vector<int32_t> win_contig, win_kind;    // kind: 0 = graph from the contig's matrices, 1 = low-memory path on the device, 2 = low-memory path on the host
+    std::vector<int64_t> win_row0;                // [W + 1] into mask_ids / nbr_off
+    std::vector<int32_t> mask_ids;                // the window's reads (ascending)
+    std::vector<int64_t> nbr_off;                 // [rows + 1] the neighbour list of every row ...
+    std::vector<int32_t> nbr;                     // ... as read ids
+    // layout of the call (SimdiffJob): per contig the reads / words of its bit rows (0: none), its offset among them (words), the reads of its
+    // matrices (0: none), their offset (pairs), and the first of its rows in pos_orig
+    std::vector<int32_t> plane_n, words, n_reads;
+    std::vector<int64_t> plane_off, out_off, read_base;
+    std::vector<int32_t> pos_orig;                // row k of the matrices of contig c = read pos_orig[read_base[c] + k]
+    std::vector<uint64_t> alt, ref;               // the bit rows of all contigs as K5a left them
+    std::vector<int32_t> matrix;                  // (sim, diff) pairs of all matrix contigs as K5 left them
+    int64_t rows_on_host = 0, rows_late = 0;      // rows resolved on the host; of those, rows whose entries had to be fetched behind the row kernels
+    int32_t row_waves = 0;                        // wavefronts per workgroup of k_read_graph_rows (0: not launched)
+};
 // Test taps of the clustering chain of a stage-4 call (hs_sr_run_taps): the windows that have seeding SNPs, in chain order, with what the
 // kernels of the chain left -- the labels of every per-SNP Chinese-Whispers run (k_cw_seed_sets + k_cw_seeded_lanes / _rows / _wave) and
 // of the third run (inside k_window_tail), as window-local node ids / cluster indices
@@ -280,6 +304,10 @@ struct SrTaps {
     std::vector<int32_t> run_snp;                 // SNP index on its contig of every run
     std::vector<int64_t> run_off;                 // [runs + 1] into run_labels (m labels per run)
     std::vector<int32_t> run_labels, third;       // third: [win_row0.back()] what the third run left
+    // graphs mode (graphs = true on entry): sr_run stops behind build_graphs_end() / fetch_graphs() -- no Chinese-Whispers chain, no result -- and
+    // leaves `front` instead of the fields above
+    bool graphs = false;
+    SrGraphTaps front;
 };
 int sr_run(SrDeviceOps& dev, const hs_sr_contig* contigs, int32_t n_contigs, int32_t window_size, float error_rate,
            int32_t low_memory, uint32_t seed, int32_t n_threads, hs_sr_result** out, SrSparseLabels* sparse = nullptr, SrWorkspace* keep = nullptr, SrTaps* taps = nullptr);

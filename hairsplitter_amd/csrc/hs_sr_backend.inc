@@ -26,6 +26,7 @@ struct GraphRows {
     std::vector<int64_t> win_bits_off, win_mat_off;
     std::vector<int32_t> lt_w, lt_i, lt_j;
     int Wd = 0, Wmx = 0, rows_mx = 0;
+    int row_waves = 0; int64_t n_late = 0;      // wavefronts per workgroup of the row kernels (0: none launched); undecided rows of the last end() fetched behind them
     size_t amb_cap = 0;
     int64_t stage_cap = 0, stage_hint = 0;      // entries (sim / diff pairs) the undecided rows may stage / staged last time
     EventPair ev;
@@ -49,7 +50,7 @@ static int graph_rows_begin(const int32_t* d_sim, const int32_t* d_diff, const s
     const std::vector<int32_t>& ctg_n = G.ctg_n;
     const int W = (int)ws.win_contig.size();
     G.W = W; G.rows = ws.rows(); G.total = 0; G.total_exact = true; G.max_m = 1; G.begun = true; G.timed = false; G.k_ms = k_ms;
-    G.d_sim = d_sim; G.d_diff = d_diff; G.es = es;
+    G.d_sim = d_sim; G.d_diff = d_diff; G.es = es; G.row_waves = 0; G.n_late = 0;
     if (G.rows > 0x7fffffff) { set_error("read graphs: too many rows"); return HS_EINVAL; }
     const int rows = (int)G.rows;
     const int Wd = ws.n_dev_windows;
@@ -126,6 +127,7 @@ static int graph_rows_begin(const int32_t* d_sim, const int32_t* d_diff, const s
         if ((size_t)cap * 8 * 4 > 57344) waves = 1;
         if ((size_t)cap * 8 > 57344) cap = 7168;
         const float below = 1 - ws.error_rate * 2;   // :778
+        G.row_waves = waves;
         HS_HIP(ev_rec(G.ev.a, stream));
         if (rows_mx > 0) {
             if (kc) { if (int rc = kc->begin(HS_K_GRAPH_ROWS, stream)) return rc; }
@@ -209,6 +211,7 @@ static int graph_rows_end(const hs::SrWindowSet& ws, GraphRows& G, hipStream_t s
             // rows whose entries found no room in the staging area (a first call, or more of them than ever before): fetched the old way
             std::vector<int32_t> late;
             for (int32_t k : order) if (amb_so[k] < 0) late.push_back(k);
+            G.n_late = (int64_t)late.size();
             std::vector<int64_t> late_dst((size_t)late.size() + 1, 0);
             const int32_t* late_sim = nullptr; const int32_t* late_diff = nullptr;
             if (!late.empty()) {
@@ -500,11 +503,21 @@ struct HipSrOps : hs::SrDeviceOps {
             hipLaunchKernelGGL(hsdev::k_fill16, dim3(gb), dim3(256), 0, stream, reinterpret_cast<uint4*>(rng_hi), (long long)(half / 16), 0xffffffffu);
         }
         const size_t pbytes = (size_t)job.plane_total * sizeof(uint64_t);
-        if (int rc = f.d_alt.alloc(pbytes)) return rc;
-        if (int rc = f.d_ref.alloc(pbytes)) return rc;
+        const size_t tap_pad = front ? 16 : 0;      // (test taps: room for the whole 16-byte granules of the fills below)
+        if (int rc = f.d_alt.alloc(pbytes + tap_pad)) return rc;
+        if (int rc = f.d_ref.alloc(pbytes + tap_pad)) return rc;
         // (sim, diff) of a read pair side by side: K6 reads both for every masked read of a row, one 64-byte line instead of two
-        if (int rc = d_sim.alloc(std::max<size_t>((size_t)job.out_total, 1) * 2 * sizeof(int32_t))) return rc;
+        if (int rc = d_sim.alloc(std::max<size_t>((size_t)job.out_total, 1) * 2 * sizeof(int32_t) + tap_pad)) return rc;
         d_diff.release(); d_diff.p = (char*)d_sim.p + sizeof(int32_t); d_diff.bytes = 0; d_diff.cap = 0; d_diff.view = true;
+        if (front) {      // test taps only: a word K5a does not store stays all ones, an entry K5 does not write stays the sentinel
+            auto fill = [&](void* p, size_t bytes, unsigned v) {
+                const long long n16 = (long long)((bytes + 15) / 16);
+                if (n16) hipLaunchKernelGGL(hsdev::k_fill16, dim3((unsigned)std::min<long long>(256, n16 / 4096 + 1)), dim3(256), 0, stream, reinterpret_cast<uint4*>(p), n16, v);
+            };
+            fill(f.d_alt.p, pbytes, 0xffffffffu); fill(f.d_ref.p, pbytes, 0xffffffffu);
+            fill(d_sim.p, (size_t)job.out_total * 8, (unsigned)hs::SrGraphTaps::kSentinel);
+            HS_HIP(hipGetLastError());
+        }
         if (int rc = kc.begin(HS_K_SNP_PLANES, stream)) return rc;
         if (int rc = snp_planes_launch(d_col_off.as<int64_t>(), d_col_idx.as<int32_t>(), d_col_code.as<uint8_t>(), f.d_sr.as<uint8_t>(), f.d_sa.as<uint8_t>(),
                                        f.d_sc.as<int32_t>(), f.d_cb.as<int64_t>(), f.d_po.as<int64_t>(), f.d_w.as<int32_t>(), f.d_pn.as<int32_t>(), f.d_bc.as<int32_t>(),
@@ -519,9 +532,17 @@ struct HipSrOps : hs::SrDeviceOps {
                                     by_pos ? f.d_rb.as<int64_t>() : nullptr, by_pos ? f.d_orig.as<int32_t>() : nullptr, rng_lo, rng_hi)) return rc;
         if (int rc = kc.end(2 * (int64_t)pbytes + 8 * job.out_total, stream)) return rc;   // the two bit-planes in, sim + diff out
         HS_HIP(ev_rec(f.ev.b, stream));
+        if (front) {      // test taps only: bit rows and matrices to the host, as the kernels left them
+            front->alt.assign((size_t)job.plane_total, ~0ull); front->ref.assign((size_t)job.plane_total, ~0ull);
+            front->matrix.assign((size_t)job.out_total * 2, 0);
+            if (pbytes) { if (int rc = d2h_pinned(front->alt.data(), f.d_alt.p, pbytes, stream)) return rc; if (int rc = d2h_pinned(front->ref.data(), f.d_ref.p, pbytes, stream)) return rc; }
+            if (job.out_total > 0) { if (int rc = d2h_pinned(front->matrix.data(), d_sim.p, (size_t)job.out_total * 8, stream)) return rc; }
+        }
         return HS_OK;   // not waited for: the stream orders K6 behind it, the host goes on planning the windows
     }
 
+    hs::SrGraphTaps* front = nullptr;      // test taps of the front of the call (hs_driver.h), while they are on
+    void tap_front(hs::SrGraphTaps* t) override { front = t; }
     struct Keep { int64_t stage_hint = 0; };      // kept by the caller from step to step: how much the undecided graph rows staged
     Keep* keep = nullptr;
     PlaneRows plane_rows() const {
@@ -542,6 +563,7 @@ struct HipSrOps : hs::SrDeviceOps {
     int build_graphs_end(const hs::SrWindowSet& ws, int64_t* rows_on_host) override {
         const int rc = graph_rows_end(ws, G, stream, rows_on_host, &kc);
         if (!rc) k5_waited = true;      // (graph_rows_end has waited for the stream)
+        if (!rc && front) { front->rows_late = G.n_late; front->row_waves = G.row_waves; }
         if (keep) keep->stage_hint = G.stage_hint;
         return rc;      // (not waited for: K5's temporaries and the clocks are settled behind the wait of cw_chain / the destructor)
     }

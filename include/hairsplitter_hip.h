@@ -488,9 +488,30 @@ typedef struct hs_sr_taps {
     int64_t* run_off;                             /* [runs + 1] into run_labels: m labels per run, in the order of mask_ids */
     int32_t* run_labels;                          /* label = the read index the label stands for */
     int32_t* third;                               /* cluster index (-1: dropped with its small cluster) */
+    /* mode HS_SR_TAPS_GRAPHS: the fields above stay empty; the front of the call as its kernels left it, reached through the calls hs_sr_run makes
+     * (K5a k_snp_planes, K5 k_simdiff, k_simdiff_windows, K6 k_read_graph_rows and the row fetch, patch, degree and fill kernels) */
+    int32_t g_n_windows;                          /* EVERY window of the call's window set, in set order */
+    int32_t* g_win_contig; int32_t* g_win_kind;   /* kind: 0 = graph from the contig's sim / diff matrices, 1 = low-memory path on the device, 2 = on the host */
+    int64_t* g_win_row0;                          /* [g_n_windows + 1] into g_mask_ids / g_nbr_off */
+    int32_t* g_mask_ids;                          /* the window's reads, ascending */
+    int64_t* g_nbr_off; int32_t* g_nbr;           /* [rows + 1]; the neighbours of every (window, read) row as READ indices, ascending */
+    int32_t g_n_contigs;
+    int32_t* g_plane_n; int32_t* g_words;         /* [C] reads / 64-SNP words of the contig's bit rows (0: it has none) */
+    int64_t* g_plane_off;                         /* [C] first word of the contig in g_alt / g_ref; word w of read r at plane_off + r * words + w */
+    uint64_t* g_alt; uint64_t* g_ref;             /* the bit rows as K5a left them (every word is stored by K5a: the buffers are all ones before it) */
+    int32_t* g_n_reads; int64_t* g_out_off;       /* [C] reads of the contig's matrices (0: none) / its first pair in g_matrix */
+    int64_t* g_read_base; int32_t* g_pos_orig;    /* row k of the matrices of contig c is the read g_pos_orig[g_read_base[c] + k] (reads by start position) */
+    int64_t g_n_pos_orig, g_n_plane_words, g_n_pairs;
+    int32_t* g_matrix;                            /* (sim, diff) of rows (i, j) at 2 * (out_off + i * n_reads + j); HS_SR_TAP_SENTINEL in both: K5 did not write
+                                                     the pair (a tile of two 64-row blocks that share no SNP word: nobody reads it) */
+    int64_t g_rows_on_host, g_rows_late;          /* rows resolved on the host / of those, fetched behind the row kernels (no room in the staging area) */
+    int32_t g_row_waves;                          /* wavefronts per workgroup of k_read_graph_rows (4, or 1 for a window wider than 1792 reads; 0: not launched) */
 } hs_sr_taps;
+#define HS_SR_TAPS_CHAIN 0
+#define HS_SR_TAPS_GRAPHS 1                       /* stops behind the read graphs: no Chinese-Whispers chain, *out stays NULL */
+#define HS_SR_TAP_SENTINEL INT32_MIN              /* the matrices are filled with it before K5, in this mode only (the one extra launch of the taps) */
 int hs_sr_run_taps(const hs_sr_contig* contigs, int32_t n_contigs, int32_t window_size, float error_rate, int32_t low_memory, uint32_t seed,
-                   int32_t n_threads, hs_sr_result** out, hs_sr_taps** taps);
+                   int32_t n_threads, int32_t mode, hs_sr_result** out, hs_sr_taps** taps);
 void hs_sr_taps_destroy(hs_sr_taps* t);
 void hs_sr_result_destroy(hs_sr_result* r);
 /* Stage 4 directly on the result of hs_cv_run, without the .col text round trip (call_variants.cpp:1197-1204 <->

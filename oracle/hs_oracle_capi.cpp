@@ -176,6 +176,28 @@ int hso_read_graph(int32_t n, const int32_t* sim, const int32_t* diff, const uin
     return 0;
 }
 
+// create_read_graph_low_memory (separate_reads.cpp:538-693) for one window: the contig's SNP columns and the window's mask in, adj_off[N+1] and
+// adj (capacity adj_cap entries; -1 if they do not fit) = sorted neighbour lists out.
+int hso_read_graph_low_memory(int32_t n_reads, int32_t n_snps, const uint8_t* snp_ref, const uint8_t* snp_alt, const int64_t* col_off, const int32_t* col_idx,
+                              const uint8_t* col_code, const uint8_t* mask, float error_rate, int64_t* adj_off, int32_t* adj, int64_t adj_cap) {
+    std::vector<hso::Column> snps((size_t)n_snps);
+    for (int s = 0; s < n_snps; ++s) {
+        snps[(size_t)s].ref_base = snp_ref[s]; snps[(size_t)s].second_base = snp_alt[s];
+        for (int64_t e = col_off[s]; e < col_off[s + 1]; ++e) { snps[(size_t)s].readIdxs.push_back((unsigned)col_idx[e]); snps[(size_t)s].content.push_back(col_code[e]); }
+    }
+    std::vector<bool> m((size_t)n_reads);
+    for (int i = 0; i < n_reads; ++i) m[(size_t)i] = mask[i] != 0;
+    std::vector<std::vector<int>> nl((size_t)n_reads);
+    hso::create_read_graph_low_memory(snps, m, nl, error_rate);
+    adj_off[0] = 0;
+    for (int i = 0; i < n_reads; ++i) {
+        adj_off[i + 1] = adj_off[i] + (int64_t)nl[(size_t)i].size();
+        if (adj_off[i + 1] > adj_cap) return -1;
+        for (size_t k = 0; k < nl[(size_t)i].size(); ++k) adj[adj_off[i] + (int64_t)k] = nl[(size_t)i][k];
+    }
+    return 0;
+}
+
 // K7 oracle: cluster_graph.cpp:240-310
 int hso_chinese_whispers(int32_t n, const int32_t* adj_off, const int32_t* adj, const uint8_t* mask, const int32_t* init,
                          uint32_t seed, int32_t* out, int32_t* sweeps) {

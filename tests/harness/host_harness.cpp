@@ -4,6 +4,7 @@
 // The product library itself has no such backend (hs_capi.hip only knows HIP).
 //   host_harness call_variants  <11 positional args of HS_call_variants>
 //   host_harness separate_reads <9 positional args of HS_separate_reads>
+//   host_harness graph_taps <cases.i64> <out.i64>   (sr_run in the graphs mode of its test taps; both files are streams of int64, see graph_taps())
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -387,9 +388,76 @@ static int selftest() {
     return bad ? 1 : 0;
 }
 
+// `graph_taps`: stage-4 inputs given directly -> sr_run (graphs mode of hs::SrTaps) on the oracle's device interface -> the windows of the call's
+// window set with their neighbour lists. Input, int64 each: C, window, low_memory, seed, error rate (float bits); per contig: length, N, S, E, then
+// read_start[N], read_end[N], snp_pos[S], snp_ref[S], snp_alt[S], col_off[S + 1], col_idx[E], col_code[E]. Output: W, rows resolved on the host; per
+// window: contig, kind, m, ids[m], then per row: degree, neighbours (read ids).
+static int graph_taps(const char* in_path, const char* out_path) {
+    std::vector<int64_t> v;
+    {
+        std::ifstream f(in_path, std::ios::binary);
+        if (!f) return 2;
+        f.seekg(0, std::ios::end); const std::streamoff n = f.tellg(); f.seekg(0);
+        if (n < 40 || n % 8) return 2;
+        v.resize((size_t)n / 8);
+        f.read((char*)v.data(), n);
+        if (!f) return 2;
+    }
+    size_t at = 0;
+    bool bad = false;
+    auto take = [&](size_t n) -> const int64_t* { if (n > v.size() - at) { bad = true; return nullptr; } const int64_t* p = v.data() + at; at += n; return p; };
+    const int64_t* h = take(5);
+    const int C = (int)h[0], window = (int)h[1], low_memory = (int)h[2];
+    const uint32_t seed = (uint32_t)h[3];
+    float error_rate; { const uint32_t b = (uint32_t)h[4]; std::memcpy(&error_rate, &b, 4); }
+    if (C < 0 || (size_t)C > v.size()) return 2;
+    struct Store { std::vector<int32_t> rs, re, pos, idx; std::vector<uint8_t> ref, alt, code; std::vector<int64_t> off; };
+    std::vector<Store> st((size_t)C);
+    std::vector<hs_sr_contig> hc((size_t)C);
+    for (int c = 0; c < C; ++c) {
+        const int64_t* q = take(4);
+        if (bad || q[1] < 0 || q[2] < 0 || q[3] < 0) return 2;
+        const size_t N = (size_t)q[1], S = (size_t)q[2], E = (size_t)q[3];
+        Store& t = st[(size_t)c];
+        auto fill = [&](auto& dst, size_t n) { const int64_t* p = take(n); if (!p) return; dst.resize(n); for (size_t k = 0; k < n; ++k) dst[k] = (typename std::decay<decltype(dst)>::type::value_type)p[k]; };
+        fill(t.rs, N); fill(t.re, N); fill(t.pos, S); fill(t.ref, S); fill(t.alt, S); fill(t.off, S + 1); fill(t.idx, E); fill(t.code, E);
+        if (bad || t.off[0] != 0 || t.off[S] != (int64_t)E) return 2;
+        for (size_t k = 0; k < S; ++k) if (t.off[k + 1] < t.off[k]) return 2;
+        for (size_t k = 0; k < E; ++k) if (t.idx[k] < 0 || (size_t)t.idx[k] >= N) return 2;
+        t.idx.push_back(0); t.code.push_back(0); t.rs.push_back(0); t.re.push_back(0); t.pos.push_back(0); t.ref.push_back(0); t.alt.push_back(0);      // (never null)
+        hs_sr_contig& x = hc[(size_t)c];
+        x.length = q[0]; x.n_reads = (int32_t)N; x.read_start = t.rs.data(); x.read_end = t.re.data();
+        x.n_snps = (int32_t)S; x.snp_pos = t.pos.data(); x.snp_ref = t.ref.data(); x.snp_alt = t.alt.data();
+        x.col_off = t.off.data(); x.col_idx = t.idx.data(); x.col_code = t.code.data(); x.ploidy = 0;
+    }
+    OracleSrOps ops(seed);
+    hs::SrTaps tp;
+    tp.graphs = true;
+    hs_sr_result* res = nullptr;
+    if (int rc = hs::sr_run(ops, hc.data(), C, window, error_rate, low_memory, seed, 1, &res, nullptr, nullptr, &tp)) { std::cerr << hs::g_err << "\n"; return rc; }
+    if (res) return 3;      // (the graphs mode leaves no result)
+    const hs::SrGraphTaps& f = tp.front;
+    std::vector<int64_t> o;
+    const size_t W = f.win_contig.size();
+    o.push_back((int64_t)W); o.push_back(f.rows_on_host);
+    for (size_t w = 0; w < W; ++w) {
+        const int64_t r0 = f.win_row0[w], r1 = f.win_row0[w + 1];
+        o.push_back(f.win_contig[w]); o.push_back(f.win_kind[w]); o.push_back(r1 - r0);
+        for (int64_t r = r0; r < r1; ++r) o.push_back(f.mask_ids[(size_t)r]);
+        for (int64_t r = r0; r < r1; ++r) {
+            o.push_back(f.nbr_off[(size_t)r + 1] - f.nbr_off[(size_t)r]);
+            for (int64_t e = f.nbr_off[(size_t)r]; e < f.nbr_off[(size_t)r + 1]; ++e) o.push_back(f.nbr[(size_t)e]);
+        }
+    }
+    std::ofstream out(out_path, std::ios::binary);
+    out.write((const char*)o.data(), (std::streamsize)(o.size() * 8));
+    return out ? 0 : 2;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     if (!std::strcmp(argv[1], "selftest")) return selftest();
+    if (!std::strcmp(argv[1], "graph_taps")) return argc == 4 ? graph_taps(argv[2], argv[3]) : 2;
     if (!std::strcmp(argv[1], "call_variants")) {
         if (argc < 13) return 2;
         char** a = argv + 1;

@@ -134,6 +134,24 @@ def read_graph(sim, diff, mask, error_rate):
     return [adj[off[i]:off[i + 1]].tolist() for i in range(n)]
 
 
+def read_graph_low_memory(n_reads, snp_ref, snp_alt, col_off, col_idx, col_code, mask, error_rate):
+    """create_read_graph_low_memory for one window of a contig (its SNP columns, the window's mask over the contig's reads) -> list of sorted
+    neighbour lists, one per read of the contig"""
+    snp_ref = np.ascontiguousarray(snp_ref, np.uint8); snp_alt = np.ascontiguousarray(snp_alt, np.uint8)
+    col_off = np.ascontiguousarray(col_off, np.int64); mask = np.ascontiguousarray(mask, np.uint8)
+    col_idx = np.ascontiguousarray(col_idx if len(col_idx) else np.zeros(1), np.int32); col_code = np.ascontiguousarray(col_code if len(col_code) else np.zeros(1), np.uint8)
+    m = int(mask.sum())
+    off = np.zeros(n_reads + 1, np.int64); adj = np.zeros(max(m * m, 1), np.int32)
+    L = lib()
+    L.hso_read_graph_low_memory.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                            C.c_void_p, C.c_int64]
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = L.hso_read_graph_low_memory(C.c_int32(n_reads), C.c_int32(len(snp_ref)), p(snp_ref), p(snp_alt), p(col_off), p(col_idx), p(col_code), p(mask),
+                                     C.c_float(error_rate), p(off), p(adj), C.c_int64(len(adj)))
+    assert rc == 0
+    return [adj[off[i]:off[i + 1]].tolist() for i in range(n_reads)]
+
+
 def chinese_whispers(adj_lists, mask, init, seed=12345):
     n = len(adj_lists)
     off = np.zeros(n + 1, np.int32); off[1:] = np.cumsum([len(a) for a in adj_lists])
