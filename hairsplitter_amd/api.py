@@ -26,6 +26,7 @@ SYMBOLS = [
     "hs_cv_result_destroy", "hs_cv_select", "hs_cv_run_range", "hs_cv_selection_destroy", "hs_sr_run", "hs_sr_run_cv", "hs_sr_run_cv_range", "hs_pipeline_create", "hs_pipeline_select", "hs_pipeline_run", "hs_pipeline_destroy", "hs_pipeline_thread_devices", "hs_cv_batch_device", "hs_sr_result_destroy", "hs_sr_window_size", "hs_call_variants_main", "hs_call_variants_epilogue",
     "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_edlib_align", "hs_edlib_align_bytes", "hs_alignment_to_cigar", "hs_reattach_ends", "hs_trim_polished", "hs_reattach_ends_bytes", "hs_trim_polished_bytes", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
     "hs_polish_inputs", "hs_polish_inputs_from_files", "hs_polish_result_destroy", "hs_polish_inputs_main",
+    "hs_moves_to_cigar", "hs_realign_intervals", "hs_realign_records_destroy", "hs_cv_batch_create_paf", "hs_cv_batch_create_sam",
 ]
 
 HS_NKERNELS = 28
@@ -117,6 +118,7 @@ def load() -> C.CDLL:
     lib.hs_kernel_stats_reset.restype = None
     lib.hs_kernel_stats_get.restype = None
     lib.hs_kernel_stats_get.argtypes = [C.POINTER(KernelStats)]
+    lib.hs_realign_records_destroy.restype = None
     _lib = lib
     return lib
 
@@ -369,6 +371,43 @@ class CvBatch:
             lib.hs_cv_result_destroy(res)
         return sr
 
+    @classmethod
+    def _adopt(cls, handle, create_s, records=None) -> "CvBatch":
+        """a batch the library made itself (no FlatBatch behind it: `flat` is None, `records` what it was made from)"""
+        o = object.__new__(cls)
+        o.flat = None
+        o.handle = handle
+        o.create_s = create_s
+        o.records = records
+        return o
+
+    @classmethod
+    def from_paf(cls, gfa: str, reads: str, paf: str, n_threads: int = 0) -> "CvBatch":
+        """hs_cv_batch_create_paf: the files of hs_realign_paf -> a resident batch. Every PAF line's read segment is cut, aligned against
+        its contig window and turned into CIGAR words on the device; no SAM in between. `records` holds the records and the phase times."""
+        import time
+        require_gpu()
+        lib = load()
+        h = C.c_void_p(); r = C.POINTER(RealignRecords)()
+        t0 = time.perf_counter()
+        _check(lib.hs_cv_batch_create_paf(gfa.encode(), reads.encode(), paf.encode(), C.c_int32(n_threads), C.byref(h), C.byref(r)))
+        dt = time.perf_counter() - t0
+        try:
+            rec = _realign_records_to_dict(r)
+        finally:
+            lib.hs_realign_records_destroy(r)
+        return cls._adopt(h, dt, rec)
+
+    @classmethod
+    def from_sam(cls, gfa: str, reads: str, sam: str, n_threads: int = 0) -> "CvBatch":
+        """hs_cv_batch_create_sam: the three files of HS_call_variants -> a resident batch (its parser, then hs_cv_batch_create)"""
+        import time
+        require_gpu()
+        h = C.c_void_p()
+        t0 = time.perf_counter()
+        _check(load().hs_cv_batch_create_sam(gfa.encode(), reads.encode(), sam.encode(), C.c_int32(n_threads), C.byref(h)))
+        return cls._adopt(h, time.perf_counter() - t0)
+
     def close(self):
         if self.handle:
             load().hs_cv_batch_destroy(self.handle)
@@ -379,6 +418,27 @@ class CvBatch:
             self.close()
         except Exception:
             pass
+
+
+class RealignRecords(C.Structure):
+    _fields_ = [("n_intervals", C.c_int32), ("n_rec", C.c_int32), ("n_contigs", C.c_int32), ("contig_rec_off", C.POINTER(C.c_int32)),
+                ("rec_interval", C.POINTER(C.c_int32)), ("rec_read", C.POINTER(C.c_int32)), ("rec_pos", C.POINTER(C.c_int32)), ("rec_dist", C.POINTER(C.c_int32)),
+                ("rec_strand", C.POINTER(C.c_uint8)), ("rec_cig_off", C.POINTER(C.c_int64)), ("cigar", C.POINTER(C.c_uint32)),
+                ("n_dropped", C.c_int64), ("dropped", C.POINTER(C.c_int32)),
+                ("t_cut_ms", C.c_double), ("t_align_ms", C.c_double), ("t_cigar_ms", C.c_double), ("t_download_ms", C.c_double),
+                ("n_rounds", C.c_int64), ("move_bytes", C.c_int64), ("cigar_words", C.c_int64)]
+
+
+def _realign_records_to_dict(res) -> Dict:
+    r = res.contents
+    arr = lambda p, n: np.ctypeslib.as_array(p, (max(int(n), 1),))[:int(n)].copy()
+    n = r.n_rec
+    off = arr(r.rec_cig_off, n + 1)
+    return {"n_intervals": int(r.n_intervals), "n_rec": int(n), "n_contigs": int(r.n_contigs), "contig_rec_off": arr(r.contig_rec_off, r.n_contigs + 1),
+            "rec_interval": arr(r.rec_interval, n), "rec_read": arr(r.rec_read, n), "rec_pos": arr(r.rec_pos, n), "rec_dist": arr(r.rec_dist, n),
+            "rec_strand": arr(r.rec_strand, n), "rec_cig_off": off, "cigar": arr(r.cigar, off[-1]), "n_dropped": int(r.n_dropped), "dropped": arr(r.dropped, r.n_dropped),
+            "t_cut_ms": float(r.t_cut_ms), "t_align_ms": float(r.t_align_ms), "t_cigar_ms": float(r.t_cigar_ms), "t_download_ms": float(r.t_download_ms),
+            "n_rounds": int(r.n_rounds), "move_bytes": int(r.move_bytes), "cigar_words": int(r.cigar_words)}
 
 
 class CvSelection(C.Structure):
@@ -1328,3 +1388,75 @@ def reattach_ends(backbones, consensuses, alphabet=None):
 def trim_polished(to_polish, newcontigs, overhang_left, overhang_right, alphabet=None):
     """create_new_contigs.cpp:556-629, batched. alphabet as in reattach_ends (hs_trim_polished / hs_trim_polished_bytes)"""
     return _string_batch(_stage5_fn("hs_trim_polished", alphabet), [to_polish, newcontigs], [overhang_left, overhang_right])
+
+
+def moves_to_cigar(moves_list, clips=None, spans=False, count_only=False, ops_len=None):
+    """hs_moves_to_cigar: edlib move arrays (0 '=', 1 insertion, 2 deletion, 3 mismatch), one per pair, as hs_edlib_hw_align leaves them ->
+    list of uint32 arrays of packed CIGAR words (len << 4 | op; M 0, I 1, D 2, S 4). An entry that is None stands for a pair without an
+    alignment (ops_len -1): no words. clips: [(left, right), ...] soft clips around the runs, or None. spans=True: also an int32 array
+    [n, 2] of reference and read spans. count_only=True: the word offsets [n + 1] instead of the words (no word is written).
+    ops_len: the d_ops_len the call sees, where it is to differ from the arrays' lengths (a pair keeps its array's room)."""
+    import torch
+    require_gpu()
+    dev = "cuda:0"
+    n = len(moves_list)
+    arrs = [np.zeros(0, np.uint8) if m is None else _np(m, np.uint8).reshape(-1) for m in moves_list]
+    lens = np.array([-1 if m is None else len(a) for m, a in zip(moves_list, arrs)], np.int32)
+    if ops_len is not None:
+        lens = _np(ops_len, np.int32)
+        assert len(lens) == n
+    oo = np.zeros(n + 1, np.int64)
+    np.cumsum([len(a) for a in arrs], out=oo[1:])
+    flat = np.concatenate(arrs) if n and oo[-1] else np.zeros(1, np.uint8)
+    d_ops = torch.from_numpy(flat).to(dev)
+    d_len = torch.from_numpy(lens if n else np.zeros(1, np.int32)).to(dev)
+    d_cl = d_cr = None
+    if clips is not None:
+        cl = _np([c[0] for c in clips], np.int32); cr = _np([c[1] for c in clips], np.int32)
+        assert len(cl) == n
+        d_cl = torch.from_numpy(cl if n else np.zeros(1, np.int32)).to(dev); d_cr = torch.from_numpy(cr if n else np.zeros(1, np.int32)).to(dev)
+    d_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    d_sp = torch.zeros((max(n, 1), 2), dtype=torch.int32, device=dev) if spans else None
+    total = C.c_int64(0)
+    lib = load()
+    call = lambda d_words, cap: lib.hs_moves_to_cigar(_p(d_ops), _hp(oo, C.c_int64), _p(d_len), _p(d_cl), _p(d_cr), C.c_int32(n), _p(d_off), _p(d_words), C.c_int64(cap),
+                                                      _p(d_sp), C.byref(total), C.c_void_p(0))
+    _check(call(None, 0))
+    if not count_only:
+        d_words = torch.zeros(max(int(total.value), 1), dtype=torch.int32, device=dev)
+        _check(call(d_words, int(total.value)))
+    torch.cuda.synchronize()
+    off = d_off.cpu().numpy()
+    if count_only:
+        out = off
+    else:
+        w = d_words.cpu().numpy().view(np.uint32)
+        out = [w[off[i]:off[i + 1]].copy() for i in range(n)]
+    return (out, d_sp.cpu().numpy()[:n]) if spans else out
+
+
+def realign_intervals(flat_sequences, intervals, pad: int = 100, want_batch: bool = True):
+    """hs_realign_intervals: intervals held in memory -> alignment records with CIGARs (and the resident batch made from them).
+    flat_sequences: anything with contig_seq / contig_off / read_seq / read_off as a FlatBatch has them (codes 0..3, one per byte).
+    intervals: rows (read, contig, strand, qstart, qend, tstart, tend); strand 1 forward, 0 reverse; half-open, 0-based.
+    Returns (records dict, CvBatch or None): records grouped by contig, input order inside a contig (rec_interval says which row)."""
+    import time
+    require_gpu()
+    lib = load()
+    g = (lambda k: flat_sequences[k]) if isinstance(flat_sequences, dict) else (lambda k: getattr(flat_sequences, k))
+    cseq, coff, rseq, roff = _np(g("contig_seq"), np.uint8), _np(g("contig_off"), np.int64), _np(g("read_seq"), np.uint8), _np(g("read_off"), np.int64)
+    iv = np.asarray(intervals, dtype=np.int64).reshape(-1, 7)
+    if iv.size and (np.abs(iv).max() > 0x7fffffff):
+        raise HsError("realign_intervals: interval fields are 32-bit")
+    col = [_np(iv[:, k], np.uint8 if k == 2 else np.int32) for k in range(7)]
+    h = C.c_void_p(); r = C.POINTER(RealignRecords)()
+    t0 = time.perf_counter()
+    _check(lib.hs_realign_intervals(_hp(cseq, C.c_uint8), _hp(coff, C.c_int64), C.c_int32(len(coff) - 1), _hp(rseq, C.c_uint8), _hp(roff, C.c_int64), C.c_int32(len(roff) - 1),
+                                    _hp(col[0], C.c_int32), _hp(col[1], C.c_int32), _hp(col[2], C.c_uint8), _hp(col[3], C.c_int32), _hp(col[4], C.c_int32),
+                                    _hp(col[5], C.c_int32), _hp(col[6], C.c_int32), C.c_int32(len(iv)), C.c_int32(pad), C.byref(r), C.byref(h) if want_batch else None))
+    dt = time.perf_counter() - t0
+    try:
+        rec = _realign_records_to_dict(r)
+    finally:
+        lib.hs_realign_records_destroy(r)
+    return rec, (CvBatch._adopt(h, dt, rec) if want_batch else None)

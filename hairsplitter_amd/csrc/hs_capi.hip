@@ -7,6 +7,7 @@
 //   hs_capi_stage.inc    stage-level C ABI on one device, contig groups (hs_pipeline_*)
 //   hs_capi_multi.inc    several GPUs in one process
 //   hs_capi_polish.inc   the polisher's inputs of the next stage (hs_polish_inputs)
+//   hs_capi_realign.inc  the CIGAR-less input in memory: intervals -> CIGAR words on the device -> a batch (hs_realign_intervals)
 // There is no CPU fallback anywhere in this file: without a usable HIP device every entry
 // point fails with HS_ENODEVICE.
 #include <hip/hip_runtime.h>
@@ -40,6 +41,7 @@
 #include "hs_kernels_cols.hip"
 #include "hs_kernels_loopa.hip"
 #include "hs_kernels_polish.hip"
+#include "hs_kernels_realign.hip"
 
 namespace hs {
 static thread_local std::string g_err;
@@ -64,3 +66,4 @@ using hs::set_error;
 #include "hs_capi_stage.inc"
 #include "hs_capi_multi.inc"
 #include "hs_capi_polish.inc"
+#include "hs_capi_realign.inc"

@@ -1,0 +1,309 @@
+// hs_capi_realign.inc -- part of hs_capi.hip: the CIGAR-less input without the files in between. Intervals in memory (or the PAF
+// lines of hs_realign.cpp's parser) -> pairs cut on the device (k_realign_cut) -> A1 (hs_edlib_hw_align) -> CIGAR words on the
+// device (k_m2c_count, the scan, k_m2c_write; hs_kernels_realign.hip) -> the records in the layout of hs_cv_batch_create and the
+// batch made from them. Per round only the words, positions, distances and lengths come back to the host.
+namespace {
+
+// The three launches of hs_moves_to_cigar with their scratch: count() leaves offsets, total and spans, write() lays the words down.
+struct MovesToCigar {
+    DBuf d_ops_off, d_chunk_first, d_cnt, d_start, d_woff, d_scan;
+    UploadPack pk;
+    std::vector<int64_t> ops_off;
+    std::vector<int32_t> chunk_first;
+    int32_t n = 0, n_chunks = 0;
+    const uint8_t* d_ops = nullptr; const int32_t* d_ops_len = nullptr; const int32_t* d_clip_left = nullptr; const int32_t* d_clip_right = nullptr;
+
+    int count(const uint8_t* ops, const int64_t* h_ops_off, const int32_t* ops_len, const int32_t* clip_left, const int32_t* clip_right, int32_t n_pairs,
+              int64_t* d_word_off, int32_t* d_spans, int64_t* n_words, hipStream_t stream) {
+        n = n_pairs; d_ops = ops; d_ops_len = ops_len; d_clip_left = clip_left; d_clip_right = clip_right;
+        ops_off.assign(h_ops_off, h_ops_off + n + 1);
+        chunk_first.assign((size_t)n + 1, 0);
+        int64_t chunks = 0;
+        for (int32_t i = 0; i < n; ++i) {
+            const int64_t room = ops_off[(size_t)i + 1] - ops_off[(size_t)i];
+            if (room < 0 || room >= ((int64_t)1 << 28)) { set_error("hs_moves_to_cigar: pair " + std::to_string(i) + " has room for " + std::to_string(room) + " moves (0 .. 2^28 - 1: the length field of a CIGAR word)"); return HS_EINVAL; }
+            chunks += (room + hsdev::M2C_CHUNK - 1) / hsdev::M2C_CHUNK;
+            if (chunks > 0x7fffffff - 4) { set_error("hs_moves_to_cigar: more than 2^31 chunks of moves in one call"); return HS_EINVAL; }
+            chunk_first[(size_t)i + 1] = (int32_t)chunks;
+        }
+        n_chunks = (int32_t)chunks;
+        if (d_spans) HS_HIP(hipMemsetAsync(d_spans, 0, sizeof(int32_t) * 2 * (size_t)n, stream));
+        if (n_chunks == 0) {
+            HS_HIP(hipMemsetAsync(d_word_off, 0, sizeof(int64_t) * ((size_t)n + 1), stream));
+            *n_words = 0;
+            return stream_wait(stream);
+        }
+        pk.add(ops_off, d_ops_off); pk.add(chunk_first, d_chunk_first);
+        if (int rc = pk.commit(stream)) return rc;
+        if (int rc = d_cnt.alloc(sizeof(int32_t) * (size_t)n_chunks)) return rc;
+        if (int rc = d_start.alloc(sizeof(int32_t) * (size_t)n_chunks)) return rc;
+        if (int rc = d_woff.alloc(sizeof(int64_t) * ((size_t)n_chunks + 1))) return rc;
+        hipLaunchKernelGGL(hsdev::k_m2c_count, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, stream, d_ops, d_ops_off.as<int64_t>(), d_ops_len, d_clip_left, d_clip_right, n,
+                           d_chunk_first.as<int32_t>(), n_chunks, d_cnt.as<int32_t>(), d_start.as<int32_t>(), d_spans);
+        HS_HIP(hipGetLastError());
+        if (int rc = exclusive_scan_launch(d_cnt.as<int32_t>(), n_chunks, d_woff.as<int64_t>(), d_scan, stream)) return rc;
+        hipLaunchKernelGGL(hsdev::k_m2c_pair_off, dim3((unsigned)(n / 256 + 1)), dim3(256), 0, stream, d_chunk_first.as<int32_t>(), n, d_woff.as<int64_t>(), d_word_off);
+        HS_HIP(hipGetLastError());
+        return copy_d2h(n_words, d_woff.as<int64_t>() + n_chunks, sizeof(int64_t), stream);
+    }
+    // (after count(); d_words has room for the total it returned)
+    int write(uint32_t* d_words, hipStream_t stream) {
+        if (n_chunks == 0) return HS_OK;
+        hipLaunchKernelGGL(hsdev::k_m2c_write, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, stream, d_ops, d_ops_off.as<int64_t>(), d_ops_len, d_clip_left, d_clip_right, n,
+                           d_chunk_first.as<int32_t>(), n_chunks, d_start.as<int32_t>(), d_woff.as<int64_t>(), d_words);
+        HS_HIP(hipGetLastError());
+        return stream_wait(stream);
+    }
+};
+
+// one of the two buffers hs_edlib_hw_align takes, cut from a resident sequence buffer: d_out has room for off[m] rounded up to 16
+static int realign_cut_launch(const DBuf& d_off, const DBuf& d_src, const uint8_t* d_rev, int32_t m, int64_t total, const uint8_t* d_seq, uint8_t* d_out, hipStream_t stream) {
+    if (m <= 0 || total <= 0) return HS_OK;
+    const int64_t out_bytes = (total + 15) & ~(int64_t)15;
+    hipLaunchKernelGGL(hsdev::k_realign_cut, dim3((unsigned)((out_bytes + 4095) >> 12)), dim3(256), 0, stream, d_off.as<int64_t>(), d_src.as<int64_t>(), d_rev, m, d_seq, d_out, out_bytes);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+
+// a job's sequences on the device as hs_cv_batch keeps them: HS_SEQ_PAD zero bytes, the bases, HS_SEQ_PAD zero bytes
+static int upload_padded(DBuf& d, const uint8_t* src, size_t bytes) {
+    if (int rc = d.alloc(bytes + 2 * HS_SEQ_PAD)) return rc;
+    HS_HIP(hipMemset(d.p, 0, HS_SEQ_PAD));
+    HS_HIP(hipMemset((char*)d.p + HS_SEQ_PAD + bytes, 0, HS_SEQ_PAD));
+    if (bytes) HS_HIP(hipMemcpy((char*)d.p + HS_SEQ_PAD, src, bytes, hipMemcpyHostToDevice));
+    return HS_OK;
+}
+
+template <class T> static T* malloc_copy(const std::vector<T>& v) {
+    T* p = (T*)std::malloc(std::max<size_t>(1, v.size()) * sizeof(T));
+    if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
+    return p;
+}
+
+}  // namespace
+
+int hs_moves_to_cigar(const uint8_t* d_ops, const int64_t* h_ops_off, const int32_t* d_ops_len, const int32_t* d_clip_left, const int32_t* d_clip_right, int32_t n,
+                      int64_t* d_word_off, uint32_t* d_words, int64_t words_cap, int32_t* d_spans, int64_t* n_words, void* stream) {
+    if (int rc = require_device()) return rc;
+    if (n < 0) { set_error("hs_moves_to_cigar: negative number of pairs"); return HS_EINVAL; }
+    if (n == 0) {
+        if (n_words) *n_words = 0;
+        if (d_word_off) { HS_HIP(hipMemsetAsync(d_word_off, 0, sizeof(int64_t), (hipStream_t)stream)); return stream_wait((hipStream_t)stream); }
+        return HS_OK;
+    }
+    if (!d_ops || !h_ops_off || !d_ops_len || !d_word_off || !n_words || (d_words && words_cap < 0)) { set_error("hs_moves_to_cigar: bad arguments"); return HS_EINVAL; }
+    MovesToCigar mc;
+    if (int rc = mc.count(d_ops, h_ops_off, d_ops_len, d_clip_left, d_clip_right, n, d_word_off, d_spans, n_words, (hipStream_t)stream)) return rc;
+    if (!d_words) return HS_OK;
+    if (words_cap < *n_words) { set_error("hs_moves_to_cigar: the pairs have " + std::to_string(*n_words) + " words, words_cap is " + std::to_string(words_cap)); return HS_EINVAL; }
+    return mc.write(d_words, (hipStream_t)stream);      // (synchronous: the scratch goes back to the pool with this scope)
+}
+
+void hs_realign_records_destroy(hs_realign_records* r) {
+    if (!r) return;
+    void* p[] = {r->contig_rec_off, r->rec_interval, r->rec_read, r->rec_pos, r->rec_dist, r->rec_strand, r->rec_cig_off, r->cigar, r->dropped};
+    for (void* q : p) std::free(q);
+    std::free(r);
+}
+
+int hs_realign_intervals(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads,
+                         const int32_t* iv_read, const int32_t* iv_contig, const uint8_t* iv_strand, const int32_t* iv_qstart, const int32_t* iv_qend,
+                         const int32_t* iv_tstart, const int32_t* iv_tend, int32_t n_intervals, int32_t pad, hs_realign_records** out, hs_cv_batch** batch) {
+    if (int rc = require_device()) return rc;
+    if (!out || !h_contig_off || !h_read_off || n_contigs < 0 || n_reads < 0 || n_intervals < 0 || pad < 0
+        || (n_intervals > 0 && (!iv_read || !iv_contig || !iv_strand || !iv_qstart || !iv_qend || !iv_tstart || !iv_tend))) {
+        set_error("hs_realign_intervals: bad arguments"); return HS_EINVAL;
+    }
+    *out = nullptr;
+    if (batch) *batch = nullptr;
+    try {
+        const size_t n = (size_t)n_intervals;
+        // the checks of hs_realign.cpp's parser on every interval; the intervals of every contig, in input order
+        std::vector<int32_t> contig_iv_off((size_t)n_contigs + 1, 0);
+        for (size_t i = 0; i < n; ++i) {
+            const bool ids = iv_read[i] >= 0 && iv_read[i] < n_reads && iv_contig[i] >= 0 && iv_contig[i] < n_contigs;
+            const int64_t rl = ids ? h_read_off[iv_read[i] + 1] - h_read_off[iv_read[i]] : 0, cl = ids ? h_contig_off[iv_contig[i] + 1] - h_contig_off[iv_contig[i]] : 0;
+            if (!ids || iv_qstart[i] < 0 || iv_qend[i] > rl || iv_qstart[i] >= iv_qend[i] || iv_tstart[i] < 0 || iv_tend[i] > cl || iv_tstart[i] >= iv_tend[i]) {
+                set_error("hs_realign_intervals: interval " + std::to_string(i) + " (read " + std::to_string(iv_read[i]) + " [" + std::to_string(iv_qstart[i]) + ", " + std::to_string(iv_qend[i])
+                          + "), contig " + std::to_string(iv_contig[i]) + " [" + std::to_string(iv_tstart[i]) + ", " + std::to_string(iv_tend[i]) + ")) does not fit its read / contig");
+                return HS_EINVAL;
+            }
+            contig_iv_off[(size_t)iv_contig[i] + 1]++;
+        }
+        for (int c = 0; c < n_contigs; ++c) contig_iv_off[(size_t)c + 1] += contig_iv_off[(size_t)c];
+        std::vector<int32_t> order(n);
+        {
+            std::vector<int32_t> at(contig_iv_off.begin(), contig_iv_off.end() - 1);
+            for (size_t i = 0; i < n; ++i) order[(size_t)at[(size_t)iv_contig[i]]++] = (int32_t)i;
+        }
+        const hipStream_t stream = nullptr;
+        DBuf d_contigs, d_reads;      // the job's first device copy of the sequences: back in the pool before the batch is made
+        if (n) {
+            if (int rc = upload_padded(d_contigs, h_contig_seq, (size_t)h_contig_off[n_contigs])) return rc;
+            if (int rc = upload_padded(d_reads, h_read_seq, (size_t)h_read_off[n_reads])) return rc;
+        }
+        std::vector<int32_t> rec_interval, rec_read, rec_pos, rec_dist, contig_rec_off((size_t)n_contigs + 1, 0), dropped;
+        std::vector<uint8_t> rec_strand;
+        std::vector<int64_t> rec_cig_off(1, 0);
+        std::vector<uint32_t, hs::NoInitAlloc<uint32_t>> cigar;
+        double t_cut = 0, t_align = 0, t_cigar = 0, t_download = 0;
+        int64_t n_rounds = 0, move_bytes = 0;
+        auto wall = [] { return std::chrono::steady_clock::now(); };
+        auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+        const size_t chunk_bases = hs::realign_chunk_bases();
+        auto window = [&](size_t i, int& w0, int& w1) {
+            w0 = std::max(0, iv_tstart[i] - pad);
+            w1 = (int)std::min<int64_t>(h_contig_off[iv_contig[i] + 1] - h_contig_off[iv_contig[i]], (int64_t)iv_tend[i] + pad);
+        };
+        size_t done = 0;
+        while (done < n) {
+            // ---- the pairs of a round, bounded as in hs_realign.cpp: a pair needs query + window bases and as many move bytes ----
+            size_t k1 = done, bases = 0;
+            while (k1 < n && (k1 == done || bases < chunk_bases) && k1 - done < 1000000) {
+                const size_t i = (size_t)order[k1];
+                int w0, w1; window(i, w0, w1);
+                bases += (size_t)(iv_qend[i] - iv_qstart[i]) + (size_t)(w1 - w0);
+                ++k1;
+            }
+            const size_t m = k1 - done;
+            // what the host needs for the launches follows from the interval lengths alone
+            std::vector<int64_t> q_off(m + 1, 0), t_off(m + 1, 0), o_off(m + 1, 0), q_src(m), t_src(m);
+            std::vector<int32_t> win0(m), clip_l(m), clip_r(m);
+            std::vector<uint8_t> rev(m);
+            for (size_t k = 0; k < m; ++k) {
+                const size_t i = (size_t)order[done + k];
+                int w0, w1; window(i, w0, w1);
+                const int qs = iv_qstart[i], qe = iv_qend[i], qlen = (int)(h_read_off[iv_read[i] + 1] - h_read_off[iv_read[i]]);
+                const bool minus = iv_strand[i] == 0;
+                win0[k] = w0; rev[k] = minus ? 1 : 0;
+                q_off[k + 1] = q_off[k] + (qe - qs); t_off[k + 1] = t_off[k] + (w1 - w0); o_off[k + 1] = o_off[k] + (qe - qs) + (w1 - w0);
+                q_src[k] = h_read_off[iv_read[i]] + (minus ? qe - 1 : qs);
+                t_src[k] = h_contig_off[iv_contig[i]] + w0;
+                clip_l[k] = minus ? qlen - qe : qs; clip_r[k] = minus ? qs : qlen - qe;
+            }
+            DBuf dq_off, dt_off, dq_src, dt_src, d_win0, d_clip_l, d_clip_r, d_rev, dq, dt, dd, ds, de, dops, dlen, d_pos, d_word_off, d_words;
+            UploadPack pk;
+            pk.add(q_off, dq_off); pk.add(t_off, dt_off); pk.add(q_src, dq_src); pk.add(t_src, dt_src); pk.add(win0, d_win0); pk.add(clip_l, d_clip_l); pk.add(clip_r, d_clip_r); pk.add(rev, d_rev);
+            if (int rc = pk.commit(stream)) return rc;
+            if (int rc = dq.alloc((size_t)q_off[m] + 16)) return rc;
+            if (int rc = dt.alloc((size_t)t_off[m] + 16)) return rc;
+            if (int rc = dops.alloc((size_t)o_off[m] + 16)) return rc;
+            for (DBuf* b : {&dd, &ds, &de, &dlen, &d_pos}) if (int rc = b->alloc(m * sizeof(int32_t))) return rc;
+            if (int rc = d_word_off.alloc((m + 1) * sizeof(int64_t))) return rc;
+            // ---- cut ----
+            hipEvent_t ev_a = nullptr, ev_b = nullptr;
+            if (int rc = EventPair::get(&ev_a)) return rc;
+            if (int rc = EventPair::get(&ev_b)) { EventPair::cache().push_back(ev_a); return rc; }
+            struct EvBack { hipEvent_t a, b; ~EvBack() { EventPair::cache().push_back(a); EventPair::cache().push_back(b); } } ev_back{ev_a, ev_b};
+            HS_HIP(hipEventRecord(ev_a, stream));
+            if (int rc = realign_cut_launch(dq_off, dq_src, d_rev.as<uint8_t>(), (int32_t)m, q_off[m], d_reads.as<uint8_t>() + HS_SEQ_PAD, dq.as<uint8_t>(), stream)) return rc;
+            if (int rc = realign_cut_launch(dt_off, dt_src, nullptr, (int32_t)m, t_off[m], d_contigs.as<uint8_t>() + HS_SEQ_PAD, dt.as<uint8_t>(), stream)) return rc;
+            HS_HIP(hipEventRecord(ev_b, stream));
+            // ---- align (synchronous) ----
+            auto t0 = wall();
+            if (int rc = hs_edlib_hw_align(dq.as<uint8_t>(), q_off.data(), dt.as<uint8_t>(), t_off.data(), (int32_t)m, dd.as<int32_t>(), ds.as<int32_t>(), de.as<int32_t>(),
+                                           dops.as<uint8_t>(), o_off.data(), dlen.as<int32_t>(), stream)) return rc;
+            float cut_ms = 0;
+            HS_HIP(hipEventSynchronize(ev_b));
+            HS_HIP(hipEventElapsedTime(&cut_ms, ev_a, ev_b));
+            t_cut += cut_ms; t_align += ms_since(t0) - cut_ms;      // (the cut runs ahead of the aligner on the same stream)
+            // ---- moves -> words: a pair without a path gets none, so the words of the round lie compact ----
+            t0 = wall();
+            MovesToCigar mc;
+            int64_t n_words = 0;
+            if (int rc = mc.count(dops.as<uint8_t>(), o_off.data(), dlen.as<int32_t>(), d_clip_l.as<int32_t>(), d_clip_r.as<int32_t>(), (int32_t)m, d_word_off.as<int64_t>(), nullptr, &n_words, stream)) return rc;
+            if (int rc = d_words.alloc(std::max<size_t>(1, (size_t)n_words) * sizeof(uint32_t))) return rc;
+            hipLaunchKernelGGL(hsdev::k_realign_pos, dim3((unsigned)(m / 256 + 1)), dim3(256), 0, stream, d_win0.as<int32_t>(), ds.as<int32_t>(), (int)m, d_pos.as<int32_t>());
+            HS_HIP(hipGetLastError());
+            if (int rc = mc.write(d_words.as<uint32_t>(), stream)) return rc;
+            t_cigar += ms_since(t0);
+            // ---- words, positions, distances, lengths ----
+            t0 = wall();
+            std::vector<int32_t> pos(m), dist(m), olen(m);
+            std::vector<int64_t> word_off(m + 1);
+            const size_t w_at = cigar.size();
+            cigar.resize(w_at + (size_t)n_words);
+            if (int rc = d2h_pinned(cigar.data() + w_at, d_words.p, (size_t)n_words * sizeof(uint32_t), stream)) return rc;
+            if (int rc = d2h_pinned(word_off.data(), d_word_off.p, (m + 1) * sizeof(int64_t), stream)) return rc;
+            if (int rc = d2h_pinned(pos.data(), d_pos.p, m * sizeof(int32_t), stream)) return rc;
+            if (int rc = d2h_pinned(dist.data(), dd.p, m * sizeof(int32_t), stream)) return rc;
+            if (int rc = d2h_pinned(olen.data(), dlen.p, m * sizeof(int32_t), stream)) return rc;
+            t_download += ms_since(t0);
+            for (size_t k = 0; k < m; ++k) {
+                const size_t i = (size_t)order[done + k];
+                if (olen[k] <= 0) { dropped.push_back((int32_t)i); continue; }      // (edlib has no alignment for this pair: no record)
+                rec_interval.push_back((int32_t)i); rec_read.push_back(iv_read[i]); rec_pos.push_back(pos[k]); rec_dist.push_back(dist[k]);
+                rec_strand.push_back(iv_strand[i] ? 1 : 0);
+                rec_cig_off.push_back((int64_t)w_at + word_off[k + 1]);
+                contig_rec_off[(size_t)iv_contig[i] + 1]++;
+                move_bytes += olen[k];
+            }
+            ++n_rounds;
+            done = k1;
+        }
+        for (int c = 0; c < n_contigs; ++c) contig_rec_off[(size_t)c + 1] += contig_rec_off[(size_t)c];
+        std::sort(dropped.begin(), dropped.end());
+        d_contigs.release(); d_reads.release();      // (the pool hands the same blocks to hs_cv_batch_create below)
+        if (!dropped.empty())
+            std::fprintf(stderr, "hairsplitter: realign: %ld of %ld intervals have no alignment (the device aligner found none, or the read segment is longer than 2^20 bases) and were left out\n",
+                         (long)dropped.size(), (long)n);
+        hs_realign_records* r = (hs_realign_records*)std::calloc(1, sizeof(hs_realign_records));
+        if (!r) { set_error("hs_realign_intervals: out of memory"); return HS_EINVAL; }
+        r->n_intervals = n_intervals; r->n_rec = (int32_t)rec_read.size(); r->n_contigs = n_contigs;
+        r->contig_rec_off = malloc_copy(contig_rec_off); r->rec_interval = malloc_copy(rec_interval); r->rec_read = malloc_copy(rec_read); r->rec_pos = malloc_copy(rec_pos);
+        r->rec_dist = malloc_copy(rec_dist); r->rec_strand = malloc_copy(rec_strand); r->rec_cig_off = malloc_copy(rec_cig_off);
+        r->cigar = (uint32_t*)std::malloc(std::max<size_t>(1, cigar.size()) * sizeof(uint32_t));
+        if (r->cigar && !cigar.empty()) std::memcpy(r->cigar, cigar.data(), cigar.size() * sizeof(uint32_t));
+        r->n_dropped = (int64_t)dropped.size(); r->dropped = malloc_copy(dropped);
+        r->t_cut_ms = t_cut; r->t_align_ms = t_align; r->t_cigar_ms = t_cigar; r->t_download_ms = t_download;
+        r->n_rounds = n_rounds; r->move_bytes = move_bytes; r->cigar_words = (int64_t)cigar.size();
+        if (!r->contig_rec_off || !r->rec_interval || !r->rec_read || !r->rec_pos || !r->rec_dist || !r->rec_strand || !r->rec_cig_off || !r->cigar || !r->dropped) {
+            hs_realign_records_destroy(r); set_error("hs_realign_intervals: out of memory"); return HS_EINVAL;
+        }
+        if (batch) {
+            if (int rc = hs_cv_batch_create(h_contig_seq, h_contig_off, n_contigs, h_read_seq, h_read_off, n_reads, r->rec_read, r->rec_pos, r->rec_strand, r->rec_cig_off, r->cigar,
+                                            r->contig_rec_off, batch)) { hs_realign_records_destroy(r); return rc; }
+        }
+        *out = r;
+        return HS_OK;
+    } catch (const std::exception& e) { set_error(std::string("hs_realign_intervals: ") + e.what()); return HS_EINVAL; }
+}
+
+int hs_cv_batch_create_paf(const char* gfa, const char* reads, const char* paf, int32_t n_threads, hs_cv_batch** batch, hs_realign_records** recs) {
+    if (int rc = require_device()) return rc;
+    if (!gfa || !reads || !paf || !batch) { set_error("hs_cv_batch_create_paf: null argument"); return HS_EINVAL; }
+    try {
+        if (n_threads < 1) n_threads = host_threads();
+        hs::SeqSet seqs;
+        if (int rc = hs::load_sequences(gfa, reads, seqs, n_threads)) return rc;
+        std::vector<hs::PafRecord> lines;
+        long n_unknown = 0;
+        if (int rc = hs::parse_paf(paf, seqs, lines, &n_unknown)) return rc;
+        if (n_unknown) std::fprintf(stderr, "hairsplitter: realign: %ld PAF lines name a read or a contig that is in neither input file and were left out\n", n_unknown);
+        if (lines.size() > 0x7fffffffu || seqs.read_names.size() > 0x7fffffffu) { set_error("hs_cv_batch_create_paf: more than 2^31 PAF lines or reads"); return HS_EINVAL; }
+        const size_t n = lines.size();
+        std::vector<int32_t> iv_read(n), iv_contig(n), qs(n), qe(n), ts(n), te(n);
+        std::vector<uint8_t> strand(n);
+        for (size_t i = 0; i < n; ++i) {
+            const hs::PafRecord& l = lines[i];
+            iv_read[i] = (int32_t)l.read; iv_contig[i] = (int32_t)l.contig; strand[i] = l.minus ? 0 : 1; qs[i] = l.qs; qe[i] = l.qe; ts[i] = l.ts; te[i] = l.te;
+        }
+        hs_realign_records* r = nullptr;
+        if (int rc = hs_realign_intervals(seqs.contig_seq.data(), seqs.contig_off.data(), (int32_t)seqs.contig_names.size(), seqs.read_seq.data(), seqs.read_off.data(),
+                                          (int32_t)seqs.read_names.size(), iv_read.data(), iv_contig.data(), strand.data(), qs.data(), qe.data(), ts.data(), te.data(), (int32_t)n,
+                                          hs::realign_pad(), &r, batch)) return rc;
+        if (recs) *recs = r; else hs_realign_records_destroy(r);
+        return HS_OK;
+    } catch (const std::exception& e) { set_error(std::string("hs_cv_batch_create_paf: ") + e.what()); return HS_EINVAL; }
+}
+
+int hs_cv_batch_create_sam(const char* gfa, const char* reads, const char* sam, int32_t n_threads, hs_cv_batch** batch) {
+    if (int rc = require_device()) return rc;
+    if (!gfa || !reads || !sam || !batch) { set_error("hs_cv_batch_create_sam: null argument"); return HS_EINVAL; }
+    try {
+        hs::CvFileInput in;
+        if (int rc = hs::load_cv_inputs(gfa, reads, sam, false, in, n_threads < 1 ? host_threads() : n_threads)) return rc;
+        return hs_cv_batch_create(in.contig_seq.data(), in.contig_off.data(), (int32_t)in.contig_names.size(), in.read_seq.data(), in.read_off.data(), (int32_t)in.read_names.size(),
+                                  in.rec_read.data(), in.rec_pos.data(), in.rec_strand.data(), in.rec_cig_off.data(), in.cigar.data(), in.contig_rec_off.data(), batch);
+    } catch (const std::exception& e) { set_error(std::string("hs_cv_batch_create_sam: ") + e.what()); return HS_EINVAL; }
+}

@@ -141,6 +141,12 @@ int load_sequences(const std::string& gfa, const std::string& reads, SeqSet& out
 // on the device with edlib's HW path (A1)
 struct RealignStats { int64_t n_lines = 0, n_aligned = 0, query_bases = 0; double ms_device = 0, ms_total = 0; };
 int realign_paf_to_sam(const std::string& gfa, const std::string& reads, const std::string& paf, const std::string& out_sam, int n_threads, RealignStats* stats = nullptr);
+// what both CIGAR-less routes (the SAM above, the resident batch of hs_capi_realign.inc) share: the PAF lines checked against the job's
+// names and lengths, the window pad (HS_REALIGN_PAD) and the bases of one round (HS_REALIGN_CHUNK_MB)
+struct PafRecord { long read; long contig; int qlen, qs, qe, ts, te; bool minus; };
+int parse_paf(const std::string& paf, const SeqSet& seqs, std::vector<PafRecord>& recs, long* n_unknown = nullptr);
+int realign_pad();
+size_t realign_chunk_bases();
 int host_threads();
 // the .gro consumer of the next stage (hs_gaf.cpp)
 int gaf_from_files(const std::string& gfa, const std::string& reads, const std::string& sam, const std::string& gro, bool amplicon,

@@ -31,7 +31,7 @@
 namespace hs {
 
 namespace {
-struct PafRec { long read; long contig; int qlen, qs, qe, ts, te; bool minus; };
+typedef PafRecord PafRec;
 struct DevMem {      // hs_malloc'ed block, freed with the scope
     void* p = nullptr;
     ~DevMem() { if (p) hs_free(p); }
@@ -39,16 +39,12 @@ struct DevMem {      // hs_malloc'ed block, freed with the scope
 };
 }  // namespace
 
-int realign_paf_to_sam(const std::string& gfa, const std::string& reads, const std::string& paf, const std::string& out_sam, int n_threads, RealignStats* stats) {
-    if (n_threads < 1) n_threads = 1;
-    const auto t_begin = std::chrono::steady_clock::now();
-    SeqSet seqs;
-    if (int rc = load_sequences(gfa, reads, seqs, n_threads)) return rc;
+// The PAF lines of a job: qname qlen qstart qend strand tname tlen tstart tend ... against the names and lengths of `seqs`. A line that
+// names a read or a contig of neither input file is left out and counted; one whose coordinates do not fit is refused (HS_EFORMAT).
+int parse_paf(const std::string& paf, const SeqSet& seqs, std::vector<PafRecord>& recs, long* n_unknown_out) {
     std::unordered_map<std::string, long> read_of, contig_of;
     for (size_t i = 0; i < seqs.read_names.size(); ++i) read_of[seqs.read_names[i]] = (long)i;      // (a later read of the same name replaces the earlier one, as the path's own name table)
     for (size_t i = 0; i < seqs.contig_names.size(); ++i) contig_of[seqs.contig_names[i]] = (long)i;
-    // ---- the PAF lines: qname qlen qstart qend strand tname tlen tstart tend ... ----
-    std::vector<PafRec> recs;
     long n_unknown = 0;      // PAF lines that name a read or a contig of neither input file
     {
         std::ifstream f(paf);
@@ -72,11 +68,31 @@ int realign_paf_to_sam(const std::string& gfa, const std::string& reads, const s
             recs.push_back(r);
         }
     }
+    if (n_unknown_out) *n_unknown_out = n_unknown;
+    return HS_OK;
+}
+int realign_pad() {
     static const int pad = []() { const char* e = std::getenv("HS_REALIGN_PAD"); const int v = e ? std::atoi(e) : 100; return v >= 0 ? v : 100; }();
+    return pad;
+}
+size_t realign_chunk_bases() {
+    static const size_t chunk_bases = []() { const char* e = std::getenv("HS_REALIGN_CHUNK_MB"); const long v = e ? std::atol(e) : 512; return (size_t)std::max(16l, v) << 20; }();
+    return chunk_bases;
+}
+
+int realign_paf_to_sam(const std::string& gfa, const std::string& reads, const std::string& paf, const std::string& out_sam, int n_threads, RealignStats* stats) {
+    if (n_threads < 1) n_threads = 1;
+    const auto t_begin = std::chrono::steady_clock::now();
+    SeqSet seqs;
+    if (int rc = load_sequences(gfa, reads, seqs, n_threads)) return rc;
+    std::vector<PafRec> recs;
+    long n_unknown = 0;
+    if (int rc = parse_paf(paf, seqs, recs, &n_unknown)) return rc;
+    const int pad = realign_pad();
     const size_t n = recs.size();
     std::vector<std::string> sam_line(n);
     // ---- the pairs, in chunks (bounded device memory: a pair needs query + window bases and as many move bytes) ----
-    static const size_t chunk_bases = []() { const char* e = std::getenv("HS_REALIGN_CHUNK_MB"); const long v = e ? std::atol(e) : 512; return (size_t)std::max(16l, v) << 20; }();
+    const size_t chunk_bases = realign_chunk_bases();
     size_t done = 0;
     long n_aligned = 0; double ms_device = 0;
     while (done < n) {

@@ -290,6 +290,56 @@ int hs_alignment_to_cigar(const uint8_t* ops, int32_t n_ops, int32_t format, cha
 typedef struct hs_realign_stats { int64_t n_lines, n_aligned, query_bases; double ms_device, ms_total; } hs_realign_stats;
 int hs_realign_paf(const char* gfa, const char* reads, const char* paf, const char* out_sam, int32_t n_threads, hs_realign_stats* stats /* may be NULL */);
 
+/* The same input without the two files in between (hs_capi_realign.inc, kernels in hs_kernels_realign.hip): intervals in memory ->
+ * a resident hs_cv_batch. The pairs are cut on the device (k_realign_cut), aligned by hs_edlib_hw_align, and the moves it leaves
+ * become packed CIGAR words (len << 4 | op, as hs_cv_batch_create takes them) on the device; no move byte crosses to the host.
+ *
+ * hs_moves_to_cigar -- the kernel-level step: the moves of n pairs exactly as hs_edlib_hw_align leaves them (d_ops + h_ops_off[i],
+ * d_ops_len[i]; 0 '=' and 3 mismatch are one class M = 0, 1 is I = 1, 2 is D = 2; any other byte counts as M) -> the words of pair i:
+ * clip_left << 4 | 4 if the left clip is > 0, one len << 4 | op per maximal run of one class, clip_right << 4 | 4 if the right clip
+ * is > 0, at d_words + d_word_off[i]. A pair with d_ops_len[i] <= 0 gets no words. d_spans[2 i] / [2 i + 1] = M + D / M + I + clips
+ * of pair i (the reference and read span hs_cv_batch_create forms from the words). d_words == NULL counts only (offsets, total and
+ * spans). Work is split in chunks of 1024 moves, so the number of launches does not depend on n. A pair may hold at most 2^28 - 1
+ * moves (the length field of a word). Synchronous with respect to `stream`; HS_EINVAL when d_words != NULL and words_cap < *n_words
+ * (nothing is written then). */
+int hs_moves_to_cigar(const uint8_t* d_ops, const int64_t* h_ops_off /* [n+1] */, const int32_t* d_ops_len,
+                      const int32_t* d_clip_left, const int32_t* d_clip_right /* NULL: no clips */, int32_t n,
+                      int64_t* d_word_off /* [n+1] out */, uint32_t* d_words /* NULL: count only */, int64_t words_cap,
+                      int32_t* d_spans /* [n][2] reference span, read span; may be NULL */, int64_t* n_words /* host out */, void* stream);
+
+/* hs_realign_intervals -- the job-level step. Interval i says: bases [iv_qstart, iv_qend) of read iv_read lie on bases [iv_tstart,
+ * iv_tend) of contig iv_contig, on strand iv_strand (1 forward, 0 reverse: the read segment is reverse-complemented). Each is aligned
+ * against contig[max(0, tstart - pad), min(L, tend + pad)) as hs_realign_paf aligns a PAF line; an interval outside its read or
+ * contig (qstart < 0, qend > read length, qstart >= qend, and the same on the contig), or naming a read or contig that does not
+ * exist, gives HS_EINVAL and hs_last_error() names it. Rounds are bounded by HS_REALIGN_CHUNK_MB as in hs_realign_paf. The records
+ * come back grouped by contig (stable: input order inside a contig) in the layout of hs_cv_batch_create, and, when `batch` is not
+ * NULL, as a batch made from them. Everything in the result is malloc'ed: release it with hs_realign_records_destroy. */
+struct hs_cv_batch;   /* the opaque batch of the stage level below */
+typedef struct hs_realign_records {
+    int32_t n_intervals, n_rec, n_contigs;
+    int32_t* contig_rec_off;   /* [n_contigs+1] */
+    int32_t* rec_interval;     /* [n_rec] which input interval; records grouped by contig, input order inside a contig */
+    int32_t *rec_read, *rec_pos /* 0-based: window start + start location */, *rec_dist /* NM */;
+    uint8_t* rec_strand;       /* 1 forward, 0 reverse: as hs_cv_batch_create */
+    int64_t* rec_cig_off; uint32_t* cigar;
+    int64_t n_dropped; int32_t* dropped;   /* intervals the aligner had no path for (query > 2^20 bases) */
+    double t_cut_ms, t_align_ms, t_cigar_ms, t_download_ms;   /* HIP events / wall around the phases */
+    int64_t n_rounds, move_bytes, cigar_words;
+} hs_realign_records;
+int hs_realign_intervals(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs,
+                         const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads,
+                         const int32_t* iv_read, const int32_t* iv_contig, const uint8_t* iv_strand,
+                         const int32_t* iv_qstart, const int32_t* iv_qend, const int32_t* iv_tstart, const int32_t* iv_tend,
+                         int32_t n_intervals, int32_t pad,
+                         hs_realign_records** out, struct hs_cv_batch** batch /* may be NULL */);
+void hs_realign_records_destroy(hs_realign_records* r);
+/* The files of hs_realign_paf (same parser, same refusals, pad = HS_REALIGN_PAD) -> a resident batch, no SAM in between. */
+int hs_cv_batch_create_paf(const char* gfa, const char* reads, const char* paf, int32_t n_threads,
+                           struct hs_cv_batch** batch, hs_realign_records** recs /* may be NULL */);
+/* Its twin for a SAM that exists (the parser of HS_call_variants, then hs_cv_batch_create): what the file route does after hs_realign_paf
+ * has written its SAM, and the yardstick `tools/myers_bench.py realign` times hs_cv_batch_create_paf against. */
+int hs_cv_batch_create_sam(const char* gfa, const char* reads, const char* sam, int32_t n_threads, struct hs_cv_batch** batch);
+
 /* The two stage-5 computations that sit on those edlib calls, batched (two alignments per item in ONE hs_edlib_hw_align call):
  * hs_reattach_ends == tools.cpp:505-536 (the ends of the backbone that racon dropped are attached to the consensus again),
  * hs_trim_polished == create_new_contigs.cpp:556-629 (the overhangs the piece was polished with are cut off the polished

@@ -14,7 +14,11 @@ Usage: python tools/myers_bench.py [n_pairs=20000] [target_len=2000] [query_len=
        table instead of the LDS table; the equalities then make the first of them equal to every base).
        python tools/myers_bench.py dist: hs_edit_distance (distance and first end location, offsets on the device) in NW and in HW
        on the 20 000 pairs of 300 x 2 000 of the first form (8 lanes per pair) and on the 2 048 reads of 10 kb of the nw leg (a
-       wavefront per pair): pairs/s of each."""
+       wavefront per pair): pairs/s of each.
+       python tools/myers_bench.py realign [contig_kb=200] [n_contigs=4] [depth=30]: one synthetic job (ONT reads as PAF lines) from its
+       three files to a resident hs_cv_batch both ways: (a) hs_realign_paf, the SAM parser and hs_cv_batch_create
+       (hs_cv_batch_create_sam), (b) hs_cv_batch_create_paf. Wall time of each (best of two), the phase times of (b), and the bytes
+       each route brings from the device to the host."""
 import ctypes as C
 import json
 import os
@@ -179,7 +183,63 @@ def distances():
     print(json.dumps(out))
 
 
+def realign(kb, nc, depth):
+    import re
+    import tempfile
+    from hairsplitter_amd import api, synth
+    api.require_gpu()
+    lib = api.load()
+    ops_re = re.compile(r"(\d+)([MIDNSHP=X])")
+
+    class Stats(C.Structure):
+        _fields_ = [("n_lines", C.c_int64), ("n_aligned", C.c_int64), ("query_bases", C.c_int64), ("ms_device", C.c_double), ("ms_total", C.c_double)]
+    with tempfile.TemporaryDirectory() as td:
+        cs = [synth.make_contig(51, i, kb * 1000, 2, 0.01, depth, "ont") for i in range(nc)]
+        f = synth.write_files(cs, td)
+        paf, sam = os.path.join(td, "a.paf"), os.path.join(td, "re.sam")
+        d2h_a = 0      # route (a) brings the whole move buffer of every round back (query + window bytes per pair) and three ints per pair
+        with open(paf, "w") as o:
+            for c in cs:
+                for a in c.alns:
+                    qlen = len(c.reads[a.read])
+                    op, ln = a.cigar & 0xF, (a.cigar >> 4).astype(np.int64)
+                    refspan = int(ln[(op == 0) | (op == 2) | (op == 7) | (op == 8)].sum())
+                    o.write("\t".join(map(str, [c.read_names[a.read], qlen, 0, qlen, "+" if a.strand else "-", c.name, 0, a.pos, a.pos + refspan, 0, refspan, 60])) + "\n")
+                    d2h_a += qlen + (min(len(c.seq), a.pos + refspan + 100) - max(0, a.pos - 100)) + 12
+        out = {"leg": "realign", "contigs": nc, "contig_kb": kb, "depth": depth, "records": sum(len(c.alns) for c in cs)}
+        ta, tb, split_a, rec = [], [], None, None
+        for _ in range(2):
+            st = Stats()
+            t0 = time.perf_counter()
+            assert lib.hs_realign_paf(f["gfa"].encode(), f["reads"].encode(), paf.encode(), sam.encode(), C.c_int32(0), C.byref(st)) == 0, lib.hs_last_error()
+            t1 = time.perf_counter()
+            ba = api.CvBatch.from_sam(f["gfa"], f["reads"], sam)
+            t2 = time.perf_counter()
+            bp_a = ba.aligned_bp
+            ba.close()
+            if not ta or t2 - t0 < min(ta):
+                split_a = {"realign_paf_s": t1 - t0, "of_which_device_s": st.ms_device / 1e3, "sam_parser_and_batch_create_s": t2 - t1, "sam_bytes": os.path.getsize(sam)}
+            ta.append(t2 - t0)
+            t0 = time.perf_counter()
+            bb = api.CvBatch.from_paf(f["gfa"], f["reads"], paf)
+            dt = time.perf_counter() - t0
+            assert bb.aligned_bp == bp_a and bb.records["n_dropped"] == 0
+            if not tb or dt < min(tb):
+                rec = bb.records
+            tb.append(dt)
+            bb.close()
+        n = rec["n_rec"]
+        out["file_route"] = dict(split_a, wall_s=min(ta), d2h_bytes=d2h_a)
+        out["resident_route"] = {"wall_s": min(tb), "d2h_bytes": 4 * rec["cigar_words"] + n * 12 + (n + rec["n_rounds"]) * 8,
+                                 "cut_ms": rec["t_cut_ms"], "align_ms": rec["t_align_ms"], "cigar_ms": rec["t_cigar_ms"], "download_ms": rec["t_download_ms"],
+                                 "rounds": rec["n_rounds"], "move_bytes_left_on_device": rec["move_bytes"], "cigar_words": rec["cigar_words"]}
+        out["wall_ratio_file_over_resident"] = min(ta) / min(tb)
+    print(json.dumps(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "realign":
+        return realign(*(int(sys.argv[i]) if len(sys.argv) > i else d for i, d in ((2, 200), (3, 4), (4, 30))))
     if len(sys.argv) > 1 and sys.argv[1] == "nw":
         return nw_paths(int(sys.argv[2]) if len(sys.argv) > 2 else 2048, int(sys.argv[3]) if len(sys.argv) > 3 else 10000)
     if len(sys.argv) > 1 and sys.argv[1] == "bytes":
