@@ -607,7 +607,14 @@ class _SrTaps(C.Structure):
                 ("g_plane_n", C.POINTER(C.c_int32)), ("g_words", C.POINTER(C.c_int32)), ("g_plane_off", C.POINTER(C.c_int64)), ("g_alt", C.POINTER(C.c_uint64)),
                 ("g_ref", C.POINTER(C.c_uint64)), ("g_n_reads", C.POINTER(C.c_int32)), ("g_out_off", C.POINTER(C.c_int64)), ("g_read_base", C.POINTER(C.c_int64)),
                 ("g_pos_orig", C.POINTER(C.c_int32)), ("g_n_pos_orig", C.c_int64), ("g_n_plane_words", C.c_int64), ("g_n_pairs", C.c_int64),
-                ("g_matrix", C.POINTER(C.c_int32)), ("g_rows_on_host", C.c_int64), ("g_rows_late", C.c_int64), ("g_row_waves", C.c_int32)]
+                ("g_matrix", C.POINTER(C.c_int32)), ("g_rows_on_host", C.c_int64), ("g_rows_late", C.c_int64), ("g_row_waves", C.c_int32),
+                ("all_lanes", C.c_int32), ("cap_tail", C.c_int32), ("runs_lanes", C.c_int64), ("runs_overflow", C.c_int64), ("runs_rows", C.c_int64),
+                ("units_rows", C.c_int64), ("runs_wave", C.c_int64), ("runs_wave_scratch", C.c_int64), ("tail_narrow", C.c_int64), ("tail_lds", C.c_int64),
+                ("tail_scratch", C.c_int64)]
+
+
+SR_ROUTE_COUNTERS = ("all_lanes", "runs_lanes", "runs_overflow", "runs_rows", "units_rows", "runs_wave", "runs_wave_scratch", "tail_narrow", "tail_lds",
+                     "tail_scratch", "cap_tail")
 
 
 SR_TAP_SENTINEL = -2 ** 31      # HS_SR_TAP_SENTINEL
@@ -635,13 +642,9 @@ def _graph_taps_to_dict(t):
             "rows_on_host": int(t.g_rows_on_host), "rows_late": int(t.g_rows_late), "row_waves": int(t.g_row_waves)}
 
 
-def separate_reads_graph_taps(contigs: Sequence[Dict], window_size: int, error_rate: float, low_memory: bool = False, seed: int = 12345,
-                              n_threads: int = 0) -> Dict:
-    """hs_sr_run_taps in its graphs mode on stage-4 inputs given directly: one dict per contig with length, read_start, read_end, snp_pos, snp_ref,
-    snp_alt, col_off, col_idx, col_code (what separate_reads(taps=...) leaves in out["contigs"]). The call runs hs_sr_run's own code up to the read
-    graphs and returns what its kernels left (include/hairsplitter_hip.h: the g_ fields of hs_sr_taps); there is no clustering and no result."""
-    require_gpu()
-    lib = load()
+def _sr_contig_array(contigs):
+    """per-contig dicts (length, read_start, read_end, snp_pos, snp_ref, snp_alt, col_off, col_idx, col_code) -> (hs_sr_contig array, the numpy
+    buffers it points into: keep them alive for the call)"""
     Cn = len(contigs)
     arr = (SrContig * max(Cn, 1))()
     keep = []
@@ -658,11 +661,56 @@ def separate_reads_graph_taps(contigs: Sequence[Dict], window_size: int, error_r
         a.snp_pos = _hp(sp, C.c_int32); a.snp_ref = _hp(sr, C.c_uint8); a.snp_alt = _hp(sa, C.c_uint8)
         a.col_off = _hp(co, C.c_int64); a.col_idx = _hp(ci, C.c_int32); a.col_code = _hp(cc, C.c_uint8)
         a.ploidy = 0
+    return arr, keep
+
+
+def separate_reads_graph_taps(contigs: Sequence[Dict], window_size: int, error_rate: float, low_memory: bool = False, seed: int = 12345,
+                              n_threads: int = 0) -> Dict:
+    """hs_sr_run_taps in its graphs mode on stage-4 inputs given directly: one dict per contig with length, read_start, read_end, snp_pos, snp_ref,
+    snp_alt, col_off, col_idx, col_code (what separate_reads(taps=...) leaves in out["contigs"]). The call runs hs_sr_run's own code up to the read
+    graphs and returns what its kernels left (include/hairsplitter_hip.h: the g_ fields of hs_sr_taps); there is no clustering and no result."""
+    require_gpu()
+    lib = load()
+    Cn = len(contigs)
+    arr, keep = _sr_contig_array(contigs)
     res = C.POINTER(SrResult)()
     tp = C.POINTER(_SrTaps)()
     _check(_sr_run_taps_fn(lib)(C.cast(arr, C.c_void_p), C.c_int32(Cn), C.c_int32(int(window_size)), C.c_float(error_rate), C.c_int32(1 if low_memory else 0),
                                 C.c_uint32(seed), C.c_int32(n_threads), C.c_int32(1), C.byref(res), C.byref(tp)))
     out = _graph_taps_to_dict(tp.contents)
+    lib.hs_sr_taps_destroy(tp)
+    return out
+
+
+def _chain_taps_to_dict(t):
+    a = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, (max(n, 1),))[:n].astype(dt).copy()
+    Wc = int(t.n_windows)
+    row0 = a(t.win_row0, Wc + 1, np.int64); rb = a(t.run_begin, Wc + 1, np.int64)
+    n_runs = int(rb[-1]); ro = a(t.run_off, n_runs + 1, np.int64)
+    out = {"win_contig": a(t.win_contig, Wc, np.int32), "win_start": a(t.win_start, Wc, np.int32), "win_row0": row0, "mask_ids": a(t.mask_ids, int(row0[-1]), np.int32),
+           "run_begin": rb, "run_snp": a(t.run_snp, n_runs, np.int32), "run_off": ro, "run_labels": a(t.run_labels, int(ro[-1]), np.int32),
+           "third": a(t.third, int(row0[-1]), np.int32)}
+    for k in SR_ROUTE_COUNTERS:      # which kernel took which run / window (include/hairsplitter_hip.h)
+        out[k] = int(getattr(t, k))
+    return out
+
+
+def separate_reads_chain_taps(contigs: Sequence[Dict], window_size: int, error_rate: float, low_memory: bool = False, seed: int = 12345,
+                              n_threads: int = 0) -> Dict:
+    """hs_sr_run_taps in its chain mode on stage-4 inputs given directly (per-contig dicts as separate_reads_graph_taps takes them): the result
+    dict of the call plus "taps", as separate_reads(taps=True) returns them."""
+    require_gpu()
+    lib = load()
+    Cn = len(contigs)
+    arr, keep = _sr_contig_array(contigs)
+    res = C.POINTER(SrResult)()
+    tp = C.POINTER(_SrTaps)()
+    _check(_sr_run_taps_fn(lib)(C.cast(arr, C.c_void_p), C.c_int32(Cn), C.c_int32(int(window_size)), C.c_float(error_rate), C.c_int32(1 if low_memory else 0),
+                                C.c_uint32(seed), C.c_int32(n_threads), C.c_int32(0), C.byref(res), C.byref(tp)))
+    out = _sr_result_to_dict(res, Cn)
+    out["window_size"] = int(window_size)
+    lib.hs_sr_result_destroy(res)
+    out["taps"] = _chain_taps_to_dict(tp.contents)
     lib.hs_sr_taps_destroy(tp)
     return out
 
@@ -784,14 +832,7 @@ def separate_reads(cv_out: Dict, flat: FlatBatch, error_rate: float, low_memory:
     }
     lib.hs_sr_result_destroy(res)
     if taps:
-        t = tp.contents
-        Wc = int(t.n_windows)
-        a = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, (max(n, 1),))[:n].astype(dt).copy()
-        row0 = a(t.win_row0, Wc + 1, np.int64); rb = a(t.run_begin, Wc + 1, np.int64)
-        n_runs = int(rb[-1]); ro = a(t.run_off, n_runs + 1, np.int64)
-        out["taps"] = {"win_contig": a(t.win_contig, Wc, np.int32), "win_start": a(t.win_start, Wc, np.int32), "win_row0": row0, "mask_ids": a(t.mask_ids, int(row0[-1]), np.int32),
-                       "run_begin": rb, "run_snp": a(t.run_snp, n_runs, np.int32), "run_off": ro, "run_labels": a(t.run_labels, int(ro[-1]), np.int32),
-                       "third": a(t.third, int(row0[-1]), np.int32)}
+        out["taps"] = _chain_taps_to_dict(tp.contents)
         out["contigs"] = per_contig
         lib.hs_sr_taps_destroy(tp)
     return out

@@ -88,6 +88,12 @@ int hs_sr_run_taps(const hs_sr_contig* contigs, int32_t n_contigs, int32_t windo
     t->n_windows = (int32_t)Wc;
     t->win_contig = dup_vec(tp.win_contig); t->win_start = dup_vec(tp.win_start); t->win_row0 = dup_vec(tp.win_row0); t->mask_ids = dup_vec(tp.mask_ids);
     t->run_begin = dup_vec(tp.run_begin); t->run_snp = dup_vec(tp.run_snp); t->run_off = dup_vec(tp.run_off); t->run_labels = dup_vec(tp.run_labels); t->third = dup_vec(tp.third);
+    {
+        const hs::SrChainRoutes& rt = tp.routes;
+        t->all_lanes = rt.all_lanes; t->cap_tail = rt.cap_tail; t->runs_lanes = rt.runs_lanes; t->runs_overflow = rt.runs_overflow; t->runs_rows = rt.runs_rows;
+        t->units_rows = rt.units_rows; t->runs_wave = rt.runs_wave; t->runs_wave_scratch = rt.runs_wave_scratch; t->tail_narrow = rt.tail_narrow;
+        t->tail_lds = rt.tail_lds; t->tail_scratch = rt.tail_scratch;
+    }
     if (tp.graphs) {
         const hs::SrGraphTaps& f = tp.front;
         t->g_n_windows = (int32_t)f.win_contig.size();

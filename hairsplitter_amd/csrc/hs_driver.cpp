@@ -934,12 +934,12 @@ int sr_run(SrDeviceOps& dev, const hs_sr_contig* contigs, int32_t n_contigs, int
     SrChainStats cst;
     {
         const double t0 = now_ms();
-        if (taps) dev.tap_chain(&taps->run_off, &taps->run_labels);
+        if (taps) dev.tap_chain(&taps->run_off, &taps->run_labels, &taps->routes);
         if (!ch.win.empty()) { if (int rc = dev.cw_chain(ch, chain_labels, final_labels, final_ok, &k_ms[1], &cst)) return rc; }
         dev_ms += now_ms() - t0;
     }
     if (taps) {
-        dev.tap_chain(nullptr, nullptr);
+        dev.tap_chain(nullptr, nullptr, nullptr);
         taps->win_row0.assign(1, 0); taps->run_begin.assign(1, 0);
         for (size_t k = 0; k < ch.win.size(); ++k) {
             const WRef& wr = wrefs[(size_t)ch.win[k]];

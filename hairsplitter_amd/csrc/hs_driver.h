@@ -215,6 +215,21 @@ struct SrChainStats {                 // what the clustering chain did (bench.py
 };
 
 struct SrGraphTaps;
+// Test taps: the routes the clustering chain of a call took (sizes of the lists cw_chain builds on the host, and the length of the overflow
+// list its seeding kernel leaves on the device)
+struct SrChainRoutes {
+    int32_t all_lanes = 0;            // 1: every window of the chain had at most 64 reads (the host branch that fills the lists by threads)
+    int64_t runs_lanes = 0;           // per-SNP runs one per lane (windows of at most 64 reads) ...
+    int64_t runs_overflow = 0;        // ... of those, runs with more than 16 labels alive after seeding: one wavefront each
+    int64_t runs_rows = 0;            // runs in row-packed units (65 .. 255 reads) ...
+    int64_t units_rows = 0;           // ... and the units of up to eight they make
+    int64_t runs_wave = 0;            // runs with one wavefront each (more than 255 reads) ...
+    int64_t runs_wave_scratch = 0;    // ... of those, runs whose nodes do not fit LDS: labels in global scratch
+    int64_t tail_narrow = 0;          // windows whose tail keeps its labels in registers (at most 64 reads),
+    int64_t tail_lds = 0;             // in LDS,
+    int64_t tail_scratch = 0;         // in global scratch (more than cap_tail reads)
+    int32_t cap_tail = 0;             // nodes the tail's LDS holds in this call
+};
 struct SrDeviceOps {
     virtual ~SrDeviceOps() {}
     // K5a + K5: bit-planes from the SNP columns, then sim / diff for every contig with n_reads[c] > 0. The columns (the same
@@ -237,8 +252,9 @@ struct SrDeviceOps {
     virtual int cw_chain(const CwChain& chain, std::vector<int32_t>& labels, std::vector<int32_t>& final_labels,
                          std::vector<uint8_t>& final_ok, float k_ms[3], SrChainStats* stats) = 0;
     virtual int cw(CwWave& wave, float* k_ms) = 0;
-    // (test taps: the next cw_chain() also leaves the labels of its per-SNP runs -- run_off / run_labels -- and always fills `labels`)
-    virtual void tap_chain(std::vector<int64_t>* run_off, std::vector<int32_t>* run_labels) { (void)run_off; (void)run_labels; }
+    // (test taps: the next cw_chain() also leaves the labels of its per-SNP runs -- run_off / run_labels --, always fills `labels`, and says in
+    // `routes` which kernel took which run and which window)
+    virtual void tap_chain(std::vector<int64_t>* run_off, std::vector<int32_t>* run_labels, SrChainRoutes* routes) { (void)run_off; (void)run_labels; (void)routes; }
     // (test taps: the next simdiff_columns() fills the matrices with SrGraphTaps::kSentinel before K5 and leaves bit rows and matrices in `t`,
     // the next build_graphs_end() the late-row counter and the wave count; nullptr: off)
     virtual void tap_front(SrGraphTaps* t) { (void)t; }
@@ -304,6 +320,7 @@ struct SrTaps {
     std::vector<int32_t> run_snp;                 // SNP index on its contig of every run
     std::vector<int64_t> run_off;                 // [runs + 1] into run_labels (m labels per run)
     std::vector<int32_t> run_labels, third;       // third: [win_row0.back()] what the third run left
+    SrChainRoutes routes;                         // which kernels the chain went through
     // graphs mode (graphs = true on entry): sr_run stops behind build_graphs_end() / fetch_graphs() -- no Chinese-Whispers chain, no result -- and
     // leaves `front` instead of the fields above
     bool graphs = false;

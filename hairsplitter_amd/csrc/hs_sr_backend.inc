@@ -581,8 +581,8 @@ struct HipSrOps : hs::SrDeviceOps {
         return std::min(cap, (limit_bytes / (ints_per_node * 4)) / 64 * 64);
     }
 
-    std::vector<int64_t>* tap_run_off = nullptr; std::vector<int32_t>* tap_run_labels = nullptr;
-    void tap_chain(std::vector<int64_t>* run_off, std::vector<int32_t>* run_labels) override { tap_run_off = run_off; tap_run_labels = run_labels; }
+    std::vector<int64_t>* tap_run_off = nullptr; std::vector<int32_t>* tap_run_labels = nullptr; hs::SrChainRoutes* tap_routes = nullptr;
+    void tap_chain(std::vector<int64_t>* run_off, std::vector<int32_t>* run_labels, hs::SrChainRoutes* routes) override { tap_run_off = run_off; tap_run_labels = run_labels; tap_routes = routes; }
     int cw_chain(const hs::CwChain& ch, std::vector<int32_t>& labels, std::vector<int32_t>& final_labels, std::vector<uint8_t>& final_ok,
                  float k_ms[3], hs::SrChainStats* stats) override {
         if (int rc = settle_simdiff()) return rc;   // (a batch without graph windows never built graphs)
@@ -640,6 +640,16 @@ struct HipSrOps : hs::SrDeviceOps {
             if (m > cap_big) big_scr_total += 2 * (int64_t)m;
         }
         const int cap_tail = lds_nodes(max_m_chain, 7, 56 * 1024);
+        if (tap_routes) {      // (test taps: the sizes of the lists above)
+            hs::SrChainRoutes& rt = *tap_routes;
+            rt = hs::SrChainRoutes();
+            rt.all_lanes = all_lanes ? 1 : 0; rt.runs_lanes = (int64_t)list_lanes.size(); rt.units_rows = (int64_t)unit_win.size();
+            for (int32_t n : unit_n) rt.runs_rows += n;
+            rt.runs_wave = (int64_t)list_big.size();
+            for (int32_t i : list_big) if (G.win_m[(size_t)inst_win[(size_t)i]] > cap_big) rt.runs_wave_scratch++;
+            rt.cap_tail = cap_tail;
+            for (int k = 0; k < Wc; ++k) { const int m = G.win_m[(size_t)ch.win[(size_t)k]]; if (m <= 64) rt.tail_narrow++; else if (m > cap_tail) rt.tail_scratch++; else rt.tail_lds++; }
+        }
         // two launches of the tail: the windows of at most 64 nodes with LDS for 64 (more wavefronts per CU), then the wider ones
         std::vector<int32_t> tail_list((size_t)Wc);
         int n_tail_small = 0;
@@ -702,11 +712,15 @@ struct HipSrOps : hs::SrDeviceOps {
                                d_sets.as<unsigned long long>(), d_names.as<uint8_t>(), d_slots.as<uint8_t>(), d_alive.as<uint8_t>(), d_slab.as<int32_t>(), d_stat.as<unsigned long long>());
             HS_HIP(hipGetLastError());
             if (int rc = kc.end((int64_t)npad * 209, stream)) return rc;      // + sweeps * (4 nnz + 8 m) per run, counted by the kernel itself (added below)
-            if (std::getenv("HS_TIMING")) {
+            const bool timing = std::getenv("HS_TIMING") != nullptr;
+            if (timing || tap_routes) {
                 int32_t n_ovf = 0;
                 if (int rc = d2h_pinned(&n_ovf, d_ovf_n.p, 4, stream)) return rc;
-                std::fprintf(stderr, "[hs timing] sr: %d per-SNP runs one per lane, %d of them with more than 16 labels alive (-> one wavefront each); %zu runs in units of 8, %zu one wavefront each\n",
-                             n, n_ovf, unit_win.size() * 8, list_big.size());
+                if (tap_routes) tap_routes->runs_overflow = n_ovf;
+                if (timing) {
+                    std::fprintf(stderr, "[hs timing] sr: %d per-SNP runs one per lane, %d of them with more than 16 labels alive (-> one wavefront each); %zu runs in units of 8, %zu one wavefront each\n",
+                                 n, n_ovf, unit_win.size() * 8, list_big.size());
+                }
             }
             // the few runs with more labels alive than slots: one wavefront each, the list and its length are on the device
             if (int rc = kc.begin(HS_K_CW_SEEDED_WIDE, stream)) return rc;

@@ -556,6 +556,13 @@ typedef struct hs_sr_taps {
                                                      the pair (a tile of two 64-row blocks that share no SNP word: nobody reads it) */
     int64_t g_rows_on_host, g_rows_late;          /* rows resolved on the host / of those, fetched behind the row kernels (no room in the staging area) */
     int32_t g_row_waves;                          /* wavefronts per workgroup of k_read_graph_rows (4, or 1 for a window wider than 1792 reads; 0: not launched) */
+    /* mode HS_SR_TAPS_CHAIN: the routes the chain took, from the lists the call builds on the host (and the overflow list's length on the device) */
+    int32_t all_lanes;                            /* 1: every chain window had at most 64 reads (the host branch of its own for that case) */
+    int32_t cap_tail;                             /* nodes the LDS of k_window_tail holds in this call (at most 2048) */
+    int64_t runs_lanes, runs_overflow;            /* per-SNP runs one per lane (k_cw_seeded_lanes); of those, runs with more than 16 labels alive: one wavefront each */
+    int64_t runs_rows, units_rows;                /* runs of k_cw_seeded_rows (windows of 65 .. 255 reads) / its units of up to eight runs */
+    int64_t runs_wave, runs_wave_scratch;         /* runs of k_cw_seeded_wave (more than 255 reads) / of those, with their nodes in global scratch */
+    int64_t tail_narrow, tail_lds, tail_scratch;  /* windows of k_window_tail with labels in registers (at most 64 reads) / LDS / global scratch (more than cap_tail) */
 } hs_sr_taps;
 #define HS_SR_TAPS_CHAIN 0
 #define HS_SR_TAPS_GRAPHS 1                       /* stops behind the read graphs: no Chinese-Whispers chain, *out stays NULL */

@@ -141,7 +141,11 @@ struct Window { int start, end; std::vector<int> labels; };
 // test taps (tests only): when g_window_taps is set, separate_reads_on_contig leaves, for every window that builds a read graph, its reads,
 // the labels of every per-SNP Chinese-Whispers run (separate_reads.cpp:1674-1705) and of the run behind finalize_clustering's small-cluster
 // filter (:924-970), both restricted to the window's reads
-struct WindowTap { int start = 0; std::vector<int> mask_ids; std::vector<int> run_snp; std::vector<std::vector<int>> runs; std::vector<int> third; };
+struct WindowTap { int start = 0; std::vector<int> mask_ids; std::vector<int> run_snp; std::vector<std::vector<int>> runs; std::vector<int> third;
+                   // finalize_clustering's table sizes: distinct labels behind the first-seen renumbering of the third run; clusters entering
+                   // merge_wrongly_split_haplotypes, the size of its `links` map, links applied, links refused by an incompatibility count > 1
+                   int kc = 0, g = 0, n_links = 0, n_merged = 0, n_vetoed = 0;
+                   std::vector<int> split; };      // the labels merge_wrongly_split_haplotypes is given (behind merge_close_clusters), of the window's reads
 extern thread_local std::vector<WindowTap>* g_window_taps;
 
 // dense restatement of the two Eigen products (:374-433)

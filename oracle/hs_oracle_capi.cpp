@@ -284,11 +284,13 @@ extern "C" {
 struct hso_sr_taps {
     int32_t n_tap; int32_t* tap_start; int64_t* tap_row0; int32_t* mask_ids; int64_t* run_begin; int32_t* run_snp; int32_t* run_labels /* runs x m, window after window */; int32_t* third;
     int32_t n_windows; int32_t* win_start; int32_t* win_end; int32_t* win_labels /* n_windows x N */;
+    int32_t* fin /* n_tap x 5: kc, g, n_links, n_merged, n_vetoed (hs_oracle.h: WindowTap) */;
+    int32_t* split /* as third: the labels entering merge_wrongly_split_haplotypes */;
 };
 void hso_sr_taps_free(hso_sr_taps* t) {
     if (!t) return;
     std::free(t->tap_start); std::free(t->tap_row0); std::free(t->mask_ids); std::free(t->run_begin); std::free(t->run_snp); std::free(t->run_labels); std::free(t->third);
-    std::free(t->win_start); std::free(t->win_end); std::free(t->win_labels); std::free(t);
+    std::free(t->win_start); std::free(t->win_end); std::free(t->win_labels); std::free(t->fin); std::free(t->split); std::free(t);
 }
 int hso_sr_contig_taps(int32_t n_reads, int64_t length, const int32_t* read_start, const int32_t* read_end, int32_t n_snps, const int32_t* snp_pos,
                        const uint8_t* snp_ref, const uint8_t* snp_alt, const int64_t* col_off, const int32_t* col_idx, const uint8_t* col_code,
@@ -308,19 +310,23 @@ int hso_sr_contig_taps(int32_t n_reads, int64_t length, const int32_t* read_star
     std::vector<hso::Window> ws = hso::separate_reads_on_contig(c, window, error_rate, low_memory != 0, low_memory != 0, 0, seed);
     hso::g_window_taps = nullptr;
     hso_sr_taps* t = (hso_sr_taps*)std::calloc(1, sizeof(hso_sr_taps));
-    std::vector<int32_t> start, mask, rsnp, rlab, third, wst, wen, wlab; std::vector<int64_t> row0(1, 0), rb(1, 0);
+    std::vector<int32_t> start, mask, rsnp, rlab, third, wst, wen, wlab, fin, split; std::vector<int64_t> row0(1, 0), rb(1, 0);
     for (const hso::WindowTap& w : taps) {
         start.push_back(w.start);
+        for (int v : {w.kc, w.g, w.n_links, w.n_merged, w.n_vetoed}) fin.push_back(v);
         mask.insert(mask.end(), w.mask_ids.begin(), w.mask_ids.end()); row0.push_back((int64_t)mask.size());
         for (size_t k = 0; k < w.runs.size(); ++k) { rsnp.push_back(w.run_snp[k]); rlab.insert(rlab.end(), w.runs[k].begin(), w.runs[k].end()); }
         rb.push_back((int64_t)rsnp.size());
         if (w.third.size() == w.mask_ids.size()) third.insert(third.end(), w.third.begin(), w.third.end());
         else third.insert(third.end(), w.mask_ids.size(), -9);      // (a window without runs never gets there)
+        if (w.split.size() == w.mask_ids.size()) split.insert(split.end(), w.split.begin(), w.split.end());
+        else split.insert(split.end(), w.mask_ids.size(), -9);
     }
     for (const hso::Window& w : ws) { wst.push_back(w.start); wen.push_back(w.end); wlab.insert(wlab.end(), w.labels.begin(), w.labels.end()); }
     t->n_tap = (int32_t)taps.size(); t->tap_start = hso_dup(start); t->tap_row0 = hso_dup(row0); t->mask_ids = hso_dup(mask); t->run_begin = hso_dup(rb);
     t->run_snp = hso_dup(rsnp); t->run_labels = hso_dup(rlab); t->third = hso_dup(third);
     t->n_windows = (int32_t)ws.size(); t->win_start = hso_dup(wst); t->win_end = hso_dup(wen); t->win_labels = hso_dup(wlab);
+    t->fin = hso_dup(fin); t->split = hso_dup(split);
     *out = t;
     return 0;
 }

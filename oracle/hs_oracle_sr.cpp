@@ -299,6 +299,8 @@ void merge_close_clusters(const std::vector<std::vector<int>>& nl, const std::ve
     }
 }
 
+thread_local std::vector<WindowTap>* g_window_taps = nullptr;
+
 // separate_reads.cpp:1007-1327
 std::vector<int> merge_wrongly_split_haplotypes(const std::vector<int>& clusteredReads, const std::vector<Column>& snps,
                                                 const std::vector<std::vector<int>>& nl,
@@ -314,6 +316,8 @@ std::vector<int> merge_wrongly_split_haplotypes(const std::vector<int>& clustere
         }
     }
     const size_t G = listOfGroups.size();
+    WindowTap* tap = g_window_taps && !g_window_taps->empty() ? &g_window_taps->back() : nullptr;
+    if (tap) tap->g = (int)G;
     std::vector<std::vector<int>> incompat(G, std::vector<int>(G, 0));
     std::vector<std::vector<int>> pos_last(G, std::vector<int>(G, -10));
     if (G <= 1) {
@@ -382,6 +386,7 @@ std::vector<int> merge_wrongly_split_haplotypes(const std::vector<int>& clustere
     std::sort(sorted_links.begin(), sorted_links.end(),
               [](const std::pair<std::pair<int, int>, double>& a, const std::pair<std::pair<int, int>, double>& b) { return a.second > b.second; });
 
+    if (tap) tap->n_links = (int)links.size();
     std::map<int, int> o2n;
     for (int g : listOfGroups) o2n[g] = g;
     o2n[-1] = -1; o2n[-2] = -2;
@@ -395,6 +400,7 @@ std::vector<int> merge_wrongly_split_haplotypes(const std::vector<int>& clustere
             for (int g2 : listOfGroups)
                 if (o2n[g2] == o2n[c2] && incompat[indexOfGroups[g1]][indexOfGroups[g2]] > 1) bad = true;
         }
+        if (tap) { if (bad) tap->n_vetoed++; else tap->n_merged++; }
         if (!bad) {
             for (int g2 : listOfGroups) if (o2n[g2] == o2n[c2]) o2n[g2] = o2n[c1];
         }
@@ -407,8 +413,6 @@ std::vector<int> merge_wrongly_split_haplotypes(const std::vector<int>& clustere
     for (size_t r = 0; r < clusteredReads.size(); r++) out[r] = o2n[clusteredReads[r]];
     return out;
 }
-
-thread_local std::vector<WindowTap>* g_window_taps = nullptr;
 
 // separate_reads.cpp:840-885
 static std::vector<int> merge_clusterings(const std::vector<std::vector<int>>& localClusters,
@@ -466,7 +470,9 @@ static void finalize_clustering(const std::vector<Column>& snps, const std::vect
     int index_h = 0;
     for (int h : haplotypes) if (toIndex.find(h) == toIndex.end()) { toIndex[h] = index_h; index_h++; }
     for (size_t r = 0; r < haplotypes.size(); r++) haplotypes[r] = toIndex[haplotypes[r]];
+    if (g_window_taps && !g_window_taps->empty()) g_window_taps->back().kc = index_h;
     merge_close_clusters(nl, adj, low_memory, haplotypes, mask, seed);
+    if (g_window_taps && !g_window_taps->empty()) { WindowTap& t = g_window_taps->back(); for (int r : t.mask_ids) t.split.push_back(haplotypes[(size_t)r]); }
     haplotypes = merge_wrongly_split_haplotypes(haplotypes, snps, nl, adj, low_memory, posstart, posend);
 }
 

@@ -4,7 +4,7 @@ launches them in. Used by tests/test_cpu_graph_cases.py (which proves, with the 
 tests/test_gpu_graph_front.py.
 
 A case is {"contigs": [contig dict ...], "window": w, "error_rate": e, "low_memory": bool}. A contig dict holds what hairsplitter_amd.api takes (length,
-read_start, read_end, snp_pos, snp_ref, snp_alt, col_off, col_idx, col_code) plus "mask_sizes": the number of reads of each of its graph windows, as designed.
+read_start, read_end, snp_pos, snp_ref, snp_alt, col_off, col_idx, col_code) plus "mask_sizes": the number of reads of each of its graph windows, as designed, and "hap": the haplotype every read was drawn from.
 
 Every SNP column lists every read that covers the position (ascending read index), except where a case says otherwise. A read carries the reference or the
 alternative allele of its haplotype, flipped with probability `noise`, or -- with probability `third` -- a third allele that counts for neither plane.
@@ -19,12 +19,13 @@ LENGTH = 2150
 BASES = np.frombuffer(b"ACGT", np.uint8)
 
 
-def _columns(rng, read_start, read_end, snp_pos, hap, n_hap=3, noise=0.02, third=0.03):
-    """-> snp_ref, snp_alt, col_off, col_idx, col_code (and the third allele of every SNP) for reads with haplotypes `hap`"""
+def _columns(rng, read_start, read_end, snp_pos, hap, n_hap=3, noise=0.02, third=0.03, pattern=None):
+    """-> snp_ref, snp_alt, col_off, col_idx, col_code (and the third allele of every SNP) for reads with haplotypes `hap`
+    (pattern: a function (rng, S, n_hap) -> the allele of every haplotype at every SNP, instead of independent draws)"""
     N, S = len(read_start), len(snp_pos)
     pick = np.argsort(rng.random((S, 4)), axis=1)[:, :3]      # three different bases per SNP
     snp_ref, snp_alt, snp_third = BASES[pick[:, 0]], BASES[pick[:, 1]], BASES[pick[:, 2]]
-    pattern = rng.integers(0, 2, (S, n_hap))      # allele of every haplotype at every SNP (1 = alternative)
+    pattern = rng.integers(0, 2, (S, n_hap)) if pattern is None else pattern(rng, S, n_hap)      # allele of every haplotype at every SNP (1 = alternative)
     off, idx, code = [0], [], []
     for s in range(S):
         r = np.nonzero((read_start <= snp_pos[s]) & (read_end >= snp_pos[s]))[0].astype(np.int32)
@@ -39,10 +40,12 @@ def _columns(rng, read_start, read_end, snp_pos, hap, n_hap=3, noise=0.02, third
 def _contig(rng, length, read_start, read_end, snp_pos, mask_sizes, **kw):
     read_start = np.asarray(read_start, np.int32); read_end = np.asarray(read_end, np.int32); snp_pos = np.asarray(snp_pos, np.int32)
     n_hap = kw.get("n_hap", 3)
-    hap = rng.integers(0, n_hap, len(read_start))
+    hap = kw.pop("hap", None)      # (given: the haplotype of every read; else drawn)
+    if hap is None:
+        hap = rng.integers(0, n_hap, len(read_start))
     ref, alt, off, idx, code, third = _columns(rng, read_start, read_end, snp_pos, hap, **kw)
     return {"length": int(length), "read_start": read_start, "read_end": read_end, "snp_pos": snp_pos, "snp_ref": ref, "snp_alt": alt, "col_off": off,
-            "col_idx": idx, "col_code": code, "snp_third": third, "mask_sizes": list(mask_sizes)}
+            "col_idx": idx, "col_code": code, "snp_third": third, "mask_sizes": list(mask_sizes), "hap": np.asarray(hap)}
 
 
 def clump_positions(S):
@@ -53,20 +56,33 @@ def clump_positions(S):
     return np.concatenate((a, b)).astype(np.int32)
 
 
-def one_window_contig(rng, N, m, S, **kw):
+def one_window_contig(rng, N, m, S, snp_pos=None, balanced=False, full_ids=None, length=None, **kw):
     """N reads, S SNPs, one window whose mask holds m of the reads: those span the contig, the others end at 1200 or start at 1201 by turns (they are in
-    the columns of one clump only). S == 1: first and last SNP are the same column, the mask is everything that covers it."""
+    the columns of one clump only). S == 1: first and last SNP are the same column, the mask is everything that covers it.
+    snp_pos: the S positions instead of the two clumps (the first at 1200 or before, the last behind 1200, for the mask to be the m reads).
+    balanced: the m reads are dealt to the n_hap haplotypes in turn (equal sizes up to one), the others drawn.
+    full_ids: the m reads themselves (the highest index among them) instead of a draw. length: of the contig, where it is longer than the reads reach
+    (windows behind the first hold no SNP; the coverage falls)."""
     full = np.zeros(N, bool)
-    if m > 0:
+    if full_ids is not None:
+        assert len(full_ids) == m and max(full_ids) == N - 1
+        full[np.asarray(full_ids)] = True
+    elif m > 0:
         chosen = rng.permutation(N - 1)[:m - 1] if N > 1 else np.zeros(0, np.int64)
         full[chosen] = True; full[N - 1] = True      # (the read with the highest index is in the last column: see the reference's mask loop)
     start = rng.integers(0, 40, N).astype(np.int32); end = np.full(N, LENGTH - 1, np.int32)      # (start order != read order: the matrices' rows are permuted)
     is_left = (N - 1 - np.arange(N)) % 2 == 1      # (by turns, and the highest index on the right: in the last column)
     end[~full & is_left] = 1200
     start[~full & ~is_left] = 1201
-    if S == 1:
+    if S == 1 and snp_pos is None:
         m = int(np.sum(start <= 500))
-    return _contig(rng, LENGTH, start, end, clump_positions(S), [m] if S > 0 else [], **kw)
+    if balanced:
+        n_hap = kw.get("n_hap", 3)
+        hap = rng.integers(0, n_hap, N)
+        who = np.flatnonzero(full)
+        hap[who[rng.permutation(len(who))]] = np.arange(len(who)) % n_hap
+        kw["hap"] = hap
+    return _contig(rng, LENGTH if length is None else length, start, end, clump_positions(S) if snp_pos is None else snp_pos, [m] if S > 0 else [], **kw)
 
 
 # ---- the cases ----

@@ -57,13 +57,15 @@ def call_variants_flags(flat, pile, c, mean_error, automatic_snp_threshold=0.33)
 class _SrTapsO(C.Structure):
     _fields_ = [("n_tap", C.c_int32), ("tap_start", C.POINTER(C.c_int32)), ("tap_row0", C.POINTER(C.c_int64)), ("mask_ids", C.POINTER(C.c_int32)),
                 ("run_begin", C.POINTER(C.c_int64)), ("run_snp", C.POINTER(C.c_int32)), ("run_labels", C.POINTER(C.c_int32)), ("third", C.POINTER(C.c_int32)),
-                ("n_windows", C.c_int32), ("win_start", C.POINTER(C.c_int32)), ("win_end", C.POINTER(C.c_int32)), ("win_labels", C.POINTER(C.c_int32))]
+                ("n_windows", C.c_int32), ("win_start", C.POINTER(C.c_int32)), ("win_end", C.POINTER(C.c_int32)), ("win_labels", C.POINTER(C.c_int32)), ("fin", C.POINTER(C.c_int32)),
+                ("split", C.POINTER(C.c_int32))]
 
 
 def sr_contig_taps(ctg, window, error_rate, low_memory=False, seed=12345):
     """One contig (dict of numpy arrays as hairsplitter_amd.api.separate_reads(taps=True) leaves them in out["contigs"]) through the oracle's
     separate_reads_on_contig with its test taps on: per graph window its start, reads, per-SNP run labels (read ids), the labels of the run behind the
-    small-cluster filter; and the finished labels of every window."""
+    small-cluster filter ("third"), the labels its merge_wrongly_split_haplotypes is given ("split"), the table sizes of its finalize_clustering (kc, g, n_links, n_merged, n_vetoed: one array each, see oracle/hs_oracle.h WindowTap);
+    and the finished labels of every window."""
     L = lib()
     L.hso_sr_contig_taps.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int32, C.c_float, C.c_int32, C.c_uint32, C.POINTER(C.POINTER(_SrTapsO))]
@@ -84,6 +86,10 @@ def sr_contig_taps(ctg, window, error_rate, low_memory=False, seed=12345):
     out = {"tap_start": a(t.tap_start, nt, np.int32), "tap_row0": row0, "mask_ids": a(t.mask_ids, int(row0[-1]), np.int32), "run_begin": rb,
            "run_snp": a(t.run_snp, int(rb[-1]), np.int32), "run_labels": a(t.run_labels, n_lab, np.int32), "third": a(t.third, int(row0[-1]), np.int32),
            "win_start": a(t.win_start, nw, np.int32), "win_end": a(t.win_end, nw, np.int32), "win_labels": a(t.win_labels, nw * N, np.int32).reshape(nw, N) if nw else np.zeros((0, N), np.int32)}
+    out["split"] = a(t.split, int(row0[-1]), np.int32)
+    fin = a(t.fin, 5 * nt, np.int32).reshape(nt, 5)
+    for k, name in enumerate(("kc", "g", "n_links", "n_merged", "n_vetoed")):
+        out[name] = fin[:, k].copy()
     L.hso_sr_taps_free(tp)
     return out
 
