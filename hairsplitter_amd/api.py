@@ -21,7 +21,7 @@ if os.environ.get("HS_LIB_AB"):      # (tools/gpu_ab_lib.sh: another build of th
 SYMBOLS = [
     "hs_cv_batch_set_ploidy", "hs_version", "hs_last_error", "hs_device_count", "hs_warmup", "hs_set_device", "hs_device_synchronize", "hs_malloc", "hs_free",
     "hs_memcpy_h2d", "hs_memcpy_d2h", "hs_memset", "hs_event_create", "hs_event_destroy", "hs_event_record",
-    "hs_event_elapsed_ms", "hs_pileup", "hs_pileup_plan", "hs_free_host", "hs_tile_plan", "hs_column_stats_tiled", "hs_cv_column_pass_taps", "hs_cv_taps_destroy", "hs_sr_run_taps", "hs_sr_taps_destroy", "hs_exclusive_scan_i32", "hs_gaf_from_files", "hs_gaf_from_labels", "hs_gro_to_gaf_main", "hs_column_partition_test", "hs_column_partition_last_counts", "hs_partition_pair_distance", "hs_snp_planes", "hs_simdiff", "hs_read_graphs",
+    "hs_event_elapsed_ms", "hs_pileup", "hs_pileup_plan", "hs_free_host", "hs_tile_plan", "hs_column_stats_tiled", "hs_cv_column_pass_taps", "hs_cv_taps_destroy", "hs_sr_run_taps", "hs_sr_taps_destroy", "hs_exclusive_scan_i32", "hs_gaf_from_files", "hs_gaf_from_labels", "hs_gro_to_gaf_main", "hs_column_partition_test", "hs_column_partition_last_counts", "hs_loop_a_test", "hs_loop_a_result_destroy", "hs_partition_pair_distance", "hs_snp_planes", "hs_simdiff", "hs_read_graphs",
     "hs_edit_distance", "hs_cv_batch_create", "hs_cv_batch_destroy", "hs_cv_batch_aligned_bp", "hs_cv_run",
     "hs_cv_result_destroy", "hs_cv_select", "hs_cv_run_range", "hs_cv_selection_destroy", "hs_sr_run", "hs_sr_run_cv", "hs_sr_run_cv_range", "hs_pipeline_create", "hs_pipeline_select", "hs_pipeline_run", "hs_pipeline_destroy", "hs_pipeline_thread_devices", "hs_cv_batch_device", "hs_sr_result_destroy", "hs_sr_window_size", "hs_call_variants_main", "hs_call_variants_epilogue",
     "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_edlib_align", "hs_edlib_align_bytes", "hs_alignment_to_cigar", "hs_reattach_ends", "hs_trim_polished", "hs_reattach_ends_bytes", "hs_trim_polished_bytes", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
@@ -1014,6 +1014,60 @@ def column_partition_last_counts():
     out = (C.c_int32 * 3)()
     load().hs_column_partition_last_counts(out)
     return {"to_grouped": int(out[0]), "whole_columns_to_exact": int(out[1]), "pairs_to_exact": int(out[2])}
+
+
+class LoopAResult(C.Structure):
+    _fields_ = [("n_contigs", C.c_int32), ("on_device", C.POINTER(C.c_int32)), ("failed", C.POINTER(C.c_int32)), ("part_base", C.POINTER(C.c_int64)),
+                ("rec", C.POINTER(C.c_int32)), ("state", C.POINTER(C.c_int8)), ("more", C.POINTER(C.c_int32)), ("less", C.POINTER(C.c_int32))]
+
+
+LOOP_A_REC = ("left", "right", "n_occ", "n_corr", "lo", "hi", "reach", "w0", "w1")
+
+
+def loop_a_test(contigs, form, cand_bound, pool_div=6, light=False):
+    """Loop A of stage 3 on prescribed candidate columns (hs_loop_a_test). contigs: dicts of read_start, read_end [N], pos, k0 [S], off [S + 1], idx, code
+    (CSR; read indices ascending inside a column). form: "host" (cv_build_cand_bits -> cv_phase_a_host) or "device" (the k_loop_a chain of stage 3 ->
+    cv_phase_a_import; needs a GPU). Returns {"on_device": [C], "failed": [C], "contigs": [per contig {"rec": [P, 9] (LOOP_A_REC), "state", "more", "less":
+    [P, N]}]}; a contig of the device form that was not planned for the device or was handed back has P = 0."""
+    assert form in ("host", "device")
+    if form == "device":
+        require_gpu()
+    lib = load()
+    n = [len(c["read_start"]) for c in contigs]
+    read_off = _np(np.concatenate([[0], np.cumsum(n)]), np.int32)
+    col_base = _np(np.concatenate([[0], np.cumsum([len(c["pos"]) for c in contigs])]), np.int64)
+    cat = lambda key, dt: _np(np.concatenate([np.asarray(c[key]) for c in contigs] + [np.zeros(1)]), dt)
+    rs, re_, pos, k0, idx, code = cat("read_start", np.int32), cat("read_end", np.int32), cat("pos", np.int32), cat("k0", np.uint8), cat("idx", np.int32), cat("code", np.uint8)
+    off = [np.zeros(1, np.int64)]
+    e = 0
+    for c in contigs:
+        o = np.asarray(c["off"], np.int64)
+        assert o[0] == 0 and o[-1] == len(c["idx"]) == len(c["code"])
+        off.append(o[1:] + e); e += int(o[-1])
+    off = _np(np.concatenate(off), np.int64)
+    lib.hs_loop_a_test.argtypes = [C.c_int32] + [C.c_void_p] * 9 + [C.c_int32] * 4 + [C.POINTER(C.POINTER(LoopAResult)), C.c_void_p]
+    lib.hs_loop_a_result_destroy.argtypes = [C.POINTER(LoopAResult)]; lib.hs_loop_a_result_destroy.restype = None
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)
+    res = C.POINTER(LoopAResult)()
+    _check(lib.hs_loop_a_test(C.c_int32(len(contigs)), hp(read_off), hp(rs), hp(re_), hp(col_base), hp(pos), hp(k0), hp(off), hp(idx), hp(code),
+                              C.c_int32(0 if form == "host" else 1), C.c_int32(int(cand_bound)), C.c_int32(int(pool_div)), C.c_int32(1 if light else 0), C.byref(res), C.c_void_p(0)))
+    r = res.contents
+    Cn = len(contigs)
+    a = lambda p, m, dt: np.ctypeslib.as_array(p, (max(m, 1),))[:m].astype(dt).copy()
+    base = a(r.part_base, Cn + 1, np.int64)
+    out = {"on_device": a(r.on_device, Cn, np.int32), "failed": a(r.failed, Cn, np.int32), "contigs": []}
+    P = int(base[-1])
+    rec = a(r.rec, 9 * P, np.int32).reshape(P, 9)
+    D = int(sum(int(base[c + 1] - base[c]) * n[c] for c in range(Cn)))
+    state, more, less = a(r.state, D, np.int8), a(r.more, D, np.int32), a(r.less, D, np.int32)
+    d = 0
+    for c in range(Cn):
+        p = int(base[c + 1] - base[c])
+        sl = slice(d, d + p * n[c])
+        out["contigs"].append({"rec": rec[base[c]:base[c + 1]], "state": state[sl].reshape(p, n[c]), "more": more[sl].reshape(p, n[c]), "less": less[sl].reshape(p, n[c])})
+        d += p * n[c]
+    lib.hs_loop_a_result_destroy(res)
+    return out
 
 
 def partition_pair_distance(state, more, less, part_off, part_n, pair_a, pair_b, threshold_p=2):

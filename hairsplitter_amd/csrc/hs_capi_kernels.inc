@@ -473,6 +473,313 @@ int hs_column_partition_test(const int64_t* d_col_off, const int32_t* d_col_idx,
 }
 void hs_column_partition_last_counts(int32_t out[3]) { if (out) { out[0] = g_k4_last_counts[0]; out[1] = g_k4_last_counts[1]; out[2] = g_k4_last_counts[2]; } }
 
+}  // extern "C"
+
+// What loop A on the device (k_loop_a) needs of the reads of every contig: their rank by start position (ties by index: the bit order of the
+// partition bit sets, as hs::cv_rank_reads of the host glue), the inverse, the end of their alignment in rank order (the kernels index
+// everything per read by rank), and per READ {its rank, the end of its alignment}. rec_pos / rec_end: per record of the batch.
+static void loop_a_rank_reads(const int32_t* contig_rec_off, int n_contigs, const int32_t* rec_pos, const int32_t* rec_end, std::vector<int32_t>& rank_of,
+                              std::vector<int32_t>& orig_of, std::vector<int32_t>& read_end, std::vector<int32_t>& rank_end) {
+    const size_t n_rec = n_contigs > 0 ? (size_t)contig_rec_off[n_contigs] : 0;
+    rank_of.assign(n_rec, 0); orig_of.assign(n_rec, 0); read_end.assign(n_rec, 0); rank_end.assign(n_rec * 2, 0);
+    hs::hs_parallel_for(n_contigs, host_threads(), [&](int c) {
+        const int r0 = contig_rec_off[c], n = contig_rec_off[c + 1] - r0;
+        std::vector<int32_t> order((size_t)n);
+        for (int r = 0; r < n; ++r) order[(size_t)r] = r;
+        std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return rec_pos[r0 + x] != rec_pos[r0 + y] ? rec_pos[r0 + x] < rec_pos[r0 + y] : x < y; });
+        for (int k = 0; k < n; ++k) { rank_of[(size_t)(r0 + order[(size_t)k])] = k; orig_of[(size_t)(r0 + k)] = order[(size_t)k]; }
+        for (int k = 0; k < n; ++k) read_end[(size_t)(r0 + k)] = rec_end[r0 + order[(size_t)k]];
+        for (int r = r0; r < r0 + n; ++r) { rank_end[(size_t)r * 2] = rank_of[(size_t)r]; rank_end[(size_t)r * 2 + 1] = rec_end[r]; }
+    });
+}
+
+// Loop A on the device (hs_kernels_loopa.hip): the plan (which contigs, how large their partition pools), the launch sequence
+// k_loop_a_offsets -> k_loop_a_prepare -> k_loop_a -> k_loop_a_scan -> k_loop_a_pack and the collection of what they leave. HipCvOps
+// queues it on the candidates of its contig range; the direct test entry (hs_loop_a_test) on columns it was handed: the same calls.
+struct LoopAIn {      // what the kernels read, all on the device
+    const hsdev::hs_colrec_dev* rec = nullptr;      // the candidates' records (contig = index in the batch)
+    const int64_t* off = nullptr;                   // their places in idx / code
+    const int32_t* idx = nullptr; const uint8_t* code = nullptr;
+    const int32_t* len = nullptr;                   // NULL: lengths from consecutive offsets
+    const hsdev::ColumnsHeader* header = nullptr;   // n_flagged = the number of candidates
+    const int32_t* ctg_n = nullptr;                 // [C] candidates of every contig of the range
+    const int32_t* contig_rec_off = nullptr;        // the batch's
+    const int2* rank_end = nullptr;                 // per read: {rank, alignment end}
+    const int32_t* orig_of = nullptr;               // per rank: read
+    int c0 = 0;                                     // first contig of the range
+};
+struct LoopADevice {
+    struct LoopAPlan {
+        std::vector<uint8_t> on_dev; std::vector<int32_t> dev_list; std::vector<int64_t> cap_off, bits_off, cnt_off;
+        int w_max = 1, n_dev = 0;
+    } la_plan;
+    DBuf d_la_on, d_la_list, d_la_cap, d_la_bo, d_la_cno, d_la_candoff, d_la_parts, d_la_bits, d_la_cnt, d_la_meta, d_la_hdr, d_la_words, d_la_out_rec, d_la_out_bits, d_la_out_cnt, d_la_diag;
+    UploadPack la_pack;
+    HBuf h_la;
+    bool la_launched = false;
+    LoopAIn la_in;          // (of the last la_queue: a repack reads contig_rec_off and c0 again)
+    static int la_grow(HBuf& h, size_t need) { if (h.cap >= need && h.p) return HS_OK; return h.alloc(need + need / 4); }
+    static int la_grow(DBuf& d, size_t need) { if (d.cap >= need && d.p && !d.view) { d.bytes = need; return HS_OK; } return d.alloc(need + need / 4); }
+    // the meta block the kernels leave and the host reads: [totals: partitions, span words][n_parts C][n_span C][failed C][part_base C + 1][span_base C + 1]
+    struct LaLayout { size_t np, ns, nf, pb, sb, meta_bytes, rec, bits, cnt, total; int64_t cap_parts, cap_span; } lal{};
+    void la_layout(int C, int64_t cap_parts, int64_t cap_span) {
+        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        lal.np = 16; lal.ns = lal.np + (size_t)C * 4; lal.nf = lal.ns + (size_t)C * 4; lal.pb = (lal.nf + (size_t)C * 4 + 7) & ~(size_t)7; lal.sb = lal.pb + ((size_t)C + 1) * 8;
+        lal.meta_bytes = up(lal.sb + ((size_t)C + 1) * 8);
+        lal.rec = lal.meta_bytes; lal.bits = lal.rec + up((size_t)cap_parts * sizeof(hsdev::LoopAPartition)); lal.cnt = lal.bits + up((size_t)cap_span * 24); lal.total = lal.cnt + up((size_t)cap_span * 256);
+        lal.cap_parts = cap_parts; lal.cap_span = cap_span;
+    }
+    // the contigs of the range the device walks: those with 1 .. kmax candidates and at most 2048 reads that the host does not claim
+    // (force_host, optional); the pool of each holds min(k + 8, k / pool_div + 48) partitions
+    int la_make_plan(const int32_t* counts, const int32_t* n_reads, int C, int kmax, int pool_div, const uint8_t* force_host, hipStream_t stream) {
+        LoopAPlan& pl = la_plan;
+        pl = LoopAPlan();
+        pl.on_dev.assign((size_t)C, 0); pl.cap_off.assign((size_t)C + 1, 0); pl.bits_off.assign((size_t)C + 1, 0); pl.cnt_off.assign((size_t)C + 1, 0);
+        std::vector<std::pair<int64_t, int>> weight;
+        for (int c = 0; c < C; ++c) {
+            const int64_t k = counts[c];
+            const int N = n_reads[c];
+            const int W = (N + 63) >> 6;
+            const bool dev = k > 0 && k <= kmax && W <= HS_LA_MAXW && !(force_host && force_host[c]);
+            const int64_t cap = dev ? std::min<int64_t>(k + 8, k / pool_div + 48) : 0;
+            pl.cap_off[(size_t)c + 1] = pl.cap_off[(size_t)c] + cap;
+            pl.bits_off[(size_t)c + 1] = pl.bits_off[(size_t)c] + cap * 3 * W;
+            pl.cnt_off[(size_t)c + 1] = pl.cnt_off[(size_t)c] + cap * W * 64;
+            if (dev) { pl.on_dev[(size_t)c] = 1; pl.w_max = std::max(pl.w_max, W); weight.push_back(std::make_pair(-k, c)); }
+        }
+        std::sort(weight.begin(), weight.end());      // the heaviest contig first: it is what the launch waits for
+        for (auto& w : weight) pl.dev_list.push_back(w.second);
+        pl.n_dev = (int)pl.dev_list.size();
+        if (pl.n_dev == 0) return HS_OK;
+        la_pack.add(pl.on_dev, d_la_on); la_pack.add(pl.dev_list, d_la_list); la_pack.add(pl.cap_off, d_la_cap); la_pack.add(pl.bits_off, d_la_bo); la_pack.add(pl.cnt_off, d_la_cno);
+        return la_pack.commit(stream);
+    }
+    int la_pack_launch(KernelClock& kc, hipStream_t stream) {      // the partitions packed into the form the host imports, and on their way with the meta block
+        const char* meta = (const char*)d_la_meta.p;
+        hipLaunchKernelGGL(hsdev::k_loop_a_pack, dim3((unsigned)la_plan.n_dev), dim3(256), 0, stream, d_la_list.as<int32_t>(), la_plan.n_dev, (const int32_t*)(meta + lal.np), la_in.c0,
+                           la_in.contig_rec_off, d_la_cap.as<int64_t>(), d_la_bo.as<int64_t>(), d_la_parts.as<hsdev::LoopAPartition>(), d_la_bits.as<unsigned long long>(),
+                           d_la_cnt.as<int32_t>(), (const int64_t*)(meta + lal.pb), (const int64_t*)(meta + lal.sb), (long long)lal.cap_parts, (long long)lal.cap_span,
+                           d_la_out_rec.as<hsdev::LoopAPartition>(), d_la_out_bits.as<unsigned long long>(), d_la_out_cnt.as<int32_t>());
+        HS_HIP(hipGetLastError());
+        Shipment sh;
+        sh.add(h_la.p, d_la_meta.p, lal.meta_bytes);
+        sh.add_counted((char*)h_la.p + lal.rec, d_la_out_rec.p, (const long long*)meta, sizeof(hsdev::LoopAPartition), lal.cap_parts);
+        sh.add_counted((char*)h_la.p + lal.bits, d_la_out_bits.p, (const long long*)meta + 1, 24, lal.cap_span);
+        sh.add_counted((char*)h_la.p + lal.cnt, d_la_out_cnt.p, (const long long*)meta + 1, 256, lal.cap_span);
+        if (int rc = kc.begin(HS_K_SHIP, stream)) return rc;
+        if (int rc = sh.launch(stream)) return rc;
+        return kc.end(0, stream);
+    }
+    // cap_cand: candidates the arrays of `in` hold at most; span_hint: span words to make room for (0: none known); traffic_cand: the
+    // candidates the kernel clock is told of
+    int la_queue(const LoopAIn& in, int C, int64_t cap_cand, int64_t span_hint, int64_t traffic_cand, KernelClock& kc, hipStream_t stream) {
+        static_assert(sizeof(hs::CvPartRecord) == sizeof(hsdev::LoopAPartition), "partition record layouts differ");
+        la_in = in;
+        const LoopAPlan& pl = la_plan;
+        const int64_t cap_parts = std::max<int64_t>(1, pl.cap_off.back());
+        const int64_t cap_span = std::max<int64_t>(span_hint, std::min<int64_t>(cap_parts * pl.w_max, cap_parts * 3 + 4096));
+        la_layout(C, cap_parts, cap_span);
+        if (int rc = la_grow(d_la_candoff, ((size_t)C + 1) * 8)) return rc;
+        if (int rc = la_grow(d_la_parts, (size_t)cap_parts * sizeof(hsdev::LoopAPartition))) return rc;
+        if (int rc = la_grow(d_la_bits, std::max<size_t>(1, (size_t)pl.bits_off.back()) * 8)) return rc;
+        if (int rc = la_grow(d_la_cnt, std::max<size_t>(1, (size_t)pl.cnt_off.back()) * 4)) return rc;
+        if (int rc = la_grow(d_la_meta, lal.meta_bytes)) return rc;
+        if (int rc = la_grow(d_la_hdr, std::max<size_t>(1, (size_t)cap_cand) * sizeof(hsdev::LoopAColumn))) return rc;
+        if (int rc = la_grow(d_la_words, std::max<size_t>(1, (size_t)cap_cand) * 512)) return rc;
+        if (int rc = la_grow(d_la_out_rec, (size_t)cap_parts * sizeof(hsdev::LoopAPartition))) return rc;
+        if (int rc = la_grow(d_la_out_bits, (size_t)cap_span * 24)) return rc;
+        if (int rc = la_grow(d_la_out_cnt, (size_t)cap_span * 256)) return rc;
+        if (int rc = la_grow(h_la, lal.total)) return rc;
+        if (int rc = la_grow(d_la_diag, 128)) return rc;
+        char* meta = (char*)d_la_meta.p;
+        hipLaunchKernelGGL(hsdev::k_fill16, dim3(1), dim3(256), 0, stream, d_la_meta.as<uint4>(), (long long)(lal.meta_bytes / 16), 0u);
+#ifdef HS_LA_DIAG
+        hipLaunchKernelGGL(hsdev::k_fill16, dim3(1), dim3(64), 0, stream, d_la_diag.as<uint4>(), 8ll, 0u);
+#endif
+        hipLaunchKernelGGL(hsdev::k_loop_a_offsets, dim3(1), dim3(64), 0, stream, in.ctg_n, C, d_la_candoff.as<int64_t>());
+        if (int rc = kc.begin(HS_K_ROBUST_PARTITIONS, stream)) return rc;
+        hipLaunchKernelGGL(hsdev::k_loop_a_prepare, dim3((unsigned)((cap_cand + 3) / 4)), dim3(256), 0, stream, in.rec, in.off, in.idx, in.code, in.len,
+                           in.header, (long long)cap_cand, in.contig_rec_off, in.rank_end, in.c0, d_la_on.as<uint8_t>(),
+                           d_la_hdr.as<hsdev::LoopAColumn>(), d_la_words.as<unsigned long long>());
+        hipLaunchKernelGGL(hsdev::k_loop_a, dim3((unsigned)pl.n_dev), dim3(64), 0, stream, d_la_hdr.as<hsdev::LoopAColumn>(), d_la_words.as<unsigned long long>(),
+                           d_la_candoff.as<int64_t>(), d_la_list.as<int32_t>(), pl.n_dev, in.c0, in.contig_rec_off, in.orig_of,
+                           d_la_cap.as<int64_t>(), d_la_bo.as<int64_t>(), d_la_cno.as<int64_t>(), d_la_parts.as<hsdev::LoopAPartition>(), d_la_bits.as<unsigned long long>(),
+                           d_la_cnt.as<int32_t>(), (int32_t*)(meta + lal.np), (int32_t*)(meta + lal.ns), (int32_t*)(meta + lal.nf), d_la_diag.as<unsigned long long>());
+        HS_HIP(hipGetLastError());
+        if (int rc = kc.end(640 * traffic_cand, stream)) return rc;      // the columns' records and words in
+        hipLaunchKernelGGL(hsdev::k_loop_a_scan, dim3(1), dim3(64), 0, stream, (const int32_t*)(meta + lal.np), (const int32_t*)(meta + lal.ns), C, (int64_t*)(meta + lal.pb),
+                           (int64_t*)(meta + lal.sb), (long long*)meta);
+        HS_HIP(hipGetLastError());
+        if (int rc = la_pack_launch(kc, stream)) return rc;
+        la_launched = true;
+        return HS_OK;
+    }
+    // waits for what la_queue left; out views this object's pinned block. *span_words (optional): the words of all partition spans
+    int la_collect(int C, hs::CvLoopAResult& out, KernelClock& kc, hipStream_t stream, int64_t* span_words) {
+        out = hs::CvLoopAResult();
+        if (!la_launched) return HS_OK;
+        for (int attempt = 0;; ++attempt) {
+            if (int rc = stream_wait(stream)) return rc;
+            const long long* tot = (const long long*)h_la.p;
+            if (tot[0] <= lal.cap_parts && tot[1] <= lal.cap_span) break;
+            if (attempt >= 2) { set_error("loop A on the device: the packed partitions do not fit"); return HS_EINVAL; }
+            // more span words than there was room for (the pools still hold every partition): packed again with room
+            la_layout(C, std::max<int64_t>(lal.cap_parts, tot[0]), tot[1] + 64);
+            if (int rc = la_grow(d_la_out_rec, (size_t)lal.cap_parts * sizeof(hsdev::LoopAPartition))) return rc;
+            if (int rc = la_grow(d_la_out_bits, (size_t)lal.cap_span * 24)) return rc;
+            if (int rc = la_grow(d_la_out_cnt, (size_t)lal.cap_span * 256)) return rc;
+            if (int rc = la_grow(h_la, lal.total)) return rc;
+            if (int rc = la_pack_launch(kc, stream)) return rc;
+        }
+        const char* h = (const char*)h_la.p;
+        const long long* tot = (const long long*)h;
+        const int32_t* failed = (const int32_t*)(h + lal.nf);
+        out.on_device = la_plan.on_dev;
+        out.failed.assign(failed, failed + C);
+        out.part_base.assign((const int64_t*)(h + lal.pb), (const int64_t*)(h + lal.pb) + C + 1);
+        out.rec = (const hs::CvPartRecord*)(h + lal.rec); out.bits = (const uint64_t*)(h + lal.bits); out.cnt = (const int32_t*)(h + lal.cnt);
+        if (span_words) *span_words = tot[1];
+        return HS_OK;
+    }
+};
+
+extern "C" {
+
+void hs_loop_a_result_destroy(hs_loop_a_result* r) {
+    if (!r) return;
+    std::free(r->on_device); std::free(r->failed); std::free(r->part_base); std::free(r->rec); std::free(r->state); std::free(r->more); std::free(r->less);
+    delete r;
+}
+
+int hs_loop_a_test(int32_t n_contigs, const int32_t* contig_read_off, const int32_t* read_start, const int32_t* read_end, const int64_t* contig_col_off,
+                   const int32_t* col_pos, const uint8_t* col_k0, const int64_t* col_off, const int32_t* col_idx, const uint8_t* col_code,
+                   int32_t form, int32_t cand_bound, int32_t pool_div, int32_t light, hs_loop_a_result** out, void* stream_) {
+    if (!out) { set_error("hs_loop_a_test: no place for the result"); return HS_EINVAL; }
+    *out = nullptr;
+    if (n_contigs < 0 || (form != 0 && form != 1) || pool_div <= 0 || !contig_read_off || !contig_col_off || !col_off) { set_error("hs_loop_a_test: bad arguments"); return HS_EINVAL; }
+    const int C = n_contigs;
+    const int64_t S = C ? contig_col_off[C] : 0;
+    const int64_t E = S ? col_off[S] : 0;
+    if (contig_read_off[0] != 0 || contig_col_off[0] != 0 || col_off[0] != 0 || S > 0x7fffffff) { set_error("hs_loop_a_test: offsets do not start at 0"); return HS_EINVAL; }
+    for (int c = 0; c < C; ++c) {      // the kernels index with all of this: checked here, entry by entry
+        const int N = contig_read_off[c + 1] - contig_read_off[c];
+        if (N < 0 || contig_col_off[c + 1] < contig_col_off[c]) { set_error("hs_loop_a_test: offsets descend"); return HS_EINVAL; }
+        for (int64_t k = contig_col_off[c]; k < contig_col_off[c + 1]; ++k) {
+            if (col_off[k + 1] < col_off[k] || col_pos[k] < 0 || (k > contig_col_off[c] && col_pos[k] <= col_pos[k - 1])) { set_error("hs_loop_a_test: columns out of order"); return HS_EINVAL; }
+            for (int64_t e = col_off[k]; e < col_off[k + 1]; ++e)
+                if (col_idx[e] < 0 || col_idx[e] >= N || (e > col_off[k] && col_idx[e] <= col_idx[e - 1])) { set_error("hs_loop_a_test: read indices of a column out of range or order"); return HS_EINVAL; }
+        }
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    const int n_reads_all = C ? contig_read_off[C] : 0;
+    std::unique_ptr<hs_loop_a_result, void (*)(hs_loop_a_result*)> R(new hs_loop_a_result(), hs_loop_a_result_destroy);
+    std::memset(R.get(), 0, sizeof(hs_loop_a_result));
+    R->n_contigs = C;
+    R->on_device = (int32_t*)std::calloc((size_t)C + 1, 4); R->failed = (int32_t*)std::calloc((size_t)C + 1, 4); R->part_base = (int64_t*)std::calloc((size_t)C + 1, 8);
+    std::vector<hs::CvContigState*> cst((size_t)C, nullptr);
+    struct Free { std::vector<hs::CvContigState*>& v; ~Free() { for (hs::CvContigState* s : v) if (s) hs::cv_state_free(s); } } free_states{cst};
+    std::vector<char> has((size_t)C, 0);
+    hs::ContigCvResult unused;
+    for (int c = 0; c < C; ++c) {
+        cst[(size_t)c] = hs::cv_state_new();
+        hs::cv_phase_begin(*cst[(size_t)c], contig_read_off[c + 1] - contig_read_off[c], (int)(contig_col_off[c + 1] - contig_col_off[c]), 0.0f, unused);
+    }
+    if (form == 0) {      // the host's walk on the bit sets of the columns, as cv_run_range hands them to it
+        for (int c = 0; c < C; ++c) {
+            const int r0 = contig_read_off[c], N = contig_read_off[c + 1] - r0;
+            const int64_t k0 = contig_col_off[c], n = contig_col_off[c + 1] - k0;
+            std::vector<int32_t> rank_of, orig_of;
+            hs::cv_rank_reads(N, read_start + r0, rank_of, orig_of);
+            std::vector<hs_colrec> rec((size_t)n + 1);
+            for (int64_t k = 0; k < n; ++k) { std::memset(&rec[(size_t)k], 0, sizeof(hs_colrec)); rec[(size_t)k].pos = col_pos[k0 + k]; rec[(size_t)k].contig = c; rec[(size_t)k].k0 = col_k0[k0 + k]; rec[(size_t)k].flags = HS_COL_CAND; }
+            std::vector<hs::CandBits> bits((size_t)n + 1); std::vector<uint64_t> words;
+            hs::cv_build_cand_bits((int)n, col_off + k0, col_idx, col_code, rank_of.data(), read_end + r0, bits.data(), words);
+            words.push_back(0);
+            hs::CandidateSet cs;
+            cs.n = (int)n; cs.rec = rec.data(); cs.bits = bits.data(); cs.words = words.data();
+            hs::cv_phase_a_host(*cst[(size_t)c], cs, read_start + r0);
+            has[(size_t)c] = 1;
+        }
+    } else {
+        if (int rc = require_device()) return rc;
+        std::vector<int32_t> rank_of, orig_of, end_by_rank, rank_end;
+        loop_a_rank_reads(contig_read_off, C, read_start, read_end, rank_of, orig_of, end_by_rank, rank_end);
+        std::vector<int32_t> counts((size_t)C + 1, 0), n_reads((size_t)C + 1, 0), rec_off(contig_read_off, contig_read_off + C + 1);
+        std::vector<hsdev::hs_colrec_dev> rec((size_t)S + 1);
+        std::memset(rec.data(), 0, rec.size() * sizeof(hsdev::hs_colrec_dev));
+        for (int c = 0; c < C; ++c) {
+            counts[(size_t)c] = (int32_t)(contig_col_off[c + 1] - contig_col_off[c]); n_reads[(size_t)c] = contig_read_off[c + 1] - contig_read_off[c];
+            for (int64_t k = contig_col_off[c]; k < contig_col_off[c + 1]; ++k) { rec[(size_t)k].pos = col_pos[k]; rec[(size_t)k].contig = c; rec[(size_t)k].k0 = col_k0[k]; rec[(size_t)k].flags = HS_COL_CAND; }
+        }
+        // the two layouts k_loop_a_prepare reads: packed (lengths from consecutive offsets), or "light": a place and a length per column in
+        // arrays that hold the columns in another order (here: the last column first, a foreign entry between two columns)
+        std::vector<int64_t> off((size_t)S + 1, 0); std::vector<int32_t> len((size_t)S + 1, 0), idx; std::vector<uint8_t> code;
+        if (!light) { off.assign(col_off, col_off + S + 1); idx.assign(col_idx, col_idx + E); code.assign(col_code, col_code + E); }
+        else
+            for (int64_t k = S - 1; k >= 0; --k) {
+                idx.push_back(0); code.push_back(255);      // (belongs to no column)
+                off[(size_t)k] = (int64_t)idx.size(); len[(size_t)k] = (int32_t)(col_off[k + 1] - col_off[k]);
+                idx.insert(idx.end(), col_idx + col_off[k], col_idx + col_off[k + 1]); code.insert(code.end(), col_code + col_off[k], col_code + col_off[k + 1]);
+            }
+        idx.push_back(0); code.push_back(0);
+        if (n_reads_all == 0) { rank_end.assign(2, 0); orig_of.assign(1, 0); }
+        std::vector<hsdev::ColumnsHeader> header(1);
+        std::memset(header.data(), 0, sizeof(hsdev::ColumnsHeader));
+        header[0].n_cols = S; header[0].n_entries = E; header[0].n_flagged = S; header[0].n_flagged_entries = E; header[0].ok = 1;
+        LoopADevice la;
+        KernelClock kc;
+        if (int rc = la.la_make_plan(counts.data(), n_reads.data(), C, cand_bound, pool_div, nullptr, stream)) return rc;
+        for (int c = 0; c < C; ++c) R->on_device[c] = la.la_plan.on_dev[(size_t)c];
+        if (la.la_plan.n_dev > 0) {
+            DBuf d_rec, d_off, d_idx, d_code, d_len, d_hdr, d_cn, d_ro, d_re, d_oo;
+            UploadPack pk;
+            pk.add(rec, d_rec); pk.add(off, d_off); pk.add(idx, d_idx); pk.add(code, d_code); pk.add(len, d_len); pk.add(header, d_hdr); pk.add(counts, d_cn); pk.add(rec_off, d_ro);
+            pk.add(rank_end, d_re); pk.add(orig_of, d_oo);
+            if (int rc = pk.commit(stream)) return rc;
+            LoopAIn in;
+            in.rec = d_rec.as<hsdev::hs_colrec_dev>(); in.off = d_off.as<int64_t>(); in.idx = d_idx.as<int32_t>(); in.code = d_code.as<uint8_t>(); in.len = light ? d_len.as<int32_t>() : nullptr;
+            in.header = d_hdr.as<hsdev::ColumnsHeader>(); in.ctg_n = d_cn.as<int32_t>(); in.contig_rec_off = d_ro.as<int32_t>(); in.rank_end = d_re.as<int2>(); in.orig_of = d_oo.as<int32_t>(); in.c0 = 0;
+            if (int rc = la.la_queue(in, C, S, 0, S, kc, stream)) return rc;
+            hs::CvLoopAResult res;
+            const int rc = la.la_collect(C, res, kc, stream, nullptr);
+            const int rc_w = stream_wait(stream);      // (the uploads go back to the pool with this scope)
+            kc.flush();
+            if (rc) return rc;
+            if (rc_w) return rc_w;
+            for (int c = 0; c < C; ++c) {
+                R->failed[c] = res.failed[(size_t)c];
+                if (!R->on_device[c] || R->failed[c]) continue;
+                const int r0 = contig_read_off[c];
+                hs::cv_phase_a_import(*cst[(size_t)c], read_start + r0, (int)(res.part_base[(size_t)c + 1] - res.part_base[(size_t)c]), res.rec + res.part_base[(size_t)c], res.bits, res.cnt,
+                                      rank_of.data() + r0, orig_of.data() + r0);
+                has[(size_t)c] = 1;
+            }
+        }
+    }
+    // the dense export of what loop A left (a contig the device did not walk, or handed back, has no partitions here)
+    int64_t P = 0, D = 0;
+    for (int c = 0; c < C; ++c) {
+        const int64_t n = has[(size_t)c] ? hs::cv_loop_a_partitions(*cst[(size_t)c]) : 0;
+        R->part_base[c + 1] = R->part_base[c] + n; P += n; D += n * (contig_read_off[c + 1] - contig_read_off[c]);
+    }
+    R->rec = (int32_t*)std::calloc((size_t)P * 9 + 1, 4); R->state = (int8_t*)std::calloc((size_t)D + 1, 1); R->more = (int32_t*)std::calloc((size_t)D + 1, 4); R->less = (int32_t*)std::calloc((size_t)D + 1, 4);
+    int64_t d = 0;
+    for (int c = 0; c < C; ++c) {
+        const int64_t n = R->part_base[c + 1] - R->part_base[c];
+        if (n == 0) continue;
+        std::vector<hs::CvPartRecord> pr((size_t)n);
+        hs::cv_export_loop_a(*cst[(size_t)c], pr.data(), R->state + d, R->more + d, R->less + d);
+        for (int64_t p = 0; p < n; ++p) {
+            const hs::CvPartRecord& r = pr[(size_t)p];
+            const int32_t v[9] = {r.left, r.right, r.n_occ, r.n_corr, r.lo, r.hi, r.reach, r.w0, r.w1};
+            std::memcpy(R->rec + (R->part_base[c] + p) * 9, v, sizeof v);
+        }
+        d += n * (contig_read_off[c + 1] - contig_read_off[c]);
+    }
+    *out = R.release();
+    return HS_OK;
+}
+
 // K5a: one workgroup per (contig, 4 words of its bit rows); the list of workgroups is made from the host copy of words[]
 static void snp_planes_blocks(const int32_t* h_words, int n_contigs, std::vector<int32_t>& blk_c, std::vector<int32_t>& blk_w) {
     blk_c.clear(); blk_w.clear();

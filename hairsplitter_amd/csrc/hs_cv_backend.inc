@@ -209,27 +209,14 @@ int hs_cv_batch_create(const uint8_t* h_contig_seq, const int64_t* h_contig_off,
     up(b->d_contig_rec_off, b->contig_rec_off.data(), sizeof(int32_t) * b->contig_rec_off.size());
     {   // what loop A on the device (k_loop_a) needs of the reads: their rank by start position on the contig (ties by index: the
         // bit order of the partition bit sets, as rank_reads() of the host glue), the inverse, the end of their alignment
-        std::vector<int32_t> rank_of((size_t)n_rec), orig_of((size_t)n_rec), read_end((size_t)n_rec);
-        hs::hs_parallel_for(n_contigs, host_threads(), [&](int c) {
-            const int r0 = b->contig_rec_off[(size_t)c], n = b->contig_rec_off[(size_t)c + 1] - r0;
-            std::vector<int32_t> order((size_t)n);
-            for (int r = 0; r < n; ++r) order[(size_t)r] = r;
-            std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return h_rec_pos[r0 + x] != h_rec_pos[r0 + y] ? h_rec_pos[r0 + x] < h_rec_pos[r0 + y] : x < y; });
-            for (int k = 0; k < n; ++k) { rank_of[(size_t)(r0 + order[(size_t)k])] = k; orig_of[(size_t)(r0 + k)] = order[(size_t)k]; }
-            for (int k = 0; k < n; ++k) {      // (in rank order: the kernel indexes everything per read by rank)
-                const int r = order[(size_t)k];
-                read_end[(size_t)(r0 + k)] = (int32_t)std::min<int64_t>((int64_t)h_rec_pos[r0 + r] + b->rec_refspan[(size_t)(r0 + r)], 0x7fffffff);
-            }
-        });
+        std::vector<int32_t> rec_end((size_t)n_rec), rank_of, orig_of, read_end, rank_end;
+        for (int r = 0; r < n_rec; ++r) rec_end[(size_t)r] = (int32_t)std::min<int64_t>((int64_t)h_rec_pos[r] + b->rec_refspan[(size_t)r], 0x7fffffff);
+        loop_a_rank_reads(b->contig_rec_off.data(), n_contigs, h_rec_pos, rec_end.data(), rank_of, orig_of, read_end, rank_end);
         up(b->d_rank_of, rank_of.data(), sizeof(int32_t) * (size_t)n_rec);
         up(b->d_orig_of, orig_of.data(), sizeof(int32_t) * (size_t)n_rec);
         b->h_rank_of = rank_of; b->h_orig_of = orig_of;
         up(b->d_read_end, read_end.data(), sizeof(int32_t) * (size_t)n_rec);
-        {   // per READ of a contig: {its rank, the end of its alignment} (k_cand_bits: one gather per column entry)
-            std::vector<int32_t> rank_end((size_t)n_rec * 2);
-            for (int r = 0; r < n_rec; ++r) { rank_end[(size_t)r * 2] = rank_of[(size_t)r]; rank_end[(size_t)r * 2 + 1] = (int32_t)std::min<int64_t>((int64_t)h_rec_pos[r] + b->rec_refspan[(size_t)r], 0x7fffffff); }
-            up(b->d_rank_end, rank_end.data(), sizeof(int32_t) * 2 * (size_t)n_rec);
-        }
+        up(b->d_rank_end, rank_end.data(), sizeof(int32_t) * 2 * (size_t)n_rec);      // (k_cand_bits: one gather per column entry)
     }
     up(b->d_rec_qend, b->rec_qend.data(), sizeof(int32_t) * (size_t)n_rec);
     lap("tile plan + ranks");
@@ -282,7 +269,7 @@ namespace {
 
 // HIP implementation of the stage-3 device interface (the only one the product has). The columns of a contig range live in
 // this object from extract_candidates() to finish_columns(); the SNP columns it leaves (snp_*) are what stage 4 reads.
-struct HipCvOps : hs::CvDeviceOps {
+struct HipCvOps : hs::CvDeviceOps, LoopADevice {
     hs_cv_batch* b;
     hipStream_t stream = nullptr;
     hipStream_t stream_late = nullptr;      // (optional) the stream of everything behind the candidates' wait: finish_columns switches to it
@@ -715,7 +702,7 @@ struct HipCvOps : hs::CvDeviceOps {
             // loop A of the contigs that fit the device's tables runs there (k_loop_a), queued behind the bit sets of the others: the host
             // waits for those only (an event in the middle of the stream) and walks its share while the device walks its own
             la_launched = false;
-            la_plan = LoopAPlan();
+            la_plan = LoopADevice::LoopAPlan();
             if (loop_a_device_max() > 0) {
                 const bool counts_known = hinted ? (int)keep->cand_per_contig.size() == C : true;      // (not hinted: the info block has just been read)
                 if (counts_known) { if (int rc = loop_a_plan(hinted ? keep->cand_per_contig.data() : host_ctg_n(), C)) return rc; }
@@ -919,140 +906,34 @@ struct HipCvOps : hs::CvDeviceOps {
         const size_t g = order_ticket < 0 ? 0 : (size_t)order_ticket;
         return v[g < v.size() ? g : v.size() - 1];
     }
-    struct LoopAPlan {
-        std::vector<uint8_t> on_dev; std::vector<int32_t> dev_list; std::vector<int64_t> cap_off, bits_off, cnt_off;
-        int w_max = 1, n_dev = 0;
-    } la_plan;
-    DBuf d_la_on, d_la_list, d_la_cap, d_la_bo, d_la_cno, d_la_candoff, d_la_parts, d_la_bits, d_la_cnt, d_la_meta, d_la_hdr, d_la_words, d_la_out_rec, d_la_out_bits, d_la_out_cnt, d_la_diag;
-    UploadPack la_pack;
-    HBuf h_la;
     hipEvent_t ev_cand = nullptr;
-    bool la_launched = false;
-    // the meta block the kernels leave and the host reads: [totals: partitions, span words][n_parts C][n_span C][failed C][part_base C + 1][span_base C + 1]
-    struct LaLayout { size_t np, ns, nf, pb, sb, meta_bytes, rec, bits, cnt, total; int64_t cap_parts, cap_span; } lal{};
-    void la_layout(int C, int64_t cap_parts, int64_t cap_span) {
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        lal.np = 16; lal.ns = lal.np + (size_t)C * 4; lal.nf = lal.ns + (size_t)C * 4; lal.pb = (lal.nf + (size_t)C * 4 + 7) & ~(size_t)7; lal.sb = lal.pb + ((size_t)C + 1) * 8;
-        lal.meta_bytes = up(lal.sb + ((size_t)C + 1) * 8);
-        lal.rec = lal.meta_bytes; lal.bits = lal.rec + up((size_t)cap_parts * sizeof(hsdev::LoopAPartition)); lal.cnt = lal.bits + up((size_t)cap_span * 24); lal.total = lal.cnt + up((size_t)cap_span * 256);
-        lal.cap_parts = cap_parts; lal.cap_span = cap_span;
-    }
     int loop_a_plan(const int32_t* counts, int C) {
         static const int pool_div = []() { const char* e = std::getenv("HS_LOOP_A_POOL_DIV"); return e && std::atoi(e) > 0 ? std::atoi(e) : 6; }();
-        const int kmax = loop_a_device_max();
-        LoopAPlan& pl = la_plan;
-        pl = LoopAPlan();
-        pl.on_dev.assign((size_t)C, 0); pl.cap_off.assign((size_t)C + 1, 0); pl.bits_off.assign((size_t)C + 1, 0); pl.cnt_off.assign((size_t)C + 1, 0);
-        std::vector<std::pair<int64_t, int>> weight;
+        std::vector<int32_t> n_reads((size_t)C);
+        for (int c = 0; c < C; ++c) n_reads[(size_t)c] = b->contig_rec_off[(size_t)(range_c0 + c) + 1] - b->contig_rec_off[(size_t)(range_c0 + c)];
         const bool forced = keep && (int)keep->la_force_host.size() == C;
-        for (int c = 0; c < C; ++c) {
-            const int64_t k = counts[c];
-            const int N = b->contig_rec_off[(size_t)(range_c0 + c) + 1] - b->contig_rec_off[(size_t)(range_c0 + c)];
-            const int W = (N + 63) >> 6;
-            const bool dev = k > 0 && k <= kmax && W <= HS_LA_MAXW && !(forced && keep->la_force_host[(size_t)c]);
-            const int64_t cap = dev ? std::min<int64_t>(k + 8, k / pool_div + 48) : 0;
-            pl.cap_off[(size_t)c + 1] = pl.cap_off[(size_t)c] + cap;
-            pl.bits_off[(size_t)c + 1] = pl.bits_off[(size_t)c] + cap * 3 * W;
-            pl.cnt_off[(size_t)c + 1] = pl.cnt_off[(size_t)c] + cap * W * 64;
-            if (dev) { pl.on_dev[(size_t)c] = 1; pl.w_max = std::max(pl.w_max, W); weight.push_back(std::make_pair(-k, c)); }
-        }
-        std::sort(weight.begin(), weight.end());      // the heaviest contig first: it is what the launch waits for
-        for (auto& w : weight) pl.dev_list.push_back(w.second);
-        pl.n_dev = (int)pl.dev_list.size();
-        if (pl.n_dev == 0) return HS_OK;
-        la_pack.add(pl.on_dev, d_la_on); la_pack.add(pl.dev_list, d_la_list); la_pack.add(pl.cap_off, d_la_cap); la_pack.add(pl.bits_off, d_la_bo); la_pack.add(pl.cnt_off, d_la_cno);
-        return la_pack.commit(stream);
-    }
-    int loop_a_pack_launch(int C) {      // the partitions packed into the form the host imports, and on their way with the meta block
-        const char* meta = (const char*)d_la_meta.p;
-        hipLaunchKernelGGL(hsdev::k_loop_a_pack, dim3((unsigned)la_plan.n_dev), dim3(256), 0, stream, d_la_list.as<int32_t>(), la_plan.n_dev, (const int32_t*)(meta + lal.np), range_c0,
-                           b->d_contig_rec_off.as<int32_t>(), d_la_cap.as<int64_t>(), d_la_bo.as<int64_t>(), d_la_parts.as<hsdev::LoopAPartition>(), d_la_bits.as<unsigned long long>(),
-                           d_la_cnt.as<int32_t>(), (const int64_t*)(meta + lal.pb), (const int64_t*)(meta + lal.sb), (long long)lal.cap_parts, (long long)lal.cap_span,
-                           d_la_out_rec.as<hsdev::LoopAPartition>(), d_la_out_bits.as<unsigned long long>(), d_la_out_cnt.as<int32_t>());
-        HS_HIP(hipGetLastError());
-        Shipment sh;
-        sh.add(h_la.p, d_la_meta.p, lal.meta_bytes);
-        sh.add_counted((char*)h_la.p + lal.rec, d_la_out_rec.p, (const long long*)meta, sizeof(hsdev::LoopAPartition), lal.cap_parts);
-        sh.add_counted((char*)h_la.p + lal.bits, d_la_out_bits.p, (const long long*)meta + 1, 24, lal.cap_span);
-        sh.add_counted((char*)h_la.p + lal.cnt, d_la_out_cnt.p, (const long long*)meta + 1, 256, lal.cap_span);
-        if (int rc = kc.begin(HS_K_SHIP, stream)) return rc;
-        if (int rc = sh.launch(stream)) return rc;
-        (void)C;
-        return kc.end(0, stream);
+        return la_make_plan(counts, n_reads.data(), C, loop_a_device_max(), pool_div, forced ? keep->la_force_host.data() : nullptr, stream);
     }
     int loop_a_launch(int64_t cap_cand) {
-        static_assert(sizeof(hs::CvPartRecord) == sizeof(hsdev::LoopAPartition), "partition record layouts differ");
-        const int C = range_c1 - range_c0;
-        const LoopAPlan& pl = la_plan;
-        const int64_t cap_parts = std::max<int64_t>(1, pl.cap_off.back());
-        const int64_t cap_span = std::max<int64_t>(with_margin(keep ? keep->la_span : 0), std::min<int64_t>(cap_parts * pl.w_max, cap_parts * 3 + 4096));
-        la_layout(C, cap_parts, cap_span);
-        if (int rc = grow(d_la_candoff, ((size_t)C + 1) * 8)) return rc;
-        if (int rc = grow(d_la_parts, (size_t)cap_parts * sizeof(hsdev::LoopAPartition))) return rc;
-        if (int rc = grow(d_la_bits, std::max<size_t>(1, (size_t)pl.bits_off.back()) * 8)) return rc;
-        if (int rc = grow(d_la_cnt, std::max<size_t>(1, (size_t)pl.cnt_off.back()) * 4)) return rc;
-        if (int rc = grow(d_la_meta, lal.meta_bytes)) return rc;
-        if (int rc = grow(d_la_hdr, std::max<size_t>(1, (size_t)cap_cand) * sizeof(hsdev::LoopAColumn))) return rc;
-        if (int rc = grow(d_la_words, std::max<size_t>(1, (size_t)cap_cand) * 512)) return rc;
-        if (int rc = grow(d_la_out_rec, (size_t)cap_parts * sizeof(hsdev::LoopAPartition))) return rc;
-        if (int rc = grow(d_la_out_bits, (size_t)cap_span * 24)) return rc;
-        if (int rc = grow(d_la_out_cnt, (size_t)cap_span * 256)) return rc;
-        if (int rc = grow(h_la, lal.total)) return rc;
-        if (int rc = grow(d_la_diag, 128)) return rc;
         const char* cb = (const char*)d_cand_pk.p;
-        char* meta = (char*)d_la_meta.p;
-        hipLaunchKernelGGL(hsdev::k_fill16, dim3(1), dim3(256), 0, stream, d_la_meta.as<uint4>(), (long long)(lal.meta_bytes / 16), 0u);
-#ifdef HS_LA_DIAG
-        hipLaunchKernelGGL(hsdev::k_fill16, dim3(1), dim3(64), 0, stream, d_la_diag.as<uint4>(), 8ll, 0u);
-#endif
-        hipLaunchKernelGGL(hsdev::k_loop_a_offsets, dim3(1), dim3(64), 0, stream, dev_ctg_n(), C, d_la_candoff.as<int64_t>());
-        if (int rc = kc.begin(HS_K_ROBUST_PARTITIONS, stream)) return rc;
-        hipLaunchKernelGGL(hsdev::k_loop_a_prepare, dim3((unsigned)((cap_cand + 3) / 4)), dim3(256), 0, stream, (const hsdev::hs_colrec_dev*)(cb + cand_layout.rec),
-                           (const int64_t*)(cb + cand_layout.off), cand_layout.light ? d_ci.as<int32_t>() : (const int32_t*)(cb + cand_layout.idx),
-                           cand_layout.light ? d_cc.as<uint8_t>() : (const uint8_t*)(cb + cand_layout.code), cand_layout.light ? (const int32_t*)(cb + cand_layout.len) : nullptr,
-                           dev_header(), (long long)cap_cand, b->d_contig_rec_off.as<int32_t>(), b->d_rank_end.as<int2>(), range_c0, d_la_on.as<uint8_t>(),
-                           d_la_hdr.as<hsdev::LoopAColumn>(), d_la_words.as<unsigned long long>());
-        hipLaunchKernelGGL(hsdev::k_loop_a, dim3((unsigned)pl.n_dev), dim3(64), 0, stream, d_la_hdr.as<hsdev::LoopAColumn>(), d_la_words.as<unsigned long long>(),
-                           d_la_candoff.as<int64_t>(), d_la_list.as<int32_t>(), pl.n_dev, range_c0, b->d_contig_rec_off.as<int32_t>(), b->d_orig_of.as<int32_t>(),
-                           d_la_cap.as<int64_t>(), d_la_bo.as<int64_t>(), d_la_cno.as<int64_t>(), d_la_parts.as<hsdev::LoopAPartition>(), d_la_bits.as<unsigned long long>(),
-                           d_la_cnt.as<int32_t>(), (int32_t*)(meta + lal.np), (int32_t*)(meta + lal.ns), (int32_t*)(meta + lal.nf), d_la_diag.as<unsigned long long>());
-        HS_HIP(hipGetLastError());
-        if (int rc = kc.end(640 * (keep && keep->cand > 0 ? keep->cand : cap_cand), stream)) return rc;      // the columns' records and words in
-        hipLaunchKernelGGL(hsdev::k_loop_a_scan, dim3(1), dim3(64), 0, stream, (const int32_t*)(meta + lal.np), (const int32_t*)(meta + lal.ns), C, (int64_t*)(meta + lal.pb),
-                           (int64_t*)(meta + lal.sb), (long long*)meta);
-        HS_HIP(hipGetLastError());
-        if (int rc = loop_a_pack_launch(C)) return rc;
-        la_launched = true;
-        return HS_OK;
+        LoopAIn in;
+        in.rec = (const hsdev::hs_colrec_dev*)(cb + cand_layout.rec); in.off = (const int64_t*)(cb + cand_layout.off);
+        in.idx = cand_layout.light ? d_ci.as<int32_t>() : (const int32_t*)(cb + cand_layout.idx);
+        in.code = cand_layout.light ? d_cc.as<uint8_t>() : (const uint8_t*)(cb + cand_layout.code);
+        in.len = cand_layout.light ? (const int32_t*)(cb + cand_layout.len) : nullptr;
+        in.header = dev_header(); in.ctg_n = dev_ctg_n(); in.contig_rec_off = b->d_contig_rec_off.as<int32_t>(); in.rank_end = b->d_rank_end.as<int2>();
+        in.orig_of = b->d_orig_of.as<int32_t>(); in.c0 = range_c0;
+        return la_queue(in, range_c1 - range_c0, cap_cand, with_margin(keep ? keep->la_span : 0), keep && keep->cand > 0 ? keep->cand : cap_cand, kc, stream);
     }
     // the partitions loop A left on the device (after extract_candidates has returned and the host has walked its own contigs)
     int collect_partitions(hs::CvLoopAResult& out) override {
-        out = hs::CvLoopAResult();
-        if (!la_launched) return HS_OK;
+        if (!la_launched) { out = hs::CvLoopAResult(); return HS_OK; }
         const int C = range_c1 - range_c0;
-        for (int attempt = 0;; ++attempt) {
-            if (int rc = stream_wait(stream)) return rc;
-            const long long* tot = (const long long*)h_la.p;
-            if (tot[0] <= lal.cap_parts && tot[1] <= lal.cap_span) break;
-            if (attempt >= 2) { set_error("loop A on the device: the packed partitions do not fit"); return HS_EINVAL; }
-            // more span words than there was room for (the pools still hold every partition): packed again with room
-            la_layout(C, std::max<int64_t>(lal.cap_parts, tot[0]), tot[1] + 64);
-            if (int rc = grow(d_la_out_rec, (size_t)lal.cap_parts * sizeof(hsdev::LoopAPartition))) return rc;
-            if (int rc = grow(d_la_out_bits, (size_t)lal.cap_span * 24)) return rc;
-            if (int rc = grow(d_la_out_cnt, (size_t)lal.cap_span * 256)) return rc;
-            if (int rc = grow(h_la, lal.total)) return rc;
-            if (int rc = loop_a_pack_launch(C)) return rc;
-        }
-        const char* h = (const char*)h_la.p;
-        const long long* tot = (const long long*)h;
-        const int32_t* failed = (const int32_t*)(h + lal.nf);
-        out.on_device = la_plan.on_dev;
-        out.failed.assign(failed, failed + C);
-        out.part_base.assign((const int64_t*)(h + lal.pb), (const int64_t*)(h + lal.pb) + C + 1);
-        out.rec = (const hs::CvPartRecord*)(h + lal.rec); out.bits = (const uint64_t*)(h + lal.bits); out.cnt = (const int32_t*)(h + lal.cnt);
+        int64_t span = 0;
+        if (int rc = la_collect(C, out, kc, stream, &span)) return rc;
         if (keep) {
-            keep->la_span = tot[1];
-            for (int c = 0; c < C; ++c) if (failed[c]) { if ((int)keep->la_force_host.size() != C) keep->la_force_host.assign((size_t)C, 0); keep->la_force_host[(size_t)c] = 1; }
+            keep->la_span = span;
+            for (int c = 0; c < C; ++c) if (out.failed[(size_t)c]) { if ((int)keep->la_force_host.size() != C) keep->la_force_host.assign((size_t)C, 0); keep->la_force_host[(size_t)c] = 1; }
         }
 #ifdef HS_LA_DIAG
         {

@@ -71,6 +71,10 @@ void cv_phase_a_host(CvContigState& st, const CandidateSet& cs, const int32_t* r
 // (more | less << 16); rec[p].elem is not used here
 void cv_phase_a_import(CvContigState& st, const int32_t* read_start, int n_parts, const CvPartRecord* rec, const uint64_t* bits, const int32_t* cnt, const int32_t* rank_of = nullptr, const int32_t* orig_of = nullptr);
 void cv_phase_b(CvContigState& st, ContigCvResult& out, const int32_t* pair_table = nullptr);
+// loop A's partitions before loop B, for the direct test entries: their number, then a record each (w0 / w1: the words that hold reads)
+// and the dense arrays over the read indices (n_reads entries per partition; state 2 = absent)
+int cv_loop_a_partitions(const CvContigState& st);
+void cv_export_loop_a(const CvContigState& st, CvPartRecord* rec, int8_t* state, int32_t* more, int32_t* less);
 // loop B with the pair distances from the device (k_partition_pair_distance): the partitions that pass loop B's gate, their dense
 // arrays, the host's table of 3-sigma thresholds
 int cv_loop_b_survivors(CvContigState& st);

@@ -835,6 +835,17 @@ void cv_export_survivors(const CvContigState& st, int8_t* state, int32_t* more, 
     const size_t N = (size_t)st.n_reads;
     for (size_t k = 0; k < st.survivors.size(); ++k) export_dense(st.parts[(size_t)st.survivors[k]], state + k * N, more + k * N, less + k * N);
 }
+// what loop A left (cv_phase_a_host or cv_phase_a_import), in creation order: the records (w0 / w1 = the words that hold reads, word_off
+// unused) and the dense arrays, n_reads entries per partition (the direct test entries)
+int cv_loop_a_partitions(const CvContigState& st) { return (int)st.parts.size(); }
+void cv_export_loop_a(const CvContigState& st, CvPartRecord* rec, int8_t* state, int32_t* more, int32_t* less) {
+    const size_t N = (size_t)st.n_reads;
+    for (size_t k = 0; k < st.parts.size(); ++k) {
+        const RankPartition& p = st.parts[k];
+        rec[k] = CvPartRecord{p.left, p.right, p.n_occ, p.n_corr, p.lo, p.hi, p.reach, p.wlo, p.whi, 0, 0};
+        export_dense(p, state + k * N, more + k * N, less + k * N);
+    }
+}
 const std::vector<float>& cv_three_sigma_table() {
     static const std::vector<float> t = [] { std::vector<float> v(4096); for (int k = 0; k < 4096; ++k) v[(size_t)k] = three_sigma_threshold(k); return v; }();
     return t;

@@ -178,6 +178,33 @@ int hs_column_partition_test(const int64_t* d_col_off, const int32_t* d_col_idx,
 void hs_column_partition_last_counts(int32_t out[3]);
 
 /* ------------------------------------------------------------------------------------------------
+ * Test entry: loop A of keep_only_robust_variants (call_variants.cpp:590-638) on prescribed candidate columns, in either form the
+ * product has -- form 0: the host's walk (hs::cv_build_cand_bits -> hs::cv_phase_a_host), form 1: the device's (k_loop_a_prepare ->
+ * k_loop_a -> k_loop_a_scan -> k_loop_a_pack -> hs::cv_phase_a_import; the plan, the launches and the collection are the ones stage 3
+ * queues). All arrays on the HOST. Contig c has the reads [contig_read_off[c], contig_read_off[c + 1]) (read_start / read_end: their
+ * alignment's first and exclusive last position) and the columns [contig_col_off[c], contig_col_off[c + 1]) in ascending position:
+ * col_pos, the reference code col_k0, and the CSR col_off / col_idx (read indices on the contig, ascending) / col_code.
+ * cand_bound: the device walks the contigs with 1 .. cand_bound columns; pool_div: its partition pool holds min(k + 8, k / pool_div + 48)
+ * partitions for k columns; light != 0: the columns reach k_loop_a_prepare as a place and a length each in arrays that hold them in
+ * another order (the layout of a column pass that keeps no packed entries). None of the three is read from the environment here.
+ * Result: on_device[c] (planned for the device), failed[c] (the kernel handed it back); contig c's partitions in creation order are
+ * [part_base[c], part_base[c + 1]) -- none for a contig of form 1 that is not on the device or was handed back -- with 9 ints each in
+ * rec (left, right, numberOfOccurences, number_of_correlating_snps, lo, hi: first / last read index, reach: largest alignment end,
+ * w0, w1: first / last word of ranked reads that holds one) and n_reads entries each in state (2 = absent) / more / less, back to back.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hs_loop_a_result {
+    int32_t n_contigs;
+    int32_t* on_device; int32_t* failed;
+    int64_t* part_base;
+    int32_t* rec;
+    int8_t* state; int32_t* more; int32_t* less;
+} hs_loop_a_result;
+int hs_loop_a_test(int32_t n_contigs, const int32_t* contig_read_off, const int32_t* read_start, const int32_t* read_end, const int64_t* contig_col_off,
+                   const int32_t* col_pos, const uint8_t* col_k0, const int64_t* col_off, const int32_t* col_idx, const uint8_t* col_code,
+                   int32_t form, int32_t cand_bound, int32_t pool_div, int32_t light, hs_loop_a_result** out, void* stream);
+void hs_loop_a_result_destroy(hs_loop_a_result* r);
+
+/* ------------------------------------------------------------------------------------------------
  * V5 -- distance(Partition&, Partition&, threshold_p) of loop B (call_variants.cpp:977-1127) for a list of partition pairs.
  * Partitions as dense arrays one after the other: partition p occupies [part_off[p], part_off[p] + part_n[p]) of d_state
  * (mostFrequentBases in {-1, 0, 1}, 2 = read absent), d_more / d_less (moreFrequence / lessFrequence); the two partitions of a

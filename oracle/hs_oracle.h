@@ -109,6 +109,18 @@ public:
 DistRes distance(const Partition& p, const Column& col, char ref_base);                 // :778-967
 DistRes distance(const Partition& a, const Partition& b, int threshold_p);              // :977-1127
 float computeChiSquare(const DistRes& d);                                               // :1135-1163
+// loop A of keep_only_robust_variants alone (:590-638), with a tap for the tests: per column its fate (0 = skipped by the `<= 5` rule,
+// 1 = augmented partition target, 2 = created partition target) and every (column, partition) pair the loop met, in order
+struct LoopACmp {
+    int col = 0, part = 0;
+    int kind = 0;                    // 0: more than 50 000 behind (:595), not compared; 1: compared; 2: compared, no shared read
+    int n00 = 0, n01 = 0, n10 = 0, n11 = 0;
+    int second = -1;                 // the second allele distance() chose (-1: no shared read)
+    bool corr = false, fit = false;
+    float chi = 0;
+};
+struct LoopATap { std::vector<int> fate, target; std::vector<LoopACmp> cmp; };
+void loop_a(const std::vector<Column>& snps_in, std::vector<Partition>& partitions, LoopATap* tap);
 void keep_only_robust_variants(std::vector<Column>& msa, std::vector<Column>& snps_in,
                                std::vector<Column>& snps_out, float mean_error,
                                std::vector<Partition>& parts);                          // :577-768

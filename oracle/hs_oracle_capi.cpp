@@ -413,4 +413,47 @@ int hso_parse_blocks(const char* path, const char* tag, int32_t n_fixed, hso_blo
     return 0;
 }
 
+// Loop A of keep_only_robust_variants alone (call_variants.cpp:590-638) on one contig's candidate columns, given as CSR (positions
+// ascending, read indices ascending inside a column). Returns the number of partitions, in creation order: part_rec[p] = {left, right,
+// numberOfOccurences, number_of_correlating_snps}; state / more / less: n_reads entries per partition (state 2 = the read is absent);
+// fate[c] = {0 skipped by the `<= 5` rule | 1 augmented | 2 created, partition or -1}. cmp (optional): 11 ints per (column, partition)
+// pair the loop met, in order = {column, partition, kind (0: more than 50 000 behind, 1: compared, 2: compared without a shared read),
+// n00, n01, n10, n11, second allele or -1, correlates, fits, bits of the float chi-square}; *n_cmp = how many there were (the first
+// cmp_cap of them are written).
+int hso_loop_a(int32_t n_reads, int32_t n_cols, const int32_t* pos, const uint8_t* k0, const int64_t* off, const int32_t* idx, const uint8_t* code,
+               int32_t* part_rec, int8_t* state, int32_t* more, int32_t* less, int32_t* fate, int32_t* cmp, int64_t cmp_cap, int64_t* n_cmp) {
+    std::vector<hso::Column> cols((size_t)n_cols);
+    for (int c = 0; c < n_cols; ++c) {
+        hso::Column& col = cols[(size_t)c];
+        col.pos = pos[c]; col.ref_base = k0[c];
+        for (int64_t k = off[c]; k < off[c + 1]; ++k) {
+            if (idx[k] < 0 || idx[k] >= n_reads) return -1;
+            col.readIdxs.push_back((unsigned)idx[k]); col.content.push_back(code[k]);
+        }
+    }
+    std::vector<hso::Partition> parts;
+    hso::LoopATap tap;
+    hso::loop_a(cols, parts, &tap);
+    for (size_t p = 0; p < parts.size(); ++p) {
+        const hso::Partition& P = parts[p];
+        part_rec[4 * p] = P.get_left(); part_rec[4 * p + 1] = P.get_right(); part_rec[4 * p + 2] = P.number(); part_rec[4 * p + 3] = P.number_of_correlating_snps;
+        int8_t* st = state + p * (size_t)n_reads; int32_t* mo = more + p * (size_t)n_reads; int32_t* le = less + p * (size_t)n_reads;
+        for (int r = 0; r < n_reads; ++r) { st[r] = 2; mo[r] = 0; le[r] = 0; }
+        for (size_t k = 0; k < P.readIdx.size(); ++k) {
+            const int r = P.readIdx[k];
+            st[r] = (int8_t)P.mostFrequentBases[k]; mo[r] = P.moreFrequence[k]; le[r] = P.lessFrequence[k];
+        }
+    }
+    for (int c = 0; c < n_cols; ++c) { fate[2 * c] = tap.fate[(size_t)c]; fate[2 * c + 1] = tap.target[(size_t)c]; }
+    if (n_cmp) *n_cmp = (int64_t)tap.cmp.size();
+    if (cmp)
+        for (size_t k = 0; k < tap.cmp.size() && (int64_t)k < cmp_cap; ++k) {
+            const hso::LoopACmp& x = tap.cmp[k];
+            int32_t* o = cmp + 11 * k;
+            o[0] = x.col; o[1] = x.part; o[2] = x.kind; o[3] = x.n00; o[4] = x.n01; o[5] = x.n10; o[6] = x.n11; o[7] = x.second; o[8] = x.corr; o[9] = x.fit;
+            std::memcpy(o + 10, &x.chi, 4);
+        }
+    return (int)parts.size();
+}
+
 }  // extern "C"

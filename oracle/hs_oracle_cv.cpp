@@ -565,31 +565,45 @@ float computeChiSquare(const DistRes& dis) {
     return res;
 }
 
-// call_variants.cpp:577-768
-void keep_only_robust_variants(std::vector<Column>& msa, std::vector<Column>& snps_in,
-                               std::vector<Column>& snps_out, float mean_error,
-                               std::vector<Partition>& parts) {
-    snps_out.clear();
-    std::vector<Partition> partitions;
+// loop A of keep_only_robust_variants (call_variants.cpp:590-638) on its own: the candidate columns in position order build the
+// partitions. `tap` (optional, tests): what became of every column and every (column, partition) pair the loop looked at.
+void loop_a(const std::vector<Column>& snps_in, std::vector<Partition>& partitions, LoopATap* tap) {
+    partitions.clear();
+    if (tap) { tap->fate.clear(); tap->target.clear(); tap->cmp.clear(); }
     int lastposition = -5;
+    int ci = -1;
     for (const Column& snp : snps_in) {                                     // loop A :590-638
-        if (snp.pos - lastposition <= 5) continue;
+        ci++;
+        if (snp.pos - lastposition <= 5) { if (tap) { tap->fate.push_back(0); tap->target.push_back(-1); } continue; }
         bool found = false;
         int position = snp.pos;
         int number_of_correlating_snps = 0;
+        size_t taker = 0;
         for (size_t p = 0; p < partitions.size(); p++) {
-            if (std::abs(snp.pos - partitions[p].get_right()) > 50000) continue;
+            if (std::abs(snp.pos - partitions[p].get_right()) > 50000) {
+                if (tap) { LoopACmp c; c.col = ci; c.part = (int)p; c.kind = 0; tap->cmp.push_back(c); }
+                continue;
+            }
             DistRes dis = distance(partitions[p], snp, (char)snp.ref_base);
             int comparable = dis.n00 + dis.n11 + dis.n01 + dis.n10;
+            bool corr = false;
             if (dis.n00 + dis.n01 > 0.1 * comparable && dis.n00 + dis.n01 < 0.9 * comparable
                 && dis.n01 + dis.n11 > 0.1 * comparable && dis.n01 + dis.n11 < 0.9 * comparable
                 && computeChiSquare(dis) > 15) {
+                corr = true;
                 number_of_correlating_snps += 1;
                 partitions[p].number_of_correlating_snps += 1;
             }
-            if ((dis.n01 <= std::max(0.1 * (dis.n00 + dis.n01), 1.0) && dis.n10 < std::max(0.1 * (dis.n11 + dis.n10), 1.0) && (size_t)comparable >= snp.readIdxs.size() / 2)
-                || (dis.n00 <= std::max(0.1 * (dis.n00 + dis.n01), 1.0) && dis.n11 < std::max(0.1 * (dis.n11 + dis.n10), 1.0) && (size_t)comparable >= snp.readIdxs.size() / 2)) {
-                found = true;
+            const bool fit = (dis.n01 <= std::max(0.1 * (dis.n00 + dis.n01), 1.0) && dis.n10 < std::max(0.1 * (dis.n11 + dis.n10), 1.0) && (size_t)comparable >= snp.readIdxs.size() / 2)
+                || (dis.n00 <= std::max(0.1 * (dis.n00 + dis.n01), 1.0) && dis.n11 < std::max(0.1 * (dis.n11 + dis.n10), 1.0) && (size_t)comparable >= snp.readIdxs.size() / 2);
+            if (tap) {
+                LoopACmp c; c.col = ci; c.part = (int)p; c.kind = dis.augmented ? 1 : 2;
+                c.n00 = dis.n00; c.n01 = dis.n01; c.n10 = dis.n10; c.n11 = dis.n11; c.second = dis.augmented ? dis.secondBase : -1;
+                c.corr = corr; c.fit = fit; c.chi = computeChiSquare(dis);
+                tap->cmp.push_back(c);
+            }
+            if (fit) {
+                found = true; taker = p;
                 partitions[p].augmentPartition(dis.partition_to_augment, position);
                 break;
             }
@@ -598,10 +612,21 @@ void keep_only_robust_variants(std::vector<Column>& msa, std::vector<Column>& sn
             Partition p(snp, position, snp.ref_base);
             p.number_of_correlating_snps = number_of_correlating_snps;
             partitions.push_back(p);
+            if (tap) { tap->fate.push_back(2); tap->target.push_back((int)partitions.size() - 1); }
         } else {
             lastposition = snp.pos;
+            if (tap) { tap->fate.push_back(1); tap->target.push_back((int)taker); }
         }
     }
+}
+
+// call_variants.cpp:577-768
+void keep_only_robust_variants(std::vector<Column>& msa, std::vector<Column>& snps_in,
+                               std::vector<Column>& snps_out, float mean_error,
+                               std::vector<Partition>& parts) {
+    snps_out.clear();
+    std::vector<Partition> partitions;
+    loop_a(snps_in, partitions, nullptr);
     if (partitions.size() == 0) return;
 
     std::vector<Partition> finals;                                          // loop B :646-708

@@ -5,6 +5,7 @@
 //   host_harness call_variants  <11 positional args of HS_call_variants>
 //   host_harness separate_reads <9 positional args of HS_separate_reads>
 //   host_harness graph_taps <cases.i64> <out.i64>   (sr_run in the graphs mode of its test taps; both files are streams of int64, see graph_taps())
+//   host_harness loop_a <cases.i64> <out.i64>       (loop A of stage 3 on prescribed candidate columns, host form; see loop_a())
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -454,9 +455,72 @@ static int graph_taps(const char* in_path, const char* out_path) {
     return out ? 0 : 2;
 }
 
+// `loop_a`: candidate columns given directly -> hs::cv_rank_reads, hs::cv_build_cand_bits, hs::cv_phase_a_host -> what loop A leaves, before loop B.
+// Input, int64 each: C; per contig: N, S, E, then read_start[N], read_end[N], pos[S], k0[S], off[S + 1], idx[E], code[E] (read indices ascending inside
+// a column). Output: per contig P, then per partition left, right, n_occ, n_corr, lo, hi, reach, w0, w1, state[N] (2 = absent), more[N], less[N].
+static int loop_a(const char* in_path, const char* out_path) {
+    std::vector<int64_t> v;
+    {
+        std::ifstream f(in_path, std::ios::binary);
+        if (!f) return 2;
+        f.seekg(0, std::ios::end); const std::streamoff n = f.tellg(); f.seekg(0);
+        if (n < 8 || n % 8) return 2;
+        v.resize((size_t)n / 8);
+        f.read((char*)v.data(), n);
+        if (!f) return 2;
+    }
+    size_t at = 0;
+    bool bad = false;
+    auto take = [&](size_t n) -> const int64_t* { if (n > v.size() - at) { bad = true; return nullptr; } const int64_t* p = v.data() + at; at += n; return p; };
+    const int64_t C = take(1)[0];
+    if (C < 0 || (size_t)C > v.size()) return 2;
+    std::vector<int64_t> o;
+    for (int64_t c = 0; c < C; ++c) {
+        const int64_t* q = take(3);
+        if (bad || q[0] < 0 || q[1] < 0 || q[2] < 0) return 2;
+        const size_t N = (size_t)q[0], S = (size_t)q[1], E = (size_t)q[2];
+        std::vector<int32_t> rs, re, pos, idx; std::vector<uint8_t> k0, code; std::vector<int64_t> off;
+        auto fill = [&](auto& dst, size_t n) { const int64_t* p = take(n); if (!p) return; dst.resize(n); for (size_t k = 0; k < n; ++k) dst[k] = (typename std::decay<decltype(dst)>::type::value_type)p[k]; };
+        fill(rs, N); fill(re, N); fill(pos, S); fill(k0, S); fill(off, S + 1); fill(idx, E); fill(code, E);
+        if (bad || off[0] != 0 || off[S] != (int64_t)E) return 2;
+        for (size_t k = 0; k < S; ++k) if (off[k + 1] < off[k]) return 2;
+        for (size_t k = 0; k < E; ++k) if (idx[k] < 0 || (size_t)idx[k] >= N) return 2;
+        idx.push_back(0); code.push_back(0); rs.push_back(0); re.push_back(0);      // (never null)
+        std::vector<int32_t> rank_of, orig_of;
+        hs::cv_rank_reads((int)N, rs.data(), rank_of, orig_of);
+        std::vector<hs_colrec> rec(S + 1);
+        for (size_t k = 0; k < S; ++k) { std::memset(&rec[k], 0, sizeof(hs_colrec)); rec[k].pos = pos[k]; rec[k].contig = (int32_t)c; rec[k].k0 = k0[k]; rec[k].flags = HS_COL_CAND; }
+        std::vector<hs::CandBits> bits(S + 1); std::vector<uint64_t> words;
+        hs::cv_build_cand_bits((int)S, off.data(), idx.data(), code.data(), rank_of.data(), re.data(), bits.data(), words);
+        words.push_back(0);
+        hs::CandidateSet cs;
+        cs.n = (int)S; cs.rec = rec.data(); cs.bits = bits.data(); cs.words = words.data(); cs.off = off.data(); cs.idx = idx.data(); cs.code = code.data();
+        hs::CvContigState* st = hs::cv_state_new();
+        hs::ContigCvResult res;
+        hs::cv_phase_begin(*st, (int)N, (int)S, 0.0f, res);
+        hs::cv_phase_a_host(*st, cs, rs.data());
+        const size_t P = (size_t)hs::cv_loop_a_partitions(*st);
+        std::vector<hs::CvPartRecord> pr(P + 1); std::vector<int8_t> state(P * N + 1); std::vector<int32_t> more(P * N + 1), less(P * N + 1);
+        hs::cv_export_loop_a(*st, pr.data(), state.data(), more.data(), less.data());
+        hs::cv_state_free(st);
+        o.push_back((int64_t)P);
+        for (size_t p = 0; p < P; ++p) {
+            const hs::CvPartRecord& r = pr[p];
+            for (int x : {r.left, r.right, r.n_occ, r.n_corr, r.lo, r.hi, r.reach, r.w0, r.w1}) o.push_back(x);
+            for (size_t k = 0; k < N; ++k) o.push_back(state[p * N + k]);
+            for (size_t k = 0; k < N; ++k) o.push_back(more[p * N + k]);
+            for (size_t k = 0; k < N; ++k) o.push_back(less[p * N + k]);
+        }
+    }
+    std::ofstream out(out_path, std::ios::binary);
+    out.write((const char*)o.data(), (std::streamsize)(o.size() * 8));
+    return out ? 0 : 2;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
     if (!std::strcmp(argv[1], "selftest")) return selftest();
+    if (!std::strcmp(argv[1], "loop_a")) return argc == 4 ? loop_a(argv[2], argv[3]) : 2;
     if (!std::strcmp(argv[1], "graph_taps")) return argc == 4 ? graph_taps(argv[2], argv[3]) : 2;
     if (!std::strcmp(argv[1], "call_variants")) {
         if (argc < 13) return 2;

@@ -110,6 +110,40 @@ def column_partition_test(col_off, col_idx, col_code, col_contig, col_k0, col_k1
     return keep[:n], chi[:n], tab[:n]
 
 
+CMP_FIELDS = ("col", "part", "kind", "n00", "n01", "n10", "n11", "second", "corr", "fit")
+
+
+def loop_a(n_reads, pos, k0, off, idx, code):
+    """Loop A of the oracle's keep_only_robust_variants alone, on one contig's candidate columns (CSR). Returns a dict: rec [P, 4] = left, right,
+    numberOfOccurences, number_of_correlating_snps in creation order; state / more / less [P, n_reads] (state 2 = absent); fate [S, 2] = (0 skipped by
+    the `<= 5` rule | 1 augmented | 2 created, partition or -1); cmp: one int array per name of CMP_FIELDS plus the float32 "chi", one entry per
+    (column, partition) pair the loop met (kind 0: more than 50 000 behind, not compared; 1: compared; 2: compared, no shared read)."""
+    S = len(pos)
+    a = lambda x, dt: np.ascontiguousarray(x if len(x) else np.zeros(1), dt)
+    pos_ = a(pos, np.int32); k0_ = a(k0, np.uint8); off_ = np.ascontiguousarray(off, np.int64); idx_ = a(idx, np.int32); code_ = a(code, np.uint8)
+    assert len(off_) == S + 1 and off_[0] == 0 and off_[-1] == len(idx) == len(code)
+    rec = np.zeros((max(S, 1), 4), np.int32)
+    state = np.zeros((max(S, 1), max(n_reads, 1)), np.int8); more = np.zeros(state.shape, np.int32); less = np.zeros(state.shape, np.int32)
+    fate = np.zeros((max(S, 1), 2), np.int32)
+    L = lib()
+    L.hso_loop_a.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 11 + [C.c_int64, C.c_void_p]
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    cap = 4 * S + 64
+    while True:
+        cmp_ = np.zeros((cap, 11), np.int32); n_cmp = np.zeros(1, np.int64)
+        P = L.hso_loop_a(C.c_int32(n_reads), C.c_int32(S), p(pos_), p(k0_), p(off_), p(idx_), p(code_), p(rec), p(state), p(more), p(less), p(fate), p(cmp_),
+                         C.c_int64(cap), p(n_cmp))
+        assert P >= 0
+        if int(n_cmp[0]) <= cap:
+            break
+        cap = int(n_cmp[0])
+    cmp_ = cmp_[:int(n_cmp[0])]
+    out = {"rec": rec[:P].copy(), "state": state[:P, :n_reads].copy(), "more": more[:P, :n_reads].copy(), "less": less[:P, :n_reads].copy(), "fate": fate[:S].copy(),
+           "cmp": {name: cmp_[:, k].copy() for k, name in enumerate(CMP_FIELDS)}}
+    out["cmp"]["chi"] = np.ascontiguousarray(cmp_[:, 10]).view(np.float32).copy()
+    return out
+
+
 def partition_pair_distance(state, more, less, part_off, part_n, pair_a, pair_b, threshold_p=2):
     """distance(Partition, Partition, threshold_p) of the oracle for every pair: [n_pairs, 6] = n00, n01, n10, n11, phased, augmented"""
     n = len(pair_a)
