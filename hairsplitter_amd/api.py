@@ -21,7 +21,7 @@ if os.environ.get("HS_LIB_AB"):      # (tools/gpu_ab_lib.sh: another build of th
 SYMBOLS = [
     "hs_cv_batch_set_ploidy", "hs_version", "hs_last_error", "hs_device_count", "hs_warmup", "hs_set_device", "hs_device_synchronize", "hs_malloc", "hs_free",
     "hs_memcpy_h2d", "hs_memcpy_d2h", "hs_memset", "hs_event_create", "hs_event_destroy", "hs_event_record",
-    "hs_event_elapsed_ms", "hs_pileup", "hs_pileup_plan", "hs_free_host", "hs_tile_plan", "hs_column_stats_tiled", "hs_cv_column_pass_taps", "hs_cv_taps_destroy", "hs_sr_run_taps", "hs_sr_taps_destroy", "hs_exclusive_scan_i32", "hs_gaf_from_files", "hs_gaf_from_labels", "hs_gro_to_gaf_main", "hs_column_partition_test", "hs_column_partition_last_counts", "hs_loop_a_test", "hs_loop_a_result_destroy", "hs_partition_pair_distance", "hs_snp_planes", "hs_simdiff", "hs_read_graphs",
+    "hs_event_elapsed_ms", "hs_pileup", "hs_pileup_plan", "hs_free_host", "hs_tile_plan", "hs_column_stats_tiled", "hs_cv_column_pass_taps", "hs_cv_taps_destroy", "hs_cv_pileup_tap", "hs_cv_pileup_tap_destroy", "hs_sr_run_taps", "hs_sr_taps_destroy", "hs_exclusive_scan_i32", "hs_gaf_from_files", "hs_gaf_from_labels", "hs_gro_to_gaf_main", "hs_column_partition_test", "hs_column_partition_last_counts", "hs_loop_a_test", "hs_loop_a_result_destroy", "hs_partition_pair_distance", "hs_snp_planes", "hs_simdiff", "hs_read_graphs",
     "hs_edit_distance", "hs_cv_batch_create", "hs_cv_batch_destroy", "hs_cv_batch_aligned_bp", "hs_cv_run",
     "hs_cv_result_destroy", "hs_cv_select", "hs_cv_run_range", "hs_cv_selection_destroy", "hs_sr_run", "hs_sr_run_cv", "hs_sr_run_cv_range", "hs_pipeline_create", "hs_pipeline_select", "hs_pipeline_run", "hs_pipeline_destroy", "hs_pipeline_thread_devices", "hs_cv_batch_device", "hs_sr_result_destroy", "hs_sr_window_size", "hs_call_variants_main", "hs_call_variants_epilogue",
     "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_edlib_align", "hs_edlib_align_bytes", "hs_alignment_to_cigar", "hs_reattach_ends", "hs_trim_polished", "hs_reattach_ends_bytes", "hs_trim_polished_bytes", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
@@ -974,6 +974,36 @@ def cv_column_pass_taps(batch: "CvBatch", c0: int, c1: int, automatic_snp_thresh
         "contig_n_cand": arr(t.contig_n_cand, Cn, np.int32), "contig_mean_distance": arr(t.contig_mean_distance, Cn, np.float32),
     }
     lib.hs_cv_taps_destroy(tp)
+    return out
+
+
+class _CvPileupTaps(C.Structure):
+    _fields_ = [("n_rec", C.c_int32), ("pile_lead", C.c_int32), ("pile_alloc_bytes", C.c_int64), ("n_chunks", C.c_int64), ("pile", C.POINTER(C.c_uint8)),
+                ("pile_addr", C.POINTER(C.c_int64)), ("rec_stats", C.POINTER(C.c_int32)), ("rec_chunk_off", C.POINTER(C.c_int64)), ("chunk_table", C.POINTER(C.c_int32))]
+
+
+def cv_pileup_tap(batch: "CvBatch", c0: int, c1: int, fill: int = 0xFF) -> Dict:
+    """K0 + K1 of the contigs [c0, c1) as a contig group of the pipeline launches them on the resident batch (hs_cv_pileup_tap): the whole pile
+    allocation is set to the byte `fill` first, rec_stats and the chunk table to 0xFF bytes. Returns what the device holds afterwards: "pile" (the whole
+    allocation; "lead" bytes lie in front of the address 0 that "pile_addr" [n_rec + 1] counts from), "rec_stats" [n_rec, 4], "rec_chunk_off" [n_rec + 1],
+    "chunk_table" [n_chunks, 4]. The batch's pileup is overwritten: take a fresh batch for anything else."""
+    lib = load()
+    lib.hs_cv_pileup_tap.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.POINTER(_CvPileupTaps))]
+    lib.hs_cv_pileup_tap_destroy.argtypes = [C.POINTER(_CvPileupTaps)]
+    lib.hs_cv_pileup_tap_destroy.restype = None
+    tp = C.POINTER(_CvPileupTaps)()
+    _check(lib.hs_cv_pileup_tap(batch.handle, C.c_int32(c0), C.c_int32(c1), C.c_int32(fill), C.byref(tp)))
+    t = tp.contents
+    n, nch = int(t.n_rec), int(t.n_chunks)
+
+    def arr(ptr, count, dtype):
+        if count == 0:
+            return np.zeros(0, dtype)
+        return np.frombuffer(C.string_at(ptr, count * np.dtype(dtype).itemsize), dtype=dtype).copy()
+    out = {"pile": arr(t.pile, int(t.pile_alloc_bytes), np.uint8), "lead": int(t.pile_lead), "pile_addr": arr(t.pile_addr, n + 1, np.int64),
+           "rec_stats": arr(t.rec_stats, 4 * n, np.int32).reshape(n, 4), "rec_chunk_off": arr(t.rec_chunk_off, n + 1, np.int64),
+           "chunk_table": arr(t.chunk_table, 4 * nch, np.int32).reshape(nch, 4)}
+    lib.hs_cv_pileup_tap_destroy(tp)
     return out
 
 

@@ -406,6 +406,54 @@ int hs_cv_column_pass_taps(hs_cv_batch* b, int32_t c0, int32_t c1, float automat
     return HS_OK;
 }
 
+// ---- test tap of the pileup as a contig group launches it (include/hairsplitter_hip.h: hs_cv_pileup_taps) ----
+void hs_cv_pileup_tap_destroy(hs_cv_pileup_taps* t) {
+    if (!t) return;
+    std::free(t->pile); std::free(t->pile_addr); std::free(t->rec_stats); std::free(t->rec_chunk_off); std::free(t->chunk_table);
+    std::free(t);
+}
+int hs_cv_pileup_tap(hs_cv_batch* b, int32_t c0, int32_t c1, int32_t fill, hs_cv_pileup_taps** out) {
+    if (int rc = require_device()) return rc;
+    if (!b || !out || c0 < 0 || c1 > b->n_contigs || c0 > c1 || fill < 0 || fill > 255) { set_error("hs_cv_pileup_tap: bad arguments"); return HS_EINVAL; }
+    if (int rc = bind_device(b->device)) return rc;
+    HipCvOps ops(b);
+    ops.own_pileup = true;
+    const size_t n_rec = (size_t)b->n_rec;
+    DBuf d_md, d_min_reads;      // what k_contig_error leaves behind the pileup of a group
+    if (int rc = d_md.alloc(std::max<size_t>(1, (size_t)(c1 - c0)) * 4)) return rc;
+    if (int rc = d_min_reads.alloc(std::max<size_t>(1, (size_t)(c1 - c0)) * 4)) return rc;
+    HS_HIP(hipMemsetAsync(b->pile.p, fill, b->pile.bytes, ops.stream));
+    if (b->rec_stats.bytes) HS_HIP(hipMemsetAsync(b->rec_stats.p, 0xFF, b->rec_stats.bytes, ops.stream));
+    if (b->chunk_scratch.bytes) HS_HIP(hipMemsetAsync(b->chunk_scratch.p, 0xFF, b->chunk_scratch.bytes, ops.stream));
+    if (c1 > c0) { if (int rc = ops.pileup_range_launch(c0, c1, d_md.as<float>(), d_min_reads.as<int32_t>(), 3)) return rc; }
+    HS_HIP(hipStreamSynchronize(ops.stream));
+    ops.kc.flush();
+    hs_cv_pileup_taps* t = (hs_cv_pileup_taps*)std::calloc(1, sizeof(hs_cv_pileup_taps));
+    if (!t) { set_error("hs_cv_pileup_tap: out of memory"); return HS_EINVAL; }
+    t->n_rec = b->n_rec;
+    t->pile_lead = (int32_t)(b->pile_ptr() - b->pile.as<uint8_t>());
+    t->pile_alloc_bytes = (int64_t)b->pile.bytes;
+    t->n_chunks = (int64_t)(b->chunk_scratch.bytes / 16);
+    auto dup_d = [&](void** dst, const void* d, size_t bytes) -> int {
+        *dst = std::malloc(std::max<size_t>(bytes, 16));
+        if (!*dst) { set_error("hs_cv_pileup_tap: out of memory"); return HS_EINVAL; }
+        if (bytes) HS_HIP(hipMemcpy(*dst, d, bytes, hipMemcpyDeviceToHost));
+        return HS_OK;
+    };
+    int rc = dup_d((void**)&t->pile, b->pile.p, b->pile.bytes);
+    if (!rc) rc = dup_d((void**)&t->rec_stats, b->rec_stats.p, n_rec * 16);
+    if (!rc) rc = dup_d((void**)&t->rec_chunk_off, b->rec_chunk_off.p, (n_rec + 1) * 8);
+    if (!rc) rc = dup_d((void**)&t->chunk_table, b->chunk_scratch.p, b->chunk_scratch.bytes);
+    if (!rc) {
+        t->pile_addr = (int64_t*)std::malloc((n_rec + 1) * 8);
+        if (!t->pile_addr) { set_error("hs_cv_pileup_tap: out of memory"); rc = HS_EINVAL; }
+        else std::memcpy(t->pile_addr, b->pile_addr.data(), (n_rec + 1) * 8);
+    }
+    if (rc) { hs_cv_pileup_tap_destroy(t); return rc; }
+    *out = t;
+    return HS_OK;
+}
+
 int hs_pipeline_select(hs_pipeline* p, float* mean_distance, hs_pipeline_stats* st) {
     if (!p || !mean_distance) { set_error("hs_pipeline_select: null argument"); return HS_EINVAL; }
     if (int rc = bind_device(p->batch->device)) return rc;

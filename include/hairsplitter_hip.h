@@ -480,6 +480,25 @@ typedef struct hs_cv_taps {
 int hs_cv_column_pass_taps(hs_cv_batch* b, int32_t c0, int32_t c1, float automatic_snp_threshold, hs_cv_taps** out);
 void hs_cv_taps_destroy(hs_cv_taps* t);
 
+/* Test tap of the pileup as a contig group of the pipeline launches it: K0 + K1 (+ the records K0 flagged) of the contigs [c0, c1) on the resident
+ * batch's own pile layout (every record at an address = contig_off + pos mod 128) and its own prebuilt task slice. Before the launch the WHOLE pile
+ * allocation -- the bytes in front of the first record, every record, every gap, the bytes behind the last -- is set to the byte `fill`, and the batch's
+ * rec_stats and chunk table to 0xFF bytes, so that every byte a kernel writes outside its records, or outside the range, shows. Host copies of what the
+ * device holds afterwards. No kernel of its own, nothing on the product path. */
+typedef struct hs_cv_pileup_taps {
+    int32_t n_rec;
+    int32_t pile_lead;               /* bytes of the allocation in front of the pile's byte 0 (what pile_addr counts from) */
+    int64_t pile_alloc_bytes;        /* pile_lead + pile_addr[n_rec] + the bytes behind */
+    int64_t n_chunks;                /* rec_chunk_off[n_rec] */
+    uint8_t* pile;                   /* [pile_alloc_bytes] the whole allocation */
+    int64_t* pile_addr;              /* [n_rec + 1] */
+    int32_t* rec_stats;              /* [n_rec][4] q_end, n_err, n_len, events */
+    int64_t* rec_chunk_off;          /* [n_rec + 1] */
+    int32_t* chunk_table;            /* [n_chunks][4] K0's table */
+} hs_cv_pileup_taps;
+int hs_cv_pileup_tap(hs_cv_batch* b, int32_t c0, int32_t c1, int32_t fill, hs_cv_pileup_taps** out);
+void hs_cv_pileup_tap_destroy(hs_cv_pileup_taps* t);
+
 /* Several GPUs in one process. Contigs are the independent units of both stages (call_variants.cpp:1276-1280,
  * separate_reads.cpp:1506-1508): hs_cv_run_host and hs_sr_run shard them over the devices of hs_devices() by
  * longest-processing-time (stage 3: bases of the reads aligned to the contig; stage 4: N^2 + N * S), one host thread and one

@@ -158,7 +158,8 @@ def test_pileup_bytes_and_counters(batch):
     o_pile, o_stats, _ = ol.pileup(flat)
     assert np.array_equal(pile.cpu().numpy(), o_pile)
     assert np.array_equal(stats.cpu().numpy()[:, :3], o_stats[:, :3])
-    # task granularity must not change a byte (tasks of 64 / 1000 / one huge range per record)
+    # ev_per_task governs only the per-event form of the records K0 flagged (k_pileup_flagged_records): event ranges of 64 / 1000 / one huge range per
+    # record must not change a byte. The run form's task is fixed at HS_K1R_NCH chunks of ops: tests/test_gpu_pileup_cases.py sits either side of its edges.
     for ev in (64, 1000, 1 << 30):
         p2, s2 = api.pileup(t, flat, ev_per_task=ev)
         assert np.array_equal(p2.cpu().numpy(), o_pile), ev
