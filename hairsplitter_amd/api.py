@@ -12,6 +12,8 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from .dist import mean_of_positive_f32, stage4_error_rate, window_size_counts, window_size_from_counts
+
 _ROOT = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_ROOT, "lib", "libhairsplitter_hip.so")
 if os.environ.get("HS_LIB_AB"):      # (tools/gpu_ab_lib.sh: another build of the same library, for A/B timing of a code change on one box)
@@ -333,7 +335,7 @@ class CvBatch:
                   "t_device_ms": float(r.t_device_ms), "t_host_ms": float(r.t_host_ms), "t_kernel_ms": [float(x) for x in r.t_kernel_ms], "t_kernel_k4_ms": float(r.t_kernel_k4_ms),
                   "n_columns_extracted": int(r.n_columns_extracted), "n_columns_downloaded": int(r.n_columns_downloaded),
                   "n_columns_downloaded_late": int(r.n_columns_downloaded_late)}
-            e = error_rate_fn(cv) if error_rate_fn is not None else min(float("%g" % cv["error_rate"]), 0.15)
+            e = error_rate_fn(cv) if error_rate_fn is not None else stage4_error_rate(cv["error_rate"])
             sres = C.POINTER(SrResult)()
             _check(lib.hs_sr_run_cv(self.handle, res, C.c_float(e), C.c_float(rarest_strain_abundance), C.c_int32(1 if low_memory else 0),
                                     C.c_int32(1 if amplicon else 0), C.c_uint32(seed), C.c_int32(n_threads), C.c_int32(window_size),
@@ -517,9 +519,8 @@ class PipelineGroups:
         t_1 = time.perf_counter()
         md = md[:Cn]
         # call_variants.cpp:1312-1315,1377: float sum in contig order / number of contigs with a positive distance
-        from .dist import mean_of_positive_f32
         cv = {"mean_distance": md, "error_rate": mean_of_positive_f32(md)}
-        e = error_rate_fn(cv) if error_rate_fn is not None else min(float("%g" % cv["error_rate"]), 0.15)
+        e = error_rate_fn(cv) if error_rate_fn is not None else stage4_error_rate(cv["error_rate"])
         sres = C.POINTER(SrResult)()   # window_size <= 0: hs_pipeline_run chooses it over the whole batch (same rule as self.window_size())
         t_2 = time.perf_counter()
         _check(lib.hs_pipeline_run(self.handle, C.c_float(automatic_snp_threshold), C.c_float(e), C.c_float(rarest_strain_abundance),
@@ -563,19 +564,7 @@ class PipelineGroups:
         f = self.flat
         if amplicon:
             return int(np.diff(f.contig_off).max()) if f.n_contigs else 0
-        lens = f.rec_refspan + 2
-        if lens.size == 0:
-            return 2000
-        total = int(lens.sum()) & 0xFFFFFFFF
-        if total >= 1 << 31:
-            total -= 1 << 32
-        mean = total / float(lens.size)
-        above = int((lens > 4000).sum())
-        if above < 20 and 2000 < mean < 4000:
-            return 1000
-        if above < 20 and mean < 2000:
-            return 500
-        return 2000
+        return window_size_from_counts(*window_size_counts(f.rec_refspan + 2))
 
     def close(self):
         if self.handle:

@@ -34,6 +34,7 @@
 #include "hs_host.h"
 #include "hs_host_sr.h"
 #include "hs_driver.h"
+#include "hs_job_rules.h"
 #include "hs_kernels.hip"
 #include "hs_kernels_graph.hip"
 #include "hs_kernels_cw.hip"

@@ -271,12 +271,10 @@ int hs_cv_run_host(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int
     // contig order: where every contig's SNPs and column entries go (prefix sums over the contigs), then the copies on all host threads
     R->snp_off[0] = 0; R->col_off[0] = 0;
     std::vector<int64_t> ent0((size_t)n_contigs + 1, 0);
-    float total_error = 0; int n_err = 0;
     for (int c = 0; c < n_contigs; ++c) {
         const hs_cv_result* r = parts[(size_t)where[(size_t)c].first];
         const int i = where[(size_t)c].second;
         R->mean_distance[c] = r->mean_distance[i]; R->depth[c] = r->depth[i];
-        if (r->mean_distance[i] > 0) { total_error += r->mean_distance[i]; n_err++; }      // call_variants.cpp:1312-1315, contig order
         R->snp_off[c + 1] = R->snp_off[c] + (r->snp_off[i + 1] - r->snp_off[i]);
         ent0[(size_t)c + 1] = ent0[(size_t)c] + (r->col_off[r->snp_off[i + 1]] - r->col_off[r->snp_off[i]]);
     }
@@ -297,7 +295,7 @@ int hs_cv_run_host(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int
         std::memcpy(R->col_idx + ent0[(size_t)c], r->col_idx + r->col_off[q0], (size_t)ne * sizeof(int32_t));
         std::memcpy(R->col_code + ent0[(size_t)c], r->col_code + r->col_off[q0], (size_t)ne);
     });
-    R->error_rate = total_error / n_err; R->n_contigs_with_error_rate = n_err;
+    R->error_rate = hs::job_error_rate(R->mean_distance, n_contigs, &R->n_contigs_with_error_rate);      // (contig order)
     for (hs_cv_result* r : parts) {
         R->t_device_ms += r->t_device_ms; R->t_host_ms += r->t_host_ms;
         for (int k = 0; k < 4; ++k) R->t_kernel_ms[k] += r->t_kernel_ms[k];

@@ -138,10 +138,6 @@ struct hs_pipeline {
 
     int device = 0;        // = batch->device: the group threads bind themselves to it (a new thread starts on device 0)
     std::vector<int> thread_device;   // what every group thread found current after binding (hs_pipeline_thread_devices)
-    // (a contig group queues everything on its thread's default stream -- the entries below stay null; a low-priority stream for the head of its
-    // chain and a high-priority one for the rest was measured in round 4: 24.2 ms per C4 step against 18.6, the low-priority heads are on the
-    // critical path of the groups that come later)
-    std::vector<hipStream_t> s_lo, s_hi;
     void worker(int g) {
         ::prctl(PR_SET_NAME, "hs-group", 0, 0, 0);
         uint64_t seen = 0;
@@ -232,7 +228,6 @@ int hs_pipeline_create(hs_cv_batch* b, int32_t n_groups, hs_pipeline** out) {
     }
     p->rcs.assign((size_t)G, 0); p->errs.assign((size_t)G, std::string()); p->cv.assign((size_t)G, nullptr);
     p->device = b->device; p->thread_device.assign((size_t)G, -1);
-    p->s_lo.assign((size_t)G, nullptr); p->s_hi.assign((size_t)G, nullptr);
     p->sr_keep.resize((size_t)G);
     for (int g = 0; g < G; ++g) p->entry_blocks.emplace_back(new HBuf());
     for (int g = 0; g < G; ++g) p->cv_keep.emplace_back(new HipCvOps::Keep());
@@ -277,7 +272,7 @@ void hs_pipeline_destroy(hs_pipeline* p) {
     { std::lock_guard<std::mutex> lk(p->mu); p->quit = true; }
     p->cv_go.notify_all();
     for (std::thread& t : p->threads) t.join();
-    if (bind_device(p->device) == HS_OK) { for (hipStream_t st : p->s_lo) if (st) (void)hipStreamDestroy(st); for (hipStream_t st : p->s_hi) if (st) (void)hipStreamDestroy(st); }
+    (void)bind_device(p->device);
     p->drop_cv();
     delete p;
 }
@@ -475,186 +470,163 @@ int hs_pipeline_select(hs_pipeline* p, float* mean_distance, hs_pipeline_stats* 
     return HS_OK;
 }
 
+// ---- the contig-group step behind hs_pipeline_run and hs_pipeline_run_fused ----
+
+// n_threads <= 0: three workers per usable core over all groups -- a group is on the host for part of its chain only (the
+// rest it waits for the device), so that many threads keep the cores busy without queueing behind each other (500-contig
+// bench, 16 usable cores: 16 threads 74 ms per step, 32: 46, 48: 44, 64: 47, 128: 51)
+static int pipeline_threads_per_group(int n_threads, int G) {
+    if (n_threads <= 0) n_threads = 3 * host_threads();
+    return std::max(1, n_threads / G);
+}
+
+// the window size over the WHOLE batch (hs_job_rules.h: window_size_from_counts looks at every read of every contig): READ
+// limits are (POS-1, POS + reference span) (input_output.cpp:503-511); --amplicon: the longest contig
+static int32_t pipeline_window_size(const hs_cv_batch* b, bool amplicon) {
+    if (amplicon) { int32_t w = 0; for (int c = 0; c < b->n_contigs; ++c) w = std::max<int32_t>(w, (int32_t)(b->contig_off[(size_t)c + 1] - b->contig_off[(size_t)c])); return w; }
+    uint32_t sum = 0; int64_t reads = 0, above = 0;
+    for (int64_t v : b->rec_refspan) hs::window_size_count_read((int)v + 2, sum, reads, above);
+    return hs::window_size_from_counts(sum, reads, above);
+}
+
+// what the groups' stage-3 results add to the statistics of a call
+static void fold_cv_stats(hs_pipeline_stats* st, const hs_pipeline* p) {
+    for (const hs_cv_result* r : p->cv) {
+        st->n_snps += r->snp_off[r->n_contigs];
+        st->t_device_ms += r->t_device_ms; st->t_host_ms += r->t_host_ms;
+        st->t_kernel_cv_ms[2] += r->t_kernel_ms[2]; st->t_kernel_k4_ms += r->t_kernel_k4_ms;
+        st->n_columns_extracted += r->n_columns_extracted; st->n_columns_downloaded += r->n_columns_downloaded;
+        st->n_columns_downloaded_late += r->n_columns_downloaded_late;
+        st->t_kernel_cv_ms[1] += r->t_kernel_ms[1];
+    }
+}
+
+// The meeting point of the fused call's groups before stage 4: a group's mean distances are known (from the host's sums, or with
+// its candidate columns from the device), the last group to get here forms the job's error rate (hs_job_rules.h), which is long
+// before the first one needs it for stage 4; a group that fails releases the others.
+struct GroupMeeting {
+    std::mutex mu; std::condition_variable cv;
+    int arrived = 0; bool aborted = false;
+    std::vector<float> md;      // [n_contigs] what hs_pipeline_select would have returned
+    float error_rate = 0;
+    void arrive(const float* md_g, int c0, int c1, int G) {
+        if (c1 > c0) std::memcpy(md.data() + c0, md_g, (size_t)(c1 - c0) * sizeof(float));
+        std::lock_guard<std::mutex> lk(mu);
+        if (++arrived == G) {
+            error_rate = hs::error_rate_as_stage4_reads_it(hs::job_error_rate(md.data(), (int)md.size(), nullptr));
+            cv.notify_all();
+        }
+    }
+    void abort() { { std::lock_guard<std::mutex> lk(mu); aborted = true; } cv.notify_all(); }
+    bool wait_for_all(int G) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return arrived == G || aborted; }); return !aborted; }
+};
+
+// one call's state, on the caller's stack
+struct GroupCall {
+    float automatic_snp_threshold, error_rate, rarest_strain_abundance;      // (error_rate: the caller's; the fused call's comes from `meet`)
+    int32_t low_memory, amplicon; uint32_t seed; int per; int32_t window_size;
+    std::vector<hs_sr_result*> parts;
+    std::vector<hs::SrSparseLabels> sparse;      // the groups leave their labels per window; concat_sr_parts spreads them
+    GroupMeeting* meet;      // the fused call only: its groups bring up their own share of the pileup and meet before stage 4
+};
+
+// Group g's chain: the column pass, stage 3's host glue, stage 4 on the columns where stage 3 packed them. Everything is queued
+// on the thread's own stream (the null stream of HipCvOps / HipSrOps under -fgpu-default-stream=per-thread); a low-priority stream
+// for the head of the chain and a high-priority one for the rest was measured in round 4: 24.2 ms per C4 step against 18.6, the
+// low-priority heads are on the critical path of the groups that come later.
+static int pipeline_group_step(hs_pipeline* p, GroupCall& call, int g) {
+    const int c0 = p->ranges[(size_t)g].first, c1 = p->ranges[(size_t)g].second;
+    const int G = (int)p->ranges.size();
+    const int per = call.per;
+    GroupMeeting* const meet = call.meet;
+    hs_cv_result*& cv = p->cv[(size_t)g];
+    const hs::CvMeta& meta = batch_meta(p->batch);
+    HipCvOps cv_ops(p->batch);
+    cv_ops.keep = p->cv_keep[(size_t)g].get(); cv_ops.k2_order = &p->k2_order; cv_ops.order_ticket = g;
+    cv_ops.defer_entries = p->keep_columns;
+    auto fail = [&](int r) { if (meet) meet->abort(); return r; };      // (the two-call form: the worker's k2_order.abort() is all a failing group owes the others)
+    // the SNP columns stay on the device: stage 4 takes them over where stage 3 packed them (HS_COLUMNS_VIA_HOST=1: down and up again)
+    static const bool via_host = std::getenv("HS_COLUMNS_VIA_HOST") != nullptr;
+    const bool resident = !via_host && !p->keep_columns;
+    if (cv) { hs::free_cv_result(cv); cv = nullptr; }      // (the two-call form: the previous call's; the fused call has dropped them all)
+    float error_rate = call.error_rate;
+    if (meet) {
+        // the group's share of the pileup is the head of its column pass on the device (K0, K1, the contigs' distances, K2 ...): one chain,
+        // queued behind the previous group's, no host wait before the candidates
+        cv_ops.own_pileup = true;
+        const std::vector<int32_t> no_stats;
+        const std::function<void(const float*)> on_md = [&](const float* md_g) { meet->arrive(md_g, c0, c1, G); };
+        if (int r = hs::cv_run_range(cv_ops, meta, no_stats, c0, c1, call.automatic_snp_threshold, per, &cv, resident, &on_md)) return fail(r);
+        if (!meet->wait_for_all(G)) { set_error("hs_pipeline_run_fused: another contig group failed"); return HS_EINVAL; }
+        error_rate = meet->error_rate;
+    } else {
+        if (int r = hs::cv_run_range(cv_ops, meta, ((const hs::CvSelection*)p->sel->impl)->rec_stats, c0, c1, call.automatic_snp_threshold, per, &cv, resident)) return r;
+    }
+    HipSrOps ops;
+    ops.keep = &p->sr_dev_keep[(size_t)g];
+    if (!via_host) ops.adopt_columns(cv_ops);
+    if (int r = hs::sr_run_from_cv(ops, meta, c0, c1, cv, error_rate, call.rarest_strain_abundance, call.low_memory, call.amplicon, call.seed, per, call.window_size,
+                                   &call.parts[(size_t)g], &call.sparse[(size_t)g], &p->sr_keep[(size_t)g])) return fail(r);
+    // HS_PIPELINE_KEEP_COLUMNS: the entries came down beside stage 4. The two-call form copies them; the fused call's result points into
+    // the group's pinned block, which stays with the pipeline until its next call
+    const bool borrow = meet != nullptr;
+    if (int r = hs::cv_attach_entries(cv_ops, cv, per, borrow)) return fail(r);
+    if (borrow && cv && cv->entries_borrowed) p->entry_blocks[(size_t)g]->take(cv_ops.h_pk);
+    return HS_OK;
+}
+
 int hs_pipeline_run(hs_pipeline* p, float automatic_snp_threshold, float error_rate, float rarest_strain_abundance, int32_t low_memory,
                     int32_t amplicon, uint32_t seed, int32_t n_threads, int32_t window_size, hs_sr_result** out, hs_pipeline_stats* st) {
     if (!p || !out || !p->sel) { set_error("hs_pipeline_run: run hs_pipeline_select first"); return HS_EINVAL; }
     if (int rc = bind_device(p->batch->device)) return rc;
     const int G = (int)p->ranges.size();
-    // n_threads <= 0: three workers per usable core over all groups -- a group is on the host for part of its chain only (the
-    // rest it waits for the device), so that many threads keep the cores busy without queueing behind each other (500-contig
-    // bench, 16 usable cores: 16 threads 74 ms per step, 32: 46, 48: 44, 64: 47, 128: 51)
-    if (n_threads <= 0) n_threads = 3 * host_threads();
-    const int per = std::max(1, n_threads / G);
-    if (window_size <= 0) {
-        // choose the window size over the WHOLE batch (separate_reads.cpp:1466-1498 looks at every read of every contig): READ
-        // limits are (POS-1, POS + reference span) (input_output.cpp:503-511), `int sumLength` wraps
-        const hs_cv_batch* b = p->batch;
-        if (amplicon) { window_size = 0; for (int c = 0; c < b->n_contigs; ++c) window_size = std::max<int32_t>(window_size, (int32_t)(b->contig_off[(size_t)c + 1] - b->contig_off[(size_t)c])); }
-        else {
-            uint32_t sum = 0; int above = 0;
-            for (int64_t v : b->rec_refspan) { const int len = (int)v + 2; sum += (uint32_t)len; above += len > 4000; }
-            const double mean = b->rec_refspan.empty() ? 4000.0 : (int32_t)sum / double(b->rec_refspan.size());
-            window_size = 2000;
-            if (above < 20 && mean < 4000 && mean > 2000) window_size = 1000;
-            else if (above < 20 && mean < 2000) window_size = 500;
-        }
-    }
-    std::vector<hs_sr_result*> parts((size_t)G, nullptr);
-    std::vector<hs::SrSparseLabels> sparse((size_t)G);      // the groups leave their labels per window; concat_sr_parts spreads them
+    if (window_size <= 0) window_size = pipeline_window_size(p->batch, amplicon != 0);
+    GroupCall call{automatic_snp_threshold, error_rate, rarest_strain_abundance, low_memory, amplicon, seed, pipeline_threads_per_group(n_threads, G), window_size,
+                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), nullptr};
     hs::set_trace_origin();
     p->k2_order.reset();
-    const int rc = p->run([&](int g) {
-        const int c0 = p->ranges[(size_t)g].first, c1 = p->ranges[(size_t)g].second;
-        const hs::CvMeta& meta = batch_meta(p->batch);
-        HipCvOps cv_ops(p->batch);
-        cv_ops.keep = p->cv_keep[(size_t)g].get(); cv_ops.k2_order = &p->k2_order; cv_ops.order_ticket = g;
-        cv_ops.stream = p->s_lo[(size_t)g]; cv_ops.stream_late = p->s_hi[(size_t)g];
-        cv_ops.defer_entries = p->keep_columns;
-        // the SNP columns stay on the device: stage 4 takes them over where stage 3 packed them (HS_COLUMNS_VIA_HOST=1: down and up again)
-        static const bool via_host = std::getenv("HS_COLUMNS_VIA_HOST") != nullptr;
-        if (p->cv[(size_t)g]) { hs::free_cv_result(p->cv[(size_t)g]); p->cv[(size_t)g] = nullptr; }
-        if (int r = hs::cv_run_range(cv_ops, meta, ((const hs::CvSelection*)p->sel->impl)->rec_stats, c0, c1, automatic_snp_threshold, per, &p->cv[(size_t)g], !via_host && !p->keep_columns)) return r;
-        HipSrOps ops;
-        ops.keep = &p->sr_dev_keep[(size_t)g];
-        ops.stream = p->s_hi[(size_t)g];
-        if (!via_host) ops.adopt_columns(cv_ops);
-        if (int r = hs::sr_run_from_cv(ops, meta, c0, c1, p->cv[(size_t)g], error_rate, rarest_strain_abundance, low_memory, amplicon, seed, per, window_size,
-                                       &parts[(size_t)g], &sparse[(size_t)g], &p->sr_keep[(size_t)g])) return r;
-        return hs::cv_attach_entries(cv_ops, p->cv[(size_t)g], per);      // (HS_PIPELINE_KEEP_COLUMNS: the entries came down beside stage 4)
-    });
-    if (rc) { for (hs_sr_result* r : parts) if (r) hs::free_sr_result(r); return rc; }
-    if (st) {
-        for (int g = 0; g < G; ++g) {
-            const hs_cv_result* r = p->cv[(size_t)g];
-            st->n_snps += r->snp_off[r->n_contigs];
-            st->t_device_ms += r->t_device_ms; st->t_host_ms += r->t_host_ms;
-            st->t_kernel_cv_ms[2] += r->t_kernel_ms[2]; st->t_kernel_k4_ms += r->t_kernel_k4_ms;
-            st->n_columns_extracted += r->n_columns_extracted; st->n_columns_downloaded += r->n_columns_downloaded;
-            st->n_columns_downloaded_late += r->n_columns_downloaded_late;
-            st->t_kernel_cv_ms[1] += r->t_kernel_ms[1];
-        }
-    }
+    const int rc = p->run([&](int g) { return pipeline_group_step(p, call, g); });
+    if (rc) { for (hs_sr_result* r : call.parts) if (r) hs::free_sr_result(r); return rc; }
+    if (st) fold_cv_stats(st, p);      // (on top of what hs_pipeline_select wrote)
     if (std::getenv("HS_TIMING")) std::fprintf(stderr, "[hs timing] host waits so far: %ld, %.1f ms in them\n", g_waits.load(), g_wait_us.load() / 1e3);
-    hs_sr_result* R = concat_sr_parts(p, parts, sparse, st);
-    *out = R;      // (the groups' stage-3 results stay until the next call: hs_pipeline_group_cv)
+    *out = concat_sr_parts(p, call.parts, call.sparse, st);      // (the groups' stage-3 results stay until the next call: hs_pipeline_group_cv)
     return HS_OK;
 }
 
 // hs_pipeline_select + the error rate + hs_pipeline_run in ONE call for a job that lives in one process: every contig group brings
 // up its own share of the pileup (one group at a time on the device), so its host work starts a quarter of a millisecond into the
-// step instead of after the pileup of the whole batch; the job-wide error rate (call_variants.cpp:1312-1315: float sum of the
-// positive per-contig mean distances in contig order, then what hairsplitter.py makes of the printed value: %g, capped at 0.15,
-// hairsplitter.py:686-692,725) is formed when the last group has its counters, which is long before the first one needs it for
-// stage 4. mean_distance [n_contigs] and error_rate_out (optional) receive what hs_pipeline_select would have returned / what
-// the caller would have computed.
+// step instead of after the pileup of the whole batch; the job-wide error rate (hs_job_rules.h: job_error_rate, then what
+// hairsplitter.py makes of the printed value) is formed when the last group has its counters (GroupMeeting). mean_distance
+// [n_contigs] and error_rate_out (optional) receive what hs_pipeline_select would have returned / what the caller would have computed.
 int hs_pipeline_run_fused(hs_pipeline* p, float automatic_snp_threshold, float rarest_strain_abundance, int32_t low_memory, int32_t amplicon, uint32_t seed,
                           int32_t n_threads, int32_t window_size, float* mean_distance, float* error_rate_out, hs_sr_result** out, hs_pipeline_stats* st) {
     if (!p || !out) { set_error("hs_pipeline_run_fused: null argument"); return HS_EINVAL; }
     if (int rc = bind_device(p->batch->device)) return rc;
     timing_next_step();
-    hs_cv_batch* b = p->batch;
     const int G = (int)p->ranges.size();
-    const int C = b->n_contigs;
-    if (n_threads <= 0) n_threads = 3 * host_threads();
-    const int per = std::max(1, n_threads / G);
-    if (window_size <= 0) {
-        if (amplicon) { window_size = 0; for (int c = 0; c < C; ++c) window_size = std::max<int32_t>(window_size, (int32_t)(b->contig_off[(size_t)c + 1] - b->contig_off[(size_t)c])); }
-        else {
-            uint32_t sum = 0; int above = 0;
-            for (int64_t v : b->rec_refspan) { const int len = (int)v + 2; sum += (uint32_t)len; above += len > 4000; }
-            const double mean = b->rec_refspan.empty() ? 4000.0 : (int32_t)sum / double(b->rec_refspan.size());
-            window_size = 2000;
-            if (above < 20 && mean < 4000 && mean > 2000) window_size = 1000;
-            else if (above < 20 && mean < 2000) window_size = 500;
-        }
-    }
+    const int C = p->batch->n_contigs;
+    if (window_size <= 0) window_size = pipeline_window_size(p->batch, amplicon != 0);
     static const bool timing_abs = std::getenv("HS_TIMING") != nullptr && std::string(std::getenv("HS_TIMING")) == "abs";
     const double t_enter = timing_abs ? hs::trace_ms() : 0;      // (relative to the previous call's origin: the time between two calls)
     p->drop_cv();
-    hs::CvSelection* sel = new hs::CvSelection();
-    for (int k = 0; k < 4; ++k) sel->k_ms[k] = 0;
-    p->sel = (hs_cv_selection*)std::calloc(1, sizeof(hs_cv_selection));
-    p->sel->impl = sel;
-    std::vector<float> md((size_t)std::max(C, 1), 0.f);
-    std::vector<std::array<float, 4>> k_ms_g((size_t)G, std::array<float, 4>{0, 0, 0, 0});
-    // the meeting point of the groups before stage 4
-    std::mutex bm; std::condition_variable bcv;
-    int arrived = 0; bool aborted = false;
-    float error_rate = 0;
-    std::vector<hs_sr_result*> parts((size_t)G, nullptr);
-    std::vector<hs::SrSparseLabels> sparse((size_t)G);
+    p->sel = (hs_cv_selection*)std::calloc(1, sizeof(hs_cv_selection));      // (an empty selection: a two-call run may follow only after its own select)
+    p->sel->impl = new hs::CvSelection();
+    GroupMeeting meet;
+    meet.md.assign((size_t)C, 0.f);
+    GroupCall call{automatic_snp_threshold, 0.f, rarest_strain_abundance, low_memory, amplicon, seed, pipeline_threads_per_group(n_threads, G), window_size,
+                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), &meet};
     hs::set_trace_origin();
     p->k2_order.reset();
-    const std::vector<int32_t> no_stats;
-    { std::lock_guard<std::mutex> lk(p->mu); p->on_fail = [&] { { std::lock_guard<std::mutex> lk2(bm); aborted = true; } bcv.notify_all(); }; }
-    const int rc = p->run([&](int g) {
-        const int c0 = p->ranges[(size_t)g].first, c1 = p->ranges[(size_t)g].second;
-        const hs::CvMeta& meta = batch_meta(b);
-        HipCvOps cv_ops(b);
-        cv_ops.keep = p->cv_keep[(size_t)g].get(); cv_ops.k2_order = &p->k2_order; cv_ops.order_ticket = g;
-        cv_ops.stream = p->s_lo[(size_t)g]; cv_ops.stream_late = p->s_hi[(size_t)g];
-        cv_ops.defer_entries = p->keep_columns;
-        auto fail = [&](int r) { { std::lock_guard<std::mutex> lk(bm); aborted = true; } bcv.notify_all(); return r; };
-        // the group's mean distances are known (from the host's sums, or with its candidate columns from the device): the last group
-        // to get here forms the job's error rate
-        auto arrive = [&](const float* md_g) {
-            std::memcpy(md.data() + c0, md_g, (size_t)(c1 - c0) * sizeof(float));
-            std::lock_guard<std::mutex> lk(bm);
-            if (++arrived == G) {
-                float total = 0; int n = 0;
-                for (int c = 0; c < C; ++c) if (md[(size_t)c] > 0) { total += md[(size_t)c]; n++; }      // :1312-1315, contig order
-                const float er32 = total / n;
-                char buf[64];
-                std::snprintf(buf, sizeof buf, "%g", (double)er32);      // what stage 3 prints and hairsplitter.py reads back
-                double e = std::strtod(buf, nullptr);
-                if (e > 0.15) e = 0.15;
-                error_rate = (float)e;
-                bcv.notify_all();
-            }
-        };
-        static const bool via_host = std::getenv("HS_COLUMNS_VIA_HOST") != nullptr;
-        // the group's share of the pileup is the head of its column pass on the device (K0, K1, the contigs' distances, K2 ...): one chain,
-        // queued behind the previous group's, no host wait before the candidates
-        cv_ops.own_pileup = true;
-        const std::function<void(const float*)> on_md = arrive;
-        if (int r = hs::cv_run_range(cv_ops, meta, no_stats, c0, c1, automatic_snp_threshold, per, &p->cv[(size_t)g], !via_host && !p->keep_columns, &on_md)) return fail(r);
-        {
-            std::unique_lock<std::mutex> lk(bm);
-            bcv.wait(lk, [&] { return arrived == G || aborted; });
-            if (aborted) { set_error("hs_pipeline_run_fused: another contig group failed"); return HS_EINVAL; }
-        }
-        HipSrOps ops;
-        ops.keep = &p->sr_dev_keep[(size_t)g];
-        ops.stream = p->s_hi[(size_t)g];
-        if (!via_host) ops.adopt_columns(cv_ops);
-        int r = hs::sr_run_from_cv(ops, meta, c0, c1, p->cv[(size_t)g], error_rate, rarest_strain_abundance, low_memory, amplicon, seed, per, window_size,
-                                   &parts[(size_t)g], &sparse[(size_t)g], &p->sr_keep[(size_t)g]);
-        if (!r) {      // (HS_PIPELINE_KEEP_COLUMNS: the entries came down beside stage 4; the result points into the group's pinned block, which stays with the pipeline until its next call)
-            r = hs::cv_attach_entries(cv_ops, p->cv[(size_t)g], per, true);
-            if (!r && p->cv[(size_t)g] && p->cv[(size_t)g]->entries_borrowed) p->entry_blocks[(size_t)g]->take(cv_ops.h_pk);
-        }
-        return r ? fail(r) : r;
-    });
+    // a group that is gone (its job failed, or its thread never bound to the device) releases whoever waits for it at the meeting point
+    { std::lock_guard<std::mutex> lk(p->mu); p->on_fail = [&meet] { meet.abort(); }; }
+    const int rc = p->run([&](int g) { return pipeline_group_step(p, call, g); });
     { std::lock_guard<std::mutex> lk(p->mu); p->on_fail = nullptr; }
-    if (rc) { for (hs_sr_result* r : parts) if (r) hs::free_sr_result(r); return rc; }
-    if (mean_distance) std::memcpy(mean_distance, md.data(), (size_t)C * sizeof(float));
-    if (error_rate_out) *error_rate_out = error_rate;
-    if (st) {
-        std::memset(st, 0, sizeof *st);
-        for (int g = 0; g < G; ++g) {
-            st->t_kernel_cv_ms[0] += k_ms_g[(size_t)g][0]; st->t_kernel_cv_ms[3] += k_ms_g[(size_t)g][3];
-            const hs_cv_result* r = p->cv[(size_t)g];
-            st->n_snps += r->snp_off[r->n_contigs];
-            st->t_device_ms += r->t_device_ms; st->t_host_ms += r->t_host_ms;
-            st->t_kernel_cv_ms[2] += r->t_kernel_ms[2]; st->t_kernel_k4_ms += r->t_kernel_k4_ms;
-            st->n_columns_extracted += r->n_columns_extracted; st->n_columns_downloaded += r->n_columns_downloaded;
-            st->n_columns_downloaded_late += r->n_columns_downloaded_late;
-            st->t_kernel_cv_ms[1] += r->t_kernel_ms[1];
-        }
-    }
+    if (rc) { for (hs_sr_result* r : call.parts) if (r) hs::free_sr_result(r); return rc; }
+    if (mean_distance && C) std::memcpy(mean_distance, meet.md.data(), (size_t)C * sizeof(float));
+    if (error_rate_out) *error_rate_out = meet.error_rate;
+    if (st) { std::memset(st, 0, sizeof *st); fold_cv_stats(st, p); }      // (t_kernel_cv_ms[0] and [3], the pileup's own, stay 0: nothing times it apart from the chain)
     const double t_run = timing_abs ? hs::trace_ms() : 0;
-    hs_sr_result* R = concat_sr_parts(p, parts, sparse, st);
-    *out = R;
+    *out = concat_sr_parts(p, call.parts, call.sparse, st);
     { static const bool ps = std::getenv("HS_POOL_STATS") != nullptr; if (ps) std::fprintf(stderr, "[hs pools] device blocks allocated so far %ld, pinned %ld\n", g_pool_miss_dev.load(), g_pool_miss_host.load()); }
     if (timing_abs) std::fprintf(stderr, "[hs timing] fused call: entered @%.2f of the previous call's clock, groups done @%.2f, results merged @%.2f\n", t_enter, t_run, hs::trace_ms());
     return HS_OK;

@@ -1,6 +1,7 @@
 // hs_driver.cpp -- stage drivers: order of device launches and host glue for HS_call_variants and
 // HS_separate_reads, independent of how the device interface is implemented (see hs_driver.h).
 #include "hs_driver.h"
+#include "hs_job_rules.h"
 
 #include <sys/prctl.h>
 #include <algorithm>
@@ -431,10 +432,8 @@ int cv_run_range(CvDeviceOps& dev, const CvMeta& b, const std::vector<int32_t>& 
     R->n_contigs = C;
     std::vector<float> md((size_t)C), dp((size_t)C);
     std::vector<int64_t> snp_off((size_t)C + 1, 0);
-    float total_error = 0; int n_err_contigs = 0;
     for (int c = 0; c < C; ++c) {
         md[(size_t)c] = res[(size_t)c].mean_distance; dp[(size_t)c] = res[(size_t)c].depth;
-        if (res[(size_t)c].mean_distance > 0) { total_error += res[(size_t)c].mean_distance; n_err_contigs++; }   // call_variants.cpp:1312-1315
         snp_off[(size_t)c + 1] = snp_off[(size_t)c] + snps.contig_n_snp[(size_t)c];
     }
     const int64_t S = snps.n_snp, E = snps.n_entries;
@@ -471,8 +470,7 @@ int cv_run_range(CvDeviceOps& dev, const CvMeta& b, const std::vector<int32_t>& 
     }
     laps.lap("result");
     R->mean_distance = dup_vec(md); R->depth = dup_vec(dp); R->snp_off = dup_vec(snp_off);
-    R->error_rate = total_error / n_err_contigs;      // call_variants.cpp:1377 (float / int)
-    R->n_contigs_with_error_rate = n_err_contigs;
+    R->error_rate = job_error_rate(md.data(), C, &R->n_contigs_with_error_rate);
     R->t_kernel_ms[0] = k_ms[0]; R->t_kernel_ms[1] = k_ms[1]; R->t_kernel_ms[2] = k_ms[2]; R->t_kernel_ms[3] = k_ms[3]; R->t_kernel_k4_ms = k_ms_k4;
     R->t_device_ms = t_dev_done - t_start;
     R->t_host_ms = now_ms() - t_dev_done;
@@ -523,12 +521,10 @@ hs_cv_result* cv_concat_results(hs_cv_result* a, hs_cv_result* b) {
     const bool with_entries = (a->col_idx || Ea == 0) && (b->col_idx || Eb == 0);
     R->col_idx = with_entries ? (int32_t*)std::malloc(std::max<int64_t>(1, E) * sizeof(int32_t)) : nullptr;
     R->col_code = with_entries ? (uint8_t*)std::malloc(std::max<int64_t>(1, E)) : nullptr;
-    float total_error = 0; int n_err = 0;
     auto put = [&](const hs_cv_result* r, int cbase, int64_t sbase, int64_t ebase) {
         const int Cr = r->n_contigs; const int64_t Sr = r->snp_off[Cr], Er = r->col_off[Sr];
         for (int c = 0; c < Cr; ++c) {
             R->mean_distance[cbase + c] = r->mean_distance[c]; R->depth[cbase + c] = r->depth[c];
-            if (r->mean_distance[c] > 0) { total_error += r->mean_distance[c]; n_err++; }
             R->snp_off[cbase + c] = sbase + r->snp_off[c];
         }
         if (Sr) {
@@ -544,7 +540,7 @@ hs_cv_result* cv_concat_results(hs_cv_result* a, hs_cv_result* b) {
     };
     put(a, 0, 0, 0); put(b, Ca, Sa, Ea);
     R->snp_off[C] = S; R->col_off[S] = E;
-    R->error_rate = total_error / n_err; R->n_contigs_with_error_rate = n_err;
+    R->error_rate = job_error_rate(R->mean_distance, C, &R->n_contigs_with_error_rate);
     free_cv_result(a); free_cv_result(b);
     return R;
 }

@@ -8,6 +8,7 @@
 // (cluster_graph.cpp:402-501) and merge_wrongly_split_haplotypes (separate_reads.cpp:1007-1327).
 #include "hs_host_sr.h"
 #include "hs_rh8.h"
+#include "hs_job_rules.h"
 
 #include <algorithm>
 #include <atomic>
@@ -476,20 +477,11 @@ bool sr_ploidy_init_labels(const SrWindowPlan& w, int max_haplotypes, int32_t* o
 
 // choosing the window size: separate_reads.cpp:1466-1498
 int32_t sr_window_size(const hs_sr_contig* cs, int n, bool amplicon) {
-    int reads = 0, above4000 = 0;
-    uint32_t sum = 0;   // `int sumLength` in the reference; wraps the same way
+    if (amplicon) { int w = 0; for (int i = 0; i < n; ++i) w = std::max(w, (int)cs[i].length); return w; }
+    uint32_t sum = 0; int64_t reads = 0, above4000 = 0;
     for (int i = 0; i < n; ++i)
-        for (int r = 0; r < cs[i].n_reads; ++r) {
-            const int len = cs[i].read_end[r] - cs[i].read_start[r] + 1;
-            reads++; sum += (uint32_t)len;
-            if (len > 4000) above4000++;
-        }
-    const double mean = (int32_t)sum / double(reads);
-    int w = 2000;
-    if (above4000 < 20 && mean < 4000 && mean > 2000) w = 1000;
-    else if (above4000 < 20 && mean < 2000) w = 500;
-    if (amplicon) { w = 0; for (int i = 0; i < n; ++i) w = std::max(w, (int)cs[i].length); }
-    return w;
+        for (int r = 0; r < cs[i].n_reads; ++r) window_size_count_read(cs[i].read_end[r] - cs[i].read_start[r] + 1, sum, reads, above4000);
+    return window_size_from_counts(sum, reads, above4000);
 }
 
 // coverage test of separate_reads.cpp:1476-1481,1516: float accumulation in read order

@@ -15,6 +15,7 @@
 
 #include "hs_host.h"
 #include "hs_driver.h"
+#include "hs_job_rules.h"
 
 namespace {
 
@@ -160,7 +161,7 @@ extern "C" int hs_call_variants_main(int argc, char** argv) {
     if (res->col_idx || res->col_off[res->snp_off[C]] == 0) {      // the stage's outputs are complete: what may follow is hs_call_variants_epilogue
         // (HS_NO_PRECOMPUTE, or no sidecar: no companion, and no stage 4 behind this stage's back either)
         float er = 0; bool er_ok = false;
-        { std::ifstream f(error_rate_out); std::string t; if (f >> t) { double e = std::strtod(t.c_str(), nullptr); if (e > 0.15) e = 0.15; er = (float)e; er_ok = true; } }
+        { std::ifstream f(error_rate_out); std::string t; if (f >> t) { er = hs::error_rate_from_text(t.c_str()); er_ok = true; } }
         g_pending_gro.col = file_out; g_pending_gro.err = error_rate_out; g_pending_gro.amplicon = amplicon_i != 0; g_pending_gro.threads = num_threads;
         g_pending_gro.on = er_ok && hs::mark_gro_companion_pending(file_out, er, (float)std::atof("0.01"), false, amplicon_i != 0, stage4_seed());
     }
@@ -205,7 +206,7 @@ extern "C" void hs_call_variants_epilogue(void) {
     StageClock clk;
     try {
         float er = 0;
-        { std::ifstream f(g_pending_gro.err); std::string t; if (!(f >> t)) { hs::remove_gro_companion(col); return; } double e = std::strtod(t.c_str(), nullptr); if (e > 0.15) e = 0.15; er = (float)e; }
+        { std::ifstream f(g_pending_gro.err); std::string t; if (!(f >> t)) { hs::remove_gro_companion(col); return; } er = hs::error_rate_from_text(t.c_str()); }
         const float rsa = (float)std::atof("0.01");
         std::vector<hs::ColFileContig>* cs_p = new std::vector<hs::ColFileContig>();      // (left to the process end like everything else of the executable)
         if (hs::read_col_sidecar(col, rsa, *cs_p, nt) != 1) { hs::remove_gro_companion(col); return; }

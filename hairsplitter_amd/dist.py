@@ -48,7 +48,7 @@ def global_window_size(local_rec_refspan: np.ndarray, amplicon: bool = False, lo
     import torch
     import torch.distributed as dist
     lens = np.asarray(local_rec_refspan, dtype=np.int64) + 2
-    v = torch.tensor([int(lens.sum()), int(lens.size), int((lens > 4000).sum())], dtype=torch.int64)
+    v = torch.tensor(window_size_counts(lens), dtype=torch.int64)
     mx = torch.tensor([int(longest_contig)], dtype=torch.int64)
     if dist.is_available() and dist.is_initialized():
         dev = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
@@ -58,7 +58,21 @@ def global_window_size(local_rec_refspan: np.ndarray, amplicon: bool = False, lo
         v = v.cpu(); mx = mx.cpu()
     if amplicon:
         return int(mx.item())
-    total, n, above = int(v[0]), int(v[1]), int(v[2])
+    return window_size_from_counts(int(v[0]), int(v[1]), int(v[2]))
+
+
+# ---------------------------------------------------------------------------------------------
+# The reference's rules over a whole job, each stated once on this side (csrc/hs_job_rules.h states them for the library;
+# tests/test_cpu_rules.py holds the two to each other bit for bit).
+# ---------------------------------------------------------------------------------------------
+def window_size_counts(lens: np.ndarray):
+    """(sum of the read lengths, reads, reads above 4 kb): what choose_window_size needs of a set of reads"""
+    return int(lens.sum()), int(lens.size), int((lens > 4000).sum())
+
+
+def window_size_from_counts(total: int, n: int, above: int) -> int:
+    """separate_reads.cpp:1466-1498 from the counts over every read of the job; `total` wraps as the reference's `int sumLength`
+    does. No read at all: the reference's mean is 0 / 0.0, a NaN, which fails every comparison: 2000."""
     if n == 0:
         return 2000
     total &= 0xFFFFFFFF
@@ -80,6 +94,12 @@ def mean_of_positive_f32(values) -> float:
     if v.size == 0:
         return float("nan")
     return float(np.float32(np.cumsum(v, dtype=np.float32)[-1] / np.float32(v.size)))
+
+
+def stage4_error_rate(e: float) -> float:
+    """What hairsplitter.py makes of the error rate stage 3 printed (hairsplitter.py:686-692,725): six significant digits (%g),
+    read back, capped at 0.15. A NaN stays one (min keeps its first argument when the comparison fails)."""
+    return min(float("%g" % e), 0.15)
 
 
 def gather_capacity(local_n: int, group=None) -> int:

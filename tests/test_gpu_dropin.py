@@ -449,6 +449,57 @@ def test_pipeline_group_threads_run_on_the_device_of_their_batch(built):
         pg.close()
 
 
+def test_pipeline_calls_agree_on_window_size_statistics_and_reuse(built):
+    """The two-call form and the fused call run ONE contig-group step: the window size they choose for window_size=0 is
+    PipelineGroups.window_size(); the statistics differ only where the calls do (the pileup's own kernel times: hs_pipeline_select
+    reports them, the fused call has none); and either call may follow the other on the same pipeline, kept columns or not. More groups
+    are asked for than there are contigs (the pipeline settles on one contig per group)."""
+    import ctypes as C
+    from hairsplitter_amd import api, synth
+    lib = api.load()
+    contigs = [synth.make_contig(3, k, 6000, 2, 0.01, 20, "ont") for k in range(4)]
+    pg = api.PipelineGroups(contigs, 6)
+
+    def same(a, b):
+        return (a[0]["n_snps"] == b[0]["n_snps"] and np.array_equal(a[0]["mean_distance"], b[0]["mean_distance"]) and np.array_equal(a[1]["labels"], b[1]["labels"])
+                and np.array_equal(a[1]["win_start"], b[1]["win_start"]) and np.array_equal(a[1]["win_end"], b[1]["win_end"]))
+    try:
+        assert lib.hs_pipeline_groups(pg.handle) == 4
+        # 1. the window size
+        for amplicon in (False, True):
+            w = pg.window_size(amplicon)
+            assert w in (500, 1000, 2000) if not amplicon else w == int(np.diff(pg.flat.contig_off).max()) > 2000
+            for call in (pg.run, pg.run_fused):
+                chosen, given = call(0.33, 8, amplicon=amplicon, window_size=0), call(0.33, 8, amplicon=amplicon, window_size=w)
+                assert chosen[0]["n_snps"] > 0 and len(chosen[1]["win_start"]) > 0
+                assert same(chosen, given)
+        # 2. the statistics: hs_pipeline_run adds to what hs_pipeline_select wrote, the fused call starts from zero
+        md = np.zeros(4, np.float32)
+        st = api.PipelineStats()
+        api._check(lib.hs_pipeline_select(pg.handle, api._hp(md, C.c_float), C.byref(st)))
+        selected = [float(st.t_kernel_cv_ms[0]), float(st.t_kernel_cv_ms[3])]
+        assert min(selected) >= 0
+        sres = C.POINTER(api.SrResult)()
+        api._check(lib.hs_pipeline_run(pg.handle, C.c_float(0.33), C.c_float(0.05), C.c_float(0.01), C.c_int32(0), C.c_int32(0), C.c_uint32(12345), C.c_int32(8),
+                                       C.c_int32(0), C.byref(sres), C.byref(st)))
+        lib.hs_sr_result_destroy(sres)
+        assert [float(st.t_kernel_cv_ms[0]), float(st.t_kernel_cv_ms[3])] == selected
+        two, fused = pg.run(0.33, 8), pg.run_fused(0.33, 8)
+        assert two[0]["t_kernel_ms"][0] >= 0 and two[0]["t_kernel_ms"][3] >= 0
+        assert fused[0]["t_kernel_ms"][0] == 0.0 and fused[0]["t_kernel_ms"][3] == 0.0
+        for k in ("n_columns_extracted", "n_columns_downloaded", "n_snps"):
+            assert two[0][k] == fused[0][k] and two[0][k] > 0, k
+        # 3. one call after the other on the same pipeline: the fused call's borrowed entry blocks and dropped results, the two-call
+        # form's own, and the fused call again with the columns kept
+        first = pg.run_fused(0.33, 8)
+        second = pg.run(0.33, 8)
+        pg.keep_columns(True)
+        third = pg.run_fused(0.33, 8)
+        assert same(first, second) and same(first, third) and same(first, two)
+    finally:
+        pg.close()
+
+
 def test_killing_the_dropin_leaves_no_worker_behind(built):
     """The executables do their work in a forked child (hs_dropin_main.h). A caller that kills the process it started must not
     leave that child holding the GPU and writing the outputs: SIGTERM is passed on, and the child dies with its parent."""
