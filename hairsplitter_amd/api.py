@@ -29,6 +29,7 @@ SYMBOLS = [
     "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_edlib_align", "hs_edlib_align_bytes", "hs_alignment_to_cigar", "hs_reattach_ends", "hs_trim_polished", "hs_reattach_ends_bytes", "hs_trim_polished_bytes", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
     "hs_polish_inputs", "hs_polish_inputs_from_files", "hs_polish_result_destroy", "hs_polish_inputs_main",
     "hs_moves_to_cigar", "hs_realign_intervals", "hs_realign_records_destroy", "hs_cv_batch_create_paf", "hs_cv_batch_create_sam",
+    "hs_allele_table_destroy", "hs_alleles_text", "hs_alleles_lds_capacity", "hs_group_alleles_layout", "hs_group_alleles", "hs_haplotype_alleles", "hs_pipeline_alleles",
 ]
 
 HS_NKERNELS = 28
@@ -67,6 +68,25 @@ class SrResult(C.Structure):
                 ("t_kernel_ms", C.c_float * 4), ("t_kernel_graph_ms", C.c_float), ("n_graph_rows_host", C.c_int64), ("n_windows_finished_on_host", C.c_int64),
                 ("n_cw_sweeps", C.c_int64), ("cw_bytes", C.c_int64), ("graph_nnz", C.c_int64), ("n_graph_rows", C.c_int64), ("simdiff_bytes", C.c_int64)]
 
+
+class AlleleTable(C.Structure):
+    """hs_allele_table"""
+    _fields_ = [("n_windows", C.c_int64), ("n_snps", C.c_int64), ("n_groups", C.c_int64), ("n_cells", C.c_int64),
+                ("win_contig", C.POINTER(C.c_int32)), ("win_start", C.POINTER(C.c_int32)), ("win_end", C.POINTER(C.c_int32)),
+                ("win_group_off", C.POINTER(C.c_int64)), ("group_ids", C.POINTER(C.c_int32)), ("win_snp_off", C.POINTER(C.c_int64)),
+                ("snp_contig", C.POINTER(C.c_int32)), ("snp_pos", C.POINTER(C.c_int32)), ("snp_ref", C.POINTER(C.c_uint8)), ("snp_alt", C.POINTER(C.c_uint8)),
+                ("snp_n_calls", C.POINTER(C.c_int32)), ("snp_cell_off", C.POINTER(C.c_int64)), ("cells", C.c_void_p),
+                ("t_kernel_ms", C.c_double), ("n_entries", C.c_int64), ("n_wide_columns", C.c_int64)]
+
+
+class AlleleLayout(C.Structure):
+    """hs_allele_layout: byte offsets of the parts of hs_group_alleles' work buffer"""
+    _fields_ = [(k, C.c_int64) for k in ("snp_win", "grp_n", "win_snp_first", "win_snp_last", "cell_off", "grp_off", "n_calls", "grp_ids", "grp_pack",
+                                         "internal", "total_bytes")]
+
+
+# hs_allele_cell (12 bytes)
+ALLELE_CELL = np.dtype([("n", "<u2"), ("best", "<u2"), ("second", "<u2"), ("n_ref", "<u2"), ("n_alt", "<u2"), ("best_code", "u1"), ("call", "u1")])
 
 _lib = None
 
@@ -121,6 +141,12 @@ def load() -> C.CDLL:
     lib.hs_kernel_stats_get.restype = None
     lib.hs_kernel_stats_get.argtypes = [C.POINTER(KernelStats)]
     lib.hs_realign_records_destroy.restype = None
+    lib.hs_allele_table_destroy.restype = None
+    lib.hs_allele_table_destroy.argtypes = [C.c_void_p]
+    lib.hs_pipeline_alleles.restype = C.POINTER(AlleleTable)
+    lib.hs_pipeline_alleles.argtypes = [C.c_void_p]
+    lib.hs_haplotype_alleles.argtypes = [C.POINTER(SrContig), C.c_int32, C.POINTER(SrResult), C.POINTER(C.POINTER(AlleleTable))]
+    lib.hs_alleles_lds_capacity.restype = C.c_int32
     _lib = lib
     return lib
 
@@ -484,7 +510,18 @@ class PipelineGroups:
         _check(load().hs_pipeline_set_option(self.handle, C.c_int32(2), C.c_int64(1 if on else 0)))
         self._sparse = bool(on)
 
+    def alleles(self, on=True):
+        """HS_PIPELINE_ALLELES: every call also returns sr["alleles"], the allele table of the call (a copy), formed by every contig group at the
+        end of its own chain from the SNP columns on the device. HS_PIPELINE_KEEP_COLUMNS is not needed."""
+        _check(load().hs_pipeline_set_option(self.handle, C.c_int32(4), C.c_int64(1 if on else 0)))
+        self._alleles = bool(on)
+
     def _attach_sparse(self, sr):
+        if getattr(self, "_alleles", False):
+            tb = load().hs_pipeline_alleles(self.handle)
+            if not tb:
+                raise HsError("hs_pipeline_alleles: no table")
+            sr["alleles"] = _allele_table_to_dict(tb)
         if not getattr(self, "_sparse", False):
             return sr
         off, ids, lab = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
@@ -735,8 +772,9 @@ def _owned_view_i32(res, ptr, n):
 
 def separate_reads(cv_out: Dict, flat: FlatBatch, error_rate: float, low_memory: bool = False, amplicon: bool = False,
                    seed: int = 12345, n_threads: int = 0, ploidy: Optional[Sequence[int]] = None,
-                   rarest_strain_abundance: float = 0.0, window_size: Optional[int] = None, taps: bool = False) -> Dict:
-    """(taps=True: through hs_sr_run_taps -- out["taps"] holds what the kernels of the clustering chain left, out["contigs"] the per-contig
+                   rarest_strain_abundance: float = 0.0, window_size: Optional[int] = None, taps: bool = False, alleles: bool = False) -> Dict:
+    """(alleles=True: out["alleles"] = the allele table of the call, hs_haplotype_alleles on its labels and the SNPs it kept.)
+    (taps=True: through hs_sr_run_taps -- out["taps"] holds what the kernels of the clustering chain left, out["contigs"] the per-contig
     inputs as numpy arrays, for the tests. taps="graphs": the call stops behind the read graphs -- separate_reads_graph_taps on the same
     per-contig inputs; out = {"window_size", "contigs", "taps"}.)
     Stage 4 on the in-memory result of stage 3 == HS_separate_reads without the .col round trip
@@ -819,12 +857,143 @@ def separate_reads(cv_out: Dict, flat: FlatBatch, error_rate: float, low_memory:
         "n_cw_sweeps": int(r.n_cw_sweeps), "cw_bytes": int(r.cw_bytes), "graph_nnz": int(r.graph_nnz), "n_graph_rows": int(r.n_graph_rows),
         "simdiff_bytes": int(r.simdiff_bytes),
     }
+    if alleles:      # the allele table of the same call: its labels against the columns stage 4 just read
+        tb = C.POINTER(AlleleTable)()
+        _check(lib.hs_haplotype_alleles(arr, C.c_int32(Cn), res, C.byref(tb)))
+        out["alleles"] = _allele_table_to_dict(tb)
+        lib.hs_allele_table_destroy(tb)
     lib.hs_sr_result_destroy(res)
     if taps:
         out["taps"] = _chain_taps_to_dict(tp.contents)
         out["contigs"] = per_contig
         lib.hs_sr_taps_destroy(tp)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# per-group allele calls at every SNP (hs_allele_table)
+# ------------------------------------------------------------------------------------------------
+def alleles_lds_capacity() -> int:
+    """entries of the deepest column the cell kernel sorts in LDS (deeper ones go through global scratch)"""
+    return int(load().hs_alleles_lds_capacity())
+
+
+def _allele_table_to_dict(tp) -> Dict:
+    """a copy of an hs_allele_table as numpy arrays; "cells" has the dtype ALLELE_CELL"""
+    t = tp.contents
+    W, S, G, N = int(t.n_windows), int(t.n_snps), int(t.n_groups), int(t.n_cells)
+
+    def a(ptr, n, dtype):
+        if n == 0:
+            return np.zeros(0, dtype)
+        return np.ctypeslib.as_array(ptr, (n,)).astype(dtype, copy=True)
+
+    cells = np.zeros(N, ALLELE_CELL)
+    if N:
+        C.memmove(cells.ctypes.data, t.cells, N * ALLELE_CELL.itemsize)
+    return {"win_contig": a(t.win_contig, W, np.int32), "win_start": a(t.win_start, W, np.int32), "win_end": a(t.win_end, W, np.int32),
+            "win_group_off": a(t.win_group_off, W + 1, np.int64), "group_ids": a(t.group_ids, G, np.int32), "win_snp_off": a(t.win_snp_off, W + 1, np.int64),
+            "snp_contig": a(t.snp_contig, S, np.int32), "snp_pos": a(t.snp_pos, S, np.int32), "snp_ref": a(t.snp_ref, S, np.uint8), "snp_alt": a(t.snp_alt, S, np.uint8),
+            "snp_n_calls": a(t.snp_n_calls, S, np.int32), "snp_cell_off": a(t.snp_cell_off, S + 1, np.int64), "cells": cells,
+            "t_kernel_ms": float(t.t_kernel_ms), "n_entries": int(t.n_entries), "n_wide_columns": int(t.n_wide_columns)}
+
+
+def haplotype_alleles(contigs: Sequence[Dict], sr: Dict) -> Dict:
+    """hs_haplotype_alleles: which allele every group of every window carries at every SNP of the window (separate_reads.cpp:1056-1113 on
+    the final labels). contigs: one dict per contig as separate_reads_graph_taps takes them; sr: win_off, win_start, win_end, label_off and dense
+    labels in the layout of a stage-4 result -- that call's own, or any labels (ids need not be 0..G-1)."""
+    require_gpu()
+    lib = load()
+    arr, keep = _sr_contig_array(contigs)
+    Cn = len(contigs)
+    wo, ws, we = _np(sr["win_off"], np.int64), _np(sr["win_start"], np.int32), _np(sr["win_end"], np.int32)
+    lo, lab = _np(sr["label_off"], np.int64), _np(sr["labels"], np.int32)
+    if len(ws) == 0:
+        ws, we = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    if len(lab) == 0:
+        lab = np.zeros(1, np.int32)
+    r = SrResult()
+    r.n_contigs = Cn
+    r.win_off = _hp(wo, C.c_int64); r.win_start = _hp(ws, C.c_int32); r.win_end = _hp(we, C.c_int32)
+    r.label_off = _hp(lo, C.c_int64); r.labels = _hp(lab, C.c_int32)
+    tb = C.POINTER(AlleleTable)()
+    _check(lib.hs_haplotype_alleles(arr, C.c_int32(Cn), C.byref(r), C.byref(tb)))
+    out = _allele_table_to_dict(tb)
+    lib.hs_allele_table_destroy(tb)
+    del keep
+    return out
+
+
+def group_alleles(contigs: Sequence[Dict], sr: Dict) -> Dict:
+    """hs_group_alleles, the kernel-level call, in its two steps on torch tensors (inputs as haplotype_alleles takes them): the plan -- snp_win,
+    grp_n, grp_off, grp_pack, win_snp_first, win_snp_last, cell_off over EVERY window and SNP of the call -- then cells and n_calls."""
+    import torch
+    require_gpu()
+    lib = load()
+    dev = "cuda:0"
+    depth = [np.diff(_np(c["col_off"], np.int64)) for c in contigs]
+    col_off = np.concatenate([[0]] + [d for d in depth]).cumsum().astype(np.int64)
+    def cat(key, dt):      # the contigs' arrays one after the other; column entries from where the contig's col_off begins
+        parts = [_np(c[key], dt)[int(c["col_off"][0]):int(c["col_off"][-1])] if key.startswith("col_") else _np(c[key], dt) for c in contigs]
+        return np.concatenate([np.zeros(0, dt)] + parts).astype(dt)
+
+    snp_contig = np.concatenate([np.zeros(0, np.int32)] + [np.full(len(c["snp_pos"]), k, np.int32) for k, c in enumerate(contigs)]).astype(np.int32)
+    S, W, Cn = len(snp_contig), len(sr["win_start"]), len(contigs)
+    n_labels = int(sr["label_off"][-1])
+    up = lambda a, dt: torch.from_numpy(_np(a, dt) if len(a) else np.zeros(1, dt)).to(dev)
+    d = [up(col_off, np.int64), up(cat("col_idx", np.int32), np.int32), up(cat("col_code", np.uint8), np.uint8), up(cat("snp_ref", np.uint8), np.uint8),
+         up(cat("snp_alt", np.uint8), np.uint8), up(cat("snp_pos", np.int32), np.int32), up(snp_contig, np.int32)]
+    w = [up(sr["win_off"], np.int64), up(sr["win_start"], np.int32), up(sr["win_end"], np.int32)]
+    lab = [up(sr["label_off"], np.int64), up(sr["labels"], np.int32)]
+    L = AlleleLayout()
+    _check(lib.hs_group_alleles_layout(C.c_int32(S), C.c_int32(W), C.c_int64(n_labels), C.byref(L)))
+    work = torch.zeros(int(L.total_bytes), dtype=torch.uint8, device=dev)
+
+    def call(cells, cap):
+        _check(lib.hs_group_alleles(*[_p(x) for x in d], C.c_int32(S), *[_p(x) for x in w], C.c_int32(Cn), C.c_int32(W), *[_p(x) for x in lab], C.c_int64(n_labels),
+                                    _p(work), _p(cells), C.c_int64(cap), C.c_void_p(0)))
+        torch.cuda.synchronize()
+
+    call(None, 0)
+    host = work[:int(L.grp_ids)].cpu().numpy()
+    part = lambda off, n, dt: host[int(off):int(off) + n * np.dtype(dt).itemsize].view(dt).copy()
+    out = {"snp_win": part(L.snp_win, S, np.int32), "grp_n": part(L.grp_n, W, np.int32), "win_snp_first": part(L.win_snp_first, W, np.int32),
+           "win_snp_last": part(L.win_snp_last, W, np.int32), "cell_off": part(L.cell_off, S + 1, np.int64), "grp_off": part(L.grp_off, W + 1, np.int64)}
+    n_groups, n_cells = int(out["grp_off"][-1]), int(out["cell_off"][-1])
+    out["grp_pack"] = work[int(L.grp_pack):int(L.grp_pack) + 4 * n_groups].cpu().numpy().view(np.int32).copy()
+    cells = torch.zeros(max(n_cells, 1) * ALLELE_CELL.itemsize, dtype=torch.uint8, device=dev)
+    call(cells, n_cells)
+    out["cells"] = cells[:n_cells * ALLELE_CELL.itemsize].cpu().numpy().view(ALLELE_CELL).copy()
+    out["n_calls"] = work[int(L.n_calls):int(L.n_calls) + 4 * S].cpu().numpy().view(np.int32).copy()
+    return out
+
+
+def allele_context(code: int) -> str:
+    """the three bases a pileup code stands for (call_variants.cpp:25-31), "." for 0 / no code"""
+    if code < 33 or code >= 33 + 125:
+        return "."
+    v = code - 33
+    return "ACGT-"[(v % 25) // 5] + "ACGT-"[v % 5] + "ACGT-"[v // 25]
+
+
+def alleles_text(table: Dict, names: Optional[Sequence[str]] = None) -> str:
+    """the text HS_separate_reads writes to <outfile>.alleles.tsv under HS_ALLELES=1, from a table of this module"""
+    out = []
+    base = lambda code: "ACGT-"[(code - 33) % 5] if 33 <= code < 158 else "."
+    for w in range(len(table["win_start"])):
+        c = int(table["win_contig"][w])
+        g0, g1 = int(table["win_group_off"][w]), int(table["win_group_off"][w + 1])
+        ids = [int(x) for x in table["group_ids"][g0:g1]]
+        name = names[c] if names is not None and 0 <= c < len(names) else str(c)
+        out.append("WINDOW\t%s\t%d\t%d\t%s\n" % (name, table["win_start"][w], table["win_end"][w], "".join("%d," % g for g in ids)))
+        for s in range(int(table["win_snp_off"][w]), int(table["win_snp_off"][w + 1])):
+            line = "SNP\t%d\t%s\t%s\t%d" % (table["snp_pos"][s], base(int(table["snp_ref"][s])), base(int(table["snp_alt"][s])), table["snp_n_calls"][s])
+            c0 = int(table["snp_cell_off"][s])
+            for k, g in enumerate(ids):
+                x = table["cells"][c0 + k]
+                line += "\t%d:%d:%d:%d:%s" % (g, x["n"], x["n_ref"], x["n_alt"], allele_context(int(x["call"])))
+            out.append(line + "\n")
+    return "".join(out)
 
 
 # ------------------------------------------------------------------------------------------------

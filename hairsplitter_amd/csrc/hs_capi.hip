@@ -4,6 +4,7 @@
 //   hs_capi_kernels.inc  small C ABI + kernel-level entry points
 //   hs_cv_backend.inc    stage 3 on the device (hs_cv_batch, HipCvOps)
 //   hs_sr_backend.inc    stage 4 on the device (GraphRows, HipSrOps)
+//   hs_capi_alleles.inc  the allele table: labels x SNP columns per group (hs_group_alleles, hs_haplotype_alleles, a pipeline group's share)
 //   hs_capi_stage.inc    stage-level C ABI on one device, contig groups (hs_pipeline_*)
 //   hs_capi_multi.inc    several GPUs in one process
 //   hs_capi_polish.inc   the polisher's inputs of the next stage (hs_polish_inputs)
@@ -43,6 +44,7 @@
 #include "hs_kernels_loopa.hip"
 #include "hs_kernels_polish.hip"
 #include "hs_kernels_realign.hip"
+#include "hs_kernels_alleles.hip"
 
 namespace hs {
 static thread_local std::string g_err;
@@ -64,6 +66,7 @@ using hs::set_error;
 #include "hs_capi_kernels.inc"
 #include "hs_cv_backend.inc"
 #include "hs_sr_backend.inc"
+#include "hs_capi_alleles.inc"
 #include "hs_capi_stage.inc"
 #include "hs_capi_multi.inc"
 #include "hs_capi_polish.inc"

@@ -135,6 +135,8 @@ struct hs_pipeline {
     bool keep_columns = false;      // HS_PIPELINE_KEEP_COLUMNS
     bool sparse_labels = false;     // HS_PIPELINE_SPARSE_LABELS: the labels per window as (reads of the window, their labels), no dense array
     std::vector<int64_t> sp_off; std::vector<int32_t> sp_ids, sp_labels;      // (the last call's, contig order: hs_pipeline_sparse_labels)
+    bool alleles = false;           // HS_PIPELINE_ALLELES: every group crosses its labels with its SNP columns at the end of its chain
+    hs_allele_table* allele_table = nullptr;      // (the last call's, contig order: hs_pipeline_alleles)
 
     int device = 0;        // = batch->device: the group threads bind themselves to it (a new thread starts on device 0)
     std::vector<int> thread_device;   // what every group thread found current after binding (hs_pipeline_thread_devices)
@@ -242,6 +244,7 @@ int hs_pipeline_set_option(hs_pipeline* p, int32_t option, int64_t value) {
     if (!p) { set_error("hs_pipeline_set_option: null pipeline"); return HS_EINVAL; }
     if (option == HS_PIPELINE_KEEP_COLUMNS) { p->keep_columns = value != 0; return HS_OK; }
     if (option == HS_PIPELINE_SPARSE_LABELS) { p->sparse_labels = value != 0; return HS_OK; }
+    if (option == HS_PIPELINE_ALLELES) { p->alleles = value != 0; return HS_OK; }
     set_error("hs_pipeline_set_option: unknown option"); return HS_EINVAL;
 }
 int hs_pipeline_groups(const hs_pipeline* p) { return p ? (int)p->ranges.size() : 0; }
@@ -256,6 +259,7 @@ int hs_pipeline_sparse_labels(const hs_pipeline* p, const int64_t** win_row_off,
     if (n_windows) *n_windows = (int64_t)p->sp_off.size() - 1; if (n_rows) *n_rows = p->sp_off.back();
     return HS_OK;
 }
+const hs_allele_table* hs_pipeline_alleles(const hs_pipeline* p) { return p ? p->allele_table : nullptr; }
 const hs_cv_result* hs_pipeline_group_cv(const hs_pipeline* p, int32_t g) { return (p && g >= 0 && g < (int32_t)p->cv.size()) ? p->cv[(size_t)g] : nullptr; }
 // the device every contig-group thread is bound to (-1: not bound yet / failed); returns the number of groups
 int hs_pipeline_thread_devices(hs_pipeline* p, int32_t* out, int32_t cap) {
@@ -274,6 +278,7 @@ void hs_pipeline_destroy(hs_pipeline* p) {
     for (std::thread& t : p->threads) t.join();
     (void)bind_device(p->device);
     p->drop_cv();
+    hs::alleles_free(p->allele_table);
     delete p;
 }
 
@@ -528,7 +533,18 @@ struct GroupCall {
     std::vector<hs_sr_result*> parts;
     std::vector<hs::SrSparseLabels> sparse;      // the groups leave their labels per window; concat_sr_parts spreads them
     GroupMeeting* meet;      // the fused call only: its groups bring up their own share of the pileup and meet before stage 4
+    std::vector<hs_allele_table*> allele_parts;      // HS_PIPELINE_ALLELES: the groups' shares of the table
+    ~GroupCall() { for (hs_allele_table* t : allele_parts) hs::alleles_free(t); }
 };
+
+// the groups' shares of the allele table, contig order; the previous call's table goes
+static int pipeline_merge_alleles(hs_pipeline* p, GroupCall& call) {
+    hs::alleles_free(p->allele_table); p->allele_table = nullptr;
+    if (!p->alleles) return HS_OK;
+    p->allele_table = hs::alleles_concat(std::vector<const hs_allele_table*>(call.allele_parts.begin(), call.allele_parts.end()));
+    if (!p->allele_table) { set_error("allele table: out of memory"); return HS_EINVAL; }
+    return HS_OK;
+}
 
 // Group g's chain: the column pass, stage 3's host glue, stage 4 on the columns where stage 3 packed them. Everything is queued
 // on the thread's own stream (the null stream of HipCvOps / HipSrOps under -fgpu-default-stream=per-thread); a low-priority stream
@@ -567,6 +583,9 @@ static int pipeline_group_step(hs_pipeline* p, GroupCall& call, int g) {
     if (!via_host) ops.adopt_columns(cv_ops);
     if (int r = hs::sr_run_from_cv(ops, meta, c0, c1, cv, error_rate, call.rarest_strain_abundance, call.low_memory, call.amplicon, call.seed, per, call.window_size,
                                    &call.parts[(size_t)g], &call.sparse[(size_t)g], &p->sr_keep[(size_t)g])) return fail(r);
+    if (p->alleles) {
+        if (int r = pipeline_group_alleles(call.parts[(size_t)g], call.sparse[(size_t)g], cv, call.rarest_strain_abundance, c0, ops, &call.allele_parts[(size_t)g])) return fail(r);
+    }
     // HS_PIPELINE_KEEP_COLUMNS: the entries came down beside stage 4. The two-call form copies them; the fused call's result points into
     // the group's pinned block, which stays with the pipeline until its next call
     const bool borrow = meet != nullptr;
@@ -582,11 +601,12 @@ int hs_pipeline_run(hs_pipeline* p, float automatic_snp_threshold, float error_r
     const int G = (int)p->ranges.size();
     if (window_size <= 0) window_size = pipeline_window_size(p->batch, amplicon != 0);
     GroupCall call{automatic_snp_threshold, error_rate, rarest_strain_abundance, low_memory, amplicon, seed, pipeline_threads_per_group(n_threads, G), window_size,
-                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), nullptr};
+                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), nullptr, std::vector<hs_allele_table*>((size_t)G, nullptr)};
     hs::set_trace_origin();
     p->k2_order.reset();
     const int rc = p->run([&](int g) { return pipeline_group_step(p, call, g); });
     if (rc) { for (hs_sr_result* r : call.parts) if (r) hs::free_sr_result(r); return rc; }
+    if (int rc_a = pipeline_merge_alleles(p, call)) { for (hs_sr_result* r : call.parts) if (r) hs::free_sr_result(r); return rc_a; }
     if (st) fold_cv_stats(st, p);      // (on top of what hs_pipeline_select wrote)
     if (std::getenv("HS_TIMING")) std::fprintf(stderr, "[hs timing] host waits so far: %ld, %.1f ms in them\n", g_waits.load(), g_wait_us.load() / 1e3);
     *out = concat_sr_parts(p, call.parts, call.sparse, st);      // (the groups' stage-3 results stay until the next call: hs_pipeline_group_cv)
@@ -614,7 +634,7 @@ int hs_pipeline_run_fused(hs_pipeline* p, float automatic_snp_threshold, float r
     GroupMeeting meet;
     meet.md.assign((size_t)C, 0.f);
     GroupCall call{automatic_snp_threshold, 0.f, rarest_strain_abundance, low_memory, amplicon, seed, pipeline_threads_per_group(n_threads, G), window_size,
-                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), &meet};
+                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), &meet, std::vector<hs_allele_table*>((size_t)G, nullptr)};
     hs::set_trace_origin();
     p->k2_order.reset();
     // a group that is gone (its job failed, or its thread never bound to the device) releases whoever waits for it at the meeting point
@@ -622,6 +642,7 @@ int hs_pipeline_run_fused(hs_pipeline* p, float automatic_snp_threshold, float r
     const int rc = p->run([&](int g) { return pipeline_group_step(p, call, g); });
     { std::lock_guard<std::mutex> lk(p->mu); p->on_fail = nullptr; }
     if (rc) { for (hs_sr_result* r : call.parts) if (r) hs::free_sr_result(r); return rc; }
+    if (int rc_a = pipeline_merge_alleles(p, call)) { for (hs_sr_result* r : call.parts) if (r) hs::free_sr_result(r); return rc_a; }
     if (mean_distance && C) std::memcpy(mean_distance, meet.md.data(), (size_t)C * sizeof(float));
     if (error_rate_out) *error_rate_out = meet.error_rate;
     if (st) { std::memset(st, 0, sizeof *st); fold_cv_stats(st, p); }      // (t_kernel_cv_ms[0] and [3], the pileup's own, stay 0: nothing times it apart from the chain)

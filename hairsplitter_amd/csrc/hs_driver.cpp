@@ -1096,7 +1096,7 @@ int sr_run_from_cv(SrDeviceOps& dev, const CvMeta& b, int c0, int c1, const hs_c
     if (resident_in) {
         bool all = true;
         for (int64_t s = 0; s < cv->snp_off[C] && all; ++s)
-            if (!((float)cv->snp_n_alt[s] >= rsa * (float)(cv->snp_n_ref[s] + cv->snp_n_alt[s]))) all = false;
+            if (!snp_kept_by_abundance(cv->snp_n_ref[s], cv->snp_n_alt[s], rsa)) all = false;
         if (!all) {
             if (int rc = dev.fetch_columns(fetched_idx, fetched_code)) return rc;
             dev.drop_resident_columns();
@@ -1126,7 +1126,7 @@ int sr_run_from_cv(SrDeviceOps& dev, const CvMeta& b, int c0, int c1, const hs_c
             int maj = 0, sec = 0;
             if (cv->snp_n_ref && cv->snp_n_alt) { maj = cv->snp_n_ref[s]; sec = cv->snp_n_alt[s]; }   // counted by stage 3 already
             else for (int64_t e = cv->col_off[s]; e < cv->col_off[s + 1]; ++e) { if (cv_code[e] == cv->snp_ref[s]) maj++; else if (cv_code[e] == cv->snp_alt[s]) sec++; }
-            if (!((float)sec >= rsa * (float)(maj + sec))) { keep[(size_t)(s - s0)] = 0; all_kept = false; }
+            if (!snp_kept_by_abundance(maj, sec, rsa)) { keep[(size_t)(s - s0)] = 0; all_kept = false; }
         }
         hs_sr_contig& h = hc[(size_t)c];
         h.length = b.contig_off[(size_t)gc + 1] - b.contig_off[(size_t)gc];

@@ -329,6 +329,11 @@ struct SrTaps {
 int sr_run(SrDeviceOps& dev, const hs_sr_contig* contigs, int32_t n_contigs, int32_t window_size, float error_rate,
            int32_t low_memory, uint32_t seed, int32_t n_threads, hs_sr_result** out, SrSparseLabels* sparse = nullptr, SrWorkspace* keep = nullptr, SrTaps* taps = nullptr);
 
+// parse_column_file, separate_reads.cpp:167: a SNP whose second base is rarer than rarest_strain_abundance is dropped (the comparison in
+// float, a NaN drops it). Stage 4 and the allele table of a pipeline see the same SNPs through this one statement.
+inline bool snp_kept_by_abundance(int32_t n_ref, int32_t n_alt, float rarest_strain_abundance) {
+    return (float)n_alt >= rarest_strain_abundance * (float)(n_ref + n_alt);
+}
 int sr_run_from_cv(SrDeviceOps& dev, const CvMeta& meta, int c0, int c1, const hs_cv_result* cv, float error_rate, float rarest_strain_abundance,
                    int32_t low_memory, int32_t amplicon, uint32_t seed, int32_t n_threads, int32_t window_size, hs_sr_result** out,
                    SrSparseLabels* sparse = nullptr, SrWorkspace* keep = nullptr);

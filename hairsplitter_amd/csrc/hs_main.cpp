@@ -16,6 +16,7 @@
 #include "hs_host.h"
 #include "hs_driver.h"
 #include "hs_job_rules.h"
+#include "hs_alleles_host.h"
 
 namespace {
 
@@ -248,8 +249,10 @@ extern "C" int hs_separate_reads_main(int argc, char** argv) {
             while (std::getline(pf, line)) { std::istringstream iss(line); std::string ctg; int p; if (!(iss >> ctg >> p)) break; ploidy_of[ctg] = p; }
         }
     }
+    // HS_ALLELES=1: <outfile>.alleles.tsv is written too, from the labels and the columns of this run: the precomputed .gro has neither
+    const bool want_alleles = []() { const char* e = std::getenv("HS_ALLELES"); return e && e[0] && e[0] != '0'; }();
     // the .gro HS_call_variants left for exactly this call (same .col, same arguments, no ploidies): copied, no device needed
-    if (ploidy_of.empty() && hs::take_gro_companion(columns_file, error_rate, rsa, low_memory, amplicon, seed, outfile, num_threads) == 1) {
+    if (!want_alleles && ploidy_of.empty() && hs::take_gro_companion(columns_file, error_rate, rsa, low_memory, amplicon, seed, outfile, num_threads) == 1) {
         clk.lap("the precomputed .gro of this call (.col.hsgro)");
         return 0;
     }
@@ -280,6 +283,21 @@ extern "C" int hs_separate_reads_main(int argc, char** argv) {
     clk.lap("hs_sr_run");
     hs::write_gro(cs, res, outfile, num_threads);
     clk.lap("write .gro");
+    if (want_alleles) {
+        hs_allele_table* table = nullptr;
+        if (int rc = hs_haplotype_alleles(hc.data(), (int32_t)hc.size(), res, &table)) {
+            std::cout << "ERROR: " << hs_last_error() << " (" << rc << ")" << std::endl;
+            return 1;
+        }
+        std::vector<const char*> names;
+        for (const hs::ColFileContig& c : cs) names.push_back(c.name.c_str());
+        const std::string text = hs::alleles_text(table, names.data(), (int32_t)names.size());
+        std::ofstream o(outfile + ".alleles.tsv", std::ios::binary);
+        o.write(text.data(), (std::streamsize)text.size());
+        if (!o) { std::cout << "ERROR: could not write " << outfile << ".alleles.tsv" << std::endl; return 1; }
+        hs_allele_table_destroy(table);
+        clk.lap("allele table");
+    }
     if (!g_leak_at_exit) hs_sr_result_destroy(res);
     return 0;
 }

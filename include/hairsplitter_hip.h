@@ -628,6 +628,64 @@ int hs_sr_run_cv(const hs_cv_batch* b, const hs_cv_result* cv, float error_rate,
                  int32_t low_memory, int32_t amplicon, uint32_t seed, int32_t n_threads, int32_t window_size,
                  hs_sr_result** out);
 /* separate_reads.cpp:1466-1498: window size from the read limits of all contigs of the .col */
+
+/* ------------------------------------------------------------------------------------------------
+ * Per-group allele calls at every SNP: the finished labels of stage 4 crossed with the SNP columns of stage 3, on the device.
+ * The reference forms the same majority base per intermediate cluster and SNP inside merge_wrongly_split_haplotypes
+ * (separate_reads.cpp:1056-1113) and discards it; here it is formed on the FINAL labels and returned.
+ * A cell = (window, SNP column, group). The groups of a window are its distinct labels >= 0, ascending (ids are kept as they are). A window's
+ * SNPs are the columns with win_start <= pos <= win_end; windows without SNPs, and SNPs in no window, are not in the table. Over the
+ * column entries whose read has the group's label in that window (entries labelled -1 / -2 count nowhere): n = their number; best /
+ * second = the largest and second-largest count of one pileup code (two codes tied at the top: second == best); best_code = the smallest
+ * code with the count best; n_ref / n_alt = entries equal to the column's snp_ref / snp_alt; call = best_code, or 0 (undefined) when
+ * 2 * second > best or n > 2 * best -- secondMax*2 > max || nb*0.5 > max of separate_reads.cpp:1100 -- or the group has no entry.
+ * n_calls of a SNP = distinct non-zero calls among its groups (maxbases.size() of separate_reads.cpp:1113); >= 2: the SNP separates groups.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hs_allele_cell { uint16_t n, best, second, n_ref, n_alt; uint8_t best_code, call; } hs_allele_cell;   /* 12 bytes */
+typedef struct hs_allele_table {   /* separate_reads.cpp:1056-1113; host memory, CSR; release with hs_allele_table_destroy */
+    int64_t n_windows, n_snps, n_groups, n_cells;
+    int32_t *win_contig, *win_start, *win_end;   /* [n_windows] the windows that have SNPs, contig order */
+    int64_t* win_group_off;                      /* [n_windows + 1] into group_ids */
+    int32_t* group_ids;                          /* [n_groups] ascending inside a window */
+    int64_t* win_snp_off;                        /* [n_windows + 1] the window's SNPs */
+    int32_t *snp_contig, *snp_pos;               /* [n_snps] */
+    uint8_t *snp_ref, *snp_alt;                  /* [n_snps] pileup codes */
+    int32_t* snp_n_calls;                        /* [n_snps] */
+    int64_t* snp_cell_off;                       /* [n_snps + 1]: cell of group k of the SNP's window at cells[snp_cell_off[s] + k] */
+    hs_allele_cell* cells;                       /* [n_cells] */
+    double t_kernel_ms;                          /* hipEvent time of the kernels (0 on an untimed step) */
+    int64_t n_entries;                           /* column entries the cell kernels read (5 bytes each) */
+    int64_t n_wide_columns;                      /* columns deeper than hs_alleles_lds_capacity(): sorted in global scratch */
+} hs_allele_table;
+void hs_allele_table_destroy(hs_allele_table* t);   /* separate_reads.cpp:1056-1113 has no such result to release: it discards it */
+/* <outfile>.alleles.tsv of HS_separate_reads under HS_ALLELES=1 (separate_reads.cpp:1056-1113 prints nothing): per window
+ * "WINDOW <contig> <start> <end> <group ids,>", then per SNP "SNP <pos> <ref base> <alt base> <n_calls>" and per group
+ * "g:n:n_ref:n_alt:call", tab-separated; call = the three-base context of the code (call_variants.cpp:25-31) or "."; names[c] = name of
+ * contig c (NULL: indices). *out is malloc'ed: hs_free_host. */
+int hs_alleles_text(const hs_allele_table* t, const char* const* names, int32_t n_names, char** out);
+/* Entries of the deepest column whose keys one wavefront sorts in LDS; deeper columns (up to 65535 entries) go through global scratch. */
+int32_t hs_alleles_lds_capacity(void);
+/* The kernel-level call (separate_reads.cpp:1056-1113 per cluster -> per final group), asynchronous on `stream`, in two steps that share
+ * d_work (hs_group_alleles_layout: byte offsets of its parts; total_bytes to allocate, 256-byte aligned):
+ *   d_cells == NULL: the plan -- snp_win [S] (window of every SNP, -1 none), grp_n [W] / grp_ids (the groups of window w at grp_ids +
+ *     label_off[w]; windows without SNPs get none), grp_off [W + 1] / grp_pack (the same lists one after the other),
+ *     win_snp_first / win_snp_last [W] (SNP range; first == last: none), cell_off [S + 1] (cell_off[S] = cells needed);
+ *   d_cells != NULL: the cells of that plan into d_cells (a column whose cells would end beyond cells_cap is not written and gets
+ *     n_calls = -1), n_calls [S].
+ * Columns: CSR over all SNPs (d_col_off [S + 1], d_col_idx = read index on its contig, d_col_code), at most 65535 entries each; per SNP
+ * ref / alt code, position and contig; windows of contig c = [d_win_off[c], d_win_off[c + 1]), ascending; labels of window w =
+ * d_labels[d_label_off[w] ...], one per read of its contig (-2 absent, -1 unclustered, >= 0 group; ids below INT32_MAX). */
+typedef struct hs_allele_layout { int64_t snp_win, grp_n, win_snp_first, win_snp_last, cell_off, grp_off, n_calls, grp_ids, grp_pack, internal, total_bytes; } hs_allele_layout;
+int hs_group_alleles_layout(int32_t n_snps, int32_t n_windows, int64_t n_labels, hs_allele_layout* out);
+int hs_group_alleles(const int64_t* d_col_off, const int32_t* d_col_idx, const uint8_t* d_col_code,
+                     const uint8_t* d_snp_ref, const uint8_t* d_snp_alt, const int32_t* d_snp_pos, const int32_t* d_snp_contig, int32_t n_snps,
+                     const int64_t* d_win_off /* [n_contigs + 1] */, const int32_t* d_win_start, const int32_t* d_win_end, int32_t n_contigs, int32_t n_windows,
+                     const int64_t* d_label_off /* [n_windows + 1] */, const int32_t* d_labels, int64_t n_labels,
+                     void* d_work, hs_allele_cell* d_cells, int64_t cells_cap, void* stream);
+/* The stage-level call (separate_reads.cpp:1056-1113 on the final labels): the contigs hs_sr_run takes and a result with dense labels --
+ * its own, or any labels in that layout. SNP positions must ascend on every contig. */
+int hs_haplotype_alleles(const hs_sr_contig* contigs, int32_t n_contigs, const hs_sr_result* sr_result, hs_allele_table** table);
+
 /* ------------------------------------------------------------------------------------------------
  * Both stages over one resident batch with the contigs processed as n_groups consecutive ranges on persistent host threads
  * (one HIP stream and one worker pool each). hs_pipeline_select runs hs_cv_select (the streaming kernels, once over the whole
@@ -675,6 +733,12 @@ int hs_pipeline_thread_devices(hs_pipeline* p, int32_t* out, int32_t cap);
  * form) and hs_pipeline_sparse_labels returns, valid until the next call on the pipeline, win_row_off [W+1], ids [rows] (ascending
  * read indices inside a window) and labels [rows]; every read a window does not list has the label -2. */
 #define HS_PIPELINE_SPARSE_LABELS 2
+/* HS_PIPELINE_ALLELES != 0: every contig group also forms its share of the allele table (separate_reads.cpp:1056-1113 on the final labels)
+ * at the end of its own chain, from the SNP columns where stage 4 read them on the device -- HS_PIPELINE_KEEP_COLUMNS is not needed -- and
+ * hs_pipeline_alleles returns the call's table, contig order, valid until the next call on the pipeline. Off (the default): no launch and
+ * no wait is added to the step. */
+#define HS_PIPELINE_ALLELES 4
+const hs_allele_table* hs_pipeline_alleles(const hs_pipeline* p);   /* NULL before the first call with HS_PIPELINE_ALLELES */
 int hs_pipeline_set_option(hs_pipeline* p, int32_t option, int64_t value);
 int hs_pipeline_groups(const hs_pipeline* p);                                  /* number of contig groups */
 int hs_pipeline_group_range(const hs_pipeline* p, int32_t g, int32_t* c0, int32_t* c1);   /* contigs [c0, c1) of group g */
