@@ -30,6 +30,8 @@ SYMBOLS = [
     "hs_polish_inputs", "hs_polish_inputs_from_files", "hs_polish_result_destroy", "hs_polish_inputs_main",
     "hs_moves_to_cigar", "hs_realign_intervals", "hs_realign_records_destroy", "hs_cv_batch_create_paf", "hs_cv_batch_create_sam",
     "hs_allele_table_destroy", "hs_alleles_text", "hs_alleles_lds_capacity", "hs_group_alleles_layout", "hs_group_alleles", "hs_haplotype_alleles", "hs_pipeline_alleles",
+    "hs_recruit_params_default", "hs_recruit_table_destroy", "hs_recruit_reads", "hs_group_recruit_layout", "hs_group_recruit", "hs_recruit_apply", "hs_recruit_text",
+    "hs_pipeline_recruits", "hs_pipeline_set_recruit_params",
 ]
 
 HS_NKERNELS = 28
@@ -85,6 +87,28 @@ class AlleleLayout(C.Structure):
                                          "internal", "total_bytes")]
 
 
+class RecruitParams(C.Structure):
+    """hs_recruit_params"""
+    _fields_ = [(k, C.c_int32) for k in ("which", "min_informative", "min_margin", "mismatch_num", "mismatch_den")]
+
+
+class RecruitTable(C.Structure):
+    """hs_recruit_table"""
+    _fields_ = [("n_windows", C.c_int64), ("n_rows", C.c_int64), ("n_assigned", C.c_int64),
+                ("win_contig", C.POINTER(C.c_int32)), ("win_start", C.POINTER(C.c_int32)), ("win_end", C.POINTER(C.c_int32)),
+                ("win_index", C.POINTER(C.c_int64)), ("win_row_off", C.POINTER(C.c_int64)), ("rows", C.c_void_p), ("params", RecruitParams),
+                ("n_call_windows", C.c_int64), ("n_counter_words", C.c_int64), ("n_entries", C.c_int64), ("t_kernel_ms", C.c_double)]
+
+
+class RecruitLayout(C.Structure):
+    """hs_recruit_layout: byte offsets of the parts of hs_group_recruit's work buffer (the allele plan's in front)"""
+    _fields_ = [("alleles", AlleleLayout)] + [(k, C.c_int64) for k in ("flag", "row_idx", "ctr_off", "win_row_off", "status", "internal", "total_bytes")]
+
+
+HS_RECRUIT_ABSENT, HS_RECRUIT_UNCLUSTERED, HS_RECRUIT_LABELLED = 1, 2, 4
+# hs_recruit_row (40 bytes)
+RECRUIT_ROW = np.dtype([("read", "<i4"), ("label", "<i4"), ("best_group", "<i4"), ("second_group", "<i4"), ("m_best", "<u4"), ("x_best", "<u4"),
+                        ("m_second", "<u4"), ("x_second", "<u4"), ("n_entries", "<u4"), ("assigned", "<i4")])
 # hs_allele_cell (12 bytes)
 ALLELE_CELL = np.dtype([("n", "<u2"), ("best", "<u2"), ("second", "<u2"), ("n_ref", "<u2"), ("n_alt", "<u2"), ("best_code", "u1"), ("call", "u1")])
 
@@ -147,6 +171,16 @@ def load() -> C.CDLL:
     lib.hs_pipeline_alleles.argtypes = [C.c_void_p]
     lib.hs_haplotype_alleles.argtypes = [C.POINTER(SrContig), C.c_int32, C.POINTER(SrResult), C.POINTER(C.POINTER(AlleleTable))]
     lib.hs_alleles_lds_capacity.restype = C.c_int32
+    lib.hs_recruit_params_default.restype = RecruitParams
+    lib.hs_recruit_table_destroy.restype = None
+    lib.hs_recruit_table_destroy.argtypes = [C.c_void_p]
+    lib.hs_pipeline_recruits.restype = C.POINTER(RecruitTable)
+    lib.hs_pipeline_recruits.argtypes = [C.c_void_p]
+    lib.hs_pipeline_set_recruit_params.argtypes = [C.c_void_p, C.POINTER(RecruitParams)]
+    lib.hs_recruit_reads.argtypes = [C.POINTER(SrContig), C.c_int32, C.POINTER(SrResult), C.POINTER(RecruitParams), C.POINTER(C.POINTER(AlleleTable)),
+                                     C.POINTER(C.POINTER(RecruitTable))]
+    lib.hs_recruit_apply.argtypes = [C.POINTER(RecruitTable), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.hs_recruit_text.argtypes = [C.POINTER(RecruitTable), C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
 
@@ -516,7 +550,21 @@ class PipelineGroups:
         _check(load().hs_pipeline_set_option(self.handle, C.c_int32(4), C.c_int64(1 if on else 0)))
         self._alleles = bool(on)
 
+    def recruits(self, on=True, params=None):
+        """HS_PIPELINE_RECRUIT: every call also returns sr["recruits"], the recruit table of the call (a copy): every contig group crosses its
+        windows' unlabelled reads with its allele cells on the device. params: a dict as recruit_params() gives it (None: what the pipeline
+        has -- the defaults at first). The allele table comes along only under alleles(True)."""
+        if params is not None:
+            _check(load().hs_pipeline_set_recruit_params(self.handle, C.byref(_recruit_params(params))))
+        _check(load().hs_pipeline_set_option(self.handle, C.c_int32(8), C.c_int64(1 if on else 0)))
+        self._recruits = bool(on)
+
     def _attach_sparse(self, sr):
+        if getattr(self, "_recruits", False):
+            tb = load().hs_pipeline_recruits(self.handle)
+            if not tb:
+                raise HsError("hs_pipeline_recruits: no table")
+            sr["recruits"] = _recruit_table_to_dict(tb)
         if getattr(self, "_alleles", False):
             tb = load().hs_pipeline_alleles(self.handle)
             if not tb:
@@ -772,8 +820,11 @@ def _owned_view_i32(res, ptr, n):
 
 def separate_reads(cv_out: Dict, flat: FlatBatch, error_rate: float, low_memory: bool = False, amplicon: bool = False,
                    seed: int = 12345, n_threads: int = 0, ploidy: Optional[Sequence[int]] = None,
-                   rarest_strain_abundance: float = 0.0, window_size: Optional[int] = None, taps: bool = False, alleles: bool = False) -> Dict:
-    """(alleles=True: out["alleles"] = the allele table of the call, hs_haplotype_alleles on its labels and the SNPs it kept.)
+                   rarest_strain_abundance: float = 0.0, window_size: Optional[int] = None, taps: bool = False, alleles: bool = False,
+                   recruit=False) -> Dict:
+    """(recruit=True, or a dict of thresholds as recruit_params() gives it: out["recruits"] = the recruit table of the call, hs_recruit_reads
+    on its labels and the SNPs it kept.)
+    (alleles=True: out["alleles"] = the allele table of the call, hs_haplotype_alleles on its labels and the SNPs it kept.)
     (taps=True: through hs_sr_run_taps -- out["taps"] holds what the kernels of the clustering chain left, out["contigs"] the per-contig
     inputs as numpy arrays, for the tests. taps="graphs": the call stops behind the read graphs -- separate_reads_graph_taps on the same
     per-contig inputs; out = {"window_size", "contigs", "taps"}.)
@@ -862,6 +913,12 @@ def separate_reads(cv_out: Dict, flat: FlatBatch, error_rate: float, low_memory:
         _check(lib.hs_haplotype_alleles(arr, C.c_int32(Cn), res, C.byref(tb)))
         out["alleles"] = _allele_table_to_dict(tb)
         lib.hs_allele_table_destroy(tb)
+    if recruit:
+        rt = C.POINTER(RecruitTable)()
+        prm = _recruit_params(recruit if isinstance(recruit, dict) else None)
+        _check(lib.hs_recruit_reads(arr, C.c_int32(Cn), res, C.byref(prm), None, C.byref(rt)))
+        out["recruits"] = _recruit_table_to_dict(rt)
+        lib.hs_recruit_table_destroy(rt)
     lib.hs_sr_result_destroy(res)
     if taps:
         out["taps"] = _chain_taps_to_dict(tp.contents)
@@ -966,6 +1023,188 @@ def group_alleles(contigs: Sequence[Dict], sr: Dict) -> Dict:
     out["cells"] = cells[:n_cells * ALLELE_CELL.itemsize].cpu().numpy().view(ALLELE_CELL).copy()
     out["n_calls"] = work[int(L.n_calls):int(L.n_calls) + 4 * S].cpu().numpy().view(np.int32).copy()
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# a window's unlabelled reads recruited to its groups (hs_recruit_table)
+# ------------------------------------------------------------------------------------------------
+RECRUIT_PARAM_KEYS = ("which", "min_informative", "min_margin", "mismatch_num", "mismatch_den")
+
+
+def recruit_params(**over) -> Dict:
+    """hs_recruit_params_default() as a dict (placeholders of the interface, not validated figures), with `over` on top"""
+    d = load().hs_recruit_params_default()
+    out = {k: int(getattr(d, k)) for k in RECRUIT_PARAM_KEYS}
+    out.update({k: int(v) for k, v in over.items()})
+    return out
+
+
+def _recruit_params(params) -> RecruitParams:
+    d = recruit_params(**(params or {}))
+    return RecruitParams(*[d[k] for k in RECRUIT_PARAM_KEYS])
+
+
+def _recruit_table_to_dict(tp) -> Dict:
+    """a copy of an hs_recruit_table as numpy arrays; "rows" has the dtype RECRUIT_ROW"""
+    t = tp.contents
+    W, R = int(t.n_windows), int(t.n_rows)
+
+    def a(ptr, n, dtype):
+        if n == 0:
+            return np.zeros(0, dtype)
+        return np.ctypeslib.as_array(ptr, (n,)).astype(dtype, copy=True)
+
+    rows = np.zeros(R, RECRUIT_ROW)
+    if R:
+        C.memmove(rows.ctypes.data, t.rows, R * RECRUIT_ROW.itemsize)
+    return {"win_contig": a(t.win_contig, W, np.int32), "win_start": a(t.win_start, W, np.int32), "win_end": a(t.win_end, W, np.int32),
+            "win_index": a(t.win_index, W, np.int64), "win_row_off": a(t.win_row_off, W + 1, np.int64), "rows": rows,
+            "n_assigned": int(t.n_assigned), "params": {k: int(getattr(t.params, k)) for k in RECRUIT_PARAM_KEYS},
+            "n_call_windows": int(t.n_call_windows), "n_counter_words": int(t.n_counter_words), "n_entries": int(t.n_entries),
+            "t_kernel_ms": float(t.t_kernel_ms)}
+
+
+def _recruit_table_from_dict(table: Dict, keep: list) -> RecruitTable:
+    """an hs_recruit_table over the arrays of a dict of this module (for the device-free calls); `keep` holds the buffers"""
+    t = RecruitTable()
+    W, R = len(table["win_start"]), len(table["rows"])
+    t.n_windows, t.n_rows, t.n_assigned = W, R, int(table.get("n_assigned", int((np.asarray(table["rows"])["assigned"] != 0).sum())))
+    pad = lambda x, dt: _np(x if len(x) else np.zeros(1, dt), dt)
+    wc, ws, we = pad(table["win_contig"], np.int32), pad(table["win_start"], np.int32), pad(table["win_end"], np.int32)
+    wi, wo = pad(table["win_index"], np.int64), _np(table["win_row_off"], np.int64)
+    rows = np.ascontiguousarray(np.asarray(table["rows"]).astype(RECRUIT_ROW)) if R else np.zeros(1, RECRUIT_ROW)
+    keep += [wc, ws, we, wi, wo, rows]
+    t.win_contig, t.win_start, t.win_end = _hp(wc, C.c_int32), _hp(ws, C.c_int32), _hp(we, C.c_int32)
+    t.win_index, t.win_row_off, t.rows = _hp(wi, C.c_int64), _hp(wo, C.c_int64), rows.ctypes.data
+    t.params = _recruit_params(table.get("params"))
+    t.n_call_windows = int(table["n_call_windows"])
+    return t
+
+
+def _sr_struct(sr: Dict, Cn: int, keep: list) -> SrResult:
+    wo, ws, we = _np(sr["win_off"], np.int64), _np(sr["win_start"], np.int32), _np(sr["win_end"], np.int32)
+    lo, lab = _np(sr["label_off"], np.int64), _np(sr["labels"], np.int32)
+    if len(ws) == 0:
+        ws, we = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    if len(lab) == 0:
+        lab = np.zeros(1, np.int32)
+    keep += [wo, ws, we, lo, lab]
+    r = SrResult()
+    r.n_contigs = Cn
+    r.win_off = _hp(wo, C.c_int64); r.win_start = _hp(ws, C.c_int32); r.win_end = _hp(we, C.c_int32)
+    r.label_off = _hp(lo, C.c_int64); r.labels = _hp(lab, C.c_int32)
+    return r
+
+
+def recruit_reads(contigs: Sequence[Dict], sr: Dict, params: Optional[Dict] = None, with_alleles: bool = False):
+    """hs_recruit_reads: which group of its window every read without a label there fits best, from the allele calls of the window's groups
+    (inputs as haplotype_alleles takes them; params: recruit_params(), None = the defaults). Returns the table as a dict -- "rows" in the dtype
+    RECRUIT_ROW, window-major, reads ascending -- or (table, allele table) with with_alleles=True."""
+    require_gpu()
+    lib = load()
+    arr, keep = _sr_contig_array(contigs)
+    keep2 = []
+    r = _sr_struct(sr, len(contigs), keep2)
+    prm = _recruit_params(params)
+    rt, at = C.POINTER(RecruitTable)(), C.POINTER(AlleleTable)()
+    _check(lib.hs_recruit_reads(arr, C.c_int32(len(contigs)), C.byref(r), C.byref(prm), C.byref(at) if with_alleles else None, C.byref(rt)))
+    out = _recruit_table_to_dict(rt)
+    lib.hs_recruit_table_destroy(rt)
+    del keep, keep2
+    if not with_alleles:
+        return out
+    alleles = _allele_table_to_dict(at)
+    lib.hs_allele_table_destroy(at)
+    return out, alleles
+
+
+def recruit_apply(table: Dict, sr: Dict) -> np.ndarray:
+    """hs_recruit_apply (no device): the dense labels of `sr` with every assigned row whose label is < 0 set to its best group"""
+    lib = load()
+    keep = []
+    t = _recruit_table_from_dict(table, keep)
+    lo, lab = _np(sr["label_off"], np.int64), _np(sr["labels"], np.int32)
+    out = np.zeros(max(len(lab), 1), np.int32)
+    src = lab if len(lab) else np.zeros(1, np.int32)
+    _check(lib.hs_recruit_apply(C.byref(t), lo.ctypes.data, src.ctypes.data, out.ctypes.data, C.c_int64(len(lab))))
+    return out[:len(lab)]
+
+
+def recruit_text(table: Dict, names: Optional[Sequence[str]] = None) -> str:
+    """hs_recruit_text: the text HS_separate_reads writes to <outfile>.recruit.tsv under HS_RECRUIT=1, from a table of this module"""
+    lib = load()
+    keep = []
+    t = _recruit_table_from_dict(table, keep)
+    arr = None
+    if names is not None:
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    out = C.c_char_p()
+    _check(lib.hs_recruit_text(C.byref(t), arr, C.c_int32(len(names) if names is not None else 0), C.byref(out)))
+    text = out.value.decode()
+    lib.hs_free_host(C.cast(out, C.c_void_p))
+    return text
+
+
+def group_recruit(contigs: Sequence[Dict], sr: Dict, params: Optional[Dict] = None, fill: int = 0, extra_rows: int = 0) -> Dict:
+    """hs_group_recruit, the kernel-level call, in its two steps on torch tensors (inputs as recruit_reads takes them). The work buffer and
+    the row buffer (extra_rows more rows than the plan counts) are filled with the byte `fill` first; returns the rows, win_row_off over all
+    windows, status, the cells, and "rows_tail" -- the bytes of the row buffer behind the counted rows."""
+    import torch
+    require_gpu()
+    lib = load()
+    dev = "cuda:0"
+    depth = [np.diff(_np(c["col_off"], np.int64)) for c in contigs]
+    col_off = np.concatenate([[0]] + [d for d in depth]).cumsum().astype(np.int64)
+    def cat(key, dt):
+        parts = [_np(c[key], dt)[int(c["col_off"][0]):int(c["col_off"][-1])] if key.startswith("col_") else _np(c[key], dt) for c in contigs]
+        return np.concatenate([np.zeros(0, dt)] + parts).astype(dt)
+
+    snp_contig = np.concatenate([np.zeros(0, np.int32)] + [np.full(len(c["snp_pos"]), k, np.int32) for k, c in enumerate(contigs)]).astype(np.int32)
+    S, W, Cn = len(snp_contig), len(sr["win_start"]), len(contigs)
+    n_labels = int(sr["label_off"][-1])
+    up = lambda a, dt: torch.from_numpy(_np(a, dt) if len(a) else np.zeros(1, dt)).to(dev)
+    d = [up(col_off, np.int64), up(cat("col_idx", np.int32), np.int32), up(cat("col_code", np.uint8), np.uint8), up(cat("snp_ref", np.uint8), np.uint8),
+         up(cat("snp_alt", np.uint8), np.uint8), up(cat("snp_pos", np.int32), np.int32), up(snp_contig, np.int32)]
+    w = [up(sr["win_off"], np.int64), up(sr["win_start"], np.int32), up(sr["win_end"], np.int32)]
+    lab = [up(sr["label_off"], np.int64), up(sr["labels"], np.int32)]
+    L = RecruitLayout()
+    _check(lib.hs_group_recruit_layout(C.c_int32(S), C.c_int32(W), C.c_int64(n_labels), C.byref(L)))
+    work = torch.full((int(L.total_bytes),), fill, dtype=torch.uint8, device=dev)
+    prm = _recruit_params(params)
+
+    def call(cells, cap, ctr, ctr_cap, rows, rows_cap):
+        _check(lib.hs_group_recruit(*[_p(x) for x in d], C.c_int32(S), *[_p(x) for x in w], C.c_int32(Cn), C.c_int32(W), *[_p(x) for x in lab], C.c_int64(n_labels),
+                                    C.byref(prm), _p(work), _p(cells), C.c_int64(cap), _p(ctr), C.c_int64(ctr_cap), _p(rows), C.c_int64(rows_cap), C.c_void_p(0)))
+        torch.cuda.synchronize()
+
+    call(None, 0, None, 0, None, 0)
+    word = lambda off: int(work[int(off):int(off) + 8].cpu().numpy().view(np.int64)[0])
+    n_cells = word(L.alleles.cell_off + 8 * S)
+    n_rows, n_ctr = word(L.row_idx + 8 * n_labels), word(L.ctr_off + 8 * n_labels)
+    cells = torch.zeros(max(n_cells, 1) * ALLELE_CELL.itemsize, dtype=torch.uint8, device=dev)
+    ctr = torch.full((max(n_ctr, 1) * 4,), fill, dtype=torch.uint8, device=dev)
+    rows = torch.full(((n_rows + extra_rows) * RECRUIT_ROW.itemsize + 8,), fill, dtype=torch.uint8, device=dev)
+    call(cells, n_cells, ctr, n_ctr, rows, n_rows + extra_rows)
+    host_rows = rows.cpu().numpy()
+    part = lambda off, n, dt: work[int(off):int(off) + n * np.dtype(dt).itemsize].cpu().numpy().view(dt).copy()
+    return {"rows": host_rows[:n_rows * RECRUIT_ROW.itemsize].view(RECRUIT_ROW).copy(), "rows_tail": host_rows[n_rows * RECRUIT_ROW.itemsize:].copy(),
+            "win_row_off": part(L.win_row_off, W + 1, np.int64), "status": int(part(L.status, 1, np.int32)[0]), "n_counter_words": n_ctr,
+            "flag": part(L.flag, n_labels, np.int32), "cells": cells[:n_cells * ALLELE_CELL.itemsize].cpu().numpy().view(ALLELE_CELL).copy(),
+            "win_snp_first": part(L.alleles.win_snp_first, W, np.int32), "win_snp_last": part(L.alleles.win_snp_last, W, np.int32),
+            "work_gaps_untouched": _recruit_gaps_untouched(work, L, S, W, n_labels, fill)}
+
+
+def _recruit_gaps_untouched(work, L, S, W, n_labels, fill) -> bool:
+    """the alignment gaps behind the public parts of the recruit share of the work buffer still hold the fill byte (nothing wrote past a part)"""
+    # (flag and the counter sizes behind it are cleared in one stretch, the gap between them included: not in this list)
+    parts = [(int(L.row_idx), (n_labels + 1) * 8), (int(L.ctr_off), (n_labels + 1) * 8), (int(L.win_row_off), (W + 1) * 8), (int(L.status), 4)]
+    host = work.cpu().numpy()
+    for off, n in parts:
+        end = off + max(n, 4)
+        gap_end = (end + 255) & ~255
+        if not np.all(host[end:min(gap_end, len(host))] == fill):
+            return False
+    return True
 
 
 def allele_context(code: int) -> str:

@@ -5,6 +5,7 @@
 //   hs_cv_backend.inc    stage 3 on the device (hs_cv_batch, HipCvOps)
 //   hs_sr_backend.inc    stage 4 on the device (GraphRows, HipSrOps)
 //   hs_capi_alleles.inc  the allele table: labels x SNP columns per group (hs_group_alleles, hs_haplotype_alleles, a pipeline group's share)
+//   hs_capi_recruit.inc  the recruit table: a window's unlabelled reads x the allele calls of its groups (hs_group_recruit, hs_recruit_reads)
 //   hs_capi_stage.inc    stage-level C ABI on one device, contig groups (hs_pipeline_*)
 //   hs_capi_multi.inc    several GPUs in one process
 //   hs_capi_polish.inc   the polisher's inputs of the next stage (hs_polish_inputs)
@@ -45,6 +46,7 @@
 #include "hs_kernels_polish.hip"
 #include "hs_kernels_realign.hip"
 #include "hs_kernels_alleles.hip"
+#include "hs_kernels_recruit.hip"
 
 namespace hs {
 static thread_local std::string g_err;
@@ -67,6 +69,7 @@ using hs::set_error;
 #include "hs_cv_backend.inc"
 #include "hs_sr_backend.inc"
 #include "hs_capi_alleles.inc"
+#include "hs_capi_recruit.inc"
 #include "hs_capi_stage.inc"
 #include "hs_capi_multi.inc"
 #include "hs_capi_polish.inc"

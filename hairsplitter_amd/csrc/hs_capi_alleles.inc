@@ -87,6 +87,18 @@ static int allele_cells_launch(const AlleleDevIn& in, char* work, const AlleleWo
     return HS_OK;
 }
 
+// The recruit table behind the cells (hs_capi_recruit.inc): asked for with a RecruitReq, it shares the work buffer, the stream and both host waits
+// (declared here, defined there: this file's stage-level route queues them between its own launches)
+struct RecruitWork { AlleleWork a; hs_recruit_layout L; int64_t ctr_n, tile_sum; int n_tiles; };      // the parts of d_work behind the allele plan's (hs_recruit_layout)
+struct RecruitReq { hs_recruit_params params; hs_recruit_table* table = nullptr; };
+static RecruitWork recruit_work(int32_t S, int32_t W, int64_t n_labels);
+static int recruit_plan_launch(const AlleleDevIn& in, char* work, const RecruitWork& rw, const hs_recruit_params& params, hipStream_t st);
+static int recruit_rows_launch(const AlleleDevIn& in, char* work, const RecruitWork& rw, const hs_recruit_params& params, const hs_allele_cell* d_cells, int64_t cells_cap,
+                               uint32_t* d_counters, int64_t counters_cap, hs_recruit_row* d_rows, int64_t rows_cap, hipStream_t st);
+struct AlleleHostIn;
+static int alleles_on_device(const AlleleHostIn& h, const int64_t* d_col_off, const int32_t* d_col_idx, const uint8_t* d_col_code, const int32_t* d_labels,
+                             KernelClock& kc, hipStream_t st, hs_allele_table** out, RecruitReq* rq = nullptr);
+
 // Host copies of what the call describes (the table is assembled from them) next to the device arrays
 struct AlleleHostIn {
     std::vector<int32_t> win_contig, win_start, win_end, snp_contig, snp_pos;
@@ -100,38 +112,54 @@ struct AlleleHostIn {
 // plan -> (one wait: the number of cells) -> cells -> (one wait) -> table. The columns and the dense labels are on the device already;
 // the small per-SNP / per-window arrays of `h` are uploaded here. Launches are accounted under HS_K_OTHER.
 static int alleles_on_device(const AlleleHostIn& h, const int64_t* d_col_off, const int32_t* d_col_idx, const uint8_t* d_col_code, const int32_t* d_labels,
-                             KernelClock& kc, hipStream_t st, hs_allele_table** out) {
+                             KernelClock& kc, hipStream_t st, hs_allele_table** out, RecruitReq* rq) {
     const int64_t S64 = (int64_t)h.snp_pos.size(), W64 = (int64_t)h.win_start.size();
     if (S64 > 0x7fffffff || W64 > 0x7fffffff) { set_error("allele table: more than 2^31 SNPs or windows in one call"); return HS_EINVAL; }
     const int32_t S = (int32_t)S64, W = (int32_t)W64;
     const int32_t C = (int32_t)h.win_off.size() - 1;
     const int64_t n_labels = h.label_off.empty() ? 0 : h.label_off.back();
-    const AlleleWork a = allele_work(S, W, n_labels);
-    DBuf d_work, d_sr, d_sa, d_sp, d_sc, d_wo, d_ws, d_we, d_lo, d_cells;
+    if (rq && n_labels > 0x7fffffff - HS_SCAN_TILE) { set_error("recruit table: more than 2^31 labels in one call"); return HS_EINVAL; }
+    const RecruitWork rw = rq ? recruit_work(S, W, n_labels) : RecruitWork();      // (its allele part is allele_work's: the recruit parts lie behind it)
+    const AlleleWork a = rq ? rw.a : allele_work(S, W, n_labels);
+    const size_t work_bytes = (size_t)(rq ? rw.L.total_bytes : a.L.total_bytes);
+    DBuf d_work, d_sr, d_sa, d_sp, d_sc, d_wo, d_ws, d_we, d_lo, d_cells, d_counters, d_rows;
     UploadPack pk;
     pk.add(h.snp_ref, d_sr); pk.add(h.snp_alt, d_sa); pk.add(h.snp_pos, d_sp); pk.add(h.snp_contig, d_sc);
     pk.add(h.win_off, d_wo); pk.add(h.win_start, d_ws); pk.add(h.win_end, d_we); pk.add(h.label_off, d_lo);
     if (int rc = pk.commit(st)) return rc;
-    if (int rc = d_work.alloc((size_t)a.L.total_bytes)) return rc;
+    if (int rc = d_work.alloc(work_bytes)) return rc;
     AlleleDevIn in{d_col_off, d_col_idx, d_col_code, d_sr.as<uint8_t>(), d_sa.as<uint8_t>(), d_sp.as<int32_t>(), d_sc.as<int32_t>(), S,
                    d_wo.as<int64_t>(), d_ws.as<int32_t>(), d_we.as<int32_t>(), C, W, d_lo.as<int64_t>(), d_labels, n_labels};
     char* work = (char*)d_work.p;
-    EventPair ev_plan, ev;      // (the table's own kernel time: the plan's launches and the cells', not the wait between them)
+    EventPair ev_plan, ev, ev_rplan, ev_rrows;      // (the table's own kernel time: the plan's launches and the cells', not the wait between them)
     if (int rc = ev_plan.init()) return rc;
     if (int rc = ev.init()) return rc;
+    if (rq) { if (int rc = ev_rplan.init()) return rc; if (int rc = ev_rrows.init()) return rc; }
     HS_HIP(ev_rec(ev_plan.a, st));
     if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
     if (int rc = allele_plan_launch(in, work, a, st)) return rc;
     if (int rc = kc.end(4 * n_labels + 12 * (int64_t)S, st)) return rc;
     HS_HIP(ev_rec(ev_plan.b, st));
+    if (rq) {      // the rows' flags and the two scans over them: queued with the plan, counted in the plan's wait
+        HS_HIP(ev_rec(ev_rplan.a, st));
+        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
+        if (int rc = recruit_plan_launch(in, work, rw, rq->params, st)) return rc;
+        if (int rc = kc.end(4 * h.n_entries + 40 * n_labels, st)) return rc;
+        HS_HIP(ev_rec(ev_rplan.b, st));
+    }
     // the plan comes to the host in one shipment (the table is assembled from it); its last word says how many cells to make room for
     const size_t plan_bytes = (size_t)a.L.n_calls;      // snp_win .. grp_off lie in front of n_calls; the packed group lists follow them on the host
     const int64_t groups_cap = std::min<int64_t>(std::max<int64_t>(h.groups_bound, 0), n_labels);      // (every group has a read)
     HBuf h_plan;
-    if (int rc = h_plan.alloc(plan_bytes + (size_t)groups_cap * 4 + 256)) return rc;
+    const size_t totals_at = (plan_bytes + (size_t)groups_cap * 4 + 255) & ~(size_t)255;      // recruit: rows and counter words, behind the group lists
+    if (int rc = h_plan.alloc(totals_at + 256)) return rc;
     {
         Shipment sh;
         sh.add(h_plan.p, work, plan_bytes);
+        if (rq) {      // (a shipment moves 16-byte pieces: the piece each total lies in)
+            sh.add((char*)h_plan.p + totals_at, work + rw.L.row_idx + ((n_labels * 8) & ~(int64_t)15), 16);
+            sh.add((char*)h_plan.p + totals_at + 16, work + rw.L.ctr_off + ((n_labels * 8) & ~(int64_t)15), 16);
+        }
         if (W && S) sh.add_counted((char*)h_plan.p + plan_bytes, work + a.L.grp_pack, (const long long*)(work + a.L.grp_off) + W, 4, groups_cap);
         if (int rc = sh.launch(st, 64)) return rc;
     }
@@ -142,11 +170,28 @@ static int alleles_on_device(const AlleleHostIn& h, const int64_t* d_col_off, co
     const int64_t n_cells = cell_off[S];
     if (n_cells < 0 || grp_off[W] < 0 || grp_off[W] > groups_cap) { set_error("allele table: the device's group lists do not fit the labels of the call"); return HS_EHIP; }
     if (int rc = d_cells.alloc((size_t)std::max<int64_t>(n_cells, 1) * sizeof(hs_allele_cell) + 16)) return rc;
+    const size_t in_piece = (size_t)((n_labels * 8) & 15);
+    const int64_t n_rows = rq ? *(const int64_t*)(hp + totals_at + in_piece) : 0, n_ctr = rq ? *(const int64_t*)(hp + totals_at + 16 + in_piece) : 0;
+    if (rq) {
+        if (n_rows < 0 || n_rows > n_labels || n_ctr < n_rows) { set_error("recruit table: the device's row counts do not fit the labels of the call"); return HS_EHIP; }
+        if (int rc = d_counters.alloc((size_t)std::max<int64_t>(n_ctr, 1) * 4)) return rc;
+        if (int rc = d_rows.alloc((size_t)std::max<int64_t>(n_rows, 1) * sizeof(hs_recruit_row))) return rc;
+    }
     HS_HIP(ev_rec(ev.a, st));
     if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
     if (int rc = allele_cells_launch(in, work, a, d_cells.as<hs_allele_cell>(), n_cells, st)) return rc;
     if (int rc = kc.end(5 * h.n_entries + (int64_t)sizeof(hs_allele_cell) * n_cells, st)) return rc;
     HS_HIP(ev_rec(ev.b, st));
+    HBuf h_rows;
+    const size_t rows_bytes = (size_t)n_rows * sizeof(hs_recruit_row), wro_at = (rows_bytes + 255) & ~(size_t)255, status_at = wro_at + ((((size_t)W + 1) * 8 + 255) & ~(size_t)255);
+    if (rq) {      // counters and rows behind the cells; they come down in the cells' shipment
+        HS_HIP(ev_rec(ev_rrows.a, st));
+        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
+        if (int rc = recruit_rows_launch(in, work, rw, rq->params, d_cells.as<hs_allele_cell>(), n_cells, d_counters.as<uint32_t>(), n_ctr, d_rows.as<hs_recruit_row>(), n_rows, st)) return rc;
+        if (int rc = kc.end(5 * h.n_entries + 12 * n_ctr + 40 * n_rows + 12 * n_labels, st)) return rc;
+        HS_HIP(ev_rec(ev_rrows.b, st));
+        if (int rc = h_rows.alloc(status_at + 256)) return rc;
+    }
     const size_t cells_bytes = (size_t)n_cells * sizeof(hs_allele_cell), calls_bytes = (size_t)S * 4;
     HBuf h_cells;
     const size_t calls_at = (cells_bytes + 255) & ~(size_t)255;
@@ -155,6 +200,7 @@ static int alleles_on_device(const AlleleHostIn& h, const int64_t* d_col_off, co
         Shipment sh;
         sh.add(h_cells.p, d_cells.p, cells_bytes); sh.add((char*)h_cells.p + calls_at, work + a.L.n_calls, calls_bytes);
         sh.add((char*)h_cells.p + calls_at + ((calls_bytes + 255) & ~(size_t)255), work + a.wide_count, 4);
+        if (rq) { sh.add(h_rows.p, d_rows.p, rows_bytes); sh.add((char*)h_rows.p + wro_at, work + rw.L.win_row_off, ((size_t)W + 1) * 8); sh.add((char*)h_rows.p + status_at, work + rw.L.status, 4); }
         if (int rc = sh.launch(st, 64)) return rc;
     }
     if (int rc = stream_wait(st)) return rc;
@@ -176,6 +222,21 @@ static int alleles_on_device(const AlleleHostIn& h, const int64_t* d_col_off, co
     if (int rc = ev_plan.ms(&ms_plan)) { hs::alleles_free(t); return rc; }
     t->t_kernel_ms = (double)ms + ms_plan; t->n_entries = h.n_entries;
     t->n_wide_columns = S && W ? *(const int32_t*)((const char*)h_cells.p + calls_at + ((calls_bytes + 255) & ~(size_t)255)) : 0;
+    if (rq) {
+        hs::RecruitRaw rr;
+        rr.n_windows = W; rr.win_contig = h.win_contig.data(); rr.win_start = h.win_start.data(); rr.win_end = h.win_end.data();
+        rr.win_snp_first = raw.win_snp_first; rr.win_snp_last = raw.win_snp_last;
+        rr.win_row_off = (const int64_t*)((const char*)h_rows.p + wro_at); rr.rows = (const hs_recruit_row*)h_rows.p;
+        rr.contig_base = h.contig_base; rr.params = rq->params;
+        hs_recruit_table* rt = nullptr;
+        if (*(const int32_t*)((const char*)h_rows.p + status_at) != 0) err = "recruit table: the rows or counters did not fit their arrays";
+        else rt = hs::recruit_assemble(rr, err);
+        float ms_a = 0, ms_b = 0;
+        if (rt && (ev_rplan.ms(&ms_a) || ev_rrows.ms(&ms_b))) { hs::recruit_free(rt); hs::alleles_free(t); return HS_EHIP; }
+        if (!rt) { hs::alleles_free(t); set_error(err); return HS_EINVAL; }
+        rt->t_kernel_ms = (double)ms_a + ms_b; rt->n_counter_words = n_ctr; rt->n_entries = h.n_entries;
+        rq->table = rt;
+    }
     *out = t;
     return HS_OK;
 }
@@ -199,7 +260,8 @@ static int allele_dense_labels(const hs::SrSparseLabels& sp, const std::vector<i
 // over from stage 3 where it packed them, or uploaded by stage 4 -- HS_COLUMNS_VIA_HOST, HS_PIPELINE_KEEP_COLUMNS, a group that lost SNPs to
 // rarest_strain_abundance), the labels go up as the per-window lists the group leaves and are spread on the device. `r` / `sp`: the group's
 // stage-4 result; `cv`: its stage-3 result (contigs [c0, c0 + r->n_contigs) of the batch).
-static int pipeline_group_alleles(const hs_sr_result* r, const hs::SrSparseLabels& sp, const hs_cv_result* cv, float rsa, int c0, HipSrOps& ops, hs_allele_table** out) {
+static int pipeline_group_alleles(const hs_sr_result* r, const hs::SrSparseLabels& sp, const hs_cv_result* cv, float rsa, int c0, HipSrOps& ops, hs_allele_table** out,
+                                  RecruitReq* rq = nullptr) {
     const int C = r->n_contigs;
     AlleleHostIn h;
     h.contig_base = c0;
@@ -225,12 +287,21 @@ static int pipeline_group_alleles(const hs_sr_result* r, const hs::SrSparseLabel
         raw.cell_off = &zero;
         *out = hs::alleles_assemble(raw, err);
         if (!*out) { set_error(err); return HS_EINVAL; }
+        if (rq) {      // (no rows either; the table still says how many windows the group has)
+            const std::vector<int32_t> none((size_t)W + 1, 0);
+            const std::vector<int64_t> row_off((size_t)W + 1, 0);
+            hs::RecruitRaw rr;
+            rr.n_windows = W; rr.win_contig = h.win_contig.data(); rr.win_start = h.win_start.data(); rr.win_end = h.win_end.data();
+            rr.win_snp_first = none.data(); rr.win_snp_last = none.data(); rr.win_row_off = row_off.data(); rr.contig_base = c0; rr.params = rq->params;
+            rq->table = hs::recruit_assemble(rr, err);
+            if (!rq->table) { set_error(err); return HS_EINVAL; }
+        }
         return HS_OK;
     }
     DBuf d_labels, d_ro, d_ids, d_lab, d_lo;
     UploadPack pk;
     if (int rc = allele_dense_labels(sp, h.label_off, d_labels, pk, d_ro, d_ids, d_lab, d_lo, ops.stream)) return rc;
-    return alleles_on_device(h, ops.d_col_off.as<int64_t>(), ops.d_col_idx.as<int32_t>(), ops.d_col_code.as<uint8_t>(), d_labels.as<int32_t>(), ops.kc, ops.stream, out);
+    return alleles_on_device(h, ops.d_col_off.as<int64_t>(), ops.d_col_idx.as<int32_t>(), ops.d_col_code.as<uint8_t>(), d_labels.as<int32_t>(), ops.kc, ops.stream, out, rq);
 }
 
 }  // namespace
@@ -259,7 +330,8 @@ int hs_group_alleles(const int64_t* d_col_off, const int32_t* d_col_idx, const u
     return d_cells ? allele_cells_launch(in, (char*)d_work, a, d_cells, cells_cap, st) : allele_plan_launch(in, (char*)d_work, a, st);
 }
 
-int hs_haplotype_alleles(const hs_sr_contig* contigs, int32_t n_contigs, const hs_sr_result* sr, hs_allele_table** table) {
+// (hs_recruit_reads of hs_capi_recruit.inc is the same call with a RecruitReq)
+static int haplotype_tables(const hs_sr_contig* contigs, int32_t n_contigs, const hs_sr_result* sr, hs_allele_table** table, RecruitReq* rq) {
     if (int rc = require_device()) return rc;
     if (!contigs || !sr || !table || n_contigs < 0 || sr->n_contigs != n_contigs) { set_error("hs_haplotype_alleles: the result does not describe these contigs"); return HS_EINVAL; }
     if (!sr->labels && sr->win_off[n_contigs] > 0 && sr->label_off[sr->win_off[n_contigs]] > 0) { set_error("hs_haplotype_alleles: the result has no dense labels"); return HS_EINVAL; }
@@ -319,7 +391,11 @@ int hs_haplotype_alleles(const hs_sr_contig* contigs, int32_t n_contigs, const h
         }
     }
     KernelClock kc;
-    return alleles_on_device(h, d_co.as<int64_t>(), d_ci.as<int32_t>(), d_cc.as<uint8_t>(), d_labels.as<int32_t>(), kc, st, table);
+    return alleles_on_device(h, d_co.as<int64_t>(), d_ci.as<int32_t>(), d_cc.as<uint8_t>(), d_labels.as<int32_t>(), kc, st, table, rq);
+}
+
+int hs_haplotype_alleles(const hs_sr_contig* contigs, int32_t n_contigs, const hs_sr_result* sr, hs_allele_table** table) {
+    return haplotype_tables(contigs, n_contigs, sr, table, nullptr);
 }
 
 }  // extern "C"

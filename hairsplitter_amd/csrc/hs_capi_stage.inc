@@ -137,6 +137,9 @@ struct hs_pipeline {
     std::vector<int64_t> sp_off; std::vector<int32_t> sp_ids, sp_labels;      // (the last call's, contig order: hs_pipeline_sparse_labels)
     bool alleles = false;           // HS_PIPELINE_ALLELES: every group crosses its labels with its SNP columns at the end of its chain
     hs_allele_table* allele_table = nullptr;      // (the last call's, contig order: hs_pipeline_alleles)
+    bool recruit = false;           // HS_PIPELINE_RECRUIT: every group also recruits its windows' unlabelled reads behind its allele cells
+    hs_recruit_params recruit_params = hs_recruit_params_default();
+    hs_recruit_table* recruit_table = nullptr;    // (the last call's, contig order: hs_pipeline_recruits)
 
     int device = 0;        // = batch->device: the group threads bind themselves to it (a new thread starts on device 0)
     std::vector<int> thread_device;   // what every group thread found current after binding (hs_pipeline_thread_devices)
@@ -245,6 +248,7 @@ int hs_pipeline_set_option(hs_pipeline* p, int32_t option, int64_t value) {
     if (option == HS_PIPELINE_KEEP_COLUMNS) { p->keep_columns = value != 0; return HS_OK; }
     if (option == HS_PIPELINE_SPARSE_LABELS) { p->sparse_labels = value != 0; return HS_OK; }
     if (option == HS_PIPELINE_ALLELES) { p->alleles = value != 0; return HS_OK; }
+    if (option == HS_PIPELINE_RECRUIT) { p->recruit = value != 0; return HS_OK; }
     set_error("hs_pipeline_set_option: unknown option"); return HS_EINVAL;
 }
 int hs_pipeline_groups(const hs_pipeline* p) { return p ? (int)p->ranges.size() : 0; }
@@ -260,6 +264,12 @@ int hs_pipeline_sparse_labels(const hs_pipeline* p, const int64_t** win_row_off,
     return HS_OK;
 }
 const hs_allele_table* hs_pipeline_alleles(const hs_pipeline* p) { return p ? p->allele_table : nullptr; }
+const hs_recruit_table* hs_pipeline_recruits(const hs_pipeline* p) { return p ? p->recruit_table : nullptr; }
+int hs_pipeline_set_recruit_params(hs_pipeline* p, const hs_recruit_params* params) {
+    if (!p || !params || !hs::recruit_params_valid(*params)) { set_error("hs_pipeline_set_recruit_params: null argument or thresholds out of range"); return HS_EINVAL; }
+    p->recruit_params = *params;
+    return HS_OK;
+}
 const hs_cv_result* hs_pipeline_group_cv(const hs_pipeline* p, int32_t g) { return (p && g >= 0 && g < (int32_t)p->cv.size()) ? p->cv[(size_t)g] : nullptr; }
 // the device every contig-group thread is bound to (-1: not bound yet / failed); returns the number of groups
 int hs_pipeline_thread_devices(hs_pipeline* p, int32_t* out, int32_t cap) {
@@ -279,6 +289,7 @@ void hs_pipeline_destroy(hs_pipeline* p) {
     (void)bind_device(p->device);
     p->drop_cv();
     hs::alleles_free(p->allele_table);
+    hs::recruit_free(p->recruit_table);
     delete p;
 }
 
@@ -534,12 +545,18 @@ struct GroupCall {
     std::vector<hs::SrSparseLabels> sparse;      // the groups leave their labels per window; concat_sr_parts spreads them
     GroupMeeting* meet;      // the fused call only: its groups bring up their own share of the pileup and meet before stage 4
     std::vector<hs_allele_table*> allele_parts;      // HS_PIPELINE_ALLELES: the groups' shares of the table
-    ~GroupCall() { for (hs_allele_table* t : allele_parts) hs::alleles_free(t); }
+    std::vector<hs_recruit_table*> recruit_parts;    // HS_PIPELINE_RECRUIT: the groups' shares of the recruit table
+    ~GroupCall() { for (hs_allele_table* t : allele_parts) hs::alleles_free(t); for (hs_recruit_table* t : recruit_parts) hs::recruit_free(t); }
 };
 
 // the groups' shares of the allele table, contig order; the previous call's table goes
 static int pipeline_merge_alleles(hs_pipeline* p, GroupCall& call) {
     hs::alleles_free(p->allele_table); p->allele_table = nullptr;
+    hs::recruit_free(p->recruit_table); p->recruit_table = nullptr;
+    if (p->recruit) {
+        p->recruit_table = hs::recruit_concat(std::vector<const hs_recruit_table*>(call.recruit_parts.begin(), call.recruit_parts.end()));
+        if (!p->recruit_table) { set_error("recruit table: out of memory"); return HS_EINVAL; }
+    }
     if (!p->alleles) return HS_OK;
     p->allele_table = hs::alleles_concat(std::vector<const hs_allele_table*>(call.allele_parts.begin(), call.allele_parts.end()));
     if (!p->allele_table) { set_error("allele table: out of memory"); return HS_EINVAL; }
@@ -583,7 +600,10 @@ static int pipeline_group_step(hs_pipeline* p, GroupCall& call, int g) {
     if (!via_host) ops.adopt_columns(cv_ops);
     if (int r = hs::sr_run_from_cv(ops, meta, c0, c1, cv, error_rate, call.rarest_strain_abundance, call.low_memory, call.amplicon, call.seed, per, call.window_size,
                                    &call.parts[(size_t)g], &call.sparse[(size_t)g], &p->sr_keep[(size_t)g])) return fail(r);
-    if (p->alleles) {
+    if (p->recruit) {      // (the cells are formed on the device either way; the merge keeps the allele shares only under HS_PIPELINE_ALLELES)
+        if (int r = pipeline_group_recruit(call.parts[(size_t)g], call.sparse[(size_t)g], cv, call.rarest_strain_abundance, c0, ops, p->recruit_params,
+                                           &call.allele_parts[(size_t)g], &call.recruit_parts[(size_t)g])) return fail(r);
+    } else if (p->alleles) {
         if (int r = pipeline_group_alleles(call.parts[(size_t)g], call.sparse[(size_t)g], cv, call.rarest_strain_abundance, c0, ops, &call.allele_parts[(size_t)g])) return fail(r);
     }
     // HS_PIPELINE_KEEP_COLUMNS: the entries came down beside stage 4. The two-call form copies them; the fused call's result points into
@@ -601,7 +621,7 @@ int hs_pipeline_run(hs_pipeline* p, float automatic_snp_threshold, float error_r
     const int G = (int)p->ranges.size();
     if (window_size <= 0) window_size = pipeline_window_size(p->batch, amplicon != 0);
     GroupCall call{automatic_snp_threshold, error_rate, rarest_strain_abundance, low_memory, amplicon, seed, pipeline_threads_per_group(n_threads, G), window_size,
-                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), nullptr, std::vector<hs_allele_table*>((size_t)G, nullptr)};
+                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), nullptr, std::vector<hs_allele_table*>((size_t)G, nullptr), std::vector<hs_recruit_table*>((size_t)G, nullptr)};
     hs::set_trace_origin();
     p->k2_order.reset();
     const int rc = p->run([&](int g) { return pipeline_group_step(p, call, g); });
@@ -634,7 +654,7 @@ int hs_pipeline_run_fused(hs_pipeline* p, float automatic_snp_threshold, float r
     GroupMeeting meet;
     meet.md.assign((size_t)C, 0.f);
     GroupCall call{automatic_snp_threshold, 0.f, rarest_strain_abundance, low_memory, amplicon, seed, pipeline_threads_per_group(n_threads, G), window_size,
-                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), &meet, std::vector<hs_allele_table*>((size_t)G, nullptr)};
+                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), &meet, std::vector<hs_allele_table*>((size_t)G, nullptr), std::vector<hs_recruit_table*>((size_t)G, nullptr)};
     hs::set_trace_origin();
     p->k2_order.reset();
     // a group that is gone (its job failed, or its thread never bound to the device) releases whoever waits for it at the meeting point

@@ -17,6 +17,7 @@
 #include "hs_driver.h"
 #include "hs_job_rules.h"
 #include "hs_alleles_host.h"
+#include "hs_recruit_host.h"
 
 namespace {
 
@@ -251,8 +252,11 @@ extern "C" int hs_separate_reads_main(int argc, char** argv) {
     }
     // HS_ALLELES=1: <outfile>.alleles.tsv is written too, from the labels and the columns of this run: the precomputed .gro has neither
     const bool want_alleles = []() { const char* e = std::getenv("HS_ALLELES"); return e && e[0] && e[0] != '0'; }();
+    // HS_RECRUIT=1: <outfile>.recruit.tsv (the recruit table of this run at the default thresholds) and <outfile>.recruited.gro (the run's labels
+    // after hs_recruit_apply) are written too; <outfile> itself is what it is without the variable
+    const bool want_recruit = []() { const char* e = std::getenv("HS_RECRUIT"); return e && e[0] && e[0] != '0'; }();
     // the .gro HS_call_variants left for exactly this call (same .col, same arguments, no ploidies): copied, no device needed
-    if (!want_alleles && ploidy_of.empty() && hs::take_gro_companion(columns_file, error_rate, rsa, low_memory, amplicon, seed, outfile, num_threads) == 1) {
+    if (!want_alleles && !want_recruit && ploidy_of.empty() && hs::take_gro_companion(columns_file, error_rate, rsa, low_memory, amplicon, seed, outfile, num_threads) == 1) {
         clk.lap("the precomputed .gro of this call (.col.hsgro)");
         return 0;
     }
@@ -283,20 +287,37 @@ extern "C" int hs_separate_reads_main(int argc, char** argv) {
     clk.lap("hs_sr_run");
     hs::write_gro(cs, res, outfile, num_threads);
     clk.lap("write .gro");
-    if (want_alleles) {
+    if (want_alleles || want_recruit) {
         hs_allele_table* table = nullptr;
-        if (int rc = hs_haplotype_alleles(hc.data(), (int32_t)hc.size(), res, &table)) {
+        hs_recruit_table* recruits = nullptr;
+        if (int rc = want_recruit ? hs_recruit_reads(hc.data(), (int32_t)hc.size(), res, nullptr, &table, &recruits) : hs_haplotype_alleles(hc.data(), (int32_t)hc.size(), res, &table)) {
             std::cout << "ERROR: " << hs_last_error() << " (" << rc << ")" << std::endl;
             return 1;
         }
         std::vector<const char*> names;
         for (const hs::ColFileContig& c : cs) names.push_back(c.name.c_str());
-        const std::string text = hs::alleles_text(table, names.data(), (int32_t)names.size());
-        std::ofstream o(outfile + ".alleles.tsv", std::ios::binary);
-        o.write(text.data(), (std::streamsize)text.size());
-        if (!o) { std::cout << "ERROR: could not write " << outfile << ".alleles.tsv" << std::endl; return 1; }
+        if (want_alleles) {
+            const std::string text = hs::alleles_text(table, names.data(), (int32_t)names.size());
+            std::ofstream o(outfile + ".alleles.tsv", std::ios::binary);
+            o.write(text.data(), (std::streamsize)text.size());
+            if (!o) { std::cout << "ERROR: could not write " << outfile << ".alleles.tsv" << std::endl; return 1; }
+        }
         hs_allele_table_destroy(table);
         clk.lap("allele table");
+        if (want_recruit) {
+            const std::string text = hs::recruit_text(recruits, names.data(), (int32_t)names.size());
+            { std::ofstream o(outfile + ".recruit.tsv", std::ios::binary); o.write(text.data(), (std::streamsize)text.size()); if (!o) { std::cout << "ERROR: could not write " << outfile << ".recruit.tsv" << std::endl; return 1; } }
+            // the run's labels with every assigned row applied, through the same writer
+            const int64_t W = res->win_off[res->n_contigs], n_labels = res->label_off[W];
+            std::vector<int32_t> applied((size_t)std::max<int64_t>(n_labels, 1));
+            if (hs_recruit_apply(recruits, res->label_off, res->labels, applied.data(), n_labels)) { std::cout << "ERROR: the recruit table does not describe the labels of this run" << std::endl; return 1; }
+            hs_sr_result shown = *res;
+            shown.labels = applied.data();
+            { std::ofstream o(outfile + ".recruited.gro"); }      // (write_gro appends)
+            hs::write_gro(cs, &shown, outfile + ".recruited.gro", num_threads);
+            hs_recruit_table_destroy(recruits);
+            clk.lap("recruit table");
+        }
     }
     if (!g_leak_at_exit) hs_sr_result_destroy(res);
     return 0;

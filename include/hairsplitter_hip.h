@@ -687,6 +687,76 @@ int hs_group_alleles(const int64_t* d_col_off, const int32_t* d_col_idx, const u
 int hs_haplotype_alleles(const hs_sr_contig* contigs, int32_t n_contigs, const hs_sr_result* sr_result, hs_allele_table** table);
 
 /* ------------------------------------------------------------------------------------------------
+ * A window's unlabelled reads recruited to its groups: stage 4 labels only the reads present at a window's first AND last SNP
+ * (separate_reads.cpp:1590-1622); every other read that crosses the window is -2 there, and the reads of clusters below the size filter
+ * are -1 (separate_reads.cpp:938). Such a read still carries alleles at some of the window's SNPs; here they are held against the calls
+ * of the allele table (separate_reads.cpp:1056-1113 on the final labels), on the device that holds both.
+ * Windows, SNPs, groups and cells are exactly the allele table's. A ROW is a pair (window w, read r) where r has at least one entry in a
+ * SNP column of w (0 <= r < n_reads of the contig; other indices are ignored) and r's label in w is selected by `which`:
+ * HS_RECRUIT_ABSENT -2, HS_RECRUIT_UNCLUSTERED -1, HS_RECRUIT_LABELLED >= 0 (evaluation rows: they never change a label). A window with
+ * SNPs but no group has no rows; a read in two windows has two independent rows. Rows are window-major, reads ascending.
+ * For group k of w, over every entry (r, code) of r in a column s of w, duplicates counted: call(s, k) == 0: not counted for k;
+ * code == call(s, k): a match (m_k); any other code: a mismatch (x_k). Any of the 125 codes can match. Counters are 32-bit; n_entries =
+ * the read's entries in the window's columns. score_k = m_k - x_k, signed. best = the group of largest score, the smallest id among equal
+ * scores; second = the same among the others (one group: -1, counts 0). assigned iff (a) m_best + x_best >= min_informative, (b) one group
+ * or score_best - score_second >= min_margin, (c) x_best * mismatch_den <= mismatch_num * (m_best + x_best), in 64 bits.
+ * ---------------------------------------------------------------------------------------------- */
+#define HS_RECRUIT_ABSENT 1
+#define HS_RECRUIT_UNCLUSTERED 2
+#define HS_RECRUIT_LABELLED 4
+/* separate_reads.cpp:1590-1622, 938, 1056-1113. Refused with HS_EINVAL unless min_informative >= 1, min_margin >= 1 (equal scores never
+ * assign), mismatch_den >= 1 and 0 <= mismatch_num <= mismatch_den. */
+typedef struct hs_recruit_params { int32_t which, min_informative, min_margin, mismatch_num, mismatch_den; } hs_recruit_params;
+/* which = ABSENT | UNCLUSTERED, min_informative 3, min_margin 2, mismatch 1/4. These defaults are PLACEHOLDERS of the interface: nobody
+ * has validated or tuned them (separate_reads.cpp:1590-1622, 938, 1056-1113 has no such step to take figures from). */
+hs_recruit_params hs_recruit_params_default(void);
+/* separate_reads.cpp:1590-1622, 938, 1056-1113: one row; groups as ids, -1 = none. 40 bytes. */
+typedef struct hs_recruit_row {
+    int32_t read, label, best_group, second_group;
+    uint32_t m_best, x_best, m_second, x_second, n_entries;
+    int32_t assigned;
+} hs_recruit_row;
+typedef struct hs_recruit_table {   /* separate_reads.cpp:1590-1622, 938, 1056-1113; host memory; release with hs_recruit_table_destroy */
+    int64_t n_windows, n_rows, n_assigned;
+    int32_t *win_contig, *win_start, *win_end;   /* [n_windows] the allele table's windows (those that have SNPs), same order */
+    int64_t* win_index;                          /* [n_windows] the window's index among ALL windows of the call (label_off of its result) */
+    int64_t* win_row_off;                        /* [n_windows + 1] into rows */
+    hs_recruit_row* rows;                        /* [n_rows] */
+    hs_recruit_params params;                    /* the thresholds used */
+    int64_t n_call_windows;                      /* all windows of the call, with or without SNPs */
+    int64_t n_counter_words;                     /* 32-bit counters the kernels kept: 1 + 2 * groups per row */
+    int64_t n_entries;                           /* column entries the count kernel read */
+    double t_kernel_ms;                          /* hipEvent time of the recruit kernels alone (0 on an untimed step) */
+} hs_recruit_table;
+void hs_recruit_table_destroy(hs_recruit_table* t);   /* separate_reads.cpp:1590-1622, 938, 1056-1113 */
+/* The stage-level call (separate_reads.cpp:1590-1622, 938, 1056-1113), twin of hs_haplotype_alleles with the same input rules. params ==
+ * NULL: the defaults. alleles may be NULL; otherwise *alleles receives the allele table of the same call. On an error *out stays NULL. */
+int hs_recruit_reads(const hs_sr_contig* contigs, int32_t n_contigs, const hs_sr_result* sr_result, const hs_recruit_params* params,
+                     hs_allele_table** alleles, hs_recruit_table** out);
+/* The kernel-level call (separate_reads.cpp:1590-1622, 938, 1056-1113), twin of hs_group_alleles with the same inputs, asynchronous on
+ * `stream`, in two steps over d_work (hs_group_recruit_layout; the allele plan lies at its front, `alleles` gives its parts):
+ *   d_cells == NULL: the allele plan, then `flag` [n_labels] (1 = the read's slot of the dense label layout is a row), `row_idx`
+ *     [n_labels + 1] (row of every flagged slot; row_idx[n_labels] = rows) and `ctr_off` [n_labels + 1] (first counter word of every
+ *     flagged slot; ctr_off[n_labels] = 32-bit words to make room for in d_counters);
+ *   d_cells != NULL: the cells, then the counters and d_rows [rows], `win_row_off` [n_windows + 1] over all windows of the call. Nothing
+ *     is written beyond rows_cap rows or counters_cap words; `status` is 0, or 1 when either did not suffice. */
+typedef struct hs_recruit_layout { hs_allele_layout alleles; int64_t flag, row_idx, ctr_off, win_row_off, status, internal, total_bytes; } hs_recruit_layout;
+int hs_group_recruit_layout(int32_t n_snps, int32_t n_windows, int64_t n_labels, hs_recruit_layout* out);
+int hs_group_recruit(const int64_t* d_col_off, const int32_t* d_col_idx, const uint8_t* d_col_code,
+                     const uint8_t* d_snp_ref, const uint8_t* d_snp_alt, const int32_t* d_snp_pos, const int32_t* d_snp_contig, int32_t n_snps,
+                     const int64_t* d_win_off, const int32_t* d_win_start, const int32_t* d_win_end, int32_t n_contigs, int32_t n_windows,
+                     const int64_t* d_label_off, const int32_t* d_labels, int64_t n_labels, const hs_recruit_params* params,
+                     void* d_work, hs_allele_cell* d_cells, int64_t cells_cap, uint32_t* d_counters, int64_t counters_cap,
+                     hs_recruit_row* d_rows, int64_t rows_cap, void* stream);
+/* Device-free (separate_reads.cpp:1590-1622, 938, 1056-1113): labels_out = labels_in, except that every assigned row whose old label is
+ * < 0 gets its best_group. label_off: of the result the table was formed on ([n_call_windows + 1]); LABELLED rows never change anything. */
+int hs_recruit_apply(const hs_recruit_table* table, const int64_t* label_off, const int32_t* labels_in, int32_t* labels_out, int64_t n_labels);
+/* <outfile>.recruit.tsv of HS_separate_reads under HS_RECRUIT=1 (separate_reads.cpp:1590-1622, 938, 1056-1113 prints nothing): per window
+ * "WINDOW <contig> <start> <end>", then per row "READ <index> <label> <best> <m> <x> <second> <m2> <x2> <n_entries> <0|1>", tab-separated.
+ * names[c] = name of contig c (NULL: indices). *out is malloc'ed: hs_free_host. */
+int hs_recruit_text(const hs_recruit_table* t, const char* const* names, int32_t n_names, char** out);
+
+/* ------------------------------------------------------------------------------------------------
  * Both stages over one resident batch with the contigs processed as n_groups consecutive ranges on persistent host threads
  * (one HIP stream and one worker pool each). hs_pipeline_select runs hs_cv_select (the streaming kernels, once over the whole
  * batch) and returns the per-contig mean distances, which only need K1's per-record counters; the caller forms the error
@@ -739,6 +809,14 @@ int hs_pipeline_thread_devices(hs_pipeline* p, int32_t* out, int32_t cap);
  * no wait is added to the step. */
 #define HS_PIPELINE_ALLELES 4
 const hs_allele_table* hs_pipeline_alleles(const hs_pipeline* p);   /* NULL before the first call with HS_PIPELINE_ALLELES */
+/* HS_PIPELINE_RECRUIT != 0: every contig group also recruits its windows' unlabelled reads (separate_reads.cpp:1590-1622, 938, 1056-1113;
+ * hs_recruit_table above) behind its allele cells, from the dense labels that share uploads, in the two host waits it makes anyway. It
+ * implies the cells on the device; the allele table itself is exposed only if HS_PIPELINE_ALLELES is set too. hs_pipeline_recruits returns
+ * the call's table, contig order, valid until the next call. Thresholds: hs_pipeline_set_recruit_params (HS_EINVAL for a refused set; the
+ * defaults until then). Off (the default): no launch, allocation or wait is added to the step. */
+#define HS_PIPELINE_RECRUIT 8
+const hs_recruit_table* hs_pipeline_recruits(const hs_pipeline* p);   /* NULL before the first call with HS_PIPELINE_RECRUIT */
+int hs_pipeline_set_recruit_params(hs_pipeline* p, const hs_recruit_params* params);
 int hs_pipeline_set_option(hs_pipeline* p, int32_t option, int64_t value);
 int hs_pipeline_groups(const hs_pipeline* p);                                  /* number of contig groups */
 int hs_pipeline_group_range(const hs_pipeline* p, int32_t g, int32_t* c0, int32_t* c1);   /* contigs [c0, c1) of group g */
