@@ -935,16 +935,18 @@ def alleles_lds_capacity() -> int:
     return int(load().hs_alleles_lds_capacity())
 
 
+def _table_array(ptr, n, dtype) -> np.ndarray:
+    """a copy of the n elements a table's pointer field points to"""
+    if n == 0:
+        return np.zeros(0, dtype)
+    return np.ctypeslib.as_array(ptr, (n,)).astype(dtype, copy=True)
+
+
 def _allele_table_to_dict(tp) -> Dict:
     """a copy of an hs_allele_table as numpy arrays; "cells" has the dtype ALLELE_CELL"""
     t = tp.contents
     W, S, G, N = int(t.n_windows), int(t.n_snps), int(t.n_groups), int(t.n_cells)
-
-    def a(ptr, n, dtype):
-        if n == 0:
-            return np.zeros(0, dtype)
-        return np.ctypeslib.as_array(ptr, (n,)).astype(dtype, copy=True)
-
+    a = _table_array
     cells = np.zeros(N, ALLELE_CELL)
     if N:
         C.memmove(cells.ctypes.data, t.cells, N * ALLELE_CELL.itemsize)
@@ -962,23 +964,35 @@ def haplotype_alleles(contigs: Sequence[Dict], sr: Dict) -> Dict:
     require_gpu()
     lib = load()
     arr, keep = _sr_contig_array(contigs)
-    Cn = len(contigs)
-    wo, ws, we = _np(sr["win_off"], np.int64), _np(sr["win_start"], np.int32), _np(sr["win_end"], np.int32)
-    lo, lab = _np(sr["label_off"], np.int64), _np(sr["labels"], np.int32)
-    if len(ws) == 0:
-        ws, we = np.zeros(1, np.int32), np.zeros(1, np.int32)
-    if len(lab) == 0:
-        lab = np.zeros(1, np.int32)
-    r = SrResult()
-    r.n_contigs = Cn
-    r.win_off = _hp(wo, C.c_int64); r.win_start = _hp(ws, C.c_int32); r.win_end = _hp(we, C.c_int32)
-    r.label_off = _hp(lo, C.c_int64); r.labels = _hp(lab, C.c_int32)
+    keep2 = []
+    r = _sr_struct(sr, len(contigs), keep2)
     tb = C.POINTER(AlleleTable)()
-    _check(lib.hs_haplotype_alleles(arr, C.c_int32(Cn), C.byref(r), C.byref(tb)))
+    _check(lib.hs_haplotype_alleles(arr, C.c_int32(len(contigs)), C.byref(r), C.byref(tb)))
     out = _allele_table_to_dict(tb)
     lib.hs_allele_table_destroy(tb)
-    del keep
+    del keep, keep2
     return out
+
+
+def _group_call_inputs(contigs: Sequence[Dict], sr: Dict, dev: str):
+    """the leading arguments hs_group_alleles and hs_group_recruit share -- the contigs' arrays one after the other on `dev`, the windows and labels
+    of `sr`, with their counts --, the tensors behind them, and (S, W, n_labels)"""
+    import torch
+    depth = [np.diff(_np(c["col_off"], np.int64)) for c in contigs]
+    col_off = np.concatenate([[0]] + [d for d in depth]).cumsum().astype(np.int64)
+    def cat(key, dt):      # column entries from where the contig's col_off begins
+        parts = [_np(c[key], dt)[int(c["col_off"][0]):int(c["col_off"][-1])] if key.startswith("col_") else _np(c[key], dt) for c in contigs]
+        return np.concatenate([np.zeros(0, dt)] + parts).astype(dt)
+
+    snp_contig = np.concatenate([np.zeros(0, np.int32)] + [np.full(len(c["snp_pos"]), k, np.int32) for k, c in enumerate(contigs)]).astype(np.int32)
+    S, W, n_labels = len(snp_contig), len(sr["win_start"]), int(sr["label_off"][-1])
+    up = lambda a, dt: torch.from_numpy(_np(a, dt) if len(a) else np.zeros(1, dt)).to(dev)
+    d = [up(col_off, np.int64), up(cat("col_idx", np.int32), np.int32), up(cat("col_code", np.uint8), np.uint8), up(cat("snp_ref", np.uint8), np.uint8),
+         up(cat("snp_alt", np.uint8), np.uint8), up(cat("snp_pos", np.int32), np.int32), up(snp_contig, np.int32)]
+    w = [up(sr["win_off"], np.int64), up(sr["win_start"], np.int32), up(sr["win_end"], np.int32)]
+    lab = [up(sr["label_off"], np.int64), up(sr["labels"], np.int32)]
+    args = [_p(x) for x in d] + [C.c_int32(S)] + [_p(x) for x in w] + [C.c_int32(len(contigs)), C.c_int32(W)] + [_p(x) for x in lab] + [C.c_int64(n_labels)]
+    return args, d + w + lab, (S, W, n_labels)
 
 
 def group_alleles(contigs: Sequence[Dict], sr: Dict) -> Dict:
@@ -988,27 +1002,13 @@ def group_alleles(contigs: Sequence[Dict], sr: Dict) -> Dict:
     require_gpu()
     lib = load()
     dev = "cuda:0"
-    depth = [np.diff(_np(c["col_off"], np.int64)) for c in contigs]
-    col_off = np.concatenate([[0]] + [d for d in depth]).cumsum().astype(np.int64)
-    def cat(key, dt):      # the contigs' arrays one after the other; column entries from where the contig's col_off begins
-        parts = [_np(c[key], dt)[int(c["col_off"][0]):int(c["col_off"][-1])] if key.startswith("col_") else _np(c[key], dt) for c in contigs]
-        return np.concatenate([np.zeros(0, dt)] + parts).astype(dt)
-
-    snp_contig = np.concatenate([np.zeros(0, np.int32)] + [np.full(len(c["snp_pos"]), k, np.int32) for k, c in enumerate(contigs)]).astype(np.int32)
-    S, W, Cn = len(snp_contig), len(sr["win_start"]), len(contigs)
-    n_labels = int(sr["label_off"][-1])
-    up = lambda a, dt: torch.from_numpy(_np(a, dt) if len(a) else np.zeros(1, dt)).to(dev)
-    d = [up(col_off, np.int64), up(cat("col_idx", np.int32), np.int32), up(cat("col_code", np.uint8), np.uint8), up(cat("snp_ref", np.uint8), np.uint8),
-         up(cat("snp_alt", np.uint8), np.uint8), up(cat("snp_pos", np.int32), np.int32), up(snp_contig, np.int32)]
-    w = [up(sr["win_off"], np.int64), up(sr["win_start"], np.int32), up(sr["win_end"], np.int32)]
-    lab = [up(sr["label_off"], np.int64), up(sr["labels"], np.int32)]
+    args, keep, (S, W, n_labels) = _group_call_inputs(contigs, sr, dev)
     L = AlleleLayout()
     _check(lib.hs_group_alleles_layout(C.c_int32(S), C.c_int32(W), C.c_int64(n_labels), C.byref(L)))
     work = torch.zeros(int(L.total_bytes), dtype=torch.uint8, device=dev)
 
     def call(cells, cap):
-        _check(lib.hs_group_alleles(*[_p(x) for x in d], C.c_int32(S), *[_p(x) for x in w], C.c_int32(Cn), C.c_int32(W), *[_p(x) for x in lab], C.c_int64(n_labels),
-                                    _p(work), _p(cells), C.c_int64(cap), C.c_void_p(0)))
+        _check(lib.hs_group_alleles(*args, _p(work), _p(cells), C.c_int64(cap), C.c_void_p(0)))
         torch.cuda.synchronize()
 
     call(None, 0)
@@ -1048,12 +1048,7 @@ def _recruit_table_to_dict(tp) -> Dict:
     """a copy of an hs_recruit_table as numpy arrays; "rows" has the dtype RECRUIT_ROW"""
     t = tp.contents
     W, R = int(t.n_windows), int(t.n_rows)
-
-    def a(ptr, n, dtype):
-        if n == 0:
-            return np.zeros(0, dtype)
-        return np.ctypeslib.as_array(ptr, (n,)).astype(dtype, copy=True)
-
+    a = _table_array
     rows = np.zeros(R, RECRUIT_ROW)
     if R:
         C.memmove(rows.ctypes.data, t.rows, R * RECRUIT_ROW.itemsize)
@@ -1153,28 +1148,14 @@ def group_recruit(contigs: Sequence[Dict], sr: Dict, params: Optional[Dict] = No
     require_gpu()
     lib = load()
     dev = "cuda:0"
-    depth = [np.diff(_np(c["col_off"], np.int64)) for c in contigs]
-    col_off = np.concatenate([[0]] + [d for d in depth]).cumsum().astype(np.int64)
-    def cat(key, dt):
-        parts = [_np(c[key], dt)[int(c["col_off"][0]):int(c["col_off"][-1])] if key.startswith("col_") else _np(c[key], dt) for c in contigs]
-        return np.concatenate([np.zeros(0, dt)] + parts).astype(dt)
-
-    snp_contig = np.concatenate([np.zeros(0, np.int32)] + [np.full(len(c["snp_pos"]), k, np.int32) for k, c in enumerate(contigs)]).astype(np.int32)
-    S, W, Cn = len(snp_contig), len(sr["win_start"]), len(contigs)
-    n_labels = int(sr["label_off"][-1])
-    up = lambda a, dt: torch.from_numpy(_np(a, dt) if len(a) else np.zeros(1, dt)).to(dev)
-    d = [up(col_off, np.int64), up(cat("col_idx", np.int32), np.int32), up(cat("col_code", np.uint8), np.uint8), up(cat("snp_ref", np.uint8), np.uint8),
-         up(cat("snp_alt", np.uint8), np.uint8), up(cat("snp_pos", np.int32), np.int32), up(snp_contig, np.int32)]
-    w = [up(sr["win_off"], np.int64), up(sr["win_start"], np.int32), up(sr["win_end"], np.int32)]
-    lab = [up(sr["label_off"], np.int64), up(sr["labels"], np.int32)]
+    args, keep, (S, W, n_labels) = _group_call_inputs(contigs, sr, dev)
     L = RecruitLayout()
     _check(lib.hs_group_recruit_layout(C.c_int32(S), C.c_int32(W), C.c_int64(n_labels), C.byref(L)))
     work = torch.full((int(L.total_bytes),), fill, dtype=torch.uint8, device=dev)
     prm = _recruit_params(params)
 
     def call(cells, cap, ctr, ctr_cap, rows, rows_cap):
-        _check(lib.hs_group_recruit(*[_p(x) for x in d], C.c_int32(S), *[_p(x) for x in w], C.c_int32(Cn), C.c_int32(W), *[_p(x) for x in lab], C.c_int64(n_labels),
-                                    C.byref(prm), _p(work), _p(cells), C.c_int64(cap), _p(ctr), C.c_int64(ctr_cap), _p(rows), C.c_int64(rows_cap), C.c_void_p(0)))
+        _check(lib.hs_group_recruit(*args, C.byref(prm), _p(work), _p(cells), C.c_int64(cap), _p(ctr), C.c_int64(ctr_cap), _p(rows), C.c_int64(rows_cap), C.c_void_p(0)))
         torch.cuda.synchronize()
 
     call(None, 0, None, 0, None, 0)

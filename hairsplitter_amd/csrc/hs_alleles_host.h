@@ -12,11 +12,7 @@
 
 #include "../../include/hairsplitter_hip.h"
 
-#if defined(__HIP__)
-#define HS_ALLELE_HD __host__ __device__
-#else
-#define HS_ALLELE_HD
-#endif
+#include "hs_rules.h"      // HS_HD
 
 namespace hs {
 
@@ -25,7 +21,7 @@ namespace hs {
 struct AlleleCounts {
     uint32_t n = 0, best = 0, second = 0, n_ref = 0, n_alt = 0;
     uint8_t best_code = 0;
-    HS_ALLELE_HD void add_run(uint8_t code, uint32_t count, uint8_t ref, uint8_t alt) {
+    HS_HD void add_run(uint8_t code, uint32_t count, uint8_t ref, uint8_t alt) {
         if (count == 0) return;
         n += count;
         if (code == ref) n_ref += count;
@@ -39,7 +35,7 @@ struct AlleleCounts {
 };
 struct AlleleCellValue { uint32_t n, best, second, n_ref, n_alt; uint8_t best_code, call; };
 // call = best_code, or 0 (undefined) when secondMax * 2 > max || nb * 0.5 > max (separate_reads.cpp:1100); a tie at the top is always undefined
-HS_ALLELE_HD inline AlleleCellValue allele_cell_finish(const AlleleCounts& c) {
+HS_HD inline AlleleCellValue allele_cell_finish(const AlleleCounts& c) {
     AlleleCellValue v;
     v.n = c.n; v.best = c.best; v.second = c.second; v.n_ref = c.n_ref; v.n_alt = c.n_alt; v.best_code = c.best_code;
     v.call = (c.n == 0 || 2u * c.second > c.best || c.n > 2u * c.best) ? (uint8_t)0 : c.best_code;

@@ -4,28 +4,34 @@ static_assert(sizeof(hs_allele_cell) == sizeof(hsdev::AlleleCell) && sizeof(hs_a
 
 namespace {
 
-// the parts of d_work (hs_allele_layout), 256-byte aligned. The small arrays lie in front (they go to the host in one shipment), then the
+// the two tables of one call (or of one contig group of a pipeline), until somebody takes them over: what is still here when the holder goes is freed
+struct TableFree { void operator()(hs_allele_table* t) const { hs::alleles_free(t); } void operator()(hs_recruit_table* t) const { hs::recruit_free(t); } };
+struct TablePair { std::unique_ptr<hs_allele_table, TableFree> alleles; std::unique_ptr<hs_recruit_table, TableFree> recruit; };
+
+// the parts of a work buffer, one after the other: 256-byte aligned, 4 bytes at least
+struct WorkParts {
+    int64_t o = 0;
+    int64_t take(int64_t bytes) { const int64_t at = o; o = (o + std::max<int64_t>(bytes, 4) + 255) & ~(int64_t)255; return at; }
+};
+// the parts of d_work (hs_allele_layout). The small arrays lie in front (they go to the host in one shipment), then the
 // group lists per window (room for one group per read) and one after the other; `internal`: has_snp [W], n_cells [S], the scans' tile sums
 // and offsets, the wide route's counter and list [S], then its slabs
 struct AlleleWork {
     hs_allele_layout L;
     int64_t has_snp, n_cells, tile_sum, wide_count, wide_list, slabs;
-    int n_tiles, n_tiles_w;
 };
 static AlleleWork allele_work(int32_t S, int32_t W, int64_t n_labels) {
     AlleleWork a;
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = o; o = (o + std::max<int64_t>(bytes, 4) + 255) & ~(int64_t)255; return at; };
-    a.n_tiles = (S + HS_SCAN_TILE - 1) / HS_SCAN_TILE; a.n_tiles_w = (W + HS_SCAN_TILE - 1) / HS_SCAN_TILE;
-    a.L.snp_win = take((int64_t)S * 4); a.L.grp_n = take((int64_t)W * 4);
-    a.L.win_snp_first = take((int64_t)W * 4); a.L.win_snp_last = take((int64_t)W * 4);      // (the two lie back to back: one clearing)
-    a.L.cell_off = take(((int64_t)S + 1) * 8); a.L.grp_off = take(((int64_t)W + 1) * 8); a.L.n_calls = take((int64_t)S * 4);
-    a.L.grp_ids = take(n_labels * 4); a.L.grp_pack = take(n_labels * 4);
-    a.L.internal = o;
-    a.has_snp = take((int64_t)W * 4); a.n_cells = take((int64_t)S * 4); a.tile_sum = take((int64_t)std::max(std::max(a.n_tiles, a.n_tiles_w), 1) * 16);
-    a.wide_count = take(4); a.wide_list = take((int64_t)S * 4);
-    a.slabs = take((int64_t)HS_ALLELE_WIDE_BLOCKS * HS_ALLELE_WIDE_KEYS * 4);
-    a.L.total_bytes = o;
+    WorkParts p;
+    a.L.snp_win = p.take((int64_t)S * 4); a.L.grp_n = p.take((int64_t)W * 4);
+    a.L.win_snp_first = p.take((int64_t)W * 4); a.L.win_snp_last = p.take((int64_t)W * 4);      // (the two lie back to back: one clearing)
+    a.L.cell_off = p.take(((int64_t)S + 1) * 8); a.L.grp_off = p.take(((int64_t)W + 1) * 8); a.L.n_calls = p.take((int64_t)S * 4);
+    a.L.grp_ids = p.take(n_labels * 4); a.L.grp_pack = p.take(n_labels * 4);
+    a.L.internal = p.o;
+    a.has_snp = p.take((int64_t)W * 4); a.n_cells = p.take((int64_t)S * 4); a.tile_sum = p.take((int64_t)std::max(scan_tiles(std::max(S, W)), 1) * 16);
+    a.wide_count = p.take(4); a.wide_list = p.take((int64_t)S * 4);
+    a.slabs = p.take((int64_t)HS_ALLELE_WIDE_BLOCKS * HS_ALLELE_WIDE_KEYS * 4);
+    a.L.total_bytes = p.o;
     return a;
 }
 
@@ -57,16 +63,19 @@ static int allele_plan_launch(const AlleleDevIn& in, char* work, const AlleleWor
                        in.d_win_start, in.d_win_end, in.n_contigs, snp_win, has_snp);
     hipLaunchKernelGGL(hsdev::k_allele_groups, dim3((unsigned)W), dim3(256), 0, st, in.d_label_off, in.d_labels, W, has_snp, grp_n, grp_ids);
     hipLaunchKernelGGL(hsdev::k_allele_cell_counts, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, snp_win, S, grp_n, n_cells, first, last);
-    hipLaunchKernelGGL(hsdev::k_scan_tile_sums, dim3((unsigned)a.n_tiles), dim3(256), 0, st, n_cells, S, tile_sum);
-    hipLaunchKernelGGL(hsdev::k_scan_tile_offsets, dim3(1), dim3(1024), 0, st, tile_sum, a.n_tiles, tile_sum + a.n_tiles, cell_off + S);
-    hipLaunchKernelGGL(hsdev::k_scan_apply, dim3((unsigned)a.n_tiles), dim3(256), 0, st, n_cells, S, tile_sum + a.n_tiles, cell_off);
-    // (the second scan takes the tile scratch over: the stream orders it behind the first)
-    hipLaunchKernelGGL(hsdev::k_scan_tile_sums, dim3((unsigned)a.n_tiles_w), dim3(256), 0, st, grp_n, W, tile_sum);
-    hipLaunchKernelGGL(hsdev::k_scan_tile_offsets, dim3(1), dim3(1024), 0, st, tile_sum, a.n_tiles_w, tile_sum + a.n_tiles_w, grp_off + W);
-    hipLaunchKernelGGL(hsdev::k_scan_apply, dim3((unsigned)a.n_tiles_w), dim3(256), 0, st, grp_n, W, tile_sum + a.n_tiles_w, grp_off);
+    if (int rc = exclusive_scan_launch(n_cells, S, cell_off, tile_sum, st)) return rc;
+    if (int rc = exclusive_scan_launch(grp_n, W, grp_off, tile_sum, st)) return rc;      // (it takes the tile scratch over: the stream orders it behind the first)
     hipLaunchKernelGGL(hsdev::k_allele_pack_groups, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, grp_n, grp_off, in.d_label_off, grp_ids, W, grp_pack);
     HS_HIP(hipGetLastError());
     return HS_OK;
+}
+
+// what the column kernels of both tables read, from the call and the plan in `work`
+static void column_args(const AlleleDevIn& in, char* work, const AlleleWork& a, int64_t cells_cap, hsdev::ColumnArgs& A) {
+    A.col_off = in.d_col_off; A.col_idx = in.d_col_idx; A.col_code = in.d_col_code; A.n_snps = in.n_snps;
+    A.snp_win = (const int32_t*)(work + a.L.snp_win); A.label_off = in.d_label_off; A.labels = in.d_labels; A.n_labels = in.n_labels; A.n_windows = in.n_windows;
+    A.grp_n = (const int32_t*)(work + a.L.grp_n); A.grp_ids = (const int32_t*)(work + a.L.grp_ids); A.cell_off = (const int64_t*)(work + a.L.cell_off);
+    A.cells_cap = cells_cap;
 }
 
 // the cells of the plan in `work`
@@ -75,10 +84,8 @@ static int allele_cells_launch(const AlleleDevIn& in, char* work, const AlleleWo
     if (S == 0) return HS_OK;
     if (in.n_windows == 0) { HS_HIP(hipMemsetAsync(work + a.L.n_calls, 0, (size_t)S * 4, st)); return HS_OK; }
     hsdev::AlleleArgs A;
-    A.col_off = in.d_col_off; A.col_idx = in.d_col_idx; A.col_code = in.d_col_code; A.snp_ref = in.d_snp_ref; A.snp_alt = in.d_snp_alt;
-    A.snp_win = (const int32_t*)(work + a.L.snp_win); A.label_off = in.d_label_off; A.labels = in.d_labels;
-    A.grp_n = (const int32_t*)(work + a.L.grp_n); A.grp_ids = (const int32_t*)(work + a.L.grp_ids); A.cell_off = (const int64_t*)(work + a.L.cell_off);
-    A.cells = reinterpret_cast<hsdev::AlleleCell*>(d_cells); A.cells_cap = cells_cap; A.n_calls = (int32_t*)(work + a.L.n_calls); A.n_snps = S;
+    column_args(in, work, a, cells_cap, A);
+    A.snp_ref = in.d_snp_ref; A.snp_alt = in.d_snp_alt; A.cells = reinterpret_cast<hsdev::AlleleCell*>(d_cells); A.n_calls = (int32_t*)(work + a.L.n_calls);
     A.wide_count = (int32_t*)(work + a.wide_count); A.wide_list = (int32_t*)(work + a.wide_list);
     HS_HIP(hipMemsetAsync(A.wide_count, 0, 4, st));
     hipLaunchKernelGGL(hsdev::k_allele_cells, dim3((unsigned)S), dim3(64), 0, st, A);
@@ -87,17 +94,13 @@ static int allele_cells_launch(const AlleleDevIn& in, char* work, const AlleleWo
     return HS_OK;
 }
 
-// The recruit table behind the cells (hs_capi_recruit.inc): asked for with a RecruitReq, it shares the work buffer, the stream and both host waits
+// The recruit table behind the cells (hs_capi_recruit.inc): asked for with its thresholds, it shares the work buffer, the stream and both host waits
 // (declared here, defined there: this file's stage-level route queues them between its own launches)
-struct RecruitWork { AlleleWork a; hs_recruit_layout L; int64_t ctr_n, tile_sum; int n_tiles; };      // the parts of d_work behind the allele plan's (hs_recruit_layout)
-struct RecruitReq { hs_recruit_params params; hs_recruit_table* table = nullptr; };
+struct RecruitWork { AlleleWork a; hs_recruit_layout L; int64_t ctr_n, tile_sum; };      // the parts of d_work behind the allele plan's (hs_recruit_layout)
 static RecruitWork recruit_work(int32_t S, int32_t W, int64_t n_labels);
 static int recruit_plan_launch(const AlleleDevIn& in, char* work, const RecruitWork& rw, const hs_recruit_params& params, hipStream_t st);
 static int recruit_rows_launch(const AlleleDevIn& in, char* work, const RecruitWork& rw, const hs_recruit_params& params, const hs_allele_cell* d_cells, int64_t cells_cap,
                                uint32_t* d_counters, int64_t counters_cap, hs_recruit_row* d_rows, int64_t rows_cap, hipStream_t st);
-struct AlleleHostIn;
-static int alleles_on_device(const AlleleHostIn& h, const int64_t* d_col_off, const int32_t* d_col_idx, const uint8_t* d_col_code, const int32_t* d_labels,
-                             KernelClock& kc, hipStream_t st, hs_allele_table** out, RecruitReq* rq = nullptr);
 
 // Host copies of what the call describes (the table is assembled from them) next to the device arrays
 struct AlleleHostIn {
@@ -107,138 +110,179 @@ struct AlleleHostIn {
     int32_t contig_base = 0;
     int64_t n_entries = 0;
     int64_t groups_bound = 0;      // no more groups than this over all windows (labels >= 0 of the call: every group has a read)
+    void windows_of(const hs_sr_result* r) {      // (win_contig: the caller's, it walks the contigs anyway)
+        const int64_t W = r->win_off[r->n_contigs];
+        win_off.assign(r->win_off, r->win_off + r->n_contigs + 1);
+        win_start.assign(r->win_start, r->win_start + W); win_end.assign(r->win_end, r->win_end + W);
+        label_off.assign(r->label_off, r->label_off + W + 1);
+        win_contig.resize((size_t)W);
+    }
 };
 
-// plan -> (one wait: the number of cells) -> cells -> (one wait) -> table. The columns and the dense labels are on the device already;
-// the small per-SNP / per-window arrays of `h` are uploaded here. Launches are accounted under HS_K_OTHER.
-static int alleles_on_device(const AlleleHostIn& h, const int64_t* d_col_off, const int32_t* d_col_idx, const uint8_t* d_col_code, const int32_t* d_labels,
-                             KernelClock& kc, hipStream_t st, hs_allele_table** out, RecruitReq* rq) {
-    const int64_t S64 = (int64_t)h.snp_pos.size(), W64 = (int64_t)h.win_start.size();
-    if (S64 > 0x7fffffff || W64 > 0x7fffffff) { set_error("allele table: more than 2^31 SNPs or windows in one call"); return HS_EINVAL; }
-    const int32_t S = (int32_t)S64, W = (int32_t)W64;
-    const int32_t C = (int32_t)h.win_off.size() - 1;
-    const int64_t n_labels = h.label_off.empty() ? 0 : h.label_off.back();
-    if (rq && n_labels > 0x7fffffff - HS_SCAN_TILE) { set_error("recruit table: more than 2^31 labels in one call"); return HS_EINVAL; }
-    const RecruitWork rw = rq ? recruit_work(S, W, n_labels) : RecruitWork();      // (its allele part is allele_work's: the recruit parts lie behind it)
-    const AlleleWork a = rq ? rw.a : allele_work(S, W, n_labels);
-    const size_t work_bytes = (size_t)(rq ? rw.L.total_bytes : a.L.total_bytes);
+// Where the two shipments of a stage-level call land in pinned host memory: byte offsets, 256-byte aligned. The first goes to one block:
+// the front of the work buffer as it lies on the device (snp_win .. grp_off, all in front of n_calls: the fields of hs_allele_layout hold
+// there too), the packed group lists, the 16-byte pieces of the recruit table's two totals. The second is sized by those totals and
+// goes to two blocks: cells, n_calls and the wide route's counter; rows, win_row_off and status.
+struct TableLanding {
+    int64_t groups_cap;      // (every group has a read)
+    size_t plan_bytes, grp_pack, n_rows_piece, n_ctr_piece, plan_size;
+    size_t cells_bytes, n_calls, calls_bytes, wide_count, cells_size;
+    size_t rows_bytes, win_row_off, win_row_off_bytes, status, rows_size;
+};
+static TableLanding table_landing(const AlleleWork& a, int32_t S, int32_t W, int64_t groups_cap, int64_t n_cells = 0, int64_t n_rows = 0) {
+    const auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    TableLanding t;
+    t.groups_cap = groups_cap;
+    t.plan_bytes = (size_t)a.L.n_calls; t.grp_pack = t.plan_bytes;
+    t.n_rows_piece = up(t.grp_pack + (size_t)groups_cap * 4); t.n_ctr_piece = t.n_rows_piece + 16; t.plan_size = t.n_rows_piece + 256;
+    t.cells_bytes = (size_t)n_cells * sizeof(hs_allele_cell); t.calls_bytes = (size_t)S * 4;
+    t.n_calls = up(t.cells_bytes); t.wide_count = t.n_calls + up(t.calls_bytes); t.cells_size = t.wide_count + 256;
+    t.rows_bytes = (size_t)n_rows * sizeof(hs_recruit_row); t.win_row_off_bytes = ((size_t)W + 1) * 8;
+    t.win_row_off = up(t.rows_bytes); t.status = t.win_row_off + up(t.win_row_off_bytes); t.rows_size = t.status + 256;
+    return t;
+}
+
+// One stage-level call between its parts: plan -> (one wait: the totals) -> cells, and rows behind them -> (one wait) -> the tables. The
+// columns and the dense labels are on the device already; the small per-SNP / per-window arrays of `h` are uploaded here. With `recruit`
+// (its thresholds; nullptr: the allele table alone) the recruit table's launches are queued behind the allele table's, in the same two
+// shipments. Launches are accounted under HS_K_OTHER.
+struct TableCall {
+    const AlleleHostIn& h; const hs_recruit_params* recruit; KernelClock& kc; hipStream_t st;
+    int32_t S = 0, W = 0;
+    int64_t n_labels = 0, n_cells = 0, n_rows = 0, n_ctr = 0;
+    RecruitWork rw;      // (its allele part is allele_work's: the recruit parts lie behind it)
+    TableLanding at;
+    AlleleDevIn in;
     DBuf d_work, d_sr, d_sa, d_sp, d_sc, d_wo, d_ws, d_we, d_lo, d_cells, d_counters, d_rows;
     UploadPack pk;
-    pk.add(h.snp_ref, d_sr); pk.add(h.snp_alt, d_sa); pk.add(h.snp_pos, d_sp); pk.add(h.snp_contig, d_sc);
-    pk.add(h.win_off, d_wo); pk.add(h.win_start, d_ws); pk.add(h.win_end, d_we); pk.add(h.label_off, d_lo);
-    if (int rc = pk.commit(st)) return rc;
-    if (int rc = d_work.alloc(work_bytes)) return rc;
-    AlleleDevIn in{d_col_off, d_col_idx, d_col_code, d_sr.as<uint8_t>(), d_sa.as<uint8_t>(), d_sp.as<int32_t>(), d_sc.as<int32_t>(), S,
-                   d_wo.as<int64_t>(), d_ws.as<int32_t>(), d_we.as<int32_t>(), C, W, d_lo.as<int64_t>(), d_labels, n_labels};
-    char* work = (char*)d_work.p;
-    EventPair ev_plan, ev, ev_rplan, ev_rrows;      // (the table's own kernel time: the plan's launches and the cells', not the wait between them)
-    if (int rc = ev_plan.init()) return rc;
-    if (int rc = ev.init()) return rc;
-    if (rq) { if (int rc = ev_rplan.init()) return rc; if (int rc = ev_rrows.init()) return rc; }
-    HS_HIP(ev_rec(ev_plan.a, st));
-    if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
-    if (int rc = allele_plan_launch(in, work, a, st)) return rc;
-    if (int rc = kc.end(4 * n_labels + 12 * (int64_t)S, st)) return rc;
-    HS_HIP(ev_rec(ev_plan.b, st));
-    if (rq) {      // the rows' flags and the two scans over them: queued with the plan, counted in the plan's wait
-        HS_HIP(ev_rec(ev_rplan.a, st));
+    HBuf h_plan, h_cells, h_rows;
+    EventPair ev_plan, ev_cells, ev_rplan, ev_rrows;      // (the tables' own kernel time: the plans' launches and the cells' and rows', not the wait between them)
+    const int64_t* h_n_rows = nullptr; const int64_t* h_n_ctr = nullptr;      // the two totals where the first shipment leaves them
+
+    char* work() const { return (char*)d_work.p; }
+    template <class Launch> int timed(EventPair& ev, int64_t bytes, Launch launch) {
+        HS_HIP(ev_rec(ev.a, st));
         if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
-        if (int rc = recruit_plan_launch(in, work, rw, rq->params, st)) return rc;
-        if (int rc = kc.end(4 * h.n_entries + 40 * n_labels, st)) return rc;
-        HS_HIP(ev_rec(ev_rplan.b, st));
+        if (int rc = launch()) return rc;
+        if (int rc = kc.end(bytes, st)) return rc;
+        HS_HIP(ev_rec(ev.b, st));
+        return HS_OK;
     }
-    // the plan comes to the host in one shipment (the table is assembled from it); its last word says how many cells to make room for
-    const size_t plan_bytes = (size_t)a.L.n_calls;      // snp_win .. grp_off lie in front of n_calls; the packed group lists follow them on the host
-    const int64_t groups_cap = std::min<int64_t>(std::max<int64_t>(h.groups_bound, 0), n_labels);      // (every group has a read)
-    HBuf h_plan;
-    const size_t totals_at = (plan_bytes + (size_t)groups_cap * 4 + 255) & ~(size_t)255;      // recruit: rows and counter words, behind the group lists
-    if (int rc = h_plan.alloc(totals_at + 256)) return rc;
-    {
+
+    // uploads, the plan(s), and their shipment: the plan comes to the host in one piece (the table is assembled from it) with the totals that size the rest
+    int queue_plan(const int64_t* d_col_off, const int32_t* d_col_idx, const uint8_t* d_col_code, const int32_t* d_labels) {
+        const int64_t S64 = (int64_t)h.snp_pos.size(), W64 = (int64_t)h.win_start.size();
+        if (S64 > 0x7fffffff || W64 > 0x7fffffff) { set_error("allele table: more than 2^31 SNPs or windows in one call"); return HS_EINVAL; }
+        S = (int32_t)S64; W = (int32_t)W64;
+        n_labels = h.label_off.empty() ? 0 : h.label_off.back();
+        if (recruit && n_labels > 0x7fffffff - HS_SCAN_TILE) { set_error("recruit table: more than 2^31 labels in one call"); return HS_EINVAL; }
+        rw = recruit_work(S, W, n_labels);
+        at = table_landing(rw.a, S, W, std::min<int64_t>(std::max<int64_t>(h.groups_bound, 0), n_labels));
+        pk.add(h.snp_ref, d_sr); pk.add(h.snp_alt, d_sa); pk.add(h.snp_pos, d_sp); pk.add(h.snp_contig, d_sc);
+        pk.add(h.win_off, d_wo); pk.add(h.win_start, d_ws); pk.add(h.win_end, d_we); pk.add(h.label_off, d_lo);
+        if (int rc = pk.commit(st)) return rc;
+        if (int rc = d_work.alloc((size_t)(recruit ? rw.L.total_bytes : rw.a.L.total_bytes))) return rc;
+        in = AlleleDevIn{d_col_off, d_col_idx, d_col_code, d_sr.as<uint8_t>(), d_sa.as<uint8_t>(), d_sp.as<int32_t>(), d_sc.as<int32_t>(), S,
+                         d_wo.as<int64_t>(), d_ws.as<int32_t>(), d_we.as<int32_t>(), (int32_t)h.win_off.size() - 1, W, d_lo.as<int64_t>(), d_labels, n_labels};
+        if (int rc = ev_plan.init()) return rc;
+        if (int rc = ev_cells.init()) return rc;
+        if (recruit) { if (int rc = ev_rplan.init()) return rc; if (int rc = ev_rrows.init()) return rc; }
+        if (int rc = timed(ev_plan, 4 * n_labels + 12 * (int64_t)S, [&] { return allele_plan_launch(in, work(), rw.a, st); })) return rc;
+        // (the rows' flags and the two scans over them: queued with the plan, counted in the plan's wait)
+        if (recruit) { if (int rc = timed(ev_rplan, 4 * h.n_entries + 40 * n_labels, [&] { return recruit_plan_launch(in, work(), rw, *recruit, st); })) return rc; }
+        if (int rc = h_plan.alloc(at.plan_size)) return rc;
+        char* hp = (char*)h_plan.p;
         Shipment sh;
-        sh.add(h_plan.p, work, plan_bytes);
-        if (rq) {      // (a shipment moves 16-byte pieces: the piece each total lies in)
-            sh.add((char*)h_plan.p + totals_at, work + rw.L.row_idx + ((n_labels * 8) & ~(int64_t)15), 16);
-            sh.add((char*)h_plan.p + totals_at + 16, work + rw.L.ctr_off + ((n_labels * 8) & ~(int64_t)15), 16);
+        sh.add(hp, work(), at.plan_bytes);
+        if (recruit) {
+            h_n_rows = sh.add_word(hp + at.n_rows_piece, (const int64_t*)(work() + rw.L.row_idx) + n_labels);
+            h_n_ctr = sh.add_word(hp + at.n_ctr_piece, (const int64_t*)(work() + rw.L.ctr_off) + n_labels);
         }
-        if (W && S) sh.add_counted((char*)h_plan.p + plan_bytes, work + a.L.grp_pack, (const long long*)(work + a.L.grp_off) + W, 4, groups_cap);
-        if (int rc = sh.launch(st, 64)) return rc;
+        if (W && S) sh.add_counted(hp + at.grp_pack, work() + rw.a.L.grp_pack, (const long long*)(work() + rw.a.L.grp_off) + W, 4, at.groups_cap);
+        return sh.launch(st, 64);
     }
-    if (int rc = stream_wait(st)) return rc;
-    const char* hp = (const char*)h_plan.p;
-    const int64_t* cell_off = (const int64_t*)(hp + a.L.cell_off);
-    const int64_t* grp_off = (const int64_t*)(hp + a.L.grp_off);
-    const int64_t n_cells = cell_off[S];
-    if (n_cells < 0 || grp_off[W] < 0 || grp_off[W] > groups_cap) { set_error("allele table: the device's group lists do not fit the labels of the call"); return HS_EHIP; }
-    if (int rc = d_cells.alloc((size_t)std::max<int64_t>(n_cells, 1) * sizeof(hs_allele_cell) + 16)) return rc;
-    const size_t in_piece = (size_t)((n_labels * 8) & 15);
-    const int64_t n_rows = rq ? *(const int64_t*)(hp + totals_at + in_piece) : 0, n_ctr = rq ? *(const int64_t*)(hp + totals_at + 16 + in_piece) : 0;
-    if (rq) {
-        if (n_rows < 0 || n_rows > n_labels || n_ctr < n_rows) { set_error("recruit table: the device's row counts do not fit the labels of the call"); return HS_EHIP; }
-        if (int rc = d_counters.alloc((size_t)std::max<int64_t>(n_ctr, 1) * 4)) return rc;
-        if (int rc = d_rows.alloc((size_t)std::max<int64_t>(n_rows, 1) * sizeof(hs_recruit_row))) return rc;
+
+    // behind the first wait: the totals, and room for what they count
+    int size_buffers() {
+        const char* hp = (const char*)h_plan.p;
+        const int64_t n_groups = ((const int64_t*)(hp + rw.a.L.grp_off))[W];
+        n_cells = ((const int64_t*)(hp + rw.a.L.cell_off))[S];
+        if (n_cells < 0 || n_groups < 0 || n_groups > at.groups_cap) { set_error("allele table: the device's group lists do not fit the labels of the call"); return HS_EHIP; }
+        if (int rc = d_cells.alloc((size_t)std::max<int64_t>(n_cells, 1) * sizeof(hs_allele_cell) + 16)) return rc;
+        if (recruit) {
+            n_rows = *h_n_rows; n_ctr = *h_n_ctr;
+            if (n_rows < 0 || n_rows > n_labels || n_ctr < n_rows) { set_error("recruit table: the device's row counts do not fit the labels of the call"); return HS_EHIP; }
+            if (int rc = d_counters.alloc((size_t)std::max<int64_t>(n_ctr, 1) * 4)) return rc;
+            if (int rc = d_rows.alloc((size_t)std::max<int64_t>(n_rows, 1) * sizeof(hs_recruit_row))) return rc;
+        }
+        at = table_landing(rw.a, S, W, at.groups_cap, n_cells, n_rows);
+        return HS_OK;
     }
-    HS_HIP(ev_rec(ev.a, st));
-    if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
-    if (int rc = allele_cells_launch(in, work, a, d_cells.as<hs_allele_cell>(), n_cells, st)) return rc;
-    if (int rc = kc.end(5 * h.n_entries + (int64_t)sizeof(hs_allele_cell) * n_cells, st)) return rc;
-    HS_HIP(ev_rec(ev.b, st));
-    HBuf h_rows;
-    const size_t rows_bytes = (size_t)n_rows * sizeof(hs_recruit_row), wro_at = (rows_bytes + 255) & ~(size_t)255, status_at = wro_at + ((((size_t)W + 1) * 8 + 255) & ~(size_t)255);
-    if (rq) {      // counters and rows behind the cells; they come down in the cells' shipment
-        HS_HIP(ev_rec(ev_rrows.a, st));
-        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
-        if (int rc = recruit_rows_launch(in, work, rw, rq->params, d_cells.as<hs_allele_cell>(), n_cells, d_counters.as<uint32_t>(), n_ctr, d_rows.as<hs_recruit_row>(), n_rows, st)) return rc;
-        if (int rc = kc.end(5 * h.n_entries + 12 * n_ctr + 40 * n_rows + 12 * n_labels, st)) return rc;
-        HS_HIP(ev_rec(ev_rrows.b, st));
-        if (int rc = h_rows.alloc(status_at + 256)) return rc;
-    }
-    const size_t cells_bytes = (size_t)n_cells * sizeof(hs_allele_cell), calls_bytes = (size_t)S * 4;
-    HBuf h_cells;
-    const size_t calls_at = (cells_bytes + 255) & ~(size_t)255;
-    if (int rc = h_cells.alloc(calls_at + ((calls_bytes + 255) & ~(size_t)255) + 256)) return rc;
-    {
+
+    // the cells, counters and rows behind them, and their shipment
+    int queue_cells() {
+        hs_allele_cell* cells = d_cells.as<hs_allele_cell>();
+        if (int rc = timed(ev_cells, 5 * h.n_entries + (int64_t)sizeof(hs_allele_cell) * n_cells, [&] { return allele_cells_launch(in, work(), rw.a, cells, n_cells, st); })) return rc;
+        if (recruit) {
+            if (int rc = timed(ev_rrows, 5 * h.n_entries + 12 * n_ctr + 40 * n_rows + 12 * n_labels, [&] {
+                    return recruit_rows_launch(in, work(), rw, *recruit, cells, n_cells, d_counters.as<uint32_t>(), n_ctr, d_rows.as<hs_recruit_row>(), n_rows, st); })) return rc;
+            if (int rc = h_rows.alloc(at.rows_size)) return rc;
+        }
+        if (int rc = h_cells.alloc(at.cells_size)) return rc;
+        char* hc = (char*)h_cells.p; char* hr = (char*)h_rows.p;
         Shipment sh;
-        sh.add(h_cells.p, d_cells.p, cells_bytes); sh.add((char*)h_cells.p + calls_at, work + a.L.n_calls, calls_bytes);
-        sh.add((char*)h_cells.p + calls_at + ((calls_bytes + 255) & ~(size_t)255), work + a.wide_count, 4);
-        if (rq) { sh.add(h_rows.p, d_rows.p, rows_bytes); sh.add((char*)h_rows.p + wro_at, work + rw.L.win_row_off, ((size_t)W + 1) * 8); sh.add((char*)h_rows.p + status_at, work + rw.L.status, 4); }
-        if (int rc = sh.launch(st, 64)) return rc;
+        sh.add(hc, d_cells.p, at.cells_bytes); sh.add(hc + at.n_calls, work() + rw.a.L.n_calls, at.calls_bytes); sh.add(hc + at.wide_count, work() + rw.a.wide_count, 4);
+        if (recruit) { sh.add(hr, d_rows.p, at.rows_bytes); sh.add(hr + at.win_row_off, work() + rw.L.win_row_off, at.win_row_off_bytes); sh.add(hr + at.status, work() + rw.L.status, 4); }
+        return sh.launch(st, 64);
     }
+
+    // behind the second wait: the tables from what the two shipments left (an error leaves what exists to the holder)
+    int assemble(TablePair& out) {
+        const char* hp = (const char*)h_plan.p; const char* hc = (const char*)h_cells.p; const char* hr = (const char*)h_rows.p;
+        hs::AlleleRaw raw;
+        raw.n_windows = W; raw.n_snps = S;
+        raw.win_contig = h.win_contig.data(); raw.win_start = h.win_start.data(); raw.win_end = h.win_end.data(); raw.grp_off = (const int64_t*)(hp + rw.a.L.grp_off);
+        raw.grp_n = (const int32_t*)(hp + rw.a.L.grp_n); raw.grp_ids = (const int32_t*)(hp + at.grp_pack);
+        raw.win_snp_first = (const int32_t*)(hp + rw.a.L.win_snp_first); raw.win_snp_last = (const int32_t*)(hp + rw.a.L.win_snp_last);
+        raw.snp_contig = h.snp_contig.data(); raw.snp_pos = h.snp_pos.data(); raw.snp_ref = h.snp_ref.data(); raw.snp_alt = h.snp_alt.data();
+        raw.snp_win = (const int32_t*)(hp + rw.a.L.snp_win); raw.cell_off = (const int64_t*)(hp + rw.a.L.cell_off);
+        raw.cells = (const hs_allele_cell*)hc; raw.n_calls = (const int32_t*)(hc + at.n_calls);
+        raw.contig_base = h.contig_base;
+        std::string err;
+        out.alleles.reset(hs::alleles_assemble(raw, err));
+        if (!out.alleles) { set_error(err); return HS_EINVAL; }
+        float ms = 0, ms_plan = 0;
+        if (int rc = ev_cells.ms(&ms)) return rc;
+        if (int rc = ev_plan.ms(&ms_plan)) return rc;
+        out.alleles->t_kernel_ms = (double)ms + ms_plan; out.alleles->n_entries = h.n_entries;
+        out.alleles->n_wide_columns = S && W ? *(const int32_t*)(hc + at.wide_count) : 0;
+        if (recruit) {
+            hs::RecruitRaw rr;
+            rr.n_windows = W; rr.win_contig = h.win_contig.data(); rr.win_start = h.win_start.data(); rr.win_end = h.win_end.data();
+            rr.win_snp_first = raw.win_snp_first; rr.win_snp_last = raw.win_snp_last;
+            rr.win_row_off = (const int64_t*)(hr + at.win_row_off); rr.rows = (const hs_recruit_row*)hr;
+            rr.contig_base = h.contig_base; rr.params = *recruit;
+            if (*(const int32_t*)(hr + at.status) != 0) err = "recruit table: the rows or counters did not fit their arrays";
+            else out.recruit.reset(hs::recruit_assemble(rr, err));
+            if (!out.recruit) { set_error(err); return HS_EINVAL; }
+            float ms_a = 0, ms_b = 0;
+            if (ev_rplan.ms(&ms_a) || ev_rrows.ms(&ms_b)) return HS_EHIP;
+            out.recruit->t_kernel_ms = (double)ms_a + ms_b; out.recruit->n_counter_words = n_ctr; out.recruit->n_entries = h.n_entries;
+        }
+        return HS_OK;
+    }
+};
+
+static int alleles_on_device(const AlleleHostIn& h, const int64_t* d_col_off, const int32_t* d_col_idx, const uint8_t* d_col_code, const int32_t* d_labels,
+                             KernelClock& kc, hipStream_t st, const hs_recruit_params* recruit, TablePair& out) {
+    TableCall c{h, recruit, kc, st};
+    if (int rc = c.queue_plan(d_col_off, d_col_idx, d_col_code, d_labels)) return rc;
+    if (int rc = stream_wait(st)) return rc;
+    if (int rc = c.size_buffers()) return rc;
+    if (int rc = c.queue_cells()) return rc;
     if (int rc = stream_wait(st)) return rc;
     kc.flush();
-    hs::AlleleRaw raw;
-    raw.n_windows = W; raw.n_snps = S;
-    raw.win_contig = h.win_contig.data(); raw.win_start = h.win_start.data(); raw.win_end = h.win_end.data(); raw.grp_off = grp_off;
-    raw.grp_n = (const int32_t*)(hp + a.L.grp_n); raw.grp_ids = (const int32_t*)(hp + plan_bytes);
-    raw.win_snp_first = (const int32_t*)(hp + a.L.win_snp_first); raw.win_snp_last = (const int32_t*)(hp + a.L.win_snp_last);
-    raw.snp_contig = h.snp_contig.data(); raw.snp_pos = h.snp_pos.data(); raw.snp_ref = h.snp_ref.data(); raw.snp_alt = h.snp_alt.data();
-    raw.snp_win = (const int32_t*)(hp + a.L.snp_win); raw.cell_off = cell_off;
-    raw.cells = (const hs_allele_cell*)h_cells.p; raw.n_calls = (const int32_t*)((const char*)h_cells.p + calls_at);
-    raw.contig_base = h.contig_base;
-    std::string err;
-    hs_allele_table* t = hs::alleles_assemble(raw, err);
-    if (!t) { set_error(err); return HS_EINVAL; }
-    float ms = 0, ms_plan = 0;
-    if (int rc = ev.ms(&ms)) { hs::alleles_free(t); return rc; }
-    if (int rc = ev_plan.ms(&ms_plan)) { hs::alleles_free(t); return rc; }
-    t->t_kernel_ms = (double)ms + ms_plan; t->n_entries = h.n_entries;
-    t->n_wide_columns = S && W ? *(const int32_t*)((const char*)h_cells.p + calls_at + ((calls_bytes + 255) & ~(size_t)255)) : 0;
-    if (rq) {
-        hs::RecruitRaw rr;
-        rr.n_windows = W; rr.win_contig = h.win_contig.data(); rr.win_start = h.win_start.data(); rr.win_end = h.win_end.data();
-        rr.win_snp_first = raw.win_snp_first; rr.win_snp_last = raw.win_snp_last;
-        rr.win_row_off = (const int64_t*)((const char*)h_rows.p + wro_at); rr.rows = (const hs_recruit_row*)h_rows.p;
-        rr.contig_base = h.contig_base; rr.params = rq->params;
-        hs_recruit_table* rt = nullptr;
-        if (*(const int32_t*)((const char*)h_rows.p + status_at) != 0) err = "recruit table: the rows or counters did not fit their arrays";
-        else rt = hs::recruit_assemble(rr, err);
-        float ms_a = 0, ms_b = 0;
-        if (rt && (ev_rplan.ms(&ms_a) || ev_rrows.ms(&ms_b))) { hs::recruit_free(rt); hs::alleles_free(t); return HS_EHIP; }
-        if (!rt) { hs::alleles_free(t); set_error(err); return HS_EINVAL; }
-        rt->t_kernel_ms = (double)ms_a + ms_b; rt->n_counter_words = n_ctr; rt->n_entries = h.n_entries;
-        rq->table = rt;
-    }
-    *out = t;
-    return HS_OK;
+    return c.assemble(out);
 }
 
 // dense labels on the device from the per-window lists a contig group leaves (SrSparseLabels)
@@ -260,16 +304,14 @@ static int allele_dense_labels(const hs::SrSparseLabels& sp, const std::vector<i
 // over from stage 3 where it packed them, or uploaded by stage 4 -- HS_COLUMNS_VIA_HOST, HS_PIPELINE_KEEP_COLUMNS, a group that lost SNPs to
 // rarest_strain_abundance), the labels go up as the per-window lists the group leaves and are spread on the device. `r` / `sp`: the group's
 // stage-4 result; `cv`: its stage-3 result (contigs [c0, c0 + r->n_contigs) of the batch).
-static int pipeline_group_alleles(const hs_sr_result* r, const hs::SrSparseLabels& sp, const hs_cv_result* cv, float rsa, int c0, HipSrOps& ops, hs_allele_table** out,
-                                  RecruitReq* rq = nullptr) {
+// `recruit`: the thresholds of the recruit table, queued behind the cells and assembled with them (nullptr: the allele table alone).
+static int pipeline_group_tables(const hs_sr_result* r, const hs::SrSparseLabels& sp, const hs_cv_result* cv, float rsa, int c0, HipSrOps& ops, const hs_recruit_params* recruit,
+                                 TablePair& out) {
     const int C = r->n_contigs;
     AlleleHostIn h;
     h.contig_base = c0;
     const int64_t W = r->win_off[C];
-    h.win_off.assign(r->win_off, r->win_off + C + 1);
-    h.win_start.assign(r->win_start, r->win_start + W); h.win_end.assign(r->win_end, r->win_end + W);
-    h.label_off.assign(r->label_off, r->label_off + W + 1);
-    h.win_contig.resize((size_t)W);
+    h.windows_of(r);
     for (int c = 0; c < C; ++c) for (int64_t w = r->win_off[c]; w < r->win_off[c + 1]; ++w) h.win_contig[(size_t)w] = c;
     for (int c = 0; c < C; ++c)
         for (int64_t s = cv->snp_off[c]; s < cv->snp_off[c + 1]; ++s) {
@@ -285,23 +327,23 @@ static int pipeline_group_alleles(const hs_sr_result* r, const hs::SrSparseLabel
         std::string err;
         const int64_t zero = 0;
         raw.cell_off = &zero;
-        *out = hs::alleles_assemble(raw, err);
-        if (!*out) { set_error(err); return HS_EINVAL; }
-        if (rq) {      // (no rows either; the table still says how many windows the group has)
+        out.alleles.reset(hs::alleles_assemble(raw, err));
+        if (!out.alleles) { set_error(err); return HS_EINVAL; }
+        if (recruit) {      // (no rows either; the table still says how many windows the group has)
             const std::vector<int32_t> none((size_t)W + 1, 0);
             const std::vector<int64_t> row_off((size_t)W + 1, 0);
             hs::RecruitRaw rr;
             rr.n_windows = W; rr.win_contig = h.win_contig.data(); rr.win_start = h.win_start.data(); rr.win_end = h.win_end.data();
-            rr.win_snp_first = none.data(); rr.win_snp_last = none.data(); rr.win_row_off = row_off.data(); rr.contig_base = c0; rr.params = rq->params;
-            rq->table = hs::recruit_assemble(rr, err);
-            if (!rq->table) { set_error(err); return HS_EINVAL; }
+            rr.win_snp_first = none.data(); rr.win_snp_last = none.data(); rr.win_row_off = row_off.data(); rr.contig_base = c0; rr.params = *recruit;
+            out.recruit.reset(hs::recruit_assemble(rr, err));
+            if (!out.recruit) { set_error(err); return HS_EINVAL; }
         }
         return HS_OK;
     }
     DBuf d_labels, d_ro, d_ids, d_lab, d_lo;
     UploadPack pk;
     if (int rc = allele_dense_labels(sp, h.label_off, d_labels, pk, d_ro, d_ids, d_lab, d_lo, ops.stream)) return rc;
-    return alleles_on_device(h, ops.d_col_off.as<int64_t>(), ops.d_col_idx.as<int32_t>(), ops.d_col_code.as<uint8_t>(), d_labels.as<int32_t>(), ops.kc, ops.stream, out, rq);
+    return alleles_on_device(h, ops.d_col_off.as<int64_t>(), ops.d_col_idx.as<int32_t>(), ops.d_col_code.as<uint8_t>(), d_labels.as<int32_t>(), ops.kc, ops.stream, recruit, out);
 }
 
 }  // namespace
@@ -330,17 +372,14 @@ int hs_group_alleles(const int64_t* d_col_off, const int32_t* d_col_idx, const u
     return d_cells ? allele_cells_launch(in, (char*)d_work, a, d_cells, cells_cap, st) : allele_plan_launch(in, (char*)d_work, a, st);
 }
 
-// (hs_recruit_reads of hs_capi_recruit.inc is the same call with a RecruitReq)
-static int haplotype_tables(const hs_sr_contig* contigs, int32_t n_contigs, const hs_sr_result* sr, hs_allele_table** table, RecruitReq* rq) {
+// (hs_recruit_reads of hs_capi_recruit.inc is the same call with thresholds and a second table)
+static int haplotype_tables(const hs_sr_contig* contigs, int32_t n_contigs, const hs_sr_result* sr, hs_allele_table** table, const hs_recruit_params* recruit,
+                            hs_recruit_table** recruit_table) {
     if (int rc = require_device()) return rc;
     if (!contigs || !sr || !table || n_contigs < 0 || sr->n_contigs != n_contigs) { set_error("hs_haplotype_alleles: the result does not describe these contigs"); return HS_EINVAL; }
     if (!sr->labels && sr->win_off[n_contigs] > 0 && sr->label_off[sr->win_off[n_contigs]] > 0) { set_error("hs_haplotype_alleles: the result has no dense labels"); return HS_EINVAL; }
     AlleleHostIn h;
-    const int64_t W = sr->win_off[n_contigs];
-    h.win_off.assign(sr->win_off, sr->win_off + n_contigs + 1);
-    h.win_start.assign(sr->win_start, sr->win_start + W); h.win_end.assign(sr->win_end, sr->win_end + W);
-    h.label_off.assign(sr->label_off, sr->label_off + W + 1);
-    h.win_contig.resize((size_t)W);
+    h.windows_of(sr);
     std::vector<int64_t> col_off(1, 0);
     for (int c = 0; c < n_contigs; ++c) {
         const hs_sr_contig& k = contigs[c];
@@ -391,11 +430,15 @@ static int haplotype_tables(const hs_sr_contig* contigs, int32_t n_contigs, cons
         }
     }
     KernelClock kc;
-    return alleles_on_device(h, d_co.as<int64_t>(), d_ci.as<int32_t>(), d_cc.as<uint8_t>(), d_labels.as<int32_t>(), kc, st, table, rq);
+    TablePair t;
+    if (int rc = alleles_on_device(h, d_co.as<int64_t>(), d_ci.as<int32_t>(), d_cc.as<uint8_t>(), d_labels.as<int32_t>(), kc, st, recruit, t)) return rc;
+    *table = t.alleles.release();
+    if (recruit) *recruit_table = t.recruit.release();
+    return HS_OK;
 }
 
 int hs_haplotype_alleles(const hs_sr_contig* contigs, int32_t n_contigs, const hs_sr_result* sr, hs_allele_table** table) {
-    return haplotype_tables(contigs, n_contigs, sr, table, nullptr);
+    return haplotype_tables(contigs, n_contigs, sr, table, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -217,18 +217,22 @@ int hs_pileup_plan(const int64_t* h_rec_cig_off, const uint32_t* h_cigar, int32_
 }
 void hs_free_host(void* p) { std::free(p); }
 
-// exclusive scan of n ints into n + 1 offsets (see hs_kernels_graph.hip); `scratch` must outlive the launches
-static int exclusive_scan_launch(const int32_t* d_in, int n, int64_t* d_out, DBuf& scratch, hipStream_t stream) {
-    const int n_tiles = (n + HS_SCAN_TILE - 1) / HS_SCAN_TILE;
+// exclusive scan of n ints into n + 1 offsets (see hs_kernels_graph.hip); the tile scratch (room for 2 * scan_tiles(n) words) must outlive
+// the launches -- the caller's own, or a DBuf sized here
+static int scan_tiles(int64_t n) { return (int)((n + HS_SCAN_TILE - 1) / HS_SCAN_TILE); }
+static int exclusive_scan_launch(const int32_t* d_in, int n, int64_t* d_out, long long* tile_sum, hipStream_t stream) {
+    const int n_tiles = scan_tiles(n);
     if (n_tiles == 0) { HS_HIP(hipMemsetAsync(d_out, 0, sizeof(int64_t), stream)); return HS_OK; }
-    if (int rc = scratch.alloc((size_t)n_tiles * 16)) return rc;
-    long long* tile_sum = scratch.as<long long>();
     long long* tile_off = tile_sum + n_tiles;
     hipLaunchKernelGGL(hsdev::k_scan_tile_sums, dim3((unsigned)n_tiles), dim3(256), 0, stream, d_in, n, tile_sum);
     hipLaunchKernelGGL(hsdev::k_scan_tile_offsets, dim3(1), dim3(1024), 0, stream, tile_sum, n_tiles, tile_off, d_out + n);
     hipLaunchKernelGGL(hsdev::k_scan_apply, dim3((unsigned)n_tiles), dim3(256), 0, stream, d_in, n, tile_off, d_out);
     HS_HIP(hipGetLastError());
     return HS_OK;
+}
+static int exclusive_scan_launch(const int32_t* d_in, int n, int64_t* d_out, DBuf& scratch, hipStream_t stream) {
+    if (n > 0) { if (int rc = scratch.alloc((size_t)scan_tiles(n) * 16)) return rc; }
+    return exclusive_scan_launch(d_in, n, d_out, scratch.as<long long>(), stream);
 }
 
 // K2's selection list: the kernels fill 256 scratch slots + one count per tile; scan + compact give the sorted list and its

@@ -544,21 +544,29 @@ struct GroupCall {
     std::vector<hs_sr_result*> parts;
     std::vector<hs::SrSparseLabels> sparse;      // the groups leave their labels per window; concat_sr_parts spreads them
     GroupMeeting* meet;      // the fused call only: its groups bring up their own share of the pileup and meet before stage 4
-    std::vector<hs_allele_table*> allele_parts;      // HS_PIPELINE_ALLELES: the groups' shares of the table
-    std::vector<hs_recruit_table*> recruit_parts;    // HS_PIPELINE_RECRUIT: the groups' shares of the recruit table
-    ~GroupCall() { for (hs_allele_table* t : allele_parts) hs::alleles_free(t); for (hs_recruit_table* t : recruit_parts) hs::recruit_free(t); }
+    std::vector<TablePair> tables;      // HS_PIPELINE_ALLELES, HS_PIPELINE_RECRUIT: the groups' shares of the two tables
 };
+// (error_rate: the two-call form's; meet: the fused call's)
+static GroupCall group_call(const hs_pipeline* p, float automatic_snp_threshold, float error_rate, float rarest_strain_abundance, int32_t low_memory, int32_t amplicon,
+                            uint32_t seed, int32_t n_threads, int32_t window_size, GroupMeeting* meet) {
+    const size_t G = p->ranges.size();
+    if (window_size <= 0) window_size = pipeline_window_size(p->batch, amplicon != 0);
+    return GroupCall{automatic_snp_threshold, error_rate, rarest_strain_abundance, low_memory, amplicon, seed, pipeline_threads_per_group(n_threads, (int)G), window_size,
+                     std::vector<hs_sr_result*>(G, nullptr), std::vector<hs::SrSparseLabels>(G), meet, std::vector<TablePair>(G)};
+}
 
 // the groups' shares of the allele table, contig order; the previous call's table goes
 static int pipeline_merge_alleles(hs_pipeline* p, GroupCall& call) {
     hs::alleles_free(p->allele_table); p->allele_table = nullptr;
     hs::recruit_free(p->recruit_table); p->recruit_table = nullptr;
+    std::vector<const hs_allele_table*> alleles; std::vector<const hs_recruit_table*> recruit;
+    for (const TablePair& t : call.tables) { alleles.push_back(t.alleles.get()); recruit.push_back(t.recruit.get()); }
     if (p->recruit) {
-        p->recruit_table = hs::recruit_concat(std::vector<const hs_recruit_table*>(call.recruit_parts.begin(), call.recruit_parts.end()));
+        p->recruit_table = hs::recruit_concat(recruit);
         if (!p->recruit_table) { set_error("recruit table: out of memory"); return HS_EINVAL; }
     }
     if (!p->alleles) return HS_OK;
-    p->allele_table = hs::alleles_concat(std::vector<const hs_allele_table*>(call.allele_parts.begin(), call.allele_parts.end()));
+    p->allele_table = hs::alleles_concat(alleles);
     if (!p->allele_table) { set_error("allele table: out of memory"); return HS_EINVAL; }
     return HS_OK;
 }
@@ -600,11 +608,9 @@ static int pipeline_group_step(hs_pipeline* p, GroupCall& call, int g) {
     if (!via_host) ops.adopt_columns(cv_ops);
     if (int r = hs::sr_run_from_cv(ops, meta, c0, c1, cv, error_rate, call.rarest_strain_abundance, call.low_memory, call.amplicon, call.seed, per, call.window_size,
                                    &call.parts[(size_t)g], &call.sparse[(size_t)g], &p->sr_keep[(size_t)g])) return fail(r);
-    if (p->recruit) {      // (the cells are formed on the device either way; the merge keeps the allele shares only under HS_PIPELINE_ALLELES)
-        if (int r = pipeline_group_recruit(call.parts[(size_t)g], call.sparse[(size_t)g], cv, call.rarest_strain_abundance, c0, ops, p->recruit_params,
-                                           &call.allele_parts[(size_t)g], &call.recruit_parts[(size_t)g])) return fail(r);
-    } else if (p->alleles) {
-        if (int r = pipeline_group_alleles(call.parts[(size_t)g], call.sparse[(size_t)g], cv, call.rarest_strain_abundance, c0, ops, &call.allele_parts[(size_t)g])) return fail(r);
+    if (p->recruit || p->alleles) {      // (the cells are formed on the device either way; the merge keeps the allele shares only under HS_PIPELINE_ALLELES)
+        if (int r = pipeline_group_tables(call.parts[(size_t)g], call.sparse[(size_t)g], cv, call.rarest_strain_abundance, c0, ops, p->recruit ? &p->recruit_params : nullptr,
+                                          call.tables[(size_t)g])) return fail(r);
     }
     // HS_PIPELINE_KEEP_COLUMNS: the entries came down beside stage 4. The two-call form copies them; the fused call's result points into
     // the group's pinned block, which stays with the pipeline until its next call
@@ -618,10 +624,7 @@ int hs_pipeline_run(hs_pipeline* p, float automatic_snp_threshold, float error_r
                     int32_t amplicon, uint32_t seed, int32_t n_threads, int32_t window_size, hs_sr_result** out, hs_pipeline_stats* st) {
     if (!p || !out || !p->sel) { set_error("hs_pipeline_run: run hs_pipeline_select first"); return HS_EINVAL; }
     if (int rc = bind_device(p->batch->device)) return rc;
-    const int G = (int)p->ranges.size();
-    if (window_size <= 0) window_size = pipeline_window_size(p->batch, amplicon != 0);
-    GroupCall call{automatic_snp_threshold, error_rate, rarest_strain_abundance, low_memory, amplicon, seed, pipeline_threads_per_group(n_threads, G), window_size,
-                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), nullptr, std::vector<hs_allele_table*>((size_t)G, nullptr), std::vector<hs_recruit_table*>((size_t)G, nullptr)};
+    GroupCall call = group_call(p, automatic_snp_threshold, error_rate, rarest_strain_abundance, low_memory, amplicon, seed, n_threads, window_size, nullptr);
     hs::set_trace_origin();
     p->k2_order.reset();
     const int rc = p->run([&](int g) { return pipeline_group_step(p, call, g); });
@@ -643,9 +646,7 @@ int hs_pipeline_run_fused(hs_pipeline* p, float automatic_snp_threshold, float r
     if (!p || !out) { set_error("hs_pipeline_run_fused: null argument"); return HS_EINVAL; }
     if (int rc = bind_device(p->batch->device)) return rc;
     timing_next_step();
-    const int G = (int)p->ranges.size();
     const int C = p->batch->n_contigs;
-    if (window_size <= 0) window_size = pipeline_window_size(p->batch, amplicon != 0);
     static const bool timing_abs = std::getenv("HS_TIMING") != nullptr && std::string(std::getenv("HS_TIMING")) == "abs";
     const double t_enter = timing_abs ? hs::trace_ms() : 0;      // (relative to the previous call's origin: the time between two calls)
     p->drop_cv();
@@ -653,8 +654,7 @@ int hs_pipeline_run_fused(hs_pipeline* p, float automatic_snp_threshold, float r
     p->sel->impl = new hs::CvSelection();
     GroupMeeting meet;
     meet.md.assign((size_t)C, 0.f);
-    GroupCall call{automatic_snp_threshold, 0.f, rarest_strain_abundance, low_memory, amplicon, seed, pipeline_threads_per_group(n_threads, G), window_size,
-                   std::vector<hs_sr_result*>((size_t)G, nullptr), std::vector<hs::SrSparseLabels>((size_t)G), &meet, std::vector<hs_allele_table*>((size_t)G, nullptr), std::vector<hs_recruit_table*>((size_t)G, nullptr)};
+    GroupCall call = group_call(p, automatic_snp_threshold, 0.f, rarest_strain_abundance, low_memory, amplicon, seed, n_threads, window_size, &meet);
     hs::set_trace_origin();
     p->k2_order.reset();
     // a group that is gone (its job failed, or its thread never bound to the device) releases whoever waits for it at the meeting point

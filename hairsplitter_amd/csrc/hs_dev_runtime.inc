@@ -301,17 +301,22 @@ static int ship_kernel(void* dst, const void* src, size_t bytes, hipStream_t str
 // is a count on the device take it from there when the kernel runs
 struct Shipment {
     hsdev::ShipList L;
+    bool too_many = false;      // a segment beyond the list's: launch() refuses
     Shipment() { L.n = 0; }
-    void add(void* dst, const void* src, size_t bytes) {
-        if (!bytes) return;
-        hsdev::ShipSeg& g = L.seg[L.n++];
-        g.src = src; g.dst = dst; g.bytes = (long long)bytes; g.count = nullptr; g.stride = 0; g.cap = 0; g.extra = 0;
-    }
+    void seg(const hsdev::ShipSeg& g) { if (L.n < (int)(sizeof L.seg / sizeof L.seg[0])) L.seg[L.n++] = g; else too_many = true; }
+    void add(void* dst, const void* src, size_t bytes) { if (bytes) seg(hsdev::ShipSeg{src, dst, (long long)bytes, nullptr, 0, 0, 0}); }
     void add_counted(void* dst, const void* src, const long long* d_count, size_t stride, long long cap, size_t extra = 0) {
-        hsdev::ShipSeg& g = L.seg[L.n++];
-        g.src = src; g.dst = dst; g.bytes = 0; g.count = d_count; g.stride = (long long)stride; g.cap = cap; g.extra = (long long)extra;
+        seg(hsdev::ShipSeg{src, dst, 0, d_count, (long long)stride, cap, (long long)extra});
+    }
+    // one 8-byte word of the device: a shipment moves 16-byte pieces, so the aligned piece that holds it goes to dst (16 bytes);
+    // returns where the word then lies on the host
+    const int64_t* add_word(void* dst, const int64_t* d_word) {
+        const uintptr_t in_piece = reinterpret_cast<uintptr_t>(d_word) & 15;
+        add(dst, reinterpret_cast<const char*>(d_word) - in_piece, 16);
+        return reinterpret_cast<const int64_t*>((const char*)dst + in_piece);
     }
     int launch(hipStream_t s, int blocks = 256) {
+        if (too_many) { set_error("a shipment of more segments than its list holds"); return HS_EINVAL; }
         if (L.n == 0) return HS_OK;
         hipLaunchKernelGGL(hsdev::k_ship, dim3((unsigned)blocks), dim3(256), 0, s, L);
         HS_HIP(hipGetLastError());

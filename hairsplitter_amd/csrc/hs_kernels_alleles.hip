@@ -154,28 +154,44 @@ static __device__ void allele_column(uint32_t* keys, int n_pow2, uint32_t* s_cal
     __syncthreads();
 }
 
-struct AlleleArgs {
-    const int64_t* col_off; const int32_t* col_idx; const uint8_t* col_code; const uint8_t* snp_ref; const uint8_t* snp_alt;
-    const int32_t* snp_win; const int64_t* label_off; const int32_t* labels; const int32_t* grp_n; const int32_t* grp_ids;
-    const int64_t* cell_off; AlleleCell* cells; long long cells_cap; int32_t* n_calls; int n_snps;
+// what the column kernels of this table and of the recruit table (hs_kernels_recruit.hip) read: the columns, the dense labels and the plan
+struct ColumnArgs {
+    const int64_t* col_off; const int32_t* col_idx; const uint8_t* col_code; int n_snps;
+    const int32_t* snp_win; const int64_t* label_off; const int32_t* labels; long long n_labels; int n_windows;
+    const int32_t* grp_n; const int32_t* grp_ids; const int64_t* cell_off; long long cells_cap;
+};
+// a column as those kernels see it: its window and the window's G groups, its `depth` entries from e0 (the path's columns hold at most
+// 65535; the C ABI refuses deeper ones), the window's n_reads labels from l0. false: nothing to do -- no window (then depth = 0), no
+// group, or labels that are not the call's
+struct Column { int w, G, depth; long long e0, l0, n_reads; };
+static __device__ __forceinline__ bool column_load(const ColumnArgs& A, int s, Column& c) {
+    c.w = A.snp_win[s]; c.G = 0; c.depth = 0;
+    if (c.w < 0 || c.w >= A.n_windows) return false;
+    c.G = A.grp_n[c.w];
+    c.e0 = A.col_off[s];
+    const long long d = A.col_off[s + 1] - c.e0;
+    c.depth = d < 0 ? 0 : (d > 65535 ? 65535 : (int)d);
+    c.l0 = A.label_off[c.w];
+    c.n_reads = A.label_off[c.w + 1] - c.l0;
+    return c.G > 0 && c.l0 >= 0 && c.l0 + c.n_reads <= A.n_labels;
+}
+
+struct AlleleArgs : ColumnArgs {
+    const uint8_t* snp_ref; const uint8_t* snp_alt; AlleleCell* cells; int32_t* n_calls;
     int32_t* wide_count; int32_t* wide_list;      // columns deeper than HS_ALLELE_LDS_KEYS, for k_allele_cells_wide
 };
 
 // one column, by whichever kernel owns it; false: the column is not this route's (too deep for `cap` keys)
 static __device__ bool allele_one(const AlleleArgs& A, int s, uint32_t* keys, int cap, uint32_t* s_calls) {
-    const int w = A.snp_win[s];
-    if (w < 0) { if (threadIdx.x == 0) A.n_calls[s] = 0; return true; }
-    const long long e0 = A.col_off[s];
-    const long long d64 = A.col_off[s + 1] - e0;
-    const int depth = d64 < 0 ? 0 : (d64 > 65535 ? 65535 : (int)d64);      // (the path's columns hold at most 65535 entries; the C ABI refuses deeper ones)
-    if (depth > cap) return false;
-    const int G = A.grp_n[w];
+    Column c;
+    const bool work = column_load(A, s, c);
+    if (c.depth > cap) return false;
+    if (!work) { if (threadIdx.x == 0) A.n_calls[s] = 0; return true; }
     const long long c0 = A.cell_off[s];
-    if (c0 < 0 || c0 + G > A.cells_cap) { if (threadIdx.x == 0) A.n_calls[s] = -1; return true; }      // never write beyond the caller's cells
+    if (c0 < 0 || c0 + c.G > A.cells_cap) { if (threadIdx.x == 0) A.n_calls[s] = -1; return true; }      // never write beyond the caller's cells
     int n_pow2 = 2;
-    while (n_pow2 < depth) n_pow2 <<= 1;
-    const long long l0 = A.label_off[w];
-    allele_column(keys, n_pow2, s_calls, e0, depth, A.col_idx, A.col_code, A.labels + l0, (int)(A.label_off[w + 1] - l0), A.grp_ids + l0, G,
+    while (n_pow2 < c.depth) n_pow2 <<= 1;
+    allele_column(keys, n_pow2, s_calls, c.e0, c.depth, A.col_idx, A.col_code, A.labels + c.l0, (int)c.n_reads, A.grp_ids + c.l0, c.G,
                   A.snp_ref[s], A.snp_alt[s], A.cells + c0, A.n_calls + s);
     return true;
 }

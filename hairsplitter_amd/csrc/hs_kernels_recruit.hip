@@ -20,40 +20,23 @@
 
 namespace hsdev {
 
-struct RecruitArgs {
-    const int64_t* col_off; const int32_t* col_idx; const uint8_t* col_code; int n_snps;
-    const int32_t* snp_win; const int64_t* label_off; const int32_t* labels; long long n_labels; int n_windows;
-    const int32_t* grp_n; const int32_t* grp_ids; const int64_t* cell_off; const uint8_t* cells /* 12-byte cells, call at byte 11 */; long long cells_cap;
+struct RecruitArgs : ColumnArgs {      // (ColumnArgs, Column, column_load: hs_kernels_alleles.hip)
+    const AlleleCell* cells;
     int32_t* flag; int32_t* ctr_n; const int64_t* row_idx; const int64_t* ctr_off;
     uint32_t* counters; long long counters_cap; hs_recruit_row* rows; long long rows_cap; int64_t* win_row_off; int32_t* status;
     hs_recruit_params params;
 };
 
-// depth of a column as every kernel of the table reads it (the path's columns hold at most 65535 entries)
-static __device__ __forceinline__ int recruit_depth(const RecruitArgs& A, int s, long long* e0) {
-    *e0 = A.col_off[s];
-    const long long d = A.col_off[s + 1] - *e0;
-    return d < 0 ? 0 : (d > 65535 ? 65535 : (int)d);
-}
-
 __global__ __launch_bounds__(64) void k_recruit_mark(RecruitArgs A) {
     const int s = (int)blockIdx.x;
-    if (s >= A.n_snps) return;
-    const int w = A.snp_win[s];
-    if (w < 0 || w >= A.n_windows) return;
-    const int G = A.grp_n[w];
-    if (G <= 0) return;      // a window with SNPs and no group has no rows
-    long long e0;
-    const int depth = recruit_depth(A, s, &e0);
-    const long long l0 = A.label_off[w];
-    const long long n_reads = A.label_off[w + 1] - l0;
-    if (l0 < 0 || l0 + n_reads > A.n_labels) return;
-    for (int i = (int)threadIdx.x; i < depth; i += 64) {
-        const int r = A.col_idx[e0 + i];
-        if (r < 0 || r >= n_reads) continue;
-        if (!hs::recruit_selected(A.labels[l0 + r], A.params.which)) continue;
-        A.flag[l0 + r] = 1;
-        A.ctr_n[l0 + r] = 1 + 2 * G;
+    Column c;
+    if (s >= A.n_snps || !column_load(A, s, c)) return;      // (a window with SNPs and no group has no rows)
+    for (int i = (int)threadIdx.x; i < c.depth; i += 64) {
+        const int r = A.col_idx[c.e0 + i];
+        if (r < 0 || r >= c.n_reads) continue;
+        if (!hs::recruit_selected(A.labels[c.l0 + r], A.params.which)) continue;
+        A.flag[c.l0 + r] = 1;
+        A.ctr_n[c.l0 + r] = 1 + 2 * c.G;
     }
 }
 
@@ -69,19 +52,12 @@ __global__ __launch_bounds__(256) void k_recruit_win_rows(RecruitArgs A) {
 
 __global__ __launch_bounds__(64) void k_recruit_count(RecruitArgs A) {
     const int s = (int)blockIdx.x;
-    if (s >= A.n_snps) return;
-    const int w = A.snp_win[s];
-    if (w < 0 || w >= A.n_windows) return;
-    const int G = A.grp_n[w];
-    if (G <= 0) return;
-    const long long c0 = A.cell_off[s];
+    Column c;
+    if (s >= A.n_snps || !column_load(A, s, c)) return;
+    const int G = c.G, depth = c.depth;
+    const long long e0 = c.e0, l0 = c.l0, n_reads = c.n_reads, c0 = A.cell_off[s];
     if (c0 < 0 || c0 + G > A.cells_cap) return;      // (the cell kernel refused the column too: n_calls = -1 stops the assembly)
-    long long e0;
-    const int depth = recruit_depth(A, s, &e0);
-    const long long l0 = A.label_off[w];
-    const long long n_reads = A.label_off[w + 1] - l0;
-    if (l0 < 0 || l0 + n_reads > A.n_labels) return;
-    const uint8_t* __restrict__ calls = A.cells + c0 * 12 + 11;
+    const AlleleCell* __restrict__ cells = A.cells + c0;
     for (int base = 0; base < depth; base += 64) {
         const int i = base + (int)threadIdx.x;
         long long at = -1;
@@ -96,7 +72,7 @@ __global__ __launch_bounds__(64) void k_recruit_count(RecruitArgs A) {
         if (__ballot(at >= 0) == 0) continue;      // (no row among these 64 entries: wave-uniform)
         if (at >= 0) atomicAdd(A.counters + at, 1u);
         for (int k = 0; k < G; ++k) {
-            const uint8_t call = calls[(long long)k * 12];      // (the same address in every lane)
+            const uint8_t call = cells[k].call;      // (the same address in every lane)
             const int what = hs::recruit_entry(code, call);
             if (at >= 0 && what) atomicAdd(A.counters + at + 1 + 2 * k + (what - 1), 1u);
         }

@@ -12,13 +12,7 @@
 
 #include "../../include/hairsplitter_hip.h"
 
-#ifndef HS_HD      // (hs_rules.h defines it the same way)
-#if defined(__HIP__)
-#define HS_HD __host__ __device__
-#else
-#define HS_HD
-#endif
-#endif
+#include "hs_rules.h"      // HS_HD
 
 namespace hs {
 

@@ -791,7 +791,7 @@ struct HipSrOps : hs::SrDeviceOps {
             if (int rc = h4.alloc(o_ok + (size_t)Wc + 256)) return rc;
             Shipment sh;
             sh.add(h4.p, d_stat.p, 416);
-            sh.add((char*)h4.p + o_nnz, G.d_off.as<int64_t>() + (G.rows & ~(int64_t)1), 16);      // (the granule that holds d_off[rows])
+            const int64_t* h_nnz = sh.add_word((char*)h4.p + o_nnz, G.d_off.as<int64_t>() + G.rows);      // (d_off[rows]; the block is 16-byte aligned)
             bool need_chain_labels = !finish || tap_run_labels != nullptr;
             if (finish) {
                 sh.add((char*)h4.p + o_final, d_final.p, (size_t)total_m * sizeof(int32_t));
@@ -818,7 +818,7 @@ struct HipSrOps : hs::SrDeviceOps {
                 if (slab) { if (int rc = d2h_pinned(tap_run_labels->data(), d_slab.p, (size_t)slab * sizeof(int32_t), stream)) return rc; }
                 tap_run_off->assign(inst_slab.begin(), inst_slab.end()); tap_run_off->push_back(slab);
             }
-            if (!G.total_exact) { G.total = ((const int64_t*)((const char*)h4.p + o_nnz))[G.rows & 1]; G.total_exact = true; }
+            if (!G.total_exact) { G.total = *h_nnz; G.total_exact = true; }
             if (int rc = graph_rows_settle(G, &kc)) return rc;
             const unsigned long long* st = (const unsigned long long*)h4.p;
             if (stats) { stats->n_instances = n_inst + 2 * (int64_t)Wc; stats->sweeps = (int64_t)(st[0] + st[2]); stats->bytes = (int64_t)(st[1] + st[3]); stats->graph_nnz = G.total; }

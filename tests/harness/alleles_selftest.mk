@@ -4,10 +4,10 @@
 CXX ?= g++
 P := ../../hairsplitter_amd/csrc
 all: _build/alleles_selftest
-_build/alleles_selftest: alleles_selftest.cpp $(P)/hs_alleles_host.cpp $(P)/hs_alleles_host.h
+_build/alleles_selftest: alleles_selftest.cpp $(P)/hs_alleles_host.cpp $(P)/hs_alleles_host.h $(P)/hs_rules.h
 	@mkdir -p _build
 	$(CXX) -std=c++17 -O2 -Wall -o $@ alleles_selftest.cpp $(P)/hs_alleles_host.cpp
 asan: _build/alleles_selftest_asan
-_build/alleles_selftest_asan: alleles_selftest.cpp $(P)/hs_alleles_host.cpp $(P)/hs_alleles_host.h
+_build/alleles_selftest_asan: alleles_selftest.cpp $(P)/hs_alleles_host.cpp $(P)/hs_alleles_host.h $(P)/hs_rules.h
 	@mkdir -p _build
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Wall -o $@ alleles_selftest.cpp $(P)/hs_alleles_host.cpp

@@ -4,10 +4,10 @@
 CXX ?= g++
 P := ../../hairsplitter_amd/csrc
 all: _build/recruit_selftest
-_build/recruit_selftest: recruit_selftest.cpp $(P)/hs_recruit_host.cpp $(P)/hs_recruit_host.h
+_build/recruit_selftest: recruit_selftest.cpp $(P)/hs_recruit_host.cpp $(P)/hs_recruit_host.h $(P)/hs_rules.h
 	@mkdir -p _build
 	$(CXX) -std=c++17 -O2 -Wall -o $@ recruit_selftest.cpp $(P)/hs_recruit_host.cpp
 asan: _build/recruit_selftest_asan
-_build/recruit_selftest_asan: recruit_selftest.cpp $(P)/hs_recruit_host.cpp $(P)/hs_recruit_host.h
+_build/recruit_selftest_asan: recruit_selftest.cpp $(P)/hs_recruit_host.cpp $(P)/hs_recruit_host.h $(P)/hs_rules.h
 	@mkdir -p _build
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Wall -o $@ recruit_selftest.cpp $(P)/hs_recruit_host.cpp
