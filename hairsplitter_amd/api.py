@@ -32,6 +32,8 @@ SYMBOLS = [
     "hs_allele_table_destroy", "hs_alleles_text", "hs_alleles_lds_capacity", "hs_group_alleles_layout", "hs_group_alleles", "hs_haplotype_alleles", "hs_pipeline_alleles",
     "hs_recruit_params_default", "hs_recruit_table_destroy", "hs_recruit_reads", "hs_group_recruit_layout", "hs_group_recruit", "hs_recruit_apply", "hs_recruit_text",
     "hs_pipeline_recruits", "hs_pipeline_set_recruit_params",
+    "hs_map_params_default", "hs_map_index_create", "hs_map_index_destroy", "hs_map_index_download", "hs_map_reads", "hs_map_result_destroy", "hs_map_lds_capacity",
+    "hs_map_to_batch", "hs_map_text", "hs_map_files", "hs_map_main",
 ]
 
 HS_NKERNELS = 28
@@ -103,6 +105,23 @@ class RecruitTable(C.Structure):
 class RecruitLayout(C.Structure):
     """hs_recruit_layout: byte offsets of the parts of hs_group_recruit's work buffer (the allele plan's in front)"""
     _fields_ = [("alleles", AlleleLayout)] + [(k, C.c_int64) for k in ("flag", "row_idx", "ctr_off", "win_row_off", "status", "internal", "total_bytes")]
+
+
+class MapParams(C.Structure):
+    """hs_map_params"""
+    _fields_ = [(k, C.c_int32) for k in ("k", "w", "max_occ", "band_log2", "min_votes", "extend", "bucket_bits")]
+
+
+MAP_FIELDS = ("contig", "strand", "qstart", "qend", "tstart", "tend", "votes", "second", "n_minimizers", "n_skipped", "n_hits")
+
+
+class MapResult(C.Structure):
+    """hs_map_result"""
+    _fields_ = [("n_reads", C.c_int32), ("contig", C.POINTER(C.c_int32)), ("strand", C.POINTER(C.c_uint8)), ("qstart", C.POINTER(C.c_int32)), ("qend", C.POINTER(C.c_int32)),
+                ("tstart", C.POINTER(C.c_int32)), ("tend", C.POINTER(C.c_int32)), ("votes", C.POINTER(C.c_int32)), ("second", C.POINTER(C.c_int32)),
+                ("n_minimizers", C.POINTER(C.c_int32)), ("n_skipped", C.POINTER(C.c_int32)), ("n_hits", C.POINTER(C.c_int64)),
+                ("n_wide", C.c_int64), ("total_minimizers", C.c_int64), ("total_hits", C.c_int64),
+                ("t_minimizers_ms", C.c_double), ("t_hits_ms", C.c_double), ("t_vote_ms", C.c_double)]
 
 
 HS_RECRUIT_ABSENT, HS_RECRUIT_UNCLUSTERED, HS_RECRUIT_LABELLED = 1, 2, 4
@@ -181,6 +200,18 @@ def load() -> C.CDLL:
                                      C.POINTER(C.POINTER(RecruitTable))]
     lib.hs_recruit_apply.argtypes = [C.POINTER(RecruitTable), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     lib.hs_recruit_text.argtypes = [C.POINTER(RecruitTable), C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
+    lib.hs_map_params_default.restype = MapParams
+    lib.hs_map_lds_capacity.restype = C.c_int32
+    lib.hs_map_index_destroy.restype = None
+    lib.hs_map_index_destroy.argtypes = [C.c_void_p]
+    lib.hs_map_result_destroy.restype = None
+    lib.hs_map_result_destroy.argtypes = [C.POINTER(MapResult)]
+    lib.hs_map_index_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MapParams), C.POINTER(C.c_void_p)]
+    lib.hs_map_index_download.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hs_map_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.POINTER(MapResult))]
+    lib.hs_map_to_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p),
+                                    C.POINTER(C.POINTER(RealignRecords)), C.POINTER(C.POINTER(MapResult))]
+    lib.hs_map_text.argtypes = [C.POINTER(MapResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
 
@@ -1963,3 +1994,149 @@ def realign_intervals(flat_sequences, intervals, pad: int = 100, want_batch: boo
     finally:
         lib.hs_realign_records_destroy(r)
     return rec, (CvBatch._adopt(h, dt, rec) if want_batch else None)
+
+
+# ---- the read mapper (hs_map_*): minimizer seeds against a resident index of the contigs, a vote over diagonal bins ----
+def map_params(**kw) -> MapParams:
+    """hs_map_params_default with the given fields replaced"""
+    p = load().hs_map_params_default()
+    for k, v in kw.items():
+        if k not in dict(MapParams._fields_):
+            raise HsError("map_params: no field " + k)
+        setattr(p, k, int(v))
+    return p
+
+
+def map_lds_capacity() -> int:
+    return int(load().hs_map_lds_capacity())
+
+
+def _flat(seqs):
+    """list of code arrays -> (codes, offsets)"""
+    off = np.zeros(len(seqs) + 1, np.int64)
+    if len(seqs):
+        np.cumsum([len(s) for s in seqs], out=off[1:])
+    flat = np.concatenate([_np(s, np.uint8).reshape(-1) for s in seqs]) if len(seqs) and off[-1] else np.zeros(0, np.uint8)
+    return np.ascontiguousarray(flat), off
+
+
+class MapIndex:
+    """hs_map_index: the contigs' minimizers, resident on the device until close(); serves any number of map_reads calls"""
+
+    def __init__(self, handle, contig_seq, contig_off, params):
+        self._h, self.contig_seq, self.contig_off, self.params = handle, contig_seq, contig_off, params
+
+    def close(self):
+        if self._h is not None:
+            load().hs_map_index_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def entries(self) -> Dict:
+        """hs_map_index_download: bucket_bits, bucket_off and the entries (hash, contig, t, strand bit) as the device holds them"""
+        lib = load()
+        n = C.c_int64(0); bits = C.c_int32(0)
+        _check(lib.hs_map_index_download(self._h, C.byref(n), C.byref(bits), None, None, None, None))
+        off = np.zeros((1 << bits.value) + 1, np.int64)
+        h = np.zeros(max(n.value, 1), np.uint32); c = np.zeros(max(n.value, 1), np.int32); ts = np.zeros(max(n.value, 1), np.uint32)
+        _check(lib.hs_map_index_download(self._h, None, None, off.ctypes.data, h.ctypes.data, c.ctypes.data, ts.ctypes.data))
+        m = int(n.value)
+        return {"bucket_bits": int(bits.value), "bucket_off": off, "hash": h[:m], "contig": c[:m], "t": (ts[:m] >> 1).astype(np.int64), "strand": (ts[:m] & 1).astype(np.uint8)}
+
+
+def map_index(contigs, params: Optional[MapParams] = None) -> MapIndex:
+    """hs_map_index_create. contigs: a list of code arrays (0..3), or a (codes, offsets) pair."""
+    require_gpu()
+    lib = load()
+    cseq, coff = (_np(contigs[0], np.uint8), _np(contigs[1], np.int64)) if isinstance(contigs, tuple) else _flat(contigs)
+    prm = params if params is not None else lib.hs_map_params_default()
+    h = C.c_void_p()
+    _check(lib.hs_map_index_create(cseq.ctypes.data, coff.ctypes.data, C.c_int32(len(coff) - 1), C.byref(prm), C.byref(h)))
+    return MapIndex(h, cseq, coff, prm)
+
+
+def _map_result_to_dict(r) -> Dict:
+    res = r.contents
+    n = int(res.n_reads)
+    out = {k: np.ctypeslib.as_array(getattr(res, k), shape=(n,)).copy() if n else np.zeros(0, np.int64) for k in MAP_FIELDS}
+    for k in ("n_wide", "total_minimizers", "total_hits"):
+        out[k] = int(getattr(res, k))
+    for k in ("t_minimizers_ms", "t_hits_ms", "t_vote_ms"):
+        out[k] = float(getattr(res, k))
+    return out
+
+
+def map_reads(index: MapIndex, reads) -> Dict:
+    """hs_map_reads: per read contig (-1 unmapped), strand, qstart, qend, tstart, tend, votes, second, n_minimizers, n_hits, n_skipped; per call n_wide.
+    reads: a list of code arrays, or a (codes, offsets) pair."""
+    lib = load()
+    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
+    r = C.POINTER(MapResult)()
+    _check(lib.hs_map_reads(index._h, rseq.ctypes.data, roff.ctypes.data, C.c_int32(len(roff) - 1), C.byref(r)))
+    try:
+        return _map_result_to_dict(r)
+    finally:
+        lib.hs_map_result_destroy(r)
+
+
+def map_intervals(res: Dict) -> np.ndarray:
+    """the mapped reads of a map result as the rows realign_intervals takes: (read, contig, strand, qstart, qend, tstart, tend)"""
+    m = np.flatnonzero(res["contig"] >= 0)
+    return np.stack([m, res["contig"][m], res["strand"][m], res["qstart"][m], res["qend"][m], res["tstart"][m], res["tend"][m]], axis=1).astype(np.int64).reshape(-1, 7)
+
+
+def map_to_batch(index: MapIndex, reads, pad: int = 100):
+    """hs_map_to_batch: map_reads, then realign_intervals on the mapped reads. Returns (CvBatch, records dict, map result dict)."""
+    import time
+    lib = load()
+    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
+    h = C.c_void_p(); rec = C.POINTER(RealignRecords)(); r = C.POINTER(MapResult)()
+    t0 = time.perf_counter()
+    _check(lib.hs_map_to_batch(index._h, index.contig_seq.ctypes.data, index.contig_off.ctypes.data, C.c_int32(len(index.contig_off) - 1), rseq.ctypes.data, roff.ctypes.data,
+                               C.c_int32(len(roff) - 1), C.c_int32(pad), C.byref(h), C.byref(rec), C.byref(r)))
+    dt = time.perf_counter() - t0
+    try:
+        records = _realign_records_to_dict(rec)
+        res = _map_result_to_dict(r)
+    finally:
+        lib.hs_realign_records_destroy(rec)
+        lib.hs_map_result_destroy(r)
+    return CvBatch._adopt(h, dt, records), records, res
+
+
+def map_text(res: Dict, read_lengths, contig_lengths, read_names=None, contig_names=None) -> str:
+    """hs_map_text: the PAF lines of the mapped reads of a map result"""
+    lib = load()
+    n = len(res["contig"])
+    keep = [_np(res[k], np.uint8 if k == "strand" else np.int32) for k in ("contig", "strand", "qstart", "qend", "tstart", "tend", "votes", "second")]
+    r = MapResult()
+    r.n_reads = n
+    for k, a in zip(("contig", "strand", "qstart", "qend", "tstart", "tend", "votes", "second"), keep):
+        setattr(r, k, a.ctypes.data_as(C.POINTER(C.c_uint8 if k == "strand" else C.c_int32)))
+    roff = np.zeros(n + 1, np.int64); np.cumsum(_np(read_lengths, np.int64), out=roff[1:])
+    coff = np.zeros(len(contig_lengths) + 1, np.int64); np.cumsum(_np(contig_lengths, np.int64), out=coff[1:])
+    names = lambda v: (C.c_char_p * len(v))(*[x.encode() for x in v]) if v is not None else None
+    rn, cn = names(read_names), names(contig_names)
+    text = C.c_char_p()
+    _check(lib.hs_map_text(C.byref(r), rn, roff.ctypes.data, cn, coff.ctypes.data, C.c_int32(len(contig_lengths)), C.byref(text)))
+    try:
+        return text.value.decode()
+    finally:
+        lib.hs_free_host(text)
+
+
+def map_files(gfa: str, reads: str, out_paf: str, n_threads: int = 0, params: Optional[MapParams] = None):
+    """hs_map_files: the job's files -> the PAF of the mapped reads (what bin/hs_map writes)"""
+    require_gpu()
+    _check(load().hs_map_files(gfa.encode(), reads.encode(), out_paf.encode(), C.c_int32(n_threads), C.byref(params) if params is not None else None))

@@ -10,6 +10,7 @@
 //   hs_capi_multi.inc    several GPUs in one process
 //   hs_capi_polish.inc   the polisher's inputs of the next stage (hs_polish_inputs)
 //   hs_capi_realign.inc  the CIGAR-less input in memory: intervals -> CIGAR words on the device -> a batch (hs_realign_intervals)
+//   hs_capi_map.inc      the read mapper in front of it: minimizer index of the contigs, seeds and a diagonal vote per read (hs_map_reads)
 // There is no CPU fallback anywhere in this file: without a usable HIP device every entry
 // point fails with HS_ENODEVICE.
 #include <hip/hip_runtime.h>
@@ -27,6 +28,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <iostream>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -47,6 +50,7 @@
 #include "hs_kernels_realign.hip"
 #include "hs_kernels_alleles.hip"
 #include "hs_kernels_recruit.hip"
+#include "hs_kernels_map.hip"
 
 namespace hs {
 static thread_local std::string g_err;
@@ -74,3 +78,4 @@ using hs::set_error;
 #include "hs_capi_multi.inc"
 #include "hs_capi_polish.inc"
 #include "hs_capi_realign.inc"
+#include "hs_capi_map.inc"

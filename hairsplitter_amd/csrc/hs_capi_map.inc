@@ -1,0 +1,335 @@
+// hs_capi_map.inc -- part of hs_capi.hip: the read mapper (include/hairsplitter_hip.h: hs_map_index_create, hs_map_reads, hs_map_to_batch). Kernels
+// in hs_kernels_map.hip, the rule and the host half in hs_map_host.h / hs_map_host.cpp. An index call waits once (the number of minimizers sizes
+// the entries), a map call twice (the minimizers, then the hits: each total sizes what follows). Launches are accounted under HS_K_OTHER.
+struct hs_map_index {
+    hs_map_params params{};
+    int32_t n_contigs = 0, bucket_bits = 0;
+    int64_t n_entries = 0;
+    std::vector<int64_t> contig_off;
+    DBuf d_contig_off, d_bucket_off, d_e_h, d_e_c, d_e_ts;
+};
+
+namespace {
+
+static int map_upload(DBuf& d, const void* src, size_t bytes) {
+    if (int rc = d.alloc(bytes + 16)) return rc;
+    if (bytes) HS_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+    return HS_OK;
+}
+
+// offsets of a job's sequences: ascending from 0, every sequence below 2^31 bases, the whole below 2^38
+static int map_check_offsets(const int64_t* off, int32_t n, const char* what) {
+    bool ok = off[0] == 0;
+    for (int32_t i = 0; ok && i < n; ++i) ok = off[i + 1] >= off[i] && off[i + 1] - off[i] <= 0x7fffffff;
+    if (!ok || off[n] > ((int64_t)1 << 38)) { set_error(std::string(what) + ": offsets must ascend from 0, a sequence holds at most 2^31 - 1 bases and a call 2^38"); return HS_EINVAL; }
+    return HS_OK;
+}
+
+// the minimizers of resident sequences, (sequence, position) ascending: count, scan, (one wait: the total), write
+struct MapMinimizersDev {
+    DBuf h, ps, seq, blk_cnt, blk_off, scan;
+    int64_t n = 0;
+    int run(const uint8_t* d_seq, const int64_t* d_off, int32_t n_seqs, int64_t total, const hs_map_params& p, hipStream_t st) {
+        n = 0;
+        const int64_t n_blk = (total + 255) / 256;
+        if (n_blk > 0) {
+            if (int rc = blk_cnt.alloc((size_t)n_blk * 4)) return rc;
+            if (int rc = blk_off.alloc(((size_t)n_blk + 1) * 8)) return rc;
+            hipLaunchKernelGGL(hsdev::k_map_minimizers<false>, dim3((unsigned)n_blk), dim3(256), 0, st, d_seq, d_off, n_seqs, (long long)total, p.k, p.w, blk_cnt.as<int32_t>(),
+                               (const int64_t*)nullptr, 0ll, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr);
+            HS_HIP(hipGetLastError());
+            if (int rc = exclusive_scan_launch(blk_cnt.as<int32_t>(), (int)n_blk, blk_off.as<int64_t>(), scan, st)) return rc;
+            if (int rc = copy_d2h(&n, blk_off.as<int64_t>() + n_blk, 8, st)) return rc;
+            if (n < 0 || n > total) { set_error("map: the device's minimizer count does not fit the sequences"); return HS_EHIP; }
+        }
+        for (DBuf* b : {&h, &ps, &seq}) if (int rc = b->alloc((size_t)std::max<int64_t>(n, 1) * 4)) return rc;
+        if (n > 0) {
+            hipLaunchKernelGGL(hsdev::k_map_minimizers<true>, dim3((unsigned)n_blk), dim3(256), 0, st, d_seq, d_off, n_seqs, (long long)total, p.k, p.w, (int32_t*)nullptr,
+                               blk_off.as<int64_t>(), (long long)n, h.as<uint32_t>(), ps.as<uint32_t>(), seq.as<int32_t>());
+            HS_HIP(hipGetLastError());
+        }
+        return HS_OK;
+    }
+};
+
+template <class T> static T* map_download(const DBuf& d, size_t n, hipStream_t st, int* rc) {
+    T* p = (T*)std::calloc(std::max<size_t>(1, n), sizeof(T));
+    if (!p) { set_error("hs_map_reads: out of memory"); *rc = HS_EINVAL; return nullptr; }
+    if (n && *rc == HS_OK) *rc = d2h_pinned(p, d.p, n * sizeof(T), st);
+    return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t hs_map_lds_capacity(void) { return HS_MAP_LDS_KEYS; }
+
+void hs_map_index_destroy(hs_map_index* index) { delete index; }
+
+int hs_map_index_create(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const hs_map_params* params, hs_map_index** index) {
+    if (int rc = require_device()) return rc;
+    if (!index || !h_contig_off || n_contigs < 0) { set_error("hs_map_index_create: bad arguments"); return HS_EINVAL; }
+    *index = nullptr;
+    const hs_map_params prm = params ? *params : hs_map_params_default();
+    if (!hs::map_params_valid(prm)) { set_error("hs_map_index_create: parameters out of range (k 5..16, w 1..32, max_occ >= 1, band_log2 0..30, min_votes >= 1, extend 0|1, bucket_bits -1..26)"); return HS_EINVAL; }
+    if (int rc = map_check_offsets(h_contig_off, n_contigs, "hs_map_index_create")) return rc;
+    const int64_t total = h_contig_off[n_contigs];
+    if (total > 0 && !h_contig_seq) { set_error("hs_map_index_create: bad arguments"); return HS_EINVAL; }
+    try {
+        std::unique_ptr<hs_map_index> ix(new hs_map_index());
+        ix->params = prm; ix->n_contigs = n_contigs;
+        ix->contig_off.assign(h_contig_off, h_contig_off + n_contigs + 1);
+        const hipStream_t st = nullptr;
+        KernelClock kc;
+        DBuf d_seq, d_cnt, d_scan;
+        if (int rc = map_upload(d_seq, h_contig_seq, (size_t)total)) return rc;
+        if (int rc = map_upload(ix->d_contig_off, h_contig_off, ((size_t)n_contigs + 1) * 8)) return rc;
+        MapMinimizersDev mz;
+        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
+        if (int rc = mz.run(d_seq.as<uint8_t>(), ix->d_contig_off.as<int64_t>(), n_contigs, total, prm, st)) return rc;
+        if (int rc = kc.end(total + 12 * mz.n, st)) return rc;
+        const int64_t n = ix->n_entries = mz.n;
+        if (n > 0x7fffffff - HS_SCAN_TILE) { set_error("hs_map_index_create: more than 2^31 contig minimizers"); return HS_EINVAL; }
+        ix->bucket_bits = hs::map_bucket_bits(prm, n);
+        const int64_t n_buckets = (int64_t)1 << ix->bucket_bits;
+        const uint32_t mask = (uint32_t)(n_buckets - 1);
+        if (int rc = d_cnt.alloc((size_t)n_buckets * 4)) return rc;
+        if (int rc = ix->d_bucket_off.alloc(((size_t)n_buckets + 1) * 8)) return rc;
+        if (int rc = ix->d_e_h.alloc((size_t)std::max<int64_t>(n, 1) * 4)) return rc;
+        if (int rc = ix->d_e_c.alloc((size_t)std::max<int64_t>(n, 1) * 4)) return rc;
+        if (int rc = ix->d_e_ts.alloc((size_t)std::max<int64_t>(n, 1) * 4)) return rc;
+        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
+        HS_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)n_buckets * 4, st));
+        const unsigned grid = (unsigned)((n + 255) / 256);
+        if (n > 0) hipLaunchKernelGGL(hsdev::k_map_bucket_count, dim3(grid), dim3(256), 0, st, mz.h.as<uint32_t>(), (long long)n, mask, d_cnt.as<int32_t>());
+        if (int rc = exclusive_scan_launch(d_cnt.as<int32_t>(), (int)n_buckets, ix->d_bucket_off.as<int64_t>(), d_scan, st)) return rc;
+        HS_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)n_buckets * 4, st));
+        if (n > 0) hipLaunchKernelGGL(hsdev::k_map_bucket_fill, dim3(grid), dim3(256), 0, st, mz.h.as<uint32_t>(), mz.ps.as<uint32_t>(), mz.seq.as<int32_t>(), (long long)n, mask,
+                                      ix->d_bucket_off.as<int64_t>(), d_cnt.as<int32_t>(), ix->d_e_h.as<uint32_t>(), ix->d_e_c.as<int32_t>(), ix->d_e_ts.as<uint32_t>());
+        HS_HIP(hipGetLastError());
+        if (int rc = kc.end(24 * n + 16 * n_buckets, st)) return rc;
+        if (int rc = stream_wait(st)) return rc;      // (the scratch goes back to the pool with this scope)
+        kc.flush();
+        *index = ix.release();
+        return HS_OK;
+    } catch (const std::exception& e) { set_error(std::string("hs_map_index_create: ") + e.what()); return HS_EINVAL; }
+}
+
+int hs_map_index_download(const hs_map_index* index, int64_t* n_entries, int32_t* bucket_bits, int64_t* bucket_off, uint32_t* e_hash, int32_t* e_contig, uint32_t* e_ts) {
+    if (int rc = require_device()) return rc;
+    if (!index) { set_error("hs_map_index_download: null argument"); return HS_EINVAL; }
+    if (n_entries) *n_entries = index->n_entries;
+    if (bucket_bits) *bucket_bits = index->bucket_bits;
+    const hipStream_t st = nullptr;
+    const size_t n = (size_t)index->n_entries;
+    if (bucket_off) { if (int rc = d2h_pinned(bucket_off, index->d_bucket_off.p, (((size_t)1 << index->bucket_bits) + 1) * 8, st)) return rc; }
+    if (e_hash && n) { if (int rc = d2h_pinned(e_hash, index->d_e_h.p, n * 4, st)) return rc; }
+    if (e_contig && n) { if (int rc = d2h_pinned(e_contig, index->d_e_c.p, n * 4, st)) return rc; }
+    if (e_ts && n) { if (int rc = d2h_pinned(e_ts, index->d_e_ts.p, n * 4, st)) return rc; }
+    return HS_OK;
+}
+
+int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, hs_map_result** result) {
+    if (int rc = require_device()) return rc;
+    if (!index || !result || !h_read_off || n_reads < 0) { set_error("hs_map_reads: bad arguments"); return HS_EINVAL; }
+    *result = nullptr;
+    if (int rc = map_check_offsets(h_read_off, n_reads, "hs_map_reads")) return rc;
+    const int64_t total = h_read_off[n_reads];
+    if (total > 0 && !h_read_seq) { set_error("hs_map_reads: bad arguments"); return HS_EINVAL; }
+    try {
+        const hs_map_params& prm = index->params;
+        const hipStream_t st = nullptr;
+        const size_t R = (size_t)n_reads;
+        KernelClock kc;
+        EventPair ev_mz, ev_hits, ev_vote;
+        for (EventPair* e : {&ev_mz, &ev_hits, &ev_vote}) if (int rc = e->init()) return rc;
+        DBuf d_seq, d_off, d_mz_off, d_cnt, d_hit_off, d_scan, d_max, d_key, d_qa, d_t, d_wide, d_slabs;
+        DBuf d_contig, d_strand, d_qs, d_qe, d_ts, d_te, d_votes, d_second, d_nmz, d_nskip, d_nhits;
+        if (int rc = map_upload(d_seq, h_read_seq, (size_t)total)) return rc;
+        if (int rc = map_upload(d_off, h_read_off, (R + 1) * 8)) return rc;
+        // ---- minimizers and every read's range of them ----
+        MapMinimizersDev mz;
+        HS_HIP(ev_rec(ev_mz.a, st));
+        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
+        if (int rc = mz.run(d_seq.as<uint8_t>(), d_off.as<int64_t>(), n_reads, total, prm, st)) return rc;
+        const int64_t M = mz.n;
+        if (M > 0x7fffffff - HS_SCAN_TILE) { set_error("hs_map_reads: more than 2^31 read minimizers in one call: map the reads in several calls"); return HS_EINVAL; }
+        if (int rc = d_mz_off.alloc((R + 1) * 8)) return rc;
+        hipLaunchKernelGGL(hsdev::k_map_seq_ranges, dim3((unsigned)(R / 256 + 1)), dim3(256), 0, st, mz.seq.as<int32_t>(), (long long)M, n_reads, d_mz_off.as<int64_t>());
+        HS_HIP(hipGetLastError());
+        if (int rc = kc.end(total + 12 * M, st)) return rc;
+        HS_HIP(ev_rec(ev_mz.b, st));
+        // ---- occ of every minimizer, the hits' offsets, (one wait: their total and the most a read has) ----
+        for (DBuf* b : {&d_contig, &d_qs, &d_qe, &d_ts, &d_te, &d_votes, &d_second, &d_nmz, &d_nskip}) if (int rc = b->alloc(std::max<size_t>(R, 1) * 4)) return rc;
+        if (int rc = d_strand.alloc(std::max<size_t>(R, 1))) return rc;
+        if (int rc = d_nhits.alloc(std::max<size_t>(R, 1) * 8)) return rc;
+        if (int rc = d_cnt.alloc((size_t)std::max<int64_t>(M, 1) * 4)) return rc;
+        if (int rc = d_hit_off.alloc(((size_t)M + 1) * 8)) return rc;
+        if (int rc = d_max.alloc(16)) return rc;
+        if (int rc = d_wide.alloc((R + 1) * 4)) return rc;      // the list, and its count behind it
+        hsdev::MapIndexDev X{index->d_bucket_off.as<int64_t>(), index->d_e_h.as<uint32_t>(), index->d_e_c.as<int32_t>(), index->d_e_ts.as<uint32_t>(),
+                             (uint32_t)(((int64_t)1 << index->bucket_bits) - 1), (long long)index->n_entries, index->d_contig_off.as<int64_t>(), index->n_contigs};
+        HS_HIP(ev_rec(ev_hits.a, st));
+        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
+        HS_HIP(hipMemsetAsync(d_nskip.p, 0, std::max<size_t>(R, 1) * 4, st));
+        HS_HIP(hipMemsetAsync(d_max.p, 0, 16, st));
+        HS_HIP(hipMemsetAsync(d_wide.as<int32_t>() + R, 0, 4, st));
+        const unsigned grid_m = (unsigned)((M + 255) / 256);
+        if (M > 0) hipLaunchKernelGGL(hsdev::k_map_hits_count, dim3(grid_m), dim3(256), 0, st, X, mz.h.as<uint32_t>(), mz.seq.as<int32_t>(), (long long)M, n_reads, prm.max_occ,
+                                      d_cnt.as<int32_t>(), d_nskip.as<int32_t>());
+        if (int rc = exclusive_scan_launch(d_cnt.as<int32_t>(), (int)M, d_hit_off.as<int64_t>(), d_scan, st)) return rc;
+        if (R) hipLaunchKernelGGL(hsdev::k_map_read_hits, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, d_mz_off.as<int64_t>(), d_hit_off.as<int64_t>(), n_reads,
+                                  d_nhits.as<int64_t>(), d_nmz.as<int32_t>(), d_max.as<unsigned long long>());
+        HS_HIP(hipGetLastError());
+        int64_t H = 0, max_hits = 0;
+        HS_HIP(HS_COPY_ASYNC(&max_hits, d_max.p, 8, hipMemcpyDeviceToHost, st));
+        if (int rc = copy_d2h(&H, d_hit_off.as<int64_t>() + M, 8, st)) return rc;
+        if (H < 0 || max_hits < 0 || max_hits > H) { set_error("hs_map_reads: the device's hit counts do not fit the minimizers"); return HS_EHIP; }
+        if (max_hits > ((int64_t)1 << 28)) { set_error("hs_map_reads: a read with more than 2^28 hits: lower max_occ"); return HS_EINVAL; }
+        // ---- the hits ----
+        if (int rc = d_key.alloc((size_t)std::max<int64_t>(H, 1) * 8)) return rc;
+        if (int rc = d_qa.alloc((size_t)std::max<int64_t>(H, 1) * 4)) return rc;
+        if (int rc = d_t.alloc((size_t)std::max<int64_t>(H, 1) * 4)) return rc;
+        if (M > 0 && H > 0) hipLaunchKernelGGL(hsdev::k_map_hits_fill, dim3(grid_m), dim3(256), 0, st, X, mz.h.as<uint32_t>(), mz.ps.as<uint32_t>(), mz.seq.as<int32_t>(), (long long)M,
+                                               d_off.as<int64_t>(), n_reads, prm, d_cnt.as<int32_t>(), d_hit_off.as<int64_t>(), (long long)H, d_key.as<uint64_t>(), d_qa.as<int32_t>(),
+                                               d_t.as<int32_t>());
+        HS_HIP(hipGetLastError());
+        if (int rc = kc.end(8 * M + 2 * 16 * H, st)) return rc;
+        HS_HIP(ev_rec(ev_hits.b, st));
+        // ---- the vote: LDS route for every read, the scratch route for the list it leaves ----
+        int64_t slab_keys = 2;
+        while (slab_keys < max_hits) slab_keys <<= 1;
+        if (max_hits <= HS_MAP_LDS_KEYS) slab_keys = 2;      // (the list stays empty)
+        const int wide_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(HS_MAP_WIDE_BLOCKS, ((int64_t)1 << 28) / slab_keys));
+        if (int rc = d_slabs.alloc((size_t)slab_keys * 8 * (size_t)wide_blocks)) return rc;
+        hsdev::MapVoteArgs A{};
+        A.mz_off = d_mz_off.as<int64_t>(); A.hit_off = d_hit_off.as<int64_t>(); A.hit_key = d_key.as<uint64_t>(); A.hit_qa = d_qa.as<int32_t>(); A.hit_t = d_t.as<int32_t>(); A.n_hits = H;
+        A.read_off = d_off.as<int64_t>(); A.contig_off = index->d_contig_off.as<int64_t>(); A.n_contigs = index->n_contigs; A.n_reads = n_reads; A.P = prm;
+        A.contig = d_contig.as<int32_t>(); A.strand = d_strand.as<uint8_t>(); A.qstart = d_qs.as<int32_t>(); A.qend = d_qe.as<int32_t>(); A.tstart = d_ts.as<int32_t>();
+        A.tend = d_te.as<int32_t>(); A.votes = d_votes.as<int32_t>(); A.second = d_second.as<int32_t>(); A.wide_list = d_wide.as<int32_t>(); A.wide_count = d_wide.as<int32_t>() + R;
+        HS_HIP(ev_rec(ev_vote.a, st));
+        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
+        if (R) hipLaunchKernelGGL(hsdev::k_map_vote, dim3((unsigned)R), dim3(256), 0, st, A);
+        hipLaunchKernelGGL(hsdev::k_map_vote_wide, dim3((unsigned)wide_blocks), dim3(256), 0, st, A, d_slabs.as<uint64_t>(), (long long)slab_keys);
+        HS_HIP(hipGetLastError());
+        if (int rc = kc.end(2 * 16 * H + 30 * (int64_t)R, st)) return rc;
+        HS_HIP(ev_rec(ev_vote.b, st));
+        // ---- the records ----
+        hs_map_result* r = (hs_map_result*)std::calloc(1, sizeof(hs_map_result));
+        if (!r) { set_error("hs_map_reads: out of memory"); return HS_EINVAL; }
+        int rc = HS_OK;
+        r->n_reads = n_reads;
+        r->contig = map_download<int32_t>(d_contig, R, st, &rc); r->strand = map_download<uint8_t>(d_strand, R, st, &rc);
+        r->qstart = map_download<int32_t>(d_qs, R, st, &rc); r->qend = map_download<int32_t>(d_qe, R, st, &rc);
+        r->tstart = map_download<int32_t>(d_ts, R, st, &rc); r->tend = map_download<int32_t>(d_te, R, st, &rc);
+        r->votes = map_download<int32_t>(d_votes, R, st, &rc); r->second = map_download<int32_t>(d_second, R, st, &rc);
+        r->n_minimizers = map_download<int32_t>(d_nmz, R, st, &rc); r->n_skipped = map_download<int32_t>(d_nskip, R, st, &rc);
+        r->n_hits = map_download<int64_t>(d_nhits, R, st, &rc);
+        int32_t n_wide = 0;
+        if (rc == HS_OK) rc = copy_d2h(&n_wide, d_wide.as<int32_t>() + R, 4, st);
+        if (rc == HS_OK) rc = stream_wait(st);
+        if (rc != HS_OK) { hs_map_result_destroy(r); return rc; }
+        r->n_wide = n_wide; r->total_minimizers = M; r->total_hits = H;
+        float ms = 0;
+        if (ev_mz.ms(&ms) == HS_OK) r->t_minimizers_ms = ms;
+        if (ev_hits.ms(&ms) == HS_OK) r->t_hits_ms = ms;
+        if (ev_vote.ms(&ms) == HS_OK) r->t_vote_ms = ms;
+        kc.flush();
+        *result = r;
+        return HS_OK;
+    } catch (const std::exception& e) { set_error(std::string("hs_map_reads: ") + e.what()); return HS_EINVAL; }
+}
+
+int hs_map_to_batch(const hs_map_index* index, const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off,
+                    int32_t n_reads, int32_t pad, hs_cv_batch** batch, hs_realign_records** records, hs_map_result** result) {
+    if (int rc = require_device()) return rc;
+    if (!index || !batch || !h_contig_off || n_contigs != index->n_contigs) { set_error("hs_map_to_batch: bad arguments (the contigs are the index's)"); return HS_EINVAL; }
+    *batch = nullptr;
+    if (records) *records = nullptr;
+    if (result) *result = nullptr;
+    hs_map_result* mr = nullptr;
+    if (int rc = hs_map_reads(index, h_read_seq, h_read_off, n_reads, &mr)) return rc;
+    try {
+        std::vector<int32_t> iv_read, iv_contig, qs, qe, ts, te;
+        std::vector<uint8_t> strand;
+        for (int32_t i = 0; i < n_reads; ++i) {
+            if (mr->contig[i] < 0) continue;
+            iv_read.push_back(i); iv_contig.push_back(mr->contig[i]); strand.push_back(mr->strand[i]);
+            qs.push_back(mr->qstart[i]); qe.push_back(mr->qend[i]); ts.push_back(mr->tstart[i]); te.push_back(mr->tend[i]);
+        }
+        hs_realign_records* rec = nullptr;
+        const int rc = hs_realign_intervals(h_contig_seq, h_contig_off, n_contigs, h_read_seq, h_read_off, n_reads, iv_read.data(), iv_contig.data(), strand.data(), qs.data(), qe.data(),
+                                            ts.data(), te.data(), (int32_t)iv_read.size(), pad, &rec, batch);
+        if (rc) { hs_map_result_destroy(mr); return rc; }
+        if (records) *records = rec; else hs_realign_records_destroy(rec);
+        if (result) *result = mr; else hs_map_result_destroy(mr);
+        return HS_OK;
+    } catch (const std::exception& e) { hs_map_result_destroy(mr); set_error(std::string("hs_map_to_batch: ") + e.what()); return HS_EINVAL; }
+}
+
+// the job's files -> PAF lines of the mapped reads. An assembly that holds no S line and begins with '>' is read as FASTA.
+int hs_map_files(const char* gfa, const char* reads, const char* out_paf, int32_t n_threads, const hs_map_params* params) {
+    if (int rc = require_device()) return rc;
+    if (!gfa || !reads || !out_paf) { set_error("hs_map_files: null argument"); return HS_EINVAL; }
+    try {
+        if (n_threads < 1) n_threads = host_threads();
+        hs::SeqSet seqs;
+        if (int rc = hs::load_sequences(gfa, reads, seqs, n_threads)) return rc;
+        if (seqs.contig_names.empty()) {
+            std::ifstream f(gfa);
+            std::string line;
+            bool fasta = false;
+            while (std::getline(f, line)) {
+                if (!line.empty() && line.back() == '\r') line.pop_back();
+                if (line.empty()) continue;
+                if (line[0] == '>') {
+                    fasta = true;
+                    if (!seqs.contig_names.empty()) seqs.contig_off.push_back((int64_t)seqs.contig_seq.size());
+                    seqs.contig_names.push_back(line.substr(1, line.find_first_of(" \t", 1) == std::string::npos ? std::string::npos : line.find_first_of(" \t", 1) - 1));
+                } else if (fasta) {
+                    for (char ch : line) seqs.contig_seq.push_back(ch == 'C' || ch == 'c' ? 1 : ch == 'G' || ch == 'g' ? 2 : ch == 'T' || ch == 't' ? 3 : 0);
+                }
+            }
+            if (fasta) seqs.contig_off.push_back((int64_t)seqs.contig_seq.size());
+        }
+        if (seqs.read_names.size() > 0x7fffffffu || seqs.contig_names.size() > 0x7fffffffu) { set_error("hs_map_files: more than 2^31 reads or contigs"); return HS_EINVAL; }
+        const int32_t C = (int32_t)seqs.contig_names.size(), R = (int32_t)seqs.read_names.size();
+        hs_map_index* ix = nullptr;
+        if (int rc = hs_map_index_create(seqs.contig_seq.data(), seqs.contig_off.data(), C, params, &ix)) return rc;
+        hs_map_result* res = nullptr;
+        const int rc = hs_map_reads(ix, seqs.read_seq.data(), seqs.read_off.data(), R, &res);
+        hs_map_index_destroy(ix);
+        if (rc) return rc;
+        std::vector<const char*> rn((size_t)R), cn((size_t)C);
+        for (int32_t i = 0; i < R; ++i) rn[(size_t)i] = seqs.read_names[(size_t)i].c_str();
+        for (int32_t i = 0; i < C; ++i) cn[(size_t)i] = seqs.contig_names[(size_t)i].c_str();
+        char* text = nullptr;
+        const int rc2 = hs_map_text(res, rn.data(), seqs.read_off.data(), cn.data(), seqs.contig_off.data(), C, &text);
+        int64_t n_mapped = 0;
+        for (int32_t i = 0; i < R; ++i) n_mapped += res->contig[i] >= 0;
+        if (std::getenv("HS_TIMING")) std::fprintf(stderr, "[hs timing] map: %ld of %d reads mapped, %ld minimizers, %ld hits, %ld reads through the scratch route, kernels %.2f + %.2f + %.2f ms\n",
+                                                   (long)n_mapped, R, (long)res->total_minimizers, (long)res->total_hits, (long)res->n_wide, res->t_minimizers_ms, res->t_hits_ms, res->t_vote_ms);
+        hs_map_result_destroy(res);
+        if (rc2) { set_error("hs_map_files: out of memory"); return rc2; }
+        std::ofstream o(out_paf);
+        o << text;
+        std::free(text);
+        o.close();
+        if (!o) { set_error(std::string("hs_map_files: could not write ") + out_paf); return HS_EIO; }
+        return HS_OK;
+    } catch (const std::exception& e) { set_error(std::string("hs_map_files: ") + e.what()); return HS_EINVAL; }
+}
+
+// argv = <gfa|fasta> <reads> <out.paf> [threads]
+int hs_map_main(int argc, char** argv) {
+    if (argc < 4) { std::cout << "Usage: hs_map <gfa|fasta> <reads> <out.paf> [threads]\n"; return argc < 2 ? 0 : 1; }
+    const int threads = argc > 4 ? std::atoi(argv[4]) : 0;
+    if (int rc = hs_map_files(argv[1], argv[2], argv[3], threads, nullptr)) {
+        std::cout << "ERROR: " << hs_last_error() << " (" << rc << ")" << std::endl;
+        return 1;
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,285 @@
+// hs_kernels_map.hip -- the read mapper on the device: minimizers of contigs and reads, the bucketed index of the contigs' minimizers, the hits
+// of every read minimizer, and the vote over diagonal bins that names a read's contig window. The rule is stated once, in hs_map_host.h, and
+// every kernel below ends in its functions (map_kmer, map_hit, map_beats, map_second_allowed, map_in_best, map_interval). gfx950, wave64;
+// builtins and plain C++ only, plain vector stores only.
+//
+//   k_map_minimizers<false|true>   a workgroup owns 256 consecutive bases of the concatenated sequences plus a halo of w - 1 <= 31 on either side;
+//                                  hashes and every window's minimum go through LDS; the count pass leaves one count per workgroup, the write
+//                                  pass (behind exclusive_scan_launch) writes in (sequence, position) order
+//   k_map_seq_ranges               the minimizer range of every sequence
+//   k_map_bucket_count / _fill     the index: bucket = low bits of the hash; no-return atomics count, an atomic cursor fills (the order inside
+//                                  a bucket differs from run to run and no result depends on it)
+//   k_map_hits_count / _fill       one lane per read minimizer scans its bucket: occ(h), then (key, qa, t) into the read's range of the scratch
+//   k_map_vote                     one workgroup per read: keys sorted in LDS (the bitonic network of k_allele_cells), runs of equal keys give n,
+//                                  a run and its successor the score, a block maximum under the rule's total order best and second, a second
+//                                  pass over the hits the four extremes. More than HS_MAP_LDS_KEYS hits: on a list for
+//   k_map_vote_wide                the same in a slab of global scratch (always queued; an empty list ends it)
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "hs_map_host.h"
+
+#define HS_MAP_LDS_KEYS 4096        /* hits of a read whose keys one workgroup sorts in LDS (32 KB) */
+#define HS_MAP_WIDE_BLOCKS 16       /* most workgroups (and slabs) of k_map_vote_wide */
+#define HS_MAP_HALO 31              /* w - 1 at most */
+
+namespace hsdev {
+
+// the sequence that holds base g of the concatenation (0 <= g < off[n_seqs]; empty sequences hold none)
+static __device__ __forceinline__ int map_seq_of(const int64_t* __restrict__ off, int n_seqs, long long g) {
+    int lo = 0, hi = n_seqs - 1;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (off[mid + 1] <= g) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_map_minimizers(const uint8_t* __restrict__ seq, const int64_t* __restrict__ off, int n_seqs, long long total, int k, int w,
+                                                        int32_t* __restrict__ blk_cnt, const int64_t* __restrict__ blk_off, long long n_out,
+                                                        uint32_t* __restrict__ out_h, uint32_t* __restrict__ out_ps, int32_t* __restrict__ out_seq) {
+    __shared__ uint64_t s_h[256 + 2 * HS_MAP_HALO];      // slot i = base g0 - HALO + i: its k-mer's hash, or all ones (no k-mer there, or a skipped one)
+    __shared__ int32_t s_arg[256 + HS_MAP_HALO];         // the window that starts at slot i: the slot of its minimizer (-1: no window, or all skipped)
+    __shared__ int32_t s_wave[4];
+    const int tid = (int)threadIdx.x;
+    const long long g0 = (long long)blockIdx.x * 256;
+    for (int i = tid; i < 256 + 2 * HS_MAP_HALO; i += 256) {
+        const long long g = g0 - HS_MAP_HALO + i;
+        uint64_t v = ~0ull;
+        if (g >= 0 && g < total) {
+            const int s = map_seq_of(off, n_seqs, g);
+            uint32_t h, sb;
+            if (g + k <= off[s + 1] && hs::map_kmer(seq + g, k, &h, &sb)) v = h;
+        }
+        s_h[i] = v;
+    }
+    __syncthreads();
+    for (int i = tid; i < 256 + HS_MAP_HALO; i += 256) {
+        const long long g = g0 - HS_MAP_HALO + i;
+        int arg = -1;
+        if (g >= 0 && g < total) {
+            const int s = map_seq_of(off, n_seqs, g);
+            const long long p = g - off[s], n = off[s + 1] - off[s] - k + 1;
+            if (n >= 1 && p <= hs::map_last_window(n, w)) {
+                const int len = (int)(n - p < w ? n - p : w);      // (a window never leaves its sequence)
+                uint64_t best = ~0ull;
+                for (int q = 0; q < len; ++q) { const uint64_t v = s_h[i + q]; if (v < best) { best = v; arg = i + q; } }      // (strict: the leftmost of equal hashes)
+            }
+        }
+        s_arg[i] = arg;
+    }
+    __syncthreads();
+    const int me = HS_MAP_HALO + tid;
+    bool named = false;
+    if (s_h[me] != ~0ull)
+        for (int j = me - (w - 1); j <= me; ++j) named = named || s_arg[j] == me;
+    const unsigned long long ballot = __ballot(named);
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) s_wave[wave] = __popcll(ballot);
+    __syncthreads();
+    if (!WRITE) {
+        if (tid == 0) blk_cnt[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        return;
+    }
+    if (!named) return;
+    long long o = blk_off[blockIdx.x] + __popcll(ballot & ((1ull << lane) - 1ull));
+    for (int v = 0; v < wave; ++v) o += s_wave[v];
+    if (o < 0 || o >= n_out) return;      // never write beyond the count pass's total
+    const long long g = g0 + tid;
+    const int s = map_seq_of(off, n_seqs, g);
+    uint32_t h = 0, sb = 0;
+    (void)hs::map_kmer(seq + g, k, &h, &sb);
+    out_h[o] = h; out_ps[o] = ((uint32_t)(g - off[s]) << 1) | sb; out_seq[o] = s;
+}
+
+// mz_off[s] = the first minimizer of a sequence >= s (mz_seq ascends), s = 0 .. n_seqs
+__global__ __launch_bounds__(256) void k_map_seq_ranges(const int32_t* __restrict__ mz_seq, long long n, int n_seqs, int64_t* __restrict__ mz_off) {
+    const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (s > n_seqs) return;
+    long long lo = 0, hi = n;
+    while (lo < hi) { const long long mid = (lo + hi) >> 1; if (mz_seq[mid] < s) lo = mid + 1; else hi = mid; }
+    mz_off[s] = lo;
+}
+
+__global__ __launch_bounds__(256) void k_map_bucket_count(const uint32_t* __restrict__ h, long long n, uint32_t mask, int32_t* __restrict__ cnt) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) atomicAdd(&cnt[h[i] & mask], 1);
+}
+__global__ __launch_bounds__(256) void k_map_bucket_fill(const uint32_t* __restrict__ h, const uint32_t* __restrict__ ps, const int32_t* __restrict__ sq, long long n, uint32_t mask,
+                                                         const int64_t* __restrict__ bucket_off, int32_t* __restrict__ cursor, uint32_t* __restrict__ e_h,
+                                                         int32_t* __restrict__ e_c, uint32_t* __restrict__ e_ts) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t b = h[i] & mask;
+    const long long o = bucket_off[b] + atomicAdd(&cursor[b], 1);
+    if (o < 0 || o >= bucket_off[b + 1] || o >= n) return;
+    e_h[o] = h[i]; e_c[o] = sq[i]; e_ts[o] = ps[i];
+}
+
+struct MapIndexDev {
+    const int64_t* bucket_off; const uint32_t* e_h; const int32_t* e_c; const uint32_t* e_ts; uint32_t mask; long long n_entries;
+    const int64_t* contig_off; int n_contigs;
+};
+
+// occ(h) of every read minimizer: cnt = occ, or 0 beyond max_occ (then the read's n_skipped counts it)
+__global__ __launch_bounds__(256) void k_map_hits_count(MapIndexDev X, const uint32_t* __restrict__ mz_h, const int32_t* __restrict__ mz_seq, long long n_mz, int n_reads, int max_occ,
+                                                        int32_t* __restrict__ cnt, int32_t* __restrict__ n_skipped) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_mz) return;
+    const uint32_t h = mz_h[i];
+    long long e = X.bucket_off[h & X.mask], e1 = X.bucket_off[(h & X.mask) + 1];
+    if (e < 0) e = 0;
+    if (e1 > X.n_entries) e1 = X.n_entries;
+    int occ = 0;
+    for (; e < e1; ++e) occ += X.e_h[e] == h ? 1 : 0;
+    const int r = mz_seq[i];
+    if (occ > max_occ) { occ = 0; if (r >= 0 && r < n_reads) atomicAdd(&n_skipped[r], 1); }
+    cnt[i] = occ;
+}
+// hits of every read, and the most any read has
+__global__ __launch_bounds__(256) void k_map_read_hits(const int64_t* __restrict__ mz_off, const int64_t* __restrict__ hit_off, int n_reads, int64_t* __restrict__ n_hits,
+                                                       int32_t* __restrict__ n_minimizers, unsigned long long* __restrict__ max_hits) {
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= n_reads) return;
+    const long long n = hit_off[mz_off[r + 1]] - hit_off[mz_off[r]];
+    n_hits[r] = n; n_minimizers[r] = (int32_t)(mz_off[r + 1] - mz_off[r]);
+    if (n > 0) atomicMax(max_hits, (unsigned long long)n);
+}
+__global__ __launch_bounds__(256) void k_map_hits_fill(MapIndexDev X, const uint32_t* __restrict__ mz_h, const uint32_t* __restrict__ mz_ps, const int32_t* __restrict__ mz_seq,
+                                                       long long n_mz, const int64_t* __restrict__ read_off, int n_reads, hs_map_params P, const int32_t* __restrict__ cnt,
+                                                       const int64_t* __restrict__ hit_off, long long n_hits, uint64_t* __restrict__ hit_key, int32_t* __restrict__ hit_qa,
+                                                       int32_t* __restrict__ hit_t) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_mz || cnt[i] == 0) return;
+    const int r = mz_seq[i];
+    if (r < 0 || r >= n_reads) return;
+    const int32_t Lr = (int32_t)(read_off[r + 1] - read_off[r]);
+    const uint32_t h = mz_h[i], ps = mz_ps[i];
+    long long o = hit_off[i];
+    long long o1 = hit_off[i + 1];
+    if (o < 0) return;
+    if (o1 > n_hits) o1 = n_hits;      // never write beyond the scratch
+    long long e = X.bucket_off[h & X.mask], e1 = X.bucket_off[(h & X.mask) + 1];
+    if (e < 0) e = 0;
+    if (e1 > X.n_entries) e1 = X.n_entries;
+    for (; e < e1 && o < o1; ++e) {
+        if (X.e_h[e] != h) continue;
+        const uint32_t ts = X.e_ts[e];
+        int32_t qa;
+        hit_key[o] = hs::map_hit(X.e_c[e], (int32_t)(ts >> 1), ts & 1u, (int32_t)(ps >> 1), ps & 1u, Lr, P, &qa);
+        hit_qa[o] = qa; hit_t[o] = (int32_t)(ts >> 1);
+        ++o;
+    }
+}
+
+struct MapVoteArgs {
+    const int64_t* mz_off; const int64_t* hit_off; const uint64_t* hit_key; const int32_t* hit_qa; const int32_t* hit_t; long long n_hits;
+    const int64_t* read_off; const int64_t* contig_off; int n_contigs, n_reads;
+    hs_map_params P;
+    int32_t* contig; uint8_t* strand; int32_t* qstart; int32_t* qend; int32_t* tstart; int32_t* tend; int32_t* votes; int32_t* second;
+    int32_t* wide_count; int32_t* wide_list;
+};
+
+// the block's best (score, key) under the rule's order; every thread calls it and gets the result. sc == 0: no candidate
+static __device__ void map_block_best(uint32_t& sc, uint64_t& key, uint32_t* s_sc, uint64_t* s_key) {
+    const int tid = (int)threadIdx.x;
+    s_sc[tid] = sc; s_key[tid] = key;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+        if (tid < d) {
+            const uint32_t so = s_sc[tid + d]; const uint64_t ko = s_key[tid + d];
+            if (so != 0 && (s_sc[tid] == 0 || hs::map_beats(so, ko, s_sc[tid], s_key[tid]))) { s_sc[tid] = so; s_key[tid] = ko; }
+        }
+        __syncthreads();
+    }
+    sc = s_sc[0]; key = s_key[0];
+    __syncthreads();
+}
+
+// one read, by whichever kernel owns it (256 threads); false: more hits than `cap` keys -- not this route's
+static __device__ bool map_vote_one(const MapVoteArgs& A, int r, uint64_t* keys, long long cap, uint32_t* s_sc, uint64_t* s_key, int32_t* s_ext) {
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+    long long h0 = A.hit_off[A.mz_off[r]], h1 = A.hit_off[A.mz_off[r + 1]];
+    if (h0 < 0 || h1 > A.n_hits || h1 < h0) h1 = h0 = 0;
+    const long long n64 = h1 - h0;
+    if (n64 > cap) return false;
+    const int n = (int)n64;
+    int n_pow2 = 2;
+    while (n_pow2 < n) n_pow2 <<= 1;
+    for (int i = tid; i < n_pow2; i += nt) keys[i] = i < n ? A.hit_key[h0 + i] : ~0ull;
+    if (tid < 4) s_ext[tid] = (tid & 1) ? INT32_MIN : INT32_MAX;      // qa_min, qa_max, t_min, t_max
+    __syncthreads();
+    for (int k = 2; k <= n_pow2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (n_pow2 >> 1); t += nt) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const uint64_t a = keys[i], b = keys[l];
+                if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[l] = a; }
+            }
+            __syncthreads();
+        }
+    // first index at or behind `from` whose key is above v
+    auto upper = [&](uint64_t v, int from) { int lo = from, hi = n; while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] <= v) lo = mid + 1; else hi = mid; } return lo; };
+    auto score = [&](int i) { const uint64_t key = keys[i]; const int e = upper(key, i + 1); return (uint32_t)(upper(key + 1, e) - i); };      // (the run and the run of the next bin lie side by side)
+    hs::MapVote v;
+    {
+        uint32_t sc = 0; uint64_t key = 0;
+        for (int i = tid; i < n; i += nt) {
+            if (i && keys[i] == keys[i - 1]) continue;
+            const uint32_t s = score(i);
+            if (sc == 0 || hs::map_beats(s, keys[i], sc, key)) { sc = s; key = keys[i]; }
+        }
+        map_block_best(sc, key, s_sc, s_key);
+        v.best = sc; v.key = key;
+    }
+    if (v.best) {
+        uint32_t sc = 0; uint64_t key = 0;
+        for (int i = tid; i < n; i += nt) {
+            if ((i && keys[i] == keys[i - 1]) || !hs::map_second_allowed(keys[i], v.key)) continue;
+            const uint32_t s = score(i);
+            if (s > sc) { sc = s; key = keys[i]; }
+        }
+        map_block_best(sc, key, s_sc, s_key);
+        v.second = sc;
+        int qa_min = INT32_MAX, qa_max = INT32_MIN, t_min = INT32_MAX, t_max = INT32_MIN;
+        for (int i = tid; i < n; i += nt) {
+            if (!hs::map_in_best(A.hit_key[h0 + i], v.key)) continue;
+            const int qa = A.hit_qa[h0 + i], t = A.hit_t[h0 + i];
+            qa_min = min(qa_min, qa); qa_max = max(qa_max, qa); t_min = min(t_min, t); t_max = max(t_max, t);
+        }
+        atomicMin(&s_ext[0], qa_min); atomicMax(&s_ext[1], qa_max); atomicMin(&s_ext[2], t_min); atomicMax(&s_ext[3], t_max);
+        __syncthreads();
+        v.qa_min = s_ext[0]; v.qa_max = s_ext[1]; v.t_min = s_ext[2]; v.t_max = s_ext[3];
+    }
+    if (tid == 0) {
+        const int c = v.best ? hs::map_key_contig(v.key) : -1;
+        const int32_t Lc = c >= 0 && c < A.n_contigs ? (int32_t)(A.contig_off[c + 1] - A.contig_off[c]) : 0;
+        const int32_t Lr = (int32_t)(A.read_off[r + 1] - A.read_off[r]);
+        hs::map_interval(A.P, v, Lr, Lc, &A.contig[r], &A.strand[r], &A.qstart[r], &A.qend[r], &A.tstart[r], &A.tend[r]);
+        A.votes[r] = (int32_t)v.best; A.second[r] = (int32_t)v.second;
+    }
+    __syncthreads();
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_map_vote(MapVoteArgs A) {
+    __shared__ uint64_t s_keys[HS_MAP_LDS_KEYS];
+    __shared__ uint64_t s_key[256];
+    __shared__ uint32_t s_sc[256];
+    __shared__ int32_t s_ext[4];
+    const int r = (int)blockIdx.x;
+    if (r >= A.n_reads) return;
+    if (!map_vote_one(A, r, s_keys, HS_MAP_LDS_KEYS, s_sc, s_key, s_ext) && threadIdx.x == 0) {
+        const int at = atomicAdd(A.wide_count, 1);
+        if (at < A.n_reads) A.wide_list[at] = r;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_map_vote_wide(MapVoteArgs A, uint64_t* __restrict__ slabs, long long slab_keys) {
+    __shared__ uint64_t s_key[256];
+    __shared__ uint32_t s_sc[256];
+    __shared__ int32_t s_ext[4];
+    const int n = min(*A.wide_count, A.n_reads);
+    uint64_t* keys = slabs + (size_t)blockIdx.x * (size_t)slab_keys;
+    for (int i = (int)blockIdx.x; i < n; i += (int)gridDim.x) (void)map_vote_one(A, A.wide_list[i], keys, slab_keys, s_sc, s_key, s_ext);
+}
+
+}  // namespace hsdev

@@ -86,7 +86,8 @@ extern "C" int hs_call_variants_main(int argc, char** argv) {
         std::cout << "Usage: ./call_variants <gfa_file> <reads_file> <sam_file> <num_threads> <tmpDir> <error_rate_out> <amplicon> <DEBUG> <file_out> <vcfFile> <automatic_snp_threshold>\n";
         return 0;
     }
-    const std::string gfafile = argv[1], reads_file = argv[2], sam_file = argv[3];
+    const std::string gfafile = argv[1], reads_file = argv[2];
+    std::string sam_file = argv[3];
     int num_threads = 1, amplicon_i = 0, debug_i = 0;
     if (parse_int_arg(argv[4], num_threads) || parse_int_arg(argv[7], amplicon_i) || parse_int_arg(argv[8], debug_i)) {
         std::cout << "ERROR: could not parse the numeric arguments" << std::endl;
@@ -104,11 +105,26 @@ extern "C" int hs_call_variants_main(int argc, char** argv) {
     });
     g_pending_gro.on = false;
     std::string realigned_sam;
+    bool mapped_here = false;
+    if (const char* e = std::getenv("HS_MAP")) {
+        // HS_MAP=1: the alignment argument is not read. The reads are mapped on the device (minimizer seeds and a diagonal vote, hs_capi_map.inc)
+        // and the PAF that leaves goes the way HS_REALIGN=1 takes any PAF
+        if (e[0] == '1') {
+            sam_file = std::string(argv[5]) + "/hs_mapped.paf";
+            std::cout << " - Mapping the reads on the contigs on the device\n";
+            if (int rc = hs_map_files(gfafile.c_str(), reads_file.c_str(), sam_file.c_str(), num_threads, nullptr)) {
+                std::cout << "ERROR: " << hs_last_error() << " (" << rc << ")" << std::endl;
+                return EXIT_FAILURE;
+            }
+            mapped_here = true;
+            clk.lap("map the reads");
+        }
+    }
     if (has_suffix(sam_file, ".paf")) {
         // the reference refuses a .paf (call_variants.cpp:1256-1259) and so does this executable -- unless HS_REALIGN=1 asks for the
         // read segments to be aligned against their contig windows on the device (hs_realign.cpp): the SAM it makes is read instead
         const char* e = std::getenv("HS_REALIGN");
-        if (!(e && e[0] == '1')) {
+        if (!mapped_here && !(e && e[0] == '1')) {
             std::cout << "ERROR: please provide a .sam file as input for the alignments of the reads on the contigs." << std::endl;
             return EXIT_FAILURE;
         }

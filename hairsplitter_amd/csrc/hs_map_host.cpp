@@ -1,0 +1,193 @@
+// hs_map_host.cpp -- the device-free half of the read mapper: the rule of hs_map_host.h over a whole job, on the host. It is the yardstick the
+// device is held to by integer equality (tests/test_gpu_map.py through tests/harness/map_selftest.cpp) and the text of hs_map_text. No HIP.
+#include "hs_map_host.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <numeric>
+#include <thread>
+
+namespace hs {
+
+void map_minimizers(const uint8_t* seq, const int64_t* off, int32_t n_seqs, const hs_map_params& p, MapMinimizers& out) {
+    out.h.clear(); out.ps.clear(); out.seq.clear();
+    out.seq_off.assign((size_t)n_seqs + 1, 0);
+    std::vector<uint32_t> h, s;
+    std::vector<uint8_t> ok, named;
+    for (int32_t i = 0; i < n_seqs; ++i) {
+        const int64_t L = off[i + 1] - off[i], n = L - p.k + 1;
+        if (n >= 1) {
+            h.assign((size_t)n, 0); s.assign((size_t)n, 0); ok.assign((size_t)n, 0); named.assign((size_t)n, 0);
+            for (int64_t q = 0; q < n; ++q) ok[(size_t)q] = map_kmer(seq + off[i] + q, p.k, &h[(size_t)q], &s[(size_t)q]) ? 1 : 0;
+            const int64_t last = map_last_window(n, p.w);
+            for (int64_t j = 0; j <= last; ++j) {
+                int64_t arg = -1;
+                for (int64_t q = j; q < j + p.w && q < n; ++q)
+                    if (ok[(size_t)q] && (arg < 0 || h[(size_t)q] < h[(size_t)arg])) arg = q;      // (strict: the leftmost of equal hashes stays)
+                if (arg >= 0) named[(size_t)arg] = 1;
+            }
+            for (int64_t q = 0; q < n; ++q)
+                if (named[(size_t)q]) { out.h.push_back(h[(size_t)q]); out.ps.push_back(((uint32_t)q << 1) | s[(size_t)q]); out.seq.push_back(i); }
+        }
+        out.seq_off[(size_t)i + 1] = (int64_t)out.h.size();
+    }
+}
+
+int map_index_host(const uint8_t* contig_seq, const int64_t* contig_off, int32_t n_contigs, const hs_map_params& p, MapIndexHost& ix, std::string& err) {
+    if (!map_params_valid(p) || n_contigs < 0 || !contig_off) { err = "map index: parameters out of range"; return HS_EINVAL; }
+    ix.params = p; ix.n_contigs = n_contigs;
+    ix.contig_len.resize((size_t)n_contigs);
+    for (int32_t c = 0; c < n_contigs; ++c) {
+        ix.contig_len[(size_t)c] = contig_off[c + 1] - contig_off[c];
+        if (ix.contig_len[(size_t)c] < 0 || ix.contig_len[(size_t)c] > 0x7fffffff) { err = "map index: a contig of more than 2^31 bases"; return HS_EINVAL; }
+    }
+    MapMinimizers mz;
+    map_minimizers(contig_seq, contig_off, n_contigs, p, mz);
+    const size_t n = mz.h.size();
+    ix.bucket_bits = map_bucket_bits(p, (int64_t)n);
+    const uint32_t mask = (uint32_t)(((uint64_t)1 << ix.bucket_bits) - 1);
+    std::vector<size_t> order(n);
+    std::iota(order.begin(), order.end(), (size_t)0);
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {      // (stable: contig and t ascend inside equal (bucket, h))
+        const uint32_t ba = mz.h[a] & mask, bb = mz.h[b] & mask;
+        return ba != bb ? ba < bb : mz.h[a] < mz.h[b];
+    });
+    ix.bucket_off.assign(((size_t)1 << ix.bucket_bits) + 1, 0);
+    ix.e_h.resize(n); ix.e_ts.resize(n); ix.e_c.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t o = order[i];
+        ix.e_h[i] = mz.h[o]; ix.e_ts[i] = mz.ps[o]; ix.e_c[i] = mz.seq[o];
+        ix.bucket_off[(size_t)(mz.h[o] & mask) + 1]++;
+    }
+    for (size_t b = 0; b + 1 < ix.bucket_off.size(); ++b) ix.bucket_off[b + 1] += ix.bucket_off[b];
+    return HS_OK;
+}
+
+namespace {
+struct Hit { uint64_t key; int32_t qa, t; };
+
+void map_one_read(const MapIndexHost& ix, const uint8_t* seq, int64_t L, size_t r, MapResultHost& out, std::vector<Hit>& hits, std::vector<uint64_t>& keys) {
+    const hs_map_params& p = ix.params;
+    const int64_t off[2] = {0, L};
+    MapMinimizers mz;
+    map_minimizers(seq, off, 1, p, mz);
+    const uint32_t mask = (uint32_t)(((uint64_t)1 << ix.bucket_bits) - 1);
+    hits.clear();
+    int32_t n_skipped = 0;
+    for (size_t m = 0; m < mz.h.size(); ++m) {
+        const uint32_t h = mz.h[m];
+        const int64_t b0 = ix.bucket_off[h & mask], b1 = ix.bucket_off[(size_t)(h & mask) + 1];
+        int64_t occ = 0;
+        for (int64_t e = b0; e < b1; ++e) occ += ix.e_h[(size_t)e] == h;
+        if (occ > p.max_occ) { ++n_skipped; continue; }
+        for (int64_t e = b0; e < b1; ++e) {
+            if (ix.e_h[(size_t)e] != h) continue;
+            Hit x;
+            x.t = (int32_t)(ix.e_ts[(size_t)e] >> 1);
+            x.key = map_hit(ix.e_c[(size_t)e], x.t, ix.e_ts[(size_t)e] & 1u, (int32_t)(mz.ps[m] >> 1), mz.ps[m] & 1u, (int32_t)L, p, &x.qa);
+            hits.push_back(x);
+        }
+    }
+    keys.resize(hits.size());
+    for (size_t i = 0; i < hits.size(); ++i) keys[i] = hits[i].key;
+    std::sort(keys.begin(), keys.end());
+    MapVote v;
+    auto count = [&](uint64_t key) { auto rg = std::equal_range(keys.begin(), keys.end(), key); return (uint32_t)(rg.second - rg.first); };
+    for (size_t i = 0; i < keys.size(); ++i) {
+        if (i && keys[i] == keys[i - 1]) continue;
+        const uint32_t sc = count(keys[i]) + count(keys[i] + 1);
+        if (v.best == 0 || map_beats(sc, keys[i], v.best, v.key)) { v.best = sc; v.key = keys[i]; }
+    }
+    for (size_t i = 0; i < keys.size(); ++i) {
+        if ((i && keys[i] == keys[i - 1]) || !map_second_allowed(keys[i], v.key)) continue;
+        v.second = std::max(v.second, count(keys[i]) + count(keys[i] + 1));
+    }
+    bool first = true;
+    for (const Hit& x : hits) {
+        if (!map_in_best(x.key, v.key)) continue;
+        if (first) { v.qa_min = v.qa_max = x.qa; v.t_min = v.t_max = x.t; first = false; }
+        v.qa_min = std::min(v.qa_min, x.qa); v.qa_max = std::max(v.qa_max, x.qa); v.t_min = std::min(v.t_min, x.t); v.t_max = std::max(v.t_max, x.t);
+    }
+    const int32_t Lc = v.best ? (int32_t)ix.contig_len[(size_t)map_key_contig(v.key)] : 0;
+    map_interval(p, v, (int32_t)L, Lc, &out.contig[r], &out.strand[r], &out.qstart[r], &out.qend[r], &out.tstart[r], &out.tend[r]);
+    out.votes[r] = (int32_t)v.best; out.second[r] = (int32_t)v.second;
+    out.n_minimizers[r] = (int32_t)mz.h.size(); out.n_hits[r] = (int64_t)hits.size(); out.n_skipped[r] = n_skipped;
+}
+}  // namespace
+
+int map_reads_host(const MapIndexHost& ix, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapResultHost& out, std::string& err) {
+    if (n_reads < 0 || !read_off) { err = "map reads: bad arguments"; return HS_EINVAL; }
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (read_off[r + 1] < read_off[r] || read_off[r + 1] - read_off[r] > 0x7fffffff) { err = "map reads: a read of more than 2^31 bases"; return HS_EINVAL; }
+    const size_t n = (size_t)n_reads;
+    for (std::vector<int32_t>* v : {&out.contig, &out.qstart, &out.qend, &out.tstart, &out.tend, &out.votes, &out.second, &out.n_minimizers, &out.n_skipped}) v->assign(n, 0);
+    out.strand.assign(n, 0); out.n_hits.assign(n, 0);
+    n_threads = std::max(1, std::min(n_threads, std::max(1, n_reads)));
+    auto work = [&](int t) {
+        std::vector<Hit> hits;
+        std::vector<uint64_t> keys;
+        for (size_t r = (size_t)t; r < n; r += (size_t)n_threads) map_one_read(ix, read_seq + read_off[r], read_off[r + 1] - read_off[r], r, out, hits, keys);
+    };
+    if (n_threads == 1) { work(0); return HS_OK; }
+    std::vector<std::thread> th;
+    for (int t = 0; t < n_threads; ++t) th.emplace_back(work, t);
+    for (std::thread& t : th) t.join();
+    return HS_OK;
+}
+
+std::string map_text(const hs_map_result* r, const char* const* read_names, const int64_t* read_len, const char* const* contig_names, const int64_t* contig_len) {
+    std::string s;
+    for (int32_t i = 0; i < r->n_reads; ++i) {
+        const int32_t c = r->contig[i];
+        if (c < 0) continue;
+        s += read_names && read_names[i] ? std::string(read_names[i]) : "r" + std::to_string(i);
+        s += '\t'; s += std::to_string(read_len[i]);
+        s += '\t'; s += std::to_string(r->qstart[i]);
+        s += '\t'; s += std::to_string(r->qend[i]);
+        s += r->strand[i] ? "\t+\t" : "\t-\t";
+        s += contig_names && contig_names[c] ? std::string(contig_names[c]) : "c" + std::to_string(c);
+        s += '\t'; s += std::to_string(contig_len[c]);
+        s += '\t'; s += std::to_string(r->tstart[i]);
+        s += '\t'; s += std::to_string(r->tend[i]);
+        s += '\t'; s += std::to_string(r->votes[i]);
+        s += '\t'; s += std::to_string(r->tend[i] - r->tstart[i]);
+        s += "\t255\ts1:i:"; s += std::to_string(r->votes[i]);
+        s += "\ts2:i:"; s += std::to_string(r->second[i]);
+        s += '\n';
+    }
+    return s;
+}
+
+}  // namespace hs
+
+extern "C" {
+
+hs_map_params hs_map_params_default(void) {
+    hs_map_params p;
+    p.k = 15; p.w = 10; p.max_occ = 64; p.band_log2 = 9; p.min_votes = 3; p.extend = 1; p.bucket_bits = -1;
+    return p;
+}
+void hs_map_result_destroy(hs_map_result* r) {
+    if (!r) return;
+    void* p[] = {r->contig, r->strand, r->qstart, r->qend, r->tstart, r->tend, r->votes, r->second, r->n_minimizers, r->n_skipped, r->n_hits};
+    for (void* q : p) std::free(q);
+    std::free(r);
+}
+int hs_map_text(const hs_map_result* result, const char* const* read_names, const int64_t* h_read_off, const char* const* contig_names, const int64_t* h_contig_off,
+                int32_t n_contigs, char** text) {
+    if (!result || !h_read_off || !h_contig_off || !text || n_contigs < 0) return HS_EINVAL;
+    std::vector<int64_t> rl((size_t)result->n_reads), cl((size_t)n_contigs);
+    for (int32_t i = 0; i < result->n_reads; ++i) {
+        rl[(size_t)i] = h_read_off[i + 1] - h_read_off[i];
+        if (result->contig[i] >= n_contigs) return HS_EINVAL;
+    }
+    for (int32_t c = 0; c < n_contigs; ++c) cl[(size_t)c] = h_contig_off[c + 1] - h_contig_off[c];
+    const std::string s = hs::map_text(result, read_names, rl.data(), contig_names, cl.data());
+    *text = (char*)std::malloc(s.size() + 1);
+    if (!*text) return HS_EINVAL;
+    std::memcpy(*text, s.c_str(), s.size() + 1);
+    return HS_OK;
+}
+
+}  // extern "C"

@@ -916,6 +916,63 @@ int hs_gfa_to_fasta(const char* gfa_in, const char* fasta_out /* NULL or "-": st
 int hs_cut_gfa_main(int argc, char** argv);
 int hs_gfa2fa_main(int argc, char** argv);
 
+/* ------------------------------------------------------------------------------------------------
+ * The step in front of the intervals: which contig window every read came from, on the device. Minimizer seeds
+ * against a resident index of the contigs and a vote over diagonal bins; no chaining and no base-level alignment -- A1 places the
+ * read inside the window (hs_realign_intervals). The reference has no counterpart (it shells out to minimap2); the rule is this
+ * library's own, stated once in csrc/hs_map_host.h for host and device. At most one interval per read (primary only).
+ * The defaults are minimap2's ONT k and w plus placeholders; they are not tuned.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hs_map_params {
+    int32_t k;             /* 5..16: bases of a k-mer (16: all 32 bits of the word in use); default 15 */
+    int32_t w;             /* 1..32: k-mers of a minimizer window; default 10 */
+    int32_t max_occ;       /* >= 1: a read minimizer whose hash has more index entries than this is not looked up; default 64 */
+    int32_t band_log2;     /* 0..30: a diagonal bin is 2^band_log2 bases wide; default 9 */
+    int32_t min_votes;     /* >= 1: hits in the best two adjacent bins for the read to count as mapped; default 3 */
+    int32_t extend;        /* 0 | 1: stretch the seeds' interval to the whole read, clipped at the contig's ends; default 1 */
+    int32_t bucket_bits;   /* 0..26: the index has 2^bucket_bits buckets (low bits of the hash); -1 (default): from the number of entries */
+} hs_map_params;
+hs_map_params hs_map_params_default(void);
+typedef struct hs_map_index hs_map_index;
+typedef struct hs_map_result {
+    int32_t n_reads;
+    /* per read; an unmapped read has contig -1 and zeros in the five fields behind it */
+    int32_t* contig;
+    uint8_t* strand;       /* 1 forward, 0 reverse, as hs_realign_intervals takes it */
+    int32_t *qstart, *qend, *tstart, *tend;   /* half-open, 0-based; q on the read as given */
+    int32_t *votes, *second;   /* score of the best candidate and of the best one elsewhere (0: none) */
+    int32_t *n_minimizers, *n_skipped;   /* the read's minimizers; those not looked up (max_occ) */
+    int64_t* n_hits;
+    /* per call */
+    int64_t n_wide;        /* reads with more hits than the LDS route holds, voted in global scratch */
+    int64_t total_minimizers, total_hits;
+    double t_minimizers_ms, t_hits_ms, t_vote_ms;   /* HIP events around the three groups of launches */
+} hs_map_result;
+/* codes 0..3, one per byte; contig c = h_contig_seq[h_contig_off[c] .. h_contig_off[c + 1]). params NULL: the defaults. The index stays
+ * on the device until it is destroyed and serves any number of calls. */
+int hs_map_index_create(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const hs_map_params* params, hs_map_index** index);
+void hs_map_index_destroy(hs_map_index* index);
+/* the index as the device holds it, for inspection: n_entries and bucket_bits; with non-NULL arrays also bucket_off [2^bucket_bits + 1] and the
+ * entries' hash, contig and t << 1 | strand bit [n_entries]. The order inside a bucket is not defined. */
+int hs_map_index_download(const hs_map_index* index, int64_t* n_entries, int32_t* bucket_bits, int64_t* bucket_off, uint32_t* e_hash, int32_t* e_contig, uint32_t* e_ts);
+int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, hs_map_result** result);
+void hs_map_result_destroy(hs_map_result* result);
+/* hits of a read that the vote sorts in LDS; a read with more goes through global scratch */
+int32_t hs_map_lds_capacity(void);
+/* hs_map_reads, then hs_realign_intervals on the mapped reads (interval i = the i-th mapped read, ascending): the resident batch, the records
+ * and the map result. records / result may be NULL. pad as hs_realign_intervals takes it. */
+int hs_map_to_batch(const hs_map_index* index, const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq,
+                    const int64_t* h_read_off, int32_t n_reads, int32_t pad, hs_cv_batch** batch, hs_realign_records** records, hs_map_result** result);
+/* PAF lines of the mapped reads: column 10 = votes, 11 = tend - tstart, 12 = 255, tags s1:i:votes s2:i:second. Names may be NULL (r<i>, c<i>).
+ * *text is released with hs_free_host. */
+int hs_map_text(const hs_map_result* result, const char* const* read_names, const int64_t* h_read_off, const char* const* contig_names,
+                const int64_t* h_contig_off, int32_t n_contigs, char** text);
+/* the same from a job's files: the assembly (GFA S lines, or FASTA) and the reads -> the PAF lines, written to out_paf. n_threads < 1: all cores
+ * (for loading). hs_map_main: argv = <gfa|fasta> <reads> <out.paf> [threads], the tool bin/hs_map. HS_call_variants with HS_MAP=1 does not read its
+ * alignment argument: it maps the reads this way into <tmpDir>/hs_mapped.paf and takes that file the way HS_REALIGN=1 takes a PAF. */
+int hs_map_files(const char* gfa, const char* reads, const char* out_paf, int32_t n_threads, const hs_map_params* params);
+int hs_map_main(int argc, char** argv);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,131 @@
+"""The read mapper (hs_map_reads, hs_map_to_batch; hs_kernels_map.hip) on a job of a bench configuration, held against the truth alignments of synth.py:
+  1. the kernels' own times (HIP events around the minimizer, hit and vote launches), the algorithmic bytes each group moves and their share of 8 TB/s:
+     minimizers 1 B per read base + 12 B per minimizer written; hits 8 B per minimizer read + 16 B per hit written and as much read back by the vote
+     with 44 B per read written (the index's buckets, read at random, are not counted);
+  2. reads per second of hs_map_reads and of hs_map_to_batch, and the share of the latter that A1 and the CIGAR words take;
+  3. the host half of the same rule (tests/harness/map_selftest, 16 threads) on a sample of the reads, the only yardstick without another mapper;
+  4. against the truth: the share of reads mapped, the share whose window [tstart - 100, tend + 100) holds the true span on the true contig and
+     strand, the share of records whose (pos, CIGAR) equal those of hs_realign_intervals on the truth intervals;
+  5. stages 3 and 4 on the mapped batch and on the truth-SAM batch: SNPs of each, SNP positions in common, the error rates; windows and groups of
+     each, and the windows both have whose label arrays are equal element by element (a report, no assertion).
+Usage: python tools/map_bench.py [config=C4] [contigs=16] [repeats=5] [host_sample=2000]      (prints one JSON line)"""
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    cfg = sys.argv[1] if len(sys.argv) > 1 else "C4"
+    n = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+    reps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+    sample = int(sys.argv[4]) if len(sys.argv) > 4 else 2000
+    import numpy as np
+    from hairsplitter_amd import synth
+    contigs, _ = synth.generate_job(cfg, list(range(n)), workers=min(16, os.cpu_count() or 1))      # before the GPU is touched (forks)
+    import map_cases as mc
+    from hairsplitter_amd import api
+    import __graft_entry__ as ge
+    api.require_gpu()
+    flat = api.FlatBatch(contigs)
+    R, bases = flat.n_reads, int(flat.read_off[-1])
+    reads = (flat.read_seq, flat.read_off)
+    med = statistics.median
+    t0 = time.perf_counter()
+    ix = api.map_index((flat.contig_seq, flat.contig_off))
+    t_index = (time.perf_counter() - t0) * 1e3
+    api.map_reads(ix, reads)      # warm-up: pools, code object
+    t_map, k_mz, k_hits, k_vote = [], [], [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        res = api.map_reads(ix, reads)
+        t_map.append(time.perf_counter() - t0)
+        k_mz.append(res["t_minimizers_ms"]); k_hits.append(res["t_hits_ms"]); k_vote.append(res["t_vote_ms"])
+    t_batch, a1_share = [], []
+    for _ in range(max(1, reps // 2)):
+        t0 = time.perf_counter()
+        batch, rec, res_b = api.map_to_batch(ix, reads)
+        dt = time.perf_counter() - t0
+        t_batch.append(dt)
+        a1_share.append((rec["t_align_ms"] + rec["t_cigar_ms"] + rec["t_cut_ms"]) / (dt * 1e3))
+        if _ < max(1, reps // 2) - 1:
+            batch.close()
+    M, H = res["total_minimizers"], res["total_hits"]
+
+    def group(ms, nbytes):
+        return {"ms": round(ms, 4), "bytes": int(nbytes), "GB_per_s": round(nbytes / (ms * 1e6), 1) if ms > 0 else None,
+                "share_of_8_TB_per_s": round(nbytes / (ms * 1e6) / 8000, 4) if ms > 0 else None}
+    kernels = {"minimizers": group(med(k_mz), bases + 12 * M), "hits": group(med(k_hits), 8 * M + 16 * H), "vote": group(med(k_vote), 16 * H + 44 * R)}
+    # ---- the truth ----
+    truth_iv, base = [], 0
+    for ci, c in enumerate(contigs):
+        for a in c.alns:
+            ops, lens = a.cigar & 0xF, (a.cigar >> 4).astype(np.int64)
+            span = int(lens[(ops == 0) | (ops == 2) | (ops == 7) | (ops == 8)].sum())
+            truth_iv.append((base + a.read, ci, 1 if a.strand else 0, 0, len(c.reads[a.read]), a.pos, a.pos + span))
+        base += len(c.reads)
+    tv = np.array(truth_iv, np.int64)
+    order = np.argsort(tv[:, 0], kind="stable")
+    tv = tv[order]
+    assert np.array_equal(tv[:, 0], np.arange(R))      # one truth alignment per read
+    mapped = res["contig"] >= 0
+    holds = mapped & (res["contig"] == tv[:, 1]) & (res["strand"] == tv[:, 2]) & (res["tstart"] - 100 <= tv[:, 5]) & (tv[:, 6] <= res["tend"] + 100)
+    rec_t, _ = api.realign_intervals(flat, tv, want_batch=False)
+
+    def by_read(r):
+        return {int(rd): (int(r["rec_pos"][k]), r["cigar"][r["rec_cig_off"][k]:r["rec_cig_off"][k + 1]].tobytes()) for k, rd in enumerate(r["rec_read"])}
+    a, b = by_read(rec), by_read(rec_t)
+    same_rec = sum(1 for rd, v in a.items() if b.get(rd) == v)
+    # ---- the host half of the rule on a sample ----
+    pick = np.linspace(0, R - 1, min(sample, R)).astype(np.int64)
+    sub = [flat.read_seq[flat.read_off[i]:flat.read_off[i + 1]] for i in pick]
+    cs = [flat.contig_seq[flat.contig_off[c]:flat.contig_off[c + 1]] for c in range(flat.n_contigs)]
+    with tempfile.NamedTemporaryFile("w", suffix=".txt") as f:
+        mc.write_job(f.name, mc.params(), cs, sub, threads=16)
+        import subprocess
+        t0 = time.perf_counter()
+        out = subprocess.run([ge.paths()["map_selftest"], f.name], stdout=subprocess.PIPE, check=True).stdout.decode()
+        t_host = time.perf_counter() - t0
+    host_rows = {int(t[1]): [int(x) for x in t[2:8]] for t in (l.split() for l in out.splitlines()) if t[0] == "R"}
+    host_same = all(host_rows[k] == [int(res[f][i]) for f in ("contig", "strand", "qstart", "qend", "tstart", "tend")] for k, i in enumerate(pick))
+    # ---- stages 3 and 4 on both batches ----
+    truth_batch = api.CvBatch(flat)
+    ra, rb = batch.run(), truth_batch.run()
+    (_, s4a), (_, s4b) = batch.run_pipeline(), truth_batch.run_pipeline()
+    batch.close(); truth_batch.close(); ix.close()
+
+    def windows(sr):
+        out = {}
+        for c in range(len(sr["win_off"]) - 1):
+            for w in range(int(sr["win_off"][c]), int(sr["win_off"][c + 1])):
+                out[(c, int(sr["win_start"][w]), int(sr["win_end"][w]))] = sr["labels"][int(sr["label_off"][w]):int(sr["label_off"][w + 1])]
+        return out
+    wa, wb = windows(s4a), windows(s4b)
+    n_groups = lambda ws: int(sum(len(set(v[v >= 0].tolist())) for v in ws.values()))
+    both = [k for k in wa if k in wb]
+
+    def snps(r):
+        return set((int(c), int(p)) for c in range(len(r["snp_off"]) - 1) for p in r["snp_pos"][r["snp_off"][c]:r["snp_off"][c + 1]])
+    sa, sb = snps(ra), snps(rb)
+    print(json.dumps({
+        "config": cfg, "contigs": n, "reads": R, "read_bases": bases, "contig_bases": int(flat.contig_off[-1]), "index_create_ms": round(t_index, 2),
+        "minimizers": M, "hits": H, "reads_through_scratch_route": res["n_wide"], "kernels": kernels,
+        "map_reads": {"ms": round(med(t_map) * 1e3, 2), "reads_per_s": round(R / med(t_map)), "Mbases_per_s": round(bases / med(t_map) / 1e6, 1)},
+        "map_to_batch": {"ms": round(med(t_batch) * 1e3, 2), "reads_per_s": round(R / med(t_batch)), "share_of_A1_cut_and_cigar": round(med(a1_share), 3)},
+        "host_rule_16_threads": {"reads": len(pick), "s_with_index_and_text_io": round(t_host, 3), "equals_device": bool(host_same)},
+        "truth": {"share_mapped": round(float(mapped.mean()), 5), "share_window_holds_true_span": round(float(holds.mean()), 5),
+                  "share_records_equal_truth_interval_records": round(same_rec / max(len(b), 1), 5), "records": len(a), "dropped": int(rec["n_dropped"])},
+        "stage3": {"snps_mapped_batch": len(sa), "snps_truth_batch": len(sb), "snps_in_common": len(sa & sb),
+                   "error_rate_mapped": float(ra["error_rate"]), "error_rate_truth": float(rb["error_rate"])},
+        "stage4": {"windows_mapped_batch": len(wa), "windows_truth_batch": len(wb), "windows_in_common": len(both), "groups_mapped_batch": n_groups(wa),
+                   "groups_truth_batch": n_groups(wb), "common_windows_with_equal_label_arrays": int(sum(np.array_equal(wa[k], wb[k]) for k in both))}}))
+
+
+if __name__ == "__main__":
+    main()
