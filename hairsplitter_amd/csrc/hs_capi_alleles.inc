@@ -160,14 +160,6 @@ struct TableCall {
     const int64_t* h_n_rows = nullptr; const int64_t* h_n_ctr = nullptr;      // the two totals where the first shipment leaves them
 
     char* work() const { return (char*)d_work.p; }
-    template <class Launch> int timed(EventPair& ev, int64_t bytes, Launch launch) {
-        HS_HIP(ev_rec(ev.a, st));
-        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
-        if (int rc = launch()) return rc;
-        if (int rc = kc.end(bytes, st)) return rc;
-        HS_HIP(ev_rec(ev.b, st));
-        return HS_OK;
-    }
 
     // uploads, the plan(s), and their shipment: the plan comes to the host in one piece (the table is assembled from it) with the totals that size the rest
     int queue_plan(const int64_t* d_col_off, const int32_t* d_col_idx, const uint8_t* d_col_code, const int32_t* d_labels) {
@@ -187,9 +179,9 @@ struct TableCall {
         if (int rc = ev_plan.init()) return rc;
         if (int rc = ev_cells.init()) return rc;
         if (recruit) { if (int rc = ev_rplan.init()) return rc; if (int rc = ev_rrows.init()) return rc; }
-        if (int rc = timed(ev_plan, 4 * n_labels + 12 * (int64_t)S, [&] { return allele_plan_launch(in, work(), rw.a, st); })) return rc;
+        if (int rc = timed_launch(kc, ev_plan, st, 4 * n_labels + 12 * (int64_t)S, [&] { return allele_plan_launch(in, work(), rw.a, st); })) return rc;
         // (the rows' flags and the two scans over them: queued with the plan, counted in the plan's wait)
-        if (recruit) { if (int rc = timed(ev_rplan, 4 * h.n_entries + 40 * n_labels, [&] { return recruit_plan_launch(in, work(), rw, *recruit, st); })) return rc; }
+        if (recruit) { if (int rc = timed_launch(kc, ev_rplan, st, 4 * h.n_entries + 40 * n_labels, [&] { return recruit_plan_launch(in, work(), rw, *recruit, st); })) return rc; }
         if (int rc = h_plan.alloc(at.plan_size)) return rc;
         char* hp = (char*)h_plan.p;
         Shipment sh;
@@ -222,9 +214,9 @@ struct TableCall {
     // the cells, counters and rows behind them, and their shipment
     int queue_cells() {
         hs_allele_cell* cells = d_cells.as<hs_allele_cell>();
-        if (int rc = timed(ev_cells, 5 * h.n_entries + (int64_t)sizeof(hs_allele_cell) * n_cells, [&] { return allele_cells_launch(in, work(), rw.a, cells, n_cells, st); })) return rc;
+        if (int rc = timed_launch(kc, ev_cells, st, 5 * h.n_entries + (int64_t)sizeof(hs_allele_cell) * n_cells, [&] { return allele_cells_launch(in, work(), rw.a, cells, n_cells, st); })) return rc;
         if (recruit) {
-            if (int rc = timed(ev_rrows, 5 * h.n_entries + 12 * n_ctr + 40 * n_rows + 12 * n_labels, [&] {
+            if (int rc = timed_launch(kc, ev_rrows, st, 5 * h.n_entries + 12 * n_ctr + 40 * n_rows + 12 * n_labels, [&] {
                     return recruit_rows_launch(in, work(), rw, *recruit, cells, n_cells, d_counters.as<uint32_t>(), n_ctr, d_rows.as<hs_recruit_row>(), n_rows, st); })) return rc;
             if (int rc = h_rows.alloc(at.rows_size)) return rc;
         }

@@ -1,6 +1,7 @@
 // hs_capi_map.inc -- part of hs_capi.hip: the read mapper (include/hairsplitter_hip.h: hs_map_index_create, hs_map_reads, hs_map_to_batch). Kernels
-// in hs_kernels_map.hip, the rule and the host half in hs_map_host.h / hs_map_host.cpp. An index call waits once (the number of minimizers sizes
-// the entries), a map call twice (the minimizers, then the hits: each total sizes what follows). Launches are accounted under HS_K_OTHER.
+// in hs_kernels_map.hip, the rule and the host half in hs_map_host.h / hs_map_host.cpp. An index call waits twice (the number of minimizers, which
+// sizes the entries; the end), a map call three times (the minimizers, then the hits -- each total sizes what follows --, then the records: one
+// block, one shipment). Sequences go up by the runtime's upload_pageable. Launches are accounted under HS_K_OTHER.
 struct hs_map_index {
     hs_map_params params{};
     int32_t n_contigs = 0, bucket_bits = 0;
@@ -11,11 +12,8 @@ struct hs_map_index {
 
 namespace {
 
-static int map_upload(DBuf& d, const void* src, size_t bytes) {
-    if (int rc = d.alloc(bytes + 16)) return rc;
-    if (bytes) HS_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-    return HS_OK;
-}
+// zero bytes behind every array a call uploads: a load a little past an end finds zeros, not a neighbour's block
+static const size_t MAP_SLACK = 16;
 
 // offsets of a job's sequences: ascending from 0, every sequence below 2^31 bases, the whole below 2^38
 static int map_check_offsets(const int64_t* off, int32_t n, const char* what) {
@@ -52,11 +50,23 @@ struct MapMinimizersDev {
     }
 };
 
-template <class T> static T* map_download(const DBuf& d, size_t n, hipStream_t st, int* rc) {
-    T* p = (T*)std::calloc(std::max<size_t>(1, n), sizeof(T));
-    if (!p) { set_error("hs_map_reads: out of memory"); *rc = HS_EINVAL; return nullptr; }
-    if (n && *rc == HS_OK) *rc = d2h_pinned(p, d.p, n * sizeof(T), st);
-    return p;
+// The parts of a map call's output block: the per-read records under the names hs_map_result gives them, then what a call clears -- n_skipped,
+// the wide route's counter, the word of the largest read -- side by side (one clearing). Up to `shipped` the block goes to the host in one
+// shipment and lands there at the same offsets; behind it lies the wide route's list [R].
+struct MapWork {
+    int64_t contig, strand, qstart, qend, tstart, tend, votes, second, n_minimizers, n_hits, n_skipped, wide_count, max_hits, shipped, wide_list, total_bytes;
+};
+static MapWork map_work(int32_t n_reads) {
+    const int64_t R = n_reads;
+    MapWork m;
+    WorkParts p;
+    m.contig = p.take(R * 4); m.strand = p.take(R); m.qstart = p.take(R * 4); m.qend = p.take(R * 4); m.tstart = p.take(R * 4); m.tend = p.take(R * 4);
+    m.votes = p.take(R * 4); m.second = p.take(R * 4); m.n_minimizers = p.take(R * 4); m.n_hits = p.take(R * 8);
+    m.n_skipped = p.take(R * 4); m.wide_count = p.take(4); m.max_hits = p.take(16);
+    m.shipped = p.o;
+    m.wide_list = p.take(R * 4);
+    m.total_bytes = p.o;
+    return m;
 }
 
 }  // namespace
@@ -82,13 +92,16 @@ int hs_map_index_create(const uint8_t* h_contig_seq, const int64_t* h_contig_off
         ix->contig_off.assign(h_contig_off, h_contig_off + n_contigs + 1);
         const hipStream_t st = nullptr;
         KernelClock kc;
+        EventPair untimed;      // (an index reports no kernel times of its own: the KernelClock's accounting alone)
         DBuf d_seq, d_cnt, d_scan;
-        if (int rc = map_upload(d_seq, h_contig_seq, (size_t)total)) return rc;
-        if (int rc = map_upload(ix->d_contig_off, h_contig_off, ((size_t)n_contigs + 1) * 8)) return rc;
+        if (int rc = upload_pageable(d_seq, h_contig_seq, (size_t)total, 0, MAP_SLACK)) return rc;
+        if (int rc = upload_pageable(ix->d_contig_off, h_contig_off, ((size_t)n_contigs + 1) * 8, 0, MAP_SLACK)) return rc;
         MapMinimizersDev mz;
-        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
-        if (int rc = mz.run(d_seq.as<uint8_t>(), ix->d_contig_off.as<int64_t>(), n_contigs, total, prm, st)) return rc;
-        if (int rc = kc.end(total + 12 * mz.n, st)) return rc;
+        int64_t mz_bytes = total;
+        if (int rc = timed_launch(kc, untimed, st, mz_bytes, [&] {
+                const int rc = mz.run(d_seq.as<uint8_t>(), ix->d_contig_off.as<int64_t>(), n_contigs, total, prm, st);
+                mz_bytes += 12 * mz.n;
+                return rc; })) return rc;
         const int64_t n = ix->n_entries = mz.n;
         if (n > 0x7fffffff - HS_SCAN_TILE) { set_error("hs_map_index_create: more than 2^31 contig minimizers"); return HS_EINVAL; }
         ix->bucket_bits = hs::map_bucket_bits(prm, n);
@@ -96,19 +109,17 @@ int hs_map_index_create(const uint8_t* h_contig_seq, const int64_t* h_contig_off
         const uint32_t mask = (uint32_t)(n_buckets - 1);
         if (int rc = d_cnt.alloc((size_t)n_buckets * 4)) return rc;
         if (int rc = ix->d_bucket_off.alloc(((size_t)n_buckets + 1) * 8)) return rc;
-        if (int rc = ix->d_e_h.alloc((size_t)std::max<int64_t>(n, 1) * 4)) return rc;
-        if (int rc = ix->d_e_c.alloc((size_t)std::max<int64_t>(n, 1) * 4)) return rc;
-        if (int rc = ix->d_e_ts.alloc((size_t)std::max<int64_t>(n, 1) * 4)) return rc;
-        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
-        HS_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)n_buckets * 4, st));
-        const unsigned grid = (unsigned)((n + 255) / 256);
-        if (n > 0) hipLaunchKernelGGL(hsdev::k_map_bucket_count, dim3(grid), dim3(256), 0, st, mz.h.as<uint32_t>(), (long long)n, mask, d_cnt.as<int32_t>());
-        if (int rc = exclusive_scan_launch(d_cnt.as<int32_t>(), (int)n_buckets, ix->d_bucket_off.as<int64_t>(), d_scan, st)) return rc;
-        HS_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)n_buckets * 4, st));
-        if (n > 0) hipLaunchKernelGGL(hsdev::k_map_bucket_fill, dim3(grid), dim3(256), 0, st, mz.h.as<uint32_t>(), mz.ps.as<uint32_t>(), mz.seq.as<int32_t>(), (long long)n, mask,
-                                      ix->d_bucket_off.as<int64_t>(), d_cnt.as<int32_t>(), ix->d_e_h.as<uint32_t>(), ix->d_e_c.as<int32_t>(), ix->d_e_ts.as<uint32_t>());
-        HS_HIP(hipGetLastError());
-        if (int rc = kc.end(24 * n + 16 * n_buckets, st)) return rc;
+        for (DBuf* b : {&ix->d_e_h, &ix->d_e_c, &ix->d_e_ts}) if (int rc = b->alloc((size_t)std::max<int64_t>(n, 1) * 4)) return rc;
+        if (int rc = timed_launch(kc, untimed, st, 24 * n + 16 * n_buckets, [&]() -> int {
+                HS_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)n_buckets * 4, st));
+                const unsigned grid = (unsigned)((n + 255) / 256);
+                if (n > 0) hipLaunchKernelGGL(hsdev::k_map_bucket_count, dim3(grid), dim3(256), 0, st, mz.h.as<uint32_t>(), (long long)n, mask, d_cnt.as<int32_t>());
+                if (int rc = exclusive_scan_launch(d_cnt.as<int32_t>(), (int)n_buckets, ix->d_bucket_off.as<int64_t>(), d_scan, st)) return rc;
+                HS_HIP(hipMemsetAsync(d_cnt.p, 0, (size_t)n_buckets * 4, st));
+                if (n > 0) hipLaunchKernelGGL(hsdev::k_map_bucket_fill, dim3(grid), dim3(256), 0, st, mz.h.as<uint32_t>(), mz.ps.as<uint32_t>(), mz.seq.as<int32_t>(), (long long)n, mask,
+                                              ix->d_bucket_off.as<int64_t>(), d_cnt.as<int32_t>(), ix->d_e_h.as<uint32_t>(), ix->d_e_c.as<int32_t>(), ix->d_e_ts.as<uint32_t>());
+                HS_HIP(hipGetLastError());
+                return HS_OK; })) return rc;
         if (int rc = stream_wait(st)) return rc;      // (the scratch goes back to the pool with this scope)
         kc.flush();
         *index = ix.release();
@@ -144,93 +155,87 @@ int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int
         KernelClock kc;
         EventPair ev_mz, ev_hits, ev_vote;
         for (EventPair* e : {&ev_mz, &ev_hits, &ev_vote}) if (int rc = e->init()) return rc;
-        DBuf d_seq, d_off, d_mz_off, d_cnt, d_hit_off, d_scan, d_max, d_key, d_qa, d_t, d_wide, d_slabs;
-        DBuf d_contig, d_strand, d_qs, d_qe, d_ts, d_te, d_votes, d_second, d_nmz, d_nskip, d_nhits;
-        if (int rc = map_upload(d_seq, h_read_seq, (size_t)total)) return rc;
-        if (int rc = map_upload(d_off, h_read_off, (R + 1) * 8)) return rc;
-        // ---- minimizers and every read's range of them ----
+        DBuf d_seq, d_off, d_mz_off, d_cnt, d_hit_off, d_scan, d_key, d_qa, d_t, d_slabs, d_out;
+        if (int rc = upload_pageable(d_seq, h_read_seq, (size_t)total, 0, MAP_SLACK)) return rc;
+        if (int rc = upload_pageable(d_off, h_read_off, (R + 1) * 8, 0, MAP_SLACK)) return rc;
+        // ---- minimizers and every read's range of them (one wait: their total) ----
         MapMinimizersDev mz;
-        HS_HIP(ev_rec(ev_mz.a, st));
-        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
-        if (int rc = mz.run(d_seq.as<uint8_t>(), d_off.as<int64_t>(), n_reads, total, prm, st)) return rc;
+        int64_t mz_bytes = total;
+        if (int rc = timed_launch(kc, ev_mz, st, mz_bytes, [&]() -> int {
+                if (int rc = mz.run(d_seq.as<uint8_t>(), d_off.as<int64_t>(), n_reads, total, prm, st)) return rc;
+                mz_bytes += 12 * mz.n;
+                if (mz.n > 0x7fffffff - HS_SCAN_TILE) { set_error("hs_map_reads: more than 2^31 read minimizers in one call: map the reads in several calls"); return HS_EINVAL; }
+                if (int rc = d_mz_off.alloc((R + 1) * 8)) return rc;
+                hipLaunchKernelGGL(hsdev::k_map_seq_ranges, dim3((unsigned)(R / 256 + 1)), dim3(256), 0, st, mz.seq.as<int32_t>(), (long long)mz.n, n_reads, d_mz_off.as<int64_t>());
+                HS_HIP(hipGetLastError());
+                return HS_OK; })) return rc;
         const int64_t M = mz.n;
-        if (M > 0x7fffffff - HS_SCAN_TILE) { set_error("hs_map_reads: more than 2^31 read minimizers in one call: map the reads in several calls"); return HS_EINVAL; }
-        if (int rc = d_mz_off.alloc((R + 1) * 8)) return rc;
-        hipLaunchKernelGGL(hsdev::k_map_seq_ranges, dim3((unsigned)(R / 256 + 1)), dim3(256), 0, st, mz.seq.as<int32_t>(), (long long)M, n_reads, d_mz_off.as<int64_t>());
-        HS_HIP(hipGetLastError());
-        if (int rc = kc.end(total + 12 * M, st)) return rc;
-        HS_HIP(ev_rec(ev_mz.b, st));
-        // ---- occ of every minimizer, the hits' offsets, (one wait: their total and the most a read has) ----
-        for (DBuf* b : {&d_contig, &d_qs, &d_qe, &d_ts, &d_te, &d_votes, &d_second, &d_nmz, &d_nskip}) if (int rc = b->alloc(std::max<size_t>(R, 1) * 4)) return rc;
-        if (int rc = d_strand.alloc(std::max<size_t>(R, 1))) return rc;
-        if (int rc = d_nhits.alloc(std::max<size_t>(R, 1) * 8)) return rc;
+        // ---- occ of every minimizer, the hits' offsets, (one wait: their total and the most a read has), the hits ----
+        const MapWork w = map_work(n_reads);
+        if (int rc = d_out.alloc((size_t)w.total_bytes)) return rc;
+        char* out = (char*)d_out.p;
         if (int rc = d_cnt.alloc((size_t)std::max<int64_t>(M, 1) * 4)) return rc;
         if (int rc = d_hit_off.alloc(((size_t)M + 1) * 8)) return rc;
-        if (int rc = d_max.alloc(16)) return rc;
-        if (int rc = d_wide.alloc((R + 1) * 4)) return rc;      // the list, and its count behind it
         hsdev::MapIndexDev X{index->d_bucket_off.as<int64_t>(), index->d_e_h.as<uint32_t>(), index->d_e_c.as<int32_t>(), index->d_e_ts.as<uint32_t>(),
                              (uint32_t)(((int64_t)1 << index->bucket_bits) - 1), (long long)index->n_entries, index->d_contig_off.as<int64_t>(), index->n_contigs};
-        HS_HIP(ev_rec(ev_hits.a, st));
-        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
-        HS_HIP(hipMemsetAsync(d_nskip.p, 0, std::max<size_t>(R, 1) * 4, st));
-        HS_HIP(hipMemsetAsync(d_max.p, 0, 16, st));
-        HS_HIP(hipMemsetAsync(d_wide.as<int32_t>() + R, 0, 4, st));
-        const unsigned grid_m = (unsigned)((M + 255) / 256);
-        if (M > 0) hipLaunchKernelGGL(hsdev::k_map_hits_count, dim3(grid_m), dim3(256), 0, st, X, mz.h.as<uint32_t>(), mz.seq.as<int32_t>(), (long long)M, n_reads, prm.max_occ,
-                                      d_cnt.as<int32_t>(), d_nskip.as<int32_t>());
-        if (int rc = exclusive_scan_launch(d_cnt.as<int32_t>(), (int)M, d_hit_off.as<int64_t>(), d_scan, st)) return rc;
-        if (R) hipLaunchKernelGGL(hsdev::k_map_read_hits, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, d_mz_off.as<int64_t>(), d_hit_off.as<int64_t>(), n_reads,
-                                  d_nhits.as<int64_t>(), d_nmz.as<int32_t>(), d_max.as<unsigned long long>());
-        HS_HIP(hipGetLastError());
-        int64_t H = 0, max_hits = 0;
-        HS_HIP(HS_COPY_ASYNC(&max_hits, d_max.p, 8, hipMemcpyDeviceToHost, st));
-        if (int rc = copy_d2h(&H, d_hit_off.as<int64_t>() + M, 8, st)) return rc;
-        if (H < 0 || max_hits < 0 || max_hits > H) { set_error("hs_map_reads: the device's hit counts do not fit the minimizers"); return HS_EHIP; }
-        if (max_hits > ((int64_t)1 << 28)) { set_error("hs_map_reads: a read with more than 2^28 hits: lower max_occ"); return HS_EINVAL; }
-        // ---- the hits ----
-        if (int rc = d_key.alloc((size_t)std::max<int64_t>(H, 1) * 8)) return rc;
-        if (int rc = d_qa.alloc((size_t)std::max<int64_t>(H, 1) * 4)) return rc;
-        if (int rc = d_t.alloc((size_t)std::max<int64_t>(H, 1) * 4)) return rc;
-        if (M > 0 && H > 0) hipLaunchKernelGGL(hsdev::k_map_hits_fill, dim3(grid_m), dim3(256), 0, st, X, mz.h.as<uint32_t>(), mz.ps.as<uint32_t>(), mz.seq.as<int32_t>(), (long long)M,
-                                               d_off.as<int64_t>(), n_reads, prm, d_cnt.as<int32_t>(), d_hit_off.as<int64_t>(), (long long)H, d_key.as<uint64_t>(), d_qa.as<int32_t>(),
-                                               d_t.as<int32_t>());
-        HS_HIP(hipGetLastError());
-        if (int rc = kc.end(8 * M + 2 * 16 * H, st)) return rc;
-        HS_HIP(ev_rec(ev_hits.b, st));
+        int64_t H = 0, max_hits = 0, hit_bytes = 8 * M;
+        if (int rc = timed_launch(kc, ev_hits, st, hit_bytes, [&]() -> int {
+                HS_HIP(hipMemsetAsync(out + w.n_skipped, 0, (size_t)(w.shipped - w.n_skipped), st));      // (n_skipped, the wide counter, the largest read)
+                const unsigned grid_m = (unsigned)((M + 255) / 256);
+                if (M > 0) hipLaunchKernelGGL(hsdev::k_map_hits_count, dim3(grid_m), dim3(256), 0, st, X, mz.h.as<uint32_t>(), mz.seq.as<int32_t>(), (long long)M, n_reads, prm.max_occ,
+                                              d_cnt.as<int32_t>(), (int32_t*)(out + w.n_skipped));
+                if (int rc = exclusive_scan_launch(d_cnt.as<int32_t>(), (int)M, d_hit_off.as<int64_t>(), d_scan, st)) return rc;
+                if (R) hipLaunchKernelGGL(hsdev::k_map_read_hits, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, d_mz_off.as<int64_t>(), d_hit_off.as<int64_t>(), n_reads,
+                                          (int64_t*)(out + w.n_hits), (int32_t*)(out + w.n_minimizers), (unsigned long long*)(out + w.max_hits));
+                HS_HIP(hipGetLastError());
+                HS_HIP(HS_COPY_ASYNC(&max_hits, out + w.max_hits, 8, hipMemcpyDeviceToHost, st));
+                if (int rc = copy_d2h(&H, d_hit_off.as<int64_t>() + M, 8, st)) return rc;
+                if (H < 0 || max_hits < 0 || max_hits > H) { set_error("hs_map_reads: the device's hit counts do not fit the minimizers"); return HS_EHIP; }
+                if (max_hits > ((int64_t)1 << 28)) { set_error("hs_map_reads: a read with more than 2^28 hits: lower max_occ"); return HS_EINVAL; }
+                hit_bytes += 2 * 16 * H;
+                if (int rc = d_key.alloc((size_t)std::max<int64_t>(H, 1) * 8)) return rc;
+                if (int rc = d_qa.alloc((size_t)std::max<int64_t>(H, 1) * 4)) return rc;
+                if (int rc = d_t.alloc((size_t)std::max<int64_t>(H, 1) * 4)) return rc;
+                if (M > 0 && H > 0) hipLaunchKernelGGL(hsdev::k_map_hits_fill, dim3(grid_m), dim3(256), 0, st, X, mz.h.as<uint32_t>(), mz.ps.as<uint32_t>(), mz.seq.as<int32_t>(), (long long)M,
+                                                       d_off.as<int64_t>(), n_reads, prm, d_cnt.as<int32_t>(), d_hit_off.as<int64_t>(), (long long)H, d_key.as<uint64_t>(), d_qa.as<int32_t>(),
+                                                       d_t.as<int32_t>());
+                HS_HIP(hipGetLastError());
+                return HS_OK; })) return rc;
         // ---- the vote: LDS route for every read, the scratch route for the list it leaves ----
-        int64_t slab_keys = 2;
-        while (slab_keys < max_hits) slab_keys <<= 1;
-        if (max_hits <= HS_MAP_LDS_KEYS) slab_keys = 2;      // (the list stays empty)
+        const int64_t slab_keys = max_hits <= HS_MAP_LDS_KEYS ? 2 : hsdev::pow2_at_least((int)max_hits);      // (2: the list stays empty)
         const int wide_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(HS_MAP_WIDE_BLOCKS, ((int64_t)1 << 28) / slab_keys));
         if (int rc = d_slabs.alloc((size_t)slab_keys * 8 * (size_t)wide_blocks)) return rc;
         hsdev::MapVoteArgs A{};
         A.mz_off = d_mz_off.as<int64_t>(); A.hit_off = d_hit_off.as<int64_t>(); A.hit_key = d_key.as<uint64_t>(); A.hit_qa = d_qa.as<int32_t>(); A.hit_t = d_t.as<int32_t>(); A.n_hits = H;
         A.read_off = d_off.as<int64_t>(); A.contig_off = index->d_contig_off.as<int64_t>(); A.n_contigs = index->n_contigs; A.n_reads = n_reads; A.P = prm;
-        A.contig = d_contig.as<int32_t>(); A.strand = d_strand.as<uint8_t>(); A.qstart = d_qs.as<int32_t>(); A.qend = d_qe.as<int32_t>(); A.tstart = d_ts.as<int32_t>();
-        A.tend = d_te.as<int32_t>(); A.votes = d_votes.as<int32_t>(); A.second = d_second.as<int32_t>(); A.wide_list = d_wide.as<int32_t>(); A.wide_count = d_wide.as<int32_t>() + R;
-        HS_HIP(ev_rec(ev_vote.a, st));
-        if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
-        if (R) hipLaunchKernelGGL(hsdev::k_map_vote, dim3((unsigned)R), dim3(256), 0, st, A);
-        hipLaunchKernelGGL(hsdev::k_map_vote_wide, dim3((unsigned)wide_blocks), dim3(256), 0, st, A, d_slabs.as<uint64_t>(), (long long)slab_keys);
-        HS_HIP(hipGetLastError());
-        if (int rc = kc.end(2 * 16 * H + 30 * (int64_t)R, st)) return rc;
-        HS_HIP(ev_rec(ev_vote.b, st));
-        // ---- the records ----
+        A.contig = (int32_t*)(out + w.contig); A.strand = (uint8_t*)(out + w.strand); A.qstart = (int32_t*)(out + w.qstart); A.qend = (int32_t*)(out + w.qend);
+        A.tstart = (int32_t*)(out + w.tstart); A.tend = (int32_t*)(out + w.tend); A.votes = (int32_t*)(out + w.votes); A.second = (int32_t*)(out + w.second);
+        A.wide_list = (int32_t*)(out + w.wide_list); A.wide_count = (int32_t*)(out + w.wide_count);
+        if (int rc = timed_launch(kc, ev_vote, st, 2 * 16 * H + 30 * (int64_t)R, [&]() -> int {
+                if (R) hipLaunchKernelGGL(hsdev::k_map_vote, dim3((unsigned)R), dim3(256), 0, st, A);
+                hipLaunchKernelGGL(hsdev::k_map_vote_wide, dim3((unsigned)wide_blocks), dim3(256), 0, st, A, d_slabs.as<uint64_t>(), (long long)slab_keys);
+                HS_HIP(hipGetLastError());
+                return HS_OK; })) return rc;
+        // ---- the records: one shipment to one pinned block (one wait), the result's arrays filled from it ----
+        HBuf h_out;
+        if (int rc = h_out.alloc((size_t)w.shipped)) return rc;
+        Shipment sh;
+        sh.add(h_out.p, out, (size_t)w.shipped);
+        if (int rc = sh.launch(st)) return rc;
+        if (int rc = stream_wait(st)) return rc;
+        const char* hp = (const char*)h_out.p;
         hs_map_result* r = (hs_map_result*)std::calloc(1, sizeof(hs_map_result));
         if (!r) { set_error("hs_map_reads: out of memory"); return HS_EINVAL; }
-        int rc = HS_OK;
         r->n_reads = n_reads;
-        r->contig = map_download<int32_t>(d_contig, R, st, &rc); r->strand = map_download<uint8_t>(d_strand, R, st, &rc);
-        r->qstart = map_download<int32_t>(d_qs, R, st, &rc); r->qend = map_download<int32_t>(d_qe, R, st, &rc);
-        r->tstart = map_download<int32_t>(d_ts, R, st, &rc); r->tend = map_download<int32_t>(d_te, R, st, &rc);
-        r->votes = map_download<int32_t>(d_votes, R, st, &rc); r->second = map_download<int32_t>(d_second, R, st, &rc);
-        r->n_minimizers = map_download<int32_t>(d_nmz, R, st, &rc); r->n_skipped = map_download<int32_t>(d_nskip, R, st, &rc);
-        r->n_hits = map_download<int64_t>(d_nhits, R, st, &rc);
-        int32_t n_wide = 0;
-        if (rc == HS_OK) rc = copy_d2h(&n_wide, d_wide.as<int32_t>() + R, 4, st);
-        if (rc == HS_OK) rc = stream_wait(st);
-        if (rc != HS_OK) { hs_map_result_destroy(r); return rc; }
-        r->n_wide = n_wide; r->total_minimizers = M; r->total_hits = H;
+        bool oom = false;
+        auto fill = [&](auto*& dst, int64_t at) {      // (one element of room at least, as hs_map_result_destroy and the callers expect)
+            dst = (decltype(+dst))std::calloc(std::max<size_t>(1, R), sizeof *dst);
+            if (!dst) oom = true; else if (R) std::memcpy(dst, hp + at, R * sizeof *dst);
+        };
+        fill(r->contig, w.contig); fill(r->strand, w.strand); fill(r->qstart, w.qstart); fill(r->qend, w.qend); fill(r->tstart, w.tstart); fill(r->tend, w.tend);
+        fill(r->votes, w.votes); fill(r->second, w.second); fill(r->n_minimizers, w.n_minimizers); fill(r->n_skipped, w.n_skipped); fill(r->n_hits, w.n_hits);
+        if (oom) { hs_map_result_destroy(r); set_error("hs_map_reads: out of memory"); return HS_EINVAL; }
+        r->n_wide = *(const int32_t*)(hp + w.wide_count); r->total_minimizers = M; r->total_hits = H;
         float ms = 0;
         if (ev_mz.ms(&ms) == HS_OK) r->t_minimizers_ms = ms;
         if (ev_hits.ms(&ms) == HS_OK) r->t_hits_ms = ms;
@@ -276,23 +281,7 @@ int hs_map_files(const char* gfa, const char* reads, const char* out_paf, int32_
         if (n_threads < 1) n_threads = host_threads();
         hs::SeqSet seqs;
         if (int rc = hs::load_sequences(gfa, reads, seqs, n_threads)) return rc;
-        if (seqs.contig_names.empty()) {
-            std::ifstream f(gfa);
-            std::string line;
-            bool fasta = false;
-            while (std::getline(f, line)) {
-                if (!line.empty() && line.back() == '\r') line.pop_back();
-                if (line.empty()) continue;
-                if (line[0] == '>') {
-                    fasta = true;
-                    if (!seqs.contig_names.empty()) seqs.contig_off.push_back((int64_t)seqs.contig_seq.size());
-                    seqs.contig_names.push_back(line.substr(1, line.find_first_of(" \t", 1) == std::string::npos ? std::string::npos : line.find_first_of(" \t", 1) - 1));
-                } else if (fasta) {
-                    for (char ch : line) seqs.contig_seq.push_back(ch == 'C' || ch == 'c' ? 1 : ch == 'G' || ch == 'g' ? 2 : ch == 'T' || ch == 't' ? 3 : 0);
-                }
-            }
-            if (fasta) seqs.contig_off.push_back((int64_t)seqs.contig_seq.size());
-        }
+        if (seqs.contig_names.empty()) hs::load_fasta_contigs(gfa, seqs);
         if (seqs.read_names.size() > 0x7fffffffu || seqs.contig_names.size() > 0x7fffffffu) { set_error("hs_map_files: more than 2^31 reads or contigs"); return HS_EINVAL; }
         const int32_t C = (int32_t)seqs.contig_names.size(), R = (int32_t)seqs.read_names.size();
         hs_map_index* ix = nullptr;

@@ -31,11 +31,6 @@ void polish_backbone_ranges(int L, int start, int end, const PolishIntervalBound
     polish_substr(L, end, std::min(b.ovr + 1, L - end - 1), pos[2], len[2]);
 }
 
-template <class T> T* polish_malloc_copy(const std::vector<T>& v) {
-    T* p = static_cast<T*>(std::malloc(std::max<size_t>(v.size(), 1) * sizeof(T)));
-    if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
 // a large device array into pageable host memory, 64 MB of pinned staging at a time
 int polish_download(void* dst, const void* d, size_t n, hipStream_t s) {
     const size_t step = (size_t)64 << 20;
@@ -48,9 +43,9 @@ struct PolishTimer {   // HIP events around a group of launches, summed when the
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
     hipStream_t s;
     explicit PolishTimer(hipStream_t st) : s(st) {}
-    ~PolishTimer() { for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } }
-    void begin() { hipEvent_t a = nullptr, b = nullptr; (void)hipEventCreate(&a); (void)hipEventCreate(&b); ev.push_back({a, b}); (void)hipEventRecord(a, s); }
-    void end() { (void)hipEventRecord(ev.back().second, s); }
+    ~PolishTimer() { for (auto& e : ev) for (hipEvent_t x : {e.first, e.second}) if (x) EventPair::cache().push_back(x); }      // (recycled, as every timing event of the library)
+    void begin() { hipEvent_t a = nullptr, b = nullptr; (void)EventPair::get(&a); (void)EventPair::get(&b); ev.push_back({a, b}); (void)ev_rec(a, s); }
+    void end() { (void)ev_rec(ev.back().second, s); }
     double ms() { double t = 0; for (auto& e : ev) { float x = 0; if (hipEventElapsedTime(&x, e.first, e.second) == hipSuccess) t += x; } return t; }
 };
 
@@ -275,13 +270,13 @@ int polish_inputs_core(hs_cv_batch* b, int c0, int c1, const std::vector<std::ve
         const int32_t v[9] = {bu.contig, bu.interval, bu.start, bu.end, bu.group, bu.left, bu.right, bu.ovl, bu.ovr};
         for (int j = 0; j < 9; ++j) f[j].push_back(v[j]);
     }
-    res->bundle_contig = polish_malloc_copy(f[0]); res->bundle_interval = polish_malloc_copy(f[1]); res->bundle_start = polish_malloc_copy(f[2]);
-    res->bundle_end = polish_malloc_copy(f[3]); res->bundle_group = polish_malloc_copy(f[4]); res->bundle_left_to_polish = polish_malloc_copy(f[5]);
-    res->bundle_right_to_polish = polish_malloc_copy(f[6]); res->bundle_overhang_left = polish_malloc_copy(f[7]); res->bundle_overhang_right = polish_malloc_copy(f[8]);
-    res->backbone_off = polish_malloc_copy(backbone_off); res->piece_off = polish_malloc_copy(piece_off);
-    res->piece_rec = polish_malloc_copy(piece_rec); res->piece_read_start = polish_malloc_copy(piece_rs); res->piece_read_end = polish_malloc_copy(piece_re);
-    res->piece_sam_pos = polish_malloc_copy(piece_sam); res->piece_flags = polish_malloc_copy(piece_flags);
-    res->base_off = polish_malloc_copy(base_off); res->cig_off = polish_malloc_copy(cig_off); res->dropped = polish_malloc_copy(dropped);
+    res->bundle_contig = malloc_copy(f[0]); res->bundle_interval = malloc_copy(f[1]); res->bundle_start = malloc_copy(f[2]);
+    res->bundle_end = malloc_copy(f[3]); res->bundle_group = malloc_copy(f[4]); res->bundle_left_to_polish = malloc_copy(f[5]);
+    res->bundle_right_to_polish = malloc_copy(f[6]); res->bundle_overhang_left = malloc_copy(f[7]); res->bundle_overhang_right = malloc_copy(f[8]);
+    res->backbone_off = malloc_copy(backbone_off); res->piece_off = malloc_copy(piece_off);
+    res->piece_rec = malloc_copy(piece_rec); res->piece_read_start = malloc_copy(piece_rs); res->piece_read_end = malloc_copy(piece_re);
+    res->piece_sam_pos = malloc_copy(piece_sam); res->piece_flags = malloc_copy(piece_flags);
+    res->base_off = malloc_copy(base_off); res->cig_off = malloc_copy(cig_off); res->dropped = malloc_copy(dropped);
     res->t_scan_ms = t_scan.ms(); res->t_cut_ms = t_cut.ms(); res->t_gather_ms = t_gather.ms(); res->t_cigar_ms = t_cigar.ms();
     res->n_tasks = n_tasks; res->n_rounds = n_rounds; res->cut_ops_read = cut_ops;
     *out = guard.release();

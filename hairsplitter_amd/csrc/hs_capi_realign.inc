@@ -65,21 +65,6 @@ static int realign_cut_launch(const DBuf& d_off, const DBuf& d_src, const uint8_
     return HS_OK;
 }
 
-// a job's sequences on the device as hs_cv_batch keeps them: HS_SEQ_PAD zero bytes, the bases, HS_SEQ_PAD zero bytes
-static int upload_padded(DBuf& d, const uint8_t* src, size_t bytes) {
-    if (int rc = d.alloc(bytes + 2 * HS_SEQ_PAD)) return rc;
-    HS_HIP(hipMemset(d.p, 0, HS_SEQ_PAD));
-    HS_HIP(hipMemset((char*)d.p + HS_SEQ_PAD + bytes, 0, HS_SEQ_PAD));
-    if (bytes) HS_HIP(hipMemcpy((char*)d.p + HS_SEQ_PAD, src, bytes, hipMemcpyHostToDevice));
-    return HS_OK;
-}
-
-template <class T> static T* malloc_copy(const std::vector<T>& v) {
-    T* p = (T*)std::malloc(std::max<size_t>(1, v.size()) * sizeof(T));
-    if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
-
 }  // namespace
 
 int hs_moves_to_cigar(const uint8_t* d_ops, const int64_t* h_ops_off, const int32_t* d_ops_len, const int32_t* d_clip_left, const int32_t* d_clip_right, int32_t n,
@@ -139,8 +124,8 @@ int hs_realign_intervals(const uint8_t* h_contig_seq, const int64_t* h_contig_of
         const hipStream_t stream = nullptr;
         DBuf d_contigs, d_reads;      // the job's first device copy of the sequences: back in the pool before the batch is made
         if (n) {
-            if (int rc = upload_padded(d_contigs, h_contig_seq, (size_t)h_contig_off[n_contigs])) return rc;
-            if (int rc = upload_padded(d_reads, h_read_seq, (size_t)h_read_off[n_reads])) return rc;
+            if (int rc = upload_pageable(d_contigs, h_contig_seq, (size_t)h_contig_off[n_contigs], HS_SEQ_PAD, HS_SEQ_PAD)) return rc;
+            if (int rc = upload_pageable(d_reads, h_read_seq, (size_t)h_read_off[n_reads], HS_SEQ_PAD, HS_SEQ_PAD)) return rc;
         }
         std::vector<int32_t> rec_interval, rec_read, rec_pos, rec_dist, contig_rec_off((size_t)n_contigs + 1, 0), dropped;
         std::vector<uint8_t> rec_strand;
@@ -191,21 +176,18 @@ int hs_realign_intervals(const uint8_t* h_contig_seq, const int64_t* h_contig_of
             for (DBuf* b : {&dd, &ds, &de, &dlen, &d_pos}) if (int rc = b->alloc(m * sizeof(int32_t))) return rc;
             if (int rc = d_word_off.alloc((m + 1) * sizeof(int64_t))) return rc;
             // ---- cut ----
-            hipEvent_t ev_a = nullptr, ev_b = nullptr;
-            if (int rc = EventPair::get(&ev_a)) return rc;
-            if (int rc = EventPair::get(&ev_b)) { EventPair::cache().push_back(ev_a); return rc; }
-            struct EvBack { hipEvent_t a, b; ~EvBack() { EventPair::cache().push_back(a); EventPair::cache().push_back(b); } } ev_back{ev_a, ev_b};
-            HS_HIP(hipEventRecord(ev_a, stream));
+            EventPair ev_cut;      // (whatever the step: the records report the cut's time of every call)
+            if (int rc = ev_cut.take()) return rc;
+            HS_HIP(ev_rec(ev_cut.a, stream));
             if (int rc = realign_cut_launch(dq_off, dq_src, d_rev.as<uint8_t>(), (int32_t)m, q_off[m], d_reads.as<uint8_t>() + HS_SEQ_PAD, dq.as<uint8_t>(), stream)) return rc;
             if (int rc = realign_cut_launch(dt_off, dt_src, nullptr, (int32_t)m, t_off[m], d_contigs.as<uint8_t>() + HS_SEQ_PAD, dt.as<uint8_t>(), stream)) return rc;
-            HS_HIP(hipEventRecord(ev_b, stream));
+            HS_HIP(ev_rec(ev_cut.b, stream));
             // ---- align (synchronous) ----
             auto t0 = wall();
             if (int rc = hs_edlib_hw_align(dq.as<uint8_t>(), q_off.data(), dt.as<uint8_t>(), t_off.data(), (int32_t)m, dd.as<int32_t>(), ds.as<int32_t>(), de.as<int32_t>(),
                                            dops.as<uint8_t>(), o_off.data(), dlen.as<int32_t>(), stream)) return rc;
             float cut_ms = 0;
-            HS_HIP(hipEventSynchronize(ev_b));
-            HS_HIP(hipEventElapsedTime(&cut_ms, ev_a, ev_b));
+            if (int rc = ev_cut.ms(&cut_ms)) return rc;
             t_cut += cut_ms; t_align += ms_since(t0) - cut_ms;      // (the cut runs ahead of the aligner on the same stream)
             // ---- moves -> words: a pair without a path gets none, so the words of the round lie compact ----
             t0 = wall();

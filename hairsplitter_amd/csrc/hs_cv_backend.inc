@@ -138,55 +138,11 @@ int hs_cv_batch_create(const uint8_t* h_contig_seq, const int64_t* h_contig_off,
     }
     lap("spans+depth");
     int rc = 0;
-    // Large pageable arrays (read bases, CIGAR ops: gigabytes) go up through two pinned 32-MB buffers: a chunk is copied into one on
-    // several host threads while the other is on its way (a plain hipMemcpy from pageable memory stages through the runtime's own
-    // buffers with one copying thread: 12-15 GB/s)
-    HBuf stage[2];
-    hipEvent_t stage_done[2] = {nullptr, nullptr};
-    auto up_big = [&](void* dst, const char* src, size_t bytes) -> int {
-        const size_t CH = (size_t)32 << 20;
-        for (int k = 0; k < 2; ++k) {
-            if (!stage[k].p) { if (int r = stage[k].alloc(CH)) return r; }
-            if (!stage_done[k]) HS_HIP(hipEventCreateWithFlags(&stage_done[k], hipEventDisableTiming));
-        }
-        int k = 0;
-        for (size_t off = 0; off < bytes; off += CH, k ^= 1) {
-            const size_t n = std::min(CH, bytes - off);
-            HS_HIP(hipEventSynchronize(stage_done[k]));      // (the copy that last used this buffer; returns at once the first time)
-            const int parts = 8;
-            hs::hs_parallel_for(parts, std::min(parts, host_threads()), [&](int q) {
-                const size_t a = n * (size_t)q / parts, e = n * ((size_t)q + 1) / parts;
-                std::memcpy((char*)stage[k].p + a, src + off + a, e - a);
-            });
-            HS_HIP(hipMemcpyAsync((char*)dst + off, stage[k].p, n, hipMemcpyHostToDevice, nullptr));
-            HS_HIP(ev_rec(stage_done[k], nullptr));
-        }
-        HS_HIP(hipStreamSynchronize(nullptr));
-        return HS_OK;
-    };
-    auto up = [&](DBuf& d, const void* src, size_t bytes) {
-        if (rc) return;
-        rc = d.alloc(bytes);
-        if (rc || !bytes) return;
-        if (bytes >= ((size_t)64 << 20)) { rc = up_big(d.p, (const char*)src, bytes); return; }
-        hipError_t e = hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = HS_EHIP; }
-    };
-    auto up_padded = [&](DBuf& d, const void* src, size_t bytes) {      // HS_SEQ_PAD zero bytes, the data, HS_SEQ_PAD zero bytes
-        if (rc) return;
-        rc = d.alloc(bytes + 2 * HS_SEQ_PAD);
-        if (rc) return;
-        hipError_t e = hipMemset(d.p, 0, HS_SEQ_PAD);
-        if (e == hipSuccess) e = hipMemset((char*)d.p + HS_SEQ_PAD + bytes, 0, HS_SEQ_PAD);
-        if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = HS_EHIP; return; }
-        if (!bytes) return;
-        if (bytes >= ((size_t)64 << 20)) { rc = up_big((char*)d.p + HS_SEQ_PAD, (const char*)src, bytes); return; }
-        e = hipMemcpy((char*)d.p + HS_SEQ_PAD, src, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { set_error(hipGetErrorString(e)); rc = HS_EHIP; }
-    };
-    up_padded(b->contig_seq, h_contig_seq, (size_t)b->total_len);
+    // (every array below goes up by the runtime's one route, upload_pageable; the first failure stops the rest)
+    auto up = [&](DBuf& d, const void* src, size_t bytes, size_t pad = 0) { if (!rc) rc = upload_pageable(d, src, bytes, pad, pad); };
+    up(b->contig_seq, h_contig_seq, (size_t)b->total_len, HS_SEQ_PAD);
     up(b->d_contig_off, b->contig_off.data(), sizeof(int64_t) * b->contig_off.size());
-    up_padded(b->read_seq, h_read_seq, (size_t)h_read_off[n_reads]);
+    up(b->read_seq, h_read_seq, (size_t)h_read_off[n_reads], HS_SEQ_PAD);
     up(b->read_off, h_read_off, sizeof(int64_t) * ((size_t)n_reads + 1));
     lap("sequences up");
     up(b->rec_read, h_rec_read, sizeof(int32_t) * (size_t)n_rec);
@@ -249,7 +205,6 @@ int hs_cv_batch_create(const uint8_t* h_contig_seq, const int64_t* h_contig_off,
     }
     if (!rc) rc = b->pile.alloc((size_t)b->pile_bytes + 512);
     if (!rc) rc = b->rec_stats.alloc(sizeof(int32_t) * 4 * (size_t)n_rec);
-    for (int k = 0; k < 2; ++k) if (stage_done[k]) (void)hipEventDestroy(stage_done[k]);
     if (rc) { delete b; return rc; }
     lap("pileup plan + tasks + buffers");
     if (lap_on) std::fprintf(stderr, "[hs timing] hs_cv_batch_create laps (ms):%s\n", lap_s.c_str());

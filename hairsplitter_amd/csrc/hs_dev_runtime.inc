@@ -345,7 +345,8 @@ struct EventPair {
         HS_HIP(hipEventCreateWithFlags(e, hipEventDefault));
         return HS_OK;
     }
-    int init() { if (!timing_on()) return HS_OK; if (int rc = get(&a)) return rc; return get(&b); }
+    int take() { if (int rc = get(&a)) return rc; return get(&b); }      // (whatever the step: a caller that times every call)
+    int init() { return timing_on() ? take() : HS_OK; }
     // (called after the stream has been waited for: the events are complete and no synchronising call -- an ioctl in the
     // runtime -- is needed; one that is not yet complete is waited for the slow way)
     int ms(float* out) {
@@ -418,7 +419,59 @@ struct KernelClock {
     ~KernelClock() { flush(); if (open_a) EventPair::cache().push_back(open_a); }
 };
 
+// a launch (or a short run of launches of one family) between the two records of a caller's EventPair and the KernelClock's, under
+// HS_K_OTHER. `bytes` is read when the launch has returned: one that learns its size on the way (the minimizers' count) sets it then.
+template <class Launch> static int timed_launch(KernelClock& kc, EventPair& ev, hipStream_t st, const int64_t& bytes, Launch launch) {
+    HS_HIP(ev_rec(ev.a, st));
+    if (int rc = kc.begin(HS_K_OTHER, st)) return rc;
+    if (int rc = launch()) return rc;
+    if (int rc = kc.end(bytes, st)) return rc;
+    HS_HIP(ev_rec(ev.b, st));
+    return HS_OK;
+}
+
 static int host_threads() { return hs::host_threads(); }      // usable cores (hs_driver.cpp)
+
+// How a caller's pageable array goes up, stated once: into a block of its own, `before` zero bytes in front and `behind` zero bytes
+// behind it (a job's sequences carry HS_SEQ_PAD readable bytes on either side). Below 64 MB a plain hipMemcpy. Read bases and CIGAR ops
+// are gigabytes: from 64 MB on the array goes through two pinned 32-MB buffers, a chunk copied into one on several host threads while
+// the other is on its way (a plain hipMemcpy from pageable memory stages through the runtime's own buffers with one copying thread:
+// 12-15 GB/s when batch creation was measured; at 115 MB the two are level, DESIGN 4.9d). Synchronous on the calling thread's default stream.
+static int upload_pageable(DBuf& d, const void* src, size_t bytes, size_t before = 0, size_t behind = 0) {
+    if (int rc = d.alloc(before + bytes + behind)) return rc;
+    char* dst = (char*)d.p + before;
+    if (before) HS_HIP(hipMemset(d.p, 0, before));
+    if (behind) HS_HIP(hipMemset(dst + bytes, 0, behind));
+    if (!bytes) return HS_OK;
+    if (bytes < ((size_t)64 << 20)) { HS_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return HS_OK; }
+    const size_t CH = (size_t)32 << 20;
+    HBuf stage[2];
+    EventPair done;      // a: the copy that last used stage[0], b: stage[1]'s
+    if (int rc = done.take()) return rc;
+    const hipEvent_t stage_done[2] = {done.a, done.b};
+    for (int k = 0; k < 2; ++k) if (int rc = stage[k].alloc(CH)) return rc;
+    int k = 0;
+    for (size_t off = 0; off < bytes; off += CH, k ^= 1) {
+        const size_t n = std::min(CH, bytes - off);
+        if (off >= 2 * CH) HS_HIP(hipEventSynchronize(stage_done[k]));      // (the copy that last used this buffer)
+        const int parts = 8;
+        hs::hs_parallel_for(parts, std::min(parts, host_threads()), [&](int q) {
+            const size_t a = n * (size_t)q / parts, e = n * ((size_t)q + 1) / parts;
+            std::memcpy((char*)stage[k].p + a, (const char*)src + off + a, e - a);
+        });
+        HS_HIP(hipMemcpyAsync(dst + off, stage[k].p, n, hipMemcpyHostToDevice, nullptr));
+        HS_HIP(ev_rec(stage_done[k], nullptr));
+    }
+    HS_HIP(hipStreamSynchronize(nullptr));
+    return HS_OK;
+}
+
+// a vector's elements in a malloc'd array of the C ABI's results (one element of room at least); nullptr: out of memory
+template <class T> static T* malloc_copy(const std::vector<T>& v) {
+    T* p = static_cast<T*>(std::malloc(std::max<size_t>(v.size(), 1) * sizeof(T)));
+    if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
+    return p;
+}
 
 // K2 of one contig group at a time: the kernel fills the device on its own; eight of them side by side only slow each other
 // down (0.29 ms alone, 1.0 ms each among eight) and every group would get its selection at the same late moment, whereas one

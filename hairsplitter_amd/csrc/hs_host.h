@@ -141,6 +141,7 @@ struct SeqSet {
     std::vector<int64_t> read_off, contig_off;
 };
 int load_sequences(const std::string& gfa, const std::string& reads, SeqSet& out, int n_threads = 1);
+void load_fasta_contigs(const std::string& fasta, SeqSet& out);      // (hs_map_files: an assembly without S lines that begins with '>')
 // CIGAR-less input (hs_realign.cpp): a PAF file becomes the SAM the path reads, every read segment aligned against its contig window
 // on the device with edlib's HW path (A1)
 struct RealignStats { int64_t n_lines = 0, n_aligned = 0, query_bases = 0; double ms_device = 0, ms_total = 0; };

@@ -303,6 +303,26 @@ int load_sequences(const std::string& gfa, const std::string& reads, SeqSet& out
     return HS_OK;
 }
 
+// the contigs of an assembly given as FASTA ('>' headers, the name up to the first blank; sequence lines coded as the mapper reads them:
+// C 1, G 2, T 3, anything else 0), behind a load_sequences that found no S line in the file (one without a header either leaves `out` as it is)
+void load_fasta_contigs(const std::string& fasta, SeqSet& out) {
+    std::ifstream f(fasta);
+    std::string line;
+    bool found = false;
+    while (std::getline(f, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        if (line[0] == '>') {
+            found = true;
+            if (!out.contig_names.empty()) out.contig_off.push_back((int64_t)out.contig_seq.size());
+            out.contig_names.push_back(line.substr(1, line.find_first_of(" \t", 1) == std::string::npos ? std::string::npos : line.find_first_of(" \t", 1) - 1));
+        } else if (found) {
+            for (char ch : line) out.contig_seq.push_back(ch == 'C' || ch == 'c' ? 1 : ch == 'G' || ch == 'g' ? 2 : ch == 'T' || ch == 't' ? 3 : 0);
+        }
+    }
+    if (found) out.contig_off.push_back((int64_t)out.contig_seq.size());
+}
+
 int load_cv_inputs(const std::string& gfa, const std::string& reads, const std::string& sam, bool amplicon, CvFileInput& in, int n_threads) {
     if (n_threads < 1) n_threads = 1;
     const bool tim = std::getenv("HS_TIMING") != nullptr;

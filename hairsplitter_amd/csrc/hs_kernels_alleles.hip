@@ -7,7 +7,7 @@
 // hs_alleles_host.h (allele_cell_finish), and both the host restatement and the kernel below end in it.
 //
 // Route of k_allele_cells: one workgroup per SNP column. Every entry of the column becomes a key (group slot << 8 | code), or the
-// invalid key when its read has no label >= 0 in the window. The keys are sorted (bitonic network over the next power of two) and a
+// invalid key when its read has no label >= 0 in the window. The keys are sorted (block_bitonic_sort of hs_device.h, over the next power of two) and a
 // lane per group finds its stretch of the sorted keys by bisection and hops from one run of equal keys to the next by bisection too.
 // A per-group histogram over the 125 codes needs 250 B per group -- 300 groups do not fit the LDS next to anything else, 65535 not at
 // all --, the sorted keys need 4 B per ENTRY whatever the number of groups, and a run costs log2(depth) probes however long it is.
@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "hs_alleles_host.h"
+#include "hs_device.h"
 
 #define HS_ALLELE_LDS_KEYS 2048         /* entries of a column whose keys one wavefront sorts in LDS (8 KB) */
 #define HS_ALLELE_WIDE_KEYS 65536       /* keys of a slab of global scratch: the next power of two of the path's deepest column */
@@ -118,15 +119,7 @@ static __device__ void allele_column(uint32_t* keys, int n_pow2, uint32_t* s_cal
         keys[i] = key;
     }
     __syncthreads();
-    for (int k = 2; k <= n_pow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (n_pow2 >> 1); t += nt) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const uint32_t a = keys[i], b = keys[l];
-                if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[l] = a; }
-            }
-            __syncthreads();
-        }
+    block_bitonic_sort(keys, n_pow2);
     // first index whose key is >= v
     auto lower = [&](uint32_t v, int from) { int lo = from, hi = depth; while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] < v) lo = mid + 1; else hi = mid; } return lo; };
     for (int g = tid; g < G; g += nt) {
@@ -189,9 +182,7 @@ static __device__ bool allele_one(const AlleleArgs& A, int s, uint32_t* keys, in
     if (!work) { if (threadIdx.x == 0) A.n_calls[s] = 0; return true; }
     const long long c0 = A.cell_off[s];
     if (c0 < 0 || c0 + c.G > A.cells_cap) { if (threadIdx.x == 0) A.n_calls[s] = -1; return true; }      // never write beyond the caller's cells
-    int n_pow2 = 2;
-    while (n_pow2 < c.depth) n_pow2 <<= 1;
-    allele_column(keys, n_pow2, s_calls, c.e0, c.depth, A.col_idx, A.col_code, A.labels + c.l0, (int)c.n_reads, A.grp_ids + c.l0, c.G,
+    allele_column(keys, pow2_at_least(c.depth), s_calls, c.e0, c.depth, A.col_idx, A.col_code, A.labels + c.l0, (int)c.n_reads, A.grp_ids + c.l0, c.G,
                   A.snp_ref[s], A.snp_alt[s], A.cells + c0, A.n_calls + s);
     return true;
 }
@@ -201,7 +192,7 @@ __global__ __launch_bounds__(64) void k_allele_cells(AlleleArgs A) {
     __shared__ uint32_t s_calls[8];
     const int s = (int)blockIdx.x;
     if (s >= A.n_snps) return;
-    if (!allele_one(A, s, s_keys, HS_ALLELE_LDS_KEYS, s_calls) && threadIdx.x == 0) A.wide_list[atomicAdd(A.wide_count, 1)] = s;
+    if (!allele_one(A, s, s_keys, HS_ALLELE_LDS_KEYS, s_calls) && threadIdx.x == 0) wide_list_push(A.wide_count, A.wide_list, A.n_snps, s);
 }
 
 __global__ __launch_bounds__(256) void k_allele_cells_wide(AlleleArgs A, uint32_t* __restrict__ slabs) {

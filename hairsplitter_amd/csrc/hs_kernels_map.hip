@@ -10,7 +10,7 @@
 //   k_map_bucket_count / _fill     the index: bucket = low bits of the hash; no-return atomics count, an atomic cursor fills (the order inside
 //                                  a bucket differs from run to run and no result depends on it)
 //   k_map_hits_count / _fill       one lane per read minimizer scans its bucket: occ(h), then (key, qa, t) into the read's range of the scratch
-//   k_map_vote                     one workgroup per read: keys sorted in LDS (the bitonic network of k_allele_cells), runs of equal keys give n,
+//   k_map_vote                     one workgroup per read: keys sorted in LDS (block_bitonic_sort of hs_device.h), runs of equal keys give n,
 //                                  a run and its successor the score, a block maximum under the rule's total order best and second, a second
 //                                  pass over the hits the four extremes. More than HS_MAP_LDS_KEYS hits: on a list for
 //   k_map_vote_wide                the same in a slab of global scratch (always queued; an empty list ends it)
@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "hs_map_host.h"
+#include "hs_device.h"
 
 #define HS_MAP_LDS_KEYS 4096        /* hits of a read whose keys one workgroup sorts in LDS (32 KB) */
 #define HS_MAP_WIDE_BLOCKS 16       /* most workgroups (and slabs) of k_map_vote_wide */
@@ -202,20 +203,11 @@ static __device__ bool map_vote_one(const MapVoteArgs& A, int r, uint64_t* keys,
     const long long n64 = h1 - h0;
     if (n64 > cap) return false;
     const int n = (int)n64;
-    int n_pow2 = 2;
-    while (n_pow2 < n) n_pow2 <<= 1;
+    const int n_pow2 = pow2_at_least(n);
     for (int i = tid; i < n_pow2; i += nt) keys[i] = i < n ? A.hit_key[h0 + i] : ~0ull;
     if (tid < 4) s_ext[tid] = (tid & 1) ? INT32_MIN : INT32_MAX;      // qa_min, qa_max, t_min, t_max
     __syncthreads();
-    for (int k = 2; k <= n_pow2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (n_pow2 >> 1); t += nt) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                const uint64_t a = keys[i], b = keys[l];
-                if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[l] = a; }
-            }
-            __syncthreads();
-        }
+    block_bitonic_sort(keys, n_pow2);
     // first index at or behind `from` whose key is above v
     auto upper = [&](uint64_t v, int from) { int lo = from, hi = n; while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] <= v) lo = mid + 1; else hi = mid; } return lo; };
     auto score = [&](int i) { const uint64_t key = keys[i]; const int e = upper(key, i + 1); return (uint32_t)(upper(key + 1, e) - i); };      // (the run and the run of the next bin lie side by side)
@@ -267,10 +259,7 @@ __global__ __launch_bounds__(256) void k_map_vote(MapVoteArgs A) {
     __shared__ int32_t s_ext[4];
     const int r = (int)blockIdx.x;
     if (r >= A.n_reads) return;
-    if (!map_vote_one(A, r, s_keys, HS_MAP_LDS_KEYS, s_sc, s_key, s_ext) && threadIdx.x == 0) {
-        const int at = atomicAdd(A.wide_count, 1);
-        if (at < A.n_reads) A.wide_list[at] = r;
-    }
+    if (!map_vote_one(A, r, s_keys, HS_MAP_LDS_KEYS, s_sc, s_key, s_ext) && threadIdx.x == 0) wide_list_push(A.wide_count, A.wide_list, A.n_reads, r);
 }
 
 __global__ __launch_bounds__(256) void k_map_vote_wide(MapVoteArgs A, uint64_t* __restrict__ slabs, long long slab_keys) {

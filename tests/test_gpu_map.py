@@ -64,6 +64,31 @@ def test_one_index_serves_many_calls(built):
         assert np.array_equal(whole[f], want[f]) and np.array_equal(np.concatenate([x[f] for x in parts]), want[f]), f
 
 
+def test_an_index_call_waits_twice_and_a_map_call_three_times(built):
+    """a count the code defines (hs_capi_map.inc), no measurement: the minimizer total and the end for an index; the minimizer total, the hit total with
+    the largest read, and the records' one shipment for a map call. A call without a base has no minimizers to wait for."""
+    from hairsplitter_amd import api
+    p, contigs, reads = mc.get("k15_w10")
+    with api.map_index(contigs, _params(api, p)) as ix:      # warm-up: the pools' blocks, the code object
+        api.map_reads(ix, reads)
+    n0 = api.host_waits()
+    with api.map_index(contigs, _params(api, p)) as ix:
+        n1 = api.host_waits()
+        api.map_reads(ix, reads)
+        n2 = api.host_waits()
+        api.map_reads(ix, [])
+        n3 = api.host_waits()
+        api.map_reads(ix, [np.zeros(0, np.uint8), np.zeros(0, np.uint8)])
+        n4 = api.host_waits()
+    assert (n1 - n0, n2 - n1) == (2, 3)
+    assert n3 - n2 <= 3 and n4 - n3 <= 3
+    p, contigs, reads = mc.get("no_reads")
+    with api.map_index(contigs, _params(api, p)) as ix:
+        n5 = api.host_waits()
+        api.map_reads(ix, reads)
+        assert api.host_waits() - n5 <= 3
+
+
 def test_bad_input_is_refused(built):
     from hairsplitter_amd import api
     for bad in (dict(k=4), dict(k=17), dict(w=0), dict(w=33), dict(bucket_bits=27)):
