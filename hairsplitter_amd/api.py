@@ -34,6 +34,7 @@ SYMBOLS = [
     "hs_pipeline_recruits", "hs_pipeline_set_recruit_params",
     "hs_map_params_default", "hs_map_index_create", "hs_map_index_destroy", "hs_map_index_download", "hs_map_reads", "hs_map_result_destroy", "hs_map_lds_capacity",
     "hs_map_to_batch", "hs_map_text", "hs_map_files", "hs_map_main",
+    "hs_map_split_params_default", "hs_map_reads_split", "hs_map_segments_destroy", "hs_map_split_to_batch", "hs_map_segments_text",
 ]
 
 HS_NKERNELS = 28
@@ -124,6 +125,24 @@ class MapResult(C.Structure):
                 ("t_minimizers_ms", C.c_double), ("t_hits_ms", C.c_double), ("t_vote_ms", C.c_double)]
 
 
+class MapSplitParams(C.Structure):
+    """hs_map_split_params"""
+    _fields_ = [(k, C.c_int32) for k in ("max_segments", "min_votes", "min_span", "max_gap")]
+
+
+MAP_SEG_FIELDS = ("read", "contig", "strand", "qstart", "qend", "tstart", "tend", "votes", "second", "round")
+MAP_SEG_READ_FIELDS = ("n_minimizers", "n_skipped", "n_hits", "read_votes", "read_second")
+
+
+class MapSegments(C.Structure):
+    """hs_map_segments"""
+    _fields_ = ([("n_reads", C.c_int32), ("n_segments", C.c_int64), ("seg_off", C.POINTER(C.c_int64))]
+                + [(k, C.POINTER(C.c_uint8 if k == "strand" else C.c_int32)) for k in MAP_SEG_FIELDS]
+                + [(k, C.POINTER(C.c_int64 if k == "n_hits" else C.c_int32)) for k in MAP_SEG_READ_FIELDS]
+                + [("n_wide", C.c_int64), ("total_minimizers", C.c_int64), ("total_hits", C.c_int64),
+                   ("t_minimizers_ms", C.c_double), ("t_hits_ms", C.c_double), ("t_vote_ms", C.c_double)])
+
+
 HS_RECRUIT_ABSENT, HS_RECRUIT_UNCLUSTERED, HS_RECRUIT_LABELLED = 1, 2, 4
 # hs_recruit_row (40 bytes)
 RECRUIT_ROW = np.dtype([("read", "<i4"), ("label", "<i4"), ("best_group", "<i4"), ("second_group", "<i4"), ("m_best", "<u4"), ("x_best", "<u4"),
@@ -212,6 +231,13 @@ def load() -> C.CDLL:
     lib.hs_map_to_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p),
                                     C.POINTER(C.POINTER(RealignRecords)), C.POINTER(C.POINTER(MapResult))]
     lib.hs_map_text.argtypes = [C.POINTER(MapResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
+    lib.hs_map_split_params_default.restype = MapSplitParams
+    lib.hs_map_segments_destroy.restype = None
+    lib.hs_map_segments_destroy.argtypes = [C.POINTER(MapSegments)]
+    lib.hs_map_reads_split.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MapSplitParams), C.POINTER(C.POINTER(MapSegments))]
+    lib.hs_map_split_to_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MapSplitParams),
+                                          C.POINTER(C.c_void_p), C.POINTER(C.POINTER(RealignRecords)), C.POINTER(C.POINTER(MapSegments))]
+    lib.hs_map_segments_text.argtypes = [C.POINTER(MapSegments), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
     _lib = lib
     return lib
 
@@ -2140,3 +2166,86 @@ def map_files(gfa: str, reads: str, out_paf: str, n_threads: int = 0, params: Op
     """hs_map_files: the job's files -> the PAF of the mapped reads (what bin/hs_map writes)"""
     require_gpu()
     _check(load().hs_map_files(gfa.encode(), reads.encode(), out_paf.encode(), C.c_int32(n_threads), C.byref(params) if params is not None else None))
+
+
+# ---- split mappings (hs_map_reads_split): a read's parts on other contigs as further intervals ----
+def map_split_params(**kw) -> MapSplitParams:
+    """hs_map_split_params_default with the given fields replaced"""
+    p = load().hs_map_split_params_default()
+    for k, v in kw.items():
+        if k not in dict(MapSplitParams._fields_):
+            raise HsError("map_split_params: no field " + k)
+        setattr(p, k, int(v))
+    return p
+
+
+def _map_segments_to_dict(g) -> Dict:
+    res = g.contents
+    n, s = int(res.n_reads), int(res.n_segments)
+    out = {k: np.ctypeslib.as_array(getattr(res, k), shape=(s,)).copy() if s else np.zeros(0, np.int64) for k in MAP_SEG_FIELDS}
+    out.update({k: np.ctypeslib.as_array(getattr(res, k), shape=(n,)).copy() if n else np.zeros(0, np.int64) for k in MAP_SEG_READ_FIELDS})
+    out["seg_off"] = np.ctypeslib.as_array(res.seg_off, shape=(n + 1,)).copy()
+    for k in ("n_wide", "total_minimizers", "total_hits"):
+        out[k] = int(getattr(res, k))
+    for k in ("t_minimizers_ms", "t_hits_ms", "t_vote_ms"):
+        out[k] = float(getattr(res, k))
+    return out
+
+
+def map_reads_split(index: MapIndex, reads, split: Optional[MapSplitParams] = None) -> Dict:
+    """hs_map_reads_split: seg_off [n_reads + 1]; per segment read, contig, strand, qstart, qend, tstart, tend, votes, second, round; per read n_minimizers,
+    n_skipped, n_hits, read_votes, read_second; per call n_wide. reads: a list of code arrays, or a (codes, offsets) pair."""
+    lib = load()
+    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
+    g = C.POINTER(MapSegments)()
+    _check(lib.hs_map_reads_split(index._h, rseq.ctypes.data, roff.ctypes.data, C.c_int32(len(roff) - 1), C.byref(split) if split is not None else None, C.byref(g)))
+    try:
+        return _map_segments_to_dict(g)
+    finally:
+        lib.hs_map_segments_destroy(g)
+
+
+def map_segment_intervals(res: Dict) -> np.ndarray:
+    """the segments as the rows realign_intervals takes: (read, contig, strand, qstart, qend, tstart, tend)"""
+    return np.stack([np.asarray(res[k], np.int64) for k in MAP_SEG_FIELDS[:7]], axis=1).reshape(-1, 7)
+
+
+def map_split_to_batch(index: MapIndex, reads, split: Optional[MapSplitParams] = None, pad: int = 100):
+    """hs_map_split_to_batch: map_reads_split, then realign_intervals with interval i = segment i. Returns (CvBatch, records dict, segments dict)."""
+    import time
+    lib = load()
+    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
+    h = C.c_void_p(); rec = C.POINTER(RealignRecords)(); g = C.POINTER(MapSegments)()
+    t0 = time.perf_counter()
+    _check(lib.hs_map_split_to_batch(index._h, index.contig_seq.ctypes.data, index.contig_off.ctypes.data, C.c_int32(len(index.contig_off) - 1), rseq.ctypes.data, roff.ctypes.data,
+                                     C.c_int32(len(roff) - 1), C.c_int32(pad), C.byref(split) if split is not None else None, C.byref(h), C.byref(rec), C.byref(g)))
+    dt = time.perf_counter() - t0
+    try:
+        records = _realign_records_to_dict(rec)
+        res = _map_segments_to_dict(g)
+    finally:
+        lib.hs_realign_records_destroy(rec)
+        lib.hs_map_segments_destroy(g)
+    return CvBatch._adopt(h, dt, records), records, res
+
+
+def map_segments_text(res: Dict, read_lengths, contig_lengths, read_names=None, contig_names=None) -> str:
+    """hs_map_segments_text: one PAF line per segment of a map_reads_split result"""
+    lib = load()
+    keep = {k: _np(res[k], np.uint8 if k == "strand" else np.int32) for k in MAP_SEG_FIELDS}
+    seg_off = _np(res["seg_off"], np.int64)
+    g = MapSegments()
+    g.n_reads, g.n_segments = len(seg_off) - 1, len(keep["read"])
+    g.seg_off = seg_off.ctypes.data_as(C.POINTER(C.c_int64))
+    for k, a in keep.items():
+        setattr(g, k, a.ctypes.data_as(C.POINTER(C.c_uint8 if k == "strand" else C.c_int32)))
+    roff = np.zeros(len(seg_off), np.int64); np.cumsum(_np(read_lengths, np.int64), out=roff[1:])
+    coff = np.zeros(len(contig_lengths) + 1, np.int64); np.cumsum(_np(contig_lengths, np.int64), out=coff[1:])
+    names = lambda v: (C.c_char_p * len(v))(*[x.encode() for x in v]) if v is not None else None
+    rn, cn = names(read_names), names(contig_names)
+    text = C.c_char_p()
+    _check(lib.hs_map_segments_text(C.byref(g), rn, roff.ctypes.data, cn, coff.ctypes.data, C.c_int32(len(contig_lengths)), C.byref(text)))
+    try:
+        return text.value.decode()
+    finally:
+        lib.hs_free_host(text)

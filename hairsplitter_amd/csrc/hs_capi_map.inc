@@ -1,7 +1,8 @@
 // hs_capi_map.inc -- part of hs_capi.hip: the read mapper (include/hairsplitter_hip.h: hs_map_index_create, hs_map_reads, hs_map_to_batch). Kernels
 // in hs_kernels_map.hip, the rule and the host half in hs_map_host.h / hs_map_host.cpp. An index call waits twice (the number of minimizers, which
 // sizes the entries; the end), a map call three times (the minimizers, then the hits -- each total sizes what follows --, then the records: one
-// block, one shipment). Sequences go up by the runtime's upload_pageable. Launches are accounted under HS_K_OTHER.
+// block, one shipment). A split call (hs_map_reads_split) waits three times as well: its segments are compacted on the device and leave in the same
+// shipment, their number read there. Sequences go up by the runtime's upload_pageable. Launches are accounted under HS_K_OTHER.
 struct hs_map_index {
     hs_map_params params{};
     int32_t n_contigs = 0, bucket_bits = 0;
@@ -53,17 +54,27 @@ struct MapMinimizersDev {
 // The parts of a map call's output block: the per-read records under the names hs_map_result gives them, then what a call clears -- n_skipped,
 // the wide route's counter, the word of the largest read -- side by side (one clearing). Up to `shipped` the block goes to the host in one
 // shipment and lands there at the same offsets; behind it lies the wide route's list [R].
+// A split call (hs_map_reads_split) has no per-read records: in their place round 0's vote per read (votes, second -- cleared with the rest, a read
+// without a hit keeps the zeros) and, behind the shipped part, the segment count of every read (cleared too). Its segments lie in blocks of their own.
 struct MapWork {
     int64_t contig, strand, qstart, qend, tstart, tend, votes, second, n_minimizers, n_hits, n_skipped, wide_count, max_hits, shipped, wide_list, total_bytes;
+    int64_t clear_from, clear_to, seg_count;
 };
-static MapWork map_work(int32_t n_reads) {
+static MapWork map_work(int32_t n_reads, bool split = false) {
     const int64_t R = n_reads;
-    MapWork m;
+    MapWork m{};
     WorkParts p;
-    m.contig = p.take(R * 4); m.strand = p.take(R); m.qstart = p.take(R * 4); m.qend = p.take(R * 4); m.tstart = p.take(R * 4); m.tend = p.take(R * 4);
-    m.votes = p.take(R * 4); m.second = p.take(R * 4); m.n_minimizers = p.take(R * 4); m.n_hits = p.take(R * 8);
+    if (!split) {
+        m.contig = p.take(R * 4); m.strand = p.take(R); m.qstart = p.take(R * 4); m.qend = p.take(R * 4); m.tstart = p.take(R * 4); m.tend = p.take(R * 4);
+        m.votes = p.take(R * 4); m.second = p.take(R * 4);
+    }
+    m.n_minimizers = p.take(R * 4); m.n_hits = p.take(R * 8);
+    m.clear_from = p.o;
+    if (split) { m.votes = p.take(R * 4); m.second = p.take(R * 4); }
     m.n_skipped = p.take(R * 4); m.wide_count = p.take(4); m.max_hits = p.take(16);
     m.shipped = p.o;
+    if (split) m.seg_count = p.take(R * 4);
+    m.clear_to = p.o;
     m.wide_list = p.take(R * 4);
     m.total_bytes = p.o;
     return m;
@@ -141,13 +152,18 @@ int hs_map_index_download(const hs_map_index* index, int64_t* n_entries, int32_t
     return HS_OK;
 }
 
-int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, hs_map_result** result) {
+// hs_map_reads (split NULL: *result) and hs_map_reads_split (*segments): the same minimizers and hits; then one record per read, or the rounds of
+// the split rule and the segments' compaction on the device. Either way three waits: the segments leave in the same shipment as the per-read block,
+// their number read on the device when the shipment runs (the host block has room for max_segments per read).
+static int map_reads_impl(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, const hs_map_split_params* split, hs_map_result** result,
+                          hs_map_segments** segments, const std::string& who) {
     if (int rc = require_device()) return rc;
-    if (!index || !result || !h_read_off || n_reads < 0) { set_error("hs_map_reads: bad arguments"); return HS_EINVAL; }
-    *result = nullptr;
-    if (int rc = map_check_offsets(h_read_off, n_reads, "hs_map_reads")) return rc;
+    if (!index || (split ? !segments : !result) || !h_read_off || n_reads < 0) { set_error(who + ": bad arguments"); return HS_EINVAL; }
+    if (split) *segments = nullptr; else *result = nullptr;
+    if (split && !hs::map_split_params_valid(*split)) { set_error(who + ": split parameters out of range (max_segments 1..8, min_votes >= 1, min_span >= 0, max_gap >= 0)"); return HS_EINVAL; }
+    if (int rc = map_check_offsets(h_read_off, n_reads, who.c_str())) return rc;
     const int64_t total = h_read_off[n_reads];
-    if (total > 0 && !h_read_seq) { set_error("hs_map_reads: bad arguments"); return HS_EINVAL; }
+    if (total > 0 && !h_read_seq) { set_error(who + ": bad arguments"); return HS_EINVAL; }
     try {
         const hs_map_params& prm = index->params;
         const hipStream_t st = nullptr;
@@ -155,7 +171,7 @@ int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int
         KernelClock kc;
         EventPair ev_mz, ev_hits, ev_vote;
         for (EventPair* e : {&ev_mz, &ev_hits, &ev_vote}) if (int rc = e->init()) return rc;
-        DBuf d_seq, d_off, d_mz_off, d_cnt, d_hit_off, d_scan, d_key, d_qa, d_t, d_slabs, d_out;
+        DBuf d_seq, d_off, d_mz_off, d_cnt, d_hit_off, d_scan, d_key, d_qa, d_t, d_slabs, d_out, d_seg_off, d_staged, d_segs;
         if (int rc = upload_pageable(d_seq, h_read_seq, (size_t)total, 0, MAP_SLACK)) return rc;
         if (int rc = upload_pageable(d_off, h_read_off, (R + 1) * 8, 0, MAP_SLACK)) return rc;
         // ---- minimizers and every read's range of them (one wait: their total) ----
@@ -164,14 +180,14 @@ int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int
         if (int rc = timed_launch(kc, ev_mz, st, mz_bytes, [&]() -> int {
                 if (int rc = mz.run(d_seq.as<uint8_t>(), d_off.as<int64_t>(), n_reads, total, prm, st)) return rc;
                 mz_bytes += 12 * mz.n;
-                if (mz.n > 0x7fffffff - HS_SCAN_TILE) { set_error("hs_map_reads: more than 2^31 read minimizers in one call: map the reads in several calls"); return HS_EINVAL; }
+                if (mz.n > 0x7fffffff - HS_SCAN_TILE) { set_error(who + ": more than 2^31 read minimizers in one call: map the reads in several calls"); return HS_EINVAL; }
                 if (int rc = d_mz_off.alloc((R + 1) * 8)) return rc;
                 hipLaunchKernelGGL(hsdev::k_map_seq_ranges, dim3((unsigned)(R / 256 + 1)), dim3(256), 0, st, mz.seq.as<int32_t>(), (long long)mz.n, n_reads, d_mz_off.as<int64_t>());
                 HS_HIP(hipGetLastError());
                 return HS_OK; })) return rc;
         const int64_t M = mz.n;
         // ---- occ of every minimizer, the hits' offsets, (one wait: their total and the most a read has), the hits ----
-        const MapWork w = map_work(n_reads);
+        const MapWork w = map_work(n_reads, split != nullptr);
         if (int rc = d_out.alloc((size_t)w.total_bytes)) return rc;
         char* out = (char*)d_out.p;
         if (int rc = d_cnt.alloc((size_t)std::max<int64_t>(M, 1) * 4)) return rc;
@@ -180,7 +196,7 @@ int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int
                              (uint32_t)(((int64_t)1 << index->bucket_bits) - 1), (long long)index->n_entries, index->d_contig_off.as<int64_t>(), index->n_contigs};
         int64_t H = 0, max_hits = 0, hit_bytes = 8 * M;
         if (int rc = timed_launch(kc, ev_hits, st, hit_bytes, [&]() -> int {
-                HS_HIP(hipMemsetAsync(out + w.n_skipped, 0, (size_t)(w.shipped - w.n_skipped), st));      // (n_skipped, the wide counter, the largest read)
+                HS_HIP(hipMemsetAsync(out + w.clear_from, 0, (size_t)(w.clear_to - w.clear_from), st));      // (n_skipped, the wide counter, the largest read; a split call's vote and counts)
                 const unsigned grid_m = (unsigned)((M + 255) / 256);
                 if (M > 0) hipLaunchKernelGGL(hsdev::k_map_hits_count, dim3(grid_m), dim3(256), 0, st, X, mz.h.as<uint32_t>(), mz.seq.as<int32_t>(), (long long)M, n_reads, prm.max_occ,
                                               d_cnt.as<int32_t>(), (int32_t*)(out + w.n_skipped));
@@ -190,8 +206,8 @@ int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int
                 HS_HIP(hipGetLastError());
                 HS_HIP(HS_COPY_ASYNC(&max_hits, out + w.max_hits, 8, hipMemcpyDeviceToHost, st));
                 if (int rc = copy_d2h(&H, d_hit_off.as<int64_t>() + M, 8, st)) return rc;
-                if (H < 0 || max_hits < 0 || max_hits > H) { set_error("hs_map_reads: the device's hit counts do not fit the minimizers"); return HS_EHIP; }
-                if (max_hits > ((int64_t)1 << 28)) { set_error("hs_map_reads: a read with more than 2^28 hits: lower max_occ"); return HS_EINVAL; }
+                if (H < 0 || max_hits < 0 || max_hits > H) { set_error(who + ": the device's hit counts do not fit the minimizers"); return HS_EHIP; }
+                if (max_hits > ((int64_t)1 << 28)) { set_error(who + ": a read with more than 2^28 hits: lower max_occ"); return HS_EINVAL; }
                 hit_bytes += 2 * 16 * H;
                 if (int rc = d_key.alloc((size_t)std::max<int64_t>(H, 1) * 8)) return rc;
                 if (int rc = d_qa.alloc((size_t)std::max<int64_t>(H, 1) * 4)) return rc;
@@ -208,22 +224,87 @@ int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int
         hsdev::MapVoteArgs A{};
         A.mz_off = d_mz_off.as<int64_t>(); A.hit_off = d_hit_off.as<int64_t>(); A.hit_key = d_key.as<uint64_t>(); A.hit_qa = d_qa.as<int32_t>(); A.hit_t = d_t.as<int32_t>(); A.n_hits = H;
         A.read_off = d_off.as<int64_t>(); A.contig_off = index->d_contig_off.as<int64_t>(); A.n_contigs = index->n_contigs; A.n_reads = n_reads; A.P = prm;
-        A.contig = (int32_t*)(out + w.contig); A.strand = (uint8_t*)(out + w.strand); A.qstart = (int32_t*)(out + w.qstart); A.qend = (int32_t*)(out + w.qend);
-        A.tstart = (int32_t*)(out + w.tstart); A.tend = (int32_t*)(out + w.tend); A.votes = (int32_t*)(out + w.votes); A.second = (int32_t*)(out + w.second);
+        if (!split) {      // (a split call's block has no per-read records: the six stay null)
+            A.contig = (int32_t*)(out + w.contig); A.strand = (uint8_t*)(out + w.strand); A.qstart = (int32_t*)(out + w.qstart); A.qend = (int32_t*)(out + w.qend);
+            A.tstart = (int32_t*)(out + w.tstart); A.tend = (int32_t*)(out + w.tend);
+        }
+        A.votes = (int32_t*)(out + w.votes); A.second = (int32_t*)(out + w.second);
         A.wide_list = (int32_t*)(out + w.wide_list); A.wide_count = (int32_t*)(out + w.wide_count);
+        // a split call: the rounds per read into a staging of max_segments per read, the counts' scan, the compaction
+        const int64_t seg_cap = split ? (int64_t)R * split->max_segments : 0;
+        const size_t seg_bytes = (size_t)HS_MAP_SEG_WORDS * 4;
+        hsdev::MapSplitArgs B{};
+        if (split) {
+            if (int rc = d_seg_off.alloc((R + 1) * 8)) return rc;
+            if (int rc = d_staged.alloc((size_t)std::max<int64_t>(seg_cap, 1) * seg_bytes)) return rc;
+            if (int rc = d_segs.alloc((size_t)std::max<int64_t>(seg_cap, 1) * seg_bytes + MAP_SLACK)) return rc;
+            B.S = *split; B.seg_count = (int32_t*)(out + w.seg_count); B.staged = d_staged.as<int32_t>(); B.read_votes = A.votes; B.read_second = A.second;
+        }
         if (int rc = timed_launch(kc, ev_vote, st, 2 * 16 * H + 30 * (int64_t)R, [&]() -> int {
-                if (R) hipLaunchKernelGGL(hsdev::k_map_vote, dim3((unsigned)R), dim3(256), 0, st, A);
-                hipLaunchKernelGGL(hsdev::k_map_vote_wide, dim3((unsigned)wide_blocks), dim3(256), 0, st, A, d_slabs.as<uint64_t>(), (long long)slab_keys);
+                if (!split) {
+                    if (R) hipLaunchKernelGGL(hsdev::k_map_vote, dim3((unsigned)R), dim3(256), 0, st, A);
+                    hipLaunchKernelGGL(hsdev::k_map_vote_wide, dim3((unsigned)wide_blocks), dim3(256), 0, st, A, d_slabs.as<uint64_t>(), (long long)slab_keys);
+                    HS_HIP(hipGetLastError());
+                    return HS_OK;
+                }
+                if (R) hipLaunchKernelGGL(hsdev::k_map_vote_split, dim3((unsigned)R), dim3(256), 0, st, A, B);
+                hipLaunchKernelGGL(hsdev::k_map_vote_split_wide, dim3((unsigned)wide_blocks), dim3(256), 0, st, A, B, d_slabs.as<uint64_t>(), (long long)slab_keys);
+                HS_HIP(hipGetLastError());
+                if (int rc = exclusive_scan_launch(B.seg_count, n_reads, d_seg_off.as<int64_t>(), d_scan, st)) return rc;
+                if (seg_cap > 0) hipLaunchKernelGGL(hsdev::k_map_seg_compact, dim3((unsigned)((seg_cap + 255) / 256)), dim3(256), 0, st, B.seg_count, d_seg_off.as<int64_t>(),
+                                                    d_staged.as<int32_t>(), n_reads, split->max_segments, (long long)seg_cap, d_segs.as<int32_t>());
                 HS_HIP(hipGetLastError());
                 return HS_OK; })) return rc;
         // ---- the records: one shipment to one pinned block (one wait), the result's arrays filled from it ----
-        HBuf h_out;
+        HBuf h_out, h_seg_off, h_segs;
         if (int rc = h_out.alloc((size_t)w.shipped)) return rc;
         Shipment sh;
         sh.add(h_out.p, out, (size_t)w.shipped);
+        if (split) {
+            if (int rc = h_seg_off.alloc((R + 1) * 8 + 16)) return rc;
+            if (int rc = h_segs.alloc((size_t)std::max<int64_t>(seg_cap, 1) * seg_bytes + MAP_SLACK)) return rc;
+            sh.add(h_seg_off.p, d_seg_off.p, (R + 1) * 8);
+            if (seg_cap > 0) sh.add_counted(h_segs.p, d_segs.p, (const long long*)(d_seg_off.as<int64_t>() + R), seg_bytes, (long long)seg_cap);
+        }
         if (int rc = sh.launch(st)) return rc;
         if (int rc = stream_wait(st)) return rc;
         const char* hp = (const char*)h_out.p;
+        if (split) {
+            const int64_t* so = (const int64_t*)h_seg_off.p;
+            const int64_t S = so[R];
+            bool ok = so[0] == 0 && S >= 0 && S <= seg_cap;
+            for (size_t i = 0; ok && i < R; ++i) ok = so[i + 1] >= so[i] && so[i + 1] - so[i] <= split->max_segments;
+            if (!ok) { set_error(who + ": the device's segment counts do not fit the reads"); return HS_EHIP; }
+            hs_map_segments* g = (hs_map_segments*)std::calloc(1, sizeof(hs_map_segments));
+            if (!g) { set_error(who + ": out of memory"); return HS_EINVAL; }
+            g->n_reads = n_reads; g->n_segments = S;
+            bool oom = false;
+            auto room = [&](auto*& dst, size_t n) { dst = (decltype(+dst))std::calloc(std::max<size_t>(1, n), sizeof *dst); if (!dst) oom = true; };
+            room(g->seg_off, R + 1);
+            for (int32_t** a : {&g->read, &g->contig, &g->qstart, &g->qend, &g->tstart, &g->tend, &g->votes, &g->second, &g->round}) room(*a, (size_t)S);
+            room(g->strand, (size_t)S);
+            for (int32_t** a : {&g->n_minimizers, &g->n_skipped, &g->read_votes, &g->read_second}) room(*a, R);
+            room(g->n_hits, R);
+            if (oom) { hs_map_segments_destroy(g); set_error(who + ": out of memory"); return HS_EINVAL; }
+            std::memcpy(g->seg_off, so, (R + 1) * 8);
+            const int32_t* rec = (const int32_t*)h_segs.p;
+            for (int64_t i = 0; i < S; ++i, rec += HS_MAP_SEG_WORDS) {
+                g->read[i] = rec[0]; g->contig[i] = rec[1]; g->strand[i] = (uint8_t)rec[2]; g->qstart[i] = rec[3]; g->qend[i] = rec[4]; g->tstart[i] = rec[5]; g->tend[i] = rec[6];
+                g->votes[i] = rec[7]; g->second[i] = rec[8]; g->round[i] = rec[9];
+            }
+            if (R) {
+                std::memcpy(g->n_minimizers, hp + w.n_minimizers, R * 4); std::memcpy(g->n_skipped, hp + w.n_skipped, R * 4); std::memcpy(g->n_hits, hp + w.n_hits, R * 8);
+                std::memcpy(g->read_votes, hp + w.votes, R * 4); std::memcpy(g->read_second, hp + w.second, R * 4);
+            }
+            g->n_wide = *(const int32_t*)(hp + w.wide_count); g->total_minimizers = M; g->total_hits = H;
+            float ms = 0;
+            if (ev_mz.ms(&ms) == HS_OK) g->t_minimizers_ms = ms;
+            if (ev_hits.ms(&ms) == HS_OK) g->t_hits_ms = ms;
+            if (ev_vote.ms(&ms) == HS_OK) g->t_vote_ms = ms;
+            kc.flush();
+            *segments = g;
+            return HS_OK;
+        }
         hs_map_result* r = (hs_map_result*)std::calloc(1, sizeof(hs_map_result));
         if (!r) { set_error("hs_map_reads: out of memory"); return HS_EINVAL; }
         r->n_reads = n_reads;
@@ -243,7 +324,16 @@ int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int
         kc.flush();
         *result = r;
         return HS_OK;
-    } catch (const std::exception& e) { set_error(std::string("hs_map_reads: ") + e.what()); return HS_EINVAL; }
+    } catch (const std::exception& e) { set_error(who + ": " + e.what()); return HS_EINVAL; }
+}
+
+int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, hs_map_result** result) {
+    return map_reads_impl(index, h_read_seq, h_read_off, n_reads, nullptr, result, nullptr, "hs_map_reads");
+}
+
+int hs_map_reads_split(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, const hs_map_split_params* split, hs_map_segments** segments) {
+    const hs_map_split_params sp = split ? *split : hs_map_split_params_default();
+    return map_reads_impl(index, h_read_seq, h_read_off, n_reads, &sp, nullptr, segments, "hs_map_reads_split");
 }
 
 int hs_map_to_batch(const hs_map_index* index, const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off,
@@ -273,7 +363,36 @@ int hs_map_to_batch(const hs_map_index* index, const uint8_t* h_contig_seq, cons
     } catch (const std::exception& e) { hs_map_result_destroy(mr); set_error(std::string("hs_map_to_batch: ") + e.what()); return HS_EINVAL; }
 }
 
-// the job's files -> PAF lines of the mapped reads. An assembly that holds no S line and begins with '>' is read as FASTA.
+int hs_map_split_to_batch(const hs_map_index* index, const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off,
+                          int32_t n_reads, int32_t pad, const hs_map_split_params* split, hs_cv_batch** batch, hs_realign_records** records, hs_map_segments** segments) {
+    if (int rc = require_device()) return rc;
+    if (!index || !batch || !h_contig_off || n_contigs != index->n_contigs) { set_error("hs_map_split_to_batch: bad arguments (the contigs are the index's)"); return HS_EINVAL; }
+    *batch = nullptr;
+    if (records) *records = nullptr;
+    if (segments) *segments = nullptr;
+    hs_map_segments* sg = nullptr;
+    if (int rc = hs_map_reads_split(index, h_read_seq, h_read_off, n_reads, split, &sg)) return rc;
+    if (sg->n_segments > 0x7fffffff) { hs_map_segments_destroy(sg); set_error("hs_map_split_to_batch: more than 2^31 segments in one call: map the reads in several calls"); return HS_EINVAL; }
+    hs_realign_records* rec = nullptr;
+    const int rc = hs_realign_intervals(h_contig_seq, h_contig_off, n_contigs, h_read_seq, h_read_off, n_reads, sg->read, sg->contig, sg->strand, sg->qstart, sg->qend, sg->tstart, sg->tend,
+                                        (int32_t)sg->n_segments, pad, &rec, batch);
+    if (rc) { hs_map_segments_destroy(sg); return rc; }
+    if (records) *records = rec; else hs_realign_records_destroy(rec);
+    if (segments) *segments = sg; else hs_map_segments_destroy(sg);
+    return HS_OK;
+}
+
+// HS_MAP_SPLIT=<n>, n 2..8: hs_map_files writes the segment lines of hs_map_reads_split with max_segments = n. Unset, empty or 1: 0, the plain lines;
+// anything else: the plain lines too, and a line on stderr that says so
+static int map_split_from_env() {
+    const char* e = std::getenv("HS_MAP_SPLIT");
+    if (!e || !e[0] || (e[0] == '1' && !e[1])) return 0;
+    if (!e[1] && e[0] >= '2' && e[0] <= '8') return e[0] - '0';
+    std::fprintf(stderr, "hs_map: HS_MAP_SPLIT=%s is not one of 1..8: ignored, one line per mapped read is written\n", e);
+    return 0;
+}
+
+// the job's files -> PAF lines of the mapped reads (HS_MAP_SPLIT: of their segments). An assembly that holds no S line and begins with '>' is read as FASTA.
 int hs_map_files(const char* gfa, const char* reads, const char* out_paf, int32_t n_threads, const hs_map_params* params) {
     if (int rc = require_device()) return rc;
     if (!gfa || !reads || !out_paf) { set_error("hs_map_files: null argument"); return HS_EINVAL; }
@@ -286,21 +405,39 @@ int hs_map_files(const char* gfa, const char* reads, const char* out_paf, int32_
         const int32_t C = (int32_t)seqs.contig_names.size(), R = (int32_t)seqs.read_names.size();
         hs_map_index* ix = nullptr;
         if (int rc = hs_map_index_create(seqs.contig_seq.data(), seqs.contig_off.data(), C, params, &ix)) return rc;
-        hs_map_result* res = nullptr;
-        const int rc = hs_map_reads(ix, seqs.read_seq.data(), seqs.read_off.data(), R, &res);
-        hs_map_index_destroy(ix);
-        if (rc) return rc;
         std::vector<const char*> rn((size_t)R), cn((size_t)C);
         for (int32_t i = 0; i < R; ++i) rn[(size_t)i] = seqs.read_names[(size_t)i].c_str();
         for (int32_t i = 0; i < C; ++i) cn[(size_t)i] = seqs.contig_names[(size_t)i].c_str();
+        const bool timing = std::getenv("HS_TIMING") != nullptr;
         char* text = nullptr;
-        const int rc2 = hs_map_text(res, rn.data(), seqs.read_off.data(), cn.data(), seqs.contig_off.data(), C, &text);
-        int64_t n_mapped = 0;
-        for (int32_t i = 0; i < R; ++i) n_mapped += res->contig[i] >= 0;
-        if (std::getenv("HS_TIMING")) std::fprintf(stderr, "[hs timing] map: %ld of %d reads mapped, %ld minimizers, %ld hits, %ld reads through the scratch route, kernels %.2f + %.2f + %.2f ms\n",
-                                                   (long)n_mapped, R, (long)res->total_minimizers, (long)res->total_hits, (long)res->n_wide, res->t_minimizers_ms, res->t_hits_ms, res->t_vote_ms);
-        hs_map_result_destroy(res);
-        if (rc2) { set_error("hs_map_files: out of memory"); return rc2; }
+        int rc_text = HS_OK;
+        if (const int n_split = map_split_from_env()) {
+            hs_map_split_params sp = hs_map_split_params_default();
+            sp.max_segments = n_split;
+            hs_map_segments* sg = nullptr;
+            const int rc = hs_map_reads_split(ix, seqs.read_seq.data(), seqs.read_off.data(), R, &sp, &sg);
+            hs_map_index_destroy(ix);
+            if (rc) return rc;
+            rc_text = hs_map_segments_text(sg, rn.data(), seqs.read_off.data(), cn.data(), seqs.contig_off.data(), C, &text);
+            int64_t n_mapped = 0, n_multi = 0;
+            for (int32_t i = 0; i < R; ++i) { n_mapped += sg->seg_off[i + 1] > sg->seg_off[i]; n_multi += sg->seg_off[i + 1] - sg->seg_off[i] > 1; }
+            if (timing) std::fprintf(stderr, "[hs timing] map: %ld of %d reads mapped, %ld of them in more than one segment (%ld segments), %ld minimizers, %ld hits, %ld reads through the scratch route, kernels %.2f + %.2f + %.2f ms\n",
+                                     (long)n_mapped, R, (long)n_multi, (long)sg->n_segments, (long)sg->total_minimizers, (long)sg->total_hits, (long)sg->n_wide, sg->t_minimizers_ms, sg->t_hits_ms,
+                                     sg->t_vote_ms);
+            hs_map_segments_destroy(sg);
+        } else {
+            hs_map_result* res = nullptr;
+            const int rc = hs_map_reads(ix, seqs.read_seq.data(), seqs.read_off.data(), R, &res);
+            hs_map_index_destroy(ix);
+            if (rc) return rc;
+            rc_text = hs_map_text(res, rn.data(), seqs.read_off.data(), cn.data(), seqs.contig_off.data(), C, &text);
+            int64_t n_mapped = 0;
+            for (int32_t i = 0; i < R; ++i) n_mapped += res->contig[i] >= 0;
+            if (timing) std::fprintf(stderr, "[hs timing] map: %ld of %d reads mapped, %ld minimizers, %ld hits, %ld reads through the scratch route, kernels %.2f + %.2f + %.2f ms\n",
+                                     (long)n_mapped, R, (long)res->total_minimizers, (long)res->total_hits, (long)res->n_wide, res->t_minimizers_ms, res->t_hits_ms, res->t_vote_ms);
+            hs_map_result_destroy(res);
+        }
+        if (rc_text) { set_error("hs_map_files: out of memory"); return rc_text; }
         std::ofstream o(out_paf);
         o << text;
         std::free(text);

@@ -14,6 +14,10 @@
 //                                  a run and its successor the score, a block maximum under the rule's total order best and second, a second
 //                                  pass over the hits the four extremes. More than HS_MAP_LDS_KEYS hits: on a list for
 //   k_map_vote_wide                the same in a slab of global scratch (always queued; an empty list ends it)
+//   k_map_vote_split / _split_wide the opt-in split form, the same arrangement: up to max_segments rounds per read, each the vote over the hits that
+//                                  overlap no seed span taken so far (spans and gap counters in LDS, the free hits' keys compacted by a ballot
+//                                  prefix and an LDS cursor, only that many sorted); a round without a free hit costs one pass over the hits
+//   k_map_seg_compact              the reads' staged segments side by side (behind exclusive_scan_launch over their counts)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -195,6 +199,36 @@ static __device__ void map_block_best(uint32_t& sc, uint64_t& key, uint32_t* s_s
     __syncthreads();
 }
 
+// the vote over keys[0, n), which lie padded with all ones to n_pow2 behind a __syncthreads(): sorted here; best and its key, and `second` where it is
+// asked for. Every thread calls it and gets the result. The one vote of k_map_vote and of every round of k_map_vote_split.
+static __device__ void map_vote_keys(uint64_t* keys, int n, int n_pow2, bool want_second, hs::MapVote& v, uint32_t* s_sc, uint64_t* s_key) {
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+    block_bitonic_sort(keys, n_pow2);
+    // first index at or behind `from` whose key is above v
+    auto upper = [&](uint64_t v, int from) { int lo = from, hi = n; while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] <= v) lo = mid + 1; else hi = mid; } return lo; };
+    auto score = [&](int i) { const uint64_t key = keys[i]; const int e = upper(key, i + 1); return (uint32_t)(upper(key + 1, e) - i); };      // (the run and the run of the next bin lie side by side)
+    {
+        uint32_t sc = 0; uint64_t key = 0;
+        for (int i = tid; i < n; i += nt) {
+            if (i && keys[i] == keys[i - 1]) continue;
+            const uint32_t s = score(i);
+            if (sc == 0 || hs::map_beats(s, keys[i], sc, key)) { sc = s; key = keys[i]; }
+        }
+        map_block_best(sc, key, s_sc, s_key);
+        v.best = sc; v.key = key;
+    }
+    if (v.best && want_second) {
+        uint32_t sc = 0; uint64_t key = 0;
+        for (int i = tid; i < n; i += nt) {
+            if ((i && keys[i] == keys[i - 1]) || !hs::map_second_allowed(keys[i], v.key)) continue;
+            const uint32_t s = score(i);
+            if (s > sc) { sc = s; key = keys[i]; }
+        }
+        map_block_best(sc, key, s_sc, s_key);
+        v.second = sc;
+    }
+}
+
 // one read, by whichever kernel owns it (256 threads); false: more hits than `cap` keys -- not this route's
 static __device__ bool map_vote_one(const MapVoteArgs& A, int r, uint64_t* keys, long long cap, uint32_t* s_sc, uint64_t* s_key, int32_t* s_ext) {
     const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
@@ -207,30 +241,9 @@ static __device__ bool map_vote_one(const MapVoteArgs& A, int r, uint64_t* keys,
     for (int i = tid; i < n_pow2; i += nt) keys[i] = i < n ? A.hit_key[h0 + i] : ~0ull;
     if (tid < 4) s_ext[tid] = (tid & 1) ? INT32_MIN : INT32_MAX;      // qa_min, qa_max, t_min, t_max
     __syncthreads();
-    block_bitonic_sort(keys, n_pow2);
-    // first index at or behind `from` whose key is above v
-    auto upper = [&](uint64_t v, int from) { int lo = from, hi = n; while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] <= v) lo = mid + 1; else hi = mid; } return lo; };
-    auto score = [&](int i) { const uint64_t key = keys[i]; const int e = upper(key, i + 1); return (uint32_t)(upper(key + 1, e) - i); };      // (the run and the run of the next bin lie side by side)
     hs::MapVote v;
-    {
-        uint32_t sc = 0; uint64_t key = 0;
-        for (int i = tid; i < n; i += nt) {
-            if (i && keys[i] == keys[i - 1]) continue;
-            const uint32_t s = score(i);
-            if (sc == 0 || hs::map_beats(s, keys[i], sc, key)) { sc = s; key = keys[i]; }
-        }
-        map_block_best(sc, key, s_sc, s_key);
-        v.best = sc; v.key = key;
-    }
+    map_vote_keys(keys, n, n_pow2, true, v, s_sc, s_key);
     if (v.best) {
-        uint32_t sc = 0; uint64_t key = 0;
-        for (int i = tid; i < n; i += nt) {
-            if ((i && keys[i] == keys[i - 1]) || !hs::map_second_allowed(keys[i], v.key)) continue;
-            const uint32_t s = score(i);
-            if (s > sc) { sc = s; key = keys[i]; }
-        }
-        map_block_best(sc, key, s_sc, s_key);
-        v.second = sc;
         int qa_min = INT32_MAX, qa_max = INT32_MIN, t_min = INT32_MAX, t_max = INT32_MIN;
         for (int i = tid; i < n; i += nt) {
             if (!hs::map_in_best(A.hit_key[h0 + i], v.key)) continue;
@@ -269,6 +282,157 @@ __global__ __launch_bounds__(256) void k_map_vote_wide(MapVoteArgs A, uint64_t* 
     const int n = min(*A.wide_count, A.n_reads);
     uint64_t* keys = slabs + (size_t)blockIdx.x * (size_t)slab_keys;
     for (int i = (int)blockIdx.x; i < n; i += (int)gridDim.x) (void)map_vote_one(A, A.wide_list[i], keys, slab_keys, s_sc, s_key, s_ext);
+}
+
+// ---- split mappings (hs_map_host.h, "split mappings"): the vote repeated over the hits that overlap no seed span taken so far ----
+#define HS_MAP_SEG_WORDS 10        /* a segment as it leaves: read contig strand qstart qend tstart tend votes second round */
+struct MapSplitArgs {
+    hs_map_split_params S;
+    int32_t* seg_count;            // [n_reads]: segments of every read
+    int32_t* staged;               // [n_reads * S.max_segments] segments of HS_MAP_SEG_WORDS words, a read's side by side in span order
+    int32_t* read_votes; int32_t* read_second;      // round 0's vote (cleared before the launch: a read without a hit keeps the zeros)
+};
+struct MapSplitShared {
+    int32_t a0[HS_MAP_MAX_SEGMENTS], a1[HS_MAP_MAX_SEGMENTS];      // the spans, in the order taken
+    uint32_t cnt[HS_MAP_MAX_SEGMENTS + 1];                        // the best's free hits per gap
+    int32_t n_free, stop;
+    hs::MapSegment seg[HS_MAP_MAX_SEGMENTS];
+};
+
+// one read's rounds, by whichever kernel owns it (256 threads); false: more hits than `cap` keys -- not this route's. A round is one pass over the
+// hits that compacts the free ones' keys (round 0: all of them, map_vote_one's load), and only where there are any: the sort of that many keys, the
+// vote, a pass for the gap counters (from round 1 on: round 0 has one gap) and a pass for the extremes.
+static __device__ bool map_split_one(const MapVoteArgs& A, const MapSplitArgs& B, int r, uint64_t* keys, long long cap, uint32_t* s_sc, uint64_t* s_key, int32_t* s_ext,
+                                     MapSplitShared& sh) {
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x, lane = tid & 63;
+    long long h0 = A.hit_off[A.mz_off[r]], h1 = A.hit_off[A.mz_off[r + 1]];
+    if (h0 < 0 || h1 > A.n_hits || h1 < h0) h1 = h0 = 0;
+    const long long n64 = h1 - h0;
+    if (n64 > cap) return false;
+    const int n = (int)n64, k = A.P.k;
+    const int32_t Lr = (int32_t)(A.read_off[r + 1] - A.read_off[r]);
+    const int max_segments = min(max(B.S.max_segments, 1), HS_MAP_MAX_SEGMENTS);
+    int n_spans = 0;      // (the same in every thread)
+    for (int round = 0; round < max_segments; ++round) {
+        if (tid == 0) sh.n_free = 0;
+        if (tid <= HS_MAP_MAX_SEGMENTS) sh.cnt[tid] = 0;
+        if (tid < 4) s_ext[tid] = (tid & 1) ? INT32_MIN : INT32_MAX;      // qa_min, qa_max, t_min, t_max
+        __syncthreads();
+        int n_free = n;
+        if (n_spans == 0) {
+            for (int i = tid; i < n; i += nt) keys[i] = A.hit_key[h0 + i];
+        } else {
+            for (int base = 0; base < n; base += nt) {      // (every lane takes every turn: the ballot)
+                const int i = base + tid;
+                bool is_free = false;
+                uint64_t key = 0;
+                if (i < n) {
+                    key = A.hit_key[h0 + i];
+                    is_free = hs::map_hit_free(sh.a0, sh.a1, n_spans, hs::map_hit_q(A.hit_qa[h0 + i], hs::map_key_rel(key), Lr, k), k);
+                }
+                const unsigned long long b = __ballot(is_free);
+                int at = 0;
+                if (lane == 0 && b) at = atomicAdd(&sh.n_free, __popcll(b));
+                at = __shfl(at, 0, 64);
+                if (is_free) keys[at + __popcll(b & ((1ull << lane) - 1ull))] = key;      // (at most n keys: within `cap`)
+            }
+            __syncthreads();
+            n_free = sh.n_free;
+        }
+        if (n_free == 0) break;
+        const int n_pow2 = pow2_at_least(n_free);
+        for (int i = n_free + tid; i < n_pow2; i += nt) keys[i] = ~0ull;
+        __syncthreads();
+        hs::MapVote v;
+        map_vote_keys(keys, n_free, n_pow2, round == 0, v, s_sc, s_key);
+        if (round == 0 && tid == 0) { B.read_votes[r] = (int32_t)v.best; B.read_second[r] = (int32_t)v.second; }
+        if (v.best < hs::map_round_threshold(A.P, B.S, round)) break;
+        int g = 0;
+        uint32_t n_seg = v.best;
+        if (n_spans > 0) {
+            for (int i = tid; i < n; i += nt) {
+                const uint64_t key = A.hit_key[h0 + i];
+                if (!hs::map_in_best(key, v.key)) continue;
+                const int32_t q = hs::map_hit_q(A.hit_qa[h0 + i], hs::map_key_rel(key), Lr, k);
+                if (hs::map_hit_free(sh.a0, sh.a1, n_spans, q, k)) atomicAdd(&sh.cnt[hs::map_hit_gap(sh.a1, n_spans, q)], 1u);
+            }
+            __syncthreads();
+            g = hs::map_best_gap(sh.cnt, n_spans + 1);
+            n_seg = sh.cnt[g];
+        }
+        int qa_min = INT32_MAX, qa_max = INT32_MIN, t_min = INT32_MAX, t_max = INT32_MIN;
+        for (int i = tid; i < n; i += nt) {
+            const uint64_t key = A.hit_key[h0 + i];
+            if (!hs::map_in_best(key, v.key)) continue;
+            const int qa = A.hit_qa[h0 + i];
+            const int32_t q = hs::map_hit_q(qa, hs::map_key_rel(key), Lr, k);
+            if (!hs::map_hit_free(sh.a0, sh.a1, n_spans, q, k) || hs::map_hit_gap(sh.a1, n_spans, q) != g) continue;
+            const int t = A.hit_t[h0 + i];
+            qa_min = min(qa_min, qa); qa_max = max(qa_max, qa); t_min = min(t_min, t); t_max = max(t_max, t);
+        }
+        atomicMin(&s_ext[0], qa_min); atomicMax(&s_ext[1], qa_max); atomicMin(&s_ext[2], t_min); atomicMax(&s_ext[3], t_max);
+        __syncthreads();
+        if (tid == 0) {
+            hs::MapSegment s;
+            s.key = v.key; s.n = n_seg; s.second = round == 0 ? v.second : 0u; s.round = round;
+            s.qa_min = s_ext[0]; s.qa_max = s_ext[1]; s.t_min = s_ext[2]; s.t_max = s_ext[3];
+            hs::map_seed_span(hs::map_key_rel(s.key), Lr, s.qa_min, (int64_t)s.qa_max + k, &s.a0, &s.a1);
+            const bool stands = n_seg > 0 && hs::map_segment_stands(B.S, round, n_seg, s.qa_min, (int64_t)s.qa_max + k);
+            if (stands) { sh.seg[n_spans] = s; sh.a0[n_spans] = s.a0; sh.a1[n_spans] = s.a1; }
+            sh.stop = stands ? 0 : 1;
+        }
+        __syncthreads();
+        if (sh.stop) break;
+        ++n_spans;
+    }
+    if (tid == 0) {
+        hs::map_segments_sort(sh.seg, n_spans);
+        for (int i = 0; i < n_spans; ++i) {
+            const int c = hs::map_key_contig(sh.seg[i].key);
+            const int32_t Lc = c >= 0 && c < A.n_contigs ? (int32_t)(A.contig_off[c + 1] - A.contig_off[c]) : 0;
+            int32_t contig, qs, qe, ts, te;
+            uint8_t strand;
+            hs::map_segment_interval(A.P, B.S, sh.seg, n_spans, i, Lr, Lc, &contig, &strand, &qs, &qe, &ts, &te);
+            int32_t* o = B.staged + ((size_t)r * (size_t)max_segments + (size_t)i) * HS_MAP_SEG_WORDS;
+            o[0] = r; o[1] = contig; o[2] = strand; o[3] = qs; o[4] = qe; o[5] = ts; o[6] = te; o[7] = (int32_t)sh.seg[i].n; o[8] = (int32_t)sh.seg[i].second; o[9] = sh.seg[i].round;
+        }
+        B.seg_count[r] = n_spans;
+    }
+    __syncthreads();      // (the wide route's next read finds the tables free)
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_map_vote_split(MapVoteArgs A, MapSplitArgs B) {
+    __shared__ uint64_t s_keys[HS_MAP_LDS_KEYS];
+    __shared__ uint64_t s_key[256];
+    __shared__ uint32_t s_sc[256];
+    __shared__ int32_t s_ext[4];
+    __shared__ MapSplitShared sh;
+    const int r = (int)blockIdx.x;
+    if (r >= A.n_reads) return;
+    if (!map_split_one(A, B, r, s_keys, HS_MAP_LDS_KEYS, s_sc, s_key, s_ext, sh) && threadIdx.x == 0) wide_list_push(A.wide_count, A.wide_list, A.n_reads, r);
+}
+
+__global__ __launch_bounds__(256) void k_map_vote_split_wide(MapVoteArgs A, MapSplitArgs B, uint64_t* __restrict__ slabs, long long slab_keys) {
+    __shared__ uint64_t s_key[256];
+    __shared__ uint32_t s_sc[256];
+    __shared__ int32_t s_ext[4];
+    __shared__ MapSplitShared sh;
+    const int n = min(*A.wide_count, A.n_reads);
+    uint64_t* keys = slabs + (size_t)blockIdx.x * (size_t)slab_keys;
+    for (int i = (int)blockIdx.x; i < n; i += (int)gridDim.x) (void)map_split_one(A, B, A.wide_list[i], keys, slab_keys, s_sc, s_key, s_ext, sh);
+}
+
+// the staged segments of every read, side by side at the offsets the scan of seg_count gave
+__global__ __launch_bounds__(256) void k_map_seg_compact(const int32_t* __restrict__ seg_count, const int64_t* __restrict__ seg_off, const int32_t* __restrict__ staged, int n_reads,
+                                                         int max_segments, long long cap, int32_t* __restrict__ out) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)n_reads * max_segments) return;
+    const int r = (int)(idx / max_segments), j = (int)(idx % max_segments);
+    if (j >= seg_count[r]) return;
+    const long long o = seg_off[r] + j;
+    if (o < 0 || o >= cap) return;      // never write beyond the staging's size
+    for (int w = 0; w < HS_MAP_SEG_WORDS; ++w) out[o * HS_MAP_SEG_WORDS + w] = staged[idx * HS_MAP_SEG_WORDS + w];
 }
 
 }  // namespace hsdev

@@ -1,5 +1,6 @@
 // hs_map_host.cpp -- the device-free half of the read mapper: the rule of hs_map_host.h over a whole job, on the host. It is the yardstick the
-// device is held to by integer equality (tests/test_gpu_map.py through tests/harness/map_selftest.cpp) and the text of hs_map_text. No HIP.
+// device is held to by integer equality (tests/test_gpu_map.py through tests/harness/map_selftest.cpp) and the text of hs_map_text; the same for
+// the split form (map_reads_split_host, hs_map_segments_text; tests/test_gpu_map_split.py through tests/harness/map_split_selftest.cpp). No HIP.
 #include "hs_map_host.h"
 
 #include <algorithm>
@@ -67,20 +68,21 @@ int map_index_host(const uint8_t* contig_seq, const int64_t* contig_off, int32_t
 namespace {
 struct Hit { uint64_t key; int32_t qa, t; };
 
-void map_one_read(const MapIndexHost& ix, const uint8_t* seq, int64_t L, size_t r, MapResultHost& out, std::vector<Hit>& hits, std::vector<uint64_t>& keys) {
+// the hits of one read (all of them, in minimizer order) and its minimizer counts
+void map_read_hits(const MapIndexHost& ix, const uint8_t* seq, int64_t L, std::vector<Hit>& hits, int32_t* n_minimizers, int32_t* n_skipped) {
     const hs_map_params& p = ix.params;
     const int64_t off[2] = {0, L};
     MapMinimizers mz;
     map_minimizers(seq, off, 1, p, mz);
     const uint32_t mask = (uint32_t)(((uint64_t)1 << ix.bucket_bits) - 1);
     hits.clear();
-    int32_t n_skipped = 0;
+    *n_skipped = 0;
     for (size_t m = 0; m < mz.h.size(); ++m) {
         const uint32_t h = mz.h[m];
         const int64_t b0 = ix.bucket_off[h & mask], b1 = ix.bucket_off[(size_t)(h & mask) + 1];
         int64_t occ = 0;
         for (int64_t e = b0; e < b1; ++e) occ += ix.e_h[(size_t)e] == h;
-        if (occ > p.max_occ) { ++n_skipped; continue; }
+        if (occ > p.max_occ) { ++*n_skipped; continue; }
         for (int64_t e = b0; e < b1; ++e) {
             if (ix.e_h[(size_t)e] != h) continue;
             Hit x;
@@ -89,20 +91,31 @@ void map_one_read(const MapIndexHost& ix, const uint8_t* seq, int64_t L, size_t 
             hits.push_back(x);
         }
     }
-    keys.resize(hits.size());
-    for (size_t i = 0; i < hits.size(); ++i) keys[i] = hits[i].key;
+    *n_minimizers = (int32_t)mz.h.size();
+}
+
+// the vote over these keys (sorted here): best, its key, and second where asked for
+void map_vote_keys(std::vector<uint64_t>& keys, bool want_second, MapVote& v) {
     std::sort(keys.begin(), keys.end());
-    MapVote v;
     auto count = [&](uint64_t key) { auto rg = std::equal_range(keys.begin(), keys.end(), key); return (uint32_t)(rg.second - rg.first); };
     for (size_t i = 0; i < keys.size(); ++i) {
         if (i && keys[i] == keys[i - 1]) continue;
         const uint32_t sc = count(keys[i]) + count(keys[i] + 1);
         if (v.best == 0 || map_beats(sc, keys[i], v.best, v.key)) { v.best = sc; v.key = keys[i]; }
     }
-    for (size_t i = 0; i < keys.size(); ++i) {
+    for (size_t i = 0; want_second && i < keys.size(); ++i) {
         if ((i && keys[i] == keys[i - 1]) || !map_second_allowed(keys[i], v.key)) continue;
         v.second = std::max(v.second, count(keys[i]) + count(keys[i] + 1));
     }
+}
+
+void map_one_read(const MapIndexHost& ix, const uint8_t* seq, int64_t L, size_t r, MapResultHost& out, std::vector<Hit>& hits, std::vector<uint64_t>& keys) {
+    const hs_map_params& p = ix.params;
+    map_read_hits(ix, seq, L, hits, &out.n_minimizers[r], &out.n_skipped[r]);
+    keys.resize(hits.size());
+    for (size_t i = 0; i < hits.size(); ++i) keys[i] = hits[i].key;
+    MapVote v;
+    map_vote_keys(keys, true, v);
     bool first = true;
     for (const Hit& x : hits) {
         if (!map_in_best(x.key, v.key)) continue;
@@ -112,7 +125,45 @@ void map_one_read(const MapIndexHost& ix, const uint8_t* seq, int64_t L, size_t 
     const int32_t Lc = v.best ? (int32_t)ix.contig_len[(size_t)map_key_contig(v.key)] : 0;
     map_interval(p, v, (int32_t)L, Lc, &out.contig[r], &out.strand[r], &out.qstart[r], &out.qend[r], &out.tstart[r], &out.tend[r]);
     out.votes[r] = (int32_t)v.best; out.second[r] = (int32_t)v.second;
-    out.n_minimizers[r] = (int32_t)mz.h.size(); out.n_hits[r] = (int64_t)hits.size(); out.n_skipped[r] = n_skipped;
+    out.n_hits[r] = (int64_t)hits.size();
+}
+
+// the split rule on one read: its sorted segments (n of them) and round 0's vote
+int map_split_one_read(const MapIndexHost& ix, const hs_map_split_params& sp, int32_t Lr, const std::vector<Hit>& hits, std::vector<uint64_t>& keys, MapSegment* segs, MapVote& v0) {
+    const hs_map_params& p = ix.params;
+    int32_t a0[HS_MAP_MAX_SEGMENTS], a1[HS_MAP_MAX_SEGMENTS];
+    int n = 0;
+    for (int round = 0; round < sp.max_segments; ++round) {
+        keys.clear();
+        for (const Hit& x : hits)
+            if (map_hit_free(a0, a1, n, map_hit_q(x.qa, map_key_rel(x.key), Lr, p.k), p.k)) keys.push_back(x.key);
+        if (keys.empty()) break;
+        MapVote v;
+        map_vote_keys(keys, round == 0, v);
+        if (round == 0) v0 = v;
+        if (v.best < map_round_threshold(p, sp, round)) break;
+        uint32_t cnt[HS_MAP_MAX_SEGMENTS + 1] = {0};
+        for (const Hit& x : hits) {
+            const int32_t q = map_hit_q(x.qa, map_key_rel(x.key), Lr, p.k);
+            if (map_in_best(x.key, v.key) && map_hit_free(a0, a1, n, q, p.k)) cnt[map_hit_gap(a1, n, q)]++;
+        }
+        const int g = map_best_gap(cnt, n + 1);
+        MapSegment s{};
+        s.key = v.key; s.n = cnt[g]; s.second = v.second; s.round = round;
+        bool first = true;
+        for (const Hit& x : hits) {
+            const int32_t q = map_hit_q(x.qa, map_key_rel(x.key), Lr, p.k);
+            if (!map_in_best(x.key, v.key) || !map_hit_free(a0, a1, n, q, p.k) || map_hit_gap(a1, n, q) != g) continue;
+            if (first) { s.qa_min = s.qa_max = x.qa; s.t_min = s.t_max = x.t; first = false; }
+            s.qa_min = std::min(s.qa_min, x.qa); s.qa_max = std::max(s.qa_max, x.qa); s.t_min = std::min(s.t_min, x.t); s.t_max = std::max(s.t_max, x.t);
+        }
+        if (!map_segment_stands(sp, round, s.n, s.qa_min, (int64_t)s.qa_max + p.k)) break;
+        map_seed_span(map_key_rel(s.key), Lr, s.qa_min, (int64_t)s.qa_max + p.k, &s.a0, &s.a1);
+        a0[n] = s.a0; a1[n] = s.a1;
+        segs[n++] = s;
+    }
+    map_segments_sort(segs, n);
+    return n;
 }
 }  // namespace
 
@@ -136,24 +187,94 @@ int map_reads_host(const MapIndexHost& ix, const uint8_t* read_seq, const int64_
     return HS_OK;
 }
 
+int map_reads_split_host(const MapIndexHost& ix, const hs_map_split_params& sp, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapSegmentsHost& out,
+                         std::string& err) {
+    if (!map_split_params_valid(sp)) { err = "map reads: split parameters out of range"; return HS_EINVAL; }
+    if (n_reads < 0 || !read_off) { err = "map reads: bad arguments"; return HS_EINVAL; }
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (read_off[r + 1] < read_off[r] || read_off[r + 1] - read_off[r] > 0x7fffffff) { err = "map reads: a read of more than 2^31 bases"; return HS_EINVAL; }
+    const size_t n = (size_t)n_reads;
+    for (std::vector<int32_t>* v : {&out.n_minimizers, &out.n_skipped, &out.read_votes, &out.read_second}) v->assign(n, 0);
+    out.n_hits.assign(n, 0);
+    std::vector<MapSegment> segs(n * HS_MAP_MAX_SEGMENTS);
+    std::vector<int32_t> n_segs(n, 0);
+    n_threads = std::max(1, std::min(n_threads, std::max(1, n_reads)));
+    auto work = [&](int t) {
+        std::vector<Hit> hits;
+        std::vector<uint64_t> keys;
+        for (size_t r = (size_t)t; r < n; r += (size_t)n_threads) {
+            const int32_t Lr = (int32_t)(read_off[r + 1] - read_off[r]);
+            map_read_hits(ix, read_seq + read_off[r], Lr, hits, &out.n_minimizers[r], &out.n_skipped[r]);
+            out.n_hits[r] = (int64_t)hits.size();
+            MapVote v0;
+            n_segs[r] = map_split_one_read(ix, sp, Lr, hits, keys, &segs[r * HS_MAP_MAX_SEGMENTS], v0);
+            out.read_votes[r] = (int32_t)v0.best; out.read_second[r] = (int32_t)v0.second;
+        }
+    };
+    if (n_threads == 1) work(0);
+    else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < n_threads; ++t) th.emplace_back(work, t);
+        for (std::thread& t : th) t.join();
+    }
+    out.seg_off.assign(n + 1, 0);
+    for (size_t r = 0; r < n; ++r) out.seg_off[r + 1] = out.seg_off[r] + n_segs[r];
+    const size_t S = (size_t)out.seg_off[n];
+    for (std::vector<int32_t>* v : {&out.read, &out.contig, &out.qstart, &out.qend, &out.tstart, &out.tend, &out.votes, &out.second, &out.round}) v->assign(S, 0);
+    out.strand.assign(S, 0);
+    for (size_t r = 0; r < n; ++r) {
+        const MapSegment* s = &segs[r * HS_MAP_MAX_SEGMENTS];
+        const int32_t Lr = (int32_t)(read_off[r + 1] - read_off[r]);
+        for (int i = 0; i < n_segs[r]; ++i) {
+            const size_t o = (size_t)out.seg_off[r] + (size_t)i;
+            const int32_t Lc = (int32_t)ix.contig_len[(size_t)map_key_contig(s[i].key)];
+            map_segment_interval(ix.params, sp, s, n_segs[r], i, Lr, Lc, &out.contig[o], &out.strand[o], &out.qstart[o], &out.qend[o], &out.tstart[o], &out.tend[o]);
+            out.read[o] = (int32_t)r; out.votes[o] = (int32_t)s[i].n; out.second[o] = (int32_t)s[i].second; out.round[o] = s[i].round;
+        }
+    }
+    return HS_OK;
+}
+
+namespace {
+void paf_columns(std::string& s, const std::string& read, int64_t read_len, int32_t qstart, int32_t qend, uint8_t strand, const std::string& contig, int64_t contig_len, int32_t tstart,
+                 int32_t tend, int32_t votes, int32_t second) {
+    s += read;
+    s += '\t'; s += std::to_string(read_len);
+    s += '\t'; s += std::to_string(qstart);
+    s += '\t'; s += std::to_string(qend);
+    s += strand ? "\t+\t" : "\t-\t";
+    s += contig;
+    s += '\t'; s += std::to_string(contig_len);
+    s += '\t'; s += std::to_string(tstart);
+    s += '\t'; s += std::to_string(tend);
+    s += '\t'; s += std::to_string(votes);
+    s += '\t'; s += std::to_string(tend - tstart);
+    s += "\t255\ts1:i:"; s += std::to_string(votes);
+    s += "\ts2:i:"; s += std::to_string(second);
+}
+}  // namespace
+
+std::string map_segments_text(const hs_map_segments* r, const char* const* read_names, const int64_t* read_len, const char* const* contig_names, const int64_t* contig_len) {
+    std::string s;
+    for (int32_t i = 0; i < r->n_reads; ++i)
+        for (int64_t j = r->seg_off[i]; j < r->seg_off[i + 1]; ++j) {
+            const int32_t c = r->contig[j];
+            paf_columns(s, read_names && read_names[i] ? std::string(read_names[i]) : "r" + std::to_string(i), read_len[i], r->qstart[j], r->qend[j], r->strand[j],
+                        contig_names && contig_names[c] ? std::string(contig_names[c]) : "c" + std::to_string(c), contig_len[c], r->tstart[j], r->tend[j], r->votes[j], r->second[j]);
+            s += "\tsg:i:"; s += std::to_string(r->round[j]);
+            s += "\tns:i:"; s += std::to_string(r->seg_off[i + 1] - r->seg_off[i]);
+            s += '\n';
+        }
+    return s;
+}
+
 std::string map_text(const hs_map_result* r, const char* const* read_names, const int64_t* read_len, const char* const* contig_names, const int64_t* contig_len) {
     std::string s;
     for (int32_t i = 0; i < r->n_reads; ++i) {
         const int32_t c = r->contig[i];
         if (c < 0) continue;
-        s += read_names && read_names[i] ? std::string(read_names[i]) : "r" + std::to_string(i);
-        s += '\t'; s += std::to_string(read_len[i]);
-        s += '\t'; s += std::to_string(r->qstart[i]);
-        s += '\t'; s += std::to_string(r->qend[i]);
-        s += r->strand[i] ? "\t+\t" : "\t-\t";
-        s += contig_names && contig_names[c] ? std::string(contig_names[c]) : "c" + std::to_string(c);
-        s += '\t'; s += std::to_string(contig_len[c]);
-        s += '\t'; s += std::to_string(r->tstart[i]);
-        s += '\t'; s += std::to_string(r->tend[i]);
-        s += '\t'; s += std::to_string(r->votes[i]);
-        s += '\t'; s += std::to_string(r->tend[i] - r->tstart[i]);
-        s += "\t255\ts1:i:"; s += std::to_string(r->votes[i]);
-        s += "\ts2:i:"; s += std::to_string(r->second[i]);
+        paf_columns(s, read_names && read_names[i] ? std::string(read_names[i]) : "r" + std::to_string(i), read_len[i], r->qstart[i], r->qend[i], r->strand[i],
+                    contig_names && contig_names[c] ? std::string(contig_names[c]) : "c" + std::to_string(c), contig_len[c], r->tstart[i], r->tend[i], r->votes[i], r->second[i]);
         s += '\n';
     }
     return s;
@@ -167,6 +288,35 @@ hs_map_params hs_map_params_default(void) {
     hs_map_params p;
     p.k = 15; p.w = 10; p.max_occ = 64; p.band_log2 = 9; p.min_votes = 3; p.extend = 1; p.bucket_bits = -1;
     return p;
+}
+hs_map_split_params hs_map_split_params_default(void) {
+    hs_map_split_params s;
+    s.max_segments = 4; s.min_votes = 3; s.min_span = 100; s.max_gap = 200;      // (placeholders, not tuned)
+    return s;
+}
+void hs_map_segments_destroy(hs_map_segments* r) {
+    if (!r) return;
+    void* p[] = {r->seg_off, r->read, r->contig, r->strand, r->qstart, r->qend, r->tstart, r->tend, r->votes, r->second, r->round, r->n_minimizers, r->n_skipped, r->n_hits,
+                 r->read_votes, r->read_second};
+    for (void* q : p) std::free(q);
+    std::free(r);
+}
+int hs_map_segments_text(const hs_map_segments* segments, const char* const* read_names, const int64_t* h_read_off, const char* const* contig_names, const int64_t* h_contig_off,
+                         int32_t n_contigs, char** text) {
+    if (!segments || !h_read_off || !h_contig_off || !text || n_contigs < 0 || !segments->seg_off || segments->n_reads < 0 || segments->n_segments < 0) return HS_EINVAL;
+    if (segments->seg_off[0] != 0 || segments->seg_off[segments->n_reads] != segments->n_segments) return HS_EINVAL;      // (the offsets say where the text reads)
+    for (int32_t i = 0; i < segments->n_reads; ++i)
+        if (segments->seg_off[i + 1] < segments->seg_off[i]) return HS_EINVAL;
+    std::vector<int64_t> rl((size_t)segments->n_reads), cl((size_t)n_contigs);
+    for (int32_t i = 0; i < segments->n_reads; ++i) rl[(size_t)i] = h_read_off[i + 1] - h_read_off[i];
+    for (int64_t j = 0; j < segments->n_segments; ++j)
+        if (segments->contig[j] < 0 || segments->contig[j] >= n_contigs) return HS_EINVAL;
+    for (int32_t c = 0; c < n_contigs; ++c) cl[(size_t)c] = h_contig_off[c + 1] - h_contig_off[c];
+    const std::string s = hs::map_segments_text(segments, read_names, rl.data(), contig_names, cl.data());
+    *text = (char*)std::malloc(s.size() + 1);
+    if (!*text) return HS_EINVAL;
+    std::memcpy(*text, s.c_str(), s.size() + 1);
+    return HS_OK;
 }
 void hs_map_result_destroy(hs_map_result* r) {
     if (!r) return;

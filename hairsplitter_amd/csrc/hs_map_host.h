@@ -1,6 +1,7 @@
 // hs_map_host.h -- the read mapper of include/hairsplitter_hip.h (hs_map_reads): the rule that names, for every read, the contig window it came
 // from, stated once for the host and the device. Minimizer seeds and a vote over diagonal bins; no chaining, no base-level alignment (A1 does
 // the exact placement inside the window, hs_realign_intervals). The reference has no counterpart (it shells out to minimap2): the rule is ours.
+// hs_map_reads names one window per read; hs_map_reads_split (below, "split mappings") up to max_segments over disjoint stretches of the read.
 // No device code and no HIP call in here or in hs_map_host.cpp: tests/harness/map_selftest.cpp builds both into a program of its own.
 //
 // The defaults of hs_map_params are minimap2's ONT k and w plus placeholders (max_occ, band_log2, min_votes). They are NOT tuned.
@@ -91,21 +92,105 @@ struct MapVote {
     uint64_t key = 0;
     int32_t qa_min = 0, qa_max = 0, t_min = 0, t_max = 0;      // over the best's hits
 };
+// seeds [qa_lo, qa_hi) x [t_lo, t_hi) on the contig's strand, stretched along their diagonal to the read range [b0, b1) (the same strand) and
+// clipped at the contig's ends; then turned to the read as given. The one statement of `extend` for map_interval and map_segment_interval.
+HS_HD inline void map_stretch(const hs_map_params& p, uint32_t rel, int64_t qa_lo, int64_t qa_hi, int64_t t_lo, int64_t t_hi, int32_t Lr, int32_t Lc, int64_t b0, int64_t b1,
+                              int32_t* qstart, int32_t* qend, int32_t* tstart, int32_t* tend) {
+    if (p.extend) {
+        const int64_t tl = t_lo - (qa_lo - b0), th = t_hi + (b1 - qa_hi);
+        qa_lo = b0 + (tl < 0 ? -tl : 0); t_lo = tl < 0 ? 0 : tl;
+        qa_hi = b1 - (th > Lc ? th - Lc : 0); t_hi = th > Lc ? Lc : th;
+    }
+    *qstart = (int32_t)(rel ? Lr - qa_hi : qa_lo); *qend = (int32_t)(rel ? Lr - qa_lo : qa_hi);
+    *tstart = (int32_t)t_lo; *tend = (int32_t)t_hi;
+}
 // the per-read record from the vote (Lc = the best contig's length; ignored without a hit)
 HS_HD inline void map_interval(const hs_map_params& p, const MapVote& v, int32_t Lr, int32_t Lc, int32_t* contig, uint8_t* strand, int32_t* qstart, int32_t* qend,
                                int32_t* tstart, int32_t* tend) {
     *contig = -1; *strand = 0; *qstart = *qend = *tstart = *tend = 0;
     if (v.best == 0 || v.best < (uint32_t)p.min_votes) return;
-    int64_t qa_lo = v.qa_min, qa_hi = (int64_t)v.qa_max + p.k, t_lo = v.t_min, t_hi = (int64_t)v.t_max + p.k;
-    if (p.extend) {
-        const int64_t tl = t_lo - qa_lo, th = t_hi + (Lr - qa_hi);
-        qa_lo = tl < 0 ? -tl : 0; t_lo = tl < 0 ? 0 : tl;
-        qa_hi = Lr - (th > Lc ? th - Lc : 0); t_hi = th > Lc ? Lc : th;
-    }
     const uint32_t rel = map_key_rel(v.key);
     *contig = map_key_contig(v.key); *strand = (uint8_t)(1 - rel);
-    *qstart = (int32_t)(rel ? Lr - qa_hi : qa_lo); *qend = (int32_t)(rel ? Lr - qa_lo : qa_hi);
-    *tstart = (int32_t)t_lo; *tend = (int32_t)t_hi;
+    map_stretch(p, rel, v.qa_min, (int64_t)v.qa_max + p.k, v.t_min, (int64_t)v.t_max + p.k, Lr, Lc, 0, Lr, qstart, qend, tstart, tend);
+}
+
+// ---- split mappings (hs_map_reads_split): up to max_segments intervals over disjoint stretches of a read ----
+// The defaults of hs_map_split_params (4, 3, 100, 200) are placeholders like the mapper's own. They are NOT tuned.
+//
+//   q                a hit's k-mer starts at q = rel ? Lr - k - qa : qa on the read as given (map_hit_q): nothing new is stored per hit.
+//   rounds           0 .. max_segments - 1; `spans` = the seed spans [a0, a1) of the segments taken so far, read as given, in the order taken.
+//   free             a hit whose k-mer overlaps no span: q + k <= a0 || q >= a1 for every span (map_hit_free). Round 0: every hit.
+//   vote             the vote above over the free hits only; the threshold is the index's min_votes in round 0 and the split min_votes later
+//                    (map_round_threshold). No free hit, or a best below the threshold: the read's rounds END (no other candidate is tried).
+//   gap              the spans are disjoint, and a free k-mer lies wholly inside one maximal stretch of [0, Lr) outside them: gap g = the number
+//                    of spans that end at or before q (map_hit_gap; 0 = leftmost; a gap between two spans that touch is empty and holds no hit).
+//                    Of the best's free hits (its bin and the next) the gap with the most is kept, the leftmost on a tie (map_best_gap); the
+//                    segment's hits are the best's in that gap, n their number; the best's hits in other gaps stay free.
+//   segment          extremes over its hits as above. Rounds >= 1: n < min_votes or qa_hi - qa_lo < min_span ENDS the rounds (map_segment_stands).
+//                    Seed span = [qa_lo, qa_hi), or [Lr - qa_hi, Lr - qa_lo) for rel 1 (map_seed_span). Recorded: round, key, n, and `second` as
+//                    the vote gives it in round 0, 0 in later rounds.
+//   intervals        segments by span start (map_segments_sort). Segment i may use the read range [A0, A1): A0 = the previous span's end (0 for
+//                    the first), A1 = the next span's start (Lr for the last) -- but an inner side whose distance to the neighbour's span is
+//                    above max_gap stays at the segment's own span bound (map_segment_range): a wide gap is a foreign insert and is left
+//                    unaligned, a narrow one a breakpoint both neighbours may cover. With `extend` the seeds are stretched to [A0, A1) and
+//                    clipped at the contig's ends (map_stretch); without, the interval is the seed extremes. One segment = map_interval's record.
+//   decided here     a segment's `votes` is n (round 0: the vote's best score, since round 0 has one gap). The per-read votes / second of
+//                    hs_map_segments are round 0's vote, also for a read without a segment, as hs_map_result has them.
+#define HS_MAP_MAX_SEGMENTS 8
+HS_HD inline bool map_split_params_valid(const hs_map_split_params& s) {
+    return s.max_segments >= 1 && s.max_segments <= HS_MAP_MAX_SEGMENTS && s.min_votes >= 1 && s.min_span >= 0 && s.max_gap >= 0;
+}
+HS_HD inline int32_t map_hit_q(int32_t qa, uint32_t rel, int32_t Lr, int k) { return rel ? Lr - k - qa : qa; }
+HS_HD inline bool map_hit_free(const int32_t* a0, const int32_t* a1, int n_spans, int32_t q, int k) {
+    for (int i = 0; i < n_spans; ++i)
+        if (!(q + k <= a0[i] || q >= a1[i])) return false;
+    return true;
+}
+HS_HD inline int map_hit_gap(const int32_t* a1, int n_spans, int32_t q) {
+    int g = 0;
+    for (int i = 0; i < n_spans; ++i) g += a1[i] <= q ? 1 : 0;
+    return g;
+}
+HS_HD inline int map_best_gap(const uint32_t* cnt, int n_gaps) {
+    int g = 0;
+    for (int i = 1; i < n_gaps; ++i) if (cnt[i] > cnt[g]) g = i;
+    return g;
+}
+HS_HD inline uint32_t map_round_threshold(const hs_map_params& p, const hs_map_split_params& s, int round) { return (uint32_t)(round == 0 ? p.min_votes : s.min_votes); }
+HS_HD inline bool map_segment_stands(const hs_map_split_params& s, int round, uint32_t n, int64_t qa_lo, int64_t qa_hi) {
+    return round == 0 || (n >= (uint32_t)s.min_votes && qa_hi - qa_lo >= s.min_span);
+}
+HS_HD inline void map_seed_span(uint32_t rel, int32_t Lr, int64_t qa_lo, int64_t qa_hi, int32_t* a0, int32_t* a1) {
+    *a0 = (int32_t)(rel ? Lr - qa_hi : qa_lo); *a1 = (int32_t)(rel ? Lr - qa_lo : qa_hi);
+}
+struct MapSegment {      // (no initialisers: the kernels keep a read's segments in LDS)
+    uint64_t key;
+    uint32_t n, second;
+    int32_t round, qa_min, qa_max, t_min, t_max, a0, a1;      // [a0, a1): the seed span on the read as given
+};
+// (spans are disjoint: their starts are distinct)
+HS_HD inline void map_segments_sort(MapSegment* s, int n) {
+    for (int i = 1; i < n; ++i) {
+        const MapSegment x = s[i];
+        int j = i;
+        for (; j > 0 && s[j - 1].a0 > x.a0; --j) s[j] = s[j - 1];
+        s[j] = x;
+    }
+}
+HS_HD inline void map_segment_range(const MapSegment* s, int n, int i, int32_t Lr, int32_t max_gap, int32_t* A0, int32_t* A1) {
+    *A0 = i > 0 ? s[i - 1].a1 : 0;
+    *A1 = i + 1 < n ? s[i + 1].a0 : Lr;
+    if (i > 0 && s[i].a0 - s[i - 1].a1 > max_gap) *A0 = s[i].a0;
+    if (i + 1 < n && s[i + 1].a0 - s[i].a1 > max_gap) *A1 = s[i].a1;
+}
+// the record of segment i of a read's sorted segments (Lc = its contig's length)
+HS_HD inline void map_segment_interval(const hs_map_params& p, const hs_map_split_params& sp, const MapSegment* s, int n, int i, int32_t Lr, int32_t Lc, int32_t* contig, uint8_t* strand,
+                                       int32_t* qstart, int32_t* qend, int32_t* tstart, int32_t* tend) {
+    int32_t A0, A1;
+    map_segment_range(s, n, i, Lr, sp.max_gap, &A0, &A1);
+    const uint32_t rel = map_key_rel(s[i].key);
+    *contig = map_key_contig(s[i].key); *strand = (uint8_t)(1 - rel);
+    map_stretch(p, rel, s[i].qa_min, (int64_t)s[i].qa_max + p.k, s[i].t_min, (int64_t)s[i].t_max + p.k, Lr, Lc, rel ? Lr - A1 : A0, rel ? Lr - A0 : A1, qstart, qend, tstart, tend);
 }
 
 // ---- the device-free half: a whole job on the host ----
@@ -132,8 +217,20 @@ struct MapResultHost {
     std::vector<int64_t> n_hits;
 };
 int map_reads_host(const MapIndexHost& ix, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapResultHost& out, std::string& err);
+// the split form: segments in (read, span start) order, as hs_map_segments has them
+struct MapSegmentsHost {
+    std::vector<int64_t> seg_off;      // [n_reads + 1]
+    std::vector<int32_t> read, contig, qstart, qend, tstart, tend, votes, second, round;
+    std::vector<uint8_t> strand;
+    std::vector<int32_t> n_minimizers, n_skipped, read_votes, read_second;      // per read
+    std::vector<int64_t> n_hits;
+};
+int map_reads_split_host(const MapIndexHost& ix, const hs_map_split_params& sp, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapSegmentsHost& out,
+                         std::string& err);
 // PAF lines of the mapped reads: names[] may be nullptr (then r<i> / c<i>)
 std::string map_text(const hs_map_result* r, const char* const* read_names, const int64_t* read_len, const char* const* contig_names, const int64_t* contig_len);
+// one PAF line per segment, in segment order: map_text's columns, then sg:i:<round> ns:i:<segments of the read>
+std::string map_segments_text(const hs_map_segments* r, const char* const* read_names, const int64_t* read_len, const char* const* contig_names, const int64_t* contig_len);
 
 }  // namespace hs
 #endif

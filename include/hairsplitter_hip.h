@@ -920,7 +920,8 @@ int hs_gfa2fa_main(int argc, char** argv);
  * The step in front of the intervals: which contig window every read came from, on the device. Minimizer seeds
  * against a resident index of the contigs and a vote over diagonal bins; no chaining and no base-level alignment -- A1 places the
  * read inside the window (hs_realign_intervals). The reference has no counterpart (it shells out to minimap2); the rule is this
- * library's own, stated once in csrc/hs_map_host.h for host and device. At most one interval per read (primary only).
+ * library's own, stated once in csrc/hs_map_host.h for host and device. hs_map_reads gives at most one interval per read (the primary);
+ * hs_map_reads_split below adds the read's other parts as further intervals.
  * The defaults are minimap2's ONT k and w plus placeholders; they are not tuned.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct hs_map_params {
@@ -972,6 +973,50 @@ int hs_map_text(const hs_map_result* result, const char* const* read_names, cons
  * alignment argument: it maps the reads this way into <tmpDir>/hs_mapped.paf and takes that file the way HS_REALIGN=1 takes a PAF. */
 int hs_map_files(const char* gfa, const char* reads, const char* out_paf, int32_t n_threads, const hs_map_params* params);
 int hs_map_main(int argc, char** argv);
+
+/* Split mappings: a read's parts on other contigs -- or elsewhere on the same one -- as further intervals, what a mapper's
+ * supplementary lines give. Opt-in: up to max_segments intervals per read over disjoint stretches of it, found by repeating the vote over the
+ * hits that overlap no stretch already taken (rule: csrc/hs_map_host.h, "split mappings"). A read with one segment has hs_map_reads' record.
+ * No merging of collinear segments, no secondary placements of one stretch, no MAPQ. The four defaults are placeholders; they are not tuned. */
+typedef struct hs_map_split_params {
+    int32_t max_segments;  /* 1..8: most intervals of a read; default 4 */
+    int32_t min_votes;     /* >= 1: hits a segment of a later round needs (round 0: hs_map_params.min_votes); default 3 */
+    int32_t min_span;      /* >= 0: read bases the seeds of a later round's segment must span; default 100 */
+    int32_t max_gap;       /* >= 0: two neighbouring segments further apart on the read than this are not extended towards each other; default 200 */
+} hs_map_split_params;
+hs_map_split_params hs_map_split_params_default(void);
+typedef struct hs_map_segments {
+    int32_t n_reads;
+    int64_t n_segments;
+    int64_t* seg_off;      /* [n_reads + 1]: read r has the segments seg_off[r] .. seg_off[r + 1], ascending by their start on the read */
+    /* per segment */
+    int32_t *read, *contig;
+    uint8_t* strand;
+    int32_t *qstart, *qend, *tstart, *tend;
+    int32_t *votes, *second;   /* the segment's hits; round 0's `second` as hs_map_result has it, 0 in later rounds */
+    int32_t* round;        /* the round that found the segment: 0 = the read's primary */
+    /* per read */
+    int32_t *n_minimizers, *n_skipped;
+    int64_t* n_hits;
+    int32_t *read_votes, *read_second;   /* round 0's vote, also of a read without a segment (hs_map_result's votes and second) */
+    /* per call */
+    int64_t n_wide;
+    int64_t total_minimizers, total_hits;
+    double t_minimizers_ms, t_hits_ms, t_vote_ms;
+} hs_map_segments;
+/* split NULL: the defaults. Parameters out of range: HS_EINVAL. */
+int hs_map_reads_split(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, const hs_map_split_params* split,
+                       hs_map_segments** segments);
+void hs_map_segments_destroy(hs_map_segments* segments);
+/* hs_map_reads_split, then hs_realign_intervals with interval i = segment i: the counterpart of hs_map_to_batch. records / segments may be NULL. */
+int hs_map_split_to_batch(const hs_map_index* index, const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq,
+                          const int64_t* h_read_off, int32_t n_reads, int32_t pad, const hs_map_split_params* split, hs_cv_batch** batch, hs_realign_records** records,
+                          hs_map_segments** segments);
+/* one PAF line per segment in segment order: hs_map_text's columns and s1 / s2 tags, then sg:i:<round> ns:i:<segments of the read>. With
+ * HS_MAP_SPLIT=<n> (2..8) in the environment hs_map_files (bin/hs_map, HS_MAP=1) writes these lines with max_segments = n; unset or 1: hs_map_text's (any other value too, with a line on stderr).
+ * seg_off must ascend from 0 to n_segments: HS_EINVAL otherwise. */
+int hs_map_segments_text(const hs_map_segments* segments, const char* const* read_names, const int64_t* h_read_off, const char* const* contig_names,
+                         const int64_t* h_contig_off, int32_t n_contigs, char** text);
 
 #ifdef __cplusplus
 }

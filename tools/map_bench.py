@@ -8,7 +8,11 @@
      strand, the share of records whose (pos, CIGAR) equal those of hs_realign_intervals on the truth intervals;
   5. stages 3 and 4 on the mapped batch and on the truth-SAM batch: SNPs of each, SNP positions in common, the error rates; windows and groups of
      each, and the windows both have whose label arrays are equal element by element (a report, no assertion).
-Usage: python tools/map_bench.py [config=C4] [contigs=16] [repeats=5] [host_sample=2000]      (prints one JSON line)"""
+Usage: python tools/map_bench.py [config=C4] [contigs=16] [repeats=5] [host_sample=2000]      (prints one JSON line)
+       python tools/map_bench.py [config=C4] [contigs=16] split [piece_len=20000]
+The split mode cuts the contigs into pieces and keeps the reads and their truth: reads with more than one segment of hs_map_reads_split; aligned bp and
+the mean depth over the last 1 000 bases of the pieces for the batch of hs_map_split_to_batch, of hs_map_to_batch and of the truth intervals; the vote
+group's time (HIP events, medians of 5, alternating) split against plain on the cut job and on the uncut one, where nearly every read has one segment."""
 import json
 import os
 import statistics
@@ -21,9 +25,106 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def read_offset_at(cigar, pos, x):
+    """read bases (contig orientation, clips included) in front of contig position x in an alignment that starts at pos"""
+    q, t = 0, pos
+    for w in cigar.tolist():
+        op, n = w & 0xF, w >> 4
+        in_ref, in_read = op in (0, 2, 3, 7, 8), op in (0, 1, 4, 7, 8)
+        if in_ref and t + n > x:
+            return q + (x - t if in_read else 0)
+        t += n if in_ref else 0
+        q += n if in_read else 0
+    return q
+
+
+def split_main(cfg, n, piece_len):
+    """the contigs cut into pieces of piece_len, the reads as they were: what hs_map_reads_split adds at the pieces' ends"""
+    import numpy as np
+    from hairsplitter_amd import synth
+    contigs, _ = synth.generate_job(cfg, list(range(n)), workers=min(16, os.cpu_count() or 1))      # before the GPU is touched (forks)
+    from hairsplitter_amd import api
+    api.require_gpu()
+    whole = api.FlatBatch(contigs)
+    reads = (whole.read_seq, whole.read_off)
+    R = whole.n_reads
+    pieces, piece_of, truth, base = [], [], [], 0      # piece_of[c] = [(start, end, index)]
+    for ci, c in enumerate(contigs):
+        cuts = list(range(0, len(c.seq), piece_len))
+        piece_of.append([(s, min(s + piece_len, len(c.seq)), len(pieces) + i) for i, s in enumerate(cuts)])
+        pieces += [c.seq[s:s + piece_len] for s in cuts]
+        for a in c.alns:
+            ops, lens = a.cigar & 0xF, (a.cigar >> 4).astype(np.int64)
+            end = a.pos + int(lens[(ops == 0) | (ops == 2) | (ops == 7) | (ops == 8)].sum())
+            Lr = len(c.reads[a.read])
+            for s, e, pi in piece_of[ci]:
+                o0, o1 = max(a.pos, s), min(end, e)
+                if o0 >= o1:
+                    continue
+                q0 = 0 if o0 == a.pos else read_offset_at(a.cigar, a.pos, o0)
+                q1 = Lr if o1 == end else read_offset_at(a.cigar, a.pos, o1)
+                if q1 > q0:
+                    truth.append((base + a.read, pi, 1 if a.strand else 0) + ((q0, q1) if a.strand else (Lr - q1, Lr - q0)) + (o0 - s, o1 - s))
+        base += len(c.reads)
+    truth.sort(key=lambda x: (x[0], x[3]))
+    tv = np.array(truth, np.int64)
+    pseq, poff = api._flat(pieces)
+    seqs = dict(contig_seq=pseq, contig_off=poff, read_seq=whole.read_seq, read_off=whole.read_off)
+    plen = np.diff(poff)
+    med = statistics.median
+
+    def end_depth(rec):
+        """mean depth over the last 1 000 bases of the pieces, from the records' positions and CIGAR words"""
+        ops, lens = rec["cigar"] & 0xF, (rec["cigar"] >> 4).astype(np.int64)
+        csum = np.concatenate(([0], np.cumsum(np.where((ops == 0) | (ops == 2) | (ops == 7) | (ops == 8), lens, 0))))
+        span = csum[rec["rec_cig_off"][1:]] - csum[rec["rec_cig_off"][:-1]]
+        L = plen[np.repeat(np.arange(len(plen)), np.diff(rec["contig_rec_off"]))]
+        pos = rec["rec_pos"].astype(np.int64)
+        lo = np.maximum(L - 1000, 0)
+        cover = np.clip(np.minimum(pos + span, L) - np.maximum(pos, lo), 0, None)
+        return float(cover.sum() / max(int((plen - np.maximum(plen - 1000, 0)).sum()), 1))
+
+    out = {"config": cfg, "contigs": n, "piece_len": piece_len, "pieces": len(pieces), "reads": R, "truth_parts": len(tv)}
+    with api.map_index((pseq, poff)) as ix:
+        api.map_reads(ix, reads); api.map_reads_split(ix, reads)      # warm-up: pools, code object
+        v_plain, v_split = [], []
+        for _ in range(5):      # alternating, one process, one box
+            v_plain.append(api.map_reads(ix, reads)["t_vote_ms"])
+            seg = api.map_reads_split(ix, reads)
+            v_split.append(seg["t_vote_ms"])
+        b_split, rec_split, seg = api.map_split_to_batch(ix, reads)
+        b_plain, rec_plain, res = api.map_to_batch(ix, reads)
+    rec_truth, b_truth = api.realign_intervals(seqs, tv)
+    n_seg = np.diff(seg["seg_off"])
+    out["cut"] = {"reads_with_more_than_one_segment": int((n_seg > 1).sum()), "reads_without_a_segment": int((n_seg == 0).sum()), "segments": int(n_seg.sum()),
+                  "reads_through_scratch_route": seg["n_wide"], "hits": seg["total_hits"],
+                  "aligned_bp": {"split": b_split.aligned_bp, "plain": b_plain.aligned_bp, "truth": b_truth.aligned_bp},
+                  "mean_depth_last_1000": {"split": round(end_depth(rec_split), 3), "plain": round(end_depth(rec_plain), 3), "truth": round(end_depth(rec_truth), 3)},
+                  "dropped": {"split": int(rec_split["n_dropped"]), "plain": int(rec_plain["n_dropped"]), "truth": int(rec_truth["n_dropped"])},
+                  "vote_ms": {"plain": round(med(v_plain), 4), "split": round(med(v_split), 4), "ratio": round(med(v_split) / med(v_plain), 3), "plain_all": [round(x, 4) for x in v_plain],
+                              "split_all": [round(x, 4) for x in v_split]}}
+    for b in (b_split, b_plain, b_truth):
+        b.close()
+    # the yardstick: the uncut job, where nearly every read has one segment
+    with api.map_index((whole.contig_seq, whole.contig_off)) as ix:
+        api.map_reads(ix, reads); api.map_reads_split(ix, reads)
+        v_plain, v_split = [], []
+        for _ in range(5):
+            v_plain.append(api.map_reads(ix, reads)["t_vote_ms"])
+            seg = api.map_reads_split(ix, reads)
+            v_split.append(seg["t_vote_ms"])
+    n_seg = np.diff(seg["seg_off"])
+    out["uncut"] = {"reads_with_more_than_one_segment": int((n_seg > 1).sum()), "hits": seg["total_hits"],
+                    "vote_ms": {"plain": round(med(v_plain), 4), "split": round(med(v_split), 4), "ratio": round(med(v_split) / med(v_plain), 3),
+                                "plain_all": [round(x, 4) for x in v_plain], "split_all": [round(x, 4) for x in v_split]}}
+    print(json.dumps(out))
+
+
 def main():
     cfg = sys.argv[1] if len(sys.argv) > 1 else "C4"
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+    if len(sys.argv) > 3 and sys.argv[3] == "split":
+        return split_main(cfg, n, int(sys.argv[4]) if len(sys.argv) > 4 else 20000)
     reps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
     sample = int(sys.argv[4]) if len(sys.argv) > 4 else 2000
     import numpy as np
