@@ -35,6 +35,7 @@ SYMBOLS = [
     "hs_map_params_default", "hs_map_index_create", "hs_map_index_destroy", "hs_map_index_download", "hs_map_reads", "hs_map_result_destroy", "hs_map_lds_capacity",
     "hs_map_to_batch", "hs_map_text", "hs_map_files", "hs_map_main",
     "hs_map_split_params_default", "hs_map_reads_split", "hs_map_segments_destroy", "hs_map_split_to_batch", "hs_map_segments_text",
+    "hs_map_anchor_params_default", "hs_map_reads_anchored", "hs_map_anchors_destroy", "hs_realign_intervals_anchored", "hs_map_to_batch_anchored",
 ]
 
 HS_NKERNELS = 28
@@ -143,6 +144,17 @@ class MapSegments(C.Structure):
                    ("t_minimizers_ms", C.c_double), ("t_hits_ms", C.c_double), ("t_vote_ms", C.c_double)])
 
 
+class MapAnchorParams(C.Structure):
+    """hs_map_anchor_params"""
+    _fields_ = [("spacing", C.c_int32)]
+
+
+class MapAnchors(C.Structure):
+    """hs_map_anchors"""
+    _fields_ = [("n_reads", C.c_int32), ("n_anchors", C.c_int64), ("anc_off", C.POINTER(C.c_int64)), ("anc_q", C.POINTER(C.c_int32)), ("anc_t", C.POINTER(C.c_int32)),
+                ("n_best", C.POINTER(C.c_int32)), ("n_chain", C.POINTER(C.c_int32)), ("n_supported", C.POINTER(C.c_int32)), ("t_anchors_ms", C.c_double)]
+
+
 HS_RECRUIT_ABSENT, HS_RECRUIT_UNCLUSTERED, HS_RECRUIT_LABELLED = 1, 2, 4
 # hs_recruit_row (40 bytes)
 RECRUIT_ROW = np.dtype([("read", "<i4"), ("label", "<i4"), ("best_group", "<i4"), ("second_group", "<i4"), ("m_best", "<u4"), ("x_best", "<u4"),
@@ -238,6 +250,14 @@ def load() -> C.CDLL:
     lib.hs_map_split_to_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MapSplitParams),
                                           C.POINTER(C.c_void_p), C.POINTER(C.POINTER(RealignRecords)), C.POINTER(C.POINTER(MapSegments))]
     lib.hs_map_segments_text.argtypes = [C.POINTER(MapSegments), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
+    lib.hs_map_anchor_params_default.restype = MapAnchorParams
+    lib.hs_map_anchors_destroy.restype = None
+    lib.hs_map_anchors_destroy.argtypes = [C.POINTER(MapAnchors)]
+    lib.hs_map_reads_anchored.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MapAnchorParams), C.POINTER(C.POINTER(MapResult)), C.POINTER(C.POINTER(MapAnchors))]
+    lib.hs_realign_intervals_anchored.argtypes = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3
+                                                  + [C.POINTER(C.POINTER(RealignRecords)), C.POINTER(C.c_void_p)])
+    lib.hs_map_to_batch_anchored.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MapAnchorParams), C.POINTER(C.c_void_p),
+                                             C.POINTER(C.POINTER(RealignRecords)), C.POINTER(C.POINTER(MapResult)), C.POINTER(C.POINTER(MapAnchors))]
     _lib = lib
     return lib
 
@@ -545,7 +565,7 @@ class RealignRecords(C.Structure):
                 ("rec_strand", C.POINTER(C.c_uint8)), ("rec_cig_off", C.POINTER(C.c_int64)), ("cigar", C.POINTER(C.c_uint32)),
                 ("n_dropped", C.c_int64), ("dropped", C.POINTER(C.c_int32)),
                 ("t_cut_ms", C.c_double), ("t_align_ms", C.c_double), ("t_cigar_ms", C.c_double), ("t_download_ms", C.c_double),
-                ("n_rounds", C.c_int64), ("move_bytes", C.c_int64), ("cigar_words", C.c_int64)]
+                ("n_rounds", C.c_int64), ("move_bytes", C.c_int64), ("cigar_words", C.c_int64), ("n_pieces", C.c_int64), ("t_join_ms", C.c_double)]
 
 
 def _realign_records_to_dict(res) -> Dict:
@@ -557,7 +577,7 @@ def _realign_records_to_dict(res) -> Dict:
             "rec_interval": arr(r.rec_interval, n), "rec_read": arr(r.rec_read, n), "rec_pos": arr(r.rec_pos, n), "rec_dist": arr(r.rec_dist, n),
             "rec_strand": arr(r.rec_strand, n), "rec_cig_off": off, "cigar": arr(r.cigar, off[-1]), "n_dropped": int(r.n_dropped), "dropped": arr(r.dropped, r.n_dropped),
             "t_cut_ms": float(r.t_cut_ms), "t_align_ms": float(r.t_align_ms), "t_cigar_ms": float(r.t_cigar_ms), "t_download_ms": float(r.t_download_ms),
-            "n_rounds": int(r.n_rounds), "move_bytes": int(r.move_bytes), "cigar_words": int(r.cigar_words)}
+            "n_rounds": int(r.n_rounds), "move_bytes": int(r.move_bytes), "cigar_words": int(r.cigar_words), "n_pieces": int(r.n_pieces), "t_join_ms": float(r.t_join_ms)}
 
 
 class CvSelection(C.Structure):
@@ -2249,3 +2269,91 @@ def map_segments_text(res: Dict, read_lengths, contig_lengths, read_names=None, 
         return text.value.decode()
     finally:
         lib.hs_free_host(text)
+
+
+# ---- anchored alignment (hs_map_reads_anchored, hs_realign_intervals_anchored): mapped reads cut at seed anchors before A1 ----
+MAP_ANCHOR_READ_FIELDS = ("n_best", "n_chain", "n_supported")
+
+
+def map_anchor_params(**kw) -> MapAnchorParams:
+    """hs_map_anchor_params_default with the given fields replaced"""
+    p = load().hs_map_anchor_params_default()
+    for k, v in kw.items():
+        if k not in dict(MapAnchorParams._fields_):
+            raise HsError("map_anchor_params: no field " + k)
+        setattr(p, k, int(v))
+    return p
+
+
+def _map_anchors_to_dict(a) -> Dict:
+    res = a.contents
+    n, m = int(res.n_reads), int(res.n_anchors)
+    out = {k: np.ctypeslib.as_array(getattr(res, k), shape=(m,)).copy() if m else np.zeros(0, np.int32) for k in ("anc_q", "anc_t")}
+    out.update({k: np.ctypeslib.as_array(getattr(res, k), shape=(n,)).copy() if n else np.zeros(0, np.int32) for k in MAP_ANCHOR_READ_FIELDS})
+    out["anc_off"] = np.ctypeslib.as_array(res.anc_off, shape=(n + 1,)).copy()
+    out["t_anchors_ms"] = float(res.t_anchors_ms)
+    return out
+
+
+def map_reads_anchored(index: MapIndex, reads, params: Optional[MapAnchorParams] = None):
+    """hs_map_reads_anchored: (map result dict as map_reads gives it, anchors dict): anc_off [n_reads + 1], anc_q (on the read as it aligns) and anc_t
+    per anchor, n_best / n_chain / n_supported per read. reads: a list of code arrays, or a (codes, offsets) pair."""
+    lib = load()
+    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
+    r = C.POINTER(MapResult)(); a = C.POINTER(MapAnchors)()
+    _check(lib.hs_map_reads_anchored(index._h, rseq.ctypes.data, roff.ctypes.data, C.c_int32(len(roff) - 1), C.byref(params) if params is not None else None, C.byref(r), C.byref(a)))
+    try:
+        return _map_result_to_dict(r), _map_anchors_to_dict(a)
+    finally:
+        lib.hs_map_result_destroy(r)
+        lib.hs_map_anchors_destroy(a)
+
+
+def realign_intervals_anchored(flat_sequences, intervals, anc_off, anc_q, anc_t, pad: int = 100, want_batch: bool = True):
+    """hs_realign_intervals_anchored: realign_intervals with the anchors of every interval given (anc_off [n_intervals + 1]; anc_q on the read as it
+    aligns, anc_t on the contig). Every alignment is a cheapest one through its anchors, not edlib's HW optimum. Returns (records dict, CvBatch or None)."""
+    import time
+    require_gpu()
+    lib = load()
+    g = (lambda k: flat_sequences[k]) if isinstance(flat_sequences, dict) else (lambda k: getattr(flat_sequences, k))
+    cseq, coff, rseq, roff = _np(g("contig_seq"), np.uint8), _np(g("contig_off"), np.int64), _np(g("read_seq"), np.uint8), _np(g("read_off"), np.int64)
+    iv = np.asarray(intervals, dtype=np.int64).reshape(-1, 7)
+    if iv.size and (np.abs(iv).max() > 0x7fffffff):
+        raise HsError("realign_intervals_anchored: interval fields are 32-bit")
+    col = [_np(iv[:, k], np.uint8 if k == 2 else np.int32) for k in range(7)]
+    aoff, aq, at = _np(anc_off, np.int64), _np(anc_q, np.int32), _np(anc_t, np.int32)
+    if len(aoff) != len(iv) + 1 or len(aq) != len(at) or (len(aoff) and int(aoff[-1]) > len(aq)):
+        raise HsError("realign_intervals_anchored: anc_off has one entry per interval and one more, anc_q and anc_t anc_off[-1] entries")
+    h = C.c_void_p(); r = C.POINTER(RealignRecords)()
+    t0 = time.perf_counter()
+    _check(lib.hs_realign_intervals_anchored(cseq.ctypes.data, coff.ctypes.data, C.c_int32(len(coff) - 1), rseq.ctypes.data, roff.ctypes.data, C.c_int32(len(roff) - 1),
+                                             *[c.ctypes.data for c in col], C.c_int32(len(iv)), C.c_int32(pad), aoff.ctypes.data, aq.ctypes.data, at.ctypes.data,
+                                             C.byref(r), C.byref(h) if want_batch else None))
+    dt = time.perf_counter() - t0
+    try:
+        rec = _realign_records_to_dict(r)
+    finally:
+        lib.hs_realign_records_destroy(r)
+    return rec, (CvBatch._adopt(h, dt, rec) if want_batch else None)
+
+
+def map_to_batch_anchored(index: MapIndex, reads, params: Optional[MapAnchorParams] = None, pad: int = 100):
+    """hs_map_to_batch_anchored: map_reads_anchored, then realign_intervals_anchored on the mapped reads with their anchors. Returns (CvBatch, records
+    dict, map result dict, anchors dict)."""
+    import time
+    lib = load()
+    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
+    h = C.c_void_p(); rec = C.POINTER(RealignRecords)(); r = C.POINTER(MapResult)(); a = C.POINTER(MapAnchors)()
+    t0 = time.perf_counter()
+    _check(lib.hs_map_to_batch_anchored(index._h, index.contig_seq.ctypes.data, index.contig_off.ctypes.data, C.c_int32(len(index.contig_off) - 1), rseq.ctypes.data, roff.ctypes.data,
+                                        C.c_int32(len(roff) - 1), C.c_int32(pad), C.byref(params) if params is not None else None, C.byref(h), C.byref(rec), C.byref(r), C.byref(a)))
+    dt = time.perf_counter() - t0
+    try:
+        records = _realign_records_to_dict(rec)
+        res = _map_result_to_dict(r)
+        anc = _map_anchors_to_dict(a)
+    finally:
+        lib.hs_realign_records_destroy(rec)
+        lib.hs_map_result_destroy(r)
+        lib.hs_map_anchors_destroy(a)
+    return CvBatch._adopt(h, dt, records), records, res, anc

@@ -2,7 +2,8 @@
 // in hs_kernels_map.hip, the rule and the host half in hs_map_host.h / hs_map_host.cpp. An index call waits twice (the number of minimizers, which
 // sizes the entries; the end), a map call three times (the minimizers, then the hits -- each total sizes what follows --, then the records: one
 // block, one shipment). A split call (hs_map_reads_split) waits three times as well: its segments are compacted on the device and leave in the same
-// shipment, their number read there. Sequences go up by the runtime's upload_pageable. Launches are accounted under HS_K_OTHER.
+// shipment, their number read there; so does an anchored call (hs_map_reads_anchored), whose anchors leave the same way. Sequences go up by the
+// runtime's upload_pageable. Launches are accounted under HS_K_OTHER.
 struct hs_map_index {
     hs_map_params params{};
     int32_t n_contigs = 0, bucket_bits = 0;
@@ -54,13 +55,16 @@ struct MapMinimizersDev {
 // The parts of a map call's output block: the per-read records under the names hs_map_result gives them, then what a call clears -- n_skipped,
 // the wide route's counter, the word of the largest read -- side by side (one clearing). Up to `shipped` the block goes to the host in one
 // shipment and lands there at the same offsets; behind it lies the wide route's list [R].
+// An anchored call (hs_map_reads_anchored) adds n_best, n_chain and n_supported per read at the end of the shipped part and, behind the list, the
+// anchor count of every read and the best key the vote leaves for k_map_anchors (8 bytes per read); its anchors lie in blocks of their own.
 // A split call (hs_map_reads_split) has no per-read records: in their place round 0's vote per read (votes, second -- cleared with the rest, a read
 // without a hit keeps the zeros) and, behind the shipped part, the segment count of every read (cleared too). Its segments lie in blocks of their own.
 struct MapWork {
     int64_t contig, strand, qstart, qend, tstart, tend, votes, second, n_minimizers, n_hits, n_skipped, wide_count, max_hits, shipped, wide_list, total_bytes;
     int64_t clear_from, clear_to, seg_count;
+    int64_t n_best, n_chain, n_supported, anc_count, best_key;      // an anchored call (hs_map_reads_anchored) only
 };
-static MapWork map_work(int32_t n_reads, bool split = false) {
+static MapWork map_work(int32_t n_reads, bool split = false, bool anchored = false) {
     const int64_t R = n_reads;
     MapWork m{};
     WorkParts p;
@@ -72,10 +76,12 @@ static MapWork map_work(int32_t n_reads, bool split = false) {
     m.clear_from = p.o;
     if (split) { m.votes = p.take(R * 4); m.second = p.take(R * 4); }
     m.n_skipped = p.take(R * 4); m.wide_count = p.take(4); m.max_hits = p.take(16);
+    if (anchored) { m.n_best = p.take(R * 4); m.n_chain = p.take(R * 4); m.n_supported = p.take(R * 4); }      // (k_map_anchors writes every read's: nothing to clear)
     m.shipped = p.o;
     if (split) m.seg_count = p.take(R * 4);
     m.clear_to = p.o;
     m.wide_list = p.take(R * 4);
+    if (anchored) { m.anc_count = p.take(R * 4); m.best_key = p.take(R * 8); }
     m.total_bytes = p.o;
     return m;
 }
@@ -156,10 +162,13 @@ int hs_map_index_download(const hs_map_index* index, int64_t* n_entries, int32_t
 // the split rule and the segments' compaction on the device. Either way three waits: the segments leave in the same shipment as the per-read block,
 // their number read on the device when the shipment runs (the host block has room for max_segments per read).
 static int map_reads_impl(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, const hs_map_split_params* split, hs_map_result** result,
-                          hs_map_segments** segments, const std::string& who) {
+                          hs_map_segments** segments, const std::string& who, const hs_map_anchor_params* anchor = nullptr, hs_map_anchors** anchors = nullptr) {
     if (int rc = require_device()) return rc;
     if (!index || (split ? !segments : !result) || !h_read_off || n_reads < 0) { set_error(who + ": bad arguments"); return HS_EINVAL; }
     if (split) *segments = nullptr; else *result = nullptr;
+    if (anchor && (split || !anchors)) { set_error(who + ": bad arguments"); return HS_EINVAL; }
+    if (anchor) *anchors = nullptr;
+    if (anchor && !hs::map_anchor_params_valid(*anchor)) { set_error(who + ": anchor parameters out of range (spacing >= 1)"); return HS_EINVAL; }
     if (split && !hs::map_split_params_valid(*split)) { set_error(who + ": split parameters out of range (max_segments 1..8, min_votes >= 1, min_span >= 0, max_gap >= 0)"); return HS_EINVAL; }
     if (int rc = map_check_offsets(h_read_off, n_reads, who.c_str())) return rc;
     const int64_t total = h_read_off[n_reads];
@@ -169,9 +178,9 @@ static int map_reads_impl(const hs_map_index* index, const uint8_t* h_read_seq, 
         const hipStream_t st = nullptr;
         const size_t R = (size_t)n_reads;
         KernelClock kc;
-        EventPair ev_mz, ev_hits, ev_vote;
-        for (EventPair* e : {&ev_mz, &ev_hits, &ev_vote}) if (int rc = e->init()) return rc;
-        DBuf d_seq, d_off, d_mz_off, d_cnt, d_hit_off, d_scan, d_key, d_qa, d_t, d_slabs, d_out, d_seg_off, d_staged, d_segs;
+        EventPair ev_mz, ev_hits, ev_vote, ev_anc;
+        for (EventPair* e : {&ev_mz, &ev_hits, &ev_vote, &ev_anc}) if (int rc = e->init()) return rc;
+        DBuf d_seq, d_off, d_mz_off, d_cnt, d_hit_off, d_scan, d_key, d_qa, d_t, d_slabs, d_out, d_seg_off, d_staged, d_segs, d_stage_q, d_stage_t, d_anc_off, d_anc_q, d_anc_t;
         if (int rc = upload_pageable(d_seq, h_read_seq, (size_t)total, 0, MAP_SLACK)) return rc;
         if (int rc = upload_pageable(d_off, h_read_off, (R + 1) * 8, 0, MAP_SLACK)) return rc;
         // ---- minimizers and every read's range of them (one wait: their total) ----
@@ -187,7 +196,7 @@ static int map_reads_impl(const hs_map_index* index, const uint8_t* h_read_seq, 
                 return HS_OK; })) return rc;
         const int64_t M = mz.n;
         // ---- occ of every minimizer, the hits' offsets, (one wait: their total and the most a read has), the hits ----
-        const MapWork w = map_work(n_reads, split != nullptr);
+        const MapWork w = map_work(n_reads, split != nullptr, anchor != nullptr);
         if (int rc = d_out.alloc((size_t)w.total_bytes)) return rc;
         char* out = (char*)d_out.p;
         if (int rc = d_cnt.alloc((size_t)std::max<int64_t>(M, 1) * 4)) return rc;
@@ -230,6 +239,7 @@ static int map_reads_impl(const hs_map_index* index, const uint8_t* h_read_seq, 
         }
         A.votes = (int32_t*)(out + w.votes); A.second = (int32_t*)(out + w.second);
         A.wide_list = (int32_t*)(out + w.wide_list); A.wide_count = (int32_t*)(out + w.wide_count);
+        if (anchor) A.best_key = (uint64_t*)(out + w.best_key);
         // a split call: the rounds per read into a staging of max_segments per read, the counts' scan, the compaction
         const int64_t seg_cap = split ? (int64_t)R * split->max_segments : 0;
         const size_t seg_bytes = (size_t)HS_MAP_SEG_WORDS * 4;
@@ -255,8 +265,26 @@ static int map_reads_impl(const hs_map_index* index, const uint8_t* h_read_seq, 
                                                     d_staged.as<int32_t>(), n_reads, split->max_segments, (long long)seg_cap, d_segs.as<int32_t>());
                 HS_HIP(hipGetLastError());
                 return HS_OK; })) return rc;
+        // an anchored call: the cut points of every read staged at its upper bound, the counts' scan, the compaction
+        const int64_t anc_cap = anchor ? hs::map_anchor_stage_at(total, (int64_t)R, anchor->spacing) : 0;
+        if (anchor) {
+            if (anc_cap > 0x7fffffff) { set_error(who + ": room for more than 2^31 anchors in one call: map the reads in several calls"); return HS_EINVAL; }
+            for (DBuf* b : {&d_stage_q, &d_stage_t, &d_anc_q, &d_anc_t}) if (int rc = b->alloc((size_t)std::max<int64_t>(anc_cap, 1) * 4 + MAP_SLACK)) return rc;
+            if (int rc = d_anc_off.alloc((R + 1) * 8)) return rc;
+            hsdev::MapAnchorArgs B2{};
+            B2.P = *anchor; B2.stage_q = d_stage_q.as<int32_t>(); B2.stage_t = d_stage_t.as<int32_t>(); B2.stage_cap = (long long)anc_cap;
+            B2.anc_count = (int32_t*)(out + w.anc_count); B2.n_best = (int32_t*)(out + w.n_best); B2.n_chain = (int32_t*)(out + w.n_chain); B2.n_supported = (int32_t*)(out + w.n_supported);
+            if (int rc = timed_launch(kc, ev_anc, st, 16 * H + 8 * anc_cap + 24 * (int64_t)R, [&]() -> int {
+                    if (R) hipLaunchKernelGGL(hsdev::k_map_anchors, dim3((unsigned)R), dim3(256), 0, st, A, B2);
+                    HS_HIP(hipGetLastError());
+                    if (int rc = exclusive_scan_launch(B2.anc_count, n_reads, d_anc_off.as<int64_t>(), d_scan, st)) return rc;
+                    if (R) hipLaunchKernelGGL(hsdev::k_map_anchor_compact, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, B2.anc_count, d_anc_off.as<int64_t>(), d_off.as<int64_t>(), n_reads,
+                                              anchor->spacing, d_stage_q.as<int32_t>(), d_stage_t.as<int32_t>(), (long long)anc_cap, (long long)anc_cap, d_anc_q.as<int32_t>(), d_anc_t.as<int32_t>());
+                    HS_HIP(hipGetLastError());
+                    return HS_OK; })) return rc;
+        }
         // ---- the records: one shipment to one pinned block (one wait), the result's arrays filled from it ----
-        HBuf h_out, h_seg_off, h_segs;
+        HBuf h_out, h_seg_off, h_segs, h_anc_off, h_anc_q, h_anc_t;
         if (int rc = h_out.alloc((size_t)w.shipped)) return rc;
         Shipment sh;
         sh.add(h_out.p, out, (size_t)w.shipped);
@@ -265,6 +293,15 @@ static int map_reads_impl(const hs_map_index* index, const uint8_t* h_read_seq, 
             if (int rc = h_segs.alloc((size_t)std::max<int64_t>(seg_cap, 1) * seg_bytes + MAP_SLACK)) return rc;
             sh.add(h_seg_off.p, d_seg_off.p, (R + 1) * 8);
             if (seg_cap > 0) sh.add_counted(h_segs.p, d_segs.p, (const long long*)(d_seg_off.as<int64_t>() + R), seg_bytes, (long long)seg_cap);
+        }
+        if (anchor) {
+            if (int rc = h_anc_off.alloc((R + 1) * 8 + 16)) return rc;
+            for (HBuf* b : {&h_anc_q, &h_anc_t}) if (int rc = b->alloc((size_t)std::max<int64_t>(anc_cap, 1) * 4 + MAP_SLACK)) return rc;
+            sh.add(h_anc_off.p, d_anc_off.p, (R + 1) * 8);
+            if (anc_cap > 0) {
+                sh.add_counted(h_anc_q.p, d_anc_q.p, (const long long*)(d_anc_off.as<int64_t>() + R), 4, (long long)anc_cap);
+                sh.add_counted(h_anc_t.p, d_anc_t.p, (const long long*)(d_anc_off.as<int64_t>() + R), 4, (long long)anc_cap);
+            }
         }
         if (int rc = sh.launch(st)) return rc;
         if (int rc = stream_wait(st)) return rc;
@@ -321,6 +358,25 @@ static int map_reads_impl(const hs_map_index* index, const uint8_t* h_read_seq, 
         if (ev_mz.ms(&ms) == HS_OK) r->t_minimizers_ms = ms;
         if (ev_hits.ms(&ms) == HS_OK) r->t_hits_ms = ms;
         if (ev_vote.ms(&ms) == HS_OK) r->t_vote_ms = ms;
+        if (anchor) {
+            const int64_t* ao = (const int64_t*)h_anc_off.p;
+            const int64_t N = ao[R];
+            bool ok = ao[0] == 0 && N >= 0 && N <= anc_cap;
+            for (size_t i = 0; ok && i < R; ++i) ok = ao[i + 1] >= ao[i] && ao[i + 1] - ao[i] <= hs::map_anchor_bound(h_read_off[i + 1] - h_read_off[i], anchor->spacing);
+            if (!ok) { hs_map_result_destroy(r); set_error(who + ": the device's anchor counts do not fit the reads"); return HS_EHIP; }
+            hs_map_anchors* a = (hs_map_anchors*)std::calloc(1, sizeof(hs_map_anchors));
+            if (!a) { hs_map_result_destroy(r); set_error(who + ": out of memory"); return HS_EINVAL; }
+            a->n_reads = n_reads; a->n_anchors = N;
+            auto room = [&](auto*& dst, size_t n, const void* src) {
+                dst = (decltype(+dst))std::calloc(std::max<size_t>(1, n), sizeof *dst);
+                if (!dst) oom = true; else if (n) std::memcpy(dst, src, n * sizeof *dst);
+            };
+            room(a->anc_off, R + 1, ao); room(a->anc_q, (size_t)N, h_anc_q.p); room(a->anc_t, (size_t)N, h_anc_t.p);
+            room(a->n_best, R, hp + w.n_best); room(a->n_chain, R, hp + w.n_chain); room(a->n_supported, R, hp + w.n_supported);
+            if (oom) { hs_map_anchors_destroy(a); hs_map_result_destroy(r); set_error(who + ": out of memory"); return HS_EINVAL; }
+            if (ev_anc.ms(&ms) == HS_OK) a->t_anchors_ms = ms;
+            *anchors = a;
+        }
         kc.flush();
         *result = r;
         return HS_OK;
@@ -334,6 +390,12 @@ int hs_map_reads(const hs_map_index* index, const uint8_t* h_read_seq, const int
 int hs_map_reads_split(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, const hs_map_split_params* split, hs_map_segments** segments) {
     const hs_map_split_params sp = split ? *split : hs_map_split_params_default();
     return map_reads_impl(index, h_read_seq, h_read_off, n_reads, &sp, nullptr, segments, "hs_map_reads_split");
+}
+
+int hs_map_reads_anchored(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, const hs_map_anchor_params* params, hs_map_result** result,
+                          hs_map_anchors** anchors) {
+    const hs_map_anchor_params ap = params ? *params : hs_map_anchor_params_default();
+    return map_reads_impl(index, h_read_seq, h_read_off, n_reads, nullptr, result, nullptr, "hs_map_reads_anchored", &ap, anchors);
 }
 
 int hs_map_to_batch(const hs_map_index* index, const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off,
@@ -361,6 +423,41 @@ int hs_map_to_batch(const hs_map_index* index, const uint8_t* h_contig_seq, cons
         if (result) *result = mr; else hs_map_result_destroy(mr);
         return HS_OK;
     } catch (const std::exception& e) { hs_map_result_destroy(mr); set_error(std::string("hs_map_to_batch: ") + e.what()); return HS_EINVAL; }
+}
+
+int hs_map_to_batch_anchored(const hs_map_index* index, const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off,
+                             int32_t n_reads, int32_t pad, const hs_map_anchor_params* params, hs_cv_batch** batch, hs_realign_records** records, hs_map_result** result,
+                             hs_map_anchors** anchors) {
+    if (int rc = require_device()) return rc;
+    if (!index || !batch || !h_contig_off || n_contigs != index->n_contigs) { set_error("hs_map_to_batch_anchored: bad arguments (the contigs are the index's)"); return HS_EINVAL; }
+    *batch = nullptr;
+    if (records) *records = nullptr;
+    if (result) *result = nullptr;
+    if (anchors) *anchors = nullptr;
+    hs_map_result* mr = nullptr;
+    hs_map_anchors* an = nullptr;
+    if (int rc = hs_map_reads_anchored(index, h_read_seq, h_read_off, n_reads, params, &mr, &an)) return rc;
+    int rc = HS_OK;
+    try {
+        std::vector<int32_t> iv_read, iv_contig, qs, qe, ts, te, aq, at;
+        std::vector<uint8_t> strand;
+        std::vector<int64_t> aoff(1, 0);
+        for (int32_t i = 0; i < n_reads; ++i) {
+            if (mr->contig[i] < 0) continue;
+            iv_read.push_back(i); iv_contig.push_back(mr->contig[i]); strand.push_back(mr->strand[i]);
+            qs.push_back(mr->qstart[i]); qe.push_back(mr->qend[i]); ts.push_back(mr->tstart[i]); te.push_back(mr->tend[i]);
+            aq.insert(aq.end(), an->anc_q + an->anc_off[i], an->anc_q + an->anc_off[i + 1]);
+            at.insert(at.end(), an->anc_t + an->anc_off[i], an->anc_t + an->anc_off[i + 1]);
+            aoff.push_back((int64_t)aq.size());
+        }
+        hs_realign_records* rec = nullptr;
+        rc = hs_realign_intervals_anchored(h_contig_seq, h_contig_off, n_contigs, h_read_seq, h_read_off, n_reads, iv_read.data(), iv_contig.data(), strand.data(), qs.data(), qe.data(),
+                                           ts.data(), te.data(), (int32_t)iv_read.size(), pad, aoff.data(), aq.data(), at.data(), &rec, batch);
+        if (rc == HS_OK) { if (records) *records = rec; else hs_realign_records_destroy(rec); }
+    } catch (const std::exception& e) { set_error(std::string("hs_map_to_batch_anchored: ") + e.what()); rc = HS_EINVAL; }
+    if (rc == HS_OK && result) *result = mr; else hs_map_result_destroy(mr);
+    if (rc == HS_OK && anchors) *anchors = an; else hs_map_anchors_destroy(an);
+    return rc;
 }
 
 int hs_map_split_to_batch(const hs_map_index* index, const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off,

@@ -18,6 +18,12 @@
 //                                  overlap no seed span taken so far (spans and gap counters in LDS, the free hits' keys compacted by a ballot
 //                                  prefix and an LDS cursor, only that many sorted); a round without a free hit costs one pass over the hits
 //   k_map_seg_compact              the reads' staged segments side by side (behind exclusive_scan_launch over their counts)
+//   k_map_anchors                  the opt-in anchors (hs_map_host.h, "anchors"), behind the vote and in k_map_vote_split's arrangement: a workgroup per
+//                                  read compacts the best's (qa, t) into LDS (ballot prefix, LDS cursor), sorts them under the chain's order, tests
+//                                  "t already strictly increasing" in parallel (else one lane runs the patience pass: tails and 16-bit predecessor
+//                                  links in LDS), lays the supported members side by side in parallel (ballot prefix), and one lane finds each next
+//                                  cut among them by search and writes the read's staging
+//   k_map_anchor_compact           the staged cut points side by side (behind exclusive_scan_launch over their counts), a wavefront per read
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -181,6 +187,7 @@ struct MapVoteArgs {
     hs_map_params P;
     int32_t* contig; uint8_t* strand; int32_t* qstart; int32_t* qend; int32_t* tstart; int32_t* tend; int32_t* votes; int32_t* second;
     int32_t* wide_count; int32_t* wide_list;
+    uint64_t* best_key;      // [n_reads] or null: where the vote leaves a read's best key for k_map_anchors
 };
 
 // the block's best (score, key) under the rule's order; every thread calls it and gets the result. sc == 0: no candidate
@@ -260,6 +267,7 @@ static __device__ bool map_vote_one(const MapVoteArgs& A, int r, uint64_t* keys,
         const int32_t Lr = (int32_t)(A.read_off[r + 1] - A.read_off[r]);
         hs::map_interval(A.P, v, Lr, Lc, &A.contig[r], &A.strand[r], &A.qstart[r], &A.qend[r], &A.tstart[r], &A.tend[r]);
         A.votes[r] = (int32_t)v.best; A.second[r] = (int32_t)v.second;
+        if (A.best_key) A.best_key[r] = v.key;
     }
     __syncthreads();
     return true;
@@ -433,6 +441,98 @@ __global__ __launch_bounds__(256) void k_map_seg_compact(const int32_t* __restri
     const long long o = seg_off[r] + j;
     if (o < 0 || o >= cap) return;      // never write beyond the staging's size
     for (int w = 0; w < HS_MAP_SEG_WORDS; ++w) out[o * HS_MAP_SEG_WORDS + w] = staged[idx * HS_MAP_SEG_WORDS + w];
+}
+
+
+// ---- anchors (hs_map_host.h, "anchors"): the cut points of every mapped read of the LDS route ----
+static_assert(HS_MAP_ANCHOR_CAPACITY == HS_MAP_LDS_KEYS, "a read of the LDS route has anchors; a read of the wide route has none");
+struct MapAnchorArgs {
+    hs_map_anchor_params P;
+    int32_t* stage_q; int32_t* stage_t; long long stage_cap;      // read r's cut points from map_anchor_stage_at on, map_anchor_bound of them at most
+    int32_t* anc_count; int32_t* n_best; int32_t* n_chain; int32_t* n_supported;      // [n_reads]
+};
+
+__global__ __launch_bounds__(256) void k_map_anchors(MapVoteArgs A, MapAnchorArgs B) {
+    __shared__ uint64_t s_keys[HS_MAP_LDS_KEYS];
+    __shared__ uint16_t s_chain[HS_MAP_LDS_KEYS];      // the patience tails, then the chain's members (indices into s_keys)
+    __shared__ uint16_t s_pred[HS_MAP_LDS_KEYS];       // predecessor links, then the supported members side by side
+    __shared__ int32_t s_n, s_falls, s_len, s_w[4];
+    const int r = (int)blockIdx.x;
+    if (r >= A.n_reads) return;
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x, lane = tid & 63;
+    long long h0 = A.hit_off[A.mz_off[r]], h1 = A.hit_off[A.mz_off[r + 1]];
+    if (h0 < 0 || h1 > A.n_hits || h1 < h0) h1 = h0 = 0;
+    const long long n64 = h1 - h0;
+    if (A.contig[r] < 0 || n64 > HS_MAP_LDS_KEYS) {      // (the same in every thread) unmapped, or the wide route's: no anchors
+        if (tid == 0) { B.anc_count[r] = 0; B.n_best[r] = 0; B.n_chain[r] = 0; B.n_supported[r] = 0; }
+        return;
+    }
+    const int n = (int)n64;
+    const uint64_t best = A.best_key[r];
+    if (tid == 0) { s_n = 0; s_falls = 0; s_len = 0; }
+    __syncthreads();
+    for (int base = 0; base < n; base += nt) {      // (every lane takes every turn: the ballot)
+        const int i = base + tid;
+        bool in = false;
+        uint64_t key = 0;
+        if (i < n && hs::map_in_best(A.hit_key[h0 + i], best)) { in = true; key = hs::map_anchor_key(A.hit_qa[h0 + i], A.hit_t[h0 + i]); }
+        const unsigned long long b = __ballot(in);
+        int at = 0;
+        if (lane == 0 && b) at = atomicAdd(&s_n, __popcll(b));
+        at = __shfl(at, 0, 64);
+        if (in) s_keys[at + __popcll(b & ((1ull << lane) - 1ull))] = key;      // (at most n keys)
+    }
+    __syncthreads();
+    const int nb = s_n, n_pow2 = pow2_at_least(nb);
+    for (int i = nb + tid; i < n_pow2; i += nt) s_keys[i] = ~0ull;
+    __syncthreads();
+    block_bitonic_sort(s_keys, n_pow2);
+    bool falls = false;
+    for (int i = 1 + tid; i < nb; i += nt) falls = falls || !hs::map_anchor_rises(s_keys, i);
+    if (falls) atomicOr(&s_falls, 1);
+    __syncthreads();
+    if (!s_falls) {
+        for (int i = tid; i < nb; i += nt) s_chain[i] = (uint16_t)i;
+        if (tid == 0) s_len = nb;
+    } else if (tid == 0) s_len = hs::map_anchor_chain(s_keys, nb, s_chain, s_pred);
+    __syncthreads();
+    const int len = s_len;
+    int n_sup = 0;      // (the same in every thread) the supported members side by side in chain order, where the predecessor links were
+    for (int base = 0; base < len; base += nt) {      // (every lane takes every turn: the ballot)
+        const int j = base + tid;
+        const bool s = j < len && hs::map_anchor_supported(s_keys, s_chain, len, j);
+        const uint16_t me = j < len ? s_chain[j] : (uint16_t)0;
+        const unsigned long long b = __ballot(s);
+        if (lane == 0) s_w[tid >> 6] = __popcll(b);
+        __syncthreads();
+        int at = n_sup + __popcll(b & ((1ull << lane) - 1ull));
+        for (int v = 0; v < (tid >> 6); ++v) at += s_w[v];
+        if (s) s_pred[at] = me;      // (at <= j: within the chain's length)
+        n_sup += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const long long Lr = A.read_off[r + 1] - A.read_off[r];
+        const long long at = hs::map_anchor_stage_at(A.read_off[r], r, B.P.spacing);
+        long long cap = hs::map_anchor_bound(Lr, B.P.spacing);
+        if (at < 0 || at >= B.stage_cap) cap = 0; else if (at + cap > B.stage_cap) cap = B.stage_cap - at;      // never write beyond the staging
+        B.anc_count[r] = cap > 0 ? hs::map_anchor_cuts(s_keys, s_pred, n_sup, B.P.spacing, B.stage_q + at, B.stage_t + at, cap) : 0;
+        B.n_best[r] = nb; B.n_chain[r] = len; B.n_supported[r] = n_sup;
+    }
+}
+
+// the staged cut points of every read, side by side at the offsets the scan of anc_count gave: a wavefront per read
+__global__ __launch_bounds__(256) void k_map_anchor_compact(const int32_t* __restrict__ anc_count, const int64_t* __restrict__ anc_off, const int64_t* __restrict__ read_off, int n_reads,
+                                                            int spacing, const int32_t* __restrict__ stage_q, const int32_t* __restrict__ stage_t, long long stage_cap, long long cap,
+                                                            int32_t* __restrict__ out_q, int32_t* __restrict__ out_t) {
+    const int r = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    if (r >= n_reads) return;
+    const long long at = hs::map_anchor_stage_at(read_off[r], r, spacing), o = anc_off[r];
+    const int n = anc_count[r];
+    for (int j = lane; j < n; j += 64) {
+        if (at + j < 0 || at + j >= stage_cap || o + j < 0 || o + j >= cap) continue;      // never read or write beyond either block
+        out_q[o + j] = stage_q[at + j]; out_t[o + j] = stage_t[at + j];
+    }
 }
 
 }  // namespace hsdev

@@ -235,4 +235,117 @@ __global__ __launch_bounds__(256) void k_realign_pos(const int32_t* __restrict__
     if (i < n) pos[i] = win0[i] + start[i];
 }
 
+// ------------------------------------------------------------------------------------------------
+// The anchored route (hs_realign_intervals_anchored): an interval cut at its anchors is aligned as pieces -- a head (SHW on the two
+// reversed strings), middles (NW), a tail (SHW), or one HW pair without anchors; a head or tail whose target is empty is a run of
+// insertions and never reaches the aligner. The pieces of all intervals lie in one table in (interval, head .. tail) order; the three
+// aligner calls leave their results in sections of the same arrays, so a piece names its moves by one offset and its numbers by one index.
+//   k_anchor_join_plan   a lane per interval: where each piece's moves go inside the interval's string, their total, the summed distance
+//                        and POS = the first anchor's t minus the target bases the head consumed (HW: window start + start location). An
+//                        interval with a piece the aligner has no path for gets length -1 (no record, as on the plain route)
+//   k_anchor_join        k_realign_cut's arrangement: a workgroup owns a 4096-byte aligned window of the joined strings, a lane an aligned
+//                        16-byte block that it stores whole. A block inside one piece is one unaligned 16-byte load (a head's read
+//                        backwards and its bytes turned), a block over a boundary is assembled byte by byte; bytes behind an interval's
+//                        moves are 0. The joined strings lie at the host's offsets (an interval's room = query + window bases), as
+//                        k_m2c_count / k_m2c_write take them.
+// ------------------------------------------------------------------------------------------------
+enum { ANCHOR_HW = 0, ANCHOR_HEAD = 1, ANCHOR_MID = 2, ANCHOR_TAIL = 3, ANCHOR_INS = 4 };
+struct AnchorJoinArgs {
+    int m;                              // intervals of the round
+    const int32_t* iv_piece;            // [m + 1] an interval's pieces in the table
+    const int32_t* iv_base;             // [m] the first anchor's t (no anchors: the window's start)
+    const int64_t* join_off;            // [m + 1] where an interval's joined moves lie
+    const uint8_t* pc_kind; const int32_t* pc_idx /* its numbers; ANCHOR_INS: the run's length */; const int32_t* pc_room /* moves it has room for */; const int64_t* pc_ops /* its moves in `ops` */;
+    const uint8_t* ops; const int32_t* dist; const int32_t* start; const int32_t* end; const int32_t* len;
+    int32_t* pc_at;                     // [pieces] where a piece's moves begin inside its interval's string
+    int32_t* out_len; int32_t* out_dist; int32_t* out_pos;      // [m]
+    uint8_t* joined; int64_t joined_bytes;      // rounded up to 16
+};
+
+__global__ __launch_bounds__(256) void k_anchor_join_plan(AnchorJoinArgs J) {
+    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (k >= J.m) return;
+    const int p0 = J.iv_piece[k], p1 = J.iv_piece[k + 1];
+    const int64_t room = J.join_off[k + 1] - J.join_off[k];
+    int64_t at = 0, dist = 0;
+    bool ok = p1 > p0;
+    int pos = J.iv_base[k];
+    for (int p = p0; p < p1; ++p) {
+        const int kind = J.pc_kind[p], i = J.pc_idx[p];
+        int n = i;      // (ANCHOR_INS)
+        if (kind != ANCHOR_INS) {
+            n = J.len[i];
+            dist += J.dist[i];
+            if (kind == ANCHOR_HW) pos += J.start[i];
+            if (kind == ANCHOR_HEAD) pos -= J.end[i] + 1;
+        } else dist += n;
+        ok = ok && n > 0 && n <= J.pc_room[p];
+        J.pc_at[p] = (int32_t)at;
+        at += n > 0 ? n : 0;
+    }
+    ok = ok && at <= room;      // (a path never has more moves than query + target bases)
+    J.out_len[k] = ok ? (int32_t)at : -1; J.out_dist[k] = ok ? (int32_t)dist : -1; J.out_pos[k] = ok ? pos : -1;
+}
+
+// the last i in [lo, hi] with v[i] <= a (v[lo] <= a)
+static __device__ __forceinline__ int join_last_le(const int32_t* __restrict__ v, int lo, int hi, int a) {
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (v[mid] <= a) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+// move x of interval k's string (0 <= x < out_len[k]), p = a piece at or before it
+static __device__ __forceinline__ uint32_t join_byte(const AnchorJoinArgs& J, int p, int p1, int len_k, int x) {
+    while (p + 1 < p1 && J.pc_at[p + 1] <= x) ++p;
+    const int kind = J.pc_kind[p], in = x - J.pc_at[p];
+    if (kind == ANCHOR_INS) return 1u;
+    const int n = (p + 1 < p1 ? J.pc_at[p + 1] : len_k) - J.pc_at[p];
+    return J.ops[J.pc_ops[p] + (kind == ANCHOR_HEAD ? n - 1 - in : in)];
+}
+__global__ __launch_bounds__(256) void k_anchor_join(AnchorJoinArgs J) {
+    const int64_t win = (int64_t)blockIdx.x << 12;
+    const int64_t a = win + ((int64_t)threadIdx.x << 4);
+    if (a >= J.joined_bytes) return;
+    const int64_t total = J.join_off[J.m];
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (a < total) {
+        int k = cut_piece_of(J.join_off, 0, J.m - 1, a);
+        const int len_k = J.out_len[k];
+        const int64_t x64 = a - J.join_off[k];
+        const int p0 = J.iv_piece[k], p1 = J.iv_piece[k + 1];
+        int p = p0;
+        bool whole = false;
+        if (len_k > 0 && x64 + 16 <= len_k) {
+            p = join_last_le(J.pc_at, p0, p1 - 1, (int)x64);
+            whole = (p + 1 < p1 ? J.pc_at[p + 1] : len_k) >= (int)x64 + 16;
+        }
+        if (whole) {
+            const int kind = J.pc_kind[p], in = (int)x64 - J.pc_at[p];
+            if (kind == ANCHOR_INS) v = make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);
+            else {
+                const int n = (p + 1 < p1 ? J.pc_at[p + 1] : len_k) - J.pc_at[p];
+                uint32_t d[4];
+                load16_unaligned(J.ops + J.pc_ops[p] + (kind == ANCHOR_HEAD ? n - 16 - in : in), 16, d);
+                if (kind == ANCHOR_HEAD) {
+                    v.x = __builtin_amdgcn_perm(0u, d[3], 0x00010203u); v.y = __builtin_amdgcn_perm(0u, d[2], 0x00010203u);
+                    v.z = __builtin_amdgcn_perm(0u, d[1], 0x00010203u); v.w = __builtin_amdgcn_perm(0u, d[0], 0x00010203u);
+                } else v = make_uint4(d[0], d[1], d[2], d[3]);
+            }
+        } else {
+            uint32_t q[4] = {0u, 0u, 0u, 0u};
+            int kk = k, lk = len_k, pp = p0, pe = p1;
+            for (int j = 0; j < 16 && a + j < total; ++j) {
+                if (a + j >= J.join_off[kk + 1]) {
+                    while (a + j >= J.join_off[kk + 1]) ++kk;      // (a + j < total = join_off[m]: kk stays below m)
+                    lk = J.out_len[kk]; pp = J.iv_piece[kk]; pe = J.iv_piece[kk + 1];
+                }
+                const int64_t x = a + j - J.join_off[kk];
+                if (x >= lk) continue;
+                if (j == 0 || x == 0) pp = join_last_le(J.pc_at, J.iv_piece[kk], pe - 1, (int)x);
+                q[j >> 2] |= (join_byte(J, pp, pe, lk, (int)x) & 0xffu) << (8 * (j & 3));
+            }
+            v = make_uint4(q[0], q[1], q[2], q[3]);
+        }
+    }
+    *reinterpret_cast<uint4*>(J.joined + a) = v;
+}
+
 }  // namespace hsdev

@@ -109,7 +109,7 @@ void map_vote_keys(std::vector<uint64_t>& keys, bool want_second, MapVote& v) {
     }
 }
 
-void map_one_read(const MapIndexHost& ix, const uint8_t* seq, int64_t L, size_t r, MapResultHost& out, std::vector<Hit>& hits, std::vector<uint64_t>& keys) {
+void map_one_read(const MapIndexHost& ix, const uint8_t* seq, int64_t L, size_t r, MapResultHost& out, std::vector<Hit>& hits, std::vector<uint64_t>& keys, MapVote* vote = nullptr) {
     const hs_map_params& p = ix.params;
     map_read_hits(ix, seq, L, hits, &out.n_minimizers[r], &out.n_skipped[r]);
     keys.resize(hits.size());
@@ -126,6 +126,19 @@ void map_one_read(const MapIndexHost& ix, const uint8_t* seq, int64_t L, size_t 
     map_interval(p, v, (int32_t)L, Lc, &out.contig[r], &out.strand[r], &out.qstart[r], &out.qend[r], &out.tstart[r], &out.tend[r]);
     out.votes[r] = (int32_t)v.best; out.second[r] = (int32_t)v.second;
     out.n_hits[r] = (int64_t)hits.size();
+    if (vote) *vote = v;
+}
+
+// the anchors of one mapped read (hs_map_host.h, "anchors"): the best's hits as keys, then map_anchors_of_keys
+struct ReadAnchors { std::vector<int32_t> q, t; int32_t n_best = 0, n_chain = 0, n_supported = 0; };
+void map_anchors_one_read(const hs_map_anchor_params& ap, int64_t L, const std::vector<Hit>& hits, const MapVote& v, std::vector<uint64_t>& keys, ReadAnchors& a) {
+    a = ReadAnchors();
+    if (hits.size() > (size_t)HS_MAP_ANCHOR_CAPACITY) return;      // (the wide route: aligned the plain way)
+    keys.clear();
+    for (const Hit& x : hits)
+        if (map_in_best(x.key, v.key)) keys.push_back(map_anchor_key(x.qa, x.t));
+    a.n_best = (int32_t)keys.size();
+    map_anchors_of_keys(ap, L, keys, a.q, a.t, &a.n_chain, &a.n_supported, nullptr);
 }
 
 // the split rule on one read: its sorted segments (n of them) and round 0's vote
@@ -184,6 +197,65 @@ int map_reads_host(const MapIndexHost& ix, const uint8_t* read_seq, const int64_
     std::vector<std::thread> th;
     for (int t = 0; t < n_threads; ++t) th.emplace_back(work, t);
     for (std::thread& t : th) t.join();
+    return HS_OK;
+}
+
+void map_anchors_of_keys(const hs_map_anchor_params& ap, int64_t Lr, std::vector<uint64_t>& keys, std::vector<int32_t>& q, std::vector<int32_t>& t, int32_t* n_chain,
+                         int32_t* n_supported, std::vector<int32_t>* members) {
+    std::sort(keys.begin(), keys.end());
+    const int n = (int)keys.size();
+    std::vector<uint16_t> chain((size_t)n + 1), pred((size_t)n + 1);
+    bool rises = true;
+    for (int i = 1; rises && i < n; ++i) rises = map_anchor_rises(keys.data(), i);
+    int len = n;
+    if (rises) for (int i = 0; i < n; ++i) chain[(size_t)i] = (uint16_t)i;
+    else len = map_anchor_chain(keys.data(), n, chain.data(), pred.data());
+    *n_chain = len; *n_supported = 0;
+    for (int j = 0; j < len; ++j)      // (the supported members side by side, where the predecessor links were)
+        if (map_anchor_supported(keys.data(), chain.data(), len, j)) pred[(size_t)(*n_supported)++] = chain[(size_t)j];
+    if (members) { members->clear(); for (int j = 0; j < len; ++j) members->push_back((int32_t)chain[(size_t)j]); }
+    const int64_t cap = map_anchor_bound(Lr, ap.spacing);
+    q.assign((size_t)cap, 0); t.assign((size_t)cap, 0);
+    const int m = map_anchor_cuts(keys.data(), pred.data(), *n_supported, ap.spacing, q.data(), t.data(), cap);
+    q.resize((size_t)m); t.resize((size_t)m);
+}
+
+int map_anchors_host(const MapIndexHost& ix, const hs_map_anchor_params& ap, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapResultHost& out,
+                     MapAnchorsHost& anchors, std::string& err) {
+    if (!map_anchor_params_valid(ap)) { err = "map reads: anchor parameters out of range (spacing >= 1)"; return HS_EINVAL; }
+    if (n_reads < 0 || !read_off) { err = "map reads: bad arguments"; return HS_EINVAL; }
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (read_off[r + 1] < read_off[r] || read_off[r + 1] - read_off[r] > 0x7fffffff) { err = "map reads: a read of more than 2^31 bases"; return HS_EINVAL; }
+    const size_t n = (size_t)n_reads;
+    for (std::vector<int32_t>* v : {&out.contig, &out.qstart, &out.qend, &out.tstart, &out.tend, &out.votes, &out.second, &out.n_minimizers, &out.n_skipped}) v->assign(n, 0);
+    out.strand.assign(n, 0); out.n_hits.assign(n, 0);
+    std::vector<ReadAnchors> per(n);
+    n_threads = std::max(1, std::min(n_threads, std::max(1, n_reads)));
+    auto work = [&](int t) {
+        std::vector<Hit> hits;
+        std::vector<uint64_t> keys;
+        for (size_t r = (size_t)t; r < n; r += (size_t)n_threads) {
+            MapVote v;
+            const int64_t L = read_off[r + 1] - read_off[r];
+            map_one_read(ix, read_seq + read_off[r], L, r, out, hits, keys, &v);
+            if (out.contig[r] >= 0) map_anchors_one_read(ap, L, hits, v, keys, per[r]);
+        }
+    };
+    if (n_threads == 1) work(0);
+    else {
+        std::vector<std::thread> th;
+        for (int t = 0; t < n_threads; ++t) th.emplace_back(work, t);
+        for (std::thread& t : th) t.join();
+    }
+    anchors.anc_off.assign(n + 1, 0);
+    anchors.anc_q.clear(); anchors.anc_t.clear();
+    anchors.n_best.assign(n, 0); anchors.n_chain.assign(n, 0); anchors.n_supported.assign(n, 0);
+    for (size_t r = 0; r < n; ++r) {
+        anchors.anc_q.insert(anchors.anc_q.end(), per[r].q.begin(), per[r].q.end());
+        anchors.anc_t.insert(anchors.anc_t.end(), per[r].t.begin(), per[r].t.end());
+        anchors.anc_off[r + 1] = (int64_t)anchors.anc_q.size();
+        anchors.n_best[r] = per[r].n_best; anchors.n_chain[r] = per[r].n_chain; anchors.n_supported[r] = per[r].n_supported;
+    }
     return HS_OK;
 }
 
@@ -288,6 +360,17 @@ hs_map_params hs_map_params_default(void) {
     hs_map_params p;
     p.k = 15; p.w = 10; p.max_occ = 64; p.band_log2 = 9; p.min_votes = 3; p.extend = 1; p.bucket_bits = -1;
     return p;
+}
+hs_map_anchor_params hs_map_anchor_params_default(void) {
+    hs_map_anchor_params a;
+    a.spacing = 256;      // (the fastest of one sweep on one job; not tuned beyond that)
+    return a;
+}
+void hs_map_anchors_destroy(hs_map_anchors* a) {
+    if (!a) return;
+    void* p[] = {a->anc_off, a->anc_q, a->anc_t, a->n_best, a->n_chain, a->n_supported};
+    for (void* q : p) std::free(q);
+    std::free(a);
 }
 hs_map_split_params hs_map_split_params_default(void) {
     hs_map_split_params s;

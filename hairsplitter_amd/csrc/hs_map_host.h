@@ -193,6 +193,71 @@ HS_HD inline void map_segment_interval(const hs_map_params& p, const hs_map_spli
     map_stretch(p, rel, s[i].qa_min, (int64_t)s[i].qa_max + p.k, s[i].t_min, (int64_t)s[i].t_max + p.k, Lr, Lc, rel ? Lr - A1 : A0, rel ? Lr - A0 : A1, qstart, qend, tstart, tend);
 }
 
+// ---- anchors (hs_map_reads_anchored): cut points of a mapped read along the chain of its best candidate's hits ----
+// The default of hs_map_anchor_params (spacing 256) was a placeholder like the mapper's own and is the fastest of one sweep on one job.
+// It is NOT tuned beyond that.
+//
+//   hits             the read's hits that are the best's (map_in_best), as pairs (qa, t): qa on the read as it aligns (the hits' own coordinate), t on
+//                    the contig. Repeats give duplicates in qa or in t.
+//   chain            the longest subsequence strictly increasing in qa and in t; of several, the one map_anchor_chain gives: the hits ordered by
+//                    (qa ascending, t descending) -- ascending map_anchor_key --, patience over t with a lower-bound search (the first tail >= t is
+//                    replaced, or the tails grow by one), a hit's predecessor = the tail of the next shorter length when the hit was placed, the
+//                    chain read back from the final tail of the greatest length. Ordered hits already strictly increasing in t: all of them.
+//   support          a chain member is supported when its diagonal t - qa equals that of the member before it or after it (map_anchor_supported):
+//                    a seed alone on its diagonal between two indel-free runs is not trusted as a cut.
+//   cut points       over the supported members in order: the first; then each whose qa is at least `spacing` above the LAST CUT POINT's qa
+//                    (map_anchor_cuts). At most Lr / spacing + 1 of them (map_anchor_bound).
+//   no anchors       an unmapped read; a read with more hits than hs_map_lds_capacity() (the wide route; n_wide counts those), which is aligned
+//                    the plain way. n_best, n_chain and n_supported of such a read are 0.
+#define HS_MAP_ANCHOR_NONE 0xFFFFu
+#define HS_MAP_ANCHOR_CAPACITY 4096      /* == hs_map_lds_capacity(): hits of a read beyond which it has no anchors */
+HS_HD inline bool map_anchor_params_valid(const hs_map_anchor_params& a) { return a.spacing >= 1; }
+HS_HD inline uint64_t map_anchor_key(int32_t qa, int32_t t) { return ((uint64_t)(uint32_t)qa << 32) | (uint32_t)(0x7fffffff - t); }      // (qa, t >= 0)
+HS_HD inline int32_t map_anchor_qa(uint64_t key) { return (int32_t)(key >> 32); }
+HS_HD inline int32_t map_anchor_t(uint64_t key) { return 0x7fffffff - (int32_t)(uint32_t)key; }
+HS_HD inline int32_t map_anchor_diag(uint64_t key) { return map_anchor_t(key) - map_anchor_qa(key); }
+HS_HD inline int64_t map_anchor_bound(int64_t Lr, int32_t spacing) { return Lr / spacing + 1; }
+// where read r's cut points are staged, from its offset in the concatenated reads alone: floor is superadditive, so the reads' rooms of
+// map_anchor_bound do not overlap, and all of them end at or before map_anchor_stage_at(total bases, n_reads)
+HS_HD inline int64_t map_anchor_stage_at(int64_t read_off, int64_t r, int32_t spacing) { return read_off / spacing + r; }
+// are the ordered hits i - 1, i strictly increasing in t (then in qa as well: equal qa come with t descending)?
+HS_HD inline bool map_anchor_rises(const uint64_t* keys, int i) { return map_anchor_t(keys[i - 1]) < map_anchor_t(keys[i]); }
+// keys[0, n) ascending, n < HS_MAP_ANCHOR_NONE; tail and pred have room for n. Returns the chain's length, its members' indices ascending in tail[]
+HS_HD inline int map_anchor_chain(const uint64_t* keys, int n, uint16_t* tail, uint16_t* pred) {
+    int len = 0;
+    for (int i = 0; i < n; ++i) {
+        const int32_t t = map_anchor_t(keys[i]);
+        int lo = 0, hi = len;      // the first tail whose t is >= t
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (map_anchor_t(keys[tail[mid]]) < t) lo = mid + 1; else hi = mid; }
+        pred[i] = lo ? tail[lo - 1] : (uint16_t)HS_MAP_ANCHOR_NONE;
+        tail[lo] = (uint16_t)i;
+        if (lo == len) ++len;
+    }
+    for (int j = len - 1; j > 0; --j) tail[j - 1] = pred[tail[j]];
+    return len;
+}
+HS_HD inline bool map_anchor_supported(const uint64_t* keys, const uint16_t* chain, int len, int j) {
+    const int32_t d = map_anchor_diag(keys[chain[j]]);
+    return (j > 0 && map_anchor_diag(keys[chain[j - 1]]) == d) || (j + 1 < len && map_anchor_diag(keys[chain[j + 1]]) == d);
+}
+// the cut points over the supported members, sup[0, n) = their indices into keys in chain order: the first, then each time the first member whose qa
+// is `spacing` or more above the last cut point's -- found by search, since qa rises strictly along a chain; the walk of the rule gives the same.
+// At most cap are written (map_anchor_bound holds them all); returns their number
+HS_HD inline int map_anchor_cuts(const uint64_t* keys, const uint16_t* sup, int n, int32_t spacing, int32_t* out_q, int32_t* out_t, int64_t cap) {
+    int64_t m = 0;
+    int j = 0;
+    while (j < n) {
+        const uint64_t key = keys[sup[j]];
+        if (m < cap) { out_q[m] = map_anchor_qa(key); out_t[m] = map_anchor_t(key); }
+        ++m;
+        const int64_t want = (int64_t)map_anchor_qa(key) + spacing;
+        int lo = j + 1, hi = n;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (map_anchor_qa(keys[sup[mid]]) < want) lo = mid + 1; else hi = mid; }
+        j = lo;
+    }
+    return (int)(m < cap ? m : cap);
+}
+
 // ---- the device-free half: a whole job on the host ----
 struct MapMinimizers {      // (sequence, position) ascending
     std::vector<uint32_t> h, ps;      // ps = position << 1 | strand bit
@@ -227,6 +292,17 @@ struct MapSegmentsHost {
 };
 int map_reads_split_host(const MapIndexHost& ix, const hs_map_split_params& sp, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapSegmentsHost& out,
                          std::string& err);
+// the anchored form: map_reads_host's result and the anchors of every read, as hs_map_anchors has them
+struct MapAnchorsHost {
+    std::vector<int64_t> anc_off;      // [n_reads + 1]
+    std::vector<int32_t> anc_q, anc_t, n_best, n_chain, n_supported;
+};
+// the rule on the best's hits alone: keys = map_anchor_key of each (at most HS_MAP_ANCHOR_CAPACITY; sorted here), Lr the read's length. The cut
+// points, the chain's length, its supported members and, where asked for, the chain's members as indices into the sorted keys
+void map_anchors_of_keys(const hs_map_anchor_params& ap, int64_t Lr, std::vector<uint64_t>& keys, std::vector<int32_t>& q, std::vector<int32_t>& t, int32_t* n_chain,
+                         int32_t* n_supported, std::vector<int32_t>* members);
+int map_anchors_host(const MapIndexHost& ix, const hs_map_anchor_params& ap, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapResultHost& out,
+                     MapAnchorsHost& anchors, std::string& err);
 // PAF lines of the mapped reads: names[] may be nullptr (then r<i> / c<i>)
 std::string map_text(const hs_map_result* r, const char* const* read_names, const int64_t* read_len, const char* const* contig_names, const int64_t* contig_len);
 // one PAF line per segment, in segment order: map_text's columns, then sg:i:<round> ns:i:<segments of the read>

@@ -352,6 +352,8 @@ typedef struct hs_realign_records {
     int64_t n_dropped; int32_t* dropped;   /* intervals the aligner had no path for (query > 2^20 bases) */
     double t_cut_ms, t_align_ms, t_cigar_ms, t_download_ms;   /* HIP events / wall around the phases */
     int64_t n_rounds, move_bytes, cigar_words;
+    int64_t n_pieces;          /* pairs handed to the aligner (hs_realign_intervals: one per interval) */
+    double t_join_ms;          /* hs_realign_intervals_anchored: HIP events around k_anchor_join (0 otherwise) */
 } hs_realign_records;
 int hs_realign_intervals(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs,
                          const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads,
@@ -1017,6 +1019,45 @@ int hs_map_split_to_batch(const hs_map_index* index, const uint8_t* h_contig_seq
  * seg_off must ascend from 0 to n_segments: HS_EINVAL otherwise. */
 int hs_map_segments_text(const hs_map_segments* segments, const char* const* read_names, const int64_t* h_read_off, const char* const* contig_names,
                          const int64_t* h_contig_off, int32_t n_contigs, char** text);
+
+/* Anchored alignment (opt-in; rule: csrc/hs_map_host.h, "anchors"). The hits of a mapped read's best candidate are exact k-mer matches along
+ * its diagonal. Their chain, thinned to supported members at least `spacing` read bases apart, gives cut points (q, t): q on the read AS IT
+ * ALIGNS (the read's own coordinate on strand 1, the coordinate in its reverse complement on strand 0), t on the contig. An interval cut at its
+ * anchors is aligned piece by piece -- head (start free on the contig), middles (global), tail (end free) -- and the pieces' moves are joined
+ * into one record. Such an alignment is a cheapest one THROUGH THE ANCHORS, not edlib's HW optimum in the window: NM(anchored) >= NM(plain).
+ * An unmapped read has no anchors; neither has a read with more hits than hs_map_lds_capacity() (n_wide counts those): it is aligned the
+ * plain way. spacing >= 1; the default 256 was a placeholder and is now the fastest of one sweep on one job; it is NOT tuned beyond that. */
+typedef struct hs_map_anchor_params { int32_t spacing; } hs_map_anchor_params;
+hs_map_anchor_params hs_map_anchor_params_default(void);
+typedef struct hs_map_anchors {
+    int32_t n_reads;
+    int64_t n_anchors;
+    int64_t* anc_off;                         /* [n_reads+1] */
+    int32_t *anc_q, *anc_t;                   /* [n_anchors] (room for one at least): ascending in both inside a read */
+    int32_t *n_best, *n_chain, *n_supported;  /* [n_reads] hits of the best, members of their chain, supported members (0: no anchors) */
+    double t_anchors_ms;                      /* HIP events around k_map_anchors, the scan and the compaction */
+} hs_map_anchors;
+/* hs_map_reads plus the anchors of every read. `result` is field for field hs_map_reads' result; params NULL: the defaults; spacing < 1:
+ * HS_EINVAL. Three waits, as hs_map_reads: the anchors leave in the per-read block's shipment. */
+int hs_map_reads_anchored(const hs_map_index* index, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads, const hs_map_anchor_params* params,
+                          hs_map_result** result, hs_map_anchors** anchors);
+void hs_map_anchors_destroy(hs_map_anchors* anchors);
+/* hs_realign_intervals with the anchors of every interval given: anc_off [n_intervals+1], anc_q (read as it aligns) / anc_t (contig). The
+ * alignment of an interval is a cheapest one THROUGH ITS ANCHORS, not edlib's HW optimum; an interval without anchors gets hs_realign_intervals'
+ * record. Anchors of interval i must ascend strictly in q and in t with a0 <= q <= a1 and tstart <= t <= tend ([a0, a1) = the interval's read
+ * range as it aligns): HS_EINVAL otherwise, and hs_last_error() names the interval. The pieces of an interval stay in one round and count
+ * towards its pair limit; an interval with a piece the aligner has no path for is dropped. records->n_pieces / t_join_ms say what was done. */
+int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs,
+                                  const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads,
+                                  const int32_t* iv_read, const int32_t* iv_contig, const uint8_t* iv_strand,
+                                  const int32_t* iv_qstart, const int32_t* iv_qend, const int32_t* iv_tstart, const int32_t* iv_tend,
+                                  int32_t n_intervals, int32_t pad, const int64_t* anc_off, const int32_t* anc_q, const int32_t* anc_t,
+                                  hs_realign_records** out, struct hs_cv_batch** batch /* may be NULL */);
+/* hs_map_reads_anchored, then hs_realign_intervals_anchored on the mapped reads with their anchors: hs_map_to_batch's counterpart; the
+ * alignments are cheapest ones through the anchors, not edlib's HW optima. records / result / anchors may be NULL. */
+int hs_map_to_batch_anchored(const hs_map_index* index, const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq,
+                             const int64_t* h_read_off, int32_t n_reads, int32_t pad, const hs_map_anchor_params* params, hs_cv_batch** batch,
+                             hs_realign_records** records, hs_map_result** result, hs_map_anchors** anchors);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,13 @@
+# Test infrastructure: the device-free half of the anchored mapper (hs_map_host.cpp: map_anchors_host) as a program of its own, no device and no HIP.
+# make -f map_anchor_selftest.mk          -> _build/map_anchor_selftest (tests/test_cpu_map_anchors.py, tests/test_gpu_map_anchors.py)
+# make -f map_anchor_selftest.mk asan     -> the same under AddressSanitizer + UBSan, an executable of its own (tests/test_cpu_map_anchors.py runs it once)
+CXX ?= g++
+P := ../../hairsplitter_amd/csrc
+all: _build/map_anchor_selftest
+_build/map_anchor_selftest: map_anchor_selftest.cpp $(P)/hs_map_host.cpp $(P)/hs_map_host.h $(P)/hs_rules.h ../../include/hairsplitter_hip.h
+	@mkdir -p _build
+	$(CXX) -std=c++17 -O2 -Wall -o $@ map_anchor_selftest.cpp $(P)/hs_map_host.cpp -lpthread
+asan: _build/map_anchor_selftest_asan
+_build/map_anchor_selftest_asan: map_anchor_selftest.cpp $(P)/hs_map_host.cpp $(P)/hs_map_host.h $(P)/hs_rules.h ../../include/hairsplitter_hip.h
+	@mkdir -p _build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Wall -o $@ map_anchor_selftest.cpp $(P)/hs_map_host.cpp -lpthread

@@ -12,7 +12,11 @@ Usage: python tools/map_bench.py [config=C4] [contigs=16] [repeats=5] [host_samp
        python tools/map_bench.py [config=C4] [contigs=16] split [piece_len=20000]
 The split mode cuts the contigs into pieces and keeps the reads and their truth: reads with more than one segment of hs_map_reads_split; aligned bp and
 the mean depth over the last 1 000 bases of the pieces for the batch of hs_map_split_to_batch, of hs_map_to_batch and of the truth intervals; the vote
-group's time (HIP events, medians of 5, alternating) split against plain on the cut job and on the uncut one, where nearly every read has one segment."""
+group's time (HIP events, medians of 5, alternating) split against plain on the cut job and on the uncut one, where nearly every read has one segment.
+       python tools/map_bench.py [config=C4] [contigs=16] anchored [spacings=128,256,512,1024]
+The anchored mode takes hs_map_to_batch and hs_map_to_batch_anchored in turn on the same reads, at spacing 128, 256, 512 and 1 024, five turns, one
+process: wall from reads to batch, t_align_ms, the join's and k_map_anchors' time, the vote group's time, pieces, the sum of NM of both routes and the reads
+above their optimum, stage 3 on both batches (medians, every run listed). The yardstick is the plain route of the same process."""
 import json
 import os
 import statistics
@@ -120,9 +124,106 @@ def split_main(cfg, n, piece_len):
     print(json.dumps(out))
 
 
+def anchored_main(cfg, n, spacings=(128, 256, 512, 1024), turns=5):
+    """hs_map_to_batch against hs_map_to_batch_anchored at every spacing, alternating inside one process"""
+    import numpy as np
+    from hairsplitter_amd import synth
+    contigs, _ = synth.generate_job(cfg, list(range(n)), workers=min(16, os.cpu_count() or 1))      # before the GPU is touched (forks)
+    from hairsplitter_amd import api
+    api.require_gpu()
+    flat = api.FlatBatch(contigs)
+    reads = (flat.read_seq, flat.read_off)
+    med = statistics.median
+    routes = ["plain"] + ["s%d" % s for s in spacings]
+    runs = {k: {"wall_ms": [], "align_ms": [], "cut_ms": [], "cigar_ms": [], "join_ms": [], "anchors_ms": [], "vote_ms": []} for k in routes}
+    last = {}
+
+    def one(ix, key):
+        t0 = time.perf_counter()
+        if key == "plain":
+            batch, rec, res = api.map_to_batch(ix, reads)
+            anc = None
+        else:
+            batch, rec, res, anc = api.map_to_batch_anchored(ix, reads, api.map_anchor_params(spacing=int(key[1:])))
+        dt = (time.perf_counter() - t0) * 1e3
+        r = runs[key]
+        r["wall_ms"].append(dt); r["align_ms"].append(rec["t_align_ms"]); r["cut_ms"].append(rec["t_cut_ms"]); r["cigar_ms"].append(rec["t_cigar_ms"])
+        r["join_ms"].append(rec["t_join_ms"]); r["anchors_ms"].append(anc["t_anchors_ms"] if anc else 0.0); r["vote_ms"].append(res["t_vote_ms"])
+        if key in last:
+            last[key][0].close()
+        last[key] = (batch, rec, res, anc)
+
+    with api.map_index((flat.contig_seq, flat.contig_off)) as ix:
+        for key in routes:      # warm-up: pools, code object
+            one(ix, key)
+        for r in runs.values():
+            for v in r.values():
+                v.clear()
+        for _ in range(turns):
+            for key in routes:
+                one(ix, key)
+
+    def nm_by_read(rec):
+        return dict(zip(rec["rec_read"].tolist(), rec["rec_dist"].tolist()))
+
+    def snps(r):
+        return set((int(c), int(p)) for c in range(len(r["snp_off"]) - 1) for p in r["snp_pos"][r["snp_off"][c]:r["snp_off"][c + 1]])
+    plain_nm = nm_by_read(last["plain"][1])
+    plain_run = last["plain"][0].run()
+    plain_snps = snps(plain_run)
+    out = {"config": cfg, "contigs": n, "reads": flat.n_reads, "read_bases": int(flat.read_off[-1]), "turns": turns, "routes": {}}
+    for key in routes:
+        batch, rec, res, anc = last[key]
+        nm = nm_by_read(rec)
+        run = plain_run if key == "plain" else batch.run()
+        sn = snps(run)
+        out["routes"][key] = {
+            **{k: round(med(v), 3) for k, v in runs[key].items()}, "wall_ms_all": [round(x, 1) for x in runs[key]["wall_ms"]], "align_ms_all": [round(x, 1) for x in runs[key]["align_ms"]],
+            "records": int(rec["n_rec"]), "dropped": int(rec["n_dropped"]), "pieces": int(rec["n_pieces"]), "rounds": int(rec["n_rounds"]),
+            "anchors": int(anc["anc_off"][-1]) if anc else 0, "reads_without_anchors": int((np.diff(anc["anc_off"])[res["contig"] >= 0] == 0).sum()) if anc else None,
+            "sum_nm": int(sum(nm.values())), "reads_above_plain_nm": int(sum(1 for r, v in nm.items() if v > plain_nm.get(r, v))),
+            "reads_below_plain_nm": int(sum(1 for r, v in nm.items() if v < plain_nm.get(r, v))),
+            "snps": len(sn), "snps_in_common_with_plain": len(sn & plain_snps), "error_rate": float(run["error_rate"])}
+        batch.close()
+    # the reads that have anchors alone, records only (no batch): a mapped read without anchors goes the plain way on either route, and the few reads
+    # that match their window nowhere cost a plain call most of its time
+    res, anc = last[routes[1]][2], last[routes[1]][3]
+    iv_all = api.map_intervals(res)
+    has = np.diff(anc["anc_off"])[iv_all[:, 0]] > 0
+    iv = iv_all[has]
+    sub = {k: {"wall_ms": [], "align_ms": [], "join_ms": []} for k in routes}
+    picks = {}
+    for key in routes[1:]:
+        a = last[key][3]
+        n_anc = np.diff(a["anc_off"])[iv[:, 0]]
+        idx = np.concatenate([np.arange(a["anc_off"][r], a["anc_off"][r + 1]) for r in iv[:, 0]]) if len(iv) else np.zeros(0, np.int64)
+        picks[key] = (np.concatenate([[0], np.cumsum(n_anc)]).astype(np.int64), a["anc_q"][idx], a["anc_t"][idx])
+
+    def one_sub(key):
+        t0 = time.perf_counter()
+        rec, _ = api.realign_intervals(flat, iv, want_batch=False) if key == "plain" else api.realign_intervals_anchored(flat, iv, *picks[key], want_batch=False)
+        sub[key]["wall_ms"].append((time.perf_counter() - t0) * 1e3); sub[key]["align_ms"].append(rec["t_align_ms"]); sub[key]["join_ms"].append(rec["t_join_ms"])
+        return rec
+    for key in routes:
+        one_sub(key)
+    for r in sub.values():
+        for v in r.values():
+            v.clear()
+    nm_sub = {}
+    for _ in range(turns):
+        for key in routes:
+            nm_sub[key] = int(one_sub(key)["rec_dist"].sum())
+    out["reads_with_anchors_only"] = {"intervals": int(len(iv)), "left_out": int((~has).sum()), "routes": {
+        key: {**{k: round(med(v), 3) for k, v in sub[key].items()}, "wall_ms_all": [round(x, 1) for x in sub[key]["wall_ms"]], "align_ms_all": [round(x, 1) for x in sub[key]["align_ms"]],
+              "sum_nm": nm_sub[key]} for key in routes}}
+    print(json.dumps(out))
+
+
 def main():
     cfg = sys.argv[1] if len(sys.argv) > 1 else "C4"
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+    if len(sys.argv) > 3 and sys.argv[3] == "anchored":
+        return anchored_main(cfg, n, *([tuple(int(x) for x in sys.argv[4].split(","))] if len(sys.argv) > 4 else []))
     if len(sys.argv) > 3 and sys.argv[3] == "split":
         return split_main(cfg, n, int(sys.argv[4]) if len(sys.argv) > 4 else 20000)
     reps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
