@@ -2015,11 +2015,8 @@ def moves_to_cigar(moves_list, clips=None, spans=False, count_only=False, ops_le
     return (out, d_sp.cpu().numpy()[:n]) if spans else out
 
 
-def realign_intervals(flat_sequences, intervals, pad: int = 100, want_batch: bool = True):
-    """hs_realign_intervals: intervals held in memory -> alignment records with CIGARs (and the resident batch made from them).
-    flat_sequences: anything with contig_seq / contig_off / read_seq / read_off as a FlatBatch has them (codes 0..3, one per byte).
-    intervals: rows (read, contig, strand, qstart, qend, tstart, tend); strand 1 forward, 0 reverse; half-open, 0-based.
-    Returns (records dict, CvBatch or None): records grouped by contig, input order inside a contig (rec_interval says which row)."""
+def _realign(who, flat_sequences, intervals, anchors, pad, want_batch):
+    """the one body of realign_intervals (anchors None) and realign_intervals_anchored (anchors = (anc_off, anc_q, anc_t))"""
     import time
     require_gpu()
     lib = load()
@@ -2027,13 +2024,18 @@ def realign_intervals(flat_sequences, intervals, pad: int = 100, want_batch: boo
     cseq, coff, rseq, roff = _np(g("contig_seq"), np.uint8), _np(g("contig_off"), np.int64), _np(g("read_seq"), np.uint8), _np(g("read_off"), np.int64)
     iv = np.asarray(intervals, dtype=np.int64).reshape(-1, 7)
     if iv.size and (np.abs(iv).max() > 0x7fffffff):
-        raise HsError("realign_intervals: interval fields are 32-bit")
+        raise HsError(who + ": interval fields are 32-bit")
     col = [_np(iv[:, k], np.uint8 if k == 2 else np.int32) for k in range(7)]
+    args = [_hp(cseq, C.c_uint8), _hp(coff, C.c_int64), C.c_int32(len(coff) - 1), _hp(rseq, C.c_uint8), _hp(roff, C.c_int64), C.c_int32(len(roff) - 1)]
+    args += [_hp(c, C.c_uint8 if k == 2 else C.c_int32) for k, c in enumerate(col)] + [C.c_int32(len(iv)), C.c_int32(pad)]
+    if anchors is not None:
+        aoff, aq, at = _np(anchors[0], np.int64), _np(anchors[1], np.int32), _np(anchors[2], np.int32)
+        if len(aoff) != len(iv) + 1 or len(aq) != len(at) or (len(aoff) and int(aoff[-1]) > len(aq)):
+            raise HsError(who + ": anc_off has one entry per interval and one more, anc_q and anc_t anc_off[-1] entries")
+        args += [_hp(aoff, C.c_int64), _hp(aq, C.c_int32), _hp(at, C.c_int32)]
     h = C.c_void_p(); r = C.POINTER(RealignRecords)()
     t0 = time.perf_counter()
-    _check(lib.hs_realign_intervals(_hp(cseq, C.c_uint8), _hp(coff, C.c_int64), C.c_int32(len(coff) - 1), _hp(rseq, C.c_uint8), _hp(roff, C.c_int64), C.c_int32(len(roff) - 1),
-                                    _hp(col[0], C.c_int32), _hp(col[1], C.c_int32), _hp(col[2], C.c_uint8), _hp(col[3], C.c_int32), _hp(col[4], C.c_int32),
-                                    _hp(col[5], C.c_int32), _hp(col[6], C.c_int32), C.c_int32(len(iv)), C.c_int32(pad), C.byref(r), C.byref(h) if want_batch else None))
+    _check(getattr(lib, "hs_" + who)(*args, C.byref(r), C.byref(h) if want_batch else None))
     dt = time.perf_counter() - t0
     try:
         rec = _realign_records_to_dict(r)
@@ -2042,15 +2044,27 @@ def realign_intervals(flat_sequences, intervals, pad: int = 100, want_batch: boo
     return rec, (CvBatch._adopt(h, dt, rec) if want_batch else None)
 
 
+def realign_intervals(flat_sequences, intervals, pad: int = 100, want_batch: bool = True):
+    """hs_realign_intervals: intervals held in memory -> alignment records with CIGARs (and the resident batch made from them).
+    flat_sequences: anything with contig_seq / contig_off / read_seq / read_off as a FlatBatch has them (codes 0..3, one per byte).
+    intervals: rows (read, contig, strand, qstart, qend, tstart, tend); strand 1 forward, 0 reverse; half-open, 0-based.
+    Returns (records dict, CvBatch or None): records grouped by contig, input order inside a contig (rec_interval says which row)."""
+    return _realign("realign_intervals", flat_sequences, intervals, None, pad, want_batch)
+
+
 # ---- the read mapper (hs_map_*): minimizer seeds against a resident index of the contigs, a vote over diagonal bins ----
+def _params_with(default, who, kw):
+    """a parameter struct of the library's defaults with the given fields replaced"""
+    for k, v in kw.items():
+        if k not in dict(type(default)._fields_):
+            raise HsError(who + ": no field " + k)
+        setattr(default, k, int(v))
+    return default
+
+
 def map_params(**kw) -> MapParams:
     """hs_map_params_default with the given fields replaced"""
-    p = load().hs_map_params_default()
-    for k, v in kw.items():
-        if k not in dict(MapParams._fields_):
-            raise HsError("map_params: no field " + k)
-        setattr(p, k, int(v))
-    return p
+    return _params_with(load().hs_map_params_default(), "map_params", kw)
 
 
 def map_lds_capacity() -> int:
@@ -2064,6 +2078,11 @@ def _flat(seqs):
         np.cumsum([len(s) for s in seqs], out=off[1:])
     flat = np.concatenate([_np(s, np.uint8).reshape(-1) for s in seqs]) if len(seqs) and off[-1] else np.zeros(0, np.uint8)
     return np.ascontiguousarray(flat), off
+
+
+def _reads_arg(reads):
+    """a list of code arrays, or a (codes, offsets) pair -> (codes, offsets)"""
+    return (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
 
 
 class MapIndex:
@@ -2105,17 +2124,14 @@ def map_index(contigs, params: Optional[MapParams] = None) -> MapIndex:
     """hs_map_index_create. contigs: a list of code arrays (0..3), or a (codes, offsets) pair."""
     require_gpu()
     lib = load()
-    cseq, coff = (_np(contigs[0], np.uint8), _np(contigs[1], np.int64)) if isinstance(contigs, tuple) else _flat(contigs)
+    cseq, coff = _reads_arg(contigs)
     prm = params if params is not None else lib.hs_map_params_default()
     h = C.c_void_p()
     _check(lib.hs_map_index_create(cseq.ctypes.data, coff.ctypes.data, C.c_int32(len(coff) - 1), C.byref(prm), C.byref(h)))
     return MapIndex(h, cseq, coff, prm)
 
 
-def _map_result_to_dict(r) -> Dict:
-    res = r.contents
-    n = int(res.n_reads)
-    out = {k: np.ctypeslib.as_array(getattr(res, k), shape=(n,)).copy() if n else np.zeros(0, np.int64) for k in MAP_FIELDS}
+def _map_call_stats(res, out):
     for k in ("n_wide", "total_minimizers", "total_hits"):
         out[k] = int(getattr(res, k))
     for k in ("t_minimizers_ms", "t_hits_ms", "t_vote_ms"):
@@ -2123,11 +2139,17 @@ def _map_result_to_dict(r) -> Dict:
     return out
 
 
+def _map_result_to_dict(r) -> Dict:
+    res = r.contents
+    n = int(res.n_reads)
+    return _map_call_stats(res, {k: np.ctypeslib.as_array(getattr(res, k), shape=(n,)).copy() if n else np.zeros(0, np.int64) for k in MAP_FIELDS})
+
+
 def map_reads(index: MapIndex, reads) -> Dict:
     """hs_map_reads: per read contig (-1 unmapped), strand, qstart, qend, tstart, tend, votes, second, n_minimizers, n_hits, n_skipped; per call n_wide.
     reads: a list of code arrays, or a (codes, offsets) pair."""
     lib = load()
-    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
+    rseq, roff = _reads_arg(reads)
     r = C.POINTER(MapResult)()
     _check(lib.hs_map_reads(index._h, rseq.ctypes.data, roff.ctypes.data, C.c_int32(len(roff) - 1), C.byref(r)))
     try:
@@ -2142,44 +2164,56 @@ def map_intervals(res: Dict) -> np.ndarray:
     return np.stack([m, res["contig"][m], res["strand"][m], res["qstart"][m], res["qend"][m], res["tstart"][m], res["tend"][m]], axis=1).astype(np.int64).reshape(-1, 7)
 
 
-def map_to_batch(index: MapIndex, reads, pad: int = 100):
-    """hs_map_to_batch: map_reads, then realign_intervals on the mapped reads. Returns (CvBatch, records dict, map result dict)."""
+def _to_batch(fn, index, reads, pad, params, outs):
+    """the one body of the three *_to_batch calls. params: () or (the call's parameter struct or None,); outs: (struct, its to-dict, its destroy) of
+    every mapper output behind the records. Returns (CvBatch, records dict, one dict per output)."""
     import time
     lib = load()
-    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
-    h = C.c_void_p(); rec = C.POINTER(RealignRecords)(); r = C.POINTER(MapResult)()
+    rseq, roff = _reads_arg(reads)
+    h = C.c_void_p(); rec = C.POINTER(RealignRecords)()
+    got = [C.POINTER(struct)() for struct, _, _ in outs]
     t0 = time.perf_counter()
-    _check(lib.hs_map_to_batch(index._h, index.contig_seq.ctypes.data, index.contig_off.ctypes.data, C.c_int32(len(index.contig_off) - 1), rseq.ctypes.data, roff.ctypes.data,
-                               C.c_int32(len(roff) - 1), C.c_int32(pad), C.byref(h), C.byref(rec), C.byref(r)))
+    _check(getattr(lib, fn)(index._h, index.contig_seq.ctypes.data, index.contig_off.ctypes.data, C.c_int32(len(index.contig_off) - 1), rseq.ctypes.data, roff.ctypes.data,
+                            C.c_int32(len(roff) - 1), C.c_int32(pad), *[C.byref(p) if p is not None else None for p in params], C.byref(h), C.byref(rec),
+                            *[C.byref(p) for p in got]))
     dt = time.perf_counter() - t0
     try:
         records = _realign_records_to_dict(rec)
-        res = _map_result_to_dict(r)
+        dicts = [to_dict(p) for p, (_, to_dict, _) in zip(got, outs)]
     finally:
         lib.hs_realign_records_destroy(rec)
-        lib.hs_map_result_destroy(r)
-    return CvBatch._adopt(h, dt, records), records, res
+        for p, (_, _, destroy) in zip(got, outs):
+            getattr(lib, destroy)(p)
+    return (CvBatch._adopt(h, dt, records), records, *dicts)
 
 
-def map_text(res: Dict, read_lengths, contig_lengths, read_names=None, contig_names=None) -> str:
-    """hs_map_text: the PAF lines of the mapped reads of a map result"""
+def map_to_batch(index: MapIndex, reads, pad: int = 100):
+    """hs_map_to_batch: map_reads, then realign_intervals on the mapped reads. Returns (CvBatch, records dict, map result dict)."""
+    return _to_batch("hs_map_to_batch", index, reads, pad, (), [(MapResult, _map_result_to_dict, "hs_map_result_destroy")])
+
+
+def _paf_text(fn, struct, n_reads, arrays, read_lengths, contig_lengths, read_names, contig_names):
+    """the one PAF-text call: `struct` filled with n_reads and the arrays (name -> numpy array, kept alive here), the lengths as offsets, the names"""
     lib = load()
-    n = len(res["contig"])
-    keep = [_np(res[k], np.uint8 if k == "strand" else np.int32) for k in ("contig", "strand", "qstart", "qend", "tstart", "tend", "votes", "second")]
-    r = MapResult()
-    r.n_reads = n
-    for k, a in zip(("contig", "strand", "qstart", "qend", "tstart", "tend", "votes", "second"), keep):
-        setattr(r, k, a.ctypes.data_as(C.POINTER(C.c_uint8 if k == "strand" else C.c_int32)))
-    roff = np.zeros(n + 1, np.int64); np.cumsum(_np(read_lengths, np.int64), out=roff[1:])
+    struct.n_reads = n_reads
+    for k, a in arrays.items():
+        setattr(struct, k, a.ctypes.data_as(C.POINTER({np.dtype(np.uint8): C.c_uint8, np.dtype(np.int32): C.c_int32, np.dtype(np.int64): C.c_int64}[a.dtype])))
+    roff = np.zeros(n_reads + 1, np.int64); np.cumsum(_np(read_lengths, np.int64), out=roff[1:])
     coff = np.zeros(len(contig_lengths) + 1, np.int64); np.cumsum(_np(contig_lengths, np.int64), out=coff[1:])
     names = lambda v: (C.c_char_p * len(v))(*[x.encode() for x in v]) if v is not None else None
     rn, cn = names(read_names), names(contig_names)
     text = C.c_char_p()
-    _check(lib.hs_map_text(C.byref(r), rn, roff.ctypes.data, cn, coff.ctypes.data, C.c_int32(len(contig_lengths)), C.byref(text)))
+    _check(getattr(lib, fn)(C.byref(struct), rn, roff.ctypes.data, cn, coff.ctypes.data, C.c_int32(len(contig_lengths)), C.byref(text)))
     try:
         return text.value.decode()
     finally:
         lib.hs_free_host(text)
+
+
+def map_text(res: Dict, read_lengths, contig_lengths, read_names=None, contig_names=None) -> str:
+    """hs_map_text: the PAF lines of the mapped reads of a map result"""
+    keep = {k: _np(res[k], np.uint8 if k == "strand" else np.int32) for k in ("contig", "strand", "qstart", "qend", "tstart", "tend", "votes", "second")}
+    return _paf_text("hs_map_text", MapResult(), len(res["contig"]), keep, read_lengths, contig_lengths, read_names, contig_names)
 
 
 def map_files(gfa: str, reads: str, out_paf: str, n_threads: int = 0, params: Optional[MapParams] = None):
@@ -2191,12 +2225,7 @@ def map_files(gfa: str, reads: str, out_paf: str, n_threads: int = 0, params: Op
 # ---- split mappings (hs_map_reads_split): a read's parts on other contigs as further intervals ----
 def map_split_params(**kw) -> MapSplitParams:
     """hs_map_split_params_default with the given fields replaced"""
-    p = load().hs_map_split_params_default()
-    for k, v in kw.items():
-        if k not in dict(MapSplitParams._fields_):
-            raise HsError("map_split_params: no field " + k)
-        setattr(p, k, int(v))
-    return p
+    return _params_with(load().hs_map_split_params_default(), "map_split_params", kw)
 
 
 def _map_segments_to_dict(g) -> Dict:
@@ -2205,18 +2234,14 @@ def _map_segments_to_dict(g) -> Dict:
     out = {k: np.ctypeslib.as_array(getattr(res, k), shape=(s,)).copy() if s else np.zeros(0, np.int64) for k in MAP_SEG_FIELDS}
     out.update({k: np.ctypeslib.as_array(getattr(res, k), shape=(n,)).copy() if n else np.zeros(0, np.int64) for k in MAP_SEG_READ_FIELDS})
     out["seg_off"] = np.ctypeslib.as_array(res.seg_off, shape=(n + 1,)).copy()
-    for k in ("n_wide", "total_minimizers", "total_hits"):
-        out[k] = int(getattr(res, k))
-    for k in ("t_minimizers_ms", "t_hits_ms", "t_vote_ms"):
-        out[k] = float(getattr(res, k))
-    return out
+    return _map_call_stats(res, out)
 
 
 def map_reads_split(index: MapIndex, reads, split: Optional[MapSplitParams] = None) -> Dict:
     """hs_map_reads_split: seg_off [n_reads + 1]; per segment read, contig, strand, qstart, qend, tstart, tend, votes, second, round; per read n_minimizers,
     n_skipped, n_hits, read_votes, read_second; per call n_wide. reads: a list of code arrays, or a (codes, offsets) pair."""
     lib = load()
-    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
+    rseq, roff = _reads_arg(reads)
     g = C.POINTER(MapSegments)()
     _check(lib.hs_map_reads_split(index._h, rseq.ctypes.data, roff.ctypes.data, C.c_int32(len(roff) - 1), C.byref(split) if split is not None else None, C.byref(g)))
     try:
@@ -2232,43 +2257,16 @@ def map_segment_intervals(res: Dict) -> np.ndarray:
 
 def map_split_to_batch(index: MapIndex, reads, split: Optional[MapSplitParams] = None, pad: int = 100):
     """hs_map_split_to_batch: map_reads_split, then realign_intervals with interval i = segment i. Returns (CvBatch, records dict, segments dict)."""
-    import time
-    lib = load()
-    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
-    h = C.c_void_p(); rec = C.POINTER(RealignRecords)(); g = C.POINTER(MapSegments)()
-    t0 = time.perf_counter()
-    _check(lib.hs_map_split_to_batch(index._h, index.contig_seq.ctypes.data, index.contig_off.ctypes.data, C.c_int32(len(index.contig_off) - 1), rseq.ctypes.data, roff.ctypes.data,
-                                     C.c_int32(len(roff) - 1), C.c_int32(pad), C.byref(split) if split is not None else None, C.byref(h), C.byref(rec), C.byref(g)))
-    dt = time.perf_counter() - t0
-    try:
-        records = _realign_records_to_dict(rec)
-        res = _map_segments_to_dict(g)
-    finally:
-        lib.hs_realign_records_destroy(rec)
-        lib.hs_map_segments_destroy(g)
-    return CvBatch._adopt(h, dt, records), records, res
+    return _to_batch("hs_map_split_to_batch", index, reads, pad, (split,), [(MapSegments, _map_segments_to_dict, "hs_map_segments_destroy")])
 
 
 def map_segments_text(res: Dict, read_lengths, contig_lengths, read_names=None, contig_names=None) -> str:
     """hs_map_segments_text: one PAF line per segment of a map_reads_split result"""
-    lib = load()
     keep = {k: _np(res[k], np.uint8 if k == "strand" else np.int32) for k in MAP_SEG_FIELDS}
-    seg_off = _np(res["seg_off"], np.int64)
+    keep["seg_off"] = _np(res["seg_off"], np.int64)
     g = MapSegments()
-    g.n_reads, g.n_segments = len(seg_off) - 1, len(keep["read"])
-    g.seg_off = seg_off.ctypes.data_as(C.POINTER(C.c_int64))
-    for k, a in keep.items():
-        setattr(g, k, a.ctypes.data_as(C.POINTER(C.c_uint8 if k == "strand" else C.c_int32)))
-    roff = np.zeros(len(seg_off), np.int64); np.cumsum(_np(read_lengths, np.int64), out=roff[1:])
-    coff = np.zeros(len(contig_lengths) + 1, np.int64); np.cumsum(_np(contig_lengths, np.int64), out=coff[1:])
-    names = lambda v: (C.c_char_p * len(v))(*[x.encode() for x in v]) if v is not None else None
-    rn, cn = names(read_names), names(contig_names)
-    text = C.c_char_p()
-    _check(lib.hs_map_segments_text(C.byref(g), rn, roff.ctypes.data, cn, coff.ctypes.data, C.c_int32(len(contig_lengths)), C.byref(text)))
-    try:
-        return text.value.decode()
-    finally:
-        lib.hs_free_host(text)
+    g.n_segments = len(keep["read"])
+    return _paf_text("hs_map_segments_text", g, len(keep["seg_off"]) - 1, keep, read_lengths, contig_lengths, read_names, contig_names)
 
 
 # ---- anchored alignment (hs_map_reads_anchored, hs_realign_intervals_anchored): mapped reads cut at seed anchors before A1 ----
@@ -2277,12 +2275,7 @@ MAP_ANCHOR_READ_FIELDS = ("n_best", "n_chain", "n_supported")
 
 def map_anchor_params(**kw) -> MapAnchorParams:
     """hs_map_anchor_params_default with the given fields replaced"""
-    p = load().hs_map_anchor_params_default()
-    for k, v in kw.items():
-        if k not in dict(MapAnchorParams._fields_):
-            raise HsError("map_anchor_params: no field " + k)
-        setattr(p, k, int(v))
-    return p
+    return _params_with(load().hs_map_anchor_params_default(), "map_anchor_params", kw)
 
 
 def _map_anchors_to_dict(a) -> Dict:
@@ -2299,7 +2292,7 @@ def map_reads_anchored(index: MapIndex, reads, params: Optional[MapAnchorParams]
     """hs_map_reads_anchored: (map result dict as map_reads gives it, anchors dict): anc_off [n_reads + 1], anc_q (on the read as it aligns) and anc_t
     per anchor, n_best / n_chain / n_supported per read. reads: a list of code arrays, or a (codes, offsets) pair."""
     lib = load()
-    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
+    rseq, roff = _reads_arg(reads)
     r = C.POINTER(MapResult)(); a = C.POINTER(MapAnchors)()
     _check(lib.hs_map_reads_anchored(index._h, rseq.ctypes.data, roff.ctypes.data, C.c_int32(len(roff) - 1), C.byref(params) if params is not None else None, C.byref(r), C.byref(a)))
     try:
@@ -2312,48 +2305,12 @@ def map_reads_anchored(index: MapIndex, reads, params: Optional[MapAnchorParams]
 def realign_intervals_anchored(flat_sequences, intervals, anc_off, anc_q, anc_t, pad: int = 100, want_batch: bool = True):
     """hs_realign_intervals_anchored: realign_intervals with the anchors of every interval given (anc_off [n_intervals + 1]; anc_q on the read as it
     aligns, anc_t on the contig). Every alignment is a cheapest one through its anchors, not edlib's HW optimum. Returns (records dict, CvBatch or None)."""
-    import time
-    require_gpu()
-    lib = load()
-    g = (lambda k: flat_sequences[k]) if isinstance(flat_sequences, dict) else (lambda k: getattr(flat_sequences, k))
-    cseq, coff, rseq, roff = _np(g("contig_seq"), np.uint8), _np(g("contig_off"), np.int64), _np(g("read_seq"), np.uint8), _np(g("read_off"), np.int64)
-    iv = np.asarray(intervals, dtype=np.int64).reshape(-1, 7)
-    if iv.size and (np.abs(iv).max() > 0x7fffffff):
-        raise HsError("realign_intervals_anchored: interval fields are 32-bit")
-    col = [_np(iv[:, k], np.uint8 if k == 2 else np.int32) for k in range(7)]
-    aoff, aq, at = _np(anc_off, np.int64), _np(anc_q, np.int32), _np(anc_t, np.int32)
-    if len(aoff) != len(iv) + 1 or len(aq) != len(at) or (len(aoff) and int(aoff[-1]) > len(aq)):
-        raise HsError("realign_intervals_anchored: anc_off has one entry per interval and one more, anc_q and anc_t anc_off[-1] entries")
-    h = C.c_void_p(); r = C.POINTER(RealignRecords)()
-    t0 = time.perf_counter()
-    _check(lib.hs_realign_intervals_anchored(cseq.ctypes.data, coff.ctypes.data, C.c_int32(len(coff) - 1), rseq.ctypes.data, roff.ctypes.data, C.c_int32(len(roff) - 1),
-                                             *[c.ctypes.data for c in col], C.c_int32(len(iv)), C.c_int32(pad), aoff.ctypes.data, aq.ctypes.data, at.ctypes.data,
-                                             C.byref(r), C.byref(h) if want_batch else None))
-    dt = time.perf_counter() - t0
-    try:
-        rec = _realign_records_to_dict(r)
-    finally:
-        lib.hs_realign_records_destroy(r)
-    return rec, (CvBatch._adopt(h, dt, rec) if want_batch else None)
+    return _realign("realign_intervals_anchored", flat_sequences, intervals, (anc_off, anc_q, anc_t), pad, want_batch)
 
 
 def map_to_batch_anchored(index: MapIndex, reads, params: Optional[MapAnchorParams] = None, pad: int = 100):
     """hs_map_to_batch_anchored: map_reads_anchored, then realign_intervals_anchored on the mapped reads with their anchors. Returns (CvBatch, records
     dict, map result dict, anchors dict)."""
-    import time
-    lib = load()
-    rseq, roff = (_np(reads[0], np.uint8), _np(reads[1], np.int64)) if isinstance(reads, tuple) else _flat(reads)
-    h = C.c_void_p(); rec = C.POINTER(RealignRecords)(); r = C.POINTER(MapResult)(); a = C.POINTER(MapAnchors)()
-    t0 = time.perf_counter()
-    _check(lib.hs_map_to_batch_anchored(index._h, index.contig_seq.ctypes.data, index.contig_off.ctypes.data, C.c_int32(len(index.contig_off) - 1), rseq.ctypes.data, roff.ctypes.data,
-                                        C.c_int32(len(roff) - 1), C.c_int32(pad), C.byref(params) if params is not None else None, C.byref(h), C.byref(rec), C.byref(r), C.byref(a)))
-    dt = time.perf_counter() - t0
-    try:
-        records = _realign_records_to_dict(rec)
-        res = _map_result_to_dict(r)
-        anc = _map_anchors_to_dict(a)
-    finally:
-        lib.hs_realign_records_destroy(rec)
-        lib.hs_map_result_destroy(r)
-        lib.hs_map_anchors_destroy(a)
-    return CvBatch._adopt(h, dt, records), records, res, anc
+    return _to_batch("hs_map_to_batch_anchored", index, reads, pad, (params,),
+                     [(MapResult, _map_result_to_dict, "hs_map_result_destroy"), (MapAnchors, _map_anchors_to_dict, "hs_map_anchors_destroy")])
+

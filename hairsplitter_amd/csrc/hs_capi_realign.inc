@@ -2,8 +2,9 @@
 // lines of hs_realign.cpp's parser) -> pairs cut on the device (k_realign_cut) -> A1 (hs_edlib_hw_align) -> CIGAR words on the
 // device (k_m2c_count, the scan, k_m2c_write; hs_kernels_realign.hip) -> the records in the layout of hs_cv_batch_create and the
 // batch made from them. Per round only the words, positions, distances and lengths come back to the host.
-// hs_realign_intervals_anchored cuts every interval at given anchors first: pieces per class -> k_realign_cut -> at most three aligner calls ->
-// k_anchor_join_plan / k_anchor_join -> the same words, positions and download.
+// hs_realign_intervals and hs_realign_intervals_anchored are one job (realign_job): the second cuts every interval at given anchors first, pieces per
+// class -> k_realign_cut -> at most three aligner calls; a round that holds a cut interval joins its pieces (k_anchor_join_plan / k_anchor_join) before
+// the same words, positions and download, a round that holds none takes the aligner's output as it is.
 namespace {
 
 // The three launches of hs_moves_to_cigar with their scratch: count() leaves offsets, total and spans, write() lays the words down.
@@ -149,13 +150,34 @@ void hs_realign_records_destroy(hs_realign_records* r) {
     std::free(r);
 }
 
-int hs_realign_intervals(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads,
-                         const int32_t* iv_read, const int32_t* iv_contig, const uint8_t* iv_strand, const int32_t* iv_qstart, const int32_t* iv_qend,
-                         const int32_t* iv_tstart, const int32_t* iv_tend, int32_t n_intervals, int32_t pad, hs_realign_records** out, hs_cv_batch** batch) {
+namespace {
+
+// the pairs one class of pieces hands to its aligner call: offsets from 0, the cut's sources, where its results lie in the round's arrays
+struct PieceClass {
+    std::vector<int64_t> q_off{0}, t_off{0}, o_off{0}, q_src, t_src;
+    std::vector<uint8_t> q_rev, t_rev;
+    int64_t first = 0, ops_at = 0;      // its section of the numbers (an index) and of the moves (a byte offset)
+    size_t size() const { return q_src.size(); }
+    void add(int64_t qs, bool qr, int64_t ql, int64_t ts, bool tr, int64_t tl) {
+        q_src.push_back(qs); q_rev.push_back(qr ? 1 : 0); t_src.push_back(ts); t_rev.push_back(tr ? 1 : 0);
+        q_off.push_back(q_off.back() + ql); t_off.push_back(t_off.back() + tl); o_off.push_back(o_off.back() + ql + tl);
+    }
+};
+
+// The one job behind hs_realign_intervals (anc_off NULL: no interval has anchors) and hs_realign_intervals_anchored: checks, uploads, rounds, records.
+// Per round: every interval's pieces by class (include/hairsplitter_hip.h; hs_map_host.h, "anchors") -- an interval without anchors is one HW piece --,
+// k_realign_cut per class and side (a head's two strings are cut backwards; complementing both keeps every equality), at most three aligner calls -- HW,
+// SHW PATH for heads and tails, NW PATH for middles. A round whose intervals are all one HW piece is `direct`: the aligner's moves, lengths and
+// distances are the intervals' own and k_realign_pos gives POS. Any other round joins its pieces first (k_anchor_join_plan, k_anchor_join). Then one
+// tail: words on the device, the download, the records.
+static int realign_job(const char* who, const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off,
+                       int32_t n_reads, const int32_t* iv_read, const int32_t* iv_contig, const uint8_t* iv_strand, const int32_t* iv_qstart, const int32_t* iv_qend,
+                       const int32_t* iv_tstart, const int32_t* iv_tend, int32_t n_intervals, int32_t pad, const int64_t* anc_off, const int32_t* anc_q, const int32_t* anc_t,
+                       hs_realign_records** out, hs_cv_batch** batch) {
     if (int rc = require_device()) return rc;
     if (!out || !h_contig_off || !h_read_off || n_contigs < 0 || n_reads < 0 || n_intervals < 0 || pad < 0
         || (n_intervals > 0 && (!iv_read || !iv_contig || !iv_strand || !iv_qstart || !iv_qend || !iv_tstart || !iv_tend))) {
-        set_error("hs_realign_intervals: bad arguments"); return HS_EINVAL;
+        set_error(std::string(who) + ": bad arguments"); return HS_EINVAL;
     }
     *out = nullptr;
     if (batch) *batch = nullptr;
@@ -163,156 +185,35 @@ int hs_realign_intervals(const uint8_t* h_contig_seq, const int64_t* h_contig_of
         const size_t n = (size_t)n_intervals;
         std::vector<int32_t> contig_iv_off, order;
         if (int rc = realign_check_intervals(h_contig_off, n_contigs, h_read_off, n_reads, iv_read, iv_contig, iv_qstart, iv_qend, iv_tstart, iv_tend, n, contig_iv_off, order)) return rc;
-        const hipStream_t stream = nullptr;
-        DBuf d_contigs, d_reads;      // the job's first device copy of the sequences: back in the pool before the batch is made
-        if (n) {
-            if (int rc = upload_pageable(d_contigs, h_contig_seq, (size_t)h_contig_off[n_contigs], HS_SEQ_PAD, HS_SEQ_PAD)) return rc;
-            if (int rc = upload_pageable(d_reads, h_read_seq, (size_t)h_read_off[n_reads], HS_SEQ_PAD, HS_SEQ_PAD)) return rc;
-        }
-        std::vector<int32_t> rec_interval, rec_read, rec_pos, rec_dist, contig_rec_off((size_t)n_contigs + 1, 0), dropped;
-        std::vector<uint8_t> rec_strand;
-        std::vector<int64_t> rec_cig_off(1, 0);
-        std::vector<uint32_t, hs::NoInitAlloc<uint32_t>> cigar;
-        double t_cut = 0, t_align = 0, t_cigar = 0, t_download = 0;
-        int64_t n_rounds = 0, move_bytes = 0;
-        auto wall = [] { return std::chrono::steady_clock::now(); };
-        auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-        const size_t chunk_bases = hs::realign_chunk_bases();
+        // the contig window of an interval, and its read range as it aligns
         auto window = [&](size_t i, int& w0, int& w1) {
             w0 = std::max(0, iv_tstart[i] - pad);
             w1 = (int)std::min<int64_t>(h_contig_off[iv_contig[i] + 1] - h_contig_off[iv_contig[i]], (int64_t)iv_tend[i] + pad);
         };
-        size_t done = 0;
-        while (done < n) {
-            // ---- the pairs of a round, bounded as in hs_realign.cpp: a pair needs query + window bases and as many move bytes ----
-            size_t k1 = done, bases = 0;
-            while (k1 < n && (k1 == done || bases < chunk_bases) && k1 - done < 1000000) {
-                const size_t i = (size_t)order[k1];
-                int w0, w1; window(i, w0, w1);
-                bases += (size_t)(iv_qend[i] - iv_qstart[i]) + (size_t)(w1 - w0);
-                ++k1;
-            }
-            const size_t m = k1 - done;
-            // what the host needs for the launches follows from the interval lengths alone
-            std::vector<int64_t> q_off(m + 1, 0), t_off(m + 1, 0), o_off(m + 1, 0), q_src(m), t_src(m);
-            std::vector<int32_t> win0(m), clip_l(m), clip_r(m);
-            std::vector<uint8_t> rev(m);
-            for (size_t k = 0; k < m; ++k) {
-                const size_t i = (size_t)order[done + k];
-                int w0, w1; window(i, w0, w1);
-                const int qs = iv_qstart[i], qe = iv_qend[i], qlen = (int)(h_read_off[iv_read[i] + 1] - h_read_off[iv_read[i]]);
-                const bool minus = iv_strand[i] == 0;
-                win0[k] = w0; rev[k] = minus ? 1 : 0;
-                q_off[k + 1] = q_off[k] + (qe - qs); t_off[k + 1] = t_off[k] + (w1 - w0); o_off[k + 1] = o_off[k] + (qe - qs) + (w1 - w0);
-                q_src[k] = h_read_off[iv_read[i]] + (minus ? qe - 1 : qs);
-                t_src[k] = h_contig_off[iv_contig[i]] + w0;
-                clip_l[k] = minus ? qlen - qe : qs; clip_r[k] = minus ? qs : qlen - qe;
-            }
-            DBuf dq_off, dt_off, dq_src, dt_src, d_win0, d_clip_l, d_clip_r, d_rev, dq, dt, dd, ds, de, dops, dlen, d_pos, d_word_off, d_words;
-            UploadPack pk;
-            pk.add(q_off, dq_off); pk.add(t_off, dt_off); pk.add(q_src, dq_src); pk.add(t_src, dt_src); pk.add(win0, d_win0); pk.add(clip_l, d_clip_l); pk.add(clip_r, d_clip_r); pk.add(rev, d_rev);
-            if (int rc = pk.commit(stream)) return rc;
-            if (int rc = dq.alloc((size_t)q_off[m] + 16)) return rc;
-            if (int rc = dt.alloc((size_t)t_off[m] + 16)) return rc;
-            if (int rc = dops.alloc((size_t)o_off[m] + 16)) return rc;
-            for (DBuf* b : {&dd, &ds, &de, &dlen, &d_pos}) if (int rc = b->alloc(m * sizeof(int32_t))) return rc;
-            if (int rc = d_word_off.alloc((m + 1) * sizeof(int64_t))) return rc;
-            // ---- cut ----
-            EventPair ev_cut;      // (whatever the step: the records report the cut's time of every call)
-            if (int rc = ev_cut.take()) return rc;
-            HS_HIP(ev_rec(ev_cut.a, stream));
-            if (int rc = realign_cut_launch(dq_off, dq_src, d_rev.as<uint8_t>(), (int32_t)m, q_off[m], d_reads.as<uint8_t>() + HS_SEQ_PAD, dq.as<uint8_t>(), stream)) return rc;
-            if (int rc = realign_cut_launch(dt_off, dt_src, nullptr, (int32_t)m, t_off[m], d_contigs.as<uint8_t>() + HS_SEQ_PAD, dt.as<uint8_t>(), stream)) return rc;
-            HS_HIP(ev_rec(ev_cut.b, stream));
-            // ---- align (synchronous) ----
-            auto t0 = wall();
-            if (int rc = hs_edlib_hw_align(dq.as<uint8_t>(), q_off.data(), dt.as<uint8_t>(), t_off.data(), (int32_t)m, dd.as<int32_t>(), ds.as<int32_t>(), de.as<int32_t>(),
-                                           dops.as<uint8_t>(), o_off.data(), dlen.as<int32_t>(), stream)) return rc;
-            float cut_ms = 0;
-            if (int rc = ev_cut.ms(&cut_ms)) return rc;
-            t_cut += cut_ms; t_align += ms_since(t0) - cut_ms;      // (the cut runs ahead of the aligner on the same stream)
-            // ---- moves -> words: a pair without a path gets none, so the words of the round lie compact ----
-            t0 = wall();
-            MovesToCigar mc;
-            int64_t n_words = 0;
-            if (int rc = mc.count(dops.as<uint8_t>(), o_off.data(), dlen.as<int32_t>(), d_clip_l.as<int32_t>(), d_clip_r.as<int32_t>(), (int32_t)m, d_word_off.as<int64_t>(), nullptr, &n_words, stream)) return rc;
-            if (int rc = d_words.alloc(std::max<size_t>(1, (size_t)n_words) * sizeof(uint32_t))) return rc;
-            hipLaunchKernelGGL(hsdev::k_realign_pos, dim3((unsigned)(m / 256 + 1)), dim3(256), 0, stream, d_win0.as<int32_t>(), ds.as<int32_t>(), (int)m, d_pos.as<int32_t>());
-            HS_HIP(hipGetLastError());
-            if (int rc = mc.write(d_words.as<uint32_t>(), stream)) return rc;
-            t_cigar += ms_since(t0);
-            // ---- words, positions, distances, lengths ----
-            t0 = wall();
-            std::vector<int32_t> pos(m), dist(m), olen(m);
-            std::vector<int64_t> word_off(m + 1);
-            const size_t w_at = cigar.size();
-            cigar.resize(w_at + (size_t)n_words);
-            if (int rc = d2h_pinned(cigar.data() + w_at, d_words.p, (size_t)n_words * sizeof(uint32_t), stream)) return rc;
-            if (int rc = d2h_pinned(word_off.data(), d_word_off.p, (m + 1) * sizeof(int64_t), stream)) return rc;
-            if (int rc = d2h_pinned(pos.data(), d_pos.p, m * sizeof(int32_t), stream)) return rc;
-            if (int rc = d2h_pinned(dist.data(), dd.p, m * sizeof(int32_t), stream)) return rc;
-            if (int rc = d2h_pinned(olen.data(), dlen.p, m * sizeof(int32_t), stream)) return rc;
-            t_download += ms_since(t0);
-            for (size_t k = 0; k < m; ++k) {
-                const size_t i = (size_t)order[done + k];
-                if (olen[k] <= 0) { dropped.push_back((int32_t)i); continue; }      // (edlib has no alignment for this pair: no record)
-                rec_interval.push_back((int32_t)i); rec_read.push_back(iv_read[i]); rec_pos.push_back(pos[k]); rec_dist.push_back(dist[k]);
-                rec_strand.push_back(iv_strand[i] ? 1 : 0);
-                rec_cig_off.push_back((int64_t)w_at + word_off[k + 1]);
-                contig_rec_off[(size_t)iv_contig[i] + 1]++;
-                move_bytes += olen[k];
-            }
-            ++n_rounds;
-            done = k1;
-        }
-        d_contigs.release(); d_reads.release();      // (the pool hands the same blocks to hs_cv_batch_create below)
-        RealignTotals tot{t_cut, t_align, t_cigar, t_download, 0.0, n_rounds, move_bytes, (int64_t)n};
-        return realign_make_records("hs_realign_intervals", h_contig_seq, h_contig_off, n_contigs, h_read_seq, h_read_off, n_reads, n_intervals, rec_interval, rec_read, rec_pos, rec_dist,
-                                    contig_rec_off, dropped, rec_strand, rec_cig_off, cigar, tot, out, batch);
-    } catch (const std::exception& e) { set_error(std::string("hs_realign_intervals: ") + e.what()); return HS_EINVAL; }
-}
-
-// hs_realign_intervals with every interval cut at its anchors (hs_map_host.h, "anchors"; the pieces: include/hairsplitter_hip.h). Per round: the pieces'
-// offsets from the anchors on the host, k_realign_cut per class and side (a head's two strings are cut backwards; complementing both keeps every
-// equality), at most three aligner calls -- HW for the intervals without anchors, SHW PATH for heads and tails, NW PATH for middles --, the join
-// (k_anchor_join_plan, k_anchor_join), then words, positions and the download as hs_realign_intervals has them.
-int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads,
-                                  const int32_t* iv_read, const int32_t* iv_contig, const uint8_t* iv_strand, const int32_t* iv_qstart, const int32_t* iv_qend,
-                                  const int32_t* iv_tstart, const int32_t* iv_tend, int32_t n_intervals, int32_t pad, const int64_t* anc_off, const int32_t* anc_q, const int32_t* anc_t,
-                                  hs_realign_records** out, hs_cv_batch** batch) {
-    if (int rc = require_device()) return rc;
-    if (!out || !h_contig_off || !h_read_off || n_contigs < 0 || n_reads < 0 || n_intervals < 0 || pad < 0 || !anc_off
-        || (n_intervals > 0 && (!iv_read || !iv_contig || !iv_strand || !iv_qstart || !iv_qend || !iv_tstart || !iv_tend))) {
-        set_error("hs_realign_intervals_anchored: bad arguments"); return HS_EINVAL;
-    }
-    *out = nullptr;
-    if (batch) *batch = nullptr;
-    try {
-        const size_t n = (size_t)n_intervals;
-        std::vector<int32_t> contig_iv_off, order;
-        if (int rc = realign_check_intervals(h_contig_off, n_contigs, h_read_off, n_reads, iv_read, iv_contig, iv_qstart, iv_qend, iv_tstart, iv_tend, n, contig_iv_off, order)) return rc;
-        // the read range of an interval as it aligns
         auto range = [&](size_t i, int& a0, int& a1) {
             const int Lr = (int)(h_read_off[iv_read[i] + 1] - h_read_off[iv_read[i]]);
             a0 = iv_strand[i] ? iv_qstart[i] : Lr - iv_qend[i]; a1 = iv_strand[i] ? iv_qend[i] : Lr - iv_qstart[i];
         };
-        bool offsets_ok = anc_off[0] == 0;
-        for (size_t i = 0; offsets_ok && i < n; ++i) offsets_ok = anc_off[i + 1] >= anc_off[i] && anc_off[i + 1] - anc_off[i] <= 0x7fffffff;
-        if (!offsets_ok || (anc_off[n] > 0 && (!anc_q || !anc_t))) { set_error("hs_realign_intervals_anchored: anc_off must ascend from 0, and anc_q / anc_t hold anc_off[n_intervals] anchors"); return HS_EINVAL; }
-        for (size_t i = 0; i < n; ++i) {
-            int a0, a1; range(i, a0, a1);
-            for (int64_t j = anc_off[i]; j < anc_off[i + 1]; ++j) {
-                const bool rises = j == anc_off[i] || (anc_q[j] > anc_q[j - 1] && anc_t[j] > anc_t[j - 1]);
-                if (!rises || anc_q[j] < a0 || anc_q[j] > a1 || anc_t[j] < iv_tstart[i] || anc_t[j] > iv_tend[i]) {
-                    set_error("hs_realign_intervals_anchored: interval " + std::to_string(i) + ": anchor " + std::to_string(j - anc_off[i]) + " (q " + std::to_string(anc_q[j]) + ", t "
-                              + std::to_string(anc_t[j]) + ") does not ascend strictly in q and t or lies outside the interval (read as it aligns [" + std::to_string(a0) + ", " + std::to_string(a1)
-                              + "], contig [" + std::to_string(iv_tstart[i]) + ", " + std::to_string(iv_tend[i]) + "])");
-                    return HS_EINVAL;
+        auto n_anchors = [&](size_t i) { return anc_off ? anc_off[i + 1] - anc_off[i] : (int64_t)0; };
+        if (anc_off) {
+            bool offsets_ok = anc_off[0] == 0;
+            for (size_t i = 0; offsets_ok && i < n; ++i) offsets_ok = anc_off[i + 1] >= anc_off[i] && anc_off[i + 1] - anc_off[i] <= 0x7fffffff;
+            if (!offsets_ok || (anc_off[n] > 0 && (!anc_q || !anc_t))) { set_error(std::string(who) + ": anc_off must ascend from 0, and anc_q / anc_t hold anc_off[n_intervals] anchors"); return HS_EINVAL; }
+            for (size_t i = 0; i < n; ++i) {
+                int a0, a1; range(i, a0, a1);
+                for (int64_t j = anc_off[i]; j < anc_off[i + 1]; ++j) {
+                    const bool rises = j == anc_off[i] || (anc_q[j] > anc_q[j - 1] && anc_t[j] > anc_t[j - 1]);
+                    if (!rises || anc_q[j] < a0 || anc_q[j] > a1 || anc_t[j] < iv_tstart[i] || anc_t[j] > iv_tend[i]) {
+                        set_error(std::string(who) + ": interval " + std::to_string(i) + ": anchor " + std::to_string(j - anc_off[i]) + " (q " + std::to_string(anc_q[j]) + ", t "
+                                  + std::to_string(anc_t[j]) + ") does not ascend strictly in q and t or lies outside the interval (read as it aligns [" + std::to_string(a0) + ", " + std::to_string(a1)
+                                  + "], contig [" + std::to_string(iv_tstart[i]) + ", " + std::to_string(iv_tend[i]) + "])");
+                        return HS_EINVAL;
+                    }
                 }
             }
         }
         const hipStream_t stream = nullptr;
-        DBuf d_contigs, d_reads;
+        DBuf d_contigs, d_reads;      // the job's first device copy of the sequences: back in the pool before the batch is made
         if (n) {
             if (int rc = upload_pageable(d_contigs, h_contig_seq, (size_t)h_contig_off[n_contigs], HS_SEQ_PAD, HS_SEQ_PAD)) return rc;
             if (int rc = upload_pageable(d_reads, h_read_seq, (size_t)h_read_off[n_reads], HS_SEQ_PAD, HS_SEQ_PAD)) return rc;
@@ -325,33 +226,20 @@ int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_
         auto wall = [] { return std::chrono::steady_clock::now(); };
         auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
         const size_t chunk_bases = hs::realign_chunk_bases();
-        auto window = [&](size_t i, int& w0, int& w1) {
-            w0 = std::max(0, iv_tstart[i] - pad);
-            w1 = (int)std::min<int64_t>(h_contig_off[iv_contig[i] + 1] - h_contig_off[iv_contig[i]], (int64_t)iv_tend[i] + pad);
-        };
-        // the pairs one class of pieces hands to its aligner call: offsets from 0, the cut's sources, where its results lie in the round's arrays
-        struct PieceClass {
-            std::vector<int64_t> q_off{0}, t_off{0}, o_off{0}, q_src, t_src;
-            std::vector<uint8_t> q_rev, t_rev;
-            int64_t first = 0, ops_at = 0;      // its section of the numbers (an index) and of the moves (a byte offset)
-            size_t size() const { return q_src.size(); }
-            void add(int64_t qs, bool qr, int64_t ql, int64_t ts, bool tr, int64_t tl) {
-                q_src.push_back(qs); q_rev.push_back(qr ? 1 : 0); t_src.push_back(ts); t_rev.push_back(tr ? 1 : 0);
-                q_off.push_back(q_off.back() + ql); t_off.push_back(t_off.back() + tl); o_off.push_back(o_off.back() + ql + tl);
-            }
-        };
         size_t done = 0;
         while (done < n) {
-            // ---- the intervals of a round: bounded as hs_realign_intervals' by their bases; an interval's pieces stay together and count as pairs ----
+            // ---- the intervals of a round, bounded as in hs_realign.cpp: an interval needs query + window bases and as many move bytes; its pieces
+            // stay together and count as pairs ----
             size_t k1 = done, bases = 0, pairs = 0;
-            while (k1 < n && (k1 == done || (bases < chunk_bases && pairs + (size_t)(anc_off[order[k1] + 1] - anc_off[order[k1]]) + 1 <= 1000000))) {
+            while (k1 < n && (k1 == done || (bases < chunk_bases && pairs + (size_t)n_anchors((size_t)order[k1]) + 1 <= 1000000))) {
                 const size_t i = (size_t)order[k1];
                 int w0, w1; window(i, w0, w1);
                 bases += (size_t)(iv_qend[i] - iv_qstart[i]) + (size_t)(w1 - w0);
-                pairs += (size_t)(anc_off[i + 1] - anc_off[i]) + 1;
+                pairs += (size_t)n_anchors(i) + 1;
                 ++k1;
             }
             const size_t m = k1 - done;
+            // ---- the piece table: what the host needs for the launches follows from the interval lengths and the anchors alone ----
             PieceClass cls[3];      // 0: HW, 1: SHW (heads and tails), 2: NW
             std::vector<int32_t> iv_piece(m + 1, 0), iv_base(m), clip_l(m), clip_r(m), pc_idx, pc_room;
             std::vector<int64_t> join_off(m + 1, 0), pc_ops;
@@ -372,9 +260,9 @@ int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_
                     pc_kind.push_back((uint8_t)kind); pc_cls.push_back((uint8_t)c); pc_idx.push_back((int32_t)cls[c].size() - 1); pc_room.push_back((x1 - x0) + (t1 - t0));
                 };
                 auto insertions = [&](int count) { pc_kind.push_back((uint8_t)hsdev::ANCHOR_INS); pc_cls.push_back(3); pc_idx.push_back(count); pc_room.push_back(count); };
-                const int64_t j0 = anc_off[i], j1 = anc_off[i + 1];
-                if (j0 == j1) { iv_base[k] = w0; piece(0, hsdev::ANCHOR_HW, a0, a1, w0, w1); }
+                if (n_anchors(i) == 0) { iv_base[k] = w0; piece(0, hsdev::ANCHOR_HW, a0, a1, w0, w1); }
                 else {
+                    const int64_t j0 = anc_off[i], j1 = anc_off[i + 1];
                     iv_base[k] = anc_t[j0];
                     if (anc_q[j0] > a0) { if (anc_t[j0] > w0) piece(1, hsdev::ANCHOR_HEAD, a0, anc_q[j0], w0, anc_t[j0]); else insertions(anc_q[j0] - a0); }
                     for (int64_t j = j0; j + 1 < j1; ++j) piece(2, hsdev::ANCHOR_MID, anc_q[j], anc_q[j + 1], anc_t[j], anc_t[j + 1]);
@@ -382,45 +270,52 @@ int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_
                 }
                 iv_piece[k + 1] = (int32_t)pc_kind.size();
             }
+            const bool direct = cls[0].size() == m;      // (every interval of the round is one HW piece: class 0's pair k is interval k)
+            const int n_cls = direct ? 1 : 3;
             // the classes' sections: numbers from a multiple of 64, moves from a multiple of 256
             int64_t n_num = 0, n_ops = 0;
             for (PieceClass& c : cls) { c.first = n_num; c.ops_at = n_ops; n_num = (n_num + (int64_t)c.size() + 63) & ~(int64_t)63; n_ops = (n_ops + c.o_off.back() + 16 + 255) & ~(int64_t)255; }
             const size_t P = pc_kind.size();
-            pc_ops.assign(P, 0);
-            for (size_t p = 0; p < P; ++p) {
-                if (pc_cls[p] > 2) continue;
-                const PieceClass& c = cls[pc_cls[p]];
-                pc_ops[p] = c.ops_at + c.o_off[(size_t)pc_idx[p]];
-                pc_idx[p] = (int32_t)(c.first + pc_idx[p]);
-            }
             tot.n_pieces += (int64_t)(cls[0].size() + cls[1].size() + cls[2].size());
             DBuf d_q_off[3], d_t_off[3], d_q_src[3], d_t_src[3], d_q_rev[3], d_t_rev[3], d_q[3], d_t[3];
             DBuf d_iv_piece, d_iv_base, d_clip_l, d_clip_r, d_join_off, d_pc_idx, d_pc_room, d_pc_ops, d_pc_kind, dd, ds, de, dlen, dops, d_pc_at, d_len, d_dist, d_pos, d_joined, d_word_off, d_words;
             UploadPack pk;
-            for (int c = 0; c < 3; ++c) {
-                pk.add(cls[c].q_off, d_q_off[c]); pk.add(cls[c].t_off, d_t_off[c]); pk.add(cls[c].q_src, d_q_src[c]); pk.add(cls[c].t_src, d_t_src[c]);
-                pk.add(cls[c].q_rev, d_q_rev[c]); pk.add(cls[c].t_rev, d_t_rev[c]);
+            for (int c = 0; c < n_cls; ++c) {
+                pk.add(cls[c].q_off, d_q_off[c]); pk.add(cls[c].t_off, d_t_off[c]); pk.add(cls[c].q_src, d_q_src[c]); pk.add(cls[c].t_src, d_t_src[c]); pk.add(cls[c].q_rev, d_q_rev[c]);
+                if (c > 0) pk.add(cls[c].t_rev, d_t_rev[c]);      // (an HW piece's window is never cut backwards: no flags)
             }
-            pk.add(iv_piece, d_iv_piece); pk.add(iv_base, d_iv_base); pk.add(clip_l, d_clip_l); pk.add(clip_r, d_clip_r); pk.add(join_off, d_join_off);
-            pk.add(pc_idx, d_pc_idx); pk.add(pc_room, d_pc_room); pk.add(pc_ops, d_pc_ops); pk.add(pc_kind, d_pc_kind);
+            pk.add(iv_base, d_iv_base); pk.add(clip_l, d_clip_l); pk.add(clip_r, d_clip_r);
+            if (!direct) {      // the join's table
+                pc_ops.assign(P, 0);
+                for (size_t p = 0; p < P; ++p) {
+                    if (pc_cls[p] > 2) continue;
+                    const PieceClass& c = cls[pc_cls[p]];
+                    pc_ops[p] = c.ops_at + c.o_off[(size_t)pc_idx[p]];
+                    pc_idx[p] = (int32_t)(c.first + pc_idx[p]);
+                }
+                pk.add(iv_piece, d_iv_piece); pk.add(join_off, d_join_off); pk.add(pc_idx, d_pc_idx); pk.add(pc_room, d_pc_room); pk.add(pc_ops, d_pc_ops); pk.add(pc_kind, d_pc_kind);
+            }
             if (int rc = pk.commit(stream)) return rc;
-            for (int c = 0; c < 3; ++c) {
+            for (int c = 0; c < n_cls; ++c) {
                 if (int rc = d_q[c].alloc((size_t)cls[c].q_off.back() + 16)) return rc;
                 if (int rc = d_t[c].alloc((size_t)cls[c].t_off.back() + 16)) return rc;
             }
-            if (int rc = dops.alloc((size_t)n_ops + 16)) return rc;
-            for (DBuf* b : {&dd, &ds, &de, &dlen}) if (int rc = b->alloc((size_t)std::max<int64_t>(n_num, 64) * sizeof(int32_t))) return rc;
-            if (int rc = d_pc_at.alloc(std::max<size_t>(P, 1) * sizeof(int32_t))) return rc;
-            for (DBuf* b : {&d_len, &d_dist, &d_pos}) if (int rc = b->alloc(m * sizeof(int32_t))) return rc;
-            const int64_t joined_bytes = (join_off[m] + 15) & ~(int64_t)15;
-            if (int rc = d_joined.alloc((size_t)joined_bytes + 16)) return rc;
+            if (int rc = dops.alloc((size_t)(direct ? cls[0].o_off.back() : n_ops) + 16)) return rc;
+            for (DBuf* b : {&dd, &ds, &de, &dlen}) if (int rc = b->alloc((direct ? m : (size_t)std::max<int64_t>(n_num, 64)) * sizeof(int32_t))) return rc;
+            if (int rc = d_pos.alloc(m * sizeof(int32_t))) return rc;
             if (int rc = d_word_off.alloc((m + 1) * sizeof(int64_t))) return rc;
+            const int64_t joined_bytes = (join_off[m] + 15) & ~(int64_t)15;
+            if (!direct) {
+                if (int rc = d_pc_at.alloc(std::max<size_t>(P, 1) * sizeof(int32_t))) return rc;
+                for (DBuf* b : {&d_len, &d_dist}) if (int rc = b->alloc(m * sizeof(int32_t))) return rc;
+                if (int rc = d_joined.alloc((size_t)joined_bytes + 16)) return rc;
+            }
             // ---- cut: each class's two buffers ----
-            EventPair ev_cut, ev_join;
+            EventPair ev_cut, ev_join;      // (whatever the step: the records report the cut's and the join's time of every call)
             if (int rc = ev_cut.take()) return rc;
-            if (int rc = ev_join.take()) return rc;
+            if (!direct) { if (int rc = ev_join.take()) return rc; }
             HS_HIP(ev_rec(ev_cut.a, stream));
-            for (int c = 0; c < 3; ++c) {
+            for (int c = 0; c < n_cls; ++c) {
                 const int32_t mc = (int32_t)cls[c].size();
                 if (int rc = realign_cut_launch(d_q_off[c], d_q_src[c], d_q_rev[c].as<uint8_t>(), mc, cls[c].q_off.back(), d_reads.as<uint8_t>() + HS_SEQ_PAD, d_q[c].as<uint8_t>(), stream)) return rc;
                 if (int rc = realign_cut_launch(d_t_off[c], d_t_src[c], d_t_rev[c].as<uint8_t>(), mc, cls[c].t_off.back(), d_contigs.as<uint8_t>() + HS_SEQ_PAD, d_t[c].as<uint8_t>(), stream)) return rc;
@@ -428,7 +323,8 @@ int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_
             HS_HIP(ev_rec(ev_cut.b, stream));
             // ---- align (synchronous): at most three calls, none for a class without pieces ----
             auto t0 = wall();
-            for (int c = 0; c < 3; ++c) {
+            bool aligned = false;
+            for (int c = 0; c < n_cls; ++c) {
                 const int32_t mc = (int32_t)cls[c].size();
                 if (mc == 0) continue;
                 int32_t* dist = dd.as<int32_t>() + cls[c].first; int32_t* start = ds.as<int32_t>() + cls[c].first; int32_t* end = de.as<int32_t>() + cls[c].first;
@@ -438,32 +334,42 @@ int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_
                                       : hs_edlib_align(d_q[c].as<uint8_t>(), cls[c].q_off.data(), d_t[c].as<uint8_t>(), cls[c].t_off.data(), mc, c == 1 ? 1 : 0, 2, -1, dist, start, end, nullptr, ops,
                                                        cls[c].o_off.data(), len, stream);
                 if (rc) return rc;
+                aligned = true;
             }
-            if (int rc = stream_wait(stream)) return rc;      // (a round without an aligner call: the cut's events)
-            float cut_ms = 0;
+            if (!aligned) { if (int rc = stream_wait(stream)) return rc; }      // (a round without an aligner call: the cut's events)
+            float cut_ms = 0, join_ms = 0;
             if (int rc = ev_cut.ms(&cut_ms)) return rc;
-            tot.t_cut += cut_ms; tot.t_align += ms_since(t0) - cut_ms;
-            // ---- join: every interval's piece moves as one string ----
+            tot.t_cut += cut_ms; tot.t_align += ms_since(t0) - cut_ms;      // (the cut runs ahead of the aligner on the same stream)
+            // ---- join: every interval's piece moves as one string; a direct round's are the aligner's ----
             t0 = wall();
-            hsdev::AnchorJoinArgs J{};
-            J.m = (int)m; J.iv_piece = d_iv_piece.as<int32_t>(); J.iv_base = d_iv_base.as<int32_t>(); J.join_off = d_join_off.as<int64_t>();
-            J.pc_kind = d_pc_kind.as<uint8_t>(); J.pc_idx = d_pc_idx.as<int32_t>(); J.pc_room = d_pc_room.as<int32_t>(); J.pc_ops = d_pc_ops.as<int64_t>();
-            J.ops = dops.as<uint8_t>(); J.dist = dd.as<int32_t>(); J.start = ds.as<int32_t>(); J.end = de.as<int32_t>(); J.len = dlen.as<int32_t>();
-            J.pc_at = d_pc_at.as<int32_t>(); J.out_len = d_len.as<int32_t>(); J.out_dist = d_dist.as<int32_t>(); J.out_pos = d_pos.as<int32_t>();
-            J.joined = d_joined.as<uint8_t>(); J.joined_bytes = joined_bytes;
-            HS_HIP(ev_rec(ev_join.a, stream));
-            hipLaunchKernelGGL(hsdev::k_anchor_join_plan, dim3((unsigned)(m / 256 + 1)), dim3(256), 0, stream, J);
-            if (joined_bytes > 0) hipLaunchKernelGGL(hsdev::k_anchor_join, dim3((unsigned)((joined_bytes + 4095) >> 12)), dim3(256), 0, stream, J);
-            HS_HIP(hipGetLastError());
-            HS_HIP(ev_rec(ev_join.b, stream));
-            // ---- moves -> words ----
+            const uint8_t* r_ops = dops.as<uint8_t>();
+            const int64_t* r_ops_off = cls[0].o_off.data();
+            const int32_t* r_len = dlen.as<int32_t>(); const int32_t* r_dist = dd.as<int32_t>();
+            if (!direct) {
+                hsdev::AnchorJoinArgs J{};
+                J.m = (int)m; J.iv_piece = d_iv_piece.as<int32_t>(); J.iv_base = d_iv_base.as<int32_t>(); J.join_off = d_join_off.as<int64_t>();
+                J.pc_kind = d_pc_kind.as<uint8_t>(); J.pc_idx = d_pc_idx.as<int32_t>(); J.pc_room = d_pc_room.as<int32_t>(); J.pc_ops = d_pc_ops.as<int64_t>();
+                J.ops = dops.as<uint8_t>(); J.dist = dd.as<int32_t>(); J.start = ds.as<int32_t>(); J.end = de.as<int32_t>(); J.len = dlen.as<int32_t>();
+                J.pc_at = d_pc_at.as<int32_t>(); J.out_len = d_len.as<int32_t>(); J.out_dist = d_dist.as<int32_t>(); J.out_pos = d_pos.as<int32_t>();
+                J.joined = d_joined.as<uint8_t>(); J.joined_bytes = joined_bytes;
+                HS_HIP(ev_rec(ev_join.a, stream));
+                hipLaunchKernelGGL(hsdev::k_anchor_join_plan, dim3((unsigned)(m / 256 + 1)), dim3(256), 0, stream, J);
+                if (joined_bytes > 0) hipLaunchKernelGGL(hsdev::k_anchor_join, dim3((unsigned)((joined_bytes + 4095) >> 12)), dim3(256), 0, stream, J);
+                HS_HIP(hipGetLastError());
+                HS_HIP(ev_rec(ev_join.b, stream));
+                r_ops = d_joined.as<uint8_t>(); r_ops_off = join_off.data(); r_len = d_len.as<int32_t>(); r_dist = d_dist.as<int32_t>();
+            }
+            // ---- moves -> words: an interval without a path gets none, so the words of the round lie compact ----
             MovesToCigar mc;
             int64_t n_words = 0;
-            if (int rc = mc.count(d_joined.as<uint8_t>(), join_off.data(), d_len.as<int32_t>(), d_clip_l.as<int32_t>(), d_clip_r.as<int32_t>(), (int32_t)m, d_word_off.as<int64_t>(), nullptr, &n_words, stream)) return rc;
+            if (int rc = mc.count(r_ops, r_ops_off, r_len, d_clip_l.as<int32_t>(), d_clip_r.as<int32_t>(), (int32_t)m, d_word_off.as<int64_t>(), nullptr, &n_words, stream)) return rc;
             if (int rc = d_words.alloc(std::max<size_t>(1, (size_t)n_words) * sizeof(uint32_t))) return rc;
+            if (direct) {
+                hipLaunchKernelGGL(hsdev::k_realign_pos, dim3((unsigned)(m / 256 + 1)), dim3(256), 0, stream, d_iv_base.as<int32_t>(), ds.as<int32_t>(), (int)m, d_pos.as<int32_t>());
+                HS_HIP(hipGetLastError());
+            }
             if (int rc = mc.write(d_words.as<uint32_t>(), stream)) return rc;
-            float join_ms = 0;
-            if (int rc = ev_join.ms(&join_ms)) return rc;
+            if (int rc = ev_join.ms(&join_ms)) return rc;      // (0 for a direct round: it took no events)
             tot.t_join += join_ms; tot.t_cigar += ms_since(t0) - join_ms;
             // ---- words, positions, distances, lengths ----
             t0 = wall();
@@ -474,12 +380,12 @@ int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_
             if (int rc = d2h_pinned(cigar.data() + w_at, d_words.p, (size_t)n_words * sizeof(uint32_t), stream)) return rc;
             if (int rc = d2h_pinned(word_off.data(), d_word_off.p, (m + 1) * sizeof(int64_t), stream)) return rc;
             if (int rc = d2h_pinned(pos.data(), d_pos.p, m * sizeof(int32_t), stream)) return rc;
-            if (int rc = d2h_pinned(dist.data(), d_dist.p, m * sizeof(int32_t), stream)) return rc;
-            if (int rc = d2h_pinned(olen.data(), d_len.p, m * sizeof(int32_t), stream)) return rc;
+            if (int rc = d2h_pinned(dist.data(), r_dist, m * sizeof(int32_t), stream)) return rc;
+            if (int rc = d2h_pinned(olen.data(), r_len, m * sizeof(int32_t), stream)) return rc;
             tot.t_download += ms_since(t0);
             for (size_t k = 0; k < m; ++k) {
                 const size_t i = (size_t)order[done + k];
-                if (olen[k] <= 0) { dropped.push_back((int32_t)i); continue; }
+                if (olen[k] <= 0) { dropped.push_back((int32_t)i); continue; }      // (edlib has no alignment for this interval: no record)
                 rec_interval.push_back((int32_t)i); rec_read.push_back(iv_read[i]); rec_pos.push_back(pos[k]); rec_dist.push_back(dist[k]);
                 rec_strand.push_back(iv_strand[i] ? 1 : 0);
                 rec_cig_off.push_back((int64_t)w_at + word_off[k + 1]);
@@ -490,10 +396,31 @@ int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_
             done = k1;
         }
         d_contigs.release(); d_reads.release();      // (the pool hands the same blocks to hs_cv_batch_create below)
-        return realign_make_records("hs_realign_intervals_anchored", h_contig_seq, h_contig_off, n_contigs, h_read_seq, h_read_off, n_reads, n_intervals, rec_interval, rec_read, rec_pos, rec_dist,
+        return realign_make_records(who, h_contig_seq, h_contig_off, n_contigs, h_read_seq, h_read_off, n_reads, n_intervals, rec_interval, rec_read, rec_pos, rec_dist,
                                     contig_rec_off, dropped, rec_strand, rec_cig_off, cigar, tot, out, batch);
-    } catch (const std::exception& e) { set_error(std::string("hs_realign_intervals_anchored: ") + e.what()); return HS_EINVAL; }
+    } catch (const std::exception& e) { set_error(std::string(who) + ": " + e.what()); return HS_EINVAL; }
 }
+
+}  // namespace
+
+int hs_realign_intervals(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads,
+                         const int32_t* iv_read, const int32_t* iv_contig, const uint8_t* iv_strand, const int32_t* iv_qstart, const int32_t* iv_qend,
+                         const int32_t* iv_tstart, const int32_t* iv_tend, int32_t n_intervals, int32_t pad, hs_realign_records** out, hs_cv_batch** batch) {
+    return realign_job("hs_realign_intervals", h_contig_seq, h_contig_off, n_contigs, h_read_seq, h_read_off, n_reads, iv_read, iv_contig, iv_strand, iv_qstart, iv_qend, iv_tstart, iv_tend,
+                       n_intervals, pad, nullptr, nullptr, nullptr, out, batch);
+}
+
+// hs_realign_intervals with every interval cut at its anchors
+int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_contig_off, int32_t n_contigs, const uint8_t* h_read_seq, const int64_t* h_read_off, int32_t n_reads,
+                                  const int32_t* iv_read, const int32_t* iv_contig, const uint8_t* iv_strand, const int32_t* iv_qstart, const int32_t* iv_qend,
+                                  const int32_t* iv_tstart, const int32_t* iv_tend, int32_t n_intervals, int32_t pad, const int64_t* anc_off, const int32_t* anc_q, const int32_t* anc_t,
+                                  hs_realign_records** out, hs_cv_batch** batch) {
+    if (int rc = require_device()) return rc;
+    if (!anc_off) { set_error("hs_realign_intervals_anchored: bad arguments"); return HS_EINVAL; }
+    return realign_job("hs_realign_intervals_anchored", h_contig_seq, h_contig_off, n_contigs, h_read_seq, h_read_off, n_reads, iv_read, iv_contig, iv_strand, iv_qstart, iv_qend, iv_tstart,
+                       iv_tend, n_intervals, pad, anc_off, anc_q, anc_t, out, batch);
+}
+
 
 int hs_cv_batch_create_paf(const char* gfa, const char* reads, const char* paf, int32_t n_threads, hs_cv_batch** batch, hs_realign_records** recs) {
     if (int rc = require_device()) return rc;

@@ -178,25 +178,41 @@ int map_split_one_read(const MapIndexHost& ix, const hs_map_split_params& sp, in
     map_segments_sort(segs, n);
     return n;
 }
-}  // namespace
-
-int map_reads_host(const MapIndexHost& ix, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapResultHost& out, std::string& err) {
+// what the three host jobs ask of their reads
+int map_check_reads(const int64_t* read_off, int32_t n_reads, std::string& err) {
     if (n_reads < 0 || !read_off) { err = "map reads: bad arguments"; return HS_EINVAL; }
     for (int32_t r = 0; r < n_reads; ++r)
         if (read_off[r + 1] < read_off[r] || read_off[r + 1] - read_off[r] > 0x7fffffff) { err = "map reads: a read of more than 2^31 bases"; return HS_EINVAL; }
+    return HS_OK;
+}
+
+// per_read(r, hits, keys) for every read of a job: the reads strided over the threads, each thread with its own scratch; one thread runs inline
+template <class PerRead> void map_for_each_read(int32_t n_reads, int n_threads, PerRead per_read) {
     const size_t n = (size_t)n_reads;
-    for (std::vector<int32_t>* v : {&out.contig, &out.qstart, &out.qend, &out.tstart, &out.tend, &out.votes, &out.second, &out.n_minimizers, &out.n_skipped}) v->assign(n, 0);
-    out.strand.assign(n, 0); out.n_hits.assign(n, 0);
     n_threads = std::max(1, std::min(n_threads, std::max(1, n_reads)));
     auto work = [&](int t) {
         std::vector<Hit> hits;
         std::vector<uint64_t> keys;
-        for (size_t r = (size_t)t; r < n; r += (size_t)n_threads) map_one_read(ix, read_seq + read_off[r], read_off[r + 1] - read_off[r], r, out, hits, keys);
+        for (size_t r = (size_t)t; r < n; r += (size_t)n_threads) per_read(r, hits, keys);
     };
-    if (n_threads == 1) { work(0); return HS_OK; }
+    if (n_threads == 1) { work(0); return; }
     std::vector<std::thread> th;
     for (int t = 0; t < n_threads; ++t) th.emplace_back(work, t);
     for (std::thread& t : th) t.join();
+}
+
+void map_result_zero(MapResultHost& out, size_t n) {
+    for (std::vector<int32_t>* v : {&out.contig, &out.qstart, &out.qend, &out.tstart, &out.tend, &out.votes, &out.second, &out.n_minimizers, &out.n_skipped}) v->assign(n, 0);
+    out.strand.assign(n, 0); out.n_hits.assign(n, 0);
+}
+}  // namespace
+
+int map_reads_host(const MapIndexHost& ix, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapResultHost& out, std::string& err) {
+    if (int rc = map_check_reads(read_off, n_reads, err)) return rc;
+    map_result_zero(out, (size_t)n_reads);
+    map_for_each_read(n_reads, n_threads, [&](size_t r, std::vector<Hit>& hits, std::vector<uint64_t>& keys) {
+        map_one_read(ix, read_seq + read_off[r], read_off[r + 1] - read_off[r], r, out, hits, keys);
+    });
     return HS_OK;
 }
 
@@ -223,30 +239,16 @@ void map_anchors_of_keys(const hs_map_anchor_params& ap, int64_t Lr, std::vector
 int map_anchors_host(const MapIndexHost& ix, const hs_map_anchor_params& ap, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapResultHost& out,
                      MapAnchorsHost& anchors, std::string& err) {
     if (!map_anchor_params_valid(ap)) { err = "map reads: anchor parameters out of range (spacing >= 1)"; return HS_EINVAL; }
-    if (n_reads < 0 || !read_off) { err = "map reads: bad arguments"; return HS_EINVAL; }
-    for (int32_t r = 0; r < n_reads; ++r)
-        if (read_off[r + 1] < read_off[r] || read_off[r + 1] - read_off[r] > 0x7fffffff) { err = "map reads: a read of more than 2^31 bases"; return HS_EINVAL; }
+    if (int rc = map_check_reads(read_off, n_reads, err)) return rc;
     const size_t n = (size_t)n_reads;
-    for (std::vector<int32_t>* v : {&out.contig, &out.qstart, &out.qend, &out.tstart, &out.tend, &out.votes, &out.second, &out.n_minimizers, &out.n_skipped}) v->assign(n, 0);
-    out.strand.assign(n, 0); out.n_hits.assign(n, 0);
+    map_result_zero(out, n);
     std::vector<ReadAnchors> per(n);
-    n_threads = std::max(1, std::min(n_threads, std::max(1, n_reads)));
-    auto work = [&](int t) {
-        std::vector<Hit> hits;
-        std::vector<uint64_t> keys;
-        for (size_t r = (size_t)t; r < n; r += (size_t)n_threads) {
-            MapVote v;
-            const int64_t L = read_off[r + 1] - read_off[r];
-            map_one_read(ix, read_seq + read_off[r], L, r, out, hits, keys, &v);
-            if (out.contig[r] >= 0) map_anchors_one_read(ap, L, hits, v, keys, per[r]);
-        }
-    };
-    if (n_threads == 1) work(0);
-    else {
-        std::vector<std::thread> th;
-        for (int t = 0; t < n_threads; ++t) th.emplace_back(work, t);
-        for (std::thread& t : th) t.join();
-    }
+    map_for_each_read(n_reads, n_threads, [&](size_t r, std::vector<Hit>& hits, std::vector<uint64_t>& keys) {
+        MapVote v;
+        const int64_t L = read_off[r + 1] - read_off[r];
+        map_one_read(ix, read_seq + read_off[r], L, r, out, hits, keys, &v);
+        if (out.contig[r] >= 0) map_anchors_one_read(ap, L, hits, v, keys, per[r]);
+    });
     anchors.anc_off.assign(n + 1, 0);
     anchors.anc_q.clear(); anchors.anc_t.clear();
     anchors.n_best.assign(n, 0); anchors.n_chain.assign(n, 0); anchors.n_supported.assign(n, 0);
@@ -262,33 +264,20 @@ int map_anchors_host(const MapIndexHost& ix, const hs_map_anchor_params& ap, con
 int map_reads_split_host(const MapIndexHost& ix, const hs_map_split_params& sp, const uint8_t* read_seq, const int64_t* read_off, int32_t n_reads, int n_threads, MapSegmentsHost& out,
                          std::string& err) {
     if (!map_split_params_valid(sp)) { err = "map reads: split parameters out of range"; return HS_EINVAL; }
-    if (n_reads < 0 || !read_off) { err = "map reads: bad arguments"; return HS_EINVAL; }
-    for (int32_t r = 0; r < n_reads; ++r)
-        if (read_off[r + 1] < read_off[r] || read_off[r + 1] - read_off[r] > 0x7fffffff) { err = "map reads: a read of more than 2^31 bases"; return HS_EINVAL; }
+    if (int rc = map_check_reads(read_off, n_reads, err)) return rc;
     const size_t n = (size_t)n_reads;
     for (std::vector<int32_t>* v : {&out.n_minimizers, &out.n_skipped, &out.read_votes, &out.read_second}) v->assign(n, 0);
     out.n_hits.assign(n, 0);
     std::vector<MapSegment> segs(n * HS_MAP_MAX_SEGMENTS);
     std::vector<int32_t> n_segs(n, 0);
-    n_threads = std::max(1, std::min(n_threads, std::max(1, n_reads)));
-    auto work = [&](int t) {
-        std::vector<Hit> hits;
-        std::vector<uint64_t> keys;
-        for (size_t r = (size_t)t; r < n; r += (size_t)n_threads) {
-            const int32_t Lr = (int32_t)(read_off[r + 1] - read_off[r]);
-            map_read_hits(ix, read_seq + read_off[r], Lr, hits, &out.n_minimizers[r], &out.n_skipped[r]);
-            out.n_hits[r] = (int64_t)hits.size();
-            MapVote v0;
-            n_segs[r] = map_split_one_read(ix, sp, Lr, hits, keys, &segs[r * HS_MAP_MAX_SEGMENTS], v0);
-            out.read_votes[r] = (int32_t)v0.best; out.read_second[r] = (int32_t)v0.second;
-        }
-    };
-    if (n_threads == 1) work(0);
-    else {
-        std::vector<std::thread> th;
-        for (int t = 0; t < n_threads; ++t) th.emplace_back(work, t);
-        for (std::thread& t : th) t.join();
-    }
+    map_for_each_read(n_reads, n_threads, [&](size_t r, std::vector<Hit>& hits, std::vector<uint64_t>& keys) {
+        const int32_t Lr = (int32_t)(read_off[r + 1] - read_off[r]);
+        map_read_hits(ix, read_seq + read_off[r], Lr, hits, &out.n_minimizers[r], &out.n_skipped[r]);
+        out.n_hits[r] = (int64_t)hits.size();
+        MapVote v0;
+        n_segs[r] = map_split_one_read(ix, sp, Lr, hits, keys, &segs[r * HS_MAP_MAX_SEGMENTS], v0);
+        out.read_votes[r] = (int32_t)v0.best; out.read_second[r] = (int32_t)v0.second;
+    });
     out.seg_off.assign(n + 1, 0);
     for (size_t r = 0; r < n; ++r) out.seg_off[r + 1] = out.seg_off[r] + n_segs[r];
     const size_t S = (size_t)out.seg_off[n];
@@ -354,6 +343,20 @@ std::string map_text(const hs_map_result* r, const char* const* read_names, cons
 
 }  // namespace hs
 
+namespace {
+// the body of the two text entries: the lengths from the offsets, the lines, a malloc'd copy for the caller (hs_free_host)
+template <class Lines> int map_text_copy(int32_t n_reads, const int64_t* h_read_off, int32_t n_contigs, const int64_t* h_contig_off, char** text, Lines lines) {
+    std::vector<int64_t> rl((size_t)n_reads), cl((size_t)n_contigs);
+    for (int32_t i = 0; i < n_reads; ++i) rl[(size_t)i] = h_read_off[i + 1] - h_read_off[i];
+    for (int32_t c = 0; c < n_contigs; ++c) cl[(size_t)c] = h_contig_off[c + 1] - h_contig_off[c];
+    const std::string s = lines(rl.data(), cl.data());
+    *text = (char*)std::malloc(s.size() + 1);
+    if (!*text) return HS_EINVAL;
+    std::memcpy(*text, s.c_str(), s.size() + 1);
+    return HS_OK;
+}
+}  // namespace
+
 extern "C" {
 
 hs_map_params hs_map_params_default(void) {
@@ -390,16 +393,10 @@ int hs_map_segments_text(const hs_map_segments* segments, const char* const* rea
     if (segments->seg_off[0] != 0 || segments->seg_off[segments->n_reads] != segments->n_segments) return HS_EINVAL;      // (the offsets say where the text reads)
     for (int32_t i = 0; i < segments->n_reads; ++i)
         if (segments->seg_off[i + 1] < segments->seg_off[i]) return HS_EINVAL;
-    std::vector<int64_t> rl((size_t)segments->n_reads), cl((size_t)n_contigs);
-    for (int32_t i = 0; i < segments->n_reads; ++i) rl[(size_t)i] = h_read_off[i + 1] - h_read_off[i];
     for (int64_t j = 0; j < segments->n_segments; ++j)
         if (segments->contig[j] < 0 || segments->contig[j] >= n_contigs) return HS_EINVAL;
-    for (int32_t c = 0; c < n_contigs; ++c) cl[(size_t)c] = h_contig_off[c + 1] - h_contig_off[c];
-    const std::string s = hs::map_segments_text(segments, read_names, rl.data(), contig_names, cl.data());
-    *text = (char*)std::malloc(s.size() + 1);
-    if (!*text) return HS_EINVAL;
-    std::memcpy(*text, s.c_str(), s.size() + 1);
-    return HS_OK;
+    return map_text_copy(segments->n_reads, h_read_off, n_contigs, h_contig_off, text,
+                         [&](const int64_t* rl, const int64_t* cl) { return hs::map_segments_text(segments, read_names, rl, contig_names, cl); });
 }
 void hs_map_result_destroy(hs_map_result* r) {
     if (!r) return;
@@ -410,17 +407,10 @@ void hs_map_result_destroy(hs_map_result* r) {
 int hs_map_text(const hs_map_result* result, const char* const* read_names, const int64_t* h_read_off, const char* const* contig_names, const int64_t* h_contig_off,
                 int32_t n_contigs, char** text) {
     if (!result || !h_read_off || !h_contig_off || !text || n_contigs < 0) return HS_EINVAL;
-    std::vector<int64_t> rl((size_t)result->n_reads), cl((size_t)n_contigs);
-    for (int32_t i = 0; i < result->n_reads; ++i) {
-        rl[(size_t)i] = h_read_off[i + 1] - h_read_off[i];
+    for (int32_t i = 0; i < result->n_reads; ++i)
         if (result->contig[i] >= n_contigs) return HS_EINVAL;
-    }
-    for (int32_t c = 0; c < n_contigs; ++c) cl[(size_t)c] = h_contig_off[c + 1] - h_contig_off[c];
-    const std::string s = hs::map_text(result, read_names, rl.data(), contig_names, cl.data());
-    *text = (char*)std::malloc(s.size() + 1);
-    if (!*text) return HS_EINVAL;
-    std::memcpy(*text, s.c_str(), s.size() + 1);
-    return HS_OK;
+    return map_text_copy(result->n_reads, h_read_off, n_contigs, h_contig_off, text,
+                         [&](const int64_t* rl, const int64_t* cl) { return hs::map_text(result, read_names, rl, contig_names, cl); });
 }
 
 }  // extern "C"

@@ -12,29 +12,7 @@
 // stdout of a job: a line "R <read> " + map_selftest's eleven fields and a line "A <read> n_best n_chain n_supported n_anchors" per read, a line
 // "P <read> q t" per anchor. Of hits: "A 0 n n_chain n_supported n_anchors", "C <index into the ordered hits> qa t" per chain member, "P 0 q t" per
 // anchor. Exit 4: the parameters are refused.
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "../../hairsplitter_amd/csrc/hs_map_host.h"
-
-static bool read_seqs(std::ifstream& f, std::vector<uint8_t>& seq, std::vector<int64_t>& off) {
-    long n = -1;
-    std::string line;
-    if (!(f >> n) || n < 0) return false;
-    std::getline(f, line);
-    off.assign(1, 0);
-    for (long i = 0; i < n; ++i) {
-        if (!std::getline(f, line) || line.empty() || line[0] != '>') return false;
-        for (size_t c = 1; c < line.size(); ++c) {
-            if (line[c] < '0' || line[c] > '3') return false;
-            seq.push_back((uint8_t)(line[c] - '0'));
-        }
-        off.push_back((int64_t)seq.size());
-    }
-    return true;
-}
+#include "map_job_io.h"
 
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: map_anchor_selftest <job.txt>\n"); return 2; }
@@ -62,7 +40,7 @@ int main(int argc, char** argv) {
     }
     hs_map_params p;
     int threads = 1;
-    if (kind != "JOB" || !(f >> p.k >> p.w >> p.max_occ >> p.band_log2 >> p.min_votes >> p.extend >> p.bucket_bits >> threads) || !(f >> ap.spacing)) {
+    if (kind != "JOB" || !read_map_params(f, p, threads) || !(f >> ap.spacing)) {
         std::fprintf(stderr, "map_anchor_selftest: bad parameter lines\n");
         return 2;
     }
@@ -78,8 +56,7 @@ int main(int argc, char** argv) {
     if (int rc = hs::map_anchors_host(ix, ap, rseq.data(), roff.data(), R, threads, out, an, err)) { std::fprintf(stderr, "map_anchor_selftest: %s\n", err.c_str()); return rc == HS_EINVAL ? 4 : 3; }
     for (int32_t r = 0; r < R; ++r) {
         const size_t i = (size_t)r;
-        std::printf("R %d %d %d %d %d %d %d %d %d %d %lld %d\n", r, out.contig[i], (int)out.strand[i], out.qstart[i], out.qend[i], out.tstart[i], out.tend[i], out.votes[i], out.second[i],
-                    out.n_minimizers[i], (long long)out.n_hits[i], out.n_skipped[i]);
+        print_read_line(out, r);
         std::printf("A %d %d %d %d %lld\n", r, an.n_best[i], an.n_chain[i], an.n_supported[i], (long long)(an.anc_off[i + 1] - an.anc_off[i]));
         for (int64_t j = an.anc_off[i]; j < an.anc_off[i + 1]; ++j) std::printf("P %d %d %d\n", r, an.anc_q[(size_t)j], an.anc_t[(size_t)j]);
     }

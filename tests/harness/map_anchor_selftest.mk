@@ -4,10 +4,10 @@
 CXX ?= g++
 P := ../../hairsplitter_amd/csrc
 all: _build/map_anchor_selftest
-_build/map_anchor_selftest: map_anchor_selftest.cpp $(P)/hs_map_host.cpp $(P)/hs_map_host.h $(P)/hs_rules.h ../../include/hairsplitter_hip.h
+_build/map_anchor_selftest: map_anchor_selftest.cpp map_job_io.h $(P)/hs_map_host.cpp $(P)/hs_map_host.h $(P)/hs_rules.h ../../include/hairsplitter_hip.h
 	@mkdir -p _build
 	$(CXX) -std=c++17 -O2 -Wall -o $@ map_anchor_selftest.cpp $(P)/hs_map_host.cpp -lpthread
 asan: _build/map_anchor_selftest_asan
-_build/map_anchor_selftest_asan: map_anchor_selftest.cpp $(P)/hs_map_host.cpp $(P)/hs_map_host.h $(P)/hs_rules.h ../../include/hairsplitter_hip.h
+_build/map_anchor_selftest_asan: map_anchor_selftest.cpp map_job_io.h $(P)/hs_map_host.cpp $(P)/hs_map_host.h $(P)/hs_rules.h ../../include/hairsplitter_hip.h
 	@mkdir -p _build
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Wall -o $@ map_anchor_selftest.cpp $(P)/hs_map_host.cpp -lpthread

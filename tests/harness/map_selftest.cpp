@@ -7,36 +7,14 @@
 // stdout: "INDEX <bucket_bits> <n_entries>", a line "E <bucket> <hash> <contig> <t> <strand bit>" per entry (bucket, hash, contig, t ascending),
 // a line "M <read> <q> <strand bit> <hash>" per read minimizer, a line "R <read> contig strand qstart qend tstart tend votes second n_minimizers
 // n_hits n_skipped" per read, then the PAF lines of hs_map_text. Exit 4: the parameters are refused.
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "../../hairsplitter_amd/csrc/hs_map_host.h"
-
-static bool read_seqs(std::ifstream& f, std::vector<uint8_t>& seq, std::vector<int64_t>& off) {
-    long n = -1;
-    std::string line;
-    if (!(f >> n) || n < 0) return false;
-    std::getline(f, line);
-    off.assign(1, 0);
-    for (long i = 0; i < n; ++i) {
-        if (!std::getline(f, line) || line.empty() || line[0] != '>') return false;
-        for (size_t c = 1; c < line.size(); ++c) {
-            if (line[c] < '0' || line[c] > '3') return false;
-            seq.push_back((uint8_t)(line[c] - '0'));
-        }
-        off.push_back((int64_t)seq.size());
-    }
-    return true;
-}
+#include "map_job_io.h"
 
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: map_selftest <job.txt>\n"); return 2; }
     std::ifstream f(argv[1]);
     hs_map_params p;
     int threads = 1;
-    if (!(f >> p.k >> p.w >> p.max_occ >> p.band_log2 >> p.min_votes >> p.extend >> p.bucket_bits >> threads)) { std::fprintf(stderr, "map_selftest: bad parameter line\n"); return 2; }
+    if (!read_map_params(f, p, threads)) { std::fprintf(stderr, "map_selftest: bad parameter line\n"); return 2; }
     std::vector<uint8_t> cseq, rseq;
     std::vector<int64_t> coff, roff;
     if (!read_seqs(f, cseq, coff) || !read_seqs(f, rseq, roff)) { std::fprintf(stderr, "map_selftest: bad sequences\n"); return 2; }
@@ -53,9 +31,7 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < mz.h.size(); ++i) std::printf("M %d %u %u %u\n", mz.seq[i], mz.ps[i] >> 1, mz.ps[i] & 1u, mz.h[i]);
     hs::MapResultHost out;
     if (hs::map_reads_host(ix, rseq.data(), roff.data(), R, threads, out, err)) { std::fprintf(stderr, "map_selftest: %s\n", err.c_str()); return 3; }
-    for (int32_t r = 0; r < R; ++r)
-        std::printf("R %d %d %d %d %d %d %d %d %d %d %lld %d\n", r, out.contig[(size_t)r], (int)out.strand[(size_t)r], out.qstart[(size_t)r], out.qend[(size_t)r], out.tstart[(size_t)r],
-                    out.tend[(size_t)r], out.votes[(size_t)r], out.second[(size_t)r], out.n_minimizers[(size_t)r], (long long)out.n_hits[(size_t)r], out.n_skipped[(size_t)r]);
+    for (int32_t r = 0; r < R; ++r) print_read_line(out, r);
     hs_map_result res{};
     res.n_reads = R;
     res.contig = out.contig.data(); res.strand = out.strand.data(); res.qstart = out.qstart.data(); res.qend = out.qend.data(); res.tstart = out.tstart.data();

@@ -7,29 +7,7 @@
 //   n_contigs, then a line ">" + codes 0..3 per contig; n_reads, then a line per read
 // stdout: a line "R <read> n_minimizers n_hits n_skipped read_votes read_second n_segments" per read, a line "S <segment> read contig strand qstart
 // qend tstart tend votes second round" per segment, then the PAF lines of hs_map_segments_text. Exit 4: the parameters are refused.
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "../../hairsplitter_amd/csrc/hs_map_host.h"
-
-static bool read_seqs(std::ifstream& f, std::vector<uint8_t>& seq, std::vector<int64_t>& off) {
-    long n = -1;
-    std::string line;
-    if (!(f >> n) || n < 0) return false;
-    std::getline(f, line);
-    off.assign(1, 0);
-    for (long i = 0; i < n; ++i) {
-        if (!std::getline(f, line) || line.empty() || line[0] != '>') return false;
-        for (size_t c = 1; c < line.size(); ++c) {
-            if (line[c] < '0' || line[c] > '3') return false;
-            seq.push_back((uint8_t)(line[c] - '0'));
-        }
-        off.push_back((int64_t)seq.size());
-    }
-    return true;
-}
+#include "map_job_io.h"
 
 int main(int argc, char** argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: map_split_selftest <job.txt>\n"); return 2; }
@@ -37,7 +15,7 @@ int main(int argc, char** argv) {
     hs_map_params p;
     hs_map_split_params sp;
     int threads = 1;
-    if (!(f >> p.k >> p.w >> p.max_occ >> p.band_log2 >> p.min_votes >> p.extend >> p.bucket_bits >> threads) || !(f >> sp.max_segments >> sp.min_votes >> sp.min_span >> sp.max_gap)) {
+    if (!read_map_params(f, p, threads) || !(f >> sp.max_segments >> sp.min_votes >> sp.min_span >> sp.max_gap)) {
         std::fprintf(stderr, "map_split_selftest: bad parameter lines\n");
         return 2;
     }

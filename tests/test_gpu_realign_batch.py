@@ -8,6 +8,7 @@ import dataclasses
 import os
 import re
 import subprocess
+import sys
 import tempfile
 
 import numpy as np
@@ -225,3 +226,85 @@ def test_bad_input_is_refused(job):
     rc = lib.hs_realign_intervals(p8(flat.contig_seq), p64(flat.contig_off), C.c_int32(flat.n_contigs), p8(flat.read_seq), p64(flat.read_off), C.c_int32(flat.n_reads),
                                   p32(one), p32(one), p8(s), p32(one), p32(one), p32(one), p32(one), C.c_int32(-1), C.c_int32(PAD), C.byref(out), None)
     assert rc == HS_EINVAL
+
+
+# ---- a job of more than one round: the same job in two rounds (a fresh process with the smallest chunk) and in one ----
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TWO_ROUND_KEYS = ("contig_rec_off", "rec_interval", "rec_read", "rec_pos", "rec_dist", "rec_strand", "rec_cig_off", "cigar", "dropped", "n_pieces", "n_rounds")
+N_TWO_ROUND = 9000
+TWO_ROUND_CHILD = """
+import sys
+import numpy as np
+from hairsplitter_amd import api
+j = np.load(sys.argv[1])
+seqs = {k: j[k] for k in ("contig_seq", "contig_off", "read_seq", "read_off")}
+out = {}
+for case, rec in (("plain", api.realign_intervals(seqs, j["intervals"], pad=int(j["pad"]), want_batch=False)[0]),
+                  ("anchored", api.realign_intervals_anchored(seqs, j["intervals"], j["anc_off"], j["anc_q"], j["anc_t"], pad=int(j["pad"]), want_batch=False)[0])):
+    for k in sys.argv[3:]:
+        out[case + "_" + k] = np.asarray(rec[k])
+np.savez(sys.argv[2], **out)
+"""
+
+
+def _two_round_job():
+    """one contig of 3 000 bases; 50 reads of 1 000 bases cut from it with about 1 % substitutions (no indels), every second one reverse-complemented;
+    9 000 intervals (read i % 50, whole read, its true span) whose windows (pad 100) all have their 1 200 bases; three anchors per interval on the true
+    diagonal, at 250, 500 and 750 of the read as it aligns and of the span"""
+    rng = np.random.default_rng(97)
+    contig = rng.integers(0, 4, size=3000).astype(np.uint8)
+    reads, rows = [], []
+    for r in range(50):
+        start = int(rng.integers(PAD, 3000 - 1000 - PAD + 1))
+        seg = contig[start:start + 1000].copy()
+        sub = rng.random(1000) < 0.01
+        seg[sub] = (seg[sub] + rng.integers(1, 4, size=int(sub.sum()))) % 4
+        plus = r % 2 == 0
+        reads.append(seg if plus else (3 - seg[::-1]).astype(np.uint8))
+        rows.append((r, 0, 1 if plus else 0, 0, 1000, start, start + 1000))
+    intervals = np.array([rows[i % 50] for i in range(N_TWO_ROUND)], np.int64)
+    at = np.array([250, 500, 750], np.int64)
+    return {"contig_seq": contig, "contig_off": np.array([0, 3000], np.int64), "read_seq": np.concatenate(reads), "read_off": np.arange(51, dtype=np.int64) * 1000,
+            "intervals": intervals, "pad": np.int64(PAD), "anc_off": np.arange(N_TWO_ROUND + 1, dtype=np.int64) * 3, "anc_q": np.tile(at, N_TWO_ROUND).astype(np.int32),
+            "anc_t": (intervals[:, 5:6] + at[None, :]).reshape(-1).astype(np.int32)}
+
+
+@pytest.fixture(scope="module")
+def two_rounds(built, tmp_path_factory):
+    """the job's records from a child process whose rounds hold 16 MB of bases (the floor of HS_REALIGN_CHUNK_MB, read once per process), and the job"""
+    job = _two_round_job()
+    # the round bound of hs_capi_realign.inc on this job: an interval costs 1 000 + 1 200 bases and a round closes once it holds the chunk
+    cost = (job["intervals"][:, 4] - job["intervals"][:, 3]) + (np.minimum(3000, job["intervals"][:, 6] + PAD) - np.maximum(0, job["intervals"][:, 5] - PAD))
+    assert (cost == 2200).all()
+    first = int(np.searchsorted(np.cumsum(cost) - cost, 16 << 20))
+    assert (first, N_TWO_ROUND - first) == (7627, 1373)
+    td = tmp_path_factory.mktemp("two_rounds")
+    src, dst = str(td / "job.npz"), str(td / "records.npz")
+    np.savez(src, **job)
+    r = subprocess.run([sys.executable, "-c", TWO_ROUND_CHILD, src, dst, *TWO_ROUND_KEYS], cwd=ROOT, env=dict(os.environ, HS_REALIGN_CHUNK_MB="16"),
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    return job, np.load(dst)
+
+
+def _same_in_one_round(rec, child, case):
+    assert int(child[case + "_n_rounds"]) == 2 and rec["n_rounds"] == 1
+    assert rec["n_rec"] + rec["n_dropped"] == N_TWO_ROUND
+    for k in TWO_ROUND_KEYS[:-1]:
+        assert np.array_equal(np.asarray(rec[k]), child[case + "_" + k]), k
+
+
+def test_two_rounds_equal_one_round(two_rounds):
+    from hairsplitter_amd import api
+    job, child = two_rounds
+    rec, _ = api.realign_intervals(job, job["intervals"], pad=PAD, want_batch=False)
+    _same_in_one_round(rec, child, "plain")
+    assert rec["n_pieces"] == N_TWO_ROUND
+
+
+def test_two_rounds_equal_one_round_anchored(two_rounds):
+    from hairsplitter_amd import api
+    job, child = two_rounds
+    rec, _ = api.realign_intervals_anchored(job, job["intervals"], job["anc_off"], job["anc_q"], job["anc_t"], pad=PAD, want_batch=False)
+    _same_in_one_round(rec, child, "anchored")
+    assert rec["n_pieces"] == 4 * N_TWO_ROUND
