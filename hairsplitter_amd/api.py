@@ -28,6 +28,7 @@ SYMBOLS = [
     "hs_cv_result_destroy", "hs_cv_select", "hs_cv_run_range", "hs_cv_selection_destroy", "hs_sr_run", "hs_sr_run_cv", "hs_sr_run_cv_range", "hs_pipeline_create", "hs_pipeline_select", "hs_pipeline_run", "hs_pipeline_destroy", "hs_pipeline_thread_devices", "hs_cv_batch_device", "hs_sr_result_destroy", "hs_sr_window_size", "hs_call_variants_main", "hs_call_variants_epilogue",
     "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_edlib_align", "hs_edlib_align_bytes", "hs_alignment_to_cigar", "hs_reattach_ends", "hs_trim_polished", "hs_reattach_ends_bytes", "hs_trim_polished_bytes", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
     "hs_polish_inputs", "hs_polish_inputs_from_files", "hs_polish_result_destroy", "hs_polish_inputs_main",
+    "hs_consensus_default_params", "hs_polish_consensus", "hs_polish_consensus_arrays", "hs_polish_consensus_host", "hs_consensus_result_destroy",
     "hs_moves_to_cigar", "hs_realign_intervals", "hs_realign_records_destroy", "hs_cv_batch_create_paf", "hs_cv_batch_create_sam",
     "hs_allele_table_destroy", "hs_alleles_text", "hs_alleles_lds_capacity", "hs_group_alleles_layout", "hs_group_alleles", "hs_haplotype_alleles", "hs_pipeline_alleles",
     "hs_recruit_params_default", "hs_recruit_table_destroy", "hs_recruit_reads", "hs_group_recruit_layout", "hs_group_recruit", "hs_recruit_apply", "hs_recruit_text",
@@ -1789,6 +1790,85 @@ def polish_bundle_files(res: Dict, i: int, dir: str, id: str = "0") -> Dict:
             fs.write("read%d\t0\tseq\t%d\t60\t%s\t*\t0\t0\t%s\t*\tAS:i:0\tXS:i:0\n" % (
                 p - p0, int(res["piece_sam_pos"][p]), polish_cigar_string(res["cigar"][int(res["cig_off"][p]):int(res["cig_off"][p + 1])]), seq))
     return paths
+
+
+# ---- the consensus of every bundle: a vote per backbone column and per insertion slot (the rule is ours: csrc/hs_consensus_host.h) ----
+_CONSENSUS_I32 = ("trim_start", "trim_end", "n_sub", "n_del", "n_ins_bases", "n_low", "n_skipped")
+
+
+class ConsensusParams(C.Structure):
+    _fields_ = [("min_cov", C.c_int32), ("max_ins", C.c_int32)]
+
+
+class ConsensusResult(C.Structure):
+    _fields_ = ([("n_bundles", C.c_int64), ("cons_off", C.POINTER(C.c_int64)), ("cons", C.POINTER(C.c_uint8))] + [(k, C.POINTER(C.c_int32)) for k in _CONSENSUS_I32] +
+                [("t_rows_ms", C.c_double), ("t_columns_ms", C.c_double), ("t_ins_ms", C.c_double), ("t_emit_ms", C.c_double),
+                 ("n_rounds", C.c_int64), ("n_ins_records", C.c_int64), ("n_ins_slots", C.c_int64)])
+
+
+def consensus_params(**kw) -> ConsensusParams:
+    """hs_consensus_default_params (min_cov 3, max_ins 32: PLACEHOLDERS, not tuned) with the given fields replaced"""
+    lib = load()
+    lib.hs_consensus_default_params.restype = ConsensusParams
+    lib.hs_consensus_default_params.argtypes = []
+    p = lib.hs_consensus_default_params()
+    for k, v in kw.items():
+        if k not in ("min_cov", "max_ins"):
+            raise HsError("consensus_params: no field " + k)
+        setattr(p, k, int(v))
+    return p
+
+
+def polish_consensus(res: Dict, params: Optional[ConsensusParams] = None, form: str = "device") -> Dict:
+    """The consensus of every bundle of `res`: the dict polish_inputs returns, or one of hand-built arrays with the keys backbone_off, backbone,
+    bundle_overhang_left, bundle_overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar. form "device": the kernels
+    (hs_polish_consensus_arrays); "host": the host half of the same rule (hs_polish_consensus_host, no device). Returns numpy arrays cons_off, cons
+    (text), trim_start, trim_end, n_sub, n_del, n_ins_bases, n_low, n_skipped per bundle, and "stats"."""
+    if form not in ("device", "host"):
+        raise HsError("polish_consensus: form is 'device' or 'host'")
+    lib = load()
+    a64 = [_np(res[k], np.int64) for k in ("backbone_off", "piece_off", "base_off", "cig_off")]
+    a32 = [_np(res[k], np.int32) for k in ("bundle_overhang_left", "bundle_overhang_right", "piece_sam_pos", "piece_flags")]
+    backbone, bases, cigar = _np(res["backbone"], np.uint8), _np(res["bases"], np.uint8), _np(res["cigar"], np.uint32)
+    B = len(a64[0]) - 1
+    if B < 0 or len(a64[1]) != B + 1 or len(a32[0]) != B or len(a32[1]) != B:
+        raise HsError("polish_consensus: the bundle arrays do not agree")
+    P = int(a64[1][-1]) if B >= 0 and len(a64[1]) else 0
+    if len(a64[2]) != P + 1 or len(a64[3]) != P + 1 or len(a32[2]) != P or len(a32[3]) != P:
+        raise HsError("polish_consensus: the piece arrays do not agree")
+    if len(backbone) < int(a64[0][-1]) or len(bases) < int(a64[2][-1]) or len(cigar) < int(a64[3][-1]):
+        raise HsError("polish_consensus: the offsets run beyond the arrays")
+
+    def ptr(a):
+        return a.ctypes.data_as(C.c_void_p)
+    fn = lib.hs_polish_consensus_arrays if form == "device" else lib.hs_polish_consensus_host
+    fn.argtypes = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams), C.POINTER(C.POINTER(ConsensusResult))]
+    lib.hs_consensus_result_destroy.argtypes = [C.c_void_p]
+    lib.hs_consensus_result_destroy.restype = None
+    out_p = C.POINTER(ConsensusResult)()
+    _check(fn(C.c_int64(B), ptr(a64[0]), ptr(backbone), ptr(a32[0]), ptr(a32[1]), ptr(a64[1]), ptr(a32[2]), ptr(a32[3]), ptr(a64[2]), ptr(bases), ptr(a64[3]), ptr(cigar),
+              None if params is None else C.byref(params), C.byref(out_p)))
+    try:
+        r = out_p.contents
+
+        def arr(p, n, dtype):
+            return np.ctypeslib.as_array(p, (n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
+        out = {"n_bundles": int(r.n_bundles), "cons_off": arr(r.cons_off, B + 1, np.int64)}
+        out["cons"] = arr(r.cons, int(out["cons_off"][-1]), np.uint8)
+        for k in _CONSENSUS_I32:
+            out[k] = arr(getattr(r, k), B, np.int32)
+        out["stats"] = {"rows_ms": r.t_rows_ms, "columns_ms": r.t_columns_ms, "ins_ms": r.t_ins_ms, "emit_ms": r.t_emit_ms, "n_rounds": int(r.n_rounds),
+                        "n_ins_records": int(r.n_ins_records), "n_ins_slots": int(r.n_ins_slots)}
+    finally:
+        lib.hs_consensus_result_destroy(out_p)
+    return out
+
+
+def consensus_text(cons: Dict, i: int, trimmed: bool = False) -> str:
+    """The consensus of bundle i of a polish_consensus result; trimmed: without the overhangs, cons[trim_start, trim_end)"""
+    o = int(cons["cons_off"][i])
+    a, b = (int(cons["trim_start"][i]), int(cons["trim_end"][i])) if trimmed else (0, int(cons["cons_off"][i + 1]) - o)
+    return cons["cons"][o + a:o + max(a, b)].tobytes().decode()
 
 
 def edlib_hw_align(pairs, path=True):

@@ -336,6 +336,11 @@ int hs_polish_inputs_from_files(const char* gfa, const char* reads, const char* 
         hs_polish_result* r = nullptr;
         if (int rc = polish_inputs_core(b, 0, n_contigs, ivs, has, polish_everything != 0, in.rec_read, &r)) return rc;
         std::unique_ptr<hs_polish_result, void (*)(hs_polish_result*)> rguard(r, hs_polish_result_destroy);
+        // HS_CONSENSUS=1: every bundle's consensus (hs_polish_consensus, the default parameters) behind its text
+        const char* want_cons = std::getenv("HS_CONSENSUS");
+        hs_consensus_result* cons = nullptr;
+        if (want_cons && want_cons[0] == '1') { if (int rc = hs_polish_consensus(r, nullptr, &cons)) return rc; }
+        std::unique_ptr<hs_consensus_result, void (*)(hs_consensus_result*)> cguard(cons, hs_consensus_result_destroy);
         std::FILE* f = std::fopen(out_path, "wb");
         if (!f) { set_error(std::string("cannot write ") + out_path); return HS_EIO; }
         std::string text;
@@ -355,6 +360,11 @@ int hs_polish_inputs_from_files(const char* gfa, const char* reads, const char* 
                 for (int64_t q = r->cig_off[p]; q < r->cig_off[p + 1]; ++q) { text += std::to_string(r->cigar[q] >> 4); text += "MIDNSHP=X???????"[r->cigar[q] & 15u]; }
                 text += '\n';
                 text.append((const char*)r->bases + r->base_off[p], (size_t)(r->base_off[p + 1] - r->base_off[p]));
+                text += '\n';
+            }
+            if (cons) {
+                text += ">consensus " + std::to_string(cons->trim_start[k]) + " " + std::to_string(cons->trim_end[k]) + "\n";
+                text.append((const char*)cons->cons + cons->cons_off[k], (size_t)(cons->cons_off[k + 1] - cons->cons_off[k]));
                 text += '\n';
             }
             ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();

@@ -900,12 +900,56 @@ int hs_polish_inputs(hs_cv_batch* b, int32_t c0, int32_t c1, const int64_t* win_
 /* the same from the four files HS_create_new_contigs reads (main, :1586-1595), written as text: per bundle a line
  * "BUNDLE <contig> <interval start> <interval end> <group> <leftToPolish> <rightToPolish> <overhangLeft> <overhangRight> <reads>"
  * (tab-separated), then ">seq" and toPolish, then per non-empty piece ">read<k> <startPosition> <CIGAR>" and the piece
- * (tools.cpp:351-361). */
+ * (tools.cpp:351-361).  With HS_CONSENSUS=1 in the environment every bundle ends in ">consensus <trim_start> <trim_end>" and its
+ * consensus (hs_polish_consensus below, the default parameters). */
 int hs_polish_inputs_from_files(const char* gfa, const char* reads, const char* sam, const char* gro, int32_t polish_everything,
                                 const char* out_path, int32_t n_threads);
 void hs_polish_result_destroy(hs_polish_result* r);
 /* argv = <gfa> <reads> <sam> <gro> <polish_everything:0|1> <out> [threads] */
 int hs_polish_inputs_main(int argc, char** argv);
+
+/* ------------------------------------------------------------------------------------------------
+ * The consensus of every bundle (device work): a vote per backbone column and per insertion slot over the bundle's pieces, what
+ * the reference gets from minimap2 + racon (tools.cpp:317-...).  The rule is OURS, not racon's; it is stated once, in
+ * csrc/hs_consensus_host.h, and the device is held to its host half by integer equality.
+ *   walk of a piece: t = piece_sam_pos - 1, q = 0; M votes P[q] at column t, D votes deletion at t, I consumes read bases, any other
+ *     op does nothing; votes at t >= L are dropped.  Skipped (n_skipped): an empty piece, HS_POLISH_START_BEYOND_SEQ, sum(M + I) !=
+ *     its bases, piece_sam_pos - 1 >= L.
+ *   column: fewer than min_cov covering pieces keep the byte B[t] (n_low); else the largest of A C G T deletion, B[t] on a tie it
+ *     takes part in, else the first.  A winning deletion emits nothing (n_del), another base than B[t] is a substitution (n_sub).
+ *   slot t (between t - 1 and t): span = pieces covering both, nins = those with an insertion there; wins iff span >= min_cov and
+ *     2 nins > span.  Length = the most frequent (capped at max_ins) among the voters, the smaller on a tie; base j = the most
+ *     frequent at offset j over voters longer than j, A < C < G < T on a tie (n_ins_bases).
+ *   trim_start, trim_end: where the backbone columns min(overhang_left, L) and L - min(overhang_right, L) begin in the consensus
+ *     (a column begins in front of its slot's insertion): cons[trim_start, trim_end) is the bundle without its overhangs, exactly --
+ *     no alignment as in hs_trim_polished, and nothing to reattach.
+ * min_cov 3 and max_ins 32 (allowed 1..64) are PLACEHOLDERS of the interface: nobody has tuned them.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hs_consensus_params { int32_t min_cov, max_ins; } hs_consensus_params;
+hs_consensus_params hs_consensus_default_params(void);
+typedef struct hs_consensus_result {
+    int64_t n_bundles;
+    int64_t* cons_off;          /* [n_bundles + 1] into cons: the consensus of every bundle, text (a bundle without pieces: its backbone) */
+    uint8_t* cons;
+    int32_t *trim_start, *trim_end, *n_sub, *n_del, *n_ins_bases, *n_low /* columns kept for low coverage */, *n_skipped /* pieces */;
+    /* accounting (HIP events around the launches; 0 on the host half): rows, columns, insertion tables, scan + emit */
+    double t_rows_ms, t_columns_ms, t_ins_ms, t_emit_ms;
+    int64_t n_rounds /* of HS_CONSENSUS_CHUNK_MB */, n_ins_records /* insertions that voted */, n_ins_slots /* slots that won */;
+} hs_consensus_result;
+/* The arrays are those of a hs_polish_result, in host memory; they go up round by round, whole bundles within HS_CONSENSUS_CHUNK_MB
+ * (default 1024) megabytes of row bytes (one per piece and covered column).  A single bundle above that is refused and named. */
+int hs_polish_consensus(const hs_polish_result* in, const hs_consensus_params* params /* NULL: the defaults */, hs_consensus_result** out);
+int hs_polish_consensus_arrays(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left,
+                               const int32_t* overhang_right, const int64_t* piece_off, const int32_t* piece_sam_pos, const int32_t* piece_flags,
+                               const int64_t* base_off, const uint8_t* bases, const int64_t* cig_off, const uint32_t* cigar,
+                               const hs_consensus_params* params, hs_consensus_result** out);
+/* the host half of the rule behind the same signature (no device needed): what the device is tested against.  The bundles are
+ * strided over the host's threads, or over HS_CONSENSUS_HOST_THREADS of them. */
+int hs_polish_consensus_host(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left,
+                             const int32_t* overhang_right, const int64_t* piece_off, const int32_t* piece_sam_pos, const int32_t* piece_flags,
+                             const int64_t* base_off, const uint8_t* bases, const int64_t* cig_off, const uint32_t* cigar,
+                             const hs_consensus_params* params, hs_consensus_result** out);
+void hs_consensus_result_destroy(hs_consensus_result* r);
 
 /* ------------------------------------------------------------------------------------------------
  * Upstream feeders of stage 3 that are plain text transforms (host code): the 300 kb cutter the orchestrator runs before the

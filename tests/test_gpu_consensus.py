@@ -1,0 +1,169 @@
+"""The bundle consensus on the device (hs_kernels_consensus.hip, hs_capi_consensus.inc): the device equals the host half of the rule
+(hs_polish_consensus_host) on every case of tests/consensus_cases.py and every field by integer equality, twice; the wait count; one job in two
+rounds and in one; the over-budget bundle; polish_inputs -> polish_consensus on a resident batch; bin/hs_polish_inputs with HS_CONSENSUS=1."""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+import consensus_cases as cc
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KEYS = ("cons_off", "cons") + cc.FIELDS
+COUNTS = ("n_ins_records", "n_ins_slots")
+
+
+def _same(a, b, what=""):
+    for k in KEYS:
+        assert np.array_equal(a[k], b[k]), (what, k)
+    for k in COUNTS:
+        assert a["stats"][k] == b["stats"][k], (what, k)
+
+
+@pytest.mark.parametrize("group", sorted(cc.CASES))
+def test_device_equals_the_host_half(built, group):
+    from hairsplitter_amd import api
+    bundles = cc.CASES[group]()
+    job = cc.pack(bundles)
+    host = api.polish_consensus(job, form="host")
+    cc.check_claims(bundles, cc.result_as_rule(host))
+    for run in (0, 1):      # (twice: nothing may hinge on the order in which the records' additions arrive)
+        w0 = api.host_waits()
+        dev = api.polish_consensus(job)
+        assert api.host_waits() - w0 <= 3 * dev["stats"]["n_rounds"] and dev["stats"]["n_rounds"] == 1
+        _same(dev, host, (group, run))
+
+
+def test_other_parameters(built):
+    from hairsplitter_amd import api
+    job = cc.pack(cc.slots_cases() + cc.edges_cases())
+    for min_cov, max_ins in ((1, 2), (4, 64), (2, 1)):
+        prm = api.consensus_params(min_cov=min_cov, max_ins=max_ins)
+        _same(api.polish_consensus(job, prm), api.polish_consensus(job, prm, form="host"), (min_cov, max_ins))
+
+
+def test_refused_input(built):
+    from hairsplitter_amd import api
+    job = cc.pack(cc.trim_cases())
+    for kw in ({"min_cov": 0}, {"max_ins": 0}, {"max_ins": 65}):
+        for form in ("device", "host"):
+            with pytest.raises(api.HsError, match="out of range"):
+                api.polish_consensus(job, api.consensus_params(**kw), form=form)
+    bad = dict(job, piece_sam_pos=np.zeros_like(job["piece_sam_pos"]))
+    with pytest.raises(api.HsError, match="start position"):
+        api.polish_consensus(bad)
+
+
+def two_round_job():
+    """two bundles of 7 000 columns under 100 pieces each: 700 000 row bytes a bundle, so that a budget of 1 MB holds one"""
+    out = []
+    for k in (0, 1):
+        bb = cc.seq(7000, 70 + k)
+        text = bb[:3500] + "GT" + bb[3500:5000] + bb[5002:]
+        out.append(cc.Bundle("half %d" % k, bb, [(1, "3500M2I1500M2D1998M", text)] * 60 + [(1, "7000M", bb)] * 40, ovl=150, ovr=150))
+    return out
+
+
+CHILD = """
+import sys
+import numpy as np
+sys.path.insert(0, "tests")
+import consensus_cases as cc
+import test_gpu_consensus as tg
+from hairsplitter_amd import api
+job = cc.pack(tg.two_round_job())
+res = api.polish_consensus(job)
+out = {k: np.asarray(res[k]) for k in tg.KEYS}
+out.update({k: np.int64(res["stats"][k]) for k in tg.COUNTS + ("n_rounds",)})
+big = cc.pack([cc.Bundle("big", cc.seq(7000, 1), [(1, "7000M", cc.seq(7000, 1))] * 160)])
+try:
+    api.polish_consensus(big)
+    out["refused"] = np.array("")
+except api.HsError as e:
+    out["refused"] = np.array(str(e))
+np.savez(sys.argv[1], **out)
+"""
+
+
+def test_two_rounds_equal_one_round_and_the_bundle_above_the_budget_is_refused(built, tmp_path):
+    from hairsplitter_amd import api
+    dst = str(tmp_path / "child.npz")
+    r = subprocess.run([sys.executable, "-c", CHILD, dst], cwd=ROOT, env=dict(os.environ, HS_CONSENSUS_CHUNK_MB="1"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    child = np.load(dst)
+    job = cc.pack(two_round_job())
+    w0 = api.host_waits()
+    one = api.polish_consensus(job)
+    assert api.host_waits() - w0 <= 3
+    assert int(child["n_rounds"]) == 2 and one["stats"]["n_rounds"] == 1
+    for k in KEYS:
+        assert np.array_equal(one[k], child[k]), k
+    for k in COUNTS:
+        assert one["stats"][k] == int(child[k]), k
+    assert one["n_ins_bases"].tolist() == [2, 2] and one["n_del"].tolist() == [2, 2]
+    _same(one, api.polish_consensus(job, form="host"))
+    msg = str(child["refused"])
+    assert "bundle 0" in msg and "HS_CONSENSUS_CHUNK_MB" in msg, msg
+
+
+def test_polish_inputs_to_consensus_on_a_resident_batch(built):
+    """the noisy diploid contig of tests/test_cpu_consensus.py as a resident batch: its reads labelled by their haplotype in five windows"""
+    from hairsplitter_amd import api, synth
+    c = synth.make_contig(11, 0, 10_000, 2, 0.01, 60, "ont")
+    batch = api.CvBatch(api.FlatBatch([c]))
+    n = len(c.alns)
+    labels = np.array([c.haplotype_of_read[a.read] for a in c.alns], np.int32)
+    sr = {"win_off": np.array([0, 5], np.int64), "win_start": np.arange(5, dtype=np.int32) * 2000, "win_end": np.arange(5, dtype=np.int32) * 2000 + 1999,
+          "label_off": np.arange(6, dtype=np.int64) * n, "labels": np.tile(labels, 5)}
+    res = api.polish_inputs(batch, sr, contig_has_snps=[1])
+    assert res["n_bundles"] >= 2 and res["n_pieces"] + len(res["dropped"]) == n      # (every read has a label: it is a piece of its group's bundle, or dropped)
+    dev, host = api.polish_consensus(res), api.polish_consensus(res, form="host")
+    _same(dev, host)
+    assert dev["stats"]["n_ins_records"] > 0 and int(dev["n_sub"].sum()) > 0
+    batch.close()
+
+
+def _parse_tool(path):
+    """bin/hs_polish_inputs' text as bundles (the pieces it writes: the non-empty ones) and its consensus lines"""
+    bundles, cons = [], []
+    lines = open(path).read().split("\n")
+    i = 0
+    while i < len(lines):
+        if lines[i].startswith("BUNDLE\t"):
+            head = lines[i].split("\t")
+            bundles.append(cc.Bundle(lines[i], lines[i + 2], [], int(head[7]), int(head[8])))
+            i += 3
+        elif lines[i].startswith(">read"):
+            _, sam, cigar = lines[i].split(" ")
+            bundles[-1].pieces.append((int(sam), cc.words(cigar), lines[i + 1], 0))
+            i += 2
+        elif lines[i].startswith(">consensus "):
+            _, a, b = lines[i].split(" ")
+            cons.append((int(a), int(b), lines[i + 1]))
+            i += 2
+        else:
+            i += 1
+    return bundles, cons
+
+
+def test_tool_with_consensus_equals_the_api(built):
+    import polish_goldens as pg
+    from hairsplitter_amd import api
+    with tempfile.TemporaryDirectory() as td:
+        gfa, reads, sam, gro = pg.prepare("multi", td)
+        out = os.path.join(td, "polish.txt")
+        r = subprocess.run([built["polish_inputs"], gfa, reads, sam, gro, "1", out], env=dict(os.environ, HS_CONSENSUS="1"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        assert r.returncode == 0, r.stdout.decode()[-2000:]
+        bundles, cons = _parse_tool(out)
+        plain = os.path.join(td, "plain.txt")
+        api.polish_inputs_from_files(gfa, reads, sam, gro, plain, polish_everything=True)
+        assert ">consensus" not in open(plain).read()
+    assert len(bundles) == len(cons) > 0 and sum(len(b.pieces) for b in bundles) > 0
+    res = api.polish_consensus(cc.pack(bundles))
+    got = [(int(res["trim_start"][i]), int(res["trim_end"][i]), api.consensus_text(res, i)) for i in range(len(bundles))]
+    assert got == cons

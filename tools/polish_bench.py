@@ -3,7 +3,10 @@ pipeline step: own time of the two kernels (HIP events around their launches), a
 median of `runs` calls after a warm-up. Next to it, where oracle/_ref holds HS_create_new_contigs, the wall time of the reference's
 stage 5 on the files of the same job with the stand-in executables of tools/record_polish_goldens.py (no polisher runs), on one
 thread and on 16: its parsing and the .gaf are inside that time, the external tools are not.
-Usage: python tools/polish_bench.py [config=C4] [contigs=0: the configuration's own] [runs=5]      (prints one JSON line)"""
+Usage: python tools/polish_bench.py [config=C4] [contigs=0: the configuration's own] [runs=5]      (prints one JSON line)
+       python tools/polish_bench.py consensus [config=C4] [contigs=60] [runs=5]
+consensus: the consensus of the same job's bundles (hs_polish_consensus) -- per kernel group own time, algorithmic bytes and
+the fraction of the HBM peak, the whole call, the host half on 16 threads on the same bundles, and how much of the backbones changed."""
 import json
 import os
 import statistics
@@ -38,7 +41,75 @@ def reference_wall(paths, files, gro, td, threads):
     return {"threads": threads, "seconds": time.perf_counter() - t0, "exit_status": r.returncode, "bundles_handed_to_the_polisher": len(os.listdir(cap))}
 
 
+def consensus_row_bytes(res):
+    """one byte per piece and covered column: sum(M + D) of every piece that is not skipped, clipped at the end of its backbone"""
+    import numpy as np
+    w = res["cigar"].astype(np.int64)
+    ln, op = w >> 4, w & 15
+    at = res["cig_off"][:-1]
+
+    def per_piece(x):
+        c = np.concatenate(([0], np.cumsum(x)))
+        return c[res["cig_off"][1:]] - c[at]
+    cols, rd = per_piece(np.where((op == 0) | (op == 2), ln, 0)), per_piece(np.where((op == 0) | (op == 1), ln, 0))
+    n_bases = np.diff(res["base_off"])
+    L = np.repeat(np.diff(res["backbone_off"]), np.diff(res["piece_off"]))
+    s0 = res["piece_sam_pos"].astype(np.int64) - 1
+    ok = (n_bases > 0) & ((res["piece_flags"] & 2) == 0) & (rd == n_bases) & (s0 < L)
+    return int(np.where(ok, np.minimum(cols, L - s0), 0).sum())
+
+
+def main_consensus(argv):
+    cfg = argv[0] if argv else "C4"
+    n = int(argv[1]) if len(argv) > 1 else 60
+    runs = max(5, int(argv[2])) if len(argv) > 2 else 5
+    from hairsplitter_amd import synth
+    with tempfile.TemporaryDirectory() as td:
+        contigs, files = synth.generate_job(cfg, list(range(n)), workers=min(16, os.cpu_count() or 1), outdir=td)      # before the GPU is touched (forks)
+        from hairsplitter_amd import api
+        api.require_gpu()
+        pl = api.PipelineGroups(contigs, 4)
+        cv, sr = pl.run_fused(0.33, 0, rarest_strain_abundance=0.01)
+        res = api.polish_inputs(pl, sr)
+        pl.close()
+    samples = []
+    for i in range(runs + 1):
+        w0 = api.host_waits()
+        t0 = time.perf_counter()
+        cons = api.polish_consensus(res)
+        wall = time.perf_counter() - t0
+        if i:      # the first call is the warm-up
+            samples.append((cons["stats"], wall, api.host_waits() - w0))
+    st = cons["stats"]
+    C, rb = int(res["backbone_off"][-1]), consensus_row_bytes(res)
+    text = int(cons["cons_off"][-1])
+    bytes_of = {"rows": 4 * int(res["cig_off"][-1]) + int(res["base_off"][-1]) + rb + 24 * st["n_ins_records"], "columns": rb + 6 * C + 32 * res["n_pieces"],
+                "ins": 24 * st["n_ins_records"] + 5 * C, "emit": 22 * C + 2 * text}
+    out = {"mode": "consensus", "config": cfg, "contigs": n, "runs": runs, "bundles": res["n_bundles"], "pieces": res["n_pieces"], "columns": C, "row_bytes": rb,
+           "rounds": st["n_rounds"], "host_waits_per_call": samples[-1][2], "ins_records": st["n_ins_records"], "ins_slots": st["n_ins_slots"],
+           "call_wall_ms_median": statistics.median(w for _, w, _ in samples) * 1e3,
+           "changed": {k: int(cons[k].sum()) for k in ("n_sub", "n_del", "n_ins_bases", "n_low", "n_skipped")}, "consensus_bytes": text}
+    for k in ("rows", "columns", "ins", "emit"):
+        ms = statistics.median(s[k + "_ms"] for s, _, _ in samples)
+        out["k_cons_" + k] = {"ms_median": ms, "algorithmic_bytes": bytes_of[k]}
+        if ms > 0:
+            gbs = bytes_of[k] / (ms * 1e-3) / 1e9
+            out["k_cons_" + k].update({"GBs": gbs, "frac_of_hbm_peak": gbs / HBM_PEAK_GBS})
+    os.environ["HS_CONSENSUS_HOST_THREADS"] = "16"
+    host_wall = []
+    for i in range(runs + 1):
+        t0 = time.perf_counter()
+        host = api.polish_consensus(res, form="host")
+        if i:
+            host_wall.append(time.perf_counter() - t0)
+    out["host_half_16_threads_ms_median"] = statistics.median(host_wall) * 1e3
+    out["device_equals_host"] = bool(all((cons[k] == host[k]).all() for k in ("cons_off", "cons", "trim_start", "trim_end", "n_sub", "n_del", "n_ins_bases", "n_low", "n_skipped")))
+    print(json.dumps(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "consensus":
+        return main_consensus(sys.argv[2:])
     cfg = sys.argv[1] if len(sys.argv) > 1 else "C4"
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     runs = max(5, int(sys.argv[3])) if len(sys.argv) > 3 else 5
