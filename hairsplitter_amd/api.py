@@ -29,6 +29,7 @@ SYMBOLS = [
     "hs_pipeline_run_fused", "hs_realign_paf", "hs_pipeline_set_option", "hs_pipeline_groups", "hs_pipeline_group_range", "hs_pipeline_group_cv", "hs_pipeline_sparse_labels", "hs_separate_reads_main", "hs_main_process_exits", "hs_kernel_name", "hs_kernel_stats_reset", "hs_kernel_stats_get", "hs_kernel_stats_every", "hs_host_wait_stats", "hs_devices", "hs_cv_run_host", "hs_edlib_hw_align", "hs_edlib_align", "hs_edlib_align_bytes", "hs_alignment_to_cigar", "hs_reattach_ends", "hs_trim_polished", "hs_reattach_ends_bytes", "hs_trim_polished_bytes", "hs_free_strings", "hs_cut_gfa", "hs_gfa_to_fasta", "hs_cut_gfa_main", "hs_gfa2fa_main",
     "hs_polish_inputs", "hs_polish_inputs_from_files", "hs_polish_result_destroy", "hs_polish_inputs_main",
     "hs_consensus_default_params", "hs_polish_consensus", "hs_polish_consensus_arrays", "hs_polish_consensus_host", "hs_consensus_result_destroy",
+    "hs_polish_haplotypes", "hs_polish_haplotypes_from_files", "hs_haplotypes_result_destroy", "hs_polish_consensus_planned_tap",
     "hs_moves_to_cigar", "hs_realign_intervals", "hs_realign_records_destroy", "hs_cv_batch_create_paf", "hs_cv_batch_create_sam",
     "hs_allele_table_destroy", "hs_alleles_text", "hs_alleles_lds_capacity", "hs_group_alleles_layout", "hs_group_alleles", "hs_haplotype_alleles", "hs_pipeline_alleles",
     "hs_recruit_params_default", "hs_recruit_table_destroy", "hs_recruit_reads", "hs_group_recruit_layout", "hs_group_recruit", "hs_recruit_apply", "hs_recruit_text",
@@ -1720,28 +1721,36 @@ def polish_inputs(batch_or_pipeline, sr: Dict, polish_everything: bool = False, 
     _check(lib.hs_polish_inputs(batch.handle, C.c_int32(c0), C.c_int32(c1), ptr(win_off), ptr(win_start), ptr(win_end), ptr(label_off), ptr(labels),
                                 None if has is None else ptr(has), C.c_int32(1 if polish_everything else 0), C.byref(res)))
     try:
-        r = res.contents
-        B, P, D = int(r.n_bundles), int(r.n_pieces), int(r.n_dropped)
+        out = _polish_result_dict(res.contents, True)
+    finally:
+        lib.hs_polish_result_destroy(res)
+    return out
 
-        def arr(p, n, dtype):
-            return np.ctypeslib.as_array(p, (n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
-        out = {"n_bundles": B, "n_pieces": P}
-        for k in _POLISH_I32_BUNDLE:
-            out[k] = arr(getattr(r, k), B, np.int32)
-        for k in _POLISH_I32_PIECE:
-            out[k] = arr(getattr(r, k), P, np.int32)
-        out["backbone_off"] = arr(r.backbone_off, B + 1, np.int64)
-        out["piece_off"] = arr(r.piece_off, B + 1, np.int64)
-        out["base_off"] = arr(r.base_off, P + 1, np.int64)
-        out["cig_off"] = arr(r.cig_off, P + 1, np.int64)
+
+def _c_array(p, n, dtype):
+    return np.ctypeslib.as_array(p, (n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
+
+
+def _polish_result_dict(r, with_text: bool) -> Dict:
+    """a hs_polish_result as numpy arrays; with_text: backbone, bases and cigar too (hs_polish_haplotypes leaves them on the device)"""
+    B, P, D = int(r.n_bundles), int(r.n_pieces), int(r.n_dropped)
+    arr = _c_array
+    out = {"n_bundles": B, "n_pieces": P}
+    for k in _POLISH_I32_BUNDLE:
+        out[k] = arr(getattr(r, k), B, np.int32)
+    for k in _POLISH_I32_PIECE:
+        out[k] = arr(getattr(r, k), P, np.int32)
+    out["backbone_off"] = arr(r.backbone_off, B + 1, np.int64)
+    out["piece_off"] = arr(r.piece_off, B + 1, np.int64)
+    out["base_off"] = arr(r.base_off, P + 1, np.int64)
+    out["cig_off"] = arr(r.cig_off, P + 1, np.int64)
+    if with_text:
         out["backbone"] = arr(r.backbone, int(out["backbone_off"][-1]), np.uint8)
         out["bases"] = arr(r.bases, int(out["base_off"][-1]), np.uint8)
         out["cigar"] = arr(r.cigar, int(out["cig_off"][-1]), np.uint32)
-        out["dropped"] = arr(r.dropped, 3 * D, np.int32).reshape(D, 3)
-        out["stats"] = {"scan_ms": r.t_scan_ms, "cut_ms": r.t_cut_ms, "gather_ms": r.t_gather_ms, "cigar_ms": r.t_cigar_ms,
-                        "n_tasks": int(r.n_tasks), "n_rounds": int(r.n_rounds), "cut_ops_read": int(r.cut_ops_read)}
-    finally:
-        lib.hs_polish_result_destroy(res)
+    out["dropped"] = arr(r.dropped, 3 * D, np.int32).reshape(D, 3)
+    out["stats"] = {"scan_ms": r.t_scan_ms, "cut_ms": r.t_cut_ms, "gather_ms": r.t_gather_ms, "cigar_ms": r.t_cigar_ms,
+                    "n_tasks": int(r.n_tasks), "n_rounds": int(r.n_rounds), "cut_ops_read": int(r.cut_ops_read)}
     return out
 
 
@@ -1822,10 +1831,12 @@ def consensus_params(**kw) -> ConsensusParams:
 def polish_consensus(res: Dict, params: Optional[ConsensusParams] = None, form: str = "device") -> Dict:
     """The consensus of every bundle of `res`: the dict polish_inputs returns, or one of hand-built arrays with the keys backbone_off, backbone,
     bundle_overhang_left, bundle_overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar. form "device": the kernels
-    (hs_polish_consensus_arrays); "host": the host half of the same rule (hs_polish_consensus_host, no device). Returns numpy arrays cons_off, cons
+    (hs_polish_consensus_arrays); "host": the host half of the same rule (hs_polish_consensus_host, no device); "planned": the device again, but
+    every piece planned by k_cons_plan as hs_polish_haplotypes plans it (hs_polish_consensus_planned_tap) -- the result then holds "plan",
+    [n_pieces][4] = skipped, long_cigar, n_cols, n_ins as the device found them. Returns numpy arrays cons_off, cons
     (text), trim_start, trim_end, n_sub, n_del, n_ins_bases, n_low, n_skipped per bundle, and "stats"."""
-    if form not in ("device", "host"):
-        raise HsError("polish_consensus: form is 'device' or 'host'")
+    if form not in ("device", "host", "planned"):
+        raise HsError("polish_consensus: form is 'device', 'host' or 'planned'")
     lib = load()
     a64 = [_np(res[k], np.int64) for k in ("backbone_off", "piece_off", "base_off", "cig_off")]
     a32 = [_np(res[k], np.int32) for k in ("bundle_overhang_left", "bundle_overhang_right", "piece_sam_pos", "piece_flags")]
@@ -1841,26 +1852,38 @@ def polish_consensus(res: Dict, params: Optional[ConsensusParams] = None, form: 
 
     def ptr(a):
         return a.ctypes.data_as(C.c_void_p)
-    fn = lib.hs_polish_consensus_arrays if form == "device" else lib.hs_polish_consensus_host
-    fn.argtypes = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams), C.POINTER(C.POINTER(ConsensusResult))]
     lib.hs_consensus_result_destroy.argtypes = [C.c_void_p]
     lib.hs_consensus_result_destroy.restype = None
     out_p = C.POINTER(ConsensusResult)()
-    _check(fn(C.c_int64(B), ptr(a64[0]), ptr(backbone), ptr(a32[0]), ptr(a32[1]), ptr(a64[1]), ptr(a32[2]), ptr(a32[3]), ptr(a64[2]), ptr(bases), ptr(a64[3]), ptr(cigar),
-              None if params is None else C.byref(params), C.byref(out_p)))
+    args = [C.c_int64(B), ptr(a64[0]), ptr(backbone), ptr(a32[0]), ptr(a32[1]), ptr(a64[1]), ptr(a32[2]), ptr(a32[3]), ptr(a64[2]), ptr(bases), ptr(a64[3]), ptr(cigar),
+            None if params is None else C.byref(params)]
+    plan = None
+    if form == "planned":
+        plan = np.full((P, 4), -1, np.int32)
+        fn = lib.hs_polish_consensus_planned_tap
+        fn.argtypes = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams), C.c_void_p, C.POINTER(C.POINTER(ConsensusResult))]
+        _check(fn(*(args + [ptr(plan), C.byref(out_p)])))
+    else:
+        fn = lib.hs_polish_consensus_arrays if form == "device" else lib.hs_polish_consensus_host
+        fn.argtypes = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams), C.POINTER(C.POINTER(ConsensusResult))]
+        _check(fn(*(args + [C.byref(out_p)])))
     try:
-        r = out_p.contents
-
-        def arr(p, n, dtype):
-            return np.ctypeslib.as_array(p, (n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
-        out = {"n_bundles": int(r.n_bundles), "cons_off": arr(r.cons_off, B + 1, np.int64)}
-        out["cons"] = arr(r.cons, int(out["cons_off"][-1]), np.uint8)
-        for k in _CONSENSUS_I32:
-            out[k] = arr(getattr(r, k), B, np.int32)
-        out["stats"] = {"rows_ms": r.t_rows_ms, "columns_ms": r.t_columns_ms, "ins_ms": r.t_ins_ms, "emit_ms": r.t_emit_ms, "n_rounds": int(r.n_rounds),
-                        "n_ins_records": int(r.n_ins_records), "n_ins_slots": int(r.n_ins_slots)}
+        out = _consensus_result_dict(out_p.contents, B)
     finally:
         lib.hs_consensus_result_destroy(out_p)
+    if plan is not None:
+        out["plan"] = plan
+    return out
+
+
+def _consensus_result_dict(r, B: int) -> Dict:
+    arr = _c_array
+    out = {"n_bundles": int(r.n_bundles), "cons_off": arr(r.cons_off, B + 1, np.int64)}
+    out["cons"] = arr(r.cons, int(out["cons_off"][-1]), np.uint8)
+    for k in _CONSENSUS_I32:
+        out[k] = arr(getattr(r, k), B, np.int32)
+    out["stats"] = {"rows_ms": r.t_rows_ms, "columns_ms": r.t_columns_ms, "ins_ms": r.t_ins_ms, "emit_ms": r.t_emit_ms, "n_rounds": int(r.n_rounds),
+                    "n_ins_records": int(r.n_ins_records), "n_ins_slots": int(r.n_ins_slots)}
     return out
 
 
@@ -1869,6 +1892,70 @@ def consensus_text(cons: Dict, i: int, trimmed: bool = False) -> str:
     o = int(cons["cons_off"][i])
     a, b = (int(cons["trim_start"][i]), int(cons["trim_end"][i])) if trimmed else (0, int(cons["cons_off"][i + 1]) - o)
     return cons["cons"][o + a:o + max(a, b)].tobytes().decode()
+
+
+# ---- from labels to haplotype sequences: the rounds of polish_inputs with the consensus as their sink, the pieces never leaving the device ----
+class HaplotypesResult(C.Structure):
+    _fields_ = [("inputs", C.POINTER(PolishResult)), ("consensus", C.POINTER(ConsensusResult)), ("n_rounds", C.c_int64), ("n_sub_rounds", C.c_int64),
+                ("bytes_down", C.c_int64), ("bytes_up", C.c_int64), ("t_plan_ms", C.c_double)]
+
+
+def polish_haplotypes(batch_or_pipeline, sr: Dict, polish_everything: bool = False, c0: int = 0, c1: Optional[int] = None, contig_has_snps=None,
+                      params: Optional[ConsensusParams] = None) -> Dict:
+    """polish_consensus(polish_inputs(...)) in one call (hs_polish_haplotypes): the arguments of polish_inputs and the consensus parameters. One
+    dict: the metadata keys of polish_inputs (everything but backbone, bases and cigar, which stay on the device), the keys of polish_consensus,
+    and "stats" = those of both, n_rounds (resident rounds), n_sub_rounds (consensus rounds), bytes_down, bytes_up and plan_ms."""
+    batch = getattr(batch_or_pipeline, "batch", batch_or_pipeline)
+    lib = load()
+    win_off = _np(sr["win_off"], np.int64); win_start = _np(sr["win_start"], np.int32); win_end = _np(sr["win_end"], np.int32)
+    label_off = _np(sr["label_off"], np.int64); labels = _np(sr["labels"], np.int32)
+    has = None if contig_has_snps is None else _np(np.asarray(contig_has_snps).astype(np.uint8), np.uint8)
+    if len(win_off) - 1 != batch.flat.n_contigs:
+        raise HsError("polish_haplotypes: the result does not cover the contigs of the batch")
+    if c1 is None:
+        c1 = batch.flat.n_contigs
+
+    def ptr(a):
+        return a.ctypes.data_as(C.c_void_p)
+    res = C.POINTER(HaplotypesResult)()
+    lib.hs_polish_haplotypes.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.POINTER(ConsensusParams), C.POINTER(C.POINTER(HaplotypesResult))]
+    lib.hs_haplotypes_result_destroy.argtypes = [C.c_void_p]
+    lib.hs_haplotypes_result_destroy.restype = None
+    _check(lib.hs_polish_haplotypes(batch.handle, C.c_int32(c0), C.c_int32(c1), ptr(win_off), ptr(win_start), ptr(win_end), ptr(label_off), ptr(labels),
+                                    None if has is None else ptr(has), C.c_int32(1 if polish_everything else 0), None if params is None else C.byref(params),
+                                    C.byref(res)))
+    try:
+        r = res.contents
+        out = _polish_result_dict(r.inputs.contents, False)
+        cons = _consensus_result_dict(r.consensus.contents, out["n_bundles"])
+        stats = dict(out["stats"], **cons.pop("stats"))
+        out.update(cons)
+        stats.update({"n_rounds": int(r.n_rounds), "n_sub_rounds": int(r.n_sub_rounds), "bytes_down": int(r.bytes_down), "bytes_up": int(r.bytes_up), "plan_ms": r.t_plan_ms})
+        out["stats"] = stats
+    finally:
+        lib.hs_haplotypes_result_destroy(res)
+    return out
+
+
+def haplotype_text(res: Dict, i: int) -> str:
+    """The sequence of bundle i of a polish_haplotypes result: its consensus without the overhangs"""
+    return consensus_text(res, i, trimmed=True)
+
+
+def haplotype_fasta_header(res: Dict, i: int, contig_name: Optional[str] = None) -> str:
+    """The header bin/hs_polish_inputs writes for bundle i under HS_HAPLOTYPES=1 (without the '>')"""
+    name = contig_name if contig_name is not None else str(int(res["bundle_contig"][i]))
+    return "%s_%d_%d_%d" % (name, int(res["bundle_start"][i]), int(res["bundle_end"][i]), int(res["bundle_group"][i]))
+
+
+def polish_haplotypes_from_files(gfa: str, reads: str, sam: str, gro: str, out_fasta: str, polish_everything: bool = False, params: Optional[ConsensusParams] = None,
+                                 n_threads: int = 1) -> None:
+    """The same from the four files HS_create_new_contigs reads, written as FASTA: a record ">contig_start_end_group" per bundle, its trimmed consensus
+    on one line (hs_polish_haplotypes_from_files; what bin/hs_polish_inputs writes under HS_HAPLOTYPES=1)."""
+    lib = load()
+    lib.hs_polish_haplotypes_from_files.argtypes = [C.c_char_p] * 4 + [C.c_int32, C.POINTER(ConsensusParams), C.c_char_p, C.c_int32]
+    _check(lib.hs_polish_haplotypes_from_files(gfa.encode(), reads.encode(), sam.encode(), gro.encode(), C.c_int32(1 if polish_everything else 0),
+                                               None if params is None else C.byref(params), out_fasta.encode(), C.c_int32(n_threads)))
 
 
 def edlib_hw_align(pairs, path=True):

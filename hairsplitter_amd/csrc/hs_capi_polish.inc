@@ -1,7 +1,8 @@
 // hs_capi_polish.inc -- the polisher's inputs (create_new_contigs.cpp:358-521) on the resident batch: the host side of
 // hs_kernels_polish.hip. The host lists the (interval, read) tasks, k_polish_cut walks them, the sizes come back (the one host
 // wait the sizes cost), the host forms the groups and 64-bit offsets, and k_polish_gather / k_polish_cigar fill the output in
-// rounds whose device scratch stays within HS_POLISH_CHUNK_MB.
+// rounds whose device scratch stays within HS_POLISH_CHUNK_MB. A round ends in the downloads of hs_polish_inputs or, for hs_polish_haplotypes
+// (hs_capi_consensus.inc), in a sink that works on the round's buffers where they are.
 
 namespace {
 
@@ -49,19 +50,55 @@ struct PolishTimer {   // HIP events around a group of launches, summed when the
     double ms() { double t = 0; for (auto& e : ev) { float x = 0; if (hipEventElapsedTime(&x, e.first, e.second) == hipSuccess) t += x; } return t; }
 };
 
+struct BytesMoved { int64_t up = 0, down = 0; };      // what a call sent to the device and fetched from it
+
+// what the host needs of the records: strand, op ranges, reads, the reads' ranges (the batch keeps them on the device): one shipment and one
+// host wait on the batch's first polishing call, none after it
+int polish_host_recs(const hs_cv_batch* b, BytesMoved* moved) {
+    std::lock_guard<std::mutex> g(b->polish_mu);
+    if (b->polish_have) return HS_OK;
+    const size_t n_rec = (size_t)b->n_rec, n_reads = (size_t)b->n_reads;
+    const size_t part[4] = {n_rec, (n_rec + 1) * 8, (n_reads + 1) * 8, n_rec * 4};
+    const void* src[4] = {b->rec_strand.p, b->rec_cig_off.p, b->read_off.p, b->rec_read.p};
+    size_t at[4], total = 0;
+    for (int k = 0; k < 4; ++k) { at[k] = total; total += (part[k] + 31) & ~(size_t)15; }
+    HBuf h;
+    if (int rc = h.alloc(total + 16)) return rc;
+    Shipment sh;
+    for (int k = 0; k < 4; ++k) if (k == 2 || n_rec) sh.add((char*)h.p + at[k], src[k], part[k]);
+    if (int rc = sh.launch(nullptr)) return rc;
+    if (int rc = stream_wait(nullptr)) return rc;
+    b->h_rec_strand.assign(n_rec, 0); b->h_rec_cig_off.assign(n_rec + 1, 0); b->h_read_off.assign(n_reads + 1, 0); b->h_rec_read.assign(n_rec, 0);
+    void* dst[4] = {b->h_rec_strand.data(), b->h_rec_cig_off.data(), b->h_read_off.data(), b->h_rec_read.data()};
+    for (int k = 0; k < 4; ++k) if (k == 2 || n_rec) std::memcpy(dst[k], (char*)h.p + at[k], part[k]);
+    if (moved) moved->down += (int64_t)(part[0] + part[1] + part[2] + part[3]);
+    b->polish_have = true;
+    return HS_OK;
+}
+
+// a round of polish_inputs_core as its sink sees it: the bundles [b0, b1) of the call's tables (host arrays over all bundles and pieces of the
+// call) and the round's device buffers, which begin where the round's first piece and first bundle begin
+struct PolishRound {
+    int64_t b0, b1;
+    const int64_t *backbone_off, *piece_off, *base_off, *cig_off;
+    const int32_t *ovl, *ovr, *sam, *flags;
+    const uint8_t *d_bases, *d_bb;
+    const uint32_t* d_cig;
+    hipStream_t st;
+};
+typedef std::function<int(const PolishRound&)> PolishSink;
+
+// sink == nullptr: the round's bases, backbones and CIGAR words come down into the result (hs_polish_inputs). With a sink they stay on the
+// device, the sink works on them there, and the result's backbone, bases and cigar are NULL.
 int polish_inputs_core(hs_cv_batch* b, int c0, int c1, const std::vector<std::vector<hs::LabelledInterval>>& ivs, const std::vector<uint8_t>& has,
-                       bool polish_everything, const std::vector<int32_t>& rec_read, hs_polish_result** out) {
+                       bool polish_everything, hs_polish_result** out, const PolishSink* sink = nullptr, BytesMoved* moved = nullptr) {
     using namespace hsdev;
     hipStream_t st = nullptr;
     const int n_rec = b->n_rec;
-    // what the host needs of the records: strand, op ranges, read ranges (the batch keeps them on the device only)
-    std::vector<uint8_t> rec_strand((size_t)n_rec);
-    std::vector<int64_t> rec_cig_off((size_t)n_rec + 1, 0), read_off((size_t)b->n_reads + 1, 0);
-    if (n_rec) {
-        if (int rc = d2h_pinned(rec_strand.data(), b->rec_strand.p, (size_t)n_rec, st)) return rc;
-        if (int rc = d2h_pinned(rec_cig_off.data(), b->rec_cig_off.p, ((size_t)n_rec + 1) * 8, st)) return rc;
-    }
-    if (int rc = d2h_pinned(read_off.data(), b->read_off.p, ((size_t)b->n_reads + 1) * 8, st)) return rc;
+    if (int rc = polish_host_recs(b, moved)) return rc;
+    const std::vector<uint8_t>& rec_strand = b->h_rec_strand;
+    const std::vector<int64_t>&rec_cig_off = b->h_rec_cig_off, &read_off = b->h_read_off;
+    const std::vector<int32_t>& rec_read = b->h_rec_read;
 
     // ---- the intervals of the call and their tasks: every read with a label above -1 (:383-384)
     struct Interval { int32_t contig, index, start, end; PolishIntervalBounds bd; int64_t task0, task1; const std::vector<int>* lab; };
@@ -112,6 +149,7 @@ int polish_inputs_core(hs_cv_batch* b, int c0, int c1, const std::vector<std::ve
         DBuf d_tasks, d_slot, d_recs, d_chunk_off, d_tab, d_cut;
         UploadPack pk;
         pk.add(tasks, d_tasks); pk.add(slot_of_rec, d_slot); pk.add(recs, d_recs); pk.add(chunk_off, d_chunk_off);
+        if (moved) moved->up += (int64_t)pk.total;
         if (int rc = pk.commit(st)) return rc;
         if (int rc = d_tab.alloc(std::max<size_t>((size_t)chunk_off.back(), 1) * 2 * sizeof(int32_t))) return rc;
         if (int rc = d_cut.alloc(std::max<size_t>(cut.size(), 1) * sizeof(int32_t))) return rc;
@@ -130,6 +168,7 @@ int polish_inputs_core(hs_cv_batch* b, int c0, int c1, const std::vector<std::ve
         }
         HS_HIP(hipGetLastError());
         if (int rc = polish_download(cut.data(), d_cut.p, cut.size() * sizeof(int32_t), st)) return rc;      // the host wait of the call
+        if (moved) moved->down += (int64_t)(cut.size() * sizeof(int32_t));
     }
 
     // ---- groups and bundles (:478-506, :523), pieces in (bundle, record) order
@@ -181,10 +220,14 @@ int polish_inputs_core(hs_cv_batch* b, int c0, int c1, const std::vector<std::ve
     if (!res) { set_error("hs_polish_inputs: out of host memory"); return HS_EINVAL; }
     std::unique_ptr<hs_polish_result, void (*)(hs_polish_result*)> guard(res, hs_polish_result_destroy);
     res->n_bundles = n_bundles; res->n_pieces = n_pieces; res->n_dropped = (int64_t)dropped.size() / 3;
-    res->backbone = static_cast<uint8_t*>(std::malloc((size_t)std::max<int64_t>(backbone_off.back(), 1)));
-    res->bases = static_cast<uint8_t*>(std::malloc((size_t)std::max<int64_t>(base_off.back(), 1)));
-    res->cigar = static_cast<uint32_t*>(std::malloc((size_t)std::max<int64_t>(cig_off.back(), 1) * sizeof(uint32_t)));
-    if (!res->backbone || !res->bases || !res->cigar) { set_error("hs_polish_inputs: out of host memory"); return HS_EINVAL; }
+    if (!sink) {
+        res->backbone = static_cast<uint8_t*>(std::malloc((size_t)std::max<int64_t>(backbone_off.back(), 1)));
+        res->bases = static_cast<uint8_t*>(std::malloc((size_t)std::max<int64_t>(base_off.back(), 1)));
+        res->cigar = static_cast<uint32_t*>(std::malloc((size_t)std::max<int64_t>(cig_off.back(), 1) * sizeof(uint32_t)));
+        if (!res->backbone || !res->bases || !res->cigar) { set_error("hs_polish_inputs: out of host memory"); return HS_EINVAL; }
+    }
+    std::vector<int32_t> bundle_ovl, bundle_ovr;      // (what a sink reads of the bundles)
+    if (sink) for (const PolishBundle& bu : bundles) { bundle_ovl.push_back(bu.ovl); bundle_ovr.push_back(bu.ovr); }
 
     // ---- rounds over bundle ranges that end with a contig: gather + CIGAR into scratch, then down
     const char* bud = std::getenv("HS_POLISH_CHUNK_MB");
@@ -242,6 +285,7 @@ int polish_inputs_core(hs_cv_batch* b, int c0, int c1, const std::vector<std::ve
         DBuf d_rp, d_rs, d_bp, d_bs, d_ct, d_bases, d_bb, d_cig;
         UploadPack pk;
         pk.add(rp, d_rp); pk.add(rs, d_rs); pk.add(bpieces, d_bp); pk.add(bs, d_bs); pk.add(ct, d_ct);
+        if (moved) moved->up += (int64_t)pk.total;
         if (int rc = pk.commit(st)) return rc;
         if (int rc = d_bases.alloc((size_t)n_base + 16)) return rc;
         if (int rc = d_bb.alloc((size_t)n_bb + 16)) return rc;
@@ -258,9 +302,16 @@ int polish_inputs_core(hs_cv_batch* b, int c0, int c1, const std::vector<std::ve
                                b->cigar.as<uint32_t>(), d_cig.as<uint32_t>());
         t_cigar.end();
         HS_HIP(hipGetLastError());
-        if (int rc = polish_download(res->bases + base0, d_bases.p, (size_t)n_base, st)) return rc;
-        if (int rc = polish_download(res->backbone + bb0, d_bb.p, (size_t)n_bb, st)) return rc;
-        if (int rc = polish_download(res->cigar + cig0, d_cig.p, (size_t)n_cig * sizeof(uint32_t), st)) return rc;
+        if (sink) {      // the pieces stay where they are
+            const PolishRound round{b0, b1, backbone_off.data(), piece_off.data(), base_off.data(), cig_off.data(), bundle_ovl.data(), bundle_ovr.data(), piece_sam.data(),
+                                    piece_flags.data(), d_bases.as<uint8_t>(), d_bb.as<uint8_t>(), d_cig.as<uint32_t>(), st};
+            if (int rc = (*sink)(round)) return rc;
+        } else {
+            if (int rc = polish_download(res->bases + base0, d_bases.p, (size_t)n_base, st)) return rc;
+            if (int rc = polish_download(res->backbone + bb0, d_bb.p, (size_t)n_bb, st)) return rc;
+            if (int rc = polish_download(res->cigar + cig0, d_cig.p, (size_t)n_cig * sizeof(uint32_t), st)) return rc;
+            if (moved) moved->down += n_base + n_bb + n_cig * 4;
+        }
         b0 = b1;
     }
     if (int rc = stream_wait_quiet(st)) return rc;
@@ -283,12 +334,6 @@ int polish_inputs_core(hs_cv_batch* b, int c0, int c1, const std::vector<std::ve
     return HS_OK;
 }
 
-int polish_rec_read(hs_cv_batch* b, std::vector<int32_t>& rec_read) {
-    rec_read.assign((size_t)b->n_rec, 0);
-    if (b->n_rec) return d2h_pinned(rec_read.data(), b->rec_read.p, (size_t)b->n_rec * sizeof(int32_t), nullptr);
-    return HS_OK;
-}
-
 }  // namespace
 
 void hs_polish_result_destroy(hs_polish_result* r) {
@@ -306,14 +351,13 @@ int hs_polish_inputs(hs_cv_batch* b, int32_t c0, int32_t c1, const int64_t* win_
     if (!b || !out || !win_off || !label_off || c0 < 0 || c1 < c0 || c1 > b->n_contigs) { set_error("hs_polish_inputs: bad arguments"); return HS_EINVAL; }
     if (int rc = bind_device(b->device)) return rc;
     try {
-        std::vector<int32_t> rec_read;
-        if (int rc = polish_rec_read(b, rec_read)) return rc;
+        if (int rc = polish_host_recs(b, nullptr)) return rc;
         std::vector<std::vector<hs::LabelledInterval>> ivs;
         std::vector<uint8_t> has;
-        if (int rc = hs::polish_intervals_from_labels(b->n_contigs, b->contig_rec_off.data(), rec_read.data(), win_off, win_start, win_end, label_off, labels,
+        if (int rc = hs::polish_intervals_from_labels(b->n_contigs, b->contig_rec_off.data(), b->h_rec_read.data(), win_off, win_start, win_end, label_off, labels,
                                                       contig_has_snps, ivs, has))
             return rc;
-        return polish_inputs_core(b, c0, c1, ivs, has, polish_everything != 0, rec_read, out);
+        return polish_inputs_core(b, c0, c1, ivs, has, polish_everything != 0, out);
     } catch (const std::exception& e) { set_error(std::string("hs_polish_inputs: ") + e.what()); return HS_EINVAL; }
 }
 
@@ -321,6 +365,9 @@ int hs_polish_inputs_from_files(const char* gfa, const char* reads, const char* 
                                 int32_t n_threads) {
     if (int rc = require_device()) return rc;
     if (!gfa || !reads || !sam || !gro || !out_path) { set_error("hs_polish_inputs_from_files: null path"); return HS_EINVAL; }
+    // HS_HAPLOTYPES=1: the FASTA of hs_polish_haplotypes_from_files (the default parameters) in place of the bundle text; it wins over HS_CONSENSUS=1
+    const char* want_hap = std::getenv("HS_HAPLOTYPES");
+    if (want_hap && want_hap[0] == '1') return hs_polish_haplotypes_from_files(gfa, reads, sam, gro, polish_everything, nullptr, out_path, n_threads);
     try {
         hs::CvFileInput in;
         if (int rc = hs::load_cv_inputs(gfa, reads, sam, false, in, n_threads < 1 ? 1 : n_threads)) return rc;
@@ -334,7 +381,7 @@ int hs_polish_inputs_from_files(const char* gfa, const char* reads, const char* 
             return rc;
         std::unique_ptr<hs_cv_batch, void (*)(hs_cv_batch*)> bguard(b, hs_cv_batch_destroy);
         hs_polish_result* r = nullptr;
-        if (int rc = polish_inputs_core(b, 0, n_contigs, ivs, has, polish_everything != 0, in.rec_read, &r)) return rc;
+        if (int rc = polish_inputs_core(b, 0, n_contigs, ivs, has, polish_everything != 0, &r)) return rc;
         std::unique_ptr<hs_polish_result, void (*)(hs_polish_result*)> rguard(r, hs_polish_result_destroy);
         // HS_CONSENSUS=1: every bundle's consensus (hs_polish_consensus, the default parameters) behind its text
         const char* want_cons = std::getenv("HS_CONSENSUS");

@@ -27,6 +27,13 @@ struct hs_cv_batch {
         d_pile_off, d_contig_rec_off, d_rec_qend, pile, rec_stats, rec_chunk_off, chunk_scratch,
         tile_off, tile_ent, tile_lrec, d_rank_of, d_orig_of, d_read_end, d_rank_end, run_tasks /* hsdev::RunTask per task of k_pileup_runs */, run_task_ops /* their ops, 64 HS_K1R_NCH per task */;
     HBuf h_stage_a;   // pinned staging of the per-record counters
+    // what the polishing calls read of the records on the host (strand, op ranges, reads; the reads' ranges): the batch keeps them on the device,
+    // the first polishing call fetches them in one shipment (polish_host_recs) and later calls find them here
+    mutable std::mutex polish_mu;
+    mutable bool polish_have = false;
+    mutable std::vector<uint8_t> h_rec_strand;
+    mutable std::vector<int64_t> h_rec_cig_off, h_read_off;
+    mutable std::vector<int32_t> h_rec_read;
     // the pileup is padded by 256 bytes on both sides: k_gather_tiles loads the 256 bytes a record lays over a tile whole, also
     // where the record covers part of the tile only
     uint8_t* pile_ptr() const { return pile.as<uint8_t>() + 256; }

@@ -9,6 +9,10 @@
 //   k_cons_ins_decide  a lane per column: the winning slot's length and bases; every column's output length
 //   k_cons_emit        a lane per column: the text, behind the scan of the lengths
 //   k_cons_bundles     a wavefront per bundle: its offsets, trim_* and counters
+// For a caller whose pieces exist on the device only (hs_polish_haplotypes), in front of k_cons_rows:
+//   k_cons_plan        a wavefront per piece: hs::cons_piece_plan on the device -- skipped?, covered columns, voting insertions, a CIGAR beyond 2^31 - 1;
+//                      its bundle's row bytes, records and skipped pieces by no-return atomics
+//   k_cons_layout      a lane per piece: the records k_cons_rows reads, rows and records at the offsets two scans of the plan gave
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -76,6 +80,87 @@ __global__ __launch_bounds__(256) void k_cons_rows(const ConsPiece* __restrict__
         if (colmask) { any = true; I_at_last = __shfl(ins_ex, 63 - __builtin_clzll(colmask), 64); }
         T += E; Q += __builtin_amdgcn_readlane(rd_inc, 63); I += __builtin_amdgcn_readlane(ins_inc, 63);
     }
+}
+
+// ---- the plan of a piece on the device (hs::cons_piece_plan is the rule): for a caller whose clipped CIGARs exist on the device only.
+// A piece goes in as a ConsPiece whose row_off holds the index of its bundle, n_cols its base count and n_rec its piece_flags (the kernels
+// above never see these records: k_cons_layout writes theirs). Sums of up to 2^31 ops of up to 2^28 run in 64 bits: a wave's 64 lengths are
+// scanned as two 32-bit scans, of their low 16 bits and of the rest.
+struct ConsPlan { int32_t skipped, long_cigar, n_cols, n_ins; };
+struct ConsBundlePlan { long long row_bytes, n_rec; };
+
+static __device__ __forceinline__ long long wave_scan_incl_i64(uint32_t len) {
+    const int lo = wave_scan_incl((int)(len & 0xffffu)), hi = wave_scan_incl((int)(len >> 16));
+    return ((long long)hi << 16) + (long long)lo;
+}
+
+// one wavefront per piece, lanes = CIGAR ops in 64-op chunks (the layout of k_cons_rows). A voting insertion: a column op of length > 0 with
+// inserted bases behind the column op before it, a column event before it, and its first column inside the room L - s0. Whether inserted
+// bases lie between two column ops is read off the ballots; `any` and `ins_open` carry it over a chunk's edge.
+__global__ __launch_bounds__(256) void k_cons_plan(const ConsPiece* __restrict__ pieces, int n_pieces, const ConsBundle* __restrict__ bundles, const uint32_t* __restrict__ cigar,
+                                                   ConsPlan* __restrict__ plan, int32_t* __restrict__ cols, int32_t* __restrict__ recs, ConsBundlePlan* __restrict__ bundle_plan,
+                                                   int32_t* __restrict__ bundle_skipped, int32_t* __restrict__ first_long) {
+    const int lane = lane_id();
+    const int p = (int)blockIdx.x * 4 + wave_id();
+    if (p >= n_pieces) return;
+    const ConsPiece pc = pieces[p];
+    const int b = (int)pc.row_off;
+    const long long L = bundles[b].L, n_bases = pc.n_cols, room = L - pc.s0;
+    const int32_t flags = pc.n_rec;
+    const uint32_t* __restrict__ cg = cigar + pc.cig_off;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    long long T = 0, Q = 0;       // column events and read bases so far
+    bool any = false;             // a column op of length > 0 so far
+    bool ins_open = false;        // inserted bases behind the last column op (or, without one, behind the start)
+    int n_ins = 0;
+    for (int k = 0; (k << 6) < pc.n_ops; ++k) {
+        const int opi = (k << 6) + lane;
+        const uint32_t op = opi < pc.n_ops ? cg[opi] : 0u;
+        const uint32_t a_col = (uint32_t)hs::cons_col_advance(op), a_rd = (uint32_t)hs::cons_read_advance(op);
+        const long long col_inc = wave_scan_incl_i64(a_col), rd_inc = wave_scan_incl_i64(a_rd);
+        const long long col_ex = T + col_inc - a_col;
+        const bool is_col = a_col > 0;
+        const unsigned long long colmask = __ballot(is_col), insmask = __ballot((op & 15u) == 1u && (op >> 4) > 0u), below = colmask & lt_mask;
+        // the inserted bases between the column op before this lane and this lane
+        const unsigned long long since = below ? ~((2ull << (63 - __builtin_clzll(below))) - 1ull) : ~0ull;
+        const bool pending = (insmask & lt_mask & since) != 0ull || (!below && ins_open);
+        const bool votes = is_col && pending && (below != 0ull || any) && col_ex < room;
+        n_ins += __popcll(__ballot(votes));
+        if (colmask) {
+            const int last = 63 - __builtin_clzll(colmask);
+            any = true;
+            ins_open = last < 63 && (insmask >> (last + 1)) != 0ull;
+        } else ins_open = ins_open || insmask != 0ull;
+        T += __shfl(col_inc, 63, 64); Q += __shfl(rd_inc, 63, 64);
+    }
+    if (lane != 0) return;
+    const bool long_cigar = T + Q > 0x7fffffffll;
+    const bool skipped = long_cigar || n_bases == 0 || (flags & HS_POLISH_START_BEYOND_SEQ) || Q != n_bases || room <= 0;
+    ConsPlan pl;
+    pl.skipped = skipped ? 1 : 0; pl.long_cigar = long_cigar ? 1 : 0;
+    pl.n_cols = skipped ? 0 : (int32_t)(T < room ? T : room); pl.n_ins = skipped ? 0 : n_ins;
+    plan[p] = pl; cols[p] = pl.n_cols; recs[p] = pl.n_ins;
+    if (long_cigar) __hip_atomic_fetch_min(first_long, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (skipped) __hip_atomic_fetch_add(&bundle_skipped[b], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else {
+        __hip_atomic_fetch_add(&bundle_plan[b].row_bytes, (long long)pl.n_cols, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (pl.n_ins) __hip_atomic_fetch_add(&bundle_plan[b].n_rec, (long long)pl.n_ins, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// the pieces [p0, p0 + n) of a planned call as the records k_cons_rows and k_cons_columns read: rows and records at the scans' offsets, every
+// offset counted from where the range begins (base0, cig0, col0; bundle0: the range's first bundle, whose column offset and rows come first)
+__global__ __launch_bounds__(256) void k_cons_layout(const ConsPiece* __restrict__ src, long long p0, int n, const int32_t* __restrict__ cols, const int32_t* __restrict__ recs,
+                                                     const int64_t* __restrict__ col_scan, const int64_t* __restrict__ rec_scan, long long base0, long long cig0, long long col0,
+                                                     ConsPiece* __restrict__ dst) {
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= n) return;
+    const ConsPiece s = src[p0 + i];
+    ConsPiece d;
+    d.base_off = s.base_off - base0; d.cig_off = s.cig_off - cig0; d.col_off = s.col_off - col0;
+    d.row_off = col_scan[p0 + i] - col_scan[p0]; d.rec_off = rec_scan[p0 + i] - rec_scan[p0];
+    d.n_ops = s.n_ops; d.s0 = s.s0; d.n_cols = cols[p0 + i]; d.n_rec = recs[p0 + i];
+    dst[i] = d;
 }
 
 __global__ __launch_bounds__(256) void k_cons_columns(const ConsTile* __restrict__ tiles, const ConsBundle* __restrict__ bundles, const ConsPiece* __restrict__ pieces,

@@ -901,7 +901,9 @@ int hs_polish_inputs(hs_cv_batch* b, int32_t c0, int32_t c1, const int64_t* win_
  * "BUNDLE <contig> <interval start> <interval end> <group> <leftToPolish> <rightToPolish> <overhangLeft> <overhangRight> <reads>"
  * (tab-separated), then ">seq" and toPolish, then per non-empty piece ">read<k> <startPosition> <CIGAR>" and the piece
  * (tools.cpp:351-361).  With HS_CONSENSUS=1 in the environment every bundle ends in ">consensus <trim_start> <trim_end>" and its
- * consensus (hs_polish_consensus below, the default parameters). */
+ * consensus (hs_polish_consensus below, the default parameters).  With HS_HAPLOTYPES=1 the FASTA of
+ * hs_polish_haplotypes_from_files (below, the default parameters) is written in place of this text; where both are set,
+ * HS_HAPLOTYPES wins. */
 int hs_polish_inputs_from_files(const char* gfa, const char* reads, const char* sam, const char* gro, int32_t polish_everything,
                                 const char* out_path, int32_t n_threads);
 void hs_polish_result_destroy(hs_polish_result* r);
@@ -950,6 +952,40 @@ int hs_polish_consensus_host(int64_t n_bundles, const int64_t* backbone_off, con
                              const int64_t* base_off, const uint8_t* bases, const int64_t* cig_off, const uint32_t* cigar,
                              const hs_consensus_params* params, hs_consensus_result** out);
 void hs_consensus_result_destroy(hs_consensus_result* r);
+
+/* ------------------------------------------------------------------------------------------------
+ * From labels to haplotype sequences in one call (device work): the rounds of hs_polish_inputs with the consensus as their sink.  The
+ * pieces, their clipped CIGARs and the backbones stay in device memory; the plan of every piece (hs::cons_piece_plan: skipped?,
+ * covered columns, voting insertions) is computed there (k_cons_plan), and the rounds end in the kernels of hs_polish_consensus.
+ * Host waits of a call: one for the cut table, one per resident round (of HS_POLISH_CHUNK_MB) for the plan's sizes, two per
+ * consensus sub-round (whole bundles within HS_CONSENSUS_CHUNK_MB of row bytes) -- and one more on the first polishing call on a
+ * batch, which fetches the records' strand, op ranges and reads once.  No new contigs, no GFA, no .gaf.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hs_haplotypes_result {
+    hs_polish_result* inputs;        /* every bundle_* / piece_* / *_off / dropped array of hs_polish_inputs for the same call;
+                                        backbone, bases and cigar are NULL: they never came down */
+    hs_consensus_result* consensus;  /* as hs_polish_consensus of those inputs (n_rounds: the sub-rounds) */
+    int64_t n_rounds, n_sub_rounds, bytes_down, bytes_up;   /* resident rounds, consensus sub-rounds, what the call moved */
+    double t_plan_ms;                /* k_cons_plan + layout, HIP events */
+} hs_haplotypes_result;
+/* the arguments of hs_polish_inputs, then the consensus parameters (NULL: the defaults).  A bundle above HS_CONSENSUS_CHUNK_MB and a
+ * CIGAR of more than 2^31 - 1 bases are refused with the messages of hs_polish_consensus. */
+int hs_polish_haplotypes(hs_cv_batch* b, int32_t c0, int32_t c1, const int64_t* win_off, const int32_t* win_start, const int32_t* win_end,
+                         const int64_t* label_off, const int32_t* labels, const uint8_t* contig_has_snps, int32_t polish_everything,
+                         const hs_consensus_params* params, hs_haplotypes_result** out);
+/* the same from the four files of hs_polish_inputs_from_files, written as FASTA (the format is ours): one record per bundle, in bundle
+ * order; header ">" <contig name> "_" <bundle_start> "_" <bundle_end> "_" <bundle_group>; body the bundle's consensus
+ * [trim_start, trim_end) on one line (an empty line where nothing is left). */
+int hs_polish_haplotypes_from_files(const char* gfa, const char* reads, const char* sam, const char* gro, int32_t polish_everything,
+                                    const hs_consensus_params* params, const char* out_fasta, int32_t n_threads);
+void hs_haplotypes_result_destroy(hs_haplotypes_result* r);
+/* test tap: the arrays of hs_polish_consensus_arrays, uploaded whole, but planned by k_cons_plan and laid out by the scans, as the
+ * resident route plans them; plan_out [4 * n_pieces] (may be NULL) = skipped, long_cigar, n_cols, n_ins of every piece as the device
+ * found them.  n_rounds of the result: the sub-rounds. */
+int hs_polish_consensus_planned_tap(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left,
+                                    const int32_t* overhang_right, const int64_t* piece_off, const int32_t* piece_sam_pos,
+                                    const int32_t* piece_flags, const int64_t* base_off, const uint8_t* bases, const int64_t* cig_off,
+                                    const uint32_t* cigar, const hs_consensus_params* params, int32_t* plan_out, hs_consensus_result** out);
 
 /* ------------------------------------------------------------------------------------------------
  * Upstream feeders of stage 3 that are plain text transforms (host code): the 300 kb cutter the orchestrator runs before the

@@ -5,8 +5,12 @@ stage 5 on the files of the same job with the stand-in executables of tools/reco
 thread and on 16: its parsing and the .gaf are inside that time, the external tools are not.
 Usage: python tools/polish_bench.py [config=C4] [contigs=0: the configuration's own] [runs=5]      (prints one JSON line)
        python tools/polish_bench.py consensus [config=C4] [contigs=60] [runs=5]
+       python tools/polish_bench.py haplotypes [config=C4] [contigs=60] [runs=5] [alternations=3]
 consensus: the consensus of the same job's bundles (hs_polish_consensus) -- per kernel group own time, algorithmic bytes and
-the fraction of the HBM peak, the whole call, the host half on 16 threads on the same bundles, and how much of the backbones changed."""
+the fraction of the HBM peak, the whole call, the host half on 16 threads on the same bundles, and how much of the backbones changed.
+haplotypes: from the labels to the haplotype sequences -- the whole call of polish_haplotypes and of polish_inputs followed by
+polish_consensus, alternating three times (median of `runs` calls after a warm-up each time); the own time of k_cons_plan + layout, its
+algorithmic bytes and fraction of the HBM peak; what either route moved. A build without hs_polish_haplotypes times the composition alone."""
 import json
 import os
 import statistics
@@ -107,9 +111,66 @@ def main_consensus(argv):
     print(json.dumps(out))
 
 
+def main_haplotypes(argv):
+    cfg = argv[0] if argv else "C4"
+    n = int(argv[1]) if len(argv) > 1 else 60
+    runs = max(5, int(argv[2])) if len(argv) > 2 else 5
+    alternations = int(argv[3]) if len(argv) > 3 else 3
+    from hairsplitter_amd import synth
+    with tempfile.TemporaryDirectory() as td:
+        contigs, files = synth.generate_job(cfg, list(range(n)), workers=min(16, os.cpu_count() or 1), outdir=td)      # before the GPU is touched (forks)
+        from hairsplitter_amd import api
+        api.require_gpu()
+        pl = api.PipelineGroups(contigs, 4)
+        cv, sr = pl.run_fused(0.33, 0, rarest_strain_abundance=0.01)
+        have = hasattr(api, "polish_haplotypes")
+
+        def composed():
+            res = api.polish_inputs(pl, sr)
+            return res, api.polish_consensus(res)
+
+        def timed(call):
+            walls, waits, last = [], [], None
+            for i in range(runs + 1):
+                w0 = api.host_waits()
+                t0 = time.perf_counter()
+                last = call()
+                if i:      # the first call is the warm-up
+                    walls.append(time.perf_counter() - t0)
+                    waits.append(api.host_waits() - w0)
+            return statistics.median(walls) * 1e3, waits[-1], last
+        legs = {"haplotypes": [], "composed": []}
+        for _ in range(alternations):      # (the composition first: it is what a build without the new call times, in the same place of its process)
+            ms, waits_b, (res, cons) = timed(composed)
+            legs["composed"].append(ms)
+            if have:
+                ms, waits_a, hap = timed(lambda: api.polish_haplotypes(pl, sr))
+                legs["haplotypes"].append(ms)
+        pl.close()
+    cig_words, bases, bb = int(res["cig_off"][-1]), int(res["base_off"][-1]), int(res["backbone_off"][-1])
+    text = int(cons["cons_off"][-1])
+    out = {"mode": "haplotypes", "config": cfg, "contigs": n, "runs": runs, "bundles": res["n_bundles"], "pieces": res["n_pieces"],
+           "composed_wall_ms_medians": legs["composed"], "composed_host_waits_per_call": waits_b,
+           # (what the two calls move: the pieces down and up again, the consensus route's tables up, the text and the bundles' figures down)
+           "composed_bytes_down": bases + bb + 4 * cig_words + text + 32 * res["n_bundles"], "composed_bytes_up": bases + bb + 4 * cig_words + 56 * res["n_pieces"]}
+    if have:
+        st = hap["stats"]
+        plan_bytes = 4 * cig_words + 40 * res["n_pieces"]      # CIGAR words in, 40 B a piece out
+        out.update({"haplotypes_wall_ms_medians": legs["haplotypes"], "haplotypes_host_waits_per_call": waits_a, "rounds": st["n_rounds"], "sub_rounds": st["n_sub_rounds"],
+                    "haplotypes_bytes_down": st["bytes_down"], "haplotypes_bytes_up": st["bytes_up"],
+                    "k_cons_plan_and_layout": {"ms": st["plan_ms"], "algorithmic_bytes": plan_bytes},
+                    "equal": bool(all((hap[k] == cons[k]).all() for k in ("cons_off", "cons", "trim_start", "trim_end", "n_sub", "n_del", "n_ins_bases", "n_low", "n_skipped")))})
+        if st["plan_ms"] > 0:
+            gbs = plan_bytes / (st["plan_ms"] * 1e-3) / 1e9
+            out["k_cons_plan_and_layout"].update({"GBs": gbs, "frac_of_hbm_peak": gbs / HBM_PEAK_GBS})
+    print(json.dumps(out))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "consensus":
         return main_consensus(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "haplotypes":
+        return main_haplotypes(sys.argv[2:])
     cfg = sys.argv[1] if len(sys.argv) > 1 else "C4"
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     runs = max(5, int(sys.argv[3])) if len(sys.argv) > 3 else 5
