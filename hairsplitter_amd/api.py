@@ -30,6 +30,8 @@ SYMBOLS = [
     "hs_polish_inputs", "hs_polish_inputs_from_files", "hs_polish_result_destroy", "hs_polish_inputs_main",
     "hs_consensus_default_params", "hs_polish_consensus", "hs_polish_consensus_arrays", "hs_polish_consensus_host", "hs_consensus_result_destroy",
     "hs_polish_haplotypes", "hs_polish_haplotypes_from_files", "hs_haplotypes_result_destroy", "hs_polish_consensus_planned_tap",
+    "hs_polish_refine_plan_host", "hs_refine_plan_destroy", "hs_polish_haplotypes_refined", "hs_polish_refine_arrays", "hs_polish_haplotypes_refined_from_files",
+    "hs_refined_result_destroy",
     "hs_moves_to_cigar", "hs_realign_intervals", "hs_realign_records_destroy", "hs_cv_batch_create_paf", "hs_cv_batch_create_sam",
     "hs_allele_table_destroy", "hs_alleles_text", "hs_alleles_lds_capacity", "hs_group_alleles_layout", "hs_group_alleles", "hs_haplotype_alleles", "hs_pipeline_alleles",
     "hs_recruit_params_default", "hs_recruit_table_destroy", "hs_recruit_reads", "hs_group_recruit_layout", "hs_group_recruit", "hs_recruit_apply", "hs_recruit_text",
@@ -1901,10 +1903,12 @@ class HaplotypesResult(C.Structure):
 
 
 def polish_haplotypes(batch_or_pipeline, sr: Dict, polish_everything: bool = False, c0: int = 0, c1: Optional[int] = None, contig_has_snps=None,
-                      params: Optional[ConsensusParams] = None) -> Dict:
+                      params: Optional[ConsensusParams] = None, passes: int = 1) -> Dict:
     """polish_consensus(polish_inputs(...)) in one call (hs_polish_haplotypes): the arguments of polish_inputs and the consensus parameters. One
     dict: the metadata keys of polish_inputs (everything but backbone, bases and cigar, which stay on the device), the keys of polish_consensus,
-    and "stats" = those of both, n_rounds (resident rounds), n_sub_rounds (consensus rounds), bytes_down, bytes_up and plan_ms."""
+    and "stats" = those of both, n_rounds (resident rounds), n_sub_rounds (consensus rounds), bytes_down, bytes_up and plan_ms.
+    passes > 1 (hs_polish_haplotypes_refined): every piece is realigned to the consensus of the pass before and the vote is taken again, on the device;
+    the consensus keys are the last pass's and "passes" holds the per-pass figures (see polish_refine). passes == 1 calls the one-pass entry."""
     batch = getattr(batch_or_pipeline, "batch", batch_or_pipeline)
     lib = load()
     win_off = _np(sr["win_off"], np.int64); win_start = _np(sr["win_start"], np.int32); win_end = _np(sr["win_end"], np.int32)
@@ -1918,12 +1922,21 @@ def polish_haplotypes(batch_or_pipeline, sr: Dict, polish_everything: bool = Fal
     def ptr(a):
         return a.ctypes.data_as(C.c_void_p)
     res = C.POINTER(HaplotypesResult)()
+    refined = C.POINTER(RefinedResult)()
     lib.hs_polish_haplotypes.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.POINTER(ConsensusParams), C.POINTER(C.POINTER(HaplotypesResult))]
     lib.hs_haplotypes_result_destroy.argtypes = [C.c_void_p]
     lib.hs_haplotypes_result_destroy.restype = None
-    _check(lib.hs_polish_haplotypes(batch.handle, C.c_int32(c0), C.c_int32(c1), ptr(win_off), ptr(win_start), ptr(win_end), ptr(label_off), ptr(labels),
-                                    None if has is None else ptr(has), C.c_int32(1 if polish_everything else 0), None if params is None else C.byref(params),
-                                    C.byref(res)))
+    lib.hs_refined_result_destroy.argtypes = [C.c_void_p]
+    lib.hs_refined_result_destroy.restype = None
+    args = [batch.handle, C.c_int32(c0), C.c_int32(c1), ptr(win_off), ptr(win_start), ptr(win_end), ptr(label_off), ptr(labels),
+            None if has is None else ptr(has), C.c_int32(1 if polish_everything else 0), None if params is None else C.byref(params)]
+    if passes == 1:
+        _check(lib.hs_polish_haplotypes(*(args + [C.byref(res)])))
+    else:
+        lib.hs_polish_haplotypes_refined.argtypes = ([C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 +
+                                                     [C.c_int32, C.POINTER(ConsensusParams), C.c_int32, C.POINTER(C.POINTER(RefinedResult))])
+        _check(lib.hs_polish_haplotypes_refined(*(args + [C.c_int32(int(passes)), C.byref(refined)])))
+        res = refined.contents.last
     try:
         r = res.contents
         out = _polish_result_dict(r.inputs.contents, False)
@@ -1932,8 +1945,108 @@ def polish_haplotypes(batch_or_pipeline, sr: Dict, polish_everything: bool = Fal
         out.update(cons)
         stats.update({"n_rounds": int(r.n_rounds), "n_sub_rounds": int(r.n_sub_rounds), "bytes_down": int(r.bytes_down), "bytes_up": int(r.bytes_up), "plan_ms": r.t_plan_ms})
         out["stats"] = stats
+        if refined:
+            out["passes"] = _refined_passes_dict(refined.contents)
     finally:
-        lib.hs_haplotypes_result_destroy(res)
+        if refined:
+            lib.hs_refined_result_destroy(refined)
+        else:
+            lib.hs_haplotypes_result_destroy(res)
+    return out
+
+
+# ---- polishing passes: pieces realigned to the consensus of the pass before, then the vote again (the rule: csrc/hs_refine_host.h) ----
+REFINE_MAX_PASSES = 8
+_REFINE_I64 = ("n_sub", "n_del", "n_ins_bases", "n_low", "n_skipped", "n_pairs", "n_unaligned", "sum_dist", "move_bytes", "cigar_words")
+_REFINE_MS = ("t_windows_ms", "t_align_ms", "t_cigar_ms", "t_plan_ms", "t_consensus_ms")
+
+
+class RefinedResult(C.Structure):
+    _fields_ = ([("last", C.POINTER(HaplotypesResult)), ("n_passes", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_int64 * REFINE_MAX_PASSES) for k in _REFINE_I64] +
+                [(k, C.c_double * REFINE_MAX_PASSES) for k in _REFINE_MS] + [("n_waits", C.c_int64 * REFINE_MAX_PASSES)])
+
+
+class RefinePlan(C.Structure):
+    _fields_ = [("consensus", C.POINTER(ConsensusResult)), ("n_bundles", C.c_int64), ("n_pieces", C.c_int64), ("col_off", C.POINTER(C.c_int64)),
+                ("col_begin", C.POINTER(C.c_int32)), ("col_ins", C.POINTER(C.c_int32)), ("win_start", C.POINTER(C.c_int64)), ("win_end", C.POINTER(C.c_int64))]
+
+
+def _refined_passes_dict(r) -> Dict:
+    n = int(r.n_passes)
+    out = {"n_passes": n}
+    for k in _REFINE_I64 + ("n_waits",):
+        out[k] = np.array(list(getattr(r, k))[:n], np.int64)
+    for k in _REFINE_MS:
+        out[k[2:]] = np.array(list(getattr(r, k))[:n], np.float64)
+    return out
+
+
+def _consensus_arrays_args(who: str, res: Dict):
+    a64 = [_np(res[k], np.int64) for k in ("backbone_off", "piece_off", "base_off", "cig_off")]
+    a32 = [_np(res[k], np.int32) for k in ("bundle_overhang_left", "bundle_overhang_right", "piece_sam_pos", "piece_flags")]
+    backbone, bases, cigar = _np(res["backbone"], np.uint8), _np(res["bases"], np.uint8), _np(res["cigar"], np.uint32)
+    B = len(a64[0]) - 1
+    if B < 0 or len(a64[1]) != B + 1 or len(a32[0]) != B or len(a32[1]) != B:
+        raise HsError(who + ": the bundle arrays do not agree")
+    P = int(a64[1][-1])
+    if len(a64[2]) != P + 1 or len(a64[3]) != P + 1 or len(a32[2]) != P or len(a32[3]) != P:
+        raise HsError(who + ": the piece arrays do not agree")
+    if len(backbone) < int(a64[0][-1]) or len(bases) < int(a64[2][-1]) or len(cigar) < int(a64[3][-1]):
+        raise HsError(who + ": the offsets run beyond the arrays")
+    keep = a64 + a32 + [backbone, bases, cigar]
+
+    def ptr(a):
+        return a.ctypes.data_as(C.c_void_p)
+    args = [C.c_int64(B), ptr(a64[0]), ptr(backbone), ptr(a32[0]), ptr(a32[1]), ptr(a64[1]), ptr(a32[2]), ptr(a32[3]), ptr(a64[2]), ptr(bases), ptr(a64[3]), ptr(cigar)]
+    return B, P, args, keep
+
+
+def polish_refine(res: Dict, params: Optional[ConsensusParams] = None, passes: int = 2) -> Dict:
+    """`passes` polishing passes over the bundles of `res` (the arrays polish_consensus takes) on the device (hs_polish_refine_arrays): the arrays go up
+    whole, every pass from the second on realigns each piece to its window of the consensus just made (A1, NW with path) and votes again with that
+    consensus as the backbone. Returns the keys of polish_consensus for the LAST pass and "passes": n_passes and, per pass, n_sub, n_del, n_ins_bases,
+    n_low, n_skipped (sums over the bundles, each against that pass's backbone), n_pairs, n_unaligned, sum_dist, move_bytes, cigar_words (0 for pass 1),
+    windows_ms, align_ms, cigar_ms, plan_ms, consensus_ms and n_waits."""
+    lib = load()
+    B, P, args, keep = _consensus_arrays_args("polish_refine", res)
+    fn = lib.hs_polish_refine_arrays
+    fn.argtypes = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams), C.c_int32, C.POINTER(C.POINTER(RefinedResult))]
+    lib.hs_refined_result_destroy.argtypes = [C.c_void_p]
+    lib.hs_refined_result_destroy.restype = None
+    out_p = C.POINTER(RefinedResult)()
+    _check(fn(*(args + [None if params is None else C.byref(params), C.c_int32(int(passes)), C.byref(out_p)])))
+    try:
+        r = out_p.contents
+        h = r.last.contents
+        out = _consensus_result_dict(h.consensus.contents, B)
+        out["stats"].update({"n_sub_rounds": int(h.n_sub_rounds), "bytes_down": int(h.bytes_down), "bytes_up": int(h.bytes_up), "plan_ms": h.t_plan_ms})
+        out["passes"] = _refined_passes_dict(r)
+    finally:
+        lib.hs_refined_result_destroy(out_p)
+    return out
+
+
+def polish_refine_plan_host(res: Dict, params: Optional[ConsensusParams] = None) -> Dict:
+    """One pass on the host and what the next pass needs of it (hs_polish_refine_plan_host, no device): the keys of polish_consensus(form="host"), then
+    col_off [n_bundles + 1], col_begin and col_ins (L + 1 per bundle: where column t begins in the bundle's consensus, the inserted bases in front of
+    it) and per piece win_start / win_end, its window in its bundle's consensus (-1 / -1: none)."""
+    lib = load()
+    B, P, args, keep = _consensus_arrays_args("polish_refine_plan_host", res)
+    fn = lib.hs_polish_refine_plan_host
+    fn.argtypes = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams), C.POINTER(C.POINTER(RefinePlan))]
+    lib.hs_refine_plan_destroy.argtypes = [C.c_void_p]
+    lib.hs_refine_plan_destroy.restype = None
+    out_p = C.POINTER(RefinePlan)()
+    _check(fn(*(args + [None if params is None else C.byref(params), C.byref(out_p)])))
+    try:
+        r = out_p.contents
+        out = _consensus_result_dict(r.consensus.contents, B)
+        out["col_off"] = _c_array(r.col_off, B + 1, np.int64)
+        n = int(out["col_off"][-1])
+        out["col_begin"] = _c_array(r.col_begin, n, np.int32); out["col_ins"] = _c_array(r.col_ins, n, np.int32)
+        out["win_start"] = _c_array(r.win_start, P, np.int64); out["win_end"] = _c_array(r.win_end, P, np.int64)
+    finally:
+        lib.hs_refine_plan_destroy(out_p)
     return out
 
 
@@ -1949,10 +2062,15 @@ def haplotype_fasta_header(res: Dict, i: int, contig_name: Optional[str] = None)
 
 
 def polish_haplotypes_from_files(gfa: str, reads: str, sam: str, gro: str, out_fasta: str, polish_everything: bool = False, params: Optional[ConsensusParams] = None,
-                                 n_threads: int = 1) -> None:
+                                 n_threads: int = 1, passes: int = 1) -> None:
     """The same from the four files HS_create_new_contigs reads, written as FASTA: a record ">contig_start_end_group" per bundle, its trimmed consensus
     on one line (hs_polish_haplotypes_from_files; what bin/hs_polish_inputs writes under HS_HAPLOTYPES=1)."""
     lib = load()
+    if passes != 1:      # (hs_polish_haplotypes_refined_from_files; what HS_POLISH_PASSES asks of bin/hs_polish_inputs)
+        lib.hs_polish_haplotypes_refined_from_files.argtypes = [C.c_char_p] * 4 + [C.c_int32, C.POINTER(ConsensusParams), C.c_int32, C.c_char_p, C.c_int32]
+        _check(lib.hs_polish_haplotypes_refined_from_files(gfa.encode(), reads.encode(), sam.encode(), gro.encode(), C.c_int32(1 if polish_everything else 0),
+                                                           None if params is None else C.byref(params), C.c_int32(int(passes)), out_fasta.encode(), C.c_int32(n_threads)))
+        return
     lib.hs_polish_haplotypes_from_files.argtypes = [C.c_char_p] * 4 + [C.c_int32, C.POINTER(ConsensusParams), C.c_char_p, C.c_int32]
     _check(lib.hs_polish_haplotypes_from_files(gfa.encode(), reads.encode(), sam.encode(), gro.encode(), C.c_int32(1 if polish_everything else 0),
                                                None if params is None else C.byref(params), out_fasta.encode(), C.c_int32(n_threads)))

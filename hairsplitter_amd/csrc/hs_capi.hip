@@ -10,6 +10,8 @@
 //   hs_capi_multi.inc    several GPUs in one process
 //   hs_capi_polish.inc   the polisher's inputs of the next stage (hs_polish_inputs)
 //   hs_capi_consensus.inc the consensus of every bundle of those inputs: a vote per column and per insertion slot (hs_polish_consensus)
+//   hs_capi_refine.inc    polishing passes inside a consensus sub-round: pieces realigned to the consensus, then the vote again (hs_polish_haplotypes_refined);
+//                         behind hs_capi_realign.inc, whose moves -> words route it takes
 //   hs_capi_realign.inc  the CIGAR-less input in memory: intervals -> CIGAR words on the device -> a batch (hs_realign_intervals)
 //   hs_capi_map.inc      the read mapper in front of it: minimizer index of the contigs, seeds and a diagonal vote per read (hs_map_reads)
 // There is no CPU fallback anywhere in this file: without a usable HIP device every entry
@@ -49,6 +51,7 @@
 #include "hs_kernels_loopa.hip"
 #include "hs_kernels_polish.hip"
 #include "hs_kernels_consensus.hip"
+#include "hs_kernels_refine.hip"
 #include "hs_kernels_realign.hip"
 #include "hs_kernels_alleles.hip"
 #include "hs_kernels_recruit.hip"
@@ -81,4 +84,5 @@ using hs::set_error;
 #include "hs_capi_polish.inc"
 #include "hs_capi_consensus.inc"
 #include "hs_capi_realign.inc"
+#include "hs_capi_refine.inc"
 #include "hs_capi_map.inc"

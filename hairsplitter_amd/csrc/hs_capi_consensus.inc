@@ -43,9 +43,19 @@ struct ConsRound {
     int64_t np, nb, n_tiles, rb /* row bytes */, n_rec, C /* columns */, n_base, n_cig;
 };
 
-// from k_cons_rows to "the round into the result": two host waits
+// what a round leaves on the device for a caller that goes on with it (the polishing passes, hs_capi_refine.inc): its two work blocks and, inside
+// them, the text, the decided columns, the winning slots and their lengths, the text offset of every column and of every bundle
+struct ConsKeep {
+    DBuf work, work2;
+    const uint8_t* text = nullptr; const uint8_t* col = nullptr; const int64_t* slot_index = nullptr; const int32_t* ins_len = nullptr; const int64_t* out_off = nullptr;
+    const int64_t* cons_off = nullptr;
+    int64_t n_slots = 0, text_cap = 0;
+};
+
+// from k_cons_rows to "the round into the result": two host waits. keep (null: as ever): the text stays on the device and the blocks go to *keep; the
+// bundles' offsets and figures come down as ever and H grows by them, not by text
 int consensus_round_body(const char* who, const ConsRound& r, const hs_consensus_params& prm, hipStream_t st, KernelClock& kc, double t_ms[4], hs::ConsensusHost& H,
-                         BytesMoved* moved = nullptr) {
+                         BytesMoved* moved = nullptr, ConsKeep* keep = nullptr) {
     using namespace hsdev;
     const int64_t np = r.np, nb = r.nb, rb = r.rb, n_rec = r.n_rec, C = r.C;
     DBuf d_work, d_work2;
@@ -102,11 +112,11 @@ int consensus_round_body(const char* who, const ConsRound& r, const hs_consensus
             HS_HIP(hipGetLastError());
             return HS_OK; })) return rc;
     HBuf h_text, h_off, h_v;
-    if (int rc = h_text.alloc((size_t)text_cap + 16)) return rc;
+    if (!keep) { if (int rc = h_text.alloc((size_t)text_cap + 16)) return rc; }
     if (int rc = h_off.alloc((size_t)(nb + 1) * 8 + 16)) return rc;
     if (int rc = h_v.alloc((size_t)(6 * nb) * 4 + 16)) return rc;
     Shipment sh2;
-    if (text_cap > 0) sh2.add_counted(h_text.p, text, (const long long*)(out_off + C), 1, (long long)text_cap);
+    if (text_cap > 0 && !keep) sh2.add_counted(h_text.p, text, (const long long*)(out_off + C), 1, (long long)text_cap);
     sh2.add(h_off.p, d_cons_off, (size_t)(nb + 1) * 8);
     sh2.add(h_v.p, d_v, (size_t)(6 * nb) * 4);
     if (int rc = sh2.launch(st)) return rc;
@@ -120,13 +130,18 @@ int consensus_round_body(const char* who, const ConsRound& r, const hs_consensus
     for (int64_t k = 0; ok && k < nb; ++k) ok = co[k + 1] >= co[k];
     if (!ok) { set_error(std::string(who) + ": the device's consensus offsets do not fit the columns"); return HS_EHIP; }
     const int64_t at = (int64_t)H.cons.size();
-    H.cons.insert(H.cons.end(), (const uint8_t*)h_text.p, (const uint8_t*)h_text.p + co[nb]);
+    if (!keep) H.cons.insert(H.cons.end(), (const uint8_t*)h_text.p, (const uint8_t*)h_text.p + co[nb]);
     for (int64_t k = 0; k < nb; ++k) H.cons_off.push_back(at + co[k + 1]);
     const int32_t* v = (const int32_t*)h_v.p;
     std::vector<int32_t>* f[6] = {&H.trim_start, &H.trim_end, &H.n_sub, &H.n_del, &H.n_ins_bases, &H.n_low};
     for (int j = 0; j < 6; ++j) f[j]->insert(f[j]->end(), v + j * nb, v + (j + 1) * nb);
     H.n_ins_records += n_rec; H.n_ins_slots += W;
-    if (moved) moved->down += 16 + co[nb] + (nb + 1) * 8 + 6 * nb * 4;
+    if (moved) moved->down += 16 + (keep ? 0 : co[nb]) + (nb + 1) * 8 + 6 * nb * 4;
+    if (keep) {
+        keep->text = text; keep->col = col; keep->slot_index = slot_index; keep->ins_len = ins_len; keep->out_off = out_off; keep->cons_off = d_cons_off;
+        keep->n_slots = W; keep->text_cap = text_cap;
+        keep->work.take(d_work); keep->work2.take(d_work2);
+    }
     return HS_OK;
 }
 
@@ -227,8 +242,19 @@ int consensus_device(const char* who, const ConsInput& given, const hs_consensus
 // Then sub-rounds of whole bundles within HS_CONSENSUS_CHUNK_MB, by the rule of consensus_device, through consensus_round_body (two waits each).
 // H grows by the range's bundles (n_skipped included). plan_out (may be null): [4 * pieces of the range].
 struct ConsResidentStats { int64_t n_sub_rounds = 0; double t_plan_ms = 0; double t_ms[4] = {0, 0, 0, 0}; BytesMoved moved; };
+// the polishing passes of a sub-round (hs_capi_refine.inc, behind hs_capi_realign.inc: it takes the moves -> words route from there)
+struct RefineStats;
+struct RefineSubRound {
+    const hsdev::ConsPiece* d_src; const hsdev::ConsPiece* h_src; int64_t bundle_shift;      // the sub-round's pieces as k_cons_plan read them, on the device and on the host
+    const std::vector<hsdev::ConsBundle>* bundles; const int32_t* n_skipped; int32_t* n_skipped_out;      // its bundles; pass 1's skipped pieces; where the last pass's go
+    const uint8_t* d_bases; int64_t n_base;
+};
+int refine_sub_round(const char* who, const ConsRound& first, const RefineSubRound& sr, const hs_consensus_params& prm, hipStream_t st, KernelClock& kc, int32_t n_passes,
+                     hs::ConsensusHost& H, ConsResidentStats& stats, RefineStats& rs);
+// refine (null: one pass, as ever) / n_passes: the passes of every sub-round and where their figures go
 int consensus_resident(const char* who, const ConsInput& in, int64_t b0, int64_t b1, const uint8_t* d_bases, const uint32_t* d_cig, const uint8_t* d_bb,
-                       const hs_consensus_params& prm, hipStream_t st, hs::ConsensusHost& H, ConsResidentStats& stats, int32_t* plan_out) {
+                       const hs_consensus_params& prm, hipStream_t st, hs::ConsensusHost& H, ConsResidentStats& stats, int32_t* plan_out, RefineStats* refine = nullptr,
+                       int32_t n_passes = 1) {
     using namespace hsdev;
     const int64_t nb = b1 - b0, p0 = in.piece_off[b0], p1 = in.piece_off[b1], np = p1 - p0;
     if (nb <= 0) return HS_OK;
@@ -315,6 +341,7 @@ int consensus_resident(const char* who, const ConsInput& in, int64_t b0, int64_t
         }
     }
     for (int64_t k = 0; k < nb; ++k) H.n_skipped.push_back(bskip[k]);
+    const size_t skipped_at = H.n_skipped.size() - (size_t)nb;
 
     // ---- sub-rounds of whole bundles
     for (int64_t s0 = 0; s0 < nb;) {
@@ -350,7 +377,10 @@ int consensus_resident(const char* who, const ConsInput& in, int64_t b0, int64_t
                 return HS_OK; })) return rc;
         const ConsRound round{d_bases + sbase0, d_cig + scig0, d_bb + col0, d_sp.as<ConsPiece>(), d_sb.as<ConsBundle>(), d_tiles.as<ConsTile>(),
                               nq, s1 - s0, (int64_t)tiles.size(), rb, n_rec, C, sbase1 - sbase0, scig1 - scig0};
-        if (int rc = consensus_round_body(who, round, prm, st, kc, stats.t_ms, H, &stats.moved)) return rc;
+        if (refine && n_passes > 1) {
+            const RefineSubRound sr{d_pieces.as<ConsPiece>() + q0, pieces.data() + q0, s0, &sb, bskip + s0, H.n_skipped.data() + skipped_at + s0, d_bases + sbase0, sbase1 - sbase0};
+            if (int rc = refine_sub_round(who, round, sr, prm, st, kc, n_passes, H, stats, *refine)) return rc;
+        } else if (int rc = consensus_round_body(who, round, prm, st, kc, stats.t_ms, H, &stats.moved)) return rc;
         { float ms = 0; if (ev_lay.ms(&ms) == HS_OK) stats.t_plan_ms += ms; }
         s0 = s1;
     }
@@ -385,14 +415,14 @@ int consensus_planned_tap(const char* who, const ConsInput& given, const hs_cons
 
 // ---- from labels to haplotype sequences: hs_polish_inputs' rounds with the consensus as their sink
 int haplotypes_core(const char* who, hs_cv_batch* b, int c0, int c1, const std::vector<std::vector<hs::LabelledInterval>>& ivs, const std::vector<uint8_t>& has,
-                    bool polish_everything, const hs_consensus_params& prm, BytesMoved moved, hs_haplotypes_result** out) {
+                    bool polish_everything, const hs_consensus_params& prm, BytesMoved moved, hs_haplotypes_result** out, RefineStats* refine = nullptr, int32_t n_passes = 1) {
     hs::ConsensusHost H;
     H.cons_off.assign(1, 0);
     ConsResidentStats stats;
     stats.moved = moved;
     const PolishSink sink = [&](const PolishRound& r) -> int {
         const ConsInput in{r.b1, r.backbone_off, nullptr, r.ovl, r.ovr, r.piece_off, r.sam, r.flags, r.base_off, nullptr, r.cig_off, nullptr};
-        return consensus_resident(who, in, r.b0, r.b1, r.d_bases, r.d_cig, r.d_bb, prm, r.st, H, stats, nullptr);
+        return consensus_resident(who, in, r.b0, r.b1, r.d_bases, r.d_cig, r.d_bb, prm, r.st, H, stats, nullptr, refine, n_passes);
     };
     hs_polish_result* inputs = nullptr;
     if (int rc = polish_inputs_core(b, c0, c1, ivs, has, polish_everything, &inputs, &sink, &stats.moved)) return rc;
@@ -438,12 +468,14 @@ int hs_polish_haplotypes(hs_cv_batch* b, int32_t c0, int32_t c1, const int64_t* 
     } catch (const std::exception& e) { set_error(std::string("hs_polish_haplotypes: ") + e.what()); return HS_EINVAL; }
 }
 
-int hs_polish_haplotypes_from_files(const char* gfa, const char* reads, const char* sam, const char* gro, int32_t polish_everything, const hs_consensus_params* params,
-                                    const char* out_fasta, int32_t n_threads) {
+// the one body of hs_polish_haplotypes_from_files and hs_polish_haplotypes_refined_from_files (refine null: one pass)
+static int haplotypes_files(const char* who_c, const char* gfa, const char* reads, const char* sam, const char* gro, int32_t polish_everything, const hs_consensus_params* params,
+                            const char* out_fasta, int32_t n_threads, RefineStats* refine, int32_t n_passes) {
+    const std::string who(who_c);
     if (int rc = require_device()) return rc;
-    if (!gfa || !reads || !sam || !gro || !out_fasta) { set_error("hs_polish_haplotypes_from_files: null path"); return HS_EINVAL; }
+    if (!gfa || !reads || !sam || !gro || !out_fasta) { set_error(who + ": null path"); return HS_EINVAL; }
     const hs_consensus_params prm = params ? *params : hs_consensus_default_params();
-    if (!hs::consensus_params_valid(prm)) { set_error("hs_polish_haplotypes_from_files: parameters out of range (min_cov >= 1, max_ins 1..64)"); return HS_EINVAL; }
+    if (!hs::consensus_params_valid(prm)) { set_error(who + ": parameters out of range (min_cov >= 1, max_ins 1..64)"); return HS_EINVAL; }
     try {
         hs::CvFileInput in;
         if (int rc = hs::load_cv_inputs(gfa, reads, sam, false, in, n_threads < 1 ? 1 : n_threads)) return rc;
@@ -457,7 +489,7 @@ int hs_polish_haplotypes_from_files(const char* gfa, const char* reads, const ch
             return rc;
         std::unique_ptr<hs_cv_batch, void (*)(hs_cv_batch*)> bguard(b, hs_cv_batch_destroy);
         hs_haplotypes_result* r = nullptr;
-        if (int rc = haplotypes_core("hs_polish_haplotypes_from_files", b, 0, n_contigs, ivs, has, polish_everything != 0, prm, BytesMoved(), &r)) return rc;
+        if (int rc = haplotypes_core(who_c, b, 0, n_contigs, ivs, has, polish_everything != 0, prm, BytesMoved(), &r, refine, n_passes)) return rc;
         std::unique_ptr<hs_haplotypes_result, void (*)(hs_haplotypes_result*)> rguard(r, hs_haplotypes_result_destroy);
         std::FILE* f = std::fopen(out_fasta, "wb");
         if (!f) { set_error(std::string("cannot write ") + out_fasta); return HS_EIO; }
@@ -474,7 +506,12 @@ int hs_polish_haplotypes_from_files(const char* gfa, const char* reads, const ch
         ok = std::fclose(f) == 0 && ok;
         if (!ok) { set_error(std::string("short write on ") + out_fasta); return HS_EIO; }
         return HS_OK;
-    } catch (const std::exception& e) { set_error(std::string("hs_polish_haplotypes_from_files: ") + e.what()); return HS_EINVAL; }
+    } catch (const std::exception& e) { set_error(who + ": " + e.what()); return HS_EINVAL; }
+}
+
+int hs_polish_haplotypes_from_files(const char* gfa, const char* reads, const char* sam, const char* gro, int32_t polish_everything, const hs_consensus_params* params,
+                                    const char* out_fasta, int32_t n_threads) {
+    return haplotypes_files("hs_polish_haplotypes_from_files", gfa, reads, sam, gro, polish_everything, params, out_fasta, n_threads, nullptr, 1);
 }
 
 int hs_polish_consensus_planned_tap(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left, const int32_t* overhang_right,

@@ -367,7 +367,16 @@ int hs_polish_inputs_from_files(const char* gfa, const char* reads, const char* 
     if (!gfa || !reads || !sam || !gro || !out_path) { set_error("hs_polish_inputs_from_files: null path"); return HS_EINVAL; }
     // HS_HAPLOTYPES=1: the FASTA of hs_polish_haplotypes_from_files (the default parameters) in place of the bundle text; it wins over HS_CONSENSUS=1
     const char* want_hap = std::getenv("HS_HAPLOTYPES");
-    if (want_hap && want_hap[0] == '1') return hs_polish_haplotypes_from_files(gfa, reads, sam, gro, polish_everything, nullptr, out_path, n_threads);
+    if (want_hap && want_hap[0] == '1') {
+        // HS_POLISH_PASSES=<n>: that many passes (hs_polish_haplotypes_refined); unset or 1: the one-pass call; anything else is refused there by name
+        const char* passes = std::getenv("HS_POLISH_PASSES");
+        if (passes && passes[0] && std::strcmp(passes, "1") != 0) {
+            char* end = nullptr;
+            const long n = std::strtol(passes, &end, 10);
+            return hs_polish_haplotypes_refined_from_files(gfa, reads, sam, gro, polish_everything, nullptr, end && *end == 0 && n >= -1 && n <= 1000 ? (int32_t)n : -1, out_path, n_threads);
+        }
+        return hs_polish_haplotypes_from_files(gfa, reads, sam, gro, polish_everything, nullptr, out_path, n_threads);
+    }
     try {
         hs::CvFileInput in;
         if (int rc = hs::load_cv_inputs(gfa, reads, sam, false, in, n_threads < 1 ? 1 : n_threads)) return rc;

@@ -34,7 +34,7 @@ int consensus_check(int64_t n_bundles, const int64_t* backbone_off, const uint8_
 
 namespace {
 
-struct BundleOut { std::vector<uint8_t> text; int32_t v[7]; int64_t n_rec, n_slots; bool long_cigar; };
+struct BundleOut { std::vector<uint8_t> text; int32_t v[7]; int64_t n_rec, n_slots; bool long_cigar; bool want_cols = false; std::vector<int32_t> col_begin, col_ins; };
 
 // one bundle, by the rule: the walk of every piece into per-column counters and per-slot lists of insertions, then the decisions
 void consensus_bundle(int64_t L, const uint8_t* B, int32_t ovl, int32_t ovr, int64_t p0, int64_t p1, const int32_t* sam, const int32_t* flags, const int64_t* base_off,
@@ -86,14 +86,17 @@ void consensus_bundle(int64_t L, const uint8_t* B, int32_t ovl, int32_t ovr, int
     const int64_t c_start = std::min<int64_t>(ovl, L), c_end = L - std::min<int64_t>(ovr, L);
     int32_t trim_start = 0, trim_end = 0;
     o.text.clear();
+    if (o.want_cols) { o.col_begin.assign((size_t)L + 1, 0); o.col_ins.assign((size_t)L + 1, 0); }
     for (int64_t t = 0; t < L; ++t) {
         if (t == c_start) trim_start = (int32_t)o.text.size();
         if (t == c_end) trim_end = (int32_t)o.text.size();
+        if (o.want_cols) o.col_begin[(size_t)t] = (int32_t)o.text.size();
         if (slot_index[(size_t)t] >= 0) {
             const uint32_t* tb = &tab[(size_t)slot_index[(size_t)t] * W];
             const int32_t l = cons_ins_length(tb, prm.max_ins);
             for (int32_t j = 0; j < l; ++j) o.text.push_back(cons_letter(cons_ins_base(tb, prm.max_ins, j)));
             n_ib += l;
+            if (o.want_cols) o.col_ins[(size_t)t] = l;
         }
         const uint8_t cb = cons_column_byte(&votes[(size_t)t * 5], B[t], prm.min_cov);
         const int w = cb & CONS_COL_CODE;
@@ -101,6 +104,7 @@ void consensus_bundle(int64_t L, const uint8_t* B, int32_t ovl, int32_t ovr, int
         else if (w == CONS_DEL) ++n_del;
         else { o.text.push_back(cons_letter(w)); if (cb & CONS_COL_SUB) ++n_sub; }
     }
+    if (o.want_cols) o.col_begin[(size_t)L] = (int32_t)o.text.size();
     if (c_start == L) trim_start = (int32_t)o.text.size();
     if (c_end == L) trim_end = (int32_t)o.text.size();
     const int32_t v[7] = {trim_start, trim_end, n_sub, n_del, n_ib, n_low, n_skipped};
@@ -113,9 +117,18 @@ void consensus_bundle(int64_t L, const uint8_t* B, int32_t ovl, int32_t ovr, int
 int consensus_host(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left, const int32_t* overhang_right,
                    const int64_t* piece_off, const int32_t* piece_sam_pos, const int32_t* piece_flags, const int64_t* base_off, const uint8_t* bases,
                    const int64_t* cig_off, const uint32_t* cigar, const hs_consensus_params& prm, int n_threads, ConsensusHost& out, std::string& err) {
+    return consensus_host_columns(n_bundles, backbone_off, backbone, overhang_left, overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar, prm,
+                                  n_threads, out, nullptr, err);
+}
+
+int consensus_host_columns(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left, const int32_t* overhang_right,
+                           const int64_t* piece_off, const int32_t* piece_sam_pos, const int32_t* piece_flags, const int64_t* base_off, const uint8_t* bases,
+                           const int64_t* cig_off, const uint32_t* cigar, const hs_consensus_params& prm, int n_threads, ConsensusHost& out, ConsensusColumns* cols,
+                           std::string& err) {
     if (int rc = consensus_check(n_bundles, backbone_off, backbone, overhang_left, overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar, prm, err))
         return rc;
     std::vector<BundleOut> bo((size_t)n_bundles);
+    if (cols) { *cols = ConsensusColumns(); cols->col_off.assign(1, 0); for (BundleOut& o : bo) o.want_cols = true; }
     n_threads = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, n_bundles));
     auto work = [&](int t) {
         for (int64_t b = t; b < n_bundles; b += n_threads)
@@ -138,6 +151,11 @@ int consensus_host(int64_t n_bundles, const int64_t* backbone_off, const uint8_t
         out.cons_off.push_back((int64_t)out.cons.size());
         for (int j = 0; j < 7; ++j) f[j]->push_back(o.v[j]);
         out.n_ins_records += o.n_rec; out.n_ins_slots += o.n_slots;
+        if (cols) {
+            cols->col_begin.insert(cols->col_begin.end(), o.col_begin.begin(), o.col_begin.end());
+            cols->col_ins.insert(cols->col_ins.end(), o.col_ins.begin(), o.col_ins.end());
+            cols->col_off.push_back((int64_t)cols->col_begin.size());
+        }
     }
     return HS_OK;
 }

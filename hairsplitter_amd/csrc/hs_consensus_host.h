@@ -121,6 +121,13 @@ int consensus_check(int64_t n_bundles, const int64_t* backbone_off, const uint8_
 int consensus_host(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left, const int32_t* overhang_right,
                    const int64_t* piece_off, const int32_t* piece_sam_pos, const int32_t* piece_flags, const int64_t* base_off, const uint8_t* bases,
                    const int64_t* cig_off, const uint32_t* cigar, const hs_consensus_params& prm, int n_threads, ConsensusHost& out, std::string& err);
+// the same call, handing out two figures per column t of every bundle, t in [0, L] (cols may be null; hs_refine_host.h reads them): col_begin[t], where
+// column t begins in the bundle's text (column L: its end), and col_ins[t], the inserted bases in front of column t. col_off[b]: where bundle b's L + 1 entries lie.
+struct ConsensusColumns { std::vector<int64_t> col_off; std::vector<int32_t> col_begin, col_ins; };
+int consensus_host_columns(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left, const int32_t* overhang_right,
+                           const int64_t* piece_off, const int32_t* piece_sam_pos, const int32_t* piece_flags, const int64_t* base_off, const uint8_t* bases,
+                           const int64_t* cig_off, const uint32_t* cigar, const hs_consensus_params& prm, int n_threads, ConsensusHost& out, ConsensusColumns* cols,
+                           std::string& err);
 // a ConsensusHost as the malloc'd result of the C ABI (nullptr: out of memory)
 hs_consensus_result* consensus_result_from_host(const ConsensusHost& h);
 

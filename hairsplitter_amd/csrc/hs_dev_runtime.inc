@@ -126,6 +126,7 @@ struct DBuf {
     }
     template <class T> int upload(const std::vector<T>& v);
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+    void take(DBuf& o) { release(); p = o.p; bytes = o.bytes; cap = o.cap; view = o.view; owner = o.owner; o.p = nullptr; o.view = false; }      // (the block changes hands)
 };
 
 // pinned host buffer (pooled) for large downloads

@@ -988,6 +988,60 @@ int hs_polish_consensus_planned_tap(int64_t n_bundles, const int64_t* backbone_o
                                     const uint32_t* cigar, const hs_consensus_params* params, int32_t* plan_out, hs_consensus_result** out);
 
 /* ------------------------------------------------------------------------------------------------
+ * Polishing passes (device work): what the reference gets from its second minimap2 run in front of racon (tools.cpp:317-...: the reads
+ * are mapped to the contig to polish once more before the consensus).  hs_polish_haplotypes votes once, on the CIGARs the reads were given
+ * against the CONTIG; where a haplotype has an indel inside a repeat every read's aligner may place the gap in another slot and no slot
+ * wins.  A pass p >= 2 cuts every piece's window out of the consensus pass p - 1 made, aligns the piece to it (A1: edlibAlign NW, PATH,
+ * k = -1), turns the moves into CIGAR words (the k_m2c_* kernels) and votes again with that consensus as the backbone.  The rule is
+ * OURS; it is stated once, in csrc/hs_refine_host.h.  Everything between the passes stays in device memory: per pass and
+ * consensus sub-round 16 bytes a piece come down (the windows: A1's launcher takes host offsets) and the bundles' offsets and counters;
+ * only the last pass's text does.  n_passes passes run, there is no early stop.  n_passes = 1 is hs_polish_haplotypes, untouched.
+ * Limits: a piece of more than 2^20 bases has no path (n_unaligned) and is skipped by the next pass; an A1 chunk (HS_REALIGN_CHUNK_MB)
+ * holds at most 2^31 - 256 pairs and 2^31 - 1 move bytes.
+ * ---------------------------------------------------------------------------------------------- */
+#define HS_REFINE_MAX_PASSES 8
+/* one pass on the host and what the next needs of it (no device): the consensus of hs_polish_consensus_host; per bundle b and column t in
+ * [0, L] at col_off[b] + t: col_begin, where column t begins in the bundle's consensus (in front of its slot's insertion; column L: its
+ * end), and col_ins, the inserted bases in front of column t; per piece its window [win_start, win_end) in its bundle's consensus
+ * (-1 / -1: no window -- a skipped piece, or one that covers no column). */
+typedef struct hs_refine_plan {
+    hs_consensus_result* consensus;
+    int64_t n_bundles, n_pieces;
+    int64_t* col_off;           /* [n_bundles + 1] */
+    int32_t *col_begin, *col_ins;
+    int64_t *win_start, *win_end;
+} hs_refine_plan;
+int hs_polish_refine_plan_host(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left,
+                               const int32_t* overhang_right, const int64_t* piece_off, const int32_t* piece_sam_pos, const int32_t* piece_flags,
+                               const int64_t* base_off, const uint8_t* bases, const int64_t* cig_off, const uint32_t* cigar,
+                               const hs_consensus_params* params, hs_refine_plan** out);
+void hs_refine_plan_destroy(hs_refine_plan* r);
+typedef struct hs_refined_result {
+    hs_haplotypes_result* last;   /* consensus: the last pass's; inputs as hs_polish_haplotypes (NULL from hs_polish_refine_arrays) */
+    int32_t n_passes, pad;
+    /* per pass (index p - 1), summed over the bundles, each against that pass's backbone: the convergence figures */
+    int64_t n_sub[HS_REFINE_MAX_PASSES], n_del[HS_REFINE_MAX_PASSES], n_ins_bases[HS_REFINE_MAX_PASSES], n_low[HS_REFINE_MAX_PASSES], n_skipped[HS_REFINE_MAX_PASSES];
+    /* per pass from 2 on ([0] is 0): aligned pairs, pairs without a path, the sum of their edit distances, moves, CIGAR words */
+    int64_t n_pairs[HS_REFINE_MAX_PASSES], n_unaligned[HS_REFINE_MAX_PASSES], sum_dist[HS_REFINE_MAX_PASSES], move_bytes[HS_REFINE_MAX_PASSES], cigar_words[HS_REFINE_MAX_PASSES];
+    /* per pass: windows + gather (HIP events), A1 (wall, it synchronises), moves -> words (wall), the plan and the consensus (HIP events) */
+    double t_windows_ms[HS_REFINE_MAX_PASSES], t_align_ms[HS_REFINE_MAX_PASSES], t_cigar_ms[HS_REFINE_MAX_PASSES], t_plan_ms[HS_REFINE_MAX_PASSES], t_consensus_ms[HS_REFINE_MAX_PASSES];
+    int64_t n_waits[HS_REFINE_MAX_PASSES];   /* host waits of the pass, over all rounds (pass 1: those of the one-pass call) */
+} hs_refined_result;
+/* the arguments of hs_polish_haplotypes, then the number of passes: below 1 or above HS_REFINE_MAX_PASSES is HS_EINVAL and named */
+int hs_polish_haplotypes_refined(hs_cv_batch* b, int32_t c0, int32_t c1, const int64_t* win_off, const int32_t* win_start, const int32_t* win_end,
+                                 const int64_t* label_off, const int32_t* labels, const uint8_t* contig_has_snps, int32_t polish_everything,
+                                 const hs_consensus_params* params, int32_t n_passes, hs_refined_result** out);
+/* the arrays of hs_polish_consensus_arrays, uploaded whole, then the resident route with passes (as hs_polish_consensus_planned_tap for one) */
+int hs_polish_refine_arrays(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left,
+                            const int32_t* overhang_right, const int64_t* piece_off, const int32_t* piece_sam_pos, const int32_t* piece_flags,
+                            const int64_t* base_off, const uint8_t* bases, const int64_t* cig_off, const uint32_t* cigar,
+                            const hs_consensus_params* params, int32_t n_passes, hs_refined_result** out);
+/* hs_polish_haplotypes_from_files with passes (HS_POLISH_PASSES of bin/hs_polish_inputs) */
+int hs_polish_haplotypes_refined_from_files(const char* gfa, const char* reads, const char* sam, const char* gro, int32_t polish_everything,
+                                            const hs_consensus_params* params, int32_t n_passes, const char* out_fasta, int32_t n_threads);
+void hs_refined_result_destroy(hs_refined_result* r);
+
+/* ------------------------------------------------------------------------------------------------
  * Upstream feeders of stage 3 that are plain text transforms (host code): the 300 kb cutter the orchestrator runs before the
  * reads are aligned (src/cut_gfa.py:33-66, hairsplitter.py:583) and the GFA -> FASTA converter (src/gfa2fa.cpp).
  * hs_cut_gfa_main: argv of cut_gfa.py (--assembly/-a, --length/-l, --output/-o); hs_gfa2fa_main: argv[1] = gfa, FASTA on

@@ -10,7 +10,11 @@ consensus: the consensus of the same job's bundles (hs_polish_consensus, DESIGN 
 the fraction of the HBM peak, the whole call, the host half on 16 threads on the same bundles, and how much of the backbones changed.
 haplotypes: from the labels to the haplotype sequences -- the whole call of polish_haplotypes and of polish_inputs followed by
 polish_consensus, alternating three times (median of `runs` calls after a warm-up each time); the own time of k_cons_plan + layout, its
-algorithmic bytes and fraction of the HBM peak; what either route moved. A build without hs_polish_haplotypes times the composition alone."""
+algorithmic bytes and fraction of the HBM peak; what either route moved. A build without hs_polish_haplotypes times the composition alone.
+       python tools/polish_bench.py refine [config=C4] [contigs=60] [runs=5] [alternations=3]
+refine: polishing passes -- polish_haplotypes with 1, 2 and 3 passes, alternating (median of `runs` calls after a warm-up each time):
+the whole call, per pass the time per phase, the waits and the change counters, what the call moved; the own time of k_refine_windows +
+k_refine_gather with its algorithmic bytes and fraction of the HBM peak, and A1's share of a pass. A build without the passes times one pass alone."""
 import json
 import os
 import statistics
@@ -166,7 +170,62 @@ def main_haplotypes(argv):
     print(json.dumps(out))
 
 
+def main_refine(argv):
+    cfg = argv[0] if argv else "C4"
+    n = int(argv[1]) if len(argv) > 1 else 60
+    runs = max(5, int(argv[2])) if len(argv) > 2 else 5
+    alternations = int(argv[3]) if len(argv) > 3 else 3
+    from hairsplitter_amd import synth
+    with tempfile.TemporaryDirectory() as td:
+        contigs, files = synth.generate_job(cfg, list(range(n)), workers=min(16, os.cpu_count() or 1), outdir=td)      # before the GPU is touched (forks)
+        from hairsplitter_amd import api
+        api.require_gpu()
+        pl = api.PipelineGroups(contigs, 4)
+        cv, sr = pl.run_fused(0.33, 0, rarest_strain_abundance=0.01)
+        have = hasattr(api, "polish_refine")
+
+        def timed(call):
+            walls, waits, last = [], [], None
+            for i in range(runs + 1):
+                w0 = api.host_waits()
+                t0 = time.perf_counter()
+                last = call()
+                if i:      # the first call is the warm-up
+                    walls.append(time.perf_counter() - t0)
+                    waits.append(api.host_waits() - w0)
+            return statistics.median(walls) * 1e3, waits[-1], last
+        legs = {p: [] for p in ((1, 2, 3) if have else (1,))}
+        waits, last = {}, {}
+        for _ in range(alternations):
+            for p in legs:
+                ms, waits[p], last[p] = timed((lambda: api.polish_haplotypes(pl, sr)) if p == 1 else (lambda p=p: api.polish_haplotypes(pl, sr, passes=p)))
+                legs[p].append(ms)
+        pl.close()
+    one = last[1]
+    out = {"mode": "refine", "config": cfg, "contigs": n, "runs": runs, "bundles": one["n_bundles"], "pieces": one["n_pieces"], "bases": int(one["base_off"][-1]),
+           "passes": {}}
+    for p in legs:
+        st = last[p]["stats"]
+        row = {"wall_ms_medians": legs[p], "host_waits_per_call": waits[p], "bytes_down": st["bytes_down"], "bytes_up": st["bytes_up"], "sub_rounds": st["n_sub_rounds"]}
+        if p > 1:
+            ps = last[p]["passes"]
+            row["per_pass"] = {k: [float(x) for x in ps[k]] for k in ps if k != "n_passes"}
+            gather_bytes = 2 * (2 * int(one["base_off"][-1])) + 16 * one["n_pieces"]      # queries and targets (about as long) read and written, the windows
+            ms = float(ps["windows_ms"][1])
+            row["k_refine_windows_and_gather"] = {"ms": ms, "algorithmic_bytes": gather_bytes}
+            if ms > 0:
+                gbs = gather_bytes / (ms * 1e-3) / 1e9
+                row["k_refine_windows_and_gather"].update({"GBs": gbs, "frac_of_hbm_peak": gbs / HBM_PEAK_GBS})
+            device = sum(float(ps[k][1]) for k in ("windows_ms", "align_ms", "cigar_ms", "plan_ms", "consensus_ms"))
+            row["a1_share_of_pass_2"] = float(ps["align_ms"][1]) / device if device > 0 else None
+            row["text_changed_by_the_last_pass"] = bool(len(last[p]["cons"]) != len(one["cons"]) or (last[p]["cons"] != one["cons"]).any())
+        out["passes"][str(p)] = row
+    print(json.dumps(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "refine":
+        return main_refine(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "consensus":
         return main_consensus(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "haplotypes":
