@@ -969,7 +969,8 @@ typedef struct hs_haplotypes_result {
     double t_plan_ms;                /* k_cons_plan + layout, HIP events */
 } hs_haplotypes_result;
 /* the arguments of hs_polish_inputs, then the consensus parameters (NULL: the defaults).  A bundle above HS_CONSENSUS_CHUNK_MB and a
- * CIGAR of more than 2^31 - 1 bases are refused with the messages of hs_polish_consensus. */
+ * CIGAR of more than 2^31 - 1 bases (M and D lengths plus M and I lengths: an M op counts twice) are refused with the messages of
+ * hs_polish_consensus; a CIGAR of exactly 2^31 - 1 is accepted.  Both sides of that limit are tested (tests/haplotype_cases.py). */
 int hs_polish_haplotypes(hs_cv_batch* b, int32_t c0, int32_t c1, const int64_t* win_off, const int32_t* win_start, const int32_t* win_end,
                          const int64_t* label_off, const int32_t* labels, const uint8_t* contig_has_snps, int32_t polish_everything,
                          const hs_consensus_params* params, hs_haplotypes_result** out);

@@ -66,9 +66,44 @@ _CODE[ord("A")], _CODE[ord("C")], _CODE[ord("G")] = 0, 1, 2
 _LETTER = np.frombuffer(b"ACGT", np.uint8)
 
 
-def rule(job, min_cov=MIN_COV, max_ins=MAX_INS, wrong=None):
+def piece_runs(ln, op, s, L):
+    """The walk of one piece in run-length form, from the rule's text (hs_consensus_host.h: walk, slot): every op is clipped at the room left
+    (L - t) BEFORE anything per event exists, so a piece costs O(ops), whatever its lengths (an op holds up to 2^28 - 1 events).
+    Returns (runs, ins): runs = [(t, n, op, q)], the column ops inside the room -- n >= 1 events from column t on, the read cursor q at the first;
+    ins = [(slot, src, n)], the insertions that vote -- n inserted bases from read offset src, in front of column `slot`, a column event before."""
+    t, q, pending, src, runs, ins = int(s) - 1, 0, 0, 0, [], []
+    for n, c in zip((int(x) for x in ln), (int(x) for x in op)):
+        if t >= L:
+            break
+        if n == 0 or c > 2:
+            continue
+        if c == 1:
+            if pending == 0:
+                src = q
+            pending += n
+            q += n
+            continue
+        if pending and runs:
+            ins.append((t, src, pending))
+        pending = 0
+        k = min(n, L - t)
+        runs.append((t, k, c, q))
+        t += k
+        if c == 0:
+            q += n
+    return runs, ins
+
+
+def rule_rl(job, min_cov=MIN_COV, max_ins=MAX_INS):
+    """rule() with every piece walked in run-length form (piece_runs): for CIGARs whose ops np.repeat cannot hold"""
+    return rule(job, min_cov, max_ins, runs=True)
+
+
+def rule(job, min_cov=MIN_COV, max_ins=MAX_INS, wrong=None, runs=False):
     """The rule in numpy, bundle by bundle: {"cons": [bytes per bundle], FIELDS: lists, "n_ins_records", "n_ins_slots"}.
-    wrong: one of WRONG_RULES -- a deliberately wrong rule, which the case that claims the fork must tell from the right one."""
+    wrong: one of WRONG_RULES -- a deliberately wrong rule, which the case that claims the fork must tell from the right one.
+    runs: the votes of a piece come from piece_runs() instead of one array entry per event (rule_rl); the decisions are the same lines."""
+    assert not (runs and wrong)
     out = {k: [] for k in FIELDS}
     out["cons"] = []
     n_records = n_slots = 0
@@ -86,6 +121,17 @@ def rule(job, min_cov=MIN_COV, max_ins=MAX_INS, wrong=None):
             s = int(job["piece_sam_pos"][p])
             if len(text) == 0 or (int(job["piece_flags"][p]) & START_BEYOND_SEQ) or int(ln[(op == 0) | (op == 1)].sum()) != len(text) or s - 1 >= L:
                 skipped += 1
+                continue
+            if runs:
+                col_runs, voters = piece_runs(ln, op, s, L)
+                for t, n, c, q in col_runs:
+                    votes[np.arange(t, t + n), _CODE[text[q:q + n]] if c == 0 else 4] += 1
+                if col_runs:
+                    span[col_runs[0][0] + 1:col_runs[-1][0] + col_runs[-1][1]] += 1
+                for slot, src, n in voters:
+                    nins[slot] += 1
+                    ins[slot].append(text[src:src + min(n, max_ins)])
+                    n_records += 1
                 continue
             ev = np.repeat(op, ln)
             ev = ev[ev <= 2]                       # one entry per M, I or D char; nothing else moves a cursor

@@ -12,9 +12,14 @@ SUMS = ("n_sub", "n_del", "n_ins_bases", "n_low", "n_skipped")
 
 
 # ---- the restatement -------------------------------------------------------------------------------------------------------------------
-def columns(job, min_cov=cc.MIN_COV, max_ins=cc.MAX_INS):
+def columns_rl(job, min_cov=cc.MIN_COV, max_ins=cc.MAX_INS):
+    """columns() with every piece walked in run-length form (cc.piece_runs): for CIGARs whose ops np.repeat cannot hold"""
+    return columns(job, min_cov, max_ins, runs=True)
+
+
+def columns(job, min_cov=cc.MIN_COV, max_ins=cc.MAX_INS, runs=False):
     """col_off [B + 1], col_begin, col_ins (L + 1 entries per bundle), from the rule's text: a column emits its slot's insertion, then one byte unless
-    a deletion wins; column t begins where the columns before it end."""
+    a deletion wins; column t begins where the columns before it end. runs: the votes of a piece come from cc.piece_runs (columns_rl)."""
     col_off, begin, ins_all = [0], [], []
     for b in range(len(job["backbone_off"]) - 1):
         B = job["backbone"][job["backbone_off"][b]:job["backbone_off"][b + 1]]
@@ -28,6 +33,16 @@ def columns(job, min_cov=cc.MIN_COV, max_ins=cc.MAX_INS):
             text = job["bases"][job["base_off"][p]:job["base_off"][p + 1]]
             s = int(job["piece_sam_pos"][p])
             if len(text) == 0 or (int(job["piece_flags"][p]) & cc.START_BEYOND_SEQ) or int(ln[(op == 0) | (op == 1)].sum()) != len(text) or s - 1 >= L:
+                continue
+            if runs:
+                col_runs, voters = cc.piece_runs(ln, op, s, L)
+                for t, n, c, q in col_runs:
+                    votes[np.arange(t, t + n), cc._CODE[text[q:q + n]] if c == 0 else 4] += 1
+                if col_runs:
+                    span[col_runs[0][0] + 1:col_runs[-1][0] + col_runs[-1][1]] += 1
+                for slot, src, n in voters:
+                    nins[slot] += 1
+                    lens[slot].append(min(n, max_ins))
                 continue
             ev = np.repeat(op, ln)
             ev = ev[ev <= 2]
@@ -63,8 +78,8 @@ def columns(job, min_cov=cc.MIN_COV, max_ins=cc.MAX_INS):
 
 
 def windows(job, col_off, col_begin, col_ins, include_slot=False):
-    """win_start, win_end of every piece (hs::refine_window on hc.piece_plan). include_slot: the WRONG rule ws = col_begin[s0]."""
-    plan, bundle = hc.piece_plan(job)
+    """win_start, win_end of every piece (hs::refine_window on hc.piece_plan_rl). include_slot: the WRONG rule ws = col_begin[s0]."""
+    plan, bundle = hc.piece_plan_rl(job)
     n = len(plan)
     ws, we = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
     for p in range(n):
@@ -267,7 +282,78 @@ def rounds_cases():
     return out
 
 
+def a1_chunks_cases(n_bundles=8, n_pieces=300, L=4000):
+    """Queries plus windows of one sub-round above 16 MiB (8 x 300 pairs of 4001 + 4000 bases: 19.2 MB), so that A1 under HS_REALIGN_CHUNK_MB=16 (the
+    floor) runs in two chunks. In the style of rounds_cases: piece j carries the haplotype's one inserted base at 1998 + j mod 5, no slot wins pass 1,
+    pass 2 finds the haplotype. Returns (bundles, the haplotypes)."""
+    out, haps = [], []
+    for i in range(n_bundles):
+        bb = cc.seq(L, 60 + i)
+        hap = bb[:L // 2] + "G" + bb[L // 2:]
+        out.append(cc.Bundle("a bundle of %d pieces of %d bases, %d" % (n_pieces, L + 1, i), bb,
+                             [(1, "%dM1I%dM" % (L // 2 - 2 + j % 5, L - (L // 2 - 2 + j % 5)), hap) for j in range(n_pieces)]))
+        haps.append(hap)
+    return out, haps
+
+
 CASES = {"scattered": scattered_cases, "window_edges": window_edges_cases, "gather_edges": gather_edges_cases, "tiers": tiers_cases}
+
+
+def _true_cigar(events):
+    """run-length words of a string of M, I and D characters"""
+    chars = np.frombuffer(events.encode(), np.uint8)
+    cut = np.flatnonzero(np.diff(chars)) + 1
+    starts, ends = np.concatenate([[0], cut]), np.concatenate([cut, [len(chars)]])
+    return [int(((e - s) << 4) | "MID".index(chr(chars[s]))) for s, e in zip(starts, ends)]
+
+
+def noisy_cases(seed=5, n_pieces=12, hap_len=1040, piece_len=1000):
+    """Outside CASES (the CPU claims test runs a Python Needleman-Wunsch over those): two bundles of 12 seeded pieces of about 1000 bases. Every
+    piece has 8 % isolated errors of its own against its bundle's haplotype -- odd pieces 1 % substitutions and 7 % 1-base insertions and deletions,
+    even ones 4 % and 4 % -- and the backbone differs from the haplotype by three indels. Starts are staggered over 0 .. 40, the CIGARs of pass 1
+    are the true ones. Pass 2 then reads CIGARs the device wrote, of some 80 and some 140 words: beyond one and beyond two 64-op chunks."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(2):
+        hap = cc.seq(hap_len, 500 + k)
+        gone, extra = {300 + k: True, 901: True}, {600: "T"}      # haplotype bases the backbone lacks; backbone bases in front of a haplotype base
+        bb, col_of = [], []
+        for i, c in enumerate(hap):
+            bb.append(extra.get(i, ""))
+            col_of.append(sum(len(x) for x in bb))
+            if i not in gone:
+                bb.append(c)
+        bb = "".join(bb)
+        pieces = []
+        for j in range(n_pieces):
+            a = (j * 40) // (n_pieces - 1)
+            b = min(hap_len, a + piece_len)
+            p_sub, p_indel = (0.01, 0.07) if j % 2 else (0.04, 0.04)
+            kind = np.zeros(hap_len, np.int64)      # 0 none, 1 substitution, 2 the base is missing, 3 an inserted base in front
+            draw = rng.random(hap_len)
+            kind[draw < p_sub] = 1
+            kind[(draw >= p_sub) & (draw < p_sub + p_indel / 2)] = 2
+            kind[(draw >= p_sub + p_indel / 2) & (draw < p_sub + p_indel)] = 3
+            for i in range(hap_len):                # isolated, away from the piece's ends and from the backbone's own indels
+                near = any(abs(i - x) <= 2 for x in list(gone) + list(extra))
+                if kind[i] and (i < a + 3 or i >= b - 3 or near or kind[i - 1]):
+                    kind[i] = 0
+            text, ev = [], []
+            for i in range(a, b):
+                if i in extra:
+                    ev.append("D" * len(extra[i]))
+                if kind[i] == 3:
+                    text.append("ACGT"[int(rng.integers(4))]); ev.append("I")
+                if kind[i] == 2:
+                    ev.append("D")
+                else:
+                    text.append(cc.other(hap[i]) if kind[i] == 1 else hap[i]); ev.append("I" if i in gone else "M")
+            pieces.append((col_of[a] + 1, _true_cigar("".join(ev)), "".join(text)))
+        out.append(cc.Bundle("noisy bundle %d" % k, bb, pieces, ovl=20, ovr=25))
+    return out
+
+
+NOISY = {"noisy": noisy_cases}
 
 
 def check_windows(bundles, job, ws, we, key="windows"):

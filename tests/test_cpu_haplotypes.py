@@ -85,6 +85,74 @@ def test_the_new_cases_reach_what_they_name():
         assert max(len(p[1]) for b in hc.CASES[g]() for p in b.pieces) > 64
 
 
+# ---- the run-length restatements, and the limit cases they exist for ------------------------------------------------------------------------
+def _old_groups():
+    import refine_cases as rc
+    return hc.all_groups() + [("rc." + g, rc.CASES[g]()) for g in sorted(rc.CASES)]
+
+
+@pytest.mark.parametrize("params", ((cc.MIN_COV, cc.MAX_INS), (1, 2), (4, 64)))
+def test_run_length_forms_equal_the_expanding_forms_on_every_old_group(params):
+    """cc.rule_rl, hc.piece_plan_rl and rc.columns_rl against the forms that hold one array entry per event, in every field"""
+    import refine_cases as rc
+    for name, bundles in _old_groups():
+        job = cc.pack(bundles)
+        a, b = cc.rule(job, *params), cc.rule_rl(job, *params)
+        assert sorted(a) == sorted(b)
+        for k in a:
+            assert a[k] == b[k], (name, params, k)
+        for x, y in zip(hc.piece_plan(job), hc.piece_plan_rl(job)):
+            assert np.array_equal(x, y), (name, "plan")
+        for k, x, y in zip(("col_off", "col_begin", "col_ins"), rc.columns(job, *params), rc.columns_rl(job, *params)):
+            assert x.dtype == y.dtype and np.array_equal(x, y), (name, params, k)
+
+
+@pytest.mark.parametrize("group", sorted(hc.LIMIT_CASES))
+def test_host_half_and_host_plan_equal_the_run_length_forms_on_the_limit_cases(consensus_selftest, selftest, tmp_path, group):
+    """the builders assert their sums (T, Q, T + Q) as they build; the claims and the claimed plans are worked out by hand"""
+    bundles = hc.LIMIT_CASES[group]()
+    job = cc.pack(bundles)
+    plan, bundle = hc.piece_plan_rl(job)
+    hc.check_limit_plan(bundles, plan)
+    got = [[int(x) for x in line.split()[1:]] for line in run_lines(selftest, plan_lines(job, bundle), tmp_path).splitlines()]
+    assert got == plan.tolist()
+    for params in ((cc.MIN_COV, cc.MAX_INS), (1, 2), (4, 64)):
+        want = cc.rule_rl(job, *params)
+        assert np.bincount(bundle[plan[:, 0] == 1], minlength=len(bundles)).tolist() == want["n_skipped"] and int(plan[:, 3].sum()) == want["n_ins_records"]
+        res = run_host(consensus_selftest, job, tmp_path, *params)
+        cc.assert_same(res, want, (group, params))
+        if params == (cc.MIN_COV, cc.MAX_INS):
+            cc.check_claims(bundles, want)
+            cc.check_claims(bundles, res)
+
+
+def test_the_limit_cases_reach_what_they_name():
+    sums = {b.name: b.sums for g in hc.LIMIT_CASES for b in hc.LIMIT_CASES[g]()}
+    assert sum(sums["at the limit: 5M, 7 x 268435455D, 268435452D"]) == hc.INT32_MAX == sum(sums["at the limit, M and I form: 4 x 268435455M 3M 1I"])
+    assert sums["full chunk: 5M and 63 x 33554432D"][0] == 63 * 2 ** 25 + 5 < 2 ** 31
+    for b in hc.LIMIT_CASES["long_m"]():
+        assert 2 ** 16 < len(b.backbone) <= 70_000 and len(b.pieces) == 3
+    assert all(len(b.backbone) <= 100 and len(b.pieces) <= 4 for g in ("lengths", "chunks", "boundary") for b in hc.LIMIT_CASES[g]())
+    assert len(hc.LIMIT_CASES["chunks"]()[0].pieces[0][1]) == 64 == len(hc.LIMIT_CASES["chunks"]()[1].pieces[0][1])
+    assert sum(sums["at the limit, a full chunk: 5M, 62 x 33554432D, 67108853D"]) == hc.INT32_MAX and len(hc.FULL_AT_LIMIT) == 64 == len(hc.FULL_OVER_LIMIT)
+
+
+@pytest.mark.parametrize("case", range(len(hc.refused_cases())))
+def test_a_cigar_over_the_limit_is_refused_by_the_host_half_and_flagged_by_the_host_plan(consensus_selftest, selftest, tmp_path, case):
+    name, bundles, named = hc.refused_cases()[case]
+    job = cc.pack(bundles)
+    plan, bundle = hc.piece_plan_rl(job)
+    assert plan[:, 1].any() and int(bundle[plan[:, 1] == 1].min()) == named, name
+    got = [[int(x) for x in line.split()[1:]] for line in run_lines(selftest, plan_lines(job, bundle), tmp_path).splitlines()]
+    assert got == plan.tolist(), name
+    path = str(tmp_path / "job.txt")
+    for threads in (1, 2):
+        cc.write_job(path, job, threads=threads)
+        r = subprocess.run([consensus_selftest, path], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        assert r.returncode == 4 and r.stdout == b"", (name, r.returncode)
+        assert r.stderr.decode() == "consensus_selftest: bundle %d: a CIGAR of more than 2^31 - 1 bases\n" % named, (name, r.stderr.decode())
+
+
 FASTA_LINES = ["F contig_1 100 2099 0 3 7 ACGTACGTAC", "F edge_7 0 500 -1 0 4 ACGT", "F c 5 6 2 4 4 ACGTACGT", "F c 5 6 3 0 0 -", "F c 1 2 12 6 2 ACGTACGT"]
 FASTA_WANT = ">contig_1_100_2099_0\nTACG\n>edge_7_0_500_-1\nACGT\n>c_5_6_2\n\n>c_5_6_3\n\n>c_1_2_12\n\n"
 

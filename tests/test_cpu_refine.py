@@ -53,9 +53,9 @@ def run_selftest(exe, job, tmp_path):
     return out
 
 
-@pytest.mark.parametrize("group", sorted(rc.CASES))
+@pytest.mark.parametrize("group", sorted(rc.CASES) + sorted(rc.NOISY))
 def test_plan_host_equals_the_restatement(selftest, tmp_path, group):
-    bundles = rc.CASES[group]()
+    bundles = dict(rc.CASES, **rc.NOISY)[group]()
     job = cc.pack(bundles)
     col_off, begin, ins = rc.columns(job)
     ws, we = rc.windows(job, col_off, begin, ins)

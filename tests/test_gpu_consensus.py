@@ -1,6 +1,8 @@
 """The bundle consensus on the device (hs_kernels_consensus.hip, hs_capi_consensus.inc): the device equals the host half of the rule
 (hs_polish_consensus_host) on every case of tests/consensus_cases.py and every field by integer equality, twice; the wait count; one job in two
-rounds and in one; the over-budget bundle; polish_inputs -> polish_consensus on a resident batch; bin/hs_polish_inputs with HS_CONSENSUS=1."""
+rounds and in one; the over-budget bundle; polish_inputs -> polish_consensus on a resident batch; bin/hs_polish_inputs with HS_CONSENSUS=1;
+k_cons_rows on op lengths of 2^16 and more and on a CIGAR of exactly 2^31 - 1 bases (tests/haplotype_cases.py LIMIT_CASES), where its plain int
+scans run just below the bound the plan guards."""
 import os
 import subprocess
 import sys
@@ -37,6 +39,20 @@ def test_device_equals_the_host_half(built, group):
         dev = api.polish_consensus(job)
         assert api.host_waits() - w0 <= 3 * dev["stats"]["n_rounds"] and dev["stats"]["n_rounds"] == 1
         _same(dev, host, (group, run))
+
+
+def test_rows_of_the_limit_cases_equal_the_run_length_rule(built):
+    """every limit case in ONE call, behind a plain bundle: rows, records and columns of the cases at offsets other than 0"""
+    import haplotype_cases as hc
+    from hairsplitter_amd import api
+    bundles = cc.trim_cases()[:1] + [b for g in sorted(hc.LIMIT_CASES) for b in hc.LIMIT_CASES[g]()]
+    job = cc.pack(bundles)
+    want = cc.rule_rl(job)
+    cc.check_claims(bundles, want)
+    for run in (0, 1):
+        dev = api.polish_consensus(job)
+        cc.assert_same(cc.result_as_rule(dev), want, (run, [(b.name, getattr(b, "aim", "")) for b in bundles]))
+        assert dev["stats"]["n_rounds"] == 1
 
 
 def test_other_parameters(built):

@@ -2,10 +2,13 @@
 finds it equals its numpy restatement, and the planned route equals the host half, on every case of tests/consensus_cases.py and
 tests/haplotype_cases.py; (2) polish_haplotypes equals polish_consensus(polish_inputs(...)) and the host half on a noisy diploid contig, without
 bringing the pieces down, within its host waits; (3) several resident rounds and several consensus sub-rounds equal one; (4) the FASTA of
-bin/hs_polish_inputs under HS_HAPLOTYPES=1; (5) refusals; (6) the default pipeline step costs what it cost.
+bin/hs_polish_inputs under HS_HAPLOTYPES=1; (5) refusals; (6) the default pipeline step costs what it cost; (7) the limit cases of
+tests/haplotype_cases.py: op lengths of 2^16 and more and a CIGAR whose M, I and D lengths sum to exactly 2^31 - 1 on the host half, the
+host-planned route and the device-planned route, and one base more refused by all three, naming the same bundle (a CIGAR word holds 2^28 - 1 and
+a D op needs no bases: the limit is reached in milliseconds).
 
-Limits not reached by a test of seconds: a CIGAR whose M, I and D lengths sum beyond 2^31 - 1 (refused from the device's flag), more than
-2^31 - 256 pieces or bundles in a resident round, more than 2^31 - 256 insertion records or 2^30 columns in a sub-round."""
+Limits not reached by a test: more than 2^31 - 256 pieces or bundles in a resident round, more than 2^31 - 256 insertion records or 2^30 columns
+in a sub-round."""
 import os
 import subprocess
 import sys
@@ -226,6 +229,49 @@ def test_refusals(built, monkeypatch):
             api.polish_consensus(big, form="planned")
     finally:
         batch.close()
+
+
+# ---- 7. the limits -------------------------------------------------------------------------------------------------------------------------
+FORMS = ("host", "device", "planned")
+
+
+@pytest.mark.parametrize("group", sorted(hc.LIMIT_CASES))
+def test_limit_cases_agree_on_the_three_routes_and_the_device_plan_equals_the_run_length_plan(built, group):
+    """where every case aims is its `aim` (tests/haplotype_cases.py), and the assertion messages carry it"""
+    from hairsplitter_amd import api
+    bundles = hc.LIMIT_CASES[group]()
+    job = cc.pack(bundles)
+    aims = [(b.name, b.aim) for b in bundles]
+    want_plan, _ = hc.piece_plan_rl(job)
+    hc.check_limit_plan(bundles, want_plan)
+    for params in ((cc.MIN_COV, cc.MAX_INS), (1, 2), (4, 64)):
+        prm = api.consensus_params(min_cov=params[0], max_ins=params[1])
+        want = cc.rule_rl(job, *params)
+        res = {"host": api.polish_consensus(job, prm, form="host")}
+        for run in (0, 1):      # (twice: nothing may hinge on the order in which the pieces' additions arrive)
+            res.update({form: api.polish_consensus(job, prm, form=form) for form in FORMS[1:]})
+            for form in FORMS:
+                cc.assert_same(cc.result_as_rule(res[form]), want, (group, params, run, form, aims))
+            _same(res["device"], res["host"], (group, params, run, aims))
+            _same(res["planned"], res["host"], (group, params, run, aims))
+            assert np.array_equal(res["planned"]["plan"], want_plan), (group, params, run, aims, res["planned"]["plan"].tolist())
+            hc.check_limit_plan(bundles, res["planned"]["plan"])
+        if params == (cc.MIN_COV, cc.MAX_INS):
+            for form in FORMS:
+                cc.check_claims(bundles, cc.result_as_rule(res[form]))
+
+
+@pytest.mark.parametrize("case", range(len(hc.refused_cases())))
+def test_a_cigar_over_the_limit_is_refused_on_the_three_routes_naming_the_same_bundle(built, case):
+    """refused, not skipped: by the host half, by the host's plan (hs_capi_consensus.inc, consensus_device) and from the device's first_long, an
+    atomic minimum over the pieces -- twice, for the order in which two long pieces arrive there"""
+    from hairsplitter_amd import api
+    name, bundles, named = hc.refused_cases()[case]
+    job = cc.pack(bundles)
+    for run in (0, 1):
+        for form in FORMS:
+            with pytest.raises(api.HsError, match=r"bundle %d: a CIGAR of more than 2\^31 - 1 bases" % named):
+                api.polish_consensus(job, form=form)
 
 
 # ---- 6. the default step -------------------------------------------------------------------------------------------------------------------

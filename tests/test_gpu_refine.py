@@ -5,12 +5,25 @@ passes equals it on every case -- text, every per-bundle field, the per-pass sum
 (2) one pass is the planned route; (3) polish_haplotypes(passes=2) equals polish_refine on the inputs of the same job, and passes=1 is the one-pass
 call in every field, its waits and its launches; (4) several sub-rounds equal one; (5) refusals; (6) the default step costs what it cost.
 
-Limits not reached by a test of seconds: a piece above 2^20 bases (no path: n_unaligned), more than 2^31 - 256 pairs or 2^31 - 1 move bytes in an A1 chunk."""
+(7) the limit cases of tests/haplotype_cases.py -- op lengths of 2^16 and more, a CIGAR of exactly 2^31 - 1 bases, one of 2^31 refused -- through
+one and two passes; (8) pass 2 and 3 over CIGARs the device wrote for noisy pieces, of more than 64 and more than 128 words, against the
+composition; (9) A1 in several chunks equals one, several resident rounds with passes equal one.
+
+Limits not reached by a test: a piece above 2^20 bases (no path: the n_unaligned branch of k_refine_pieces) -- A1 sweeps the whole pair for its
+distance before it declines the path, and nobody has measured that sweep; more than 2^31 - 256 pairs or 2^31 - 1 move bytes in an A1 chunk; more than
+2^31 - 256 pieces, bundles or records; 2^30 columns. (A CIGAR beyond 2^31 - 1 bases IS reached, in milliseconds: a word holds 2^28 - 1, a D op needs no bases.)"""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
 import consensus_cases as cc
+import haplotype_cases as hc
 import refine_cases as rc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
@@ -23,13 +36,13 @@ def device_align(pairs):
     return [(r["ops"], r["distance"]) for r in api.edlib_align(pairs, mode="NW", task="path")]
 
 
-def yardstick(group, params=None, key=None):
-    """three passes of the composition on a case group, computed once and left unchanged"""
+def yardstick(group, params=None, key=None, passes=3):
+    """three passes (or `passes`) of the composition on a case group, computed once and left unchanged"""
     from hairsplitter_amd import api
     key = key or group
     if key not in _YARD:
-        bundles = rc.CASES[group]()
-        _YARD[key] = (bundles, cc.pack(bundles), rc.compose(cc.pack(bundles), 3, lambda job, prm: api.polish_refine_plan_host(job, prm), device_align, params))
+        bundles = dict(rc.CASES, **rc.NOISY, **hc.LIMIT_CASES)[group]()
+        _YARD[key] = (bundles, cc.pack(bundles), rc.compose(cc.pack(bundles), passes, lambda job, prm: api.polish_refine_plan_host(job, prm), device_align, params))
     return _YARD[key]
 
 
@@ -196,6 +209,133 @@ def test_several_sub_rounds_equal_one(built, monkeypatch):
         assert one["passes"][k].tolist() == many["passes"][k].tolist(), k
     assert many["passes"]["n_waits"][1] > one["passes"]["n_waits"][1]
     rc.check_pass_claims(rc.rounds_cases(), 3, many)
+
+
+# ---- 7. the limits ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("group", sorted(hc.LIMIT_CASES))
+def test_limit_cases_through_one_and_two_passes_equal_the_composition(built, group):
+    """pass 2 there realigns short pieces against short texts (but for the long M bundles: 135 546 bases against 65 578)"""
+    from hairsplitter_amd import api
+    bundles, job, want = yardstick(group, passes=2)
+    cc.check_claims(bundles, cc.result_as_rule(want[0]["res"]))
+    for passes in (1, 2):
+        dev = api.polish_refine(job, passes=passes)
+        assert_pass_equals(dev, want, (group, [b.aim for b in bundles]))
+    assert int(dev["passes"]["n_unaligned"].sum()) == 0 and int(dev["passes"]["n_pairs"][1]) > 0
+
+
+@pytest.mark.parametrize("case", range(len(hc.refused_cases())))
+def test_a_cigar_over_the_limit_is_refused_by_one_and_by_two_passes(built, case):
+    from hairsplitter_amd import api
+    name, bundles, named = hc.refused_cases()[case]
+    job = cc.pack(bundles)
+    for passes in (1, 2, 1, 2):
+        with pytest.raises(api.HsError, match=r"bundle %d: a CIGAR of more than 2\^31 - 1 bases" % named):
+            api.polish_refine(job, passes=passes)
+
+
+# ---- 8. noisy pieces -------------------------------------------------------------------------------------------------------------------------
+def test_noisy_pieces_equal_the_composition_over_cigars_the_device_wrote(built):
+    """The conditions are read off the yardstick's own pass-2 job, not off the route under test: CIGARs of the k_m2c_* kernels with more than two
+    64-op chunks and with more than one feed k_refine_pieces, k_cons_plan and k_cons_rows."""
+    from hairsplitter_amd import api
+    bundles, job, want = yardstick("noisy")
+    n_words = np.diff(want[1]["job"]["cig_off"])
+    print("noisy: words a piece in pass 2", sorted(n_words.tolist()), "sum_dist", [w["sum_dist"] for w in want])
+    assert n_words.max() >= 129 and ((n_words >= 65) & (n_words <= 128)).any() and want[1]["sum_dist"] > 0
+    assert len(bundles) == 2 and all(len(b.pieces) == 12 for b in bundles)
+    for passes in (1, 2, 3):
+        assert_pass_equals(api.polish_refine(job, passes=passes), want, "noisy")
+
+
+# ---- 9. seams --------------------------------------------------------------------------------------------------------------------------------
+PASS_KEYS = rc.SUMS + ("n_pairs", "n_unaligned", "sum_dist", "move_bytes", "cigar_words")
+
+A1_CHILD = """
+import sys
+import numpy as np
+sys.path.insert(0, "tests")
+import consensus_cases as cc
+import refine_cases as rc
+import test_gpu_refine as tr
+from hairsplitter_amd import api
+res = api.polish_refine(cc.pack(rc.a1_chunks_cases()[0]), passes=2)
+out = {k: np.asarray(res[k]) for k in tr.CONS_KEYS}
+out.update({"pass_" + k: res["passes"][k] for k in tr.PASS_KEYS + ("n_waits",)})
+np.savez(sys.argv[1], **out)
+"""
+
+
+def test_a1_in_several_chunks_equals_one(built, tmp_path):
+    """HS_REALIGN_CHUNK_MB is read once a process: a child runs the job under 16 (the floor; queries plus windows are 19.2 MB, two chunks), this process
+    under the default (one). A wait per chunk. Measured on an MI355X: the call 0.04 s in this process (A1 over the 2 400 pairs: 13 ms), the child 2.1 s with its start, the
+    test 2.2 s."""
+    import time
+    from hairsplitter_amd import api
+    bundles, haps = rc.a1_chunks_cases()
+    job = cc.pack(bundles)
+    assert int(job["base_off"][-1]) + sum(len(b.backbone) * len(b.pieces) for b in bundles) > 16 << 20
+    t0 = time.perf_counter()
+    one = api.polish_refine(job, passes=2)
+    print("a1 chunks job: polish_refine(passes=2) in this process %.2f s" % (time.perf_counter() - t0), {k: one["passes"][k].tolist() for k in ("n_pairs", "n_waits", "align_ms")})
+    dst = str(tmp_path / "child.npz")
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, "-c", A1_CHILD, dst], cwd=ROOT, env=dict(os.environ, HS_REALIGN_CHUNK_MB="16"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    print("a1 chunks job: the child %.2f s" % (time.perf_counter() - t0))
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    child = np.load(dst)
+    for k in CONS_KEYS:
+        assert np.array_equal(one[k], child[k]), k
+    for k in PASS_KEYS:
+        assert one["passes"][k].tolist() == child["pass_" + k].tolist(), k
+    assert int(child["pass_n_waits"][1]) >= int(one["passes"]["n_waits"][1]) + 1 and int(child["pass_n_waits"][0]) == int(one["passes"]["n_waits"][0])
+    assert one["stats"]["n_sub_rounds"] == 1 and int(one["passes"]["n_pairs"][1]) == sum(len(b.pieces) for b in bundles)
+    assert [api.consensus_text(one, i) for i in range(len(bundles))] == haps
+
+
+def three_contigs_two_passes(api):
+    c = diploid_contig()
+    batch = api.CvBatch(api.FlatBatch([c, c, c]))
+    try:
+        return api.polish_haplotypes(batch, labelled([c, c, c]), contig_has_snps=[1, 1, 1], passes=2)
+    finally:
+        batch.close()
+
+
+ROUNDS_CHILD = """
+import sys
+import numpy as np
+sys.path.insert(0, "tests")
+import test_gpu_haplotypes as th
+import test_gpu_refine as tr
+from hairsplitter_amd import api
+res = tr.three_contigs_two_passes(api)
+out = {k: np.asarray(res[k]) for k in th.CONS_KEYS + th.META_KEYS}
+out.update({k: np.int64(res["stats"][k]) for k in th.COUNTS + ("n_rounds", "n_sub_rounds")})
+out.update({"pass_" + k: res["passes"][k] for k in tr.PASS_KEYS})
+np.savez(sys.argv[1], **out)
+"""
+
+
+def test_several_resident_rounds_and_several_sub_rounds_with_passes_equal_one(built, tmp_path):
+    """RefineStats accumulates over the resident rounds and refine_first_pass subtracts the later passes' waits from the call's: every per-pass sum
+    but n_waits (which legitimately differs) is that of the one-round call"""
+    from hairsplitter_amd import api
+    from test_gpu_haplotypes import COUNTS, META_KEYS
+    one = three_contigs_two_passes(api)
+    assert one["stats"]["n_rounds"] == 1 and one["stats"]["n_sub_rounds"] == 1 and one["n_bundles"] >= 6 and int(one["passes"]["n_pairs"][1]) > 0
+    for env, check in (({"HS_POLISH_CHUNK_MB": "1"}, lambda r, s: r >= 2 and s >= r), ({"HS_CONSENSUS_CHUNK_MB": "1"}, lambda r, s: r == 1 and s > r)):
+        dst = str(tmp_path / ("child_%s.npz" % list(env)[0]))
+        r = subprocess.run([sys.executable, "-c", ROUNDS_CHILD, dst], cwd=ROOT, env=dict(os.environ, **env), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        child = np.load(dst)
+        assert check(int(child["n_rounds"]), int(child["n_sub_rounds"])), (env, int(child["n_rounds"]), int(child["n_sub_rounds"]))
+        for k in CONS_KEYS + META_KEYS:
+            assert np.array_equal(one[k], child[k]), (env, k)
+        for k in COUNTS:
+            assert one["stats"][k] == int(child[k]), (env, k)
+        for k in PASS_KEYS:
+            assert one["passes"][k].tolist() == child["pass_" + k].tolist(), (env, k)
 
 
 def test_tool_writes_the_refined_fasta_under_hs_polish_passes(built, tmp_path):
