@@ -1830,6 +1830,9 @@ def consensus_params(**kw) -> ConsensusParams:
     return p
 
 
+_ARRAYS_ARGTYPES = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams)]      # n_bundles, the eleven arrays of a polishing job, the parameters
+
+
 def polish_consensus(res: Dict, params: Optional[ConsensusParams] = None, form: str = "device") -> Dict:
     """The consensus of every bundle of `res`: the dict polish_inputs returns, or one of hand-built arrays with the keys backbone_off, backbone,
     bundle_overhang_left, bundle_overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar. form "device": the kernels
@@ -1840,34 +1843,19 @@ def polish_consensus(res: Dict, params: Optional[ConsensusParams] = None, form: 
     if form not in ("device", "host", "planned"):
         raise HsError("polish_consensus: form is 'device', 'host' or 'planned'")
     lib = load()
-    a64 = [_np(res[k], np.int64) for k in ("backbone_off", "piece_off", "base_off", "cig_off")]
-    a32 = [_np(res[k], np.int32) for k in ("bundle_overhang_left", "bundle_overhang_right", "piece_sam_pos", "piece_flags")]
-    backbone, bases, cigar = _np(res["backbone"], np.uint8), _np(res["bases"], np.uint8), _np(res["cigar"], np.uint32)
-    B = len(a64[0]) - 1
-    if B < 0 or len(a64[1]) != B + 1 or len(a32[0]) != B or len(a32[1]) != B:
-        raise HsError("polish_consensus: the bundle arrays do not agree")
-    P = int(a64[1][-1]) if B >= 0 and len(a64[1]) else 0
-    if len(a64[2]) != P + 1 or len(a64[3]) != P + 1 or len(a32[2]) != P or len(a32[3]) != P:
-        raise HsError("polish_consensus: the piece arrays do not agree")
-    if len(backbone) < int(a64[0][-1]) or len(bases) < int(a64[2][-1]) or len(cigar) < int(a64[3][-1]):
-        raise HsError("polish_consensus: the offsets run beyond the arrays")
-
-    def ptr(a):
-        return a.ctypes.data_as(C.c_void_p)
+    B, P, args, keep = _consensus_arrays_args("polish_consensus", res, params)
     lib.hs_consensus_result_destroy.argtypes = [C.c_void_p]
     lib.hs_consensus_result_destroy.restype = None
     out_p = C.POINTER(ConsensusResult)()
-    args = [C.c_int64(B), ptr(a64[0]), ptr(backbone), ptr(a32[0]), ptr(a32[1]), ptr(a64[1]), ptr(a32[2]), ptr(a32[3]), ptr(a64[2]), ptr(bases), ptr(a64[3]), ptr(cigar),
-            None if params is None else C.byref(params)]
     plan = None
     if form == "planned":
         plan = np.full((P, 4), -1, np.int32)
         fn = lib.hs_polish_consensus_planned_tap
-        fn.argtypes = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams), C.c_void_p, C.POINTER(C.POINTER(ConsensusResult))]
-        _check(fn(*(args + [ptr(plan), C.byref(out_p)])))
+        fn.argtypes = _ARRAYS_ARGTYPES + [C.c_void_p, C.POINTER(C.POINTER(ConsensusResult))]
+        _check(fn(*(args + [plan.ctypes.data_as(C.c_void_p), C.byref(out_p)])))
     else:
         fn = lib.hs_polish_consensus_arrays if form == "device" else lib.hs_polish_consensus_host
-        fn.argtypes = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams), C.POINTER(C.POINTER(ConsensusResult))]
+        fn.argtypes = _ARRAYS_ARGTYPES + [C.POINTER(C.POINTER(ConsensusResult))]
         _check(fn(*(args + [C.byref(out_p)])))
     try:
         out = _consensus_result_dict(out_p.contents, B)
@@ -1902,6 +1890,25 @@ class HaplotypesResult(C.Structure):
                 ("bytes_down", C.c_int64), ("bytes_up", C.c_int64), ("t_plan_ms", C.c_double)]
 
 
+def _haplotypes_result_dict(h, refined=None) -> Dict:
+    """A hs_haplotypes_result as one dict: the metadata of its inputs and the keys of its consensus, "stats" those of both with n_rounds (resident
+    rounds), n_sub_rounds, bytes_down, bytes_up and plan_ms. Without inputs (polish_refine: the arrays were the caller's) the consensus keys alone,
+    n_rounds the consensus's own. refined (a hs_refined_result): "passes" as well."""
+    cons = _consensus_result_dict(h.consensus.contents, int(h.consensus.contents.n_bundles))
+    if h.inputs:
+        out = _polish_result_dict(h.inputs.contents, False)
+        stats = dict(out["stats"], **cons.pop("stats"))
+        out.update(cons)
+        stats["n_rounds"] = int(h.n_rounds)
+    else:
+        out, stats = cons, cons["stats"]
+    stats.update({"n_sub_rounds": int(h.n_sub_rounds), "bytes_down": int(h.bytes_down), "bytes_up": int(h.bytes_up), "plan_ms": h.t_plan_ms})
+    out["stats"] = stats
+    if refined is not None:
+        out["passes"] = _refined_passes_dict(refined)
+    return out
+
+
 def polish_haplotypes(batch_or_pipeline, sr: Dict, polish_everything: bool = False, c0: int = 0, c1: Optional[int] = None, contig_has_snps=None,
                       params: Optional[ConsensusParams] = None, passes: int = 1) -> Dict:
     """polish_consensus(polish_inputs(...)) in one call (hs_polish_haplotypes): the arguments of polish_inputs and the consensus parameters. One
@@ -1923,7 +1930,9 @@ def polish_haplotypes(batch_or_pipeline, sr: Dict, polish_everything: bool = Fal
         return a.ctypes.data_as(C.c_void_p)
     res = C.POINTER(HaplotypesResult)()
     refined = C.POINTER(RefinedResult)()
-    lib.hs_polish_haplotypes.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.POINTER(ConsensusParams), C.POINTER(C.POINTER(HaplotypesResult))]
+    labels_argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.POINTER(ConsensusParams)]
+    lib.hs_polish_haplotypes.argtypes = labels_argtypes + [C.POINTER(C.POINTER(HaplotypesResult))]
+    lib.hs_polish_haplotypes_refined.argtypes = labels_argtypes + [C.c_int32, C.POINTER(C.POINTER(RefinedResult))]
     lib.hs_haplotypes_result_destroy.argtypes = [C.c_void_p]
     lib.hs_haplotypes_result_destroy.restype = None
     lib.hs_refined_result_destroy.argtypes = [C.c_void_p]
@@ -1933,26 +1942,15 @@ def polish_haplotypes(batch_or_pipeline, sr: Dict, polish_everything: bool = Fal
     if passes == 1:
         _check(lib.hs_polish_haplotypes(*(args + [C.byref(res)])))
     else:
-        lib.hs_polish_haplotypes_refined.argtypes = ([C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6 +
-                                                     [C.c_int32, C.POINTER(ConsensusParams), C.c_int32, C.POINTER(C.POINTER(RefinedResult))])
         _check(lib.hs_polish_haplotypes_refined(*(args + [C.c_int32(int(passes)), C.byref(refined)])))
         res = refined.contents.last
     try:
-        r = res.contents
-        out = _polish_result_dict(r.inputs.contents, False)
-        cons = _consensus_result_dict(r.consensus.contents, out["n_bundles"])
-        stats = dict(out["stats"], **cons.pop("stats"))
-        out.update(cons)
-        stats.update({"n_rounds": int(r.n_rounds), "n_sub_rounds": int(r.n_sub_rounds), "bytes_down": int(r.bytes_down), "bytes_up": int(r.bytes_up), "plan_ms": r.t_plan_ms})
-        out["stats"] = stats
-        if refined:
-            out["passes"] = _refined_passes_dict(refined.contents)
+        return _haplotypes_result_dict(res.contents, refined.contents if refined else None)
     finally:
         if refined:
             lib.hs_refined_result_destroy(refined)
         else:
             lib.hs_haplotypes_result_destroy(res)
-    return out
 
 
 # ---- polishing passes: pieces realigned to the consensus of the pass before, then the vote again (the rule: csrc/hs_refine_host.h) ----
@@ -1981,7 +1979,9 @@ def _refined_passes_dict(r) -> Dict:
     return out
 
 
-def _consensus_arrays_args(who: str, res: Dict):
+def _consensus_arrays_args(who: str, res: Dict, params: Optional[ConsensusParams] = None):
+    """the arrays of a polishing job, converted and checked against each other, as the arguments _ARRAYS_ARGTYPES names: n_bundles, n_pieces, the
+    argument list and the arrays it points into (to be kept alive over the call)"""
     a64 = [_np(res[k], np.int64) for k in ("backbone_off", "piece_off", "base_off", "cig_off")]
     a32 = [_np(res[k], np.int32) for k in ("bundle_overhang_left", "bundle_overhang_right", "piece_sam_pos", "piece_flags")]
     backbone, bases, cigar = _np(res["backbone"], np.uint8), _np(res["bases"], np.uint8), _np(res["cigar"], np.uint32)
@@ -1997,7 +1997,8 @@ def _consensus_arrays_args(who: str, res: Dict):
 
     def ptr(a):
         return a.ctypes.data_as(C.c_void_p)
-    args = [C.c_int64(B), ptr(a64[0]), ptr(backbone), ptr(a32[0]), ptr(a32[1]), ptr(a64[1]), ptr(a32[2]), ptr(a32[3]), ptr(a64[2]), ptr(bases), ptr(a64[3]), ptr(cigar)]
+    args = [C.c_int64(B), ptr(a64[0]), ptr(backbone), ptr(a32[0]), ptr(a32[1]), ptr(a64[1]), ptr(a32[2]), ptr(a32[3]), ptr(a64[2]), ptr(bases), ptr(a64[3]), ptr(cigar),
+            None if params is None else C.byref(params)]
     return B, P, args, keep
 
 
@@ -2008,22 +2009,19 @@ def polish_refine(res: Dict, params: Optional[ConsensusParams] = None, passes: i
     n_low, n_skipped (sums over the bundles, each against that pass's backbone), n_pairs, n_unaligned, sum_dist, move_bytes, cigar_words (0 for pass 1),
     windows_ms, align_ms, cigar_ms, plan_ms, consensus_ms and n_waits."""
     lib = load()
-    B, P, args, keep = _consensus_arrays_args("polish_refine", res)
+    B, P, args, keep = _consensus_arrays_args("polish_refine", res, params)
     fn = lib.hs_polish_refine_arrays
-    fn.argtypes = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams), C.c_int32, C.POINTER(C.POINTER(RefinedResult))]
+    fn.argtypes = _ARRAYS_ARGTYPES + [C.c_int32, C.POINTER(C.POINTER(RefinedResult))]
     lib.hs_refined_result_destroy.argtypes = [C.c_void_p]
     lib.hs_refined_result_destroy.restype = None
     out_p = C.POINTER(RefinedResult)()
-    _check(fn(*(args + [None if params is None else C.byref(params), C.c_int32(int(passes)), C.byref(out_p)])))
+    _check(fn(*(args + [C.c_int32(int(passes)), C.byref(out_p)])))
     try:
-        r = out_p.contents
-        h = r.last.contents
-        out = _consensus_result_dict(h.consensus.contents, B)
-        out["stats"].update({"n_sub_rounds": int(h.n_sub_rounds), "bytes_down": int(h.bytes_down), "bytes_up": int(h.bytes_up), "plan_ms": h.t_plan_ms})
-        out["passes"] = _refined_passes_dict(r)
+        return _haplotypes_result_dict(out_p.contents.last.contents, out_p.contents)
     finally:
         lib.hs_refined_result_destroy(out_p)
-    return out
+
+
 
 
 def polish_refine_plan_host(res: Dict, params: Optional[ConsensusParams] = None) -> Dict:
@@ -2031,13 +2029,13 @@ def polish_refine_plan_host(res: Dict, params: Optional[ConsensusParams] = None)
     col_off [n_bundles + 1], col_begin and col_ins (L + 1 per bundle: where column t begins in the bundle's consensus, the inserted bases in front of
     it) and per piece win_start / win_end, its window in its bundle's consensus (-1 / -1: none)."""
     lib = load()
-    B, P, args, keep = _consensus_arrays_args("polish_refine_plan_host", res)
+    B, P, args, keep = _consensus_arrays_args("polish_refine_plan_host", res, params)
     fn = lib.hs_polish_refine_plan_host
-    fn.argtypes = [C.c_int64] + [C.c_void_p] * 11 + [C.POINTER(ConsensusParams), C.POINTER(C.POINTER(RefinePlan))]
+    fn.argtypes = _ARRAYS_ARGTYPES + [C.POINTER(C.POINTER(RefinePlan))]
     lib.hs_refine_plan_destroy.argtypes = [C.c_void_p]
     lib.hs_refine_plan_destroy.restype = None
     out_p = C.POINTER(RefinePlan)()
-    _check(fn(*(args + [None if params is None else C.byref(params), C.byref(out_p)])))
+    _check(fn(*(args + [C.byref(out_p)])))
     try:
         r = out_p.contents
         out = _consensus_result_dict(r.consensus.contents, B)

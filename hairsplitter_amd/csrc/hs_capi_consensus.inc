@@ -4,7 +4,9 @@
 // then rounds of whole bundles within HS_CONSENSUS_CHUNK_MB of row bytes go up and through the kernels. Two host waits a round: the number of
 // winning slots (their tables are sized by it), the result. Launches are accounted under HS_K_OTHER.
 // Behind it the resident route (consensus_resident, hs_polish_haplotypes): the pieces hs_polish_inputs' kernels cut stay on the device, k_cons_plan
-// plans them there, and both routes end in the same round body.
+// plans them there (cons_plan_step: one wait for the sizes), and both routes end in the same round body.
+// What both routes and the polishing passes (hs_capi_refine.inc) share is stated once: the checked input (cons_input_checked), the rounds'
+// cut (cons_budget, cons_cut_round), a round's tables (cons_round_tables), the plan step, the result's ending (cons_result_finish).
 
 #include "hs_haplotypes_host.h"
 
@@ -45,11 +47,15 @@ struct ConsRound {
 
 // what a round leaves on the device for a caller that goes on with it (the polishing passes, hs_capi_refine.inc): its two work blocks and, inside
 // them, the text, the decided columns, the winning slots and their lengths, the text offset of every column and of every bundle
-struct ConsKeep {
-    DBuf work, work2;
+struct ConsKeepViews {
     const uint8_t* text = nullptr; const uint8_t* col = nullptr; const int64_t* slot_index = nullptr; const int32_t* ins_len = nullptr; const int64_t* out_off = nullptr;
     const int64_t* cons_off = nullptr;
     int64_t n_slots = 0, text_cap = 0;
+};
+struct ConsKeep : ConsKeepViews {
+    DBuf work, work2;
+    ConsKeep() = default;
+    ConsKeep& operator=(ConsKeep&& o) { ConsKeepViews::operator=(o); work.take(o.work); work2.take(o.work2); return *this; }      // (the blocks change hands)
 };
 
 // from k_cons_rows to "the round into the result": two host waits. keep (null: as ever): the text stays on the device and the blocks go to *keep; the
@@ -138,23 +144,77 @@ int consensus_round_body(const char* who, const ConsRound& r, const hs_consensus
     H.n_ins_records += n_rec; H.n_ins_slots += W;
     if (moved) moved->down += 16 + (keep ? 0 : co[nb]) + (nb + 1) * 8 + 6 * nb * 4;
     if (keep) {
-        keep->text = text; keep->col = col; keep->slot_index = slot_index; keep->ins_len = ins_len; keep->out_off = out_off; keep->cons_off = d_cons_off;
-        keep->n_slots = W; keep->text_cap = text_cap;
+        static_cast<ConsKeepViews&>(*keep) = ConsKeepViews{text, col, slot_index, ins_len, out_off, d_cons_off, W, text_cap};
         keep->work.take(d_work); keep->work2.take(d_work2);
     }
     return HS_OK;
 }
 
+// ---- what the routes share ------------------------------------------------------------------------------------------------------------------
+// the arrays of a call as every route reads them: a call without pieces may leave base_off and cig_off out; then hs::consensus_check
+static int cons_input_checked(const char* who, const ConsInput& given, const hs_consensus_params& prm, ConsInput& in) {
+    in = given;
+    if (in.n_bundles >= 0 && in.piece_off && in.piece_off[in.n_bundles] == 0) { static const int64_t no_offsets[1] = {0}; in.base_off = in.cig_off = no_offsets; }
+    std::string err;
+    const int rc = hs::consensus_check(in.n_bundles, in.backbone_off, in.backbone, in.ovl, in.ovr, in.piece_off, in.sam, in.flags, in.base_off, in.bases, in.cig_off, in.cigar, prm, err);
+    if (rc) set_error(std::string(who) + ": " + err);
+    return rc;
+}
+
+// the row bytes a round may hold
+static int64_t cons_budget() {
+    const char* bud = std::getenv("HS_CONSENSUS_CHUNK_MB");
+    return std::max<int64_t>(1, bud ? std::atoll(bud) : 1024) * (1 << 20);
+}
+// the next round of z: whole bundles [s0, cut.s1), at least one, within the budget and 2^30 columns, and their sums. The first call (s0 == 0)
+// refuses a bundle that no round can hold, before anything runs; it is named by its place in the call, first_named + its place in z
+struct ConsBundleSize { int64_t row_bytes, n_rec, L; };
+struct ConsCut { int64_t s1, rb, n_rec, C; };
+static int cons_cut_round(const char* who, const std::vector<ConsBundleSize>& z, int64_t first_named, int64_t s0, ConsCut& cut) {
+    const int64_t budget = cons_budget(), max_cols = (int64_t)1 << 30, n = (int64_t)z.size();
+    for (int64_t k = 0; s0 == 0 && k < n; ++k)
+        if (z[(size_t)k].row_bytes > budget) {
+            set_error(std::string(who) + ": bundle " + std::to_string(first_named + k) + " alone takes " + std::to_string(z[(size_t)k].row_bytes) + " row bytes, more than HS_CONSENSUS_CHUNK_MB allows");
+            return HS_EINVAL;
+        }
+    cut = ConsCut{s0, 0, 0, 0};
+    for (; cut.s1 < n; ++cut.s1) {
+        const ConsBundleSize& b = z[(size_t)cut.s1];
+        if (cut.s1 > s0 && (cut.rb + b.row_bytes > budget || cut.C + b.L > max_cols)) break;
+        cut.rb += b.row_bytes; cut.n_rec += b.n_rec; cut.C += b.L;
+    }
+    return HS_OK;
+}
+
+// the one size check of a round: what the kernels index with an int
+static int cons_round_fits(const char* who, size_t n_tiles, int64_t n_rec) {
+    if (n_tiles <= (size_t)0x7fffffff && n_rec <= 0x7fffffff - 256) return HS_OK;
+    set_error(std::string(who) + ": a round is too large; lower HS_CONSENSUS_CHUNK_MB");
+    return HS_EINVAL;
+}
+// the bundles of a round -- bundle_at(k): column offset, piece range, L and overhangs, counted from the round's beginning -- and a tile per 256 columns
+template <class BundleAt>
+static int cons_round_tables(const char* who, int64_t nb, int64_t n_rec, BundleAt bundle_at, std::vector<hsdev::ConsBundle>& bundles, std::vector<hsdev::ConsTile>& tiles) {
+    bundles.resize((size_t)nb);
+    for (int64_t k = 0; k < nb; ++k) {
+        bundles[(size_t)k] = bundle_at(k);
+        for (int64_t t0 = 0; t0 < bundles[(size_t)k].L; t0 += 256) tiles.push_back(hsdev::ConsTile{(int32_t)k, (int32_t)t0});
+    }
+    return cons_round_fits(who, tiles.size(), n_rec);
+}
+
+// a result of the C ABI from H, the four kernel times and the number of rounds (null: out of host memory, named)
+static hs_consensus_result* cons_result_finish(const char* who, const hs::ConsensusHost& H, const double t_ms[4], int64_t n_rounds) {
+    hs_consensus_result* r = hs::consensus_result_from_host(H);
+    if (!r) { set_error(std::string(who) + ": out of host memory"); return nullptr; }
+    r->t_rows_ms = t_ms[0]; r->t_columns_ms = t_ms[1]; r->t_ins_ms = t_ms[2]; r->t_emit_ms = t_ms[3]; r->n_rounds = n_rounds;
+    return r;
+}
+
 int consensus_device(const char* who, const ConsInput& given, const hs_consensus_params& prm, hs_consensus_result** out) {
     using namespace hsdev;
-    std::string err;
-    ConsInput in = given;
-    static const int64_t no_offsets[1] = {0};
-    if (in.n_bundles >= 0 && in.piece_off && in.piece_off[in.n_bundles] == 0) { in.base_off = no_offsets; in.cig_off = no_offsets; }      // (a call without pieces may leave them out)
-    if (int rc = hs::consensus_check(in.n_bundles, in.backbone_off, in.backbone, in.ovl, in.ovr, in.piece_off, in.sam, in.flags, in.base_off, in.bases, in.cig_off, in.cigar, prm, err)) {
-        set_error(std::string(who) + ": " + err);
-        return rc;
-    }
+    ConsInput in;
+    if (int rc = cons_input_checked(who, given, prm, in)) return rc;
     const int64_t nb_all = in.n_bundles, n_pieces = in.piece_off[nb_all];
     // ---- the plan of every piece, on the host's threads
     std::vector<hs::ConsPiecePlan> plan((size_t)n_pieces);
@@ -168,82 +228,134 @@ int consensus_device(const char* who, const ConsInput& given, const hs_consensus
                                                   in.backbone_off[b + 1] - in.backbone_off[b]);
         }
     });
-    std::vector<int64_t> row_bytes((size_t)nb_all, 0);
+    std::vector<ConsBundleSize> sizes((size_t)nb_all);
+    for (int64_t b = 0; b < nb_all; ++b) sizes[(size_t)b] = ConsBundleSize{0, 0, in.backbone_off[b + 1] - in.backbone_off[b]};
     hs::ConsensusHost H;      // the result as it grows, round by round
     H.cons_off.assign(1, 0);
     H.n_skipped.assign((size_t)nb_all, 0);
     for (int64_t p = 0; p < n_pieces; ++p) {
         const int64_t b = piece_bundle[(size_t)p];
-        if (plan[(size_t)p].long_cigar) { set_error(std::string(who) + ": bundle " + std::to_string(b) + ": a CIGAR of more than 2^31 - 1 bases"); return HS_EINVAL; }
-        if (plan[(size_t)p].skipped) H.n_skipped[(size_t)b]++;
-        row_bytes[(size_t)b] += plan[(size_t)p].n_cols;
+        const hs::ConsPiecePlan& pl = plan[(size_t)p];
+        if (pl.long_cigar) { set_error(std::string(who) + ": bundle " + std::to_string(b) + ": a CIGAR of more than 2^31 - 1 bases"); return HS_EINVAL; }
+        if (pl.skipped) H.n_skipped[(size_t)b]++; else sizes[(size_t)b].n_rec += pl.n_ins;
+        sizes[(size_t)b].row_bytes += pl.n_cols;
     }
-    const char* bud = std::getenv("HS_CONSENSUS_CHUNK_MB");
-    const int64_t budget = std::max<int64_t>(1, bud ? std::atoll(bud) : 1024) * (1 << 20), max_cols = (int64_t)1 << 30;
-    for (int64_t b = 0; b < nb_all; ++b)
-        if (row_bytes[(size_t)b] > budget) {
-            set_error(std::string(who) + ": bundle " + std::to_string(b) + " alone takes " + std::to_string(row_bytes[(size_t)b]) + " row bytes, more than HS_CONSENSUS_CHUNK_MB allows");
-            return HS_EINVAL;
-        }
 
     hipStream_t st = nullptr;
     KernelClock kc;
     double t_ms[4] = {0, 0, 0, 0};
     int64_t n_rounds = 0;
-    for (int64_t b0 = 0; b0 < nb_all;) {
-        int64_t b1 = b0, rb = 0, C = 0;
-        while (b1 < nb_all) {      // whole bundles; at least one
-            const int64_t L = in.backbone_off[b1 + 1] - in.backbone_off[b1];
-            if (b1 > b0 && (rb + row_bytes[(size_t)b1] > budget || C + L > max_cols)) break;
-            rb += row_bytes[(size_t)b1]; C += L; ++b1;
-        }
+    ConsCut cut;
+    for (int64_t b0 = 0; b0 < nb_all; b0 = cut.s1) {
+        if (int rc = cons_cut_round(who, sizes, 0, b0, cut)) return rc;
         ++n_rounds;
-        const int64_t nb = b1 - b0, p0 = in.piece_off[b0], p1 = in.piece_off[b1], np = p1 - p0;
+        const int64_t b1 = cut.s1, nb = b1 - b0, p0 = in.piece_off[b0], p1 = in.piece_off[b1], np = p1 - p0;
         const int64_t base0 = in.base_off[p0], cig0 = in.cig_off[p0], bb0 = in.backbone_off[b0];
         // ---- the round's tables
         std::vector<ConsPiece> pieces((size_t)np);
-        std::vector<ConsBundle> bundles((size_t)nb);
+        std::vector<ConsBundle> bundles;
         std::vector<ConsTile> tiles;
-        int64_t n_rec = 0, row_at = 0;
-        for (int64_t b = b0; b < b1; ++b) {
-            const int64_t L = in.backbone_off[b + 1] - in.backbone_off[b], col_off = in.backbone_off[b] - bb0;
-            bundles[(size_t)(b - b0)] = ConsBundle{col_off, (int32_t)(in.piece_off[b] - p0), (int32_t)(in.piece_off[b + 1] - p0), (int32_t)L, in.ovl[b], in.ovr[b], 0};
-            for (int64_t t0 = 0; t0 < L; t0 += 256) tiles.push_back(ConsTile{(int32_t)(b - b0), (int32_t)t0});
-            for (int64_t p = in.piece_off[b]; p < in.piece_off[b + 1]; ++p) {
-                const hs::ConsPiecePlan& pl = plan[(size_t)p];
-                pieces[(size_t)(p - p0)] = ConsPiece{in.base_off[p] - base0, in.cig_off[p] - cig0, row_at, n_rec, col_off, (int32_t)(in.cig_off[p + 1] - in.cig_off[p]), in.sam[p] - 1,
-                                                     pl.skipped ? 0 : pl.n_cols, pl.skipped ? 0 : pl.n_ins};
-                if (!pl.skipped) { row_at += pl.n_cols; n_rec += pl.n_ins; }
-            }
+        if (int rc = cons_round_tables(who, nb, cut.n_rec, [&](int64_t k) {
+                const int64_t b = b0 + k;
+                return ConsBundle{in.backbone_off[b] - bb0, (int32_t)(in.piece_off[b] - p0), (int32_t)(in.piece_off[b + 1] - p0), (int32_t)sizes[(size_t)b].L, in.ovl[b], in.ovr[b], 0};
+            }, bundles, tiles)) return rc;
+        int64_t rec_at = 0, row_at = 0;
+        for (int64_t p = p0; p < p1; ++p) {
+            const hs::ConsPiecePlan& pl = plan[(size_t)p];
+            pieces[(size_t)(p - p0)] = ConsPiece{in.base_off[p] - base0, in.cig_off[p] - cig0, row_at, rec_at, bundles[(size_t)(piece_bundle[(size_t)p] - b0)].col_off,
+                                                 (int32_t)(in.cig_off[p + 1] - in.cig_off[p]), in.sam[p] - 1, pl.skipped ? 0 : pl.n_cols, pl.skipped ? 0 : pl.n_ins};
+            if (!pl.skipped) { row_at += pl.n_cols; rec_at += pl.n_ins; }
         }
-        if (tiles.size() > (size_t)0x7fffffff || n_rec > 0x7fffffff - 256) { set_error(std::string(who) + ": a round is too large; lower HS_CONSENSUS_CHUNK_MB"); return HS_EINVAL; }
         DBuf d_pieces, d_bundles, d_tiles, d_bases, d_cigar, d_bb;
         UploadPack pk;
         pk.add(pieces, d_pieces); pk.add(bundles, d_bundles); pk.add(tiles, d_tiles);
         if (int rc = pk.commit(st)) return rc;
         if (int rc = upload_pageable(d_bases, in.bases ? in.bases + base0 : nullptr, (size_t)(in.base_off[p1] - base0), 0, 16)) return rc;
         if (int rc = upload_pageable(d_cigar, in.cigar ? in.cigar + cig0 : nullptr, (size_t)(in.cig_off[p1] - cig0) * 4, 0, 16)) return rc;
-        if (int rc = upload_pageable(d_bb, in.backbone ? in.backbone + bb0 : nullptr, (size_t)C, 0, 16)) return rc;
+        if (int rc = upload_pageable(d_bb, in.backbone ? in.backbone + bb0 : nullptr, (size_t)cut.C, 0, 16)) return rc;
         const ConsRound round{d_bases.as<uint8_t>(), d_cigar.as<uint32_t>(), d_bb.as<uint8_t>(), d_pieces.as<ConsPiece>(), d_bundles.as<ConsBundle>(), d_tiles.as<ConsTile>(),
-                              np, nb, (int64_t)tiles.size(), rb, n_rec, C, in.base_off[p1] - base0, in.cig_off[p1] - cig0};
+                              np, nb, (int64_t)tiles.size(), cut.rb, cut.n_rec, cut.C, in.base_off[p1] - base0, in.cig_off[p1] - cig0};
         if (int rc = consensus_round_body(who, round, prm, st, kc, t_ms, H)) return rc;
-        b0 = b1;
     }
-    hs_consensus_result* r = hs::consensus_result_from_host(H);
-    if (!r) { set_error(std::string(who) + ": out of host memory"); return HS_EINVAL; }
-    r->t_rows_ms = t_ms[0]; r->t_columns_ms = t_ms[1]; r->t_ins_ms = t_ms[2]; r->t_emit_ms = t_ms[3]; r->n_rounds = n_rounds;
-    *out = r;
+    *out = cons_result_finish(who, H, t_ms, n_rounds);
+    return *out ? HS_OK : HS_EINVAL;
+}
+
+// ---- the plan step of the resident route and of every polishing pass: k_cons_plan plans np pieces against their bundles, two scans lay the
+// rows and the records out, and one shipment brings the sizes to the host -- one wait. The ship block, stated here alone:
+//   first_long (16 bytes) | ConsBundlePlan[nb] | extra_bytes of the caller's (a pass's RefineSums) | n_skipped[nb]
+// The step checks what came down against the bundles and refuses a CIGAR of more than 2^31 - 1 bases; named(piece) says whose it is.
+// before / after (either may be empty) launch in front of k_cons_plan and behind the scans, inside the step's one timed launch.
+struct ConsPlanStep {
+    DBuf work; HBuf ship, plan;      // the owners; plan: ConsPlan[np] on the host, where asked for
+    const hsdev::ConsBundlePlan* bplan = nullptr; const char* extra = nullptr; const int32_t* bskip = nullptr;      // host views of the ship block
+    int32_t* d_cols = nullptr; int32_t* d_recs = nullptr; int64_t* col_scan = nullptr; int64_t* rec_scan = nullptr; char* d_extra = nullptr;
+    float ms = 0;
+};
+using ConsPlanHook = std::function<int(const ConsPlanStep&)>;
+int cons_plan_step(const char* who, const hsdev::ConsPiece* d_pieces, int64_t np, const hsdev::ConsBundle* d_bundles, const std::vector<hsdev::ConsBundle>& bundles,
+                   const uint32_t* d_cig, int64_t traffic, int64_t extra_bytes, bool want_plan, const ConsPlanHook& before, const ConsPlanHook& after,
+                   const std::function<std::string(int64_t)>& named, hipStream_t st, KernelClock& kc, BytesMoved& moved, ConsPlanStep& s) {
+    using namespace hsdev;
+    const int64_t nb = (int64_t)bundles.size();
+    struct { int64_t plan, cols, recs, col_scan, rec_scan, tile_sum, ship; } w;
+    WorkParts wp;
+    w.plan = wp.take(np * (int64_t)sizeof(ConsPlan) + 16); w.cols = wp.take(np * 4 + 16); w.recs = wp.take(np * 4 + 16); w.col_scan = wp.take((np + 1) * 8 + 16);
+    w.rec_scan = wp.take((np + 1) * 8 + 16); w.tile_sum = wp.take((int64_t)std::max(scan_tiles(np), 1) * 16);
+    const int64_t extra_at = 16 + nb * (int64_t)sizeof(ConsBundlePlan), skip_at = extra_at + extra_bytes, ship_bytes = skip_at + nb * 4;
+    w.ship = wp.take(ship_bytes + 16);
+    if (int rc = s.work.alloc((size_t)wp.o)) return rc;
+    char* work = (char*)s.work.p;
+    ConsPlan* d_plan = (ConsPlan*)(work + w.plan);
+    s.d_cols = (int32_t*)(work + w.cols); s.d_recs = (int32_t*)(work + w.recs); s.col_scan = (int64_t*)(work + w.col_scan); s.rec_scan = (int64_t*)(work + w.rec_scan);
+    s.d_extra = work + w.ship + extra_at;
+    EventPair ev;
+    if (int rc = ev.take()) return rc;
+    if (int rc = timed_launch(kc, ev, st, traffic, [&]() -> int {
+            HS_HIP(hipMemsetAsync(work + w.ship, 0, (size_t)ship_bytes, st));
+            HS_HIP(hipMemsetAsync(work + w.ship, 0x7f, 4, st));      // (first_long: no piece yet)
+            if (before) { if (int rc = before(s)) return rc; }
+            if (np) hipLaunchKernelGGL(k_cons_plan, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, st, d_pieces, (int)np, d_bundles, d_cig, d_plan, s.d_cols, s.d_recs,
+                                       (ConsBundlePlan*)(work + w.ship + 16), (int32_t*)(work + w.ship + skip_at), (int32_t*)(work + w.ship));
+            HS_HIP(hipGetLastError());
+            if (int rc = exclusive_scan_launch(s.d_cols, (int)np, s.col_scan, (long long*)(work + w.tile_sum), st)) return rc;
+            if (int rc = exclusive_scan_launch(s.d_recs, (int)np, s.rec_scan, (long long*)(work + w.tile_sum), st)) return rc;      // (it takes the tile scratch over: the stream orders it)
+            return after ? after(s) : HS_OK; })) return rc;
+    if (int rc = s.ship.alloc((size_t)ship_bytes + 16)) return rc;
+    Shipment sh;
+    sh.add(s.ship.p, work + w.ship, (size_t)ship_bytes);
+    if (want_plan && np) {
+        if (int rc = s.plan.alloc((size_t)np * sizeof(ConsPlan) + 16)) return rc;
+        sh.add(s.plan.p, d_plan, (size_t)np * sizeof(ConsPlan));
+    }
+    if (int rc = sh.launch(st)) return rc;
+    if (int rc = stream_wait(st)) return rc;      // the wait for the sizes
+    kc.flush();
+    (void)ev.ms(&s.ms);
+    moved.down += ship_bytes + (want_plan ? np * (int64_t)sizeof(ConsPlan) : 0);
+    const char* h = (const char*)s.ship.p;
+    const int32_t first_long = *(const int32_t*)h;
+    s.bplan = (const ConsBundlePlan*)(h + 16); s.extra = h + extra_at; s.bskip = (const int32_t*)(h + skip_at);
+    if (first_long >= 0 && first_long < np) { set_error(std::string(who) + ": " + named(first_long) + ": a CIGAR of more than 2^31 - 1 bases"); return HS_EINVAL; }
+    for (int64_t k = 0; k < nb; ++k) {
+        const int64_t L = bundles[(size_t)k].L, n_own = bundles[(size_t)k].piece1 - bundles[(size_t)k].piece0;
+        if (s.bplan[k].row_bytes < 0 || s.bplan[k].row_bytes > L * n_own || s.bplan[k].n_rec < 0 || s.bplan[k].n_rec > s.bplan[k].row_bytes || s.bskip[k] < 0 || s.bskip[k] > n_own) {
+            set_error(std::string(who) + ": the device's plan does not fit the bundles");
+            return HS_EHIP;
+        }
+    }
     return HS_OK;
 }
 
 // ---- the resident route: the bundles [b0, b1) of `in` whose bases, CIGAR words and backbones lie on the device (d_*: where the range begins;
 // in.bases / in.cigar / in.backbone are not read). The host knows every offset, start, flag and base count, but not what a CIGAR sums to: the
-// plan of every piece is k_cons_plan's, two scans lay the rows and records out, and the sizes come to the host in one shipment (one wait).
-// Then sub-rounds of whole bundles within HS_CONSENSUS_CHUNK_MB, by the rule of consensus_device, through consensus_round_body (two waits each).
+// plan of every piece is the plan step's. Then sub-rounds of whole bundles within HS_CONSENSUS_CHUNK_MB, by the rule of
+// consensus_device (cons_cut_round): k_cons_layout, then consensus_round_body (two waits each) or, with passes, refine_sub_round.
 // H grows by the range's bundles (n_skipped included). plan_out (may be null): [4 * pieces of the range].
 struct ConsResidentStats { int64_t n_sub_rounds = 0; double t_plan_ms = 0; double t_ms[4] = {0, 0, 0, 0}; BytesMoved moved; };
-// the polishing passes of a sub-round (hs_capi_refine.inc, behind hs_capi_realign.inc: it takes the moves -> words route from there)
-struct RefineStats;
+// the polishing passes of a sub-round (hs_capi_refine.inc, behind hs_capi_realign.inc: it takes the moves -> words route from there); their
+// per-pass figures are summed straight into the block the C ABI returns
+using RefineStats = hs_refined_result;
 struct RefineSubRound {
     const hsdev::ConsPiece* d_src; const hsdev::ConsPiece* h_src; int64_t bundle_shift;      // the sub-round's pieces as k_cons_plan read them, on the device and on the host
     const std::vector<hsdev::ConsBundle>* bundles; const int32_t* n_skipped; int32_t* n_skipped_out;      // its bundles; pass 1's skipped pieces; where the last pass's go
@@ -272,96 +384,41 @@ int consensus_resident(const char* who, const ConsInput& in, int64_t b0, int64_t
                                                  (int32_t)(in.base_off[p + 1] - in.base_off[p]), in.flags[p]};
         }
     }
-    // ---- the plan and the layout
-    struct Parts { int64_t plan, cols, recs, col_scan, rec_scan, tile_sum, ship, total; } w;
-    WorkParts wp;
-    w.plan = wp.take(np * (int64_t)sizeof(ConsPlan) + 16); w.cols = wp.take(np * 4 + 16); w.recs = wp.take(np * 4 + 16); w.col_scan = wp.take((np + 1) * 8 + 16);
-    w.rec_scan = wp.take((np + 1) * 8 + 16); w.tile_sum = wp.take((int64_t)std::max(scan_tiles(np), 1) * 16);
-    const int64_t ship_bytes = 16 + nb * (int64_t)sizeof(ConsBundlePlan) + nb * 4;      // first_long; row bytes and records; n_skipped
-    w.ship = wp.take(ship_bytes + 16);
-    w.total = wp.o;
-    DBuf d_pieces, d_bundles, d_work;
+    // ---- the plan
+    DBuf d_pieces, d_bundles;
     UploadPack pk;
     pk.add(pieces, d_pieces); pk.add(bundles, d_bundles);
     stats.moved.up += (int64_t)pk.total;
     if (int rc = pk.commit(st)) return rc;
-    if (int rc = d_work.alloc((size_t)w.total)) return rc;
-    char* work = (char*)d_work.p;
-    ConsPlan* d_plan = (ConsPlan*)(work + w.plan);
-    int32_t* d_cols = (int32_t*)(work + w.cols); int32_t* d_recs = (int32_t*)(work + w.recs);
-    int64_t* col_scan = (int64_t*)(work + w.col_scan); int64_t* rec_scan = (int64_t*)(work + w.rec_scan);
-    int32_t* d_first_long = (int32_t*)(work + w.ship);
-    ConsBundlePlan* d_bplan = (ConsBundlePlan*)(work + w.ship + 16);
-    int32_t* d_bskip = (int32_t*)(work + w.ship + 16 + nb * (int64_t)sizeof(ConsBundlePlan));
     KernelClock kc;
-    EventPair ev_plan;
-    if (int rc = ev_plan.take()) return rc;
-    if (int rc = timed_launch(kc, ev_plan, st, (in.cig_off[p1] - cig0) * 4 + np * (int64_t)(sizeof(ConsPiece) + sizeof(ConsPlan) + 8), [&]() -> int {
-            HS_HIP(hipMemsetAsync(work + w.ship, 0, (size_t)ship_bytes, st));
-            HS_HIP(hipMemsetAsync(d_first_long, 0x7f, 4, st));
-            if (np) hipLaunchKernelGGL(k_cons_plan, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, st, d_pieces.as<ConsPiece>(), (int)np, d_bundles.as<ConsBundle>(), d_cig, d_plan, d_cols,
-                                       d_recs, d_bplan, d_bskip, d_first_long);
-            HS_HIP(hipGetLastError());
-            if (int rc = exclusive_scan_launch(d_cols, (int)np, col_scan, (long long*)(work + w.tile_sum), st)) return rc;
-            return exclusive_scan_launch(d_recs, (int)np, rec_scan, (long long*)(work + w.tile_sum), st); })) return rc;      // (it takes the tile scratch over: the stream orders it)
-    HBuf h_ship, h_plan;
-    if (int rc = h_ship.alloc((size_t)ship_bytes + 16)) return rc;
-    Shipment sh;
-    sh.add(h_ship.p, work + w.ship, (size_t)ship_bytes);
-    if (plan_out && np) {
-        if (int rc = h_plan.alloc((size_t)np * sizeof(ConsPlan) + 16)) return rc;
-        sh.add(h_plan.p, d_plan, (size_t)np * sizeof(ConsPlan));
-    }
-    if (int rc = sh.launch(st)) return rc;
-    if (int rc = stream_wait(st)) return rc;      // the wait for the sizes
-    kc.flush();
-    { float ms = 0; if (ev_plan.ms(&ms) == HS_OK) stats.t_plan_ms += ms; }
-    stats.moved.down += ship_bytes + (plan_out ? np * (int64_t)sizeof(ConsPlan) : 0);
-    if (plan_out && np) std::memcpy(plan_out, h_plan.p, (size_t)np * sizeof(ConsPlan));
-    const int32_t first_long = *(const int32_t*)h_ship.p;
-    const ConsBundlePlan* bplan = (const ConsBundlePlan*)((const char*)h_ship.p + 16);
-    const int32_t* bskip = (const int32_t*)((const char*)h_ship.p + 16 + nb * (int64_t)sizeof(ConsBundlePlan));
-    if (first_long >= 0 && first_long < np) {
-        int64_t b = b0;
-        while (b + 1 < b1 && in.piece_off[b + 1] <= p0 + first_long) ++b;
-        set_error(std::string(who) + ": bundle " + std::to_string(b) + ": a CIGAR of more than 2^31 - 1 bases");
-        return HS_EINVAL;
-    }
-    const char* bud = std::getenv("HS_CONSENSUS_CHUNK_MB");
-    const int64_t budget = std::max<int64_t>(1, bud ? std::atoll(bud) : 1024) * (1 << 20), max_cols = (int64_t)1 << 30;
-    for (int64_t k = 0; k < nb; ++k) {
-        const int64_t L = bundles[(size_t)k].L, n_own = bundles[(size_t)k].piece1 - bundles[(size_t)k].piece0;
-        if (bplan[k].row_bytes < 0 || bplan[k].row_bytes > L * n_own || bplan[k].n_rec < 0 || bplan[k].n_rec > bplan[k].row_bytes || bskip[k] < 0 || bskip[k] > n_own) {
-            set_error(std::string(who) + ": the device's plan does not fit the bundles");
-            return HS_EHIP;
-        }
-        if (bplan[k].row_bytes > budget) {
-            set_error(std::string(who) + ": bundle " + std::to_string(b0 + k) + " alone takes " + std::to_string(bplan[k].row_bytes) + " row bytes, more than HS_CONSENSUS_CHUNK_MB allows");
-            return HS_EINVAL;
-        }
-    }
-    for (int64_t k = 0; k < nb; ++k) H.n_skipped.push_back(bskip[k]);
+    ConsPlanStep plan;
+    if (int rc = cons_plan_step(who, d_pieces.as<ConsPiece>(), np, d_bundles.as<ConsBundle>(), bundles, d_cig, (in.cig_off[p1] - cig0) * 4 + np * (int64_t)(sizeof(ConsPiece) + sizeof(ConsPlan) + 8),
+                                0, plan_out != nullptr, nullptr, nullptr, [&](int64_t piece) {
+                                    int64_t b = b0;
+                                    while (b + 1 < b1 && in.piece_off[b + 1] <= p0 + piece) ++b;
+                                    return "bundle " + std::to_string(b); },
+                                st, kc, stats.moved, plan)) return rc;
+    stats.t_plan_ms += plan.ms;
+    if (plan_out && np) std::memcpy(plan_out, plan.plan.p, (size_t)np * sizeof(ConsPlan));
+    std::vector<ConsBundleSize> sizes((size_t)nb);
+    for (int64_t k = 0; k < nb; ++k) sizes[(size_t)k] = ConsBundleSize{plan.bplan[k].row_bytes, plan.bplan[k].n_rec, bundles[(size_t)k].L};
+    H.n_skipped.insert(H.n_skipped.end(), plan.bskip, plan.bskip + nb);
     const size_t skipped_at = H.n_skipped.size() - (size_t)nb;
 
     // ---- sub-rounds of whole bundles
-    for (int64_t s0 = 0; s0 < nb;) {
-        int64_t s1 = s0, rb = 0, C = 0, n_rec = 0;
-        while (s1 < nb) {      // whole bundles; at least one
-            const int64_t L = bundles[(size_t)s1].L;
-            if (s1 > s0 && (rb + bplan[s1].row_bytes > budget || C + L > max_cols)) break;
-            rb += bplan[s1].row_bytes; n_rec += bplan[s1].n_rec; C += L; ++s1;
-        }
+    ConsCut cut;
+    for (int64_t s0 = 0; s0 < nb; s0 = cut.s1) {
+        if (int rc = cons_cut_round(who, sizes, b0, s0, cut)) return rc;
         ++stats.n_sub_rounds;
-        const int64_t q0 = bundles[(size_t)s0].piece0, q1 = bundles[(size_t)(s1 - 1)].piece1, nq = q1 - q0, col0 = bundles[(size_t)s0].col_off;
+        const int64_t s1 = cut.s1, q0 = bundles[(size_t)s0].piece0, q1 = bundles[(size_t)(s1 - 1)].piece1, nq = q1 - q0, col0 = bundles[(size_t)s0].col_off;
         const int64_t sbase0 = nq ? pieces[(size_t)q0].base_off : 0, scig0 = nq ? pieces[(size_t)q0].cig_off : 0;
         const int64_t sbase1 = q1 < np ? pieces[(size_t)q1].base_off : (np ? in.base_off[p1] - base0 : 0), scig1 = q1 < np ? pieces[(size_t)q1].cig_off : (np ? in.cig_off[p1] - cig0 : 0);
-        std::vector<ConsBundle> sb(bundles.begin() + s0, bundles.begin() + s1);
+        std::vector<ConsBundle> sb;
         std::vector<ConsTile> tiles;
-        for (int64_t k = 0; k < s1 - s0; ++k) {
-            sb[(size_t)k].col_off -= col0; sb[(size_t)k].piece0 -= (int32_t)q0; sb[(size_t)k].piece1 -= (int32_t)q0;
-            for (int64_t t0 = 0; t0 < sb[(size_t)k].L; t0 += 256) tiles.push_back(ConsTile{(int32_t)k, (int32_t)t0});
-        }
-        if (tiles.size() > (size_t)0x7fffffff || n_rec > 0x7fffffff - 256) { set_error(std::string(who) + ": a round is too large; lower HS_CONSENSUS_CHUNK_MB"); return HS_EINVAL; }
+        if (int rc = cons_round_tables(who, s1 - s0, cut.n_rec, [&](int64_t k) {
+                ConsBundle b = bundles[(size_t)(s0 + k)];
+                b.col_off -= col0; b.piece0 -= (int32_t)q0; b.piece1 -= (int32_t)q0;
+                return b; }, sb, tiles)) return rc;
         DBuf d_sb, d_tiles, d_sp;
         UploadPack spk;
         spk.add(sb, d_sb); spk.add(tiles, d_tiles);
@@ -371,32 +428,27 @@ int consensus_resident(const char* who, const ConsInput& in, int64_t b0, int64_t
         EventPair ev_lay;
         if (int rc = ev_lay.take()) return rc;
         if (int rc = timed_launch(kc, ev_lay, st, nq * (int64_t)(2 * sizeof(ConsPiece) + 24), [&]() -> int {
-                if (nq) hipLaunchKernelGGL(k_cons_layout, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_pieces.as<ConsPiece>(), (long long)q0, (int)nq, d_cols, d_recs, col_scan,
-                                           rec_scan, (long long)sbase0, (long long)scig0, (long long)col0, d_sp.as<ConsPiece>());
+                if (nq) hipLaunchKernelGGL(k_cons_layout, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_pieces.as<ConsPiece>(), (long long)q0, (int)nq, plan.d_cols, plan.d_recs,
+                                           plan.col_scan, plan.rec_scan, (long long)sbase0, (long long)scig0, (long long)col0, d_sp.as<ConsPiece>());
                 HS_HIP(hipGetLastError());
                 return HS_OK; })) return rc;
         const ConsRound round{d_bases + sbase0, d_cig + scig0, d_bb + col0, d_sp.as<ConsPiece>(), d_sb.as<ConsBundle>(), d_tiles.as<ConsTile>(),
-                              nq, s1 - s0, (int64_t)tiles.size(), rb, n_rec, C, sbase1 - sbase0, scig1 - scig0};
+                              nq, s1 - s0, (int64_t)tiles.size(), cut.rb, cut.n_rec, cut.C, sbase1 - sbase0, scig1 - scig0};
         if (refine && n_passes > 1) {
-            const RefineSubRound sr{d_pieces.as<ConsPiece>() + q0, pieces.data() + q0, s0, &sb, bskip + s0, H.n_skipped.data() + skipped_at + s0, d_bases + sbase0, sbase1 - sbase0};
+            const RefineSubRound sr{d_pieces.as<ConsPiece>() + q0, pieces.data() + q0, s0, &sb, plan.bskip + s0, H.n_skipped.data() + skipped_at + s0, d_bases + sbase0, sbase1 - sbase0};
             if (int rc = refine_sub_round(who, round, sr, prm, st, kc, n_passes, H, stats, *refine)) return rc;
         } else if (int rc = consensus_round_body(who, round, prm, st, kc, stats.t_ms, H, &stats.moved)) return rc;
         { float ms = 0; if (ev_lay.ms(&ms) == HS_OK) stats.t_plan_ms += ms; }
-        s0 = s1;
     }
     return HS_OK;
 }
 
-// the arrays of consensus_device, checked as it checks them and uploaded whole, then the resident route
-int consensus_planned_tap(const char* who, const ConsInput& given, const hs_consensus_params& prm, int32_t* plan_out, hs_consensus_result** out) {
-    std::string err;
-    ConsInput in = given;
-    static const int64_t no_offsets[1] = {0};
-    if (in.n_bundles >= 0 && in.piece_off && in.piece_off[in.n_bundles] == 0) { in.base_off = no_offsets; in.cig_off = no_offsets; }
-    if (int rc = hs::consensus_check(in.n_bundles, in.backbone_off, in.backbone, in.ovl, in.ovr, in.piece_off, in.sam, in.flags, in.base_off, in.bases, in.cig_off, in.cigar, prm, err)) {
-        set_error(std::string(who) + ": " + err);
-        return rc;
-    }
+// the arrays of consensus_device, checked as it checks them and uploaded whole, then the resident route: one pass through consensus_round_body
+// (refine null), more through refine_sub_round. stats (may be null): the route's figures for a caller that reports them
+int consensus_arrays_resident(const char* who, const ConsInput& given, const hs_consensus_params& prm, int32_t* plan_out, hs_consensus_result** out, ConsResidentStats* stats_out = nullptr,
+                              RefineStats* refine = nullptr, int32_t n_passes = 1) {
+    ConsInput in;
+    if (int rc = cons_input_checked(who, given, prm, in)) return rc;
     const int64_t nb = in.n_bundles, np = in.piece_off[nb];
     DBuf d_bases, d_cigar, d_bb;
     if (int rc = upload_pageable(d_bases, in.bases, (size_t)in.base_off[np], 0, 16)) return rc;
@@ -405,12 +457,10 @@ int consensus_planned_tap(const char* who, const ConsInput& given, const hs_cons
     hs::ConsensusHost H;
     H.cons_off.assign(1, 0);
     ConsResidentStats stats;
-    if (int rc = consensus_resident(who, in, 0, nb, d_bases.as<uint8_t>(), d_cigar.as<uint32_t>(), d_bb.as<uint8_t>(), prm, nullptr, H, stats, plan_out)) return rc;
-    hs_consensus_result* r = hs::consensus_result_from_host(H);
-    if (!r) { set_error(std::string(who) + ": out of host memory"); return HS_EINVAL; }
-    r->t_rows_ms = stats.t_ms[0]; r->t_columns_ms = stats.t_ms[1]; r->t_ins_ms = stats.t_ms[2]; r->t_emit_ms = stats.t_ms[3]; r->n_rounds = stats.n_sub_rounds;
-    *out = r;
-    return HS_OK;
+    if (int rc = consensus_resident(who, in, 0, nb, d_bases.as<uint8_t>(), d_cigar.as<uint32_t>(), d_bb.as<uint8_t>(), prm, nullptr, H, stats, plan_out, refine, n_passes)) return rc;
+    if (stats_out) *stats_out = stats;
+    *out = cons_result_finish(who, H, stats.t_ms, stats.n_sub_rounds);
+    return *out ? HS_OK : HS_EINVAL;
 }
 
 // ---- from labels to haplotype sequences: hs_polish_inputs' rounds with the consensus as their sink
@@ -427,14 +477,34 @@ int haplotypes_core(const char* who, hs_cv_batch* b, int c0, int c1, const std::
     hs_polish_result* inputs = nullptr;
     if (int rc = polish_inputs_core(b, c0, c1, ivs, has, polish_everything, &inputs, &sink, &stats.moved)) return rc;
     std::unique_ptr<hs_polish_result, void (*)(hs_polish_result*)> iguard(inputs, hs_polish_result_destroy);
-    hs_consensus_result* cons = hs::consensus_result_from_host(H);
+    hs_consensus_result* cons = cons_result_finish(who, H, stats.t_ms, stats.n_sub_rounds);
     hs_haplotypes_result* res = static_cast<hs_haplotypes_result*>(std::calloc(1, sizeof(hs_haplotypes_result)));
     if (!cons || !res) { hs_consensus_result_destroy(cons); std::free(res); set_error(std::string(who) + ": out of host memory"); return HS_EINVAL; }
-    cons->t_rows_ms = stats.t_ms[0]; cons->t_columns_ms = stats.t_ms[1]; cons->t_ins_ms = stats.t_ms[2]; cons->t_emit_ms = stats.t_ms[3]; cons->n_rounds = stats.n_sub_rounds;
     res->inputs = iguard.release(); res->consensus = cons;
     res->n_rounds = inputs->n_rounds; res->n_sub_rounds = stats.n_sub_rounds; res->bytes_down = stats.moved.down; res->bytes_up = stats.moved.up; res->t_plan_ms = stats.t_plan_ms;
     *out = res;
     return HS_OK;
+}
+
+// the one body of hs_polish_haplotypes and hs_polish_haplotypes_refined (refine null: one pass): the labels into intervals, then haplotypes_core
+int haplotypes_labels(const char* who, hs_cv_batch* b, int32_t c0, int32_t c1, const int64_t* win_off, const int32_t* win_start, const int32_t* win_end, const int64_t* label_off,
+                      const int32_t* labels, const uint8_t* contig_has_snps, int32_t polish_everything, const hs_consensus_params* params, hs_haplotypes_result** out,
+                      RefineStats* refine, int32_t n_passes) {
+    if (!b || !out || !win_off || !label_off || c0 < 0 || c1 < c0 || c1 > b->n_contigs) { set_error(std::string(who) + ": bad arguments"); return HS_EINVAL; }
+    *out = nullptr;
+    const hs_consensus_params prm = params ? *params : hs_consensus_default_params();
+    if (!hs::consensus_params_valid(prm)) { set_error(std::string(who) + ": parameters out of range (min_cov >= 1, max_ins 1..64)"); return HS_EINVAL; }
+    if (int rc = bind_device(b->device)) return rc;
+    try {
+        BytesMoved moved;
+        if (int rc = polish_host_recs(b, &moved)) return rc;
+        std::vector<std::vector<hs::LabelledInterval>> ivs;
+        std::vector<uint8_t> has;
+        if (int rc = hs::polish_intervals_from_labels(b->n_contigs, b->contig_rec_off.data(), b->h_rec_read.data(), win_off, win_start, win_end, label_off, labels,
+                                                      contig_has_snps, ivs, has))
+            return rc;
+        return haplotypes_core(who, b, c0, c1, ivs, has, polish_everything != 0, prm, moved, out, refine, n_passes);
+    } catch (const std::exception& e) { set_error(std::string(who) + ": " + e.what()); return HS_EINVAL; }
 }
 
 }  // namespace
@@ -451,21 +521,7 @@ void hs_haplotypes_result_destroy(hs_haplotypes_result* r) {
 int hs_polish_haplotypes(hs_cv_batch* b, int32_t c0, int32_t c1, const int64_t* win_off, const int32_t* win_start, const int32_t* win_end, const int64_t* label_off,
                          const int32_t* labels, const uint8_t* contig_has_snps, int32_t polish_everything, const hs_consensus_params* params, hs_haplotypes_result** out) {
     if (int rc = require_device()) return rc;
-    if (!b || !out || !win_off || !label_off || c0 < 0 || c1 < c0 || c1 > b->n_contigs) { set_error("hs_polish_haplotypes: bad arguments"); return HS_EINVAL; }
-    *out = nullptr;
-    const hs_consensus_params prm = params ? *params : hs_consensus_default_params();
-    if (!hs::consensus_params_valid(prm)) { set_error("hs_polish_haplotypes: parameters out of range (min_cov >= 1, max_ins 1..64)"); return HS_EINVAL; }
-    if (int rc = bind_device(b->device)) return rc;
-    try {
-        BytesMoved moved;
-        if (int rc = polish_host_recs(b, &moved)) return rc;
-        std::vector<std::vector<hs::LabelledInterval>> ivs;
-        std::vector<uint8_t> has;
-        if (int rc = hs::polish_intervals_from_labels(b->n_contigs, b->contig_rec_off.data(), b->h_rec_read.data(), win_off, win_start, win_end, label_off, labels,
-                                                      contig_has_snps, ivs, has))
-            return rc;
-        return haplotypes_core("hs_polish_haplotypes", b, c0, c1, ivs, has, polish_everything != 0, prm, moved, out);
-    } catch (const std::exception& e) { set_error(std::string("hs_polish_haplotypes: ") + e.what()); return HS_EINVAL; }
+    return haplotypes_labels("hs_polish_haplotypes", b, c0, c1, win_off, win_start, win_end, label_off, labels, contig_has_snps, polish_everything, params, out, nullptr, 1);
 }
 
 // the one body of hs_polish_haplotypes_from_files and hs_polish_haplotypes_refined_from_files (refine null: one pass)
@@ -521,7 +577,7 @@ int hs_polish_consensus_planned_tap(int64_t n_bundles, const int64_t* backbone_o
     if (!out) { set_error("hs_polish_consensus_planned_tap: bad arguments"); return HS_EINVAL; }
     *out = nullptr;
     const ConsInput in{n_bundles, backbone_off, backbone, overhang_left, overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar};
-    try { return consensus_planned_tap("hs_polish_consensus_planned_tap", in, params ? *params : hs_consensus_default_params(), plan_out, out); }
+    try { return consensus_arrays_resident("hs_polish_consensus_planned_tap", in, params ? *params : hs_consensus_default_params(), plan_out, out); }
     catch (const std::exception& e) { set_error(std::string("hs_polish_consensus_planned_tap: ") + e.what()); return HS_EINVAL; }
 }
 

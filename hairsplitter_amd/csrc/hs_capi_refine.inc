@@ -1,27 +1,20 @@
 // hs_capi_refine.inc -- part of hs_capi.hip: polishing passes (include/hairsplitter_hip.h: hs_polish_haplotypes_refined), the host side of
-// hs_kernels_refine.hip. The rule is hs_refine_host.h's. Passes run inside a consensus sub-round of the resident route (consensus_resident): when pass
-// p - 1 ends its text, out_off, ins_len and pieces are on the device (ConsKeep), and pass p is
+// hs_kernels_refine.hip. The rule is hs_refine_host.h's. Passes run inside a consensus sub-round of the resident route (consensus_resident) as one
+// loop over p: pass 1 votes on the sub-round as it came; when pass p - 1 ends, its text, out_off, ins_len and pieces are on the device (ConsKeep), and pass p is
 //   k_refine_windows + two scans -> one shipment of ws, we per piece (16 B; the wait that sizes the buffers: A1's launcher takes host offsets)
 //   k_refine_gather twice (queries, targets) -> A1 (hs_edlib_align: NW, PATH, k = -1) in chunks of HS_REALIGN_CHUNK_MB, a wait each
-//   moves -> words (MovesToCigar: k_m2c_count, the scan, k_m2c_write; two waits) -> k_refine_pieces, k_cons_plan, two scans, k_cons_layout -> one
-//   shipment of the bundles' sizes and the pass's sums (a wait) -> consensus_round_body on the kept text as backbone (two waits).
+//   moves -> words (MovesToCigar: k_m2c_count, the scan, k_m2c_write; two waits) -> the plan step (cons_plan_step) with k_refine_pieces in front of
+//   k_cons_plan, k_cons_layout behind the scans and the pass's sums in the shipment (its wait) -> consensus_round_body on the kept text
+//   as backbone (two waits).
 // 6 + the A1 chunks waits a pass and sub-round. The intermediate texts never come down.
 #include "hs_refine_host.h"
 
 namespace {
 
-struct RefineStats {
-    int64_t n_sub[HS_REFINE_MAX_PASSES] = {}, n_del[HS_REFINE_MAX_PASSES] = {}, n_ins_bases[HS_REFINE_MAX_PASSES] = {}, n_low[HS_REFINE_MAX_PASSES] = {}, n_skipped[HS_REFINE_MAX_PASSES] = {};
-    int64_t n_pairs[HS_REFINE_MAX_PASSES] = {}, n_unaligned[HS_REFINE_MAX_PASSES] = {}, sum_dist[HS_REFINE_MAX_PASSES] = {}, move_bytes[HS_REFINE_MAX_PASSES] = {}, cigar_words[HS_REFINE_MAX_PASSES] = {};
-    double t_windows[HS_REFINE_MAX_PASSES] = {}, t_align[HS_REFINE_MAX_PASSES] = {}, t_cigar[HS_REFINE_MAX_PASSES] = {}, t_plan[HS_REFINE_MAX_PASSES] = {}, t_cons[HS_REFINE_MAX_PASSES] = {};
-    int64_t n_waits[HS_REFINE_MAX_PASSES] = {};
-};
-
-// the bundles [at, at + nb) of a result into the sums of pass index k
-static void refine_count_pass(RefineStats& rs, int k, const hs::ConsensusHost& H, size_t at, int64_t nb, const int32_t* skipped) {
+// the per-bundle figures of nb bundles into the sums of pass index k
+static void refine_add_sums(RefineStats& rs, int k, int64_t nb, const int32_t* n_sub, const int32_t* n_del, const int32_t* n_ins_bases, const int32_t* n_low, const int32_t* n_skipped) {
     for (int64_t b = 0; b < nb; ++b) {
-        rs.n_sub[k] += H.n_sub[at + (size_t)b]; rs.n_del[k] += H.n_del[at + (size_t)b]; rs.n_ins_bases[k] += H.n_ins_bases[at + (size_t)b]; rs.n_low[k] += H.n_low[at + (size_t)b];
-        rs.n_skipped[k] += skipped[b];
+        rs.n_sub[k] += n_sub[b]; rs.n_del[k] += n_del[b]; rs.n_ins_bases[k] += n_ins_bases[b]; rs.n_low[k] += n_low[b]; rs.n_skipped[k] += n_skipped[b];
     }
 }
 
@@ -31,10 +24,6 @@ static bool refine_passes_valid(const char* who, int32_t n_passes) {
     return false;
 }
 
-}  // namespace
-
-namespace {
-
 int refine_sub_round(const char* who, const ConsRound& first, const RefineSubRound& sr, const hs_consensus_params& prm, hipStream_t st, KernelClock& kc, int32_t n_passes,
                      hs::ConsensusHost& H, ConsResidentStats& stats, RefineStats& rs) {
     using namespace hsdev;
@@ -42,232 +31,182 @@ int refine_sub_round(const char* who, const ConsRound& first, const RefineSubRou
     auto waits = [] { return (int64_t)g_waits.load(); };
     auto wall = [] { return std::chrono::steady_clock::now(); };
     auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-    // ---- pass 1: the round as ever, its text and column arrays kept
-    ConsKeep keep;
-    hs::ConsensusHost Hp;      // pass p - 1's offsets and figures (no text)
-    Hp.cons_off.assign(1, 0);
-    {
-        double tms[4] = {0, 0, 0, 0};
-        const int64_t w0 = waits();
-        if (int rc = consensus_round_body(who, first, prm, st, kc, tms, Hp, &stats.moved, &keep)) return rc;
-        rs.n_waits[0] += waits() - w0; rs.t_cons[0] += tms[0] + tms[1] + tms[2] + tms[3];
-        refine_count_pass(rs, 0, Hp, 0, nbs, sr.n_skipped);
-    }
+    ConsKeep keep;             // pass p - 1's text and column arrays
+    hs::ConsensusHost Hp;      // its offsets and figures (no text)
     const ConsPiece* d_src = sr.d_src;
     const ConsPiece* d_laid = first.pieces;
     int64_t shift = sr.bundle_shift;
     DBuf d_src_own, d_laid_own;      // pass p - 1's pieces from pass 2 on
-    // (a pass realigns the bundles of its sub-round as one round, whatever HS_CONSENSUS_CHUNK_MB: its rows are the windows', a few bytes beside pass 1's)
-    for (int32_t p = 2; p <= n_passes; ++p) {
+    for (int32_t p = 1; p <= n_passes; ++p) {
         const bool last = p == n_passes;
         const int k = p - 1;
         const int64_t w0 = waits();
-        const int64_t text_len = Hp.cons_off[(size_t)nbs];
-        // ---- the windows, the pairs' lengths and their offsets; 16 bytes a piece come down
-        struct { int64_t win, q_len, t_len, q_src, t_src, q_off, t_off, tile_sum, total; } w;
-        WorkParts wp;
-        w.win = wp.take(nq * (int64_t)sizeof(RefineWin) + 16); w.q_len = wp.take(nq * 4 + 16); w.t_len = wp.take(nq * 4 + 16); w.q_src = wp.take(nq * 8 + 16); w.t_src = wp.take(nq * 8 + 16);
-        w.q_off = wp.take((nq + 1) * 8 + 16); w.t_off = wp.take((nq + 1) * 8 + 16); w.tile_sum = wp.take((int64_t)std::max(scan_tiles(nq), 1) * 16);
-        w.total = wp.o;
-        DBuf d_work;
-        if (int rc = d_work.alloc((size_t)w.total)) return rc;
-        char* work = (char*)d_work.p;
-        RefineWin* d_win = (RefineWin*)(work + w.win);
-        int64_t* d_q_off = (int64_t*)(work + w.q_off); int64_t* d_t_off = (int64_t*)(work + w.t_off);
-        EventPair ev_win, ev_gather, ev_plan;
-        if (int rc = ev_win.take()) return rc;
-        if (int rc = ev_gather.take()) return rc;
-        if (int rc = ev_plan.take()) return rc;
-        if (int rc = timed_launch(kc, ev_win, st, nq * (int64_t)(2 * sizeof(ConsPiece) + sizeof(RefineWin) + 64), [&]() -> int {
-                if (nq) hipLaunchKernelGGL(k_refine_windows, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_src, d_laid, (int)nq, keep.col, keep.slot_index, (long long)keep.n_slots,
-                                           keep.ins_len, keep.out_off, d_win, (int32_t*)(work + w.q_len), (int32_t*)(work + w.t_len), (int64_t*)(work + w.q_src), (int64_t*)(work + w.t_src));
-                HS_HIP(hipGetLastError());
-                if (int rc = exclusive_scan_launch((const int32_t*)(work + w.q_len), (int)nq, d_q_off, (long long*)(work + w.tile_sum), st)) return rc;
-                return exclusive_scan_launch((const int32_t*)(work + w.t_len), (int)nq, d_t_off, (long long*)(work + w.tile_sum), st); })) return rc;      // (it takes the tile scratch over: the stream orders it)
-        HBuf h_win;
-        if (int rc = h_win.alloc((size_t)nq * sizeof(RefineWin) + 16)) return rc;
-        Shipment sh;
-        sh.add(h_win.p, d_win, (size_t)nq * sizeof(RefineWin));
-        if (int rc = sh.launch(st)) return rc;
-        if (int rc = stream_wait(st)) return rc;      // the wait for the windows
-        stats.moved.down += nq * (int64_t)sizeof(RefineWin);
-        // ---- the pairs that go to the aligner, in piece order: their host offsets
-        const RefineWin* hw = (const RefineWin*)h_win.p;
-        std::vector<int32_t> pair_of((size_t)nq, -1);
-        std::vector<int64_t> q_off(1, 0), t_off(1, 0), o_off(1, 0);
-        for (int64_t i = 0; i < nq; ++i) {
-            const int64_t ws = hw[i].ws, we = hw[i].we, n_bases = sr.h_src[i].n_cols;
-            if (!((ws == -1 && we == -1) || (ws >= 0 && ws <= we && we <= text_len))) { set_error(std::string(who) + ": the device's windows do not fit the consensus"); return HS_EHIP; }
-            if (ws < 0 || we == ws || n_bases <= 0) continue;
-            pair_of[(size_t)i] = (int32_t)(q_off.size() - 1);
-            q_off.push_back(q_off.back() + n_bases); t_off.push_back(t_off.back() + (we - ws)); o_off.push_back(o_off.back() + n_bases + (we - ws));
-        }
-        const int64_t m = (int64_t)q_off.size() - 1, q_total = q_off.back(), t_total = t_off.back();
-        rs.n_pairs[k] += m;
-        DBuf d_pair_of, d_q, d_t, d_dist, d_start, d_end, d_len, d_ops, d_word_off, d_words, d_next, d_laid_next;
-        UploadPack pk;
-        pk.add(pair_of, d_pair_of);
-        stats.moved.up += (int64_t)pk.total;
-        if (int rc = pk.commit(st)) return rc;
-        const int64_t q_bytes = (q_total + 15) & ~(int64_t)15, t_bytes = (t_total + 15) & ~(int64_t)15;
-        if (int rc = d_q.alloc((size_t)q_bytes + 16)) return rc;
-        if (int rc = d_t.alloc((size_t)t_bytes + 16)) return rc;
-        for (DBuf* b : {&d_dist, &d_start, &d_end, &d_len}) if (int rc = b->alloc((size_t)std::max<int64_t>(m, 1) * sizeof(int32_t))) return rc;
-        if (int rc = d_ops.alloc((size_t)o_off.back() + 16)) return rc;
-        if (int rc = d_word_off.alloc((size_t)(m + 1) * sizeof(int64_t))) return rc;
-        // ---- the coded queries and targets, pair behind pair
-        if (int rc = timed_launch(kc, ev_gather, st, 2 * (q_total + t_total) + 32 * nq, [&]() -> int {
-                if (q_bytes) hipLaunchKernelGGL(k_refine_gather, dim3((unsigned)((q_bytes + 4095) >> 12)), dim3(256), 0, st, d_q_off, (const int64_t*)(work + w.q_src), (int)nq, sr.d_bases,
-                                                d_q.as<uint8_t>(), q_bytes);
-                if (t_bytes) hipLaunchKernelGGL(k_refine_gather, dim3((unsigned)((t_bytes + 4095) >> 12)), dim3(256), 0, st, d_t_off, (const int64_t*)(work + w.t_src), (int)nq, keep.text,
-                                                d_t.as<uint8_t>(), t_bytes);
-                HS_HIP(hipGetLastError());
-                return HS_OK; })) return rc;
-        // ---- A1 (synchronous), in chunks bounded as hs_realign_intervals bounds its rounds
-        auto t0 = wall();
-        const int64_t chunk_bases = (int64_t)hs::realign_chunk_bases();
-        for (int64_t k0 = 0; k0 < m;) {
-            int64_t k1 = k0 + 1;
-            while (k1 < m && o_off[(size_t)k1] - o_off[(size_t)k0] < chunk_bases && k1 - k0 < 1000000) ++k1;
-            if (int rc = hs_edlib_align(d_q.as<uint8_t>(), q_off.data() + k0, d_t.as<uint8_t>(), t_off.data() + k0, (int32_t)(k1 - k0), 0, 2, -1, d_dist.as<int32_t>() + k0,
-                                        d_start.as<int32_t>() + k0, d_end.as<int32_t>() + k0, nullptr, d_ops.as<uint8_t>(), o_off.data() + k0, d_len.as<int32_t>() + k0, st))
-                return rc;
-            k0 = k1;
-        }
-        rs.t_align[k] += ms_since(t0);
-        // ---- moves -> words: a pair without a path gets none; behind them room for the one word of every empty window
-        t0 = wall();
-        MovesToCigar mc;
-        int64_t n_words = 0;
-        if (m > 0) { if (int rc = mc.count(d_ops.as<uint8_t>(), o_off.data(), d_len.as<int32_t>(), nullptr, nullptr, (int32_t)m, d_word_off.as<int64_t>(), nullptr, &n_words, st)) return rc; }
-        if (n_words < 0 || n_words > o_off.back()) { set_error(std::string(who) + ": the device's word count does not fit the moves"); return HS_EHIP; }
-        if (int rc = d_words.alloc((size_t)(n_words + nq + 4) * sizeof(uint32_t))) return rc;
-        if (m > 0) { if (int rc = mc.write(d_words.as<uint32_t>(), st)) return rc; }
-        rs.t_cigar[k] += ms_since(t0);
-        rs.cigar_words[k] += n_words;
-        // ---- pass p's bundles (the host knows pass p - 1's offsets and trims), its pieces and their plan
-        std::vector<ConsBundle> bun((size_t)nbs);
-        std::vector<ConsTile> tiles;
-        for (int64_t b = 0; b < nbs; ++b) {
-            const int64_t L = Hp.cons_off[(size_t)b + 1] - Hp.cons_off[(size_t)b];
-            const ConsBundle& ob = (*sr.bundles)[(size_t)b];
-            bun[(size_t)b] = ConsBundle{Hp.cons_off[(size_t)b], ob.piece0, ob.piece1, (int32_t)L, hs::refine_overhang_left(Hp.trim_start[(size_t)b]),
-                                        hs::refine_overhang_right(L, Hp.trim_end[(size_t)b]), 0};
-            for (int64_t t = 0; t < L; t += 256) tiles.push_back(ConsTile{(int32_t)b, (int32_t)t});
-        }
-        if (tiles.size() > (size_t)0x7fffffff) { set_error(std::string(who) + ": a round is too large; lower HS_CONSENSUS_CHUNK_MB"); return HS_EINVAL; }
-        struct { int64_t plan, cols, recs, col_scan, rec_scan, tile_sum, ship, total; } v;
-        WorkParts vp;
-        v.plan = vp.take(nq * (int64_t)sizeof(ConsPlan) + 16); v.cols = vp.take(nq * 4 + 16); v.recs = vp.take(nq * 4 + 16); v.col_scan = vp.take((nq + 1) * 8 + 16);
-        v.rec_scan = vp.take((nq + 1) * 8 + 16); v.tile_sum = vp.take((int64_t)std::max(scan_tiles(nq), 1) * 16);
-        const int64_t sums_at = 16 + nbs * (int64_t)sizeof(ConsBundlePlan), skip_at = sums_at + (int64_t)sizeof(RefineSums);      // first_long; row bytes and records; the sums; n_skipped
-        const int64_t ship_bytes = skip_at + nbs * 4;
-        v.ship = vp.take(ship_bytes + 16);
-        v.total = vp.o;
-        DBuf d_bun, d_tiles, d_plan_work;
+        // ---- what pass p votes on: the sub-round as it came, or (from pass 2 on) its pieces realigned to pass p - 1's text. A pass realigns the bundles
+        // of its sub-round as one round, whatever HS_CONSENSUS_CHUNK_MB: its rows are the windows', a few bytes beside pass 1's
+        ConsRound round = first;
+        const int32_t* skipped = sr.n_skipped;
+        DBuf d_words, d_next, d_laid_next, d_bun, d_tiles;      // (what the round of a later pass points into)
         UploadPack bpk;
-        bpk.add(bun, d_bun); bpk.add(tiles, d_tiles);
-        stats.moved.up += (int64_t)bpk.total;
-        if (int rc = bpk.commit(st)) return rc;
-        if (int rc = d_plan_work.alloc((size_t)v.total)) return rc;
-        if (int rc = d_next.alloc((size_t)std::max<int64_t>(nq, 1) * sizeof(ConsPiece))) return rc;
-        if (int rc = d_laid_next.alloc((size_t)std::max<int64_t>(nq, 1) * sizeof(ConsPiece))) return rc;
-        char* pw = (char*)d_plan_work.p;
-        int32_t* d_cols = (int32_t*)(pw + v.cols); int32_t* d_recs = (int32_t*)(pw + v.recs);
-        int64_t* col_scan = (int64_t*)(pw + v.col_scan); int64_t* rec_scan = (int64_t*)(pw + v.rec_scan);
-        if (int rc = timed_launch(kc, ev_plan, st, n_words * 4 + nq * (int64_t)(4 * sizeof(ConsPiece) + sizeof(ConsPlan) + 64), [&]() -> int {
-                HS_HIP(hipMemsetAsync(pw + v.ship, 0, (size_t)ship_bytes, st));
-                HS_HIP(hipMemsetAsync(pw + v.ship, 0x7f, 4, st));
-                if (nq) {
-                    hipLaunchKernelGGL(k_refine_pieces, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_src, d_laid, (int)nq, (long long)shift, d_win, d_pair_of.as<int32_t>(),
-                                       d_word_off.as<int64_t>(), (long long)n_words, d_dist.as<int32_t>(), d_len.as<int32_t>(), keep.cons_off, d_words.as<uint32_t>(),
-                                       d_next.as<ConsPiece>(), (RefineSums*)(pw + v.ship + sums_at));
-                    hipLaunchKernelGGL(k_cons_plan, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, d_next.as<ConsPiece>(), (int)nq, d_bun.as<ConsBundle>(), d_words.as<uint32_t>(),
-                                       (ConsPlan*)(pw + v.plan), d_cols, d_recs, (ConsBundlePlan*)(pw + v.ship + 16), (int32_t*)(pw + v.ship + skip_at), (int32_t*)(pw + v.ship));
-                }
-                HS_HIP(hipGetLastError());
-                if (int rc = exclusive_scan_launch(d_cols, (int)nq, col_scan, (long long*)(pw + v.tile_sum), st)) return rc;
-                if (int rc = exclusive_scan_launch(d_recs, (int)nq, rec_scan, (long long*)(pw + v.tile_sum), st)) return rc;
-                if (nq) hipLaunchKernelGGL(k_cons_layout, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_next.as<ConsPiece>(), 0ll, (int)nq, d_cols, d_recs, col_scan, rec_scan, 0ll, 0ll,
-                                           0ll, d_laid_next.as<ConsPiece>());
-                HS_HIP(hipGetLastError());
-                return HS_OK; })) return rc;
-        HBuf h_ship;
-        if (int rc = h_ship.alloc((size_t)ship_bytes + 16)) return rc;
-        Shipment sh2;
-        sh2.add(h_ship.p, pw + v.ship, (size_t)ship_bytes);
-        if (int rc = sh2.launch(st)) return rc;
-        if (int rc = stream_wait(st)) return rc;      // the wait for the sizes
-        kc.flush();
-        stats.moved.down += ship_bytes;
-        { float a = 0, b = 0, c = 0; if (ev_win.ms(&a) == HS_OK && ev_gather.ms(&b) == HS_OK) rs.t_windows[k] += a + b; if (ev_plan.ms(&c) == HS_OK) rs.t_plan[k] += c; }
-        const int32_t first_long = *(const int32_t*)h_ship.p;
-        const ConsBundlePlan* bplan = (const ConsBundlePlan*)((const char*)h_ship.p + 16);
-        const RefineSums* sums = (const RefineSums*)((const char*)h_ship.p + sums_at);
-        const int32_t* bskip = (const int32_t*)((const char*)h_ship.p + skip_at);
-        if (first_long >= 0 && first_long < nq) { set_error(std::string(who) + ": pass " + std::to_string(p) + ": a CIGAR of more than 2^31 - 1 bases"); return HS_EINVAL; }
-        int64_t rb = 0, n_rec = 0;
-        for (int64_t b = 0; b < nbs; ++b) {
-            const int64_t L = bun[(size_t)b].L, n_own = bun[(size_t)b].piece1 - bun[(size_t)b].piece0;
-            if (bplan[b].row_bytes < 0 || bplan[b].row_bytes > L * n_own || bplan[b].n_rec < 0 || bplan[b].n_rec > bplan[b].row_bytes || bskip[b] < 0 || bskip[b] > n_own) {
-                set_error(std::string(who) + ": the device's plan does not fit the bundles");
-                return HS_EHIP;
+        ConsPlanStep plan;
+        if (p > 1) {
+            const int64_t text_len = Hp.cons_off[(size_t)nbs];
+            // ---- the windows, the pairs' lengths and their offsets; 16 bytes a piece come down
+            struct { int64_t win, q_len, t_len, q_src, t_src, q_off, t_off, tile_sum, total; } w;
+            WorkParts wp;
+            w.win = wp.take(nq * (int64_t)sizeof(RefineWin) + 16); w.q_len = wp.take(nq * 4 + 16); w.t_len = wp.take(nq * 4 + 16); w.q_src = wp.take(nq * 8 + 16); w.t_src = wp.take(nq * 8 + 16);
+            w.q_off = wp.take((nq + 1) * 8 + 16); w.t_off = wp.take((nq + 1) * 8 + 16); w.tile_sum = wp.take((int64_t)std::max(scan_tiles(nq), 1) * 16);
+            w.total = wp.o;
+            DBuf d_work;
+            if (int rc = d_work.alloc((size_t)w.total)) return rc;
+            char* work = (char*)d_work.p;
+            RefineWin* d_win = (RefineWin*)(work + w.win);
+            int64_t* d_q_off = (int64_t*)(work + w.q_off); int64_t* d_t_off = (int64_t*)(work + w.t_off);
+            EventPair ev_win, ev_gather;
+            if (int rc = ev_win.take()) return rc;
+            if (int rc = ev_gather.take()) return rc;
+            if (int rc = timed_launch(kc, ev_win, st, nq * (int64_t)(2 * sizeof(ConsPiece) + sizeof(RefineWin) + 64), [&]() -> int {
+                    if (nq) hipLaunchKernelGGL(k_refine_windows, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_src, d_laid, (int)nq, keep.col, keep.slot_index, (long long)keep.n_slots,
+                                               keep.ins_len, keep.out_off, d_win, (int32_t*)(work + w.q_len), (int32_t*)(work + w.t_len), (int64_t*)(work + w.q_src), (int64_t*)(work + w.t_src));
+                    HS_HIP(hipGetLastError());
+                    if (int rc = exclusive_scan_launch((const int32_t*)(work + w.q_len), (int)nq, d_q_off, (long long*)(work + w.tile_sum), st)) return rc;
+                    return exclusive_scan_launch((const int32_t*)(work + w.t_len), (int)nq, d_t_off, (long long*)(work + w.tile_sum), st); })) return rc;      // (it takes the tile scratch over: the stream orders it)
+            HBuf h_win;
+            if (int rc = h_win.alloc((size_t)nq * sizeof(RefineWin) + 16)) return rc;
+            Shipment sh;
+            sh.add(h_win.p, d_win, (size_t)nq * sizeof(RefineWin));
+            if (int rc = sh.launch(st)) return rc;
+            if (int rc = stream_wait(st)) return rc;      // the wait for the windows
+            stats.moved.down += nq * (int64_t)sizeof(RefineWin);
+            // ---- the pairs that go to the aligner, in piece order: their host offsets
+            const RefineWin* hw = (const RefineWin*)h_win.p;
+            std::vector<int32_t> pair_of((size_t)nq, -1);
+            std::vector<int64_t> q_off(1, 0), t_off(1, 0), o_off(1, 0);
+            for (int64_t i = 0; i < nq; ++i) {
+                const int64_t ws = hw[i].ws, we = hw[i].we, n_bases = sr.h_src[i].n_cols;
+                if (!((ws == -1 && we == -1) || (ws >= 0 && ws <= we && we <= text_len))) { set_error(std::string(who) + ": the device's windows do not fit the consensus"); return HS_EHIP; }
+                if (ws < 0 || we == ws || n_bases <= 0) continue;
+                pair_of[(size_t)i] = (int32_t)(q_off.size() - 1);
+                q_off.push_back(q_off.back() + n_bases); t_off.push_back(t_off.back() + (we - ws)); o_off.push_back(o_off.back() + n_bases + (we - ws));
             }
-            rb += bplan[b].row_bytes; n_rec += bplan[b].n_rec;
-        }
-        if (n_rec > 0x7fffffff - 256) { set_error(std::string(who) + ": a round is too large; lower HS_CONSENSUS_CHUNK_MB"); return HS_EINVAL; }
-        rs.n_unaligned[k] += sums->n_unaligned; rs.sum_dist[k] += sums->sum_dist; rs.move_bytes[k] += sums->move_bytes;
-        // ---- the vote, pass p - 1's text as the backbone
-        const ConsRound round{sr.d_bases, d_words.as<uint32_t>(), keep.text, d_laid_next.as<ConsPiece>(), d_bun.as<ConsBundle>(), d_tiles.as<ConsTile>(),
+            const int64_t m = (int64_t)q_off.size() - 1, q_total = q_off.back(), t_total = t_off.back();
+            rs.n_pairs[k] += m;
+            DBuf d_pair_of, d_q, d_t, d_dist, d_start, d_end, d_len, d_ops, d_word_off;
+            UploadPack pk;
+            pk.add(pair_of, d_pair_of);
+            stats.moved.up += (int64_t)pk.total;
+            if (int rc = pk.commit(st)) return rc;
+            const int64_t q_bytes = (q_total + 15) & ~(int64_t)15, t_bytes = (t_total + 15) & ~(int64_t)15;
+            if (int rc = d_q.alloc((size_t)q_bytes + 16)) return rc;
+            if (int rc = d_t.alloc((size_t)t_bytes + 16)) return rc;
+            for (DBuf* b : {&d_dist, &d_start, &d_end, &d_len}) if (int rc = b->alloc((size_t)std::max<int64_t>(m, 1) * sizeof(int32_t))) return rc;
+            if (int rc = d_ops.alloc((size_t)o_off.back() + 16)) return rc;
+            if (int rc = d_word_off.alloc((size_t)(m + 1) * sizeof(int64_t))) return rc;
+            // ---- the coded queries and targets, pair behind pair
+            if (int rc = timed_launch(kc, ev_gather, st, 2 * (q_total + t_total) + 32 * nq, [&]() -> int {
+                    if (q_bytes) hipLaunchKernelGGL(k_refine_gather, dim3((unsigned)((q_bytes + 4095) >> 12)), dim3(256), 0, st, d_q_off, (const int64_t*)(work + w.q_src), (int)nq, sr.d_bases,
+                                                    d_q.as<uint8_t>(), q_bytes);
+                    if (t_bytes) hipLaunchKernelGGL(k_refine_gather, dim3((unsigned)((t_bytes + 4095) >> 12)), dim3(256), 0, st, d_t_off, (const int64_t*)(work + w.t_src), (int)nq, keep.text,
+                                                    d_t.as<uint8_t>(), t_bytes);
+                    HS_HIP(hipGetLastError());
+                    return HS_OK; })) return rc;
+            // ---- A1 (synchronous), in chunks bounded as hs_realign_intervals bounds its rounds
+            auto t0 = wall();
+            const int64_t chunk_bases = (int64_t)hs::realign_chunk_bases();
+            for (int64_t k0 = 0; k0 < m;) {
+                int64_t k1 = k0 + 1;
+                while (k1 < m && o_off[(size_t)k1] - o_off[(size_t)k0] < chunk_bases && k1 - k0 < 1000000) ++k1;
+                if (int rc = hs_edlib_align(d_q.as<uint8_t>(), q_off.data() + k0, d_t.as<uint8_t>(), t_off.data() + k0, (int32_t)(k1 - k0), 0, 2, -1, d_dist.as<int32_t>() + k0,
+                                            d_start.as<int32_t>() + k0, d_end.as<int32_t>() + k0, nullptr, d_ops.as<uint8_t>(), o_off.data() + k0, d_len.as<int32_t>() + k0, st))
+                    return rc;
+                k0 = k1;
+            }
+            rs.t_align_ms[k] += ms_since(t0);
+            // ---- moves -> words: a pair without a path gets none; behind them room for the one word of every empty window
+            t0 = wall();
+            MovesToCigar mc;
+            int64_t n_words = 0;
+            if (m > 0) { if (int rc = mc.count(d_ops.as<uint8_t>(), o_off.data(), d_len.as<int32_t>(), nullptr, nullptr, (int32_t)m, d_word_off.as<int64_t>(), nullptr, &n_words, st)) return rc; }
+            if (n_words < 0 || n_words > o_off.back()) { set_error(std::string(who) + ": the device's word count does not fit the moves"); return HS_EHIP; }
+            if (int rc = d_words.alloc((size_t)(n_words + nq + 4) * sizeof(uint32_t))) return rc;
+            if (m > 0) { if (int rc = mc.write(d_words.as<uint32_t>(), st)) return rc; }
+            rs.t_cigar_ms[k] += ms_since(t0);
+            rs.cigar_words[k] += n_words;
+            // ---- pass p's bundles (the host knows pass p - 1's offsets and trims), its pieces and their plan
+            std::vector<ConsBundle> bun;
+            std::vector<ConsTile> tiles;
+            if (int rc = cons_round_tables(who, nbs, 0, [&](int64_t b) {
+                    const int64_t L = Hp.cons_off[(size_t)b + 1] - Hp.cons_off[(size_t)b];
+                    const ConsBundle& ob = (*sr.bundles)[(size_t)b];
+                    return ConsBundle{Hp.cons_off[(size_t)b], ob.piece0, ob.piece1, (int32_t)L, hs::refine_overhang_left(Hp.trim_start[(size_t)b]), hs::refine_overhang_right(L, Hp.trim_end[(size_t)b]), 0};
+                }, bun, tiles)) return rc;
+            bpk.add(bun, d_bun); bpk.add(tiles, d_tiles);
+            stats.moved.up += (int64_t)bpk.total;
+            if (int rc = bpk.commit(st)) return rc;
+            if (int rc = d_next.alloc((size_t)std::max<int64_t>(nq, 1) * sizeof(ConsPiece))) return rc;
+            if (int rc = d_laid_next.alloc((size_t)std::max<int64_t>(nq, 1) * sizeof(ConsPiece))) return rc;
+            if (int rc = cons_plan_step(who, d_next.as<ConsPiece>(), nq, d_bun.as<ConsBundle>(), bun, d_words.as<uint32_t>(), n_words * 4 + nq * (int64_t)(4 * sizeof(ConsPiece) + sizeof(ConsPlan) + 64),
+                                        (int64_t)sizeof(RefineSums), false,
+                                        [&](const ConsPlanStep& s) -> int {
+                                            if (nq) hipLaunchKernelGGL(k_refine_pieces, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_src, d_laid, (int)nq, (long long)shift, d_win,
+                                                                       d_pair_of.as<int32_t>(), d_word_off.as<int64_t>(), (long long)n_words, d_dist.as<int32_t>(), d_len.as<int32_t>(), keep.cons_off,
+                                                                       d_words.as<uint32_t>(), d_next.as<ConsPiece>(), (RefineSums*)s.d_extra);
+                                            return HS_OK; },
+                                        [&](const ConsPlanStep& s) -> int {
+                                            if (nq) hipLaunchKernelGGL(k_cons_layout, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_next.as<ConsPiece>(), 0ll, (int)nq, s.d_cols, s.d_recs,
+                                                                       s.col_scan, s.rec_scan, 0ll, 0ll, 0ll, d_laid_next.as<ConsPiece>());
+                                            HS_HIP(hipGetLastError());
+                                            return HS_OK; },
+                                        [&](int64_t) { return "pass " + std::to_string(p); }, st, kc, stats.moved, plan)) return rc;
+            { float a = 0, b = 0; if (ev_win.ms(&a) == HS_OK && ev_gather.ms(&b) == HS_OK) rs.t_windows_ms[k] += a + b; }
+            rs.t_plan_ms[k] += plan.ms;
+            int64_t rb = 0, n_rec = 0;
+            for (int64_t b = 0; b < nbs; ++b) { rb += plan.bplan[b].row_bytes; n_rec += plan.bplan[b].n_rec; }
+            if (int rc = cons_round_fits(who, 0, n_rec)) return rc;
+            const RefineSums* sums = (const RefineSums*)plan.extra;
+            rs.n_unaligned[k] += sums->n_unaligned; rs.sum_dist[k] += sums->sum_dist; rs.move_bytes[k] += sums->move_bytes;
+            // (pass p - 1's text is the backbone)
+            round = ConsRound{sr.d_bases, d_words.as<uint32_t>(), keep.text, d_laid_next.as<ConsPiece>(), d_bun.as<ConsBundle>(), d_tiles.as<ConsTile>(),
                               nq, nbs, (int64_t)tiles.size(), rb, n_rec, text_len, sr.n_base, n_words + nq};
+            skipped = plan.bskip;
+        }
+        // ---- the vote: the last pass's into the caller's result with its text; an earlier one's text and column arrays stay on the device for the next
+        hs::ConsensusHost Hn;
+        Hn.cons_off.assign(1, 0);
+        ConsKeep keep_next;
+        hs::ConsensusHost& into = last ? H : Hn;
+        const size_t at = into.n_sub.size();
         double tms[4] = {0, 0, 0, 0};
+        if (int rc = consensus_round_body(who, round, prm, st, kc, tms, into, &stats.moved, last ? nullptr : &keep_next)) return rc;
+        refine_add_sums(rs, k, nbs, into.n_sub.data() + at, into.n_del.data() + at, into.n_ins_bases.data() + at, into.n_low.data() + at, skipped);
         if (last) {
-            const size_t at = H.n_sub.size();
-            if (int rc = consensus_round_body(who, round, prm, st, kc, tms, H, &stats.moved)) return rc;
-            refine_count_pass(rs, k, H, at, nbs, bskip);
-            for (int64_t b = 0; b < nbs; ++b) sr.n_skipped_out[b] = bskip[b];
+            for (int64_t b = 0; b < nbs; ++b) sr.n_skipped_out[b] = skipped[b];
             for (int j = 0; j < 4; ++j) stats.t_ms[j] += tms[j];
         } else {
-            ConsKeep keep_next;
-            hs::ConsensusHost Hn;
-            Hn.cons_off.assign(1, 0);
-            if (int rc = consensus_round_body(who, round, prm, st, kc, tms, Hn, &stats.moved, &keep_next)) return rc;
-            refine_count_pass(rs, k, Hn, 0, nbs, bskip);
             // (the body has waited for the stream: nothing reads pass p - 1's blocks any more)
-            keep.work.take(keep_next.work); keep.work2.take(keep_next.work2);
-            keep.text = keep_next.text; keep.col = keep_next.col; keep.slot_index = keep_next.slot_index; keep.ins_len = keep_next.ins_len; keep.out_off = keep_next.out_off;
-            keep.cons_off = keep_next.cons_off; keep.n_slots = keep_next.n_slots; keep.text_cap = keep_next.text_cap;
+            keep = std::move(keep_next);
             Hp = std::move(Hn);
-            d_src_own.take(d_next); d_laid_own.take(d_laid_next);
-            d_src = d_src_own.as<ConsPiece>(); d_laid = d_laid_own.as<ConsPiece>(); shift = 0;
+            if (p > 1) { d_src_own.take(d_next); d_laid_own.take(d_laid_next); d_src = d_src_own.as<ConsPiece>(); d_laid = d_laid_own.as<ConsPiece>(); shift = 0; }
         }
-        rs.t_cons[k] += tms[0] + tms[1] + tms[2] + tms[3];
+        rs.t_consensus_ms[k] += tms[0] + tms[1] + tms[2] + tms[3];
         rs.n_waits[k] += waits() - w0;
     }
     return HS_OK;
 }
 
-// a RefineStats and the last pass's result as the malloc'd result of the C ABI; `last` is taken over (destroyed where the result cannot be made)
+// the sums of the call and the last pass's result as the malloc'd result of the C ABI; `last` is taken over (destroyed where the result cannot be made)
 static int refined_result_make(const char* who, const RefineStats& rs, int32_t n_passes, hs_haplotypes_result* last, hs_refined_result** out) {
     hs_refined_result* r = static_cast<hs_refined_result*>(std::calloc(1, sizeof(hs_refined_result)));
     if (!r) { hs_haplotypes_result_destroy(last); set_error(std::string(who) + ": out of host memory"); return HS_EINVAL; }
+    *r = rs;
     r->last = last; r->n_passes = n_passes;
-    for (int k = 0; k < HS_REFINE_MAX_PASSES; ++k) {
-        r->n_sub[k] = rs.n_sub[k]; r->n_del[k] = rs.n_del[k]; r->n_ins_bases[k] = rs.n_ins_bases[k]; r->n_low[k] = rs.n_low[k]; r->n_skipped[k] = rs.n_skipped[k];
-        r->n_pairs[k] = rs.n_pairs[k]; r->n_unaligned[k] = rs.n_unaligned[k]; r->sum_dist[k] = rs.sum_dist[k]; r->move_bytes[k] = rs.move_bytes[k]; r->cigar_words[k] = rs.cigar_words[k];
-        r->t_windows_ms[k] = rs.t_windows[k]; r->t_align_ms[k] = rs.t_align[k]; r->t_cigar_ms[k] = rs.t_cigar[k]; r->t_plan_ms[k] = rs.t_plan[k]; r->t_consensus_ms[k] = rs.t_cons[k];
-        r->n_waits[k] = rs.n_waits[k];
-    }
     *out = r;
     return HS_OK;
 }
 // pass 1's sums of a one-pass result, and its waits: everything the call waited for that no later pass did
 static void refine_first_pass(RefineStats& rs, const hs_consensus_result* c, int32_t n_passes, int64_t waits_of_call) {
     if (n_passes == 1) {
-        for (int64_t b = 0; b < c->n_bundles; ++b) {
-            rs.n_sub[0] += c->n_sub[b]; rs.n_del[0] += c->n_del[b]; rs.n_ins_bases[0] += c->n_ins_bases[b]; rs.n_low[0] += c->n_low[b]; rs.n_skipped[0] += c->n_skipped[b];
-        }
-        rs.t_cons[0] = c->t_rows_ms + c->t_columns_ms + c->t_ins_ms + c->t_emit_ms;
+        refine_add_sums(rs, 0, c->n_bundles, c->n_sub, c->n_del, c->n_ins_bases, c->n_low, c->n_skipped);
+        rs.t_consensus_ms[0] = c->t_rows_ms + c->t_columns_ms + c->t_ins_ms + c->t_emit_ms;
     }
     rs.n_waits[0] = waits_of_call;
     for (int k = 1; k < n_passes; ++k) rs.n_waits[0] -= rs.n_waits[k];
@@ -292,26 +231,28 @@ void hs_refined_result_destroy(hs_refined_result* r) {
 int hs_polish_refine_plan_host(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left, const int32_t* overhang_right,
                                const int64_t* piece_off, const int32_t* piece_sam_pos, const int32_t* piece_flags, const int64_t* base_off, const uint8_t* bases,
                                const int64_t* cig_off, const uint32_t* cigar, const hs_consensus_params* params, hs_refine_plan** out) {
-    if (!out) { set_error("hs_polish_refine_plan_host: bad arguments"); return HS_EINVAL; }
+    const char* who = "hs_polish_refine_plan_host";
+    if (!out) { set_error(std::string(who) + ": bad arguments"); return HS_EINVAL; }
     *out = nullptr;
     try {
+        const hs_consensus_params prm = params ? *params : hs_consensus_default_params();
+        ConsInput in;
+        if (int rc = cons_input_checked(who, ConsInput{n_bundles, backbone_off, backbone, overhang_left, overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar}, prm, in))
+            return rc;
         hs::RefinePlanHost P;
         std::string err;
-        static const int64_t no_offsets[1] = {0};
-        if (n_bundles >= 0 && piece_off && piece_off[n_bundles] == 0) { base_off = no_offsets; cig_off = no_offsets; }      // (a call without pieces may leave them out)
         const char* th = std::getenv("HS_CONSENSUS_HOST_THREADS");
         const int n_threads = th ? std::max(1, std::atoi(th)) : hs::host_threads();
-        if (int rc = hs::refine_plan_host(n_bundles, backbone_off, backbone, overhang_left, overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar,
-                                          params ? *params : hs_consensus_default_params(), n_threads, P, err)) {
-            set_error("hs_polish_refine_plan_host: " + err);
+        if (int rc = hs::refine_plan_host(in.n_bundles, in.backbone_off, in.backbone, in.ovl, in.ovr, in.piece_off, in.sam, in.flags, in.base_off, in.bases, in.cig_off, in.cigar, prm, n_threads, P, err)) {
+            set_error(std::string(who) + ": " + err);
             return rc;
         }
         hs_refine_plan* r = hs::refine_plan_from_host(P);
-        if (!r) { set_error("hs_polish_refine_plan_host: out of host memory"); return HS_EINVAL; }
+        if (!r) { set_error(std::string(who) + ": out of host memory"); return HS_EINVAL; }
         r->consensus->n_rounds = 0;
         *out = r;
         return HS_OK;
-    } catch (const std::exception& e) { set_error(std::string("hs_polish_refine_plan_host: ") + e.what()); return HS_EINVAL; }
+    } catch (const std::exception& e) { set_error(std::string(who) + ": " + e.what()); return HS_EINVAL; }
 }
 
 int hs_polish_refine_arrays(int64_t n_bundles, const int64_t* backbone_off, const uint8_t* backbone, const int32_t* overhang_left, const int32_t* overhang_right,
@@ -325,34 +266,13 @@ int hs_polish_refine_arrays(int64_t n_bundles, const int64_t* backbone_off, cons
     const hs_consensus_params prm = params ? *params : hs_consensus_default_params();
     try {
         const int64_t waits0 = (int64_t)g_waits.load();
-        RefineStats rs;
+        const ConsInput in{n_bundles, backbone_off, backbone, overhang_left, overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar};
+        RefineStats rs{};
         ConsResidentStats stats;
         hs_consensus_result* c = nullptr;
-        if (n_passes == 1) {
-            const ConsInput in{n_bundles, backbone_off, backbone, overhang_left, overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar};
-            if (int rc = consensus_planned_tap(who, in, prm, nullptr, &c)) return rc;
-            stats.n_sub_rounds = c->n_rounds;
-        } else {
-            std::string err;
-            ConsInput in{n_bundles, backbone_off, backbone, overhang_left, overhang_right, piece_off, piece_sam_pos, piece_flags, base_off, bases, cig_off, cigar};
-            static const int64_t no_offsets[1] = {0};
-            if (in.n_bundles >= 0 && in.piece_off && in.piece_off[in.n_bundles] == 0) { in.base_off = no_offsets; in.cig_off = no_offsets; }
-            if (int rc = hs::consensus_check(in.n_bundles, in.backbone_off, in.backbone, in.ovl, in.ovr, in.piece_off, in.sam, in.flags, in.base_off, in.bases, in.cig_off, in.cigar, prm, err)) {
-                set_error(std::string(who) + ": " + err);
-                return rc;
-            }
-            const int64_t nb = in.n_bundles, np = in.piece_off[nb];
-            DBuf d_bases, d_cigar, d_bb;
-            if (int rc = upload_pageable(d_bases, in.bases, (size_t)in.base_off[np], 0, 16)) return rc;
-            if (int rc = upload_pageable(d_cigar, in.cigar, (size_t)in.cig_off[np] * 4, 0, 16)) return rc;
-            if (int rc = upload_pageable(d_bb, in.backbone, (size_t)in.backbone_off[nb], 0, 16)) return rc;
-            hs::ConsensusHost H;
-            H.cons_off.assign(1, 0);
-            if (int rc = consensus_resident(who, in, 0, nb, d_bases.as<uint8_t>(), d_cigar.as<uint32_t>(), d_bb.as<uint8_t>(), prm, nullptr, H, stats, nullptr, &rs, n_passes)) return rc;
-            c = hs::consensus_result_from_host(H);
-            if (!c) { set_error(std::string(who) + ": out of host memory"); return HS_EINVAL; }
-            c->t_rows_ms = stats.t_ms[0]; c->t_columns_ms = stats.t_ms[1]; c->t_ins_ms = stats.t_ms[2]; c->t_emit_ms = stats.t_ms[3]; c->n_rounds = stats.n_sub_rounds;
-        }
+        // (one pass is the planned route's call and reports as it does: its sub-rounds, no bytes and no plan time)
+        if (int rc = consensus_arrays_resident(who, in, prm, nullptr, &c, n_passes > 1 ? &stats : nullptr, n_passes > 1 ? &rs : nullptr, n_passes)) return rc;
+        stats.n_sub_rounds = c->n_rounds;
         refine_first_pass(rs, c, n_passes, (int64_t)g_waits.load() - waits0);
         hs_haplotypes_result* h = refine_wrap_consensus(c, stats);
         if (!h) { set_error(std::string(who) + ": out of host memory"); return HS_EINVAL; }
@@ -369,26 +289,12 @@ int hs_polish_haplotypes_refined(hs_cv_batch* b, int32_t c0, int32_t c1, const i
     *out = nullptr;
     if (!refine_passes_valid(who, n_passes)) return HS_EINVAL;
     const int64_t waits0 = (int64_t)g_waits.load();
-    RefineStats rs;
+    RefineStats rs{};
     hs_haplotypes_result* h = nullptr;
-    if (n_passes == 1) {      // the one-pass call itself
-        if (int rc = hs_polish_haplotypes(b, c0, c1, win_off, win_start, win_end, label_off, labels, contig_has_snps, polish_everything, params, &h)) return rc;
-    } else {
-        if (!b || !win_off || !label_off || c0 < 0 || c1 < c0 || c1 > b->n_contigs) { set_error(std::string(who) + ": bad arguments"); return HS_EINVAL; }
-        const hs_consensus_params prm = params ? *params : hs_consensus_default_params();
-        if (!hs::consensus_params_valid(prm)) { set_error(std::string(who) + ": parameters out of range (min_cov >= 1, max_ins 1..64)"); return HS_EINVAL; }
-        if (int rc = bind_device(b->device)) return rc;
-        try {
-            BytesMoved moved;
-            if (int rc = polish_host_recs(b, &moved)) return rc;
-            std::vector<std::vector<hs::LabelledInterval>> ivs;
-            std::vector<uint8_t> has;
-            if (int rc = hs::polish_intervals_from_labels(b->n_contigs, b->contig_rec_off.data(), b->h_rec_read.data(), win_off, win_start, win_end, label_off, labels,
-                                                          contig_has_snps, ivs, has))
-                return rc;
-            if (int rc = haplotypes_core(who, b, c0, c1, ivs, has, polish_everything != 0, prm, moved, &h, &rs, n_passes)) return rc;
-        } catch (const std::exception& e) { set_error(std::string(who) + ": " + e.what()); return HS_EINVAL; }
-    }
+    // (one pass: the one-pass call itself; more: its body with the passes)
+    if (int rc = n_passes == 1 ? hs_polish_haplotypes(b, c0, c1, win_off, win_start, win_end, label_off, labels, contig_has_snps, polish_everything, params, &h)
+                               : haplotypes_labels(who, b, c0, c1, win_off, win_start, win_end, label_off, labels, contig_has_snps, polish_everything, params, &h, &rs, n_passes))
+        return rc;
     refine_first_pass(rs, h->consensus, n_passes, (int64_t)g_waits.load() - waits0);
     return refined_result_make(who, rs, n_passes, h, out);
 }
@@ -398,7 +304,7 @@ int hs_polish_haplotypes_refined_from_files(const char* gfa, const char* reads, 
     const char* who = "hs_polish_haplotypes_refined_from_files";
     if (!refine_passes_valid(who, n_passes)) return HS_EINVAL;
     if (n_passes == 1) return hs_polish_haplotypes_from_files(gfa, reads, sam, gro, polish_everything, params, out_fasta, n_threads);
-    RefineStats rs;
+    RefineStats rs{};
     return haplotypes_files(who, gfa, reads, sam, gro, polish_everything, params, out_fasta, n_threads, &rs, n_passes);
 }
 

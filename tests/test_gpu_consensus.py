@@ -1,6 +1,6 @@
 """The bundle consensus on the device (hs_kernels_consensus.hip, hs_capi_consensus.inc): the device equals the host half of the rule
 (hs_polish_consensus_host) on every case of tests/consensus_cases.py and every field by integer equality, twice; the wait count; one job in two
-rounds and in one; the over-budget bundle; polish_inputs -> polish_consensus on a resident batch; bin/hs_polish_inputs with HS_CONSENSUS=1;
+rounds and in one; the over-budget bundle; the round cutter at its seams on the host-planned and the resident route; polish_inputs -> polish_consensus on a resident batch; bin/hs_polish_inputs with HS_CONSENSUS=1;
 k_cons_rows on op lengths of 2^16 and more and on a CIGAR of exactly 2^31 - 1 bases (tests/haplotype_cases.py LIMIT_CASES), where its plain int
 scans run just below the bound the plan guards."""
 import os
@@ -125,6 +125,69 @@ def test_two_rounds_equal_one_round_and_the_bundle_above_the_budget_is_refused(b
     _same(one, api.polish_consensus(job, form="host"))
     msg = str(child["refused"])
     assert "bundle 0" in msg and "HS_CONSENSUS_CHUNK_MB" in msg, msg
+
+
+BUDGET = 1 << 20      # HS_CONSENSUS_CHUNK_MB=1
+
+
+def rounds_by_rule(row_bytes, budget=BUDGET):
+    """whole bundles in order; a bundle opens a round where the round before would exceed the budget with it"""
+    n, used = 0, budget + 1
+    for rb in row_bytes:
+        n, used = (n + 1, rb) if used + rb > budget else (n, used + rb)
+    return n
+
+
+def seam_bundle(n_pieces, L, seed):
+    """n_pieces pieces of L columns, all M: n_pieces * L row bytes"""
+    bb = cc.seq(L, seed)
+    return cc.Bundle("%d x %d" % (n_pieces, L), bb, [(1, "%dM" % L, bb)] * n_pieces)
+
+
+SEAM_BUNDLES = {"budget - 1": (1023, 1025), "budget": (1024, 1024), "one": (1, 1), "budget + 1": (17, 61681)}
+SEAM_ORDERS = (("budget - 1", "budget", "one"), ("one", "budget - 1", "budget"), ("budget", "one", "budget - 1"))
+
+SEAM_CHILD = """
+import json
+import sys
+sys.path.insert(0, "tests")
+import consensus_cases as cc
+import test_gpu_consensus as tg
+from hairsplitter_amd import api
+out = {"rounds": [], "refused": []}
+for order in tg.SEAM_ORDERS:
+    job = cc.pack([tg.seam_bundle(*tg.SEAM_BUNDLES[k], seed=i) for i, k in enumerate(order)])
+    dev, planned = api.polish_consensus(job, form="device"), api.polish_consensus(job, form="planned")
+    tg._same(dev, planned, order)
+    assert [len(api.consensus_text(dev, i)) for i in range(3)] == [tg.SEAM_BUNDLES[k][1] for k in order] and int(dev["n_sub"].sum()) == 0
+    out["rounds"].append([dev["stats"]["n_rounds"], planned["stats"]["n_rounds"]])
+big = cc.pack([tg.seam_bundle(*tg.SEAM_BUNDLES["one"], seed=1), tg.seam_bundle(*tg.SEAM_BUNDLES["budget + 1"], seed=2)])
+for form in ("device", "planned"):
+    try:
+        api.polish_consensus(big, form=form)
+        out["refused"].append("")
+    except api.HsError as e:
+        out["refused"].append(str(e))
+json.dump(out, open(sys.argv[1], "w"))
+"""
+
+
+def test_the_round_cutter_at_its_seams_on_both_routes(built, tmp_path):
+    """Row bytes of budget - 1, budget and 1 under HS_CONSENSUS_CHUNK_MB=1, in three orders: the host-planned route and the resident route cut the same
+    rounds, those of the rule restated above (3, 2 and 2: the single byte joins a neighbour only beside budget - 1); one byte above the budget is
+    refused by both, by name. A child, as the variable's other tests."""
+    import json
+    sizes = {k: n * L for k, (n, L) in SEAM_BUNDLES.items()}
+    assert [sizes[k] for k in ("budget - 1", "budget", "one", "budget + 1")] == [BUDGET - 1, BUDGET, 1, BUDGET + 1]
+    want = [rounds_by_rule([sizes[k] for k in order]) for order in SEAM_ORDERS]
+    assert want == [3, 2, 2]
+    dst = str(tmp_path / "child.json")
+    r = subprocess.run([sys.executable, "-c", SEAM_CHILD, dst], cwd=ROOT, env=dict(os.environ, HS_CONSENSUS_CHUNK_MB="1"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    child = json.load(open(dst))
+    assert child["rounds"] == [[n, n] for n in want], child["rounds"]
+    for entry, msg in zip(("hs_polish_consensus", "hs_polish_consensus_planned_tap"), child["refused"]):
+        assert msg.endswith("%s: bundle 1 alone takes %d row bytes, more than HS_CONSENSUS_CHUNK_MB allows" % (entry, BUDGET + 1)), msg
 
 
 def test_polish_inputs_to_consensus_on_a_resident_batch(built):

@@ -7,7 +7,8 @@ call in every field, its waits and its launches; (4) several sub-rounds equal on
 
 (7) the limit cases of tests/haplotype_cases.py -- op lengths of 2^16 and more, a CIGAR of exactly 2^31 - 1 bases, one of 2^31 refused -- through
 one and two passes; (8) pass 2 and 3 over CIGARs the device wrote for noisy pieces, of more than 64 and more than 128 words, against the
-composition; (9) A1 in several chunks equals one, several resident rounds with passes equal one.
+composition; (9) A1 in several chunks equals one, several resident rounds with passes equal one; (10) one refusal and a call without pieces through
+the four doors of the arrays (polish_consensus device and planned, polish_refine with one and two passes).
 
 Limits not reached by a test: a piece above 2^20 bases (no path: the n_unaligned branch of k_refine_pieces) -- A1 sweeps the whole pair for its
 distance before it declines the path, and nobody has measured that sweep; more than 2^31 - 256 pairs or 2^31 - 1 move bytes in an A1 chunk; more than
@@ -181,18 +182,9 @@ def _refined_entry_one_pass(api, batch, sr):
     api._check(lib.hs_polish_haplotypes_refined(batch.handle, 0, batch.flat.n_contigs, ptr(arr["win_off"]), ptr(arr["win_start"]), ptr(arr["win_end"]), ptr(arr["label_off"]),
                                                 ptr(arr["labels"]), ptr(has), 0, None, 1, C.byref(out_p)))
     try:
-        r = out_p.contents
-        h = r.last.contents
-        out = api._polish_result_dict(h.inputs.contents, False)
-        cons = api._consensus_result_dict(h.consensus.contents, out["n_bundles"])
-        stats = dict(out["stats"], **cons.pop("stats"))
-        out.update(cons)
-        stats.update({"n_rounds": int(h.n_rounds), "n_sub_rounds": int(h.n_sub_rounds), "bytes_down": int(h.bytes_down), "bytes_up": int(h.bytes_up)})
-        out["stats"] = stats
-        out["passes"] = api._refined_passes_dict(r)
+        return api._haplotypes_result_dict(out_p.contents.last.contents, out_p.contents)
     finally:
         lib.hs_refined_result_destroy(out_p)
-    return out
 
 
 def test_several_sub_rounds_equal_one(built, monkeypatch):
@@ -377,6 +369,52 @@ def test_refusals(built):
         batch.close()
     with pytest.raises(api.HsError, match="out of range"):
         api.polish_refine(job, api.consensus_params(max_ins=65), passes=2)
+
+
+# ---- 10. the four doors of the arrays: one checked input, one plan step, one cutter behind them ------------------------------------------------
+DOORS = (("hs_polish_consensus", lambda api, job: api.polish_consensus(job, form="device")),
+         ("hs_polish_consensus_planned_tap", lambda api, job: api.polish_consensus(job, form="planned")),
+         ("hs_polish_refine_arrays", lambda api, job: api.polish_refine(job, passes=1)),
+         ("hs_polish_refine_arrays", lambda api, job: api.polish_refine(job, passes=2)))
+
+
+def test_one_refusal_through_every_door(built):
+    """An input hs::consensus_check rejects and a CIGAR of 2^31 bases (tests/haplotype_cases.py refused_cases, the long piece in bundle 2 of 3): behind the
+    entry's own name the same text and status through all four doors -- the texts the calls gave before they shared their check and their plan step.
+    The long CIGAR is refused by the host's plan without a wait and by the device's at its first wait: with two passes too, pass 1's plan, before any A1 launch."""
+    import re
+    from hairsplitter_amd import api
+    good = cc.pack(cc.trim_cases())
+    bad = dict(good, bundle_overhang_right=-np.ones_like(good["bundle_overhang_right"]))
+    _, bundles, named = hc.refused_cases()[2]
+    assert named == 2
+    for job, status, text, waits in ((bad, -2, "bundle 0: a negative overhang", (0, 0, 0, 0)),
+                                     (cc.pack(bundles), -2, "bundle 2: a CIGAR of more than 2^31 - 1 bases", (0, 1, 1, 1))):
+        for (entry, call), n_waits in zip(DOORS, waits):
+            w0 = api.host_waits()
+            with pytest.raises(api.HsError) as e:
+                call(api, job)
+            m = re.fullmatch(r"hairsplitter_hip error (-?\d+): %s: (.*)" % entry, str(e.value))
+            assert m and (int(m.group(1)), m.group(2)) == (status, text), (entry, str(e.value))
+            assert api.host_waits() - w0 == n_waits, (entry, text)
+
+
+def test_no_pieces_through_every_door(built):
+    """No bundle at all, then two bundles with backbones and no piece, base_off and cig_off given as the one-element arrays such a call may pass: every
+    door returns the backbones themselves, every column low where min_cov >= 1 asks for a piece, as the host half does; two passes realign no pair."""
+    from hairsplitter_amd import api
+    bundles = [cc.Bundle("300 columns, no piece", cc.seq(300, 5), [], ovl=3, ovr=4), cc.Bundle("7 columns, no piece", cc.seq(7, 6), [])]
+    for some in ([], bundles):
+        job = dict(cc.pack(some), base_off=np.zeros(1, np.int64), cig_off=np.zeros(1, np.int64))
+        host = api.polish_consensus(job, form="host")
+        assert [api.consensus_text(host, i) for i in range(len(some))] == [b.backbone for b in some]
+        assert host["n_low"].tolist() == [len(b.backbone) for b in some] and not any(host[k].any() for k in ("n_sub", "n_del", "n_ins_bases", "n_skipped"))
+        results = [call(api, job) for _, call in DOORS] + [api.polish_refine_plan_host(job)]
+        for res in results:
+            for k in CONS_KEYS:
+                assert np.array_equal(res[k], host[k]), (len(some), k)
+        assert results[3]["passes"]["n_pairs"].tolist() == [0, 0] and results[3]["passes"]["n_low"].tolist() == [int(host["n_low"].sum())] * 2
+        assert len(results[4]["win_start"]) == 0
 
 
 def test_default_step_costs_what_it_cost_before_a_refined_call(built):
