@@ -40,6 +40,7 @@ SYMBOLS = [
     "hs_map_to_batch", "hs_map_text", "hs_map_files", "hs_map_main",
     "hs_map_split_params_default", "hs_map_reads_split", "hs_map_segments_destroy", "hs_map_split_to_batch", "hs_map_segments_text",
     "hs_map_anchor_params_default", "hs_map_reads_anchored", "hs_map_anchors_destroy", "hs_realign_intervals_anchored", "hs_map_to_batch_anchored",
+    "hs_realign_cut_tap", "hs_anchor_join_tap",
 ]
 
 HS_NKERNELS = 28
@@ -2333,6 +2334,52 @@ def realign_intervals(flat_sequences, intervals, pad: int = 100, want_batch: boo
     intervals: rows (read, contig, strand, qstart, qend, tstart, tend); strand 1 forward, 0 reverse; half-open, 0-based.
     Returns (records dict, CvBatch or None): records grouped by contig, input order inside a contig (rec_interval says which row)."""
     return _realign("realign_intervals", flat_sequences, intervals, None, pad, want_batch)
+
+
+def realign_cut_tap(seq, off, src, rev=None, fill: int = 0xA5, out_cap: Optional[int] = None, m: Optional[int] = None) -> np.ndarray:
+    """hs_realign_cut_tap: k_realign_cut through the job's own launch on the pieces (off [m + 1], src [m], rev [m] or None) of `seq`; returns all out_cap
+    bytes (default: off[m] rounded up to 16, and 64 guard bytes behind), those behind the rounded length still `fill`. A refused table raises HsError."""
+    require_gpu()
+    seq, off, src = _np(seq, np.uint8), _np(off, np.int64), _np(src, np.int64)
+    m = len(src) if m is None else int(m)
+    if len(off) != m + 1 or len(src) < m or (rev is not None and len(rev) != m):
+        raise HsError("realign_cut_tap: off has one entry per piece and one more, src and rev one per piece")
+    rev = None if rev is None else _np(rev, np.uint8)
+    if out_cap is None:
+        out_cap = ((int(off[-1]) + 15) & ~15) + 64 if m >= 1 and 0 <= int(off[-1]) < (1 << 40) else 64
+    out = np.empty(max(int(out_cap), 1), np.uint8)
+    _check(load().hs_realign_cut_tap(_hp(seq, C.c_uint8), C.c_int64(len(seq)), _hp(off, C.c_int64), _hp(src, C.c_int64), _hp(rev, C.c_uint8) if rev is not None else None,
+                                     C.c_int32(m), C.c_int32(fill), _hp(out, C.c_uint8), C.c_int64(out_cap)))
+    return out[:int(out_cap)]
+
+
+JOIN_TABLE = (("iv_piece", np.int32), ("iv_base", np.int32), ("join_off", np.int64), ("pc_kind", np.uint8), ("pc_idx", np.int32), ("pc_room", np.int32), ("pc_ops", np.int64))
+JOIN_NUMBERS = ("dist", "start", "end", "len")
+
+
+def anchor_join_tap(table: Dict, fill: int = 0xA5, joined_cap: Optional[int] = None) -> Dict:
+    """hs_anchor_join_tap: k_anchor_join_plan and k_anchor_join through the job's own launches. table: the piece table of a round (iv_piece, iv_base,
+    join_off, pc_kind, pc_idx, pc_room, pc_ops) and the aligner's side (ops; dist, start, end, len of equal length). Returns pc_at, out_len, out_dist,
+    out_pos and `joined`: all joined_cap bytes (default: join_off[m] rounded up to 16, and 64 guard bytes behind). A refused table raises HsError."""
+    require_gpu()
+    t = {k: _np(table[k], dt) for k, dt in JOIN_TABLE}
+    num = {k: _np(table[k], np.int32) for k in JOIN_NUMBERS}
+    ops = _np(table["ops"], np.uint8)
+    m, P, n_num = len(t["iv_base"]), len(t["pc_kind"]), len(num["dist"])
+    if len(t["iv_piece"]) != m + 1 or len(t["join_off"]) != m + 1 or any(len(t[k]) != P for k in ("pc_idx", "pc_room", "pc_ops")) or any(len(v) != n_num for v in num.values()):
+        raise HsError("anchor_join_tap: iv_piece and join_off have one entry per interval and one more, the pc_ arrays one per piece, the numbers one length")
+    if m >= 1 and int(t["iv_piece"][-1]) > P:
+        raise HsError("anchor_join_tap: iv_piece names %d pieces, the table has %d" % (int(t["iv_piece"][-1]), P))
+    if joined_cap is None:
+        joined_cap = ((int(t["join_off"][-1]) + 15) & ~15) + 64 if 0 <= int(t["join_off"][-1]) < (1 << 40) else 64
+    one = lambda a: a if len(a) else np.zeros(1, a.dtype)      # (an empty array still has an address)
+    outs = dict(pc_at=np.full(max(P, 1), -7, np.int32), out_len=np.full(max(m, 1), -7, np.int32), out_dist=np.full(max(m, 1), -7, np.int32), out_pos=np.full(max(m, 1), -7, np.int32),
+                joined=np.empty(max(int(joined_cap), 1), np.uint8))
+    args = [C.c_int32(m)] + [_hp(one(t[k]), C.c_int64 if dt is np.int64 else (C.c_uint8 if dt is np.uint8 else C.c_int32)) for k, dt in JOIN_TABLE]
+    args += [_hp(one(ops), C.c_uint8), C.c_int64(len(ops))] + [_hp(one(num[k]), C.c_int32) for k in JOIN_NUMBERS] + [C.c_int32(n_num), C.c_int32(fill)]
+    args += [_hp(outs[k], C.c_int32) for k in ("pc_at", "out_len", "out_dist", "out_pos")] + [_hp(outs["joined"], C.c_uint8), C.c_int64(joined_cap)]
+    _check(load().hs_anchor_join_tap(*args))
+    return dict(pc_at=outs["pc_at"][:P], out_len=outs["out_len"][:m], out_dist=outs["out_dist"][:m], out_pos=outs["out_pos"][:m], joined=outs["joined"][:int(joined_cap)])
 
 
 # ---- the read mapper (hs_map_*): minimizer seeds against a resident index of the contigs, a vote over diagonal bins ----

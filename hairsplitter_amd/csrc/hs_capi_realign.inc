@@ -68,6 +68,14 @@ static int realign_cut_launch(const DBuf& d_off, const DBuf& d_src, const uint8_
     return HS_OK;
 }
 
+// the join of a round's pieces: the plan (a lane per interval), then the joined strings (a lane per 16-byte block of J.joined_bytes)
+static int anchor_join_launch(const hsdev::AnchorJoinArgs& J, hipStream_t stream) {
+    hipLaunchKernelGGL(hsdev::k_anchor_join_plan, dim3((unsigned)(J.m / 256 + 1)), dim3(256), 0, stream, J);
+    if (J.joined_bytes > 0) hipLaunchKernelGGL(hsdev::k_anchor_join, dim3((unsigned)((J.joined_bytes + 4095) >> 12)), dim3(256), 0, stream, J);
+    HS_HIP(hipGetLastError());
+    return HS_OK;
+}
+
 // the checks of hs_realign.cpp's parser on every interval; the intervals of every contig, in input order
 static int realign_check_intervals(const int64_t* h_contig_off, int32_t n_contigs, const int64_t* h_read_off, int32_t n_reads, const int32_t* iv_read, const int32_t* iv_contig,
                                    const int32_t* iv_qstart, const int32_t* iv_qend, const int32_t* iv_tstart, const int32_t* iv_tend, size_t n, std::vector<int32_t>& contig_iv_off,
@@ -353,9 +361,7 @@ static int realign_job(const char* who, const uint8_t* h_contig_seq, const int64
                 J.pc_at = d_pc_at.as<int32_t>(); J.out_len = d_len.as<int32_t>(); J.out_dist = d_dist.as<int32_t>(); J.out_pos = d_pos.as<int32_t>();
                 J.joined = d_joined.as<uint8_t>(); J.joined_bytes = joined_bytes;
                 HS_HIP(ev_rec(ev_join.a, stream));
-                hipLaunchKernelGGL(hsdev::k_anchor_join_plan, dim3((unsigned)(m / 256 + 1)), dim3(256), 0, stream, J);
-                if (joined_bytes > 0) hipLaunchKernelGGL(hsdev::k_anchor_join, dim3((unsigned)((joined_bytes + 4095) >> 12)), dim3(256), 0, stream, J);
-                HS_HIP(hipGetLastError());
+                if (int rc = anchor_join_launch(J, stream)) return rc;
                 HS_HIP(ev_rec(ev_join.b, stream));
                 r_ops = d_joined.as<uint8_t>(); r_ops_off = join_off.data(); r_len = d_len.as<int32_t>(); r_dist = d_dist.as<int32_t>();
             }
@@ -421,6 +427,108 @@ int hs_realign_intervals_anchored(const uint8_t* h_contig_seq, const int64_t* h_
                        iv_tend, n_intervals, pad, anc_off, anc_q, anc_t, out, batch);
 }
 
+
+// ---- test taps of the cut and the join (include/hairsplitter_hip.h): the job's own launches on given tables, every table checked before any launch ----
+int hs_realign_cut_tap(const uint8_t* seq, int64_t seq_len, const int64_t* off, const int64_t* src, const uint8_t* rev, int32_t m, int32_t fill, uint8_t* out, int64_t out_cap) {
+    if (int rc = require_device()) return rc;
+    if (!seq || !off || !src || !out || seq_len < 1 || m < 1 || out_cap < 0) { set_error("hs_realign_cut_tap: bad arguments"); return HS_EINVAL; }
+    try {
+        if (off[0] != 0) { set_error("hs_realign_cut_tap: off must ascend strictly from 0 (off[0] is " + std::to_string(off[0]) + ")"); return HS_EINVAL; }
+        for (int32_t i = 0; i < m; ++i) {
+            if (off[i + 1] <= off[i] || off[i + 1] > ((int64_t)1 << 40)) { set_error("hs_realign_cut_tap: off must ascend strictly from 0 (piece " + std::to_string(i) + ")"); return HS_EINVAL; }
+            const int64_t n = off[i + 1] - off[i];
+            const bool r = rev && rev[i];
+            // (src inside the sequence first: the piece's other end is then src -+ (n - 1) without overflow)
+            if (src[i] < 0 || src[i] >= seq_len || (r ? src[i] - (n - 1) < 0 : src[i] + (n - 1) >= seq_len)) {
+                set_error("hs_realign_cut_tap: piece " + std::to_string(i) + " (src " + std::to_string(src[i]) + ", " + std::to_string(n) + " bases, " + (r ? "reversed" : "forward")
+                          + ") leaves the sequence [0, " + std::to_string(seq_len) + ")");
+                return HS_EINVAL;
+            }
+        }
+        const int64_t total = off[m], out_bytes = (total + 15) & ~(int64_t)15;
+        if (out_cap < out_bytes) { set_error("hs_realign_cut_tap: out_cap " + std::to_string(out_cap) + " is below off[m] rounded up to 16 (" + std::to_string(out_bytes) + ")"); return HS_EINVAL; }
+        const hipStream_t stream = nullptr;
+        DBuf d_seq, d_off, d_src, d_rev, d_out;
+        if (int rc = upload_pageable(d_seq, seq, (size_t)seq_len, HS_SEQ_PAD, HS_SEQ_PAD)) return rc;
+        const std::vector<int64_t> v_off(off, off + m + 1), v_src(src, src + m);
+        std::vector<uint8_t> v_rev;
+        if (rev) v_rev.assign(rev, rev + m);
+        UploadPack pk;
+        pk.add(v_off, d_off); pk.add(v_src, d_src);
+        if (rev) pk.add(v_rev, d_rev);
+        if (int rc = pk.commit(stream)) return rc;
+        if (int rc = d_out.alloc((size_t)out_cap)) return rc;
+        if (out_cap) HS_HIP(hipMemsetAsync(d_out.p, fill & 0xff, (size_t)out_cap, stream));
+        if (int rc = realign_cut_launch(d_off, d_src, rev ? d_rev.as<uint8_t>() : nullptr, m, total, d_seq.as<uint8_t>() + HS_SEQ_PAD, d_out.as<uint8_t>(), stream)) return rc;
+        return d2h_pinned(out, d_out.p, (size_t)out_cap, stream);
+    } catch (const std::exception& e) { set_error(std::string("hs_realign_cut_tap: ") + e.what()); return HS_EINVAL; }
+}
+
+int hs_anchor_join_tap(int32_t m, const int32_t* iv_piece, const int32_t* iv_base, const int64_t* join_off, const uint8_t* pc_kind, const int32_t* pc_idx, const int32_t* pc_room,
+                       const int64_t* pc_ops, const uint8_t* ops, int64_t ops_bytes, const int32_t* dist, const int32_t* start, const int32_t* end, const int32_t* len, int32_t n_num,
+                       int32_t fill, int32_t* pc_at, int32_t* out_len, int32_t* out_dist, int32_t* out_pos, uint8_t* joined, int64_t joined_cap) {
+    if (int rc = require_device()) return rc;
+    if (m < 1 || !iv_piece || !iv_base || !join_off || !pc_kind || !pc_idx || !pc_room || !pc_ops || !ops || ops_bytes < 0 || !dist || !start || !end || !len || n_num < 0 || !pc_at
+        || !out_len || !out_dist || !out_pos || !joined || joined_cap < 0) { set_error("hs_anchor_join_tap: bad arguments"); return HS_EINVAL; }
+    try {
+        const std::string who = "hs_anchor_join_tap: ";
+        if (iv_piece[0] != 0 || join_off[0] != 0) { set_error(who + "iv_piece and join_off must ascend from 0"); return HS_EINVAL; }
+        for (int32_t k = 0; k < m; ++k) {
+            if (iv_piece[k + 1] <= iv_piece[k]) { set_error(who + "interval " + std::to_string(k) + " has no pieces (iv_piece must ascend strictly)"); return HS_EINVAL; }
+            if (join_off[k + 1] < join_off[k] || join_off[k + 1] > ((int64_t)1 << 40)) { set_error(who + "join_off must ascend from 0 (interval " + std::to_string(k) + ")"); return HS_EINVAL; }
+        }
+        for (int32_t k = 0; k < m; ++k) {
+            int64_t rooms = 0;
+            for (int32_t p = iv_piece[k]; p < iv_piece[k + 1]; ++p) {
+                if (pc_kind[p] > hsdev::ANCHOR_INS) { set_error(who + "piece " + std::to_string(p) + " is of kind " + std::to_string(pc_kind[p]) + " (0 .. 4)"); return HS_EINVAL; }
+                if (pc_room[p] < 0) { set_error(who + "piece " + std::to_string(p) + " has a negative room"); return HS_EINVAL; }
+                if (pc_kind[p] != hsdev::ANCHOR_INS) {
+                    if (pc_idx[p] < 0 || pc_idx[p] >= n_num) { set_error(who + "piece " + std::to_string(p) + " names the numbers at " + std::to_string(pc_idx[p]) + " of " + std::to_string(n_num)); return HS_EINVAL; }
+                    if (pc_ops[p] < 0 || pc_ops[p] > ops_bytes - pc_room[p]) {
+                        set_error(who + "piece " + std::to_string(p) + " has its moves at " + std::to_string(pc_ops[p]) + " + " + std::to_string(pc_room[p]) + " of " + std::to_string(ops_bytes) + " bytes");
+                        return HS_EINVAL;
+                    }
+                }
+                rooms += pc_room[p];
+            }
+            const int64_t room = join_off[k + 1] - join_off[k];
+            if (room < rooms || room > 0x7fffffff) {
+                set_error(who + "interval " + std::to_string(k) + " has room for " + std::to_string(room) + " moves, its pieces for " + std::to_string(rooms) + " (at least their sum, at most 2^31 - 1)");
+                return HS_EINVAL;
+            }
+        }
+        const int64_t joined_bytes = (join_off[m] + 15) & ~(int64_t)15;
+        if (joined_cap < joined_bytes) { set_error(who + "joined_cap " + std::to_string(joined_cap) + " is below join_off[m] rounded up to 16 (" + std::to_string(joined_bytes) + ")"); return HS_EINVAL; }
+        const size_t P = (size_t)iv_piece[m], M = (size_t)m;
+        const hipStream_t stream = nullptr;
+        const std::vector<int32_t> v_iv_piece(iv_piece, iv_piece + M + 1), v_iv_base(iv_base, iv_base + M), v_pc_idx(pc_idx, pc_idx + P), v_pc_room(pc_room, pc_room + P);
+        const std::vector<int32_t> v_dist(dist, dist + n_num), v_start(start, start + n_num), v_end(end, end + n_num), v_len(len, len + n_num);
+        const std::vector<int64_t> v_join_off(join_off, join_off + M + 1), v_pc_ops(pc_ops, pc_ops + P);
+        const std::vector<uint8_t> v_pc_kind(pc_kind, pc_kind + P);
+        DBuf d_iv_piece, d_iv_base, d_join_off, d_pc_kind, d_pc_idx, d_pc_room, d_pc_ops, d_ops, dd, ds, de, dlen, d_pc_at, d_len, d_dist, d_pos, d_joined;
+        UploadPack pk;
+        pk.add(v_iv_piece, d_iv_piece); pk.add(v_iv_base, d_iv_base); pk.add(v_join_off, d_join_off); pk.add(v_pc_kind, d_pc_kind); pk.add(v_pc_idx, d_pc_idx); pk.add(v_pc_room, d_pc_room);
+        pk.add(v_pc_ops, d_pc_ops); pk.add(v_dist, dd); pk.add(v_start, ds); pk.add(v_end, de); pk.add(v_len, dlen);
+        if (int rc = pk.commit(stream)) return rc;
+        if (int rc = upload_pageable(d_ops, ops, (size_t)ops_bytes, 0, 16)) return rc;      // (as the job's moves: 16 bytes of room behind them)
+        if (int rc = d_pc_at.alloc(P * sizeof(int32_t))) return rc;
+        for (DBuf* b : {&d_len, &d_dist, &d_pos}) if (int rc = b->alloc(M * sizeof(int32_t))) return rc;
+        if (int rc = d_joined.alloc((size_t)joined_cap)) return rc;
+        if (joined_cap) HS_HIP(hipMemsetAsync(d_joined.p, fill & 0xff, (size_t)joined_cap, stream));
+        hsdev::AnchorJoinArgs J{};
+        J.m = m; J.iv_piece = d_iv_piece.as<int32_t>(); J.iv_base = d_iv_base.as<int32_t>(); J.join_off = d_join_off.as<int64_t>();
+        J.pc_kind = d_pc_kind.as<uint8_t>(); J.pc_idx = d_pc_idx.as<int32_t>(); J.pc_room = d_pc_room.as<int32_t>(); J.pc_ops = d_pc_ops.as<int64_t>();
+        J.ops = d_ops.as<uint8_t>(); J.dist = dd.as<int32_t>(); J.start = ds.as<int32_t>(); J.end = de.as<int32_t>(); J.len = dlen.as<int32_t>();
+        J.pc_at = d_pc_at.as<int32_t>(); J.out_len = d_len.as<int32_t>(); J.out_dist = d_dist.as<int32_t>(); J.out_pos = d_pos.as<int32_t>();
+        J.joined = d_joined.as<uint8_t>(); J.joined_bytes = joined_bytes;
+        if (int rc = anchor_join_launch(J, stream)) return rc;
+        if (int rc = d2h_pinned(pc_at, d_pc_at.p, P * sizeof(int32_t), stream)) return rc;
+        if (int rc = d2h_pinned(out_len, d_len.p, M * sizeof(int32_t), stream)) return rc;
+        if (int rc = d2h_pinned(out_dist, d_dist.p, M * sizeof(int32_t), stream)) return rc;
+        if (int rc = d2h_pinned(out_pos, d_pos.p, M * sizeof(int32_t), stream)) return rc;
+        return d2h_pinned(joined, d_joined.p, (size_t)joined_cap, stream);
+    } catch (const std::exception& e) { set_error(std::string("hs_anchor_join_tap: ") + e.what()); return HS_EINVAL; }
+}
 
 int hs_cv_batch_create_paf(const char* gfa, const char* reads, const char* paf, int32_t n_threads, hs_cv_batch** batch, hs_realign_records** recs) {
     if (int rc = require_device()) return rc;

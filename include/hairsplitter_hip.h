@@ -1194,6 +1194,29 @@ int hs_map_to_batch_anchored(const hs_map_index* index, const uint8_t* h_contig_
                              const int64_t* h_read_off, int32_t n_reads, int32_t pad, const hs_map_anchor_params* params, hs_cv_batch** batch,
                              hs_realign_records** records, hs_map_result** result, hs_map_anchors** anchors);
 
+/* Test taps of the two device steps around A1 on the CIGAR-less route (hs_kernels_realign.hip), each through the launch the job itself makes; host
+ * arrays in, host arrays out, nothing on the product path. Both check their tables on the host before any launch and refuse with HS_EINVAL and a
+ * message: no table they accept can make a kernel read or write outside its buffers.
+ *
+ * hs_realign_cut_tap -- k_realign_cut. `seq` goes up as the job's sequences do (HS_SEQ_PAD zero bytes on either side); piece i of the output is
+ * out[off[i], off[i + 1]): seq[src[i]], seq[src[i] + 1], ... or, where rev[i] is set, 3 - seq[src[i]], 3 - seq[src[i] - 1], ... as a byte. The
+ * out_cap device bytes are set to the byte `fill` before the launch and all come back, so the bytes behind off[m] rounded up to 16 are guards.
+ * Refused: m < 1, off that does not ascend strictly from 0, a piece that leaves [0, seq_len) at either end, out_cap below off[m] rounded up to 16. */
+int hs_realign_cut_tap(const uint8_t* seq, int64_t seq_len, const int64_t* off /* [m + 1] */, const int64_t* src /* [m] */, const uint8_t* rev /* [m], may be NULL */,
+                       int32_t m, int32_t fill, uint8_t* out, int64_t out_cap);
+/* hs_anchor_join_tap -- k_anchor_join_plan and k_anchor_join on a piece table as hs_realign_intervals_anchored builds it per round: interval k has the
+ * pieces [iv_piece[k], iv_piece[k + 1]) and the room [join_off[k], join_off[k + 1]) in the joined buffer; piece p is of kind pc_kind[p] (0 HW, 1 HEAD,
+ * 2 MID, 3 TAIL, 4 INS), has room for pc_room[p] moves at ops + pc_ops[p] and its numbers at index pc_idx[p] of dist / start / end / len (INS: pc_idx is
+ * the run's length, pc_ops is not used). The aligner's side is given: ops [ops_bytes] and the n_num numbers. joined_cap device bytes are set to `fill`
+ * before the launches and all come back; pc_at [iv_piece[m]], out_len / out_dist / out_pos [m] as the plan leaves them.
+ * Refused: m < 1; iv_piece that does not ascend strictly from 0; join_off that does not ascend from 0; a kind above 4; a pc_idx outside [0, n_num) (INS
+ * excepted); a negative pc_room, or pc_ops + pc_room outside [0, ops_bytes] (INS excepted); an interval whose room is below the sum of its pieces' rooms
+ * or above 2^31 - 1; joined_cap below join_off[m] rounded up to 16. */
+int hs_anchor_join_tap(int32_t m, const int32_t* iv_piece /* [m + 1] */, const int32_t* iv_base /* [m] */, const int64_t* join_off /* [m + 1] */,
+                       const uint8_t* pc_kind, const int32_t* pc_idx, const int32_t* pc_room, const int64_t* pc_ops /* [iv_piece[m]] each */,
+                       const uint8_t* ops, int64_t ops_bytes, const int32_t* dist, const int32_t* start, const int32_t* end, const int32_t* len, int32_t n_num,
+                       int32_t fill, int32_t* pc_at, int32_t* out_len, int32_t* out_dist, int32_t* out_pos, uint8_t* joined, int64_t joined_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -238,6 +238,35 @@ def words_of(moves, clip_l, clip_r):
     return np.array(w + ([(clip_r << 4) | 4] if clip_r > 0 else []), np.uint32)
 
 
+def expected_records(api, job, pad):
+    """job: C, reads, ivs, ancs (per interval its anchors as (q, t)). Every interval's record from its pieces aligned alone (three calls of api.edlib_align, the entry the committed edlib vectors pin) and stitched in numpy"""
+    C, pcs_of, pairs, where = job["C"], [], {"HW": [], "SHW": [], "NW": []}, []
+    for iv, a in zip(job["ivs"], job["ancs"]):
+        read = job["reads"][iv[0]]
+        R = read_as_aligned(read, int(iv[2]))
+        pcs, rng, win = pieces_of(iv, len(read), len(C), [q for q, _ in a], [t for _, t in a], pad)
+        pcs_of.append((pcs, rng, win))
+        for kind, x0, x1, t0, t1 in pcs:
+            mode = {"HW": "HW", "HEAD": "SHW", "TAIL": "SHW", "MID": "NW", "INS": None}[kind]
+            if mode is None:
+                where.append(None)
+                continue
+            pair = (R[x0:x1][::-1].copy(), C[t0:t1][::-1].copy()) if kind == "HEAD" else (R[x0:x1], C[t0:t1])
+            where.append((mode, len(pairs[mode])))
+            pairs[mode].append(pair)
+    res = {m: api.edlib_align(v, mode=m, task="path") if v else [] for m, v in pairs.items()}
+    out, at = [], 0
+    for (pcs, (a0, a1), win), iv in zip(pcs_of, job["ivs"]):
+        aligned = []
+        for _ in pcs:
+            w = where[at]; at += 1
+            aligned.append(None if w is None else (lambda r: (r["distance"], r["start"], r["end"], r["ops"]))(res[w[0]][w[1]]))
+        pos, nm, moves = stitch(pcs, aligned)
+        Lr = len(job["reads"][iv[0]])
+        out.append(dict(pos=pos, nm=nm, words=words_of(moves, a0, Lr - a1), window=win, n_pieces=sum(p[0] != "INS" for p in pcs)))
+    return out
+
+
 def walk_cigar(words, pos, read, contig, strand, window):
     """a record's CIGAR over the two sequences: (read bases consumed clips included, NM, stays inside the window?)"""
     R = read_as_aligned(read, strand)

@@ -171,32 +171,7 @@ def job():
 
 
 def _expected(api, job):
-    """every interval's record from its pieces aligned alone (three calls of api.edlib_align, the entry the committed edlib vectors pin) and stitched in numpy"""
-    C, pcs_of, pairs, where = job["C"], [], {"HW": [], "SHW": [], "NW": []}, []
-    for iv, a in zip(job["ivs"], job["ancs"]):
-        read = job["reads"][iv[0]]
-        R = ac.read_as_aligned(read, int(iv[2]))
-        pcs, rng, win = ac.pieces_of(iv, len(read), len(C), [q for q, _ in a], [t for _, t in a], PAD)
-        pcs_of.append((pcs, rng, win))
-        for kind, x0, x1, t0, t1 in pcs:
-            mode = {"HW": "HW", "HEAD": "SHW", "TAIL": "SHW", "MID": "NW", "INS": None}[kind]
-            if mode is None:
-                where.append(None)
-                continue
-            pair = (R[x0:x1][::-1].copy(), C[t0:t1][::-1].copy()) if kind == "HEAD" else (R[x0:x1], C[t0:t1])
-            where.append((mode, len(pairs[mode])))
-            pairs[mode].append(pair)
-    res = {m: api.edlib_align(v, mode=m, task="path") if v else [] for m, v in pairs.items()}
-    out, at = [], 0
-    for (pcs, (a0, a1), win), iv in zip(pcs_of, job["ivs"]):
-        aligned = []
-        for _ in pcs:
-            w = where[at]; at += 1
-            aligned.append(None if w is None else (lambda r: (r["distance"], r["start"], r["end"], r["ops"]))(res[w[0]][w[1]]))
-        pos, nm, moves = ac.stitch(pcs, aligned)
-        Lr = len(job["reads"][iv[0]])
-        out.append(dict(pos=pos, nm=nm, words=ac.words_of(moves, a0, Lr - a1), window=win, n_pieces=sum(p[0] != "INS" for p in pcs)))
-    return out
+    return ac.expected_records(api, job, PAD)
 
 
 def _records(rec):
